@@ -2,12 +2,28 @@
 """bench.py -- decode tokens/s of the MI355X hot path on BASELINE.json's workloads.
 
     python bench.py --gpus N --steps K --warmup W [--batch B | --total-seqs T] [--model qwen3-0.6b|qwen3-4b|nano-168m] [--quant q80|q4k|f32]
+                    [--dump-outputs DIR] [--full]
 
 Default workload (BASELINE.json configs[2]): Qwen3-0.6B shape, Q80 gs=64, random-init synthetic
 weights written in the reference's .bin format, max_seq_len 512, greedy decode, ONE sequence per GPU (what the reference
 engine does).  A "step" is one decode step of the hot path for the sequences resident on a GPU.  After an untimed
 16-token prompt and W warm-up decode steps exactly K decode steps are timed between barrier + device synchronisation on
-both sides; the MAX over ranks is the job's time.
+both sides; the MAX over ranks is the job's time, `ms_per_step` = that time / K.
+
+Setup also runs the timed positions once, untimed: a HIP graph per 64-position bucket is captured at its first use, and
+that capture belongs to setup, not to the timed steps.  When W + K decode steps do not fit in the 512-token context
+after the prompt, the warm-up and the timed steps run as consecutive windows that each restart from the same start
+state (same token, same positions): still exactly W warm-up and K timed steps.
+
+  --dump-outputs DIR  after the timed steps, what they computed goes to DIR as .npy files (64 MB at most):
+                  ids.npy     float64 [steps, sequences]: the greedy ids the timed call returned (its last window's when
+                              the timed steps ran as several windows), every rank's sequences;
+                  logits.npy  float32 [sequences of rank 0, vocab]: the logits of the last timed step, read back from the
+                              device after the timing.
+                  Same arguments, same inputs: the model file, the prompts and the positions are seeded and fixed.
+  --full          also everything beyond the headline (off by default; a plain run does only what the headline needs):
+                  repeated windows and their median, the window to the end of the context, the measured read bandwidth,
+                  the classifier's own timing, the rocprofv3 counter pass and kernel table, the CPU baseline.
 
   --gpus N        N > 1 without a torchrun environment: bench.py starts its own N ranks (python -m torch.distributed.run,
                   rendezvous on 127.0.0.1) and the JSON line reports the RCCL world size the ranks saw.
@@ -24,13 +40,14 @@ both sides; the MAX over ranks is the job's time.
   --replicas N    the one-process alternative of SURVEY 8e: N weight replicas inside ONE process, driven through the C engine
                   (nano_context_replicate + nano_forward_batch, no torch in the process); see replicas_main().
 
-The timed region is exactly K decode steps between device synchronisations.  When K steps last less than ~0.25 s (the
-driver's `--steps 20` is 12 ms of GPU time) the SAME K-step window -- same start token, same positions -- is repeated and
-the MEDIAN window is reported (`windows`, `window_ms` on the line), so that the headline does not hang on one 12 ms sample.
+The timed region is exactly K decode steps between device synchronisations.  With --full, when K steps last less than
+~0.25 s (the driver's `--steps 20` is 12 ms of GPU time) the SAME K-step window -- same start token, same positions -- is
+repeated and the MEDIAN window is reported beside the headline (`windows`, `window_ms`, `value_median_window`).
 
 Extra objects on the JSON line:
   roofline      HEADLINE = the whole decode step: algorithmic bytes per step (every weight byte once + the KV rows read
-                at the mid-run position) / the measured ms per step, against the 8 TB/s HBM peak.  `traffic` =
+                at the mid-run position) / the measured ms per step, against the 8 TB/s HBM peak.  With --full:
+                `peak_measured` = a streaming read of this GPU, and `traffic` =
                 HBM bytes per step from this line's own counter pass (a child run of eager steps under `rocprofv3 --pmc
                 FETCH_SIZE --kernel-trace`, x 1024 x 2 on gfx950 as MI355X_MICROARCH.md prescribes), or from --pmc-csv.
                 `kernels` = the same pass's kernel trace: per kernel name the launches per step, each launch's own
@@ -38,9 +55,9 @@ Extra objects on the JSON line:
                 in-graph ones, so every rate is a lower bound.  `dominant_kernel` = the per-layer launches as one
                 family (projections, attention, quantizers): their algorithmic bytes / the sum of their durations;
                 `best_kernel` = the classifier launch with its own start / stop HIP events inside whole steps.
-  cpu_baseline  the reference engine itself (oracle/_ref, built from the reference's sources with its Makefile flags)
-                or, where that is absent, the plain-C port (oracle/), timed on this box's host cores on a bounded sample
-                of the same workload (rank 0, N = 1 only).
+  cpu_baseline  (--full) the reference engine itself (oracle/_ref, built from the reference's sources with its Makefile
+                flags) or, where that is absent, the plain-C port (oracle/), timed on this box's host cores on a bounded
+                sample of the same workload (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -60,8 +77,36 @@ PROMPT_LEN = 16
 SEQ_LEN = 512
 
 
+DUMP_BUDGET = 64 << 20          # --dump-outputs: bytes of all arrays together
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def step_plan(W, K):
+    """Where W warm-up and K timed decode steps go in the context after the prompt: (w_lin, span).  The first w_lin warm-up
+    steps continue the prompt; the timed steps start after them and run in windows of at most `span` steps, each from that
+    same start state; the other W - w_lin warm-up steps run the same way before the timing.  W + K steps that fit in
+    the context: w_lin = W and one window of K steps."""
+    room = SEQ_LEN - PROMPT_LEN
+    w_lin = min(W, room - min(K, room))
+    return w_lin, room - w_lin
+
+
+def dump_outputs(d, arrays):
+    """np.save every array as d/<name>.npy; an array beyond what is left of DUMP_BUDGET becomes a fixed, seeded sample of
+    its flattened elements (in index order)."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > left - 4096:
+            n = max(0, (left - 4096) // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(39).choice(a.size, n, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes + 128
+    log(f"[bench] outputs of the timed steps written to {d}: {', '.join(arrays)}")
 
 
 def model_path(name, quant, gs):
@@ -333,7 +378,8 @@ def cpu_only(args):
 def all_configs(args):
     """One JSON line per BASELINE.json config that runs here, each from a child run of this file; the default line last."""
     import subprocess
-    common = ["--gpus", str(args.gpus), "--warmup", str(args.warmup)] + (["--steps", str(args.steps)] if args.steps is not None else [])
+    common = ["--gpus", str(args.gpus), "--warmup", str(args.warmup)] + (["--steps", str(args.steps)] if args.steps is not None else []) + \
+             (["--full"] if args.full else [])
     runs = [("configs[1] Nano-168M FP32, seq_len 512, greedy decode", ["--model", "nano-168m", "--quant", "f32", "--no-cpu-baseline", "--no-kernel-table"]),
             ("configs[3] Qwen3-0.6B Q4K", ["--quant", "q4k", "--no-cpu-baseline", "--no-kernel-table"]),
             ("configs[4] Qwen3-4B Q80, 64 independent prompts over the visible GPUs", ["--model", "qwen3-4b", "--total-seqs", "64", "--no-cpu-baseline", "--no-kernel-table"]),
@@ -367,7 +413,7 @@ def replicas_main(args):
     per = (T + N - 1) // N
     W = args.warmup
     K = args.steps if args.steps is not None else 128
-    K = min(K, SEQ_LEN - PROMPT_LEN - W)
+    w_lin, span = step_plan(W, K)
     gs = args.gs if args.quant == "q80" else 0
     path, spec = ensure_model(args.model, args.quant, gs)
     ndev = nb.device_count()
@@ -396,16 +442,27 @@ def replicas_main(args):
         step([int(pr[pos]) for pr in prompts], pos)
     tok = np.asarray([int(pr[-1]) for pr in prompts], np.uint32)
     pos = PROMPT_LEN - 1
-    for _ in range(W):
+    for _ in range(w_lin):
         tok = step(tok, pos); pos += 1
+    tok0, pos0 = tok, pos
+
+    def run(n):                  # n steps in windows of at most `span`, each from (tok0, pos0); the last step's ids
+        t, p = tok0, pos0
+        for i in range(n):
+            if i % span == 0:
+                t, p = tok0, pos0
+            t = step(t, p); p += 1
+        return t
+    run(W - w_lin)
     t0 = time.perf_counter()
-    for _ in range(K):
-        tok = step(tok, pos); pos += 1
+    tok = run(K)
     elapsed = time.perf_counter() - t0
     step_bytes = spec.algorithmic_bytes_per_token()
     e.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": np.asarray(tok, np.float64).reshape(1, T)})
     ms = elapsed / K * 1e3
-    kv_mid = 8 * spec.n_layer * spec.kv_dim * (pos - K // 2)
+    kv_mid = 8 * spec.n_layer * spec.kv_dim * (pos0 + min(K, span) - min(K, span) // 2)
     achieved = (N * step_bytes + T * kv_mid) / (ms * 1e-3) / 1e9          # every replica streams its weights once per step
     print(json.dumps({
         "metric": "decode_tokens_per_sec", "value": round(T * K / elapsed, 2), "unit": "tokens/s", "n_gpus": min(N, ndev), "steps": K, "warmup": W,
@@ -441,6 +498,9 @@ def main():
     ap.add_argument("--cpu-only", action="store_true", help="no GPU: the reference CPU engine on --model / --quant (BASELINE configs[0]: --model nano-56m --quant f32)")
     ap.add_argument("--cpu-cores", type=int, default=1, help="OMP_NUM_THREADS of --cpu-only")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) nothing but --steps eager decode steps: what measure_traffic() profiles")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed (their ids, the last step's logits) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline (repeated windows, full-context "
+                    "window, read bandwidth, classifier timing, counter pass, CPU baseline)")
     args = ap.parse_args()
     if args.pmc_child:
         from nano_amd import binding as nb
@@ -471,9 +531,13 @@ def main():
     strong = args.total_seqs > 0
     W = args.warmup
     K = args.steps if args.steps is not None else (128 if strong else 480)
-    if PROMPT_LEN + W + K > SEQ_LEN:
-        K = SEQ_LEN - PROMPT_LEN - W
-        log(f"[bench] steps clamped to {K} (prompt {PROMPT_LEN} + warmup {W} + steps <= seq_len {SEQ_LEN})")
+    if K < 1 or W < 0:
+        log(f"[bench] --steps {K} --warmup {W}: need steps >= 1, warmup >= 0")
+        sys.exit(2)
+    w_lin, span = step_plan(W, K)
+    if w_lin < W or K > span:
+        log(f"[bench] prompt {PROMPT_LEN} + warmup {W} + steps {K} > seq_len {SEQ_LEN}: the timed steps run as windows of at most {span} "
+            f"steps from position {PROMPT_LEN - 1 + w_lin}, {W - w_lin} warm-up steps the same way")
     gs = args.gs if args.quant == "q80" else 0
 
     dist, world_seen = None, 1
@@ -527,10 +591,20 @@ def main():
         m.prefill(pr[:-1], 0, b)
     tok = [int(pr[-1]) for pr in prompts]
     pos0 = PROMPT_LEN - 1
-    warm = m.decode_greedy(tok, [pos0] * B, W) if W > 0 else np.zeros((0, B), np.uint32)
+    warm = m.decode_greedy(tok, [pos0] * B, w_lin) if w_lin > 0 else np.zeros((0, B), np.uint32)
+    tok = [int(t) for t in warm[-1]] if w_lin > 0 else tok
+    pos0 += w_lin
+
+    def run(n):
+        """n decode steps in windows of at most `span` steps, each from the start state (tok, pos0); the last window's ids."""
+        ids = None
+        while n > 0:
+            ids = m.decode_greedy(tok, [pos0] * B, min(n, span))     # graph replays; tokens / positions stay on the device, the ids come back at the end
+            n -= min(n, span)
+        return ids
+    run(min(K, span))                                     # setup: the timed positions once, so that their HIP graphs are captured before the timing
+    run(W - w_lin)                                        # the rest of the warm-up (only when warm-up + steps overflow the context)
     log(f"[bench] rank {rank}: prefill + warm-up done")
-    tok = [int(t) for t in warm[-1]] if W > 0 else tok
-    pos0 += W
 
     def barrier():
         if dist is not None:
@@ -540,22 +614,25 @@ def main():
                 torch.cuda.synchronize()
         m.sync()
 
-    # ---- the timed region: exactly K decode steps between barrier + device synchronisation on both sides.  Short windows
-    #      (the driver's --steps 20 = 12 ms) are repeated from the same start state and the median window is reported.
+    # ---- the timed region: exactly K decode steps between barrier + device synchronisation on both sides.  With --full short windows
+    #      (the driver's --steps 20 = 12 ms) are repeated from the same start state and the median window is reported beside it.
     def window():
         barrier()
         t0 = time.perf_counter()
-        ids = m.decode_greedy(tok, [pos0] * B, K)         # K graph replays; tokens / positions stay on the device, the ids come back at the end
+        ids = run(K)
         m.sync()
         barrier()
         return time.perf_counter() - t0, ids
 
     first, timed_ids = window()
+    outputs = None
+    if args.dump_outputs and rank == 0:                   # the last timed step's logits, before anything else runs on the model
+        outputs = {"logits": np.stack([m.read_state("logits", spec.vocab_size, slot=b) for b in range(B)])}
     wins = [first]
     n_win = 1
-    if first < args.min_window_s:
+    if args.full and first < args.min_window_s:
         n_win = int(min(max(3, args.min_window_s / max(first, 1e-6)), 400)) | 1      # odd: the median is a measured window
-    if dist is not None:                                    # every rank must run the same number of windows
+    if args.full and dist is not None:                      # every rank must run the same number of windows
         import torch
         t = torch.tensor([n_win], dtype=torch.int64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -569,11 +646,11 @@ def main():
         t = torch.tensor(wins, dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wins = [float(v) for v in t.cpu().numpy()]
-    elapsed = float(np.median(wins))
+    elapsed = wins[0]
     # the seq_len-512 number next to a short driver window: one more window from the same start state to the LAST position of the context
     full_win = None
     K_full = SEQ_LEN - pos0
-    if not strong and K_full > K and os.environ.get("NANO_BENCH_NO_FULL_WINDOW") != "1":
+    if args.full and not strong and K_full > K and os.environ.get("NANO_BENCH_NO_FULL_WINDOW") != "1":
         barrier()
         t0 = time.perf_counter()
         m.decode_greedy(tok, [pos0] * B, K_full)
@@ -587,15 +664,16 @@ def main():
             e_full = float(t.item())
         full_win = {"value": round(n_seq * K_full / e_full, 2), "unit": "tokens/s", "steps": K_full, "ms_per_step": round(e_full / K_full * 1e3, 4),
                     "positions": f"{pos0}..{pos0 + K_full - 1}", "what": "one contiguous window from the same start state to the last position of the 512-token context"}
-    log(f"[bench] rank {rank}: timed region done, {elapsed * 1e3 / K:.3f} ms/step (median of {len(wins)} windows of {K} steps, "
-        f"min {min(wins) * 1e3 / K:.3f} max {max(wins) * 1e3 / K:.3f})")
+    log(f"[bench] rank {rank}: timed region done, {elapsed * 1e3 / K:.3f} ms/step over {K} steps" +
+        (f" (repeats: median {float(np.median(wins)) * 1e3 / K:.3f} of {len(wins)} windows, min {min(wins) * 1e3 / K:.3f} max {max(wins) * 1e3 / K:.3f})" if len(wins) > 1 else ""))
 
     # ---- roofline: whole step + per launch kind (rank 0), classifier launch with its own events ----------------
-    pos_mid = min(pos0 + K // 2, SEQ_LEN - 1)
+    K_win = min(K, span)                                   # steps of one window of the timed region
+    pos_mid = min(pos0 + K_win // 2, SEQ_LEN - 1)
     table = None
     cls = None
     peak_measured = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:                                               # the fraction also against a MEASURED device read bandwidth
             peak_measured = round(float(nb.membw(local, 2 << 30, 6)), 1)       # cold streaming read of 2 GiB (> the 256 MB of L2 + MALL)
         except Exception as e:
@@ -610,14 +688,16 @@ def main():
     step_bytes = m.weight_bytes_per_step
     m.close()
 
-    all_ids = np.asarray(timed_ids.T, np.int64)            # [sequences of this rank, K]
+    all_ids = np.asarray(timed_ids.T, np.int64)            # [sequences of this rank, steps of the last window]
     if dist is not None:                                   # the end-of-job all-gather of the TIMED ids
         all_ids = nd.gather_ids(all_ids, owned, n_seq)
-        assert all_ids.shape == (n_seq, K) and (all_ids >= 0).all()
+        assert all_ids.shape == (n_seq, timed_ids.shape[0]) and (all_ids >= 0).all()
     ids_crc = zlib.crc32(np.ascontiguousarray(all_ids, np.int64).tobytes()) & 0xffffffff      # the same number whatever the sharding
 
     if rank != 0:
         return
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, {"ids": np.asarray(all_ids.T, np.float64), **outputs})
     tokens = n_seq * K
     ms_per_step = elapsed / K * 1e3
     kv_mid = 8 * spec.n_layer * spec.kv_dim * (pos_mid + 1)
@@ -626,7 +706,7 @@ def main():
     traffic = None
     if args.pmc_csv:
         traffic = parse_pmc_csv(args.pmc_csv)
-    elif n_gpus == 1 and not use_dist:
+    elif args.full and n_gpus == 1 and not use_dist:
         traffic = measure_traffic(args)
     # roofline.kernels / dominant_kernel: from the kernel trace of the counter pass -- per kernel NAME the launches per step, the mean
     # duration of a launch by its own start / end timestamps and its measured FETCH bytes.  (Rounds 2-5 derived this table from graph
@@ -679,22 +759,27 @@ def main():
     out = {
         "metric": "decode_tokens_per_sec", "value": round(tokens / elapsed, 2), "unit": "tokens/s",
         "n_gpus": n_gpus, "steps": K, "warmup": W, "ms_per_step": round(ms_per_step, 4),
-        "windows": len(wins), "window_ms": {"min": round(min(wins) * 1e3, 4), "median": round(elapsed * 1e3, 4), "max": round(max(wins) * 1e3, 4), "first": round(first * 1e3, 4)},
-        "value_first_window": round(tokens / first, 2),
-        "value_how": "median of `windows` repeats of the same K-step window (same start token and positions: later repeats re-touch the same KV rows; the first window also pays "
-                     "the first use of the position buckets' HIP graphs -- value_first_window); value_full_window = one contiguous run to the end of the context",
-        "value_full_window": full_win,
+        "value_how": "n_seq x K tokens / the time of the K timed decode steps (one timed region between device synchronisations, after setup has "
+                     "run the same positions once to capture their HIP graphs)" + ("; with --full: value_median_window = the median of `windows` repeats of the "
+                     "same K-step window (same start token and positions: later repeats re-touch the same KV rows), value_full_window = one contiguous run "
+                     "to the end of the context" if args.full else ""),
         "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
         "dtype": {"q80": "i8", "q4k": "u4", "f32": "f32"}[args.quant], "data": "synthetic",
         "config": {"workload": f"{args.model} {args.quant.upper()}" + (f" gs={spec.group_size}" if args.quant == "q80" else "") +
-                               f", greedy decode, seq_len {SEQ_LEN}, positions {pos0}..{pos0 + K - 1} after a {PROMPT_LEN}-token prompt",
+                               f", greedy decode, seq_len {SEQ_LEN}, positions {pos0}..{pos0 + K_win - 1}" + (f" (windows of {K_win} steps from the same start)" if K > K_win else "") +
+                               f" after a {PROMPT_LEN}-token prompt",
                    "sequences": n_seq, "sequences_per_gpu": B, "world_size_seen": world_seen,
                    "collectives": (BACKEND if dist is not None else None), "windows_all_reduced": bool(dist is not None),
                    "timed_ids_crc32": ids_crc,
                    "parallelism": f"dp{n_gpus} (independent sequences, sequence i on rank i mod {n_gpus}, weight replica per GPU)"},
         "roofline": roofline,
     }
-    if not args.no_cpu_baseline and n_gpus == 1:
+    if args.full:
+        out.update({"windows": len(wins), "window_ms": {"min": round(min(wins) * 1e3, 4), "median": round(float(np.median(wins)) * 1e3, 4),
+                                                        "max": round(max(wins) * 1e3, 4), "first": round(elapsed * 1e3, 4)},
+                    "value_first_window": round(tokens / elapsed, 2), "value_median_window": round(tokens / float(np.median(wins)), 2),
+                    "value_full_window": full_win})
+    if args.full and not args.no_cpu_baseline and n_gpus == 1:
         try:
             out["cpu_baseline"] = cpu_baseline(path, spec)
         except Exception as e:                              # the baseline never blocks the GPU number

@@ -1,5 +1,5 @@
 """The drop-in proof: the reference's OWN front-ends -- infer/main_sort.c and infer/main_cli.c, unmodified, compiled by
-path from /root/reference with their own infer.h and tokenizer.c / utils.c / hal_*_linux.c (tests/dropin/Makefile =
+path from the reference with their own infer.h and tokenizer.c / utils.c / hal_*_linux.c (oracle/Makefile `dropin` =
 the reference's `sort` / `cli` targets, infer/Makefile:146-152, minus infer.c and tensor.c) -- linked against
 libnano_mi355x.so and run on the GPU.
 
@@ -8,7 +8,8 @@ libnano_mi355x.so and run on the GPU.
               reference's only real-weights known answer: "251212" -> "112225" (infer/main_sort.c:3126-3131).
   nano_cli    llm_context_init from a file, generate_sync -> llm_session_init (encode_nano) -> llm_session_step
               (batched prefill, device sampler at temperature 0.7, decode_nano) with the CLI's own callbacks.
-The binaries are built where /root/reference exists (__graft_entry__.build()) and travel with the snapshot."""
+The binaries are built into oracle/_ref/dropin/ where the reference's sources are (__graft_entry__.build()), beside the
+compiled reference, and are run wherever that build went."""
 import os
 import subprocess
 import time
@@ -19,13 +20,13 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-BIN = os.path.join(ROOT, "tests", "dropin", "_bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "dropin")
 ENV = dict(os.environ, LC_ALL="C.utf8")
 
 
 def need(name):
     path = os.path.join(BIN, name)
-    assert os.path.exists(path), f"{path} missing: run __graft_entry__.build() where /root/reference exists"
+    assert os.path.exists(path), f"{path} missing: run __graft_entry__.build() where the reference's sources are"
     return path
 
 

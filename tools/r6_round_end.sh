@@ -68,7 +68,7 @@ if [ "$1" = "a" ]; then
   ( timeout 1500 python -m pytest tests -m gpu -q -s -k "fullsize or strict or sampler_ids or config4 or nano56m or wide_rows" 2>&1 | grep -E "strict|fast path|passed|failed" ) > $O/${T}_parity.txt; tail -3 $O/${T}_parity.txt
   ( timeout 600 python -m pytest tests/test_gpu_handoff.py -m gpu -q -s 2>&1 | grep -E "load on XCD|passed|failed" ) > $O/${T}_handoff_tests.txt; cat $O/${T}_handoff_tests.txt
   timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/${T}_smoke.txt
-  timeout 400 python bench.py 2> $O/${T}_bench_stderr.txt | tee $O/${T}_bench_line.json | cut -c1-300
+  timeout 400 python bench.py --full 2> $O/${T}_bench_stderr.txt | tee $O/${T}_bench_line.json | cut -c1-300
   timeout 400 python bench.py --steps 20 --warmup 5 2>/dev/null > $O/${T}_bench_driver_flags.json; one $O/${T}_bench_driver_flags.json "driver flags"
 elif [ "$1" = "b" ]; then
   prof q06_q80_b1 --steps 100 --warmup 4
