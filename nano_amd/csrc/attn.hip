@@ -37,11 +37,10 @@ static hipError_t launch_mode_kv(const AttnArgs &a_in, uint32_t nb, hipStream_t 
     // per CU, two while at most two, else the whole KV group (measured: Qwen3-0.6B batch 1 6.15 -> 5.35 us per launch = +3.7 %
     // tokens/s; Qwen3-4B's kv_mul 4: 8.65 -> 6.03 us at batch 1, 10.05 -> 7.22 with two heads at 16 sequences, where one head
     // per workgroup costs 10.3; at 64 sequences the KV rows' bandwidth rules and four heads share them: 13.7 vs 16.4).
-    constexpr bool xcd_order = true;
     AttnArgs a = a_in;
     a.kv_log2 = 0xffffffffu; a.kvmul_log2 = 0;
     const bool kv_pow2 = (a.n_kv_head & (a.n_kv_head - 1)) == 0, mul_pow2 = (kv_mul & (kv_mul - 1)) == 0;
-    if (kv_pow2 && (MODE != 0 || (xcd_order && a.n_kv_head >= 8))) { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
+    if (kv_pow2 && (MODE != 0 || a.n_kv_head >= 8)) { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
     if (mul_pow2) { uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
     if (MODE != 0 && !(kv_pow2 && mul_pow2)) return hipErrorInvalidValue;       // launch_lpr() sends such shapes to the generic mode
     const uint64_t head_wgs = (uint64_t)a.n_head * nb * a.nsplit;

@@ -106,10 +106,8 @@ struct NanoHipModel {
     uint32_t mfma_min_nb = 9;                             // sequences per step from which Q80 GEMVs go to the MFMA GEMM (NANO_MFMA_MIN_NB: measurement)
     bool fuse_qkv_attn = true;                            // one sequence, Q80 gs 64, Qwen3 head_dim 128: q|k|v projection + attention in one launch; NANO_FUSE_LAUNCHES bit 0
     unsigned long long *hand = nullptr;                   // its granule buffer (q_dim + 2 kv_dim entries of {tag, value}; tags are epochs: device_common.h)
-    bool fuse_wo_w13 = true, fuse_wo_w13_always = false;  // Wo + W1|W3 in one launch (x as granules) where it pays / wherever the shapes allow; NANO_FUSE_LAUNCHES bits 1 / 2
+    bool fuse_wo_w13 = true;                              // one sequence, Q80 gs 64: Wo + W1|W3 in one launch (x as granules); NANO_FUSE_LAUNCHES bit 1
     unsigned long long *hand2 = nullptr;                  // its granule buffer (n_embd entries)
-    bool fuse_w2_qkv = false;                             // W2 + the next layer's q|k|v + attention in one launch (measured break-even: opt-in); NANO_FUSE_LAUNCHES bit 3
-    unsigned long long *hand3 = nullptr;                  // its granule buffer for x (n_embd entries)
     uint32_t *tick = nullptr;                             // device words of the in-launch hand-offs: [0] step counter (the epoch), [1] fault word, [2] abort flag, [3] spare
     uint32_t handoff_fallbacks = 0;                       // times a hand-off gave up and the call was re-issued through the plain launches (fusion stays off after the first)
     bool reissue = true;                                  // (nano_hip_debug_fault bit 1 clears it: the give-up then surfaces as NANO_HIP_ERUNTIME)
@@ -206,7 +204,7 @@ static void destroy(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
-                    m->xn, m->hb2, m->att, m->vraw, m->stamps, m->pt, m->kvrow, m->hand, m->hand2, m->hand3, m->tick };
+                    m->xn, m->hb2, m->att, m->vraw, m->stamps, m->pt, m->kvrow, m->hand, m->hand2, m->tick };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->h_pt };
     for (void *p : host) if (p) (void)hipHostFree(p);
@@ -446,17 +444,18 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
         hipEventCreate(&m->ev1) != hipSuccess || hipEventCreate(&m->ev2) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ERUNTIME, "stream/event creation failed"); }
     if (getenv("NANO_HIP_NO_GRAPH")) m->use_graph = false;
     if (const char *mm = getenv("NANO_MFMA_MIN_NB")) { const uint32_t v = (uint32_t)strtoul(mm, nullptr, 0); if (v >= 2) m->mfma_min_nb = v; }
-    // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch where it pays, bit 2 = ... wherever the
-    // shapes allow, bit 3 = W2 + the next layer's q | k | v + attention in one launch (two launches per layer: measured break-even, opt-in).
+    // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch (higher bits are ignored).
     // Default 3; 0 = the five launches per layer; same bits in every setting
-    if (const char *fz = getenv("NANO_FUSE_LAUNCHES")) { const uint32_t v = (uint32_t)strtoul(fz, nullptr, 0); m->fuse_qkv_attn = (v & 1u) != 0; m->fuse_wo_w13 = (v & 2u) != 0; m->fuse_wo_w13_always = (v & 4u) != 0; m->fuse_w2_qkv = (v & 8u) != 0; }
+    if (const char *fz = getenv("NANO_FUSE_LAUNCHES")) { const uint32_t v = (uint32_t)strtoul(fz, nullptr, 0); m->fuse_qkv_attn = (v & 1u) != 0; m->fuse_wo_w13 = (v & 2u) != 0; }
     if (hipMalloc(reinterpret_cast<void **>(&m->tick), 64) != hipSuccess || hipMemset(m->tick, 0, 64) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off words failed"); }
     if ((m->d.quant_type == NANO_QUANT_Q80 && m->d.group_size == 64) || m->d.quant_type == NANO_QUANT_Q4K || m->d.quant_type == NANO_QUANT_F32) {
         // granule buffers of the fused one-sequence launches: tag 0 (the memset) is no epoch -- the first step's tick is 1
-        const size_t hb = (size_t)(m->QD + 2 * m->KD) * 8, hb2 = (size_t)m->d.n_embd * 8;
+        // (hand2: the Wo + W1|W3 launch, Q80 only)
+        const size_t hb = (size_t)(m->QD + 2 * m->KD) * 8, hb2 = m->d.quant_type == NANO_QUANT_Q80 ? (size_t)m->d.n_embd * 8 : 0;
         if (hipMalloc(reinterpret_cast<void **>(&m->hand), hb) != hipSuccess || hipMemset(m->hand, 0, hb) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&m->hand2), hb2) != hipSuccess || hipMemset(m->hand2, 0, hb2) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&m->hand3), hb2) != hipSuccess || hipMemset(m->hand3, 0, hb2) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off granules failed"); }
+            (hb2 && (hipMalloc(reinterpret_cast<void **>(&m->hand2), hb2) != hipSuccess || hipMemset(m->hand2, 0, hb2) != hipSuccess))) {
+            destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off granules failed");
+        }
     }
     HIP_TRY(hipDeviceSynchronize());
     *out = m;
@@ -587,7 +586,7 @@ static void drop_graphs(NanoHipModel *m) {
 }
 static void handoff_fallback(NanoHipModel *m) {
     (void)hipStreamSynchronize(m->st);
-    m->fuse_qkv_attn = m->fuse_wo_w13 = m->fuse_wo_w13_always = m->fuse_w2_qkv = false;
+    m->fuse_qkv_attn = m->fuse_wo_w13 = false;
     drop_graphs(m);
     m->handoff_fallbacks++;
 }
@@ -683,9 +682,10 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
     ea.tick = m->tick;                                                       // the step's first kernel opens a new hand-off epoch
     if (!(m->skip_embed && mode == MODE_LOOP) && (e = launch_embed(ea, nb, m->st)) != hipSuccess) return e;
 
-    // the q | k | v launch and the attention launch of layer l (arguments only)
-    auto build_qkv_attn = [&](const uint32_t l, GemvArgs &qa, AttnArgs &a) {
+    for (uint32_t l = 0; l < L; l++) {
         const size_t layer_rows = (size_t)l * S;                    // cache row offset of this layer within a slot
+        GemvArgs qa{};
+        AttnArgs a{};
         // q | raw k | v (straight into the cache row)   reference infer.c:758-786
         qa.nseg = 3;
         qa.seg[0] = mkseg(m->W[WQ][l], m->q, QD, QD);
@@ -710,26 +710,14 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
         if (wo_frag && nsplit == 1) { a.xf_out = m->gq; a.xsf_out = m->gxs; }
         if (m->kv_paged) { a.pt_rows = pt_base; a.kvrow = m->kvrow; a.pt_stride = m->pt_stride; a.pt_bstride = pt_bstride; a.pool_rows = m->kv_pages * 64u; }
         qa.ordered = 0; qa.cus = (uint32_t)m->cus; qa.err = m->dev_err;
-    };
-    bool qkv_prelaunched = false;       // layer l's q | k | v + attention already ran inside the previous layer's last launch (w2_qkv_attn_fused_kernel)
-    for (uint32_t l = 0; l < L; l++) {
-        const size_t layer_rows = (size_t)l * S;                    // cache row offset of this layer within a slot
-        GemvArgs qa{};
-        AttnArgs a{};
-        build_qkv_attn(l, qa, a);
         // ONE launch for both (one sequence, Q80 group size 64, Qwen3 attention at head_dim 128: gemv_q80_impl.h qkv_attn_fused_kernel): the
         // attention workgroups start with the projection's, ask for their K / V rows and take q / k / v from it as write-through granules
         // tagged with the epoch of this step and layer (tick * 128 + l + 1: at most 126 layers).
-        auto qkv_attn_fusable = [&](const GemvArgs &qa_, const AttnArgs &a_) {
-            return m->fuse_qkv_attn && m->hand && nb == 1 && !m->pf && !m->lora_on && !m->stamps_on && L <= 126u &&
-                   ((d.quant_type == NANO_QUANT_Q80 && kind_of(m, qa_) == ROUTE_GEMV && qkv_attn_fused_supports(qa_, a_)) ||
-                    (d.quant_type == NANO_QUANT_Q4K && kind_of(m, qa_) == ROUTE_Q4K && qkv_attn_fused_q4k_supports(qa_, a_)) ||      // (round 6: Q4K too,
-                    (d.quant_type == NANO_QUANT_F32 && kind_of(m, qa_) == ROUTE_GEMV && qkv_attn_fused_f32_supports(qa_, a_)));      //  and FP32 / Nano)
-        };
-        const bool fused = qkv_attn_fusable(qa, a);
-        if (qkv_prelaunched) {
-            qkv_prelaunched = false;                                   // (done by the launch that ended the previous layer)
-        } else if (fused) {
+        const bool fused = m->fuse_qkv_attn && m->hand && nb == 1 && !m->pf && !m->lora_on && !m->stamps_on && L <= 126u &&
+                           ((d.quant_type == NANO_QUANT_Q80 && kind_of(m, qa) == ROUTE_GEMV && qkv_attn_fused_supports(qa, a)) ||
+                            (d.quant_type == NANO_QUANT_Q4K && kind_of(m, qa) == ROUTE_Q4K && qkv_attn_fused_q4k_supports(qa, a)) ||      // (round 6: Q4K too,
+                            (d.quant_type == NANO_QUANT_F32 && kind_of(m, qa) == ROUTE_GEMV && qkv_attn_fused_f32_supports(qa, a)));      //  and FP32 / Nano)
+        if (fused) {
             if ((e = d.quant_type == NANO_QUANT_Q4K ? launch_qkv_attn_fused_q4k(qa, a, m->hand, m->tick, l + 1u, m->st)
                    : d.quant_type == NANO_QUANT_F32 ? launch_qkv_attn_fused_f32(qa, a, m->hand, m->tick, l + 1u, m->st)
                                                     : launch_qkv_attn_fused(qa, a, m->hand, m->tick, l + 1u, m->st)) != hipSuccess) return e;
@@ -770,7 +758,6 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
         {
             if (pf_combine && (e = launch_attn_combine_tokens(m->attn_part, m->attn_ml, m->xba, d.n_head, m->hd, nsplit, nb, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
         }
-        bool wo13_done = false;
         {   // x += Wo . xba   reference infer.c:885-908
             GemvArgs a{};
             a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, E, E);
@@ -794,23 +781,14 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
             a.ordered = 0; a.cus = (uint32_t)m->cus; a.err = m->dev_err; b.ordered = 0; b.cus = (uint32_t)m->cus; b.err = m->dev_err;
             // Where it is used (round 5, same-box A/Bs, profiles/r05_wo_w13_fused.txt): with the polls backed off (workgroups that produce nothing
             // nap ~2 us before their first sweep) the fused launch wins on Qwen3-0.6B's matrices at every position (1882-1887 vs 1859-1871 tok/s at
-            // positions 20..39, 1789-1795 vs 1750-1753 over 31..510); on Qwen3-4B's it LOSES (1.531 vs 1.473 ms per step: 1024-thread workgroups
-            // that spill, polls queued behind their own 207 KB of weight loads).  So: not on the wide matrices; NANO_FUSE_LAUNCHES bit 2 (value 4)
-            // forces it wherever the shapes allow (the parity test; the measurement).
-            const bool fuse13_shape = m->hand2 && nb == 1 && !m->pf && !m->lora_on && !m->stamps_on && L <= 126u &&
-                                      ((d.quant_type == NANO_QUANT_Q80 && kind_of(m, a) == ROUTE_GEMV && kind_of(m, b) == ROUTE_GEMV && wo_w13_fused_supports(a, b)) ||
-                                       (d.quant_type == NANO_QUANT_Q4K && kind_of(m, a) == ROUTE_Q4K && kind_of(m, b) == ROUTE_Q4K && wo_w13_fused_q4k_supports(a, b)) ||
-                                       (d.quant_type == NANO_QUANT_F32 && kind_of(m, a) == ROUTE_GEMV && kind_of(m, b) == ROUTE_GEMV && wo_w13_fused_f32_supports(a, b)));
-            // (Q4K, round 6: gemv_q4k_chunk.hip q4k_wo_w13_fused_kernel is bit-identical and break-even at positions 20..39, but LOSES 1 % over positions
-            //  31..510, where Wo combines attention splits -- 1642 tok/s with q|k|v + attention fused only, 1626 with both, 1596-1612 with neither, same box,
-            //  profiles/r06_q4k_fused.txt.  So for Q4K it runs under bit 2 only, like the wide Q80 matrices.  FP32 / Nano-168M, f32_wo_w13_fused_kernel: bit-identical,
-            //  -1.5 % at positions 20..39 and -2.9 % over 31..510 against q|k|v + attention fused alone: bit 2 only as well.)
-            const bool fuse13 = fuse13_shape && (m->fuse_wo_w13_always || (m->fuse_wo_w13 && !route_is_wide(b) && d.quant_type == NANO_QUANT_Q80));
+            // positions 20..39, 1789-1795 vs 1750-1753 over 31..510).  The other forms were measured and removed: on Qwen3-4B's
+            // wide matrices a 1024-thread form LOST (1.531 vs 1.473 ms per step: workgroups that spill, polls queued behind their own 207 KB of weight
+            // loads) -- wo13_shape refuses those shapes; Q4K's lost 1 % over positions 31..510 (profiles/r06_q4k_fused.txt), FP32's 1.5 % at
+            // positions 20..39 and 2.9 % over 31..510.
+            const bool fuse13 = m->fuse_wo_w13 && m->hand2 && nb == 1 && !m->pf && !m->lora_on && !m->stamps_on && L <= 126u && d.quant_type == NANO_QUANT_Q80 &&
+                                kind_of(m, a) == ROUTE_GEMV && kind_of(m, b) == ROUTE_GEMV && wo_w13_fused_supports(a, b);
             if (fuse13) {
-                if ((e = d.quant_type == NANO_QUANT_Q4K ? launch_wo_w13_fused_q4k(a, b, m->hand2, m->tick, l + 1u, m->st)
-                       : d.quant_type == NANO_QUANT_F32 ? launch_wo_w13_fused_f32(a, b, m->hand2, m->tick, l + 1u, m->st)
-                                                        : launch_wo_w13_fused(a, b, m->hand2, m->tick, l + 1u, m->st)) != hipSuccess) return e;
-                wo13_done = true;
+                if ((e = launch_wo_w13_fused(a, b, m->hand2, m->tick, l + 1u, m->st)) != hipSuccess) return e;
             } else {
                 a.stamps = next_stamps(m, 3);
                 if ((e = gemv(m, a)) != hipSuccess) return e;
@@ -818,27 +796,12 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
                 if ((e = gemv(m, b)) != hipSuccess) return e;
             }
         }
-        (void)wo13_done;
         {   // x += W2 . hb   reference infer.c:950-965
             GemvArgs a{};
             a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, E, E);
             a.n = H; a.gs = d.group_size; a.nb = nb; a.xin = m->hb; a.xin_bstride = H; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
-            // W2 of this layer + q | k | v + attention of the NEXT one in ONE launch (gemv_q80_impl.h w2_qkv_attn_fused_kernel): the residual stream
-            // reaches the next layer's projection as granules of the same launch, q / k / v its attention workgroups as before
-            bool tripled = false;
-            if (m->fuse_w2_qkv && m->hand3 && l + 1u < L) {
-                GemvArgs qn{}; AttnArgs an{};
-                build_qkv_attn(l + 1u, qn, an);
-                a.ordered = 0; a.cus = (uint32_t)m->cus; a.err = m->dev_err;
-                if (d.quant_type == NANO_QUANT_Q80 && qkv_attn_fusable(qn, an) && kind_of(m, a) == ROUTE_GEMV && w2_qkv_attn_fused_supports(a, qn, an)) {
-                    if ((e = launch_w2_qkv_attn_fused(a, qn, an, m->hand3, m->hand, m->tick, l + 1u, m->st)) != hipSuccess) return e;
-                    tripled = true; qkv_prelaunched = true;
-                }
-            }
-            if (!tripled) {
-                a.stamps = next_stamps(m, 5);
-                if ((e = gemv(m, a)) != hipSuccess) return e;
-            }
+            a.stamps = next_stamps(m, 5);
+            if ((e = gemv(m, a)) != hipSuccess) return e;
         }
     }
     if (mode == MODE_NOCLS) return hipSuccess;
@@ -1439,17 +1402,17 @@ static int decode_greedy_once(NanoHipModel *m, const uint32_t *tokens, const uin
 // ---- the in-launch hand-offs: state, switches, fault injection (tests; tools) ----------------------------------------------------------
 extern "C" int nano_hip_handoff_state(const NanoHipModel *m, uint32_t *fused_mask, uint32_t *fallbacks, uint32_t *last_code) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
-    if (fused_mask) *fused_mask = (m->fuse_qkv_attn ? 1u : 0u) | (m->fuse_wo_w13 ? 2u : 0u) | (m->fuse_wo_w13_always ? 4u : 0u) | (m->fuse_w2_qkv ? 8u : 0u);
+    if (fused_mask) *fused_mask = (m->fuse_qkv_attn ? 1u : 0u) | (m->fuse_wo_w13 ? 2u : 0u);
     if (fallbacks) *fallbacks = m->handoff_fallbacks;
     if (last_code) *last_code = m->last_dev_err;
     return 0;
 }
 extern "C" int nano_hip_set_fusion(NanoHipModel *m, uint32_t mask) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
-    if (mask & ~15u) FAIL(NANO_HIP_EINVAL, "unknown fusion bits 0x%x", mask);
+    if (mask & ~3u) FAIL(NANO_HIP_EINVAL, "unknown fusion bits 0x%x", mask);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->st));
-    m->fuse_qkv_attn = (mask & 1u) != 0; m->fuse_wo_w13 = (mask & 2u) != 0; m->fuse_wo_w13_always = (mask & 4u) != 0; m->fuse_w2_qkv = (mask & 8u) != 0;
+    m->fuse_qkv_attn = (mask & 1u) != 0; m->fuse_wo_w13 = (mask & 2u) != 0;
     drop_graphs(m);                                                        // (graphs carry the launches of the setting they were captured under)
     return 0;
 }

@@ -1,22 +1,7 @@
 // gemv_f32_slab_body.inc -- the statements of the FP32 SLAB GEMV kernel (gemv_f32.hip), included TEXTUALLY into the plain kernel and (round 6)
 // into the fused q | k | v + attention launch of FP32 models -- the arrangement of gemv_q80_slab_body.inc, for the same reason.  The includer
-// defines F32_A (the GemvDev), F32_BID (the workgroup's index among the GEMV workgroups), F32_HAND 0 | 1 (the fold threads also store every
-// result as an 8-byte {tag, value} granule: F32_HANDV the SlabHand, F32_PTAG the producers' tag), optionally F32_XHAND 1 (the activation arrives as
-// granules of the SAME launch: F32_XHANDV, F32_CTAG, F32_XWAIT naps before the first sweep) and F32_PART (0: the whole body; 1: declarations + every
-// load; 2: the rest -- a kernel that runs two bodies issues the second one's weight loads before it computes the first), and has ROLE, B, NV, UPW and
-// smem in scope.
-#ifndef F32_XHAND
-#define F32_XHAND 0
-#define F32_XHANDV (SlabHand{})
-#define F32_CTAG 0u
-#define F32_XWAIT 0u
-#define F32_XHAND_DEFAULTED 1
-#endif
-#ifndef F32_PART
-#define F32_PART 0
-#define F32_PART_DEFAULTED 1
-#endif
-#if F32_PART != 2
+// defines F32_A (the GemvDev), F32_BID (the workgroup's index among the GEMV workgroups) and F32_HAND 0 | 1 (the fold threads also store every
+// result as an 8-byte {tag, value} granule: F32_HANDV the SlabHand, F32_PTAG the producers' tag), and has ROLE, B, NV, UPW and smem in scope.
     constexpr int TR = 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -32,7 +17,7 @@
     float *P = red + B * 16 + (has_flag<ROLE>(F32_A, F_COMBINE) ? B * F32_A.attn_n_head * 8 : 0);   // [B][nmat][RW][PC]
 
     Staged<B, NV> sx;
-    if constexpr (F32_XHAND) stage_issue_nw<ROLE, B, NV>(F32_A, sx); else stage_issue<ROLE, B, NV>(F32_A, sx);
+    stage_issue<ROLE, B, NV>(F32_A, sx);
 
     const uint32_t grow0 = (F32_BID) * RW;
     const uint32_t b0 = F32_A.rows[0], b1 = b0 + F32_A.rows[1];
@@ -72,35 +57,6 @@
     float addv = 0.0f;                                              // LoRA o-branch: x += (W.act + addv), reference order
     const bool has_add = epi == GEMV_EPI_RESID && F32_A.resid_add != nullptr;
     if (has_add && fold_live) addv = F32_A.resid_add[(size_t)fb * F32_A.resid_add_bstride + lrow0 + frl];
-#endif   // F32_PART != 2
-#if F32_PART != 1
-    if constexpr (F32_XHAND) {
-        // the activation as 8-byte {tag, value} granules from the workgroups that produce it in this same launch (gemv_q80_slab_body.inc has the
-        // protocol): every thread waits for the granules of its own float4 items; bounded, giving up is reported through the sticky error word
-        static_assert(!F32_XHAND || B == 1, "granule activations: one sequence");
-        const unsigned long long *hb_ = F32_XHANDV.buf;
-        const uint32_t ctag_ = F32_CTAG;
-        bool got_ = false;
-        for (uint32_t w_ = 0; w_ < (F32_XWAIT); w_++) __builtin_amdgcn_s_sleep(16);
-        for (uint32_t spin_ = 0; spin_ < (1u << 14) && !got_; spin_++) {
-            if (spin_) __builtin_amdgcn_s_sleep(2);
-            if ((spin_ & 63u) == 63u && hand_aborted(F32_XHANDV)) break;
-            got_ = true;
-#pragma unroll
-            for (int j = 0; j < NV; j++) {
-                const uint32_t i = ((uint32_t)tid + (uint32_t)j * F32_A.nthr) * 4u;
-                if (i < n) {
-                    const unsigned long long g0_ = __hip_atomic_load(hb_ + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long g1_ = __hip_atomic_load(hb_ + i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long g2_ = __hip_atomic_load(hb_ + i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long g3_ = __hip_atomic_load(hb_ + i + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    got_ = got_ && (uint32_t)(g0_ >> 32) == ctag_ && (uint32_t)(g1_ >> 32) == ctag_ && (uint32_t)(g2_ >> 32) == ctag_ && (uint32_t)(g3_ >> 32) == ctag_;
-                    sx.x[0][j] = make_float4(__uint_as_float((uint32_t)g0_), __uint_as_float((uint32_t)g1_), __uint_as_float((uint32_t)g2_), __uint_as_float((uint32_t)g3_));
-                } else sx.x[0][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-        if (!got_) hand_give_up(F32_XHANDV, F32_A.err);
-    }
 
     stage_finish_f32<ROLE, B, NV>(F32_A, sx, xf, red, n4);
 
@@ -146,15 +102,3 @@
         } else
         if (fold_live) __hip_atomic_store(out0 + (size_t)fb * obs + (size_t)opos * ops + lrow0 + frl, finish_epi(epi, has_add ? v0 + addv : v0, v1, oldv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#endif   // F32_PART != 1
-#ifdef F32_XHAND_DEFAULTED
-#undef F32_XHAND
-#undef F32_XHANDV
-#undef F32_CTAG
-#undef F32_XWAIT
-#undef F32_XHAND_DEFAULTED
-#endif
-#ifdef F32_PART_DEFAULTED
-#undef F32_PART
-#undef F32_PART_DEFAULTED
-#endif

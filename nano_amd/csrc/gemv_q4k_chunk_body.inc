@@ -1,15 +1,11 @@
 // gemv_q4k_chunk_body.inc -- the statements of the Q4K chunk GEMV kernel (gemv_q4k_chunk.hip), included TEXTUALLY into each kernel that runs
-// them: the plain gemv_q4k_chunk_kernel and (round 6) the fused one-sequence launches -- the same arrangement, for the same reason, as
+// them: the plain gemv_q4k_chunk_kernel and (round 6) the fused q | k | v + attention launch -- the same arrangement, for the same reason, as
 // gemv_q80_slab_body.inc (a by-value kernel-argument block routed through a reference ended up in scratch).  The includer defines
 //   CHUNK_A      the GemvDev (a by-value kernel parameter, or a member of one)
 //   CHUNK_BID    the workgroup's index among this body's workgroups
 //   CHUNK_HAND   0 | 1: the fold threads also store every result as an 8-byte {tag, value} granule (CHUNK_HANDV: the SlabHand, CHUNK_PTAG: the
 //                producers' tag of this step and layer -- device_common.h)
-//   CHUNK_XHAND  0 | 1: the activation arrives as granules written by other workgroups of the SAME launch (CHUNK_XHANDV, CHUNK_CTAG; CHUNK_XWAIT:
-//                naps of 16 x 64 cycles before the first sweep), polled after the weight loads are out
-//   CHUNK_PART   0: the whole body; 1: declarations + every load (up to the fold threads' loads); 2: the rest
 // and has ROLE, NV, D, LOOP, NB and smem in scope.
-#if CHUNK_PART != 2
     const uint32_t tid = threadIdx.x, nthr = CHUNK_A.nthr, lane = tid & 63u;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), NW = nthr >> 6;
     const uint32_t n = CHUNK_A.n, bpl = n >> 8, GT = bpl * 8u, BP = bpl | 1u;    // BP: pitch of the block-sum table (odd: rows on different banks)
@@ -33,7 +29,7 @@
     if (ROLE == R_GENERIC || ROLE == R_RESID || ROLE == R_RESID_COMBINE) { karg_touch(CHUNK_A.resid_add); karg_touch(CHUNK_A.resid_add_bstride); }
     NANO_STAMP(CHUNK_A.stamps, 0, tid);
     Staged<1, NV> sx;
-    if constexpr (NB == 1) { if constexpr (CHUNK_XHAND) stage_issue_nw<ROLE, 1, NV>(CHUNK_A, sx); else stage_issue<ROLE, 1, NV>(CHUNK_A, sx); }
+    if constexpr (NB == 1) stage_issue<ROLE, 1, NV>(CHUNK_A, sx);
 
     // this workgroup's rows: inside one segment (the last workgroup of a segment may hold fewer than RW)
     const uint32_t bid = CHUNK_BID;
@@ -77,8 +73,6 @@
     if (has_add && fold_live) addv = CHUNK_A.resid_add[lrow0 + tid];
 
     NANO_STAMP(CHUNK_A.stamps, 1, tid);                                   // every load of the first ring issued
-#endif   // CHUNK_PART != 2
-#if CHUNK_PART != 1
 
     // ---- a wave-load in two halves: what needs only the weights (pre), what needs the staged activation (post) ----------------------
     float *scw = scr + wid * SL * 64u;                              // this wave's lines: group values of the six blocks of a wave-load
@@ -146,33 +140,6 @@
     } else
     if (has_flag<ROLE>(CHUNK_A, F_PRE)) unpack_q4k_wg(CHUNK_A, xg);
     else {
-        if constexpr (CHUNK_XHAND) {
-            // the activation as 8-byte {tag, value} granules from the workgroups that produce it in this same launch: every thread waits for
-            // the granules of its own float4 items (gemv_q80_slab_body.inc has the protocol and what was measured against it); bounded
-            static_assert(!CHUNK_XHAND || NB == 1, "granule activations: one sequence");
-            const unsigned long long *hb_ = CHUNK_XHANDV.buf;
-            const uint32_t ctag_ = CHUNK_CTAG;
-            bool got_ = false;
-            for (uint32_t w_ = 0; w_ < (CHUNK_XWAIT); w_++) __builtin_amdgcn_s_sleep(16);
-            for (uint32_t spin_ = 0; spin_ < (1u << 14) && !got_; spin_++) {
-                if (spin_) __builtin_amdgcn_s_sleep(2);
-                if ((spin_ & 63u) == 63u && hand_aborted(CHUNK_XHANDV)) break;
-                got_ = true;
-#pragma unroll
-                for (int j = 0; j < NV; j++) {
-                    const uint32_t i = (tid + (uint32_t)j * nthr) * 4u;
-                    if (i < n) {
-                        const unsigned long long g0_ = __hip_atomic_load(hb_ + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned long long g1_ = __hip_atomic_load(hb_ + i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned long long g2_ = __hip_atomic_load(hb_ + i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned long long g3_ = __hip_atomic_load(hb_ + i + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        got_ = got_ && (uint32_t)(g0_ >> 32) == ctag_ && (uint32_t)(g1_ >> 32) == ctag_ && (uint32_t)(g2_ >> 32) == ctag_ && (uint32_t)(g3_ >> 32) == ctag_;
-                        sx.x[0][j] = make_float4(__uint_as_float((uint32_t)g0_), __uint_as_float((uint32_t)g1_), __uint_as_float((uint32_t)g2_), __uint_as_float((uint32_t)g3_));
-                    } else sx.x[0][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-            if (!got_) hand_give_up(CHUNK_XHANDV, CHUNK_A.err);
-        }
         stage_xn<ROLE, 1, NV>(CHUNK_A, sx, nullptr, red, (n + 3u) & ~3u, true);
         NANO_STAMP(CHUNK_A.stamps, 2, red[0]);                            // the activation arrived and is normalised
         quantize_q4k_regs<1, NV, false>(CHUNK_A, sx, xg);
@@ -308,4 +275,3 @@
         }
     }
     NANO_STAMP_END(CHUNK_A.stamps, 6);
-#endif   // CHUNK_PART != 1

@@ -401,7 +401,6 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #undef SLAB_CTAG
         {
             constexpr int ROLE = R_NORM_SWIGLU, NV = NV_B, UPW = UPW_B;
-#define SLAB_EARLY (NT == 1024 ? 1 : 0)     /* the wide matrices (round 6): W1|W3's first unit before Wo's body, the other three after x has arrived */
 #define SLAB_A fa.w13
 #define SLAB_HAND 0
 #define SLAB_HANDV (SlabHand{})
@@ -428,87 +427,11 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #undef SLAB_CTAG
 #undef SLAB_XHAND_WAIT
 #undef SLAB_XHAND_NAP
-#undef SLAB_EARLY
         }
 #undef SLAB_BID
     }
 }
 
-// ---- W2 of layer l + q | k | v + attention of layer l + 1 in ONE launch (round 5) ---------------------------------------------------------
-// The third hand-off: the residual stream x = x + W2 . hb reaches the NEXT layer's q | k | v projection as granules of the same launch (an
-// all-gather, like Wo -> W1|W3 above), and q / k / v reach that layer's attention workgroups as in qkv_attn_fused_kernel.  With it a
-// one-sequence step on the small matrices is TWO launches per layer.  The projection workgroups run W2's rows first (every one of them is a
-// producer), the attention workgroups come LAST in the grid, ask for their K / V rows, nap (the q / k / v of the next layer are two bodies
-// away) and poll.  Issue order: W2's loads, q|k|v's weight loads, W2's arithmetic, q|k|v's.  Reference: infer/infer.c:950-965, 758-879.
-struct W2QkvArgs { GemvDev w2; GemvDev g; AttnArgs a; SlabHand xh; SlabHand hand; uint32_t n_attn, head_wgs, wait16, w2_wgs, xwait, ngemv; };
-template <int NV_A, int UPW_A, int NV_B, int UPW_B>
-__global__ __launch_bounds__(256) void w2_qkv_attn_fused_kernel(const W2QkvArgs fa) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint2 tk_ = hand_tick(fa.hand);
-    if (blockIdx.x >= fa.ngemv) {
-        const uint32_t ab = blockIdx.x - fa.ngemv;
-        const uint32_t split = ab / fa.head_wgs, grp = ab - split * fa.head_wgs;
-        attention_body<8, 4, 1, 1, false, false, 2, false, true>(fa.a, smem, grp, 0u, split, fa.hand, hand_ctag(tk_, fa.hand), fa.wait16);
-        return;
-    }
-    constexpr int GS = 64, B = 1;
-    {
-        constexpr int ROLE = R_RESID, NV = NV_A, UPW = UPW_A;
-#define SLAB_BID blockIdx.x
-#define SLAB_A fa.w2
-#define SLAB_HAND 1
-#define SLAB_HANDV fa.xh
-#define SLAB_PTAG hand_ptag(tk_, fa.xh)
-#define SLAB_XHAND 0
-#define SLAB_XHANDV (SlabHand{})
-#define SLAB_CTAG 0u
-#define SLAB_PART 1
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-        auto w2_rest = [&]() __attribute__((always_inline)) {
-#define SLAB_PART 2
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-        };
-#undef SLAB_A
-#undef SLAB_HAND
-#undef SLAB_HANDV
-#undef SLAB_PTAG
-#undef SLAB_XHAND
-#undef SLAB_XHANDV
-#undef SLAB_CTAG
-        {
-            constexpr int ROLE = R_NORM_STORE, NV = NV_B, UPW = UPW_B;
-#define SLAB_A fa.g
-#define SLAB_HAND 1
-#define SLAB_HANDV fa.hand
-#define SLAB_PTAG hand_ptag(tk_, fa.hand)
-#define SLAB_XHAND 1
-#define SLAB_XHANDV fa.xh
-#define SLAB_CTAG hand_ctag(tk_, fa.xh)
-#define SLAB_XHAND_WAIT fa.xwait
-#define SLAB_XHAND_NAP 2
-#define SLAB_PART 1
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-            if (blockIdx.x < fa.w2_wgs) w2_rest();
-            __syncthreads();
-#define SLAB_PART 2
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-#undef SLAB_A
-#undef SLAB_HAND
-#undef SLAB_HANDV
-#undef SLAB_PTAG
-#undef SLAB_XHAND
-#undef SLAB_XHANDV
-#undef SLAB_CTAG
-#undef SLAB_XHAND_WAIT
-#undef SLAB_XHAND_NAP
-        }
-#undef SLAB_BID
-    }
-}
 #endif
 
 // ------------------------------------------------------------------------------------------------------------
@@ -682,31 +605,20 @@ static SlabPlan plan_slab(const GemvArgs &a, int B) {
     // (round 5: TWO sequences on these matrices take the same balanced slabs, the product table twice as large -- Qwen3-4B at 2 sequences
     //  1.833 ms per step against 1.923 through G6 MODE P, same box; four sequences: 2.80 against 1.99 through G6, so two is where it ends)
     if (B <= 2 && (uint64_t)rows * a.n * nmat >= (8u << 20)) {
-        constexpr bool balanced = true;                            // (round 2's power-of-two rule below is kept for the record of what was measured)
         const uint32_t cus = a.cus ? a.cus : 256u;
         uint32_t best = 0, best_cost = ~0u;
-        if (balanced) {
-            const uint32_t ng = a.n / a.gs, pitch = (1024 / a.gs == 16) ? (((ng + 47) / 64) * 64 + 16) : (((ng + 3) & ~3u) + 4);
-            for (uint32_t c = 4; c <= 64; c++) {
-                const uint32_t tpw = (c + 3) / 4;
-                if (tpw * nchunk * nmat > 64) break;                           // <= 16 waves x 4 units
-                if ((size_t)B * nmat * tpw * 4 * pitch * 4 > 96 * 1024) break;     // product table
-                uint32_t wgs = 0;
-                if (nseg > 1) for (uint32_t s2 = 0; s2 < nseg; s2++) wgs += (a.seg[s2].rows + c - 1) / c; else wgs = (rows + c - 1) / c;
-                // rows of the busiest CU; more than one workgroup per CU pays its prologue several times over on shared issue
-                // slots (measured: QKV of Qwen3-4B, 768 workgroups of 8 rows 7.4 us vs 192 of 32 rows 6.9), so x 1.15 then
-                uint32_t cost = ((wgs + cus - 1) / cus) * c * 100u;
-                if (wgs > cus) cost += cost * 15u / 100u;
-                if (cost <= best_cost) { best_cost = cost; best = c; }
-            }
-        } else {
-            for (uint32_t c = 4; c <= 64; c *= 2) {
-                const uint64_t bytes = (uint64_t)c * a.n * nmat;
-                if (nseg > 1 && (align % c) != 0) continue;
-                if (bytes < (64u << 10) || bytes > (160u << 10) || (c / 4) * nchunk * nmat > 64) continue;
-                const uint32_t wgs = (rows + c - 1) / c, cost = ((wgs + 255) / 256) * c;
-                if (cost <= best_cost) { best_cost = cost; best = c; }
-            }
+        const uint32_t ng = a.n / a.gs, pitch = (1024 / a.gs == 16) ? (((ng + 47) / 64) * 64 + 16) : (((ng + 3) & ~3u) + 4);
+        for (uint32_t c = 4; c <= 64; c++) {
+            const uint32_t tpw = (c + 3) / 4;
+            if (tpw * nchunk * nmat > 64) break;                           // <= 16 waves x 4 units
+            if ((size_t)B * nmat * tpw * 4 * pitch * 4 > 96 * 1024) break;     // product table
+            uint32_t wgs = 0;
+            if (nseg > 1) for (uint32_t s2 = 0; s2 < nseg; s2++) wgs += (a.seg[s2].rows + c - 1) / c; else wgs = (rows + c - 1) / c;
+            // rows of the busiest CU; more than one workgroup per CU pays its prologue several times over on shared issue
+            // slots (measured: QKV of Qwen3-4B, 768 workgroups of 8 rows 7.4 us vs 192 of 32 rows 6.9), so x 1.15 then
+            uint32_t cost = ((wgs + cus - 1) / cus) * c * 100u;
+            if (wgs > cus) cost += cost * 15u / 100u;
+            if (cost <= best_cost) { best_cost = cost; best = c; }
         }
         if (best) {
             rw = best;
@@ -714,7 +626,6 @@ static SlabPlan plan_slab(const GemvArgs &a, int B) {
             large_nw = u / 2 < 8 ? 8 : (u / 2 > 16 ? 16 : u / 2);
         }
     }
-    const uint32_t force_nw = 0;
     const uint32_t units = ((rw + 3) / 4) * nchunk * nmat;
     uint32_t nw = units < 4 ? units : 4;
     // (one sequence, re-swept on round 6's last day with the three-launch layer: a wave per 384 activation values -- W2 of Qwen3-0.6B on 8 waves
@@ -728,7 +639,6 @@ static SlabPlan plan_slab(const GemvArgs &a, int B) {
     uint32_t upw = (units + nw - 1) / nw;
     while (upw > 4 && nw < 16) { nw++; upw = (units + nw - 1) / nw; }
     if (large_nw) { nw = large_nw; upw = (units + nw - 1) / nw; while (upw > 4 && nw < 16) { nw++; upw = (units + nw - 1) / nw; } }
-    if (force_nw) { nw = force_nw; upw = (units + nw - 1) / nw; }
     // (Round 4 tried a raw barrier between the activation loads and the weight loads of the large slabs, so that every wave's activation
     // is asked for before any weight -- round 3 had measured the activation of Qwen3-4B's W1|W3 "arriving" with the end of the 52.9 MB
     // burst.  Measured on one box: 1.4707 ms per step with it, 1.4594 without.  The launch is bound by latency + stream + tail, not by
@@ -843,8 +753,8 @@ static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, SlabPlan &p) {
 
 // ---- the fused Wo + W1|W3 launch: host side ----------------------------------------------------------------------------------------------
 // Both bodies run on the launch's threads = W1|W3's own plan (its rmsnorm tree follows the thread count; Wo has no tree: any count gives its
-// bits).  Instantiated: Qwen3-0.6B's shapes (256 threads) and Qwen3-4B's (1024 threads, every W1|W3 weight load of a workgroup in flight
-// while Wo computes).
+// bits).  Instantiated: Qwen3-0.6B's shapes (256 and 512 threads).  (Qwen3-4B's wide matrices had a 1024-thread form; it lost to the two
+// plain launches -- 1.531 vs 1.473 ms per step -- and was removed: those shapes are refused here and take the plain launches.)
 struct Wo13Plan { SlabPlan a, b; uint32_t nw, nv_a, upw_a, wa, wb; int sig; };
 static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (wo.gs != 64 || w13.gs != 64 || wo.nb != 1 || w13.nb != 1 || !q80_canonical(wo) || !q80_canonical(w13)) return false;
@@ -863,7 +773,6 @@ static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (q.a.rw > 64 * q.nw || q.b.rw > 64 * q.nw) return false;                                 // one fold thread per row
     q.sig = 0;
     if (q.nw == 4u && q.nv_a == 2u && q.upw_a == 1u && q.b.nv == 1u && q.b.upw == 2u) q.sig = 1;       // Qwen3-0.6B
-    if (q.nw == 16u && q.nv_a == 1u && q.upw_a == 1u && q.b.nv == 1u && q.b.upw == 4u) q.sig = 2;      // Qwen3-4B
     if (q.sig == 1) {
         // Round 6, last day: the same two bodies on EIGHT waves where that leaves one float4 item per thread and one unit per wave in both (Qwen3-0.6B:
         // Wo's 512 items, 4 units; W1|W3's 256 items, 6 units) -- the four-wave form dates from the first fused build and had Wo's threads quantize
@@ -953,67 +862,6 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
 #undef FUSED_GO
 }
 
-// W2 (layer l) + q | k | v + attention (layer l + 1)
-struct W2QkvPlan { SlabPlan a, b; uint32_t nv_a, upw_a, wa; };
-static bool w2qkv_shape(const GemvArgs &w2, const GemvArgs &ga, const AttnArgs &aa, W2QkvPlan &q) {
-    if (!fused_shape(ga, aa, q.b)) return false;
-    if (w2.gs != 64 || w2.nb != 1 || !q80_canonical(w2) || w2.nseg != 1 || w2.epi != GEMV_EPI_RESID || w2.norm_w || w2.xq_in || w2.attn_part || w2.tile_max ||
-        w2.resid_add || w2.seg[0].out_pstride || use_stream(w2)) return false;
-    if (ga.n != w2.seg[0].rows || ga.xin != w2.seg[0].out) return false;              // the projection's input is what W2 writes
-    q.a = plan_slab(w2, 1);
-    const uint32_t units_a = ((q.a.rw + 3) / 4) * ((w2.n + 1023) / 1024);
-    q.upw_a = (units_a + 3u) / 4u;                                                   // on the launch's 256 threads
-    q.nv_a = (w2.n / 4 + 255u) / 256u;
-    q.wa = (w2.seg[0].rows + q.a.rw - 1) / q.a.rw;
-    uint32_t ngemv = 0;
-    for (uint32_t s2 = 0; s2 < 3; s2++) ngemv += (ga.seg[s2].rows + q.b.rw - 1) / q.b.rw;
-    if (q.wa > ngemv || q.a.rw > 256u) return false;
-    // instantiated: Qwen3-0.6B's shapes (W2: three float4 items per thread -> NV 4, one unit per wave; q|k|v: NV 1, UPW 1)
-    return q.upw_a == 1u && q.nv_a >= 3u && q.nv_a <= 4u && q.b.nv == 1u && q.b.upw == 1u;
-}
-
-bool w2_qkv_attn_fused_supports(const GemvArgs &w2, const GemvArgs &ga, const AttnArgs &aa) { W2QkvPlan q; return w2qkv_shape(w2, ga, aa, q); }
-
-hipError_t launch_w2_qkv_attn_fused(const GemvArgs &w2, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *xhand, unsigned long long *hand,
-                                    uint32_t *tick, uint32_t layer1, hipStream_t st) {
-    W2QkvPlan q;
-    if (!xhand || !hand || !tick || !layer1 || layer1 > 126u || !w2qkv_shape(w2, ga, aa, q)) return hipErrorInvalidValue;
-    W2QkvArgs fa{};
-    fa.w2 = to_dev(w2); slab_dev_fill(fa.w2, w2, q.a, 256u);
-    GemvDev d = to_dev(ga);
-    d.tile_max = nullptr;
-    d.rw = q.b.rw; d.tpw = (q.b.rw + 3) / 4; d.magic_rw = 65536u / q.b.rw + 1u; d.log2_tiles = 0;
-    d.units = d.tpw * d.nchunk;
-    uint32_t wg[3];
-    for (uint32_t s2 = 0; s2 < 3; s2++) wg[s2] = (ga.seg[s2].rows + q.b.rw - 1) / q.b.rw;
-    d.wg_c0 = wg[0]; d.wg_c1 = wg[0] + wg[1];
-    const uint32_t ngemv = wg[0] + wg[1] + wg[2];
-    d.nthr = 256;
-    fa.g = d;
-    AttnArgs a = aa;
-    { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
-    { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
-    fa.a = a;
-    SlabHand h{};
-    h.buf = hand; h.tick = tick; h.layer1 = layer1 + 1u;                // q / k / v of the NEXT layer
-    h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
-    SlabHand xh{};
-    xh.buf = xhand; xh.tick = tick; xh.layer1 = layer1;
-    xh.base[0] = 0; xh.base[1] = 0; xh.base[2] = 0;
-    fa.hand = h; fa.xh = xh;
-    fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head; fa.w2_wgs = q.wa; fa.ngemv = ngemv;
-    // naps (x 16 x 64 cycles) before the first polls: the attention workgroups' q / k / v are two bodies away (swept 3 .. 11: 7-8 best),
-    // the projection workgroups all finish W2 together and nap ~1 us before asking for the others' rows (swept 0 .. 3: 2 best).  Measured
-    // against the default (two fused launches + W2) on one box: 1879-1898 vs 1877-1920 tok/s -- break-even, hence opt-in.
-    fa.wait16 = 7u; fa.xwait = 2u;      // (round 6 re-sweep, attention naps 2 / 4 / 7 x activation naps 0 / 2: 1890-1933 tok/s where the three-launch form does 1968-1987: opt-in still)
-    const size_t la = slab_lds(fa.w2), lb = slab_lds(fa.g);
-    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4) * sizeof(float);
-    size_t lds = la > lb ? la : lb; if (lds_a > lds) lds = lds_a;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((w2_qkv_attn_fused_kernel<4, 1, 1, 1>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa);
-    return hipGetLastError();
-}
-
 bool wo_w13_fused_supports(const GemvArgs &wo, const GemvArgs &w13) { Wo13Plan q; return wo13_shape(wo, w13, q); }
 
 hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
@@ -1035,9 +883,8 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     const bool comb = (fa.wo.flags & F_COMBINE) != 0;
 #define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_>), dim3(q.wb), dim3(NT_), lds, st, fa); return hipGetLastError(); } while (0)
     if (q.sig == 1) { if (comb) WO13_GO(R_RESID_COMBINE, 2, 1, 1, 2, 256); WO13_GO(R_RESID, 2, 1, 1, 2, 256); }
-    if (q.sig == 3) { if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 1, 512); WO13_GO(R_RESID, 1, 1, 1, 1, 512); }
-    if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 4, 1024);
-    WO13_GO(R_RESID, 1, 1, 1, 4, 1024);
+    if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 1, 512);           // (sig 3)
+    WO13_GO(R_RESID, 1, 1, 1, 1, 512);
 #undef WO13_GO
 }
 #endif

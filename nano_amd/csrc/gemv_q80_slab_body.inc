@@ -1,5 +1,5 @@
 // gemv_q80_slab_body.inc -- the statements of the SLAB GEMV kernel (gemv_q80_impl.h), included TEXTUALLY into each kernel that runs them:
-// the plain gemv_q80_slab_kernel and the fused q | k | v + attention kernel.  Textual, not a function taking the argument block by
+// the plain gemv_q80_slab_kernel and the fused q | k | v + attention and Wo + W1|W3 kernels.  Textual, not a function taking the argument block by
 // reference: routed through a reference the compiler copied the block to scratch in the multi-segment roles and fetched its fields
 // late (296 bytes of private memory, the step 25 % slower; tests/test_isa_hygiene.py).  The includer defines
 //   SLAB_A      the GemvDev (a by-value kernel parameter, or a member of one)
@@ -13,7 +13,8 @@
 //               the producers add to -- device-scope read-modify-writes on one address serialise at ~50 ns each: +6 us per layer with 128
 //               producers, +12 with 256; one flag per producer polled by one wave per workgroup, then the values by agent-scope loads --
 //               the extra round trip costs more than the polls it saves: +1.7 us per layer.  profiles/r05_wo_w13_fused.txt)
-//   SLAB_EARLY  (optional, default 0) units of a wave's weights asked for before the activation is quantized, the rest after (0 = all before)
+//   SLAB_EARLY  (optional, default 0; SLAB_PART 0 only) units of a wave's weights asked for before the activation is quantized, the rest
+//               after (0 = all before)
 //   SLAB_PART   0: the whole body; 1: declarations + every load of the launch (sections 0-3) only; 2: the rest (sections 4-6) -- a kernel
 //               that runs two bodies issues the second one's weight loads (part 1) before it computes the first (wo_w13_fused_kernel)
 // and has ROLE, GS, B, NV, UPW, smem, in scope.
@@ -26,7 +27,7 @@
 #define SLAB_XHAND_NAP 0
 #define SLAB_XHAND_WAIT_DEFAULTED 1
 #endif
-// (a unit's weight and scale loads; used by part 1 and -- SLAB_EARLY -- by part 2)
+// (a unit's weight and scale loads; used by section 2 and -- SLAB_EARLY -- by section 4)
 #define SLAB_ISSUE_UNIT(k) do { \
         const uint32_t u = (uint32_t)wid + (uint32_t)k * NW; \
         const uint32_t t = (u * SLAB_A.magic_nchunk) >> 16; \
@@ -100,8 +101,8 @@
     // whole burst (stamps, W2 of Qwen3-4B: 4.0 us in issue, THEN 1.9 us of quantization, with nothing in flight).  Such launches ask for
     // the first `early` units of every wave here and for the rest after the activation is in LDS: the first units stream while it is
     // normalised and quantized.  (early = 0: everything here -- the small matrices, whose loads all leave at once.)
-    constexpr uint32_t early_ = (uint32_t)(SLAB_EARLY);      // (compile time: a run-time choice in these kernels cost the small launches 1.3 %; with SLAB_PART 1 / 2 the
-                                                             //  includer sets it for BOTH parts: part 1 asks for the first units, part 2 for the rest)
+    constexpr uint32_t early_ = (uint32_t)(SLAB_EARLY);      // (compile time: a run-time choice in these kernels cost the small launches 1.3 %)
+    static_assert(SLAB_PART == 0 || early_ == 0u, "SLAB_EARLY: the whole body only");
     // (a macro, not a lambda: as a lambda the fused kernels' schedules changed and the one-sequence step lost 0.8 %.  Unit u = wave + k NW ->
     //  (tile, chunk); rows of the tile beyond the workgroup's RW belong to the next workgroup (RW % 4 != 0): a wave-uniform select)
 #pragma unroll

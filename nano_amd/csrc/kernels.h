@@ -189,11 +189,6 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
 // Wo + W1|W3 of one sequence in ONE launch (gemv_q80_impl.h wo_w13_fused_kernel): x reaches W1|W3 as granules of the same launch
 bool wo_w13_fused_supports(const GemvArgs &wo, const GemvArgs &w13);
 hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
-// W2 of a layer + q | k | v + attention of the next one in ONE launch (w2_qkv_attn_fused_kernel): x as granules (xhand, tag of layer1), then
-// q / k / v as granules (hand, tag of layer1 + 1)
-bool w2_qkv_attn_fused_supports(const GemvArgs &w2, const GemvArgs &ga, const AttnArgs &aa);
-hipError_t launch_w2_qkv_attn_fused(const GemvArgs &w2, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *xhand, unsigned long long *hand,
-                                    uint32_t *tick, uint32_t layer1, hipStream_t st);
 // the attention side of the fused one-sequence launches (Q80: gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip): Qwen3 decode attention on an FP32
 // contiguous cache, head_dim 128, one head per workgroup, two timestep blocks in flight; qr / kr / vr = rows of the q | k | v segments
 inline bool fused_attn_side_ok(const AttnArgs &aa, uint32_t qr, uint32_t kr, uint32_t vr) {
@@ -217,13 +212,9 @@ inline bool fused_attn_side_ok_plain(const AttnArgs &aa, uint32_t qr, uint32_t k
 }
 bool qkv_attn_fused_f32_supports(const GemvArgs &ga, const AttnArgs &aa);
 hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
-bool wo_w13_fused_f32_supports(const GemvArgs &wo, const GemvArgs &w13);
-hipError_t launch_wo_w13_fused_f32(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
 // the same launch for Q4K (gemv_q4k_chunk.hip q4k_qkv_attn_fused_kernel, round 6)
 bool qkv_attn_fused_q4k_supports(const GemvArgs &ga, const AttnArgs &aa);
 hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
-bool wo_w13_fused_q4k_supports(const GemvArgs &wo, const GemvArgs &w13);
-hipError_t launch_wo_w13_fused_q4k(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
 uint32_t attention_nsplit(uint32_t range_hint, uint32_t hd);
 hipError_t launch_attn_combine(const float *part, const float *ml, float *out, uint32_t n_head, uint32_t hd, uint32_t nsplit, hipStream_t st);
 hipError_t launch_attn_combine_tokens(const float *part, const float *ml, float *out, uint32_t n_head, uint32_t hd, uint32_t nsplit, uint32_t nb,

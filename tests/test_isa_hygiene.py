@@ -68,13 +68,16 @@ def test_q80_batch1_roles_fetch_their_arguments_up_front():
         for k in hot(recs, ["gemv_q80_slab_kernel" + sig]):
             check(k)
             assert not k["late_scalar_loads"], (k["name"], "kernel arguments fetched after the first batch", k["late_scalar_loads"])
-    seen = 0
+    expected = (["qkv_attn_fused_kernelILi%dELi%dEE" % (nv, upw) for nv in (1, 2, 4) for upw in (1, 2, 4)] +
+                ["wo_w13_fused_kernelILi%dELi2ELi1ELi1ELi2ELi256E" % role for role in (2, 3)] +         # Wo + W1|W3: 256 and 512 threads, with and
+                ["wo_w13_fused_kernelILi%dELi1ELi1ELi1ELi1ELi512E" % role for role in (2, 3)] +         # without the split combine
+                ["gemv_q80_slab_kernel" + sig for sig in ("ILi1ELi64ELi1ELi1ELi1E", "ILi2ELi64ELi1ELi2ELi1E", "ILi3ELi64ELi1ELi2ELi1E", "ILi4ELi64ELi1ELi1ELi2E")])
+    seen = set()
     for blk in re.findall(r"- \.agpr_count:.*?\.wavefront_size: *\d+", asm, re.S):
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        hot_one = ("qkv_attn_fused_kernel" in name or "wo_w13_fused_kernelILi2ELi2ELi1ELi1ELi2ELi256E" in name or "wo_w13_fused_kernelILi3ELi2ELi1ELi1ELi2ELi256E" in name or
-                   any("gemv_q80_slab_kernel" + sig in name for sig in ("ILi1ELi64ELi1ELi1ELi1E", "ILi2ELi64ELi1ELi2ELi1E", "ILi3ELi64ELi1ELi2ELi1E", "ILi4ELi64ELi1ELi1ELi2E")))
-        if hot_one:
-            seen += 1
+        hits = [e for e in expected if e in name]
+        if hits:
+            seen.update(hits)
             assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1)) == 0, (name, "scratch")
             assert int(re.search(r"\.vgpr_spill_count:\s*(\d+)", blk).group(1)) == 0, (name, "spills")
-    assert seen >= 9, seen
+    assert seen == set(expected), sorted(set(expected) - seen)

@@ -96,7 +96,6 @@ ab)    # A/B of nano_amd/lib/libnano_mi355x_prev.so (a build of an earlier commi
       bench ${tag}_new_$r "$@" --steps 32 --warmup 4 --no-kernel-table
     done
   done ;;
-head2l) for r in 1 2 3; do NANO_FUSE_LAUNCHES=11 bench head_two_launches_$r --steps 20 --warmup 5 --no-kernel-table; bench head_default_$r --steps 20 --warmup 5 --no-kernel-table; done ;;
 *) echo "unknown mode $mode";;
 esac
 done
