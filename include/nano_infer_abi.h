@@ -210,6 +210,15 @@ void nano_set_max_batch(uint32_t max_batch);
  * NANO_HIP_E* code (nano_mi355x.h). */
 int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                        float *logits, uint32_t *argmax);
+/* One decode step of `batch` sequences (slot i = sequence i, as nano_forward_batch) sampled with each sequence's
+ * own Sampler: out_ids[i] is the token generate_next_token would return for that sequence's logits.  histories[i] holds the
+ * n_history[i] ids the repetition penalty marks (histories / n_history may be NULL: no history).  Each sampler's coin comes from its
+ * own rng_state, drawn only when its temperature is not 0.  The rows are sampled on the device; rows it declines, and every row under
+ * NANO_HOST_SAMPLER=1, go through the host loops.  With replicas, each replica's share is served by its own batched call, one replica
+ * after another (not concurrently).  Returns 0 or a negative NANO_HIP_E* code. */
+int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                              Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
+                              uint32_t *out_ids);
 /* Replicas of the context's model on the listed further GPUs of the node, in this process: nano_forward_batch then serves
  * sequence i from replica i mod (1 + n_devices) (replica 0 = the context's own device) and the replicas decode their
  * shares concurrently -- independent sequences shard trivially, no collective.  The one-process-per-GPU

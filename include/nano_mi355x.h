@@ -181,6 +181,26 @@ int nano_hip_forward_sample(NanoHipModel *m, uint32_t token, uint32_t pos, const
 int nano_hip_op_sample(NanoHipModel *m, const float *logits, const uint32_t *history, uint32_t n_history,
                        float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out);
 
+/* ---- device-side sampling of a batched step -------------------------------------------------------------
+ * The sampler above over rows: row i gets its own penalty, temperature, top_p, coin and history, and its result equals what
+ * nano_hip_op_sample returns for that row's logits alone, field by field.  The six kernels run once for all rows; temperature-0
+ * rows take the penalised arg-max; a row whose nucleus does not fit the LDS sorter goes through the wide phase (rows one after
+ * another); NANO_SAMPLE_FALLBACK means the same as above (the row's logits: nano_hip_read_state(m, i, 4, ...)).
+ * Each slot keeps its own record of the ids already marked: when row i's history extends slot i's last one only the new ids are
+ * uploaded, otherwise the slot's set starts over.  The scratch (about 1.5 MB per row at V = 151 936, sized to max_batch rows) is
+ * allocated on the first call; NANO_HIP_ENOMEM if it cannot be, and the model stays usable.  batch <= max_batch; histories are
+ * checked as by the single-row calls (null pointers, length <= max_seq_len + 1, ids < V). */
+typedef struct NanoHipSampleParams {
+    float repetition_penalty, temperature, top_p, coin;
+    const uint32_t *history; uint32_t n_history;     /* the ids the penalty marks (reference infer.c:1158-1166) */
+} NanoHipSampleParams;
+/* one decode step of slots 0..batch-1 (as nano_hip_forward), then row i sampled with params[i] into out[i] */
+int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                  const NanoHipSampleParams *params, NanoHipSample *out);
+/* the sampler alone on caller logits [batch][V] (host pointer; operator parity tests) */
+int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, uint32_t batch,
+                             const NanoHipSampleParams *params, NanoHipSample *out);
+
 /* ---- strict-parity / per-phase mode -------------------------------------------------------------------------
  * nano_hip_set_strict(m, 1): every later forward / prefill runs eagerly, one kernel per reference operator, with
  * every float reduction (rmsnorm, q.k, softmax sum, weighted V, FP32 matmul) in the reference's sequential order

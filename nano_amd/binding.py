@@ -81,6 +81,8 @@ def lib() -> C.CDLL:
     fn("nano_hip_lora_enable", C.c_int, [vp, C.c_int])
     fn("nano_hip_forward_sample", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
     fn("nano_hip_op_sample", C.c_int, [vp, f32p, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
+    fn("nano_hip_forward_sample_batch", C.c_int, [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParams), C.POINTER(NanoHipSample)])
+    fn("nano_hip_op_sample_batch", C.c_int, [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParams), C.POINTER(NanoHipSample)])
     fn("nano_hip_sync", C.c_int, [vp])
     fn("nano_hip_set_strict", C.c_int, [vp, C.c_int])
     fn("nano_hip_set_phase_hook", C.c_int, [vp, PHASE_FN, vp])
@@ -152,6 +154,24 @@ class NanoHipSample(C.Structure):
     """Result of the device-side sampler (include/nano_mi355x.h NanoHipSample)."""
     _fields_ = [("token", C.c_uint32), ("status", C.c_uint32), ("n_candidates", C.c_uint32), ("n_sorted", C.c_uint32), ("nucleus", C.c_uint32),
                 ("top", C.c_uint32 * 6), ("sum_bits", C.c_uint32), ("walked_chunks", C.c_uint32)]
+
+
+class NanoHipSampleParams(C.Structure):
+    """One row of the batched device sampler (include/nano_mi355x.h NanoHipSampleParams)."""
+    _fields_ = [("repetition_penalty", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("coin", C.c_float),
+                ("history", C.POINTER(C.c_uint32)), ("n_history", C.c_uint32)]
+
+
+def sample_params(rows):
+    """rows: (repetition_penalty, temperature, top_p, coin, history) per row -> (ctypes array, the history arrays it points into:
+    keep them alive for the call)"""
+    arr = (NanoHipSampleParams * len(rows))()
+    keep = []
+    for i, (rp, temp, top_p, coin, hist) in enumerate(rows):
+        h = np.ascontiguousarray(hist if hist is not None else [], np.uint32).reshape(-1)
+        keep.append(h)
+        arr[i] = NanoHipSampleParams(rp, temp, top_p, coin, h.ctypes.data_as(C.POINTER(C.c_uint32)) if h.size else None, h.size)
+    return arr, keep
 
 
 class DeviceModel:
@@ -232,6 +252,25 @@ class DeviceModel:
         r = NanoHipSample()
         check(lib().nano_hip_op_sample(self.h, l, h, h.size, repetition_penalty, temperature, top_p, coin, C.byref(r)))
         return r
+
+    def forward_sample_batch(self, tokens: Sequence[int], pos: Sequence[int], params) -> list:
+        """One decode step of slots 0..B-1, then row i sampled on the device with params[i] =
+        (repetition_penalty, temperature, top_p, coin, history); one NanoHipSample per row."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        arr, _keep = sample_params(params)
+        out = (NanoHipSample * max(t.size, 1))()
+        check(lib().nano_hip_forward_sample_batch(self.h, t, p, t.size, arr, out))
+        return list(out)[:t.size]
+
+    def op_sample_batch(self, logits: np.ndarray, params) -> list:
+        """The batched device sampler alone, on host logits [B][V]; params as forward_sample_batch."""
+        l = np.ascontiguousarray(logits, np.float32)
+        assert l.ndim == 2 and l.shape[1] == self.vocab
+        arr, _keep = sample_params(params)
+        out = (NanoHipSample * max(l.shape[0], 1))()
+        check(lib().nano_hip_op_sample_batch(self.h, l.reshape(-1), l.shape[0], arr, out))
+        return list(out)[:l.shape[0]]
 
     def lora_attach_file(self, path: str):
         """Attach a LoRA module file (reference format: 256-byte header, rank / alpha = words 6 / 7, then FP32 tensors)."""
@@ -450,6 +489,11 @@ class Engine:
         L.llm_session_free.argtypes = [vp]
         L.nano_forward_batch.restype = C.c_int
         L.nano_forward_batch.argtypes = [vp, u32p, u32p, C.c_uint32, vp, vp]
+        L.nano_forward_batch_sample.restype = C.c_int
+        L.nano_forward_batch_sample.argtypes = [vp, u32p, u32p, C.c_uint32, vp, vp, vp, vp]
+        L.build_sampler.restype = C.POINTER(SamplerC)
+        L.build_sampler.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64]
+        L.free_sampler.argtypes = [C.POINTER(SamplerC)]
         L.nano_set_device(device)
         L.nano_set_max_batch(max_batch)
         self.L = L
@@ -475,6 +519,38 @@ class Engine:
             ids[pos + 1] = self.next_token(ids, pos, 0)
         return ids[:n_prompt + n_decode]
 
+    def build_sampler(self, vocab_size: int, rep_pen: float, temperature: float, top_p: float, seed: int, top_k: int = 0):
+        """A Sampler of the engine (build_sampler); free it with free_sampler.  .contents.rng_state is its generator state."""
+        return self.L.build_sampler(vocab_size, rep_pen, temperature, top_p, top_k, seed)
+
+    def free_sampler(self, s):
+        self.L.free_sampler(s)
+
+    def forward_batch(self, tokens: Sequence[int], pos: Sequence[int], want_logits: bool = True, vocab: int = 0):
+        """nano_forward_batch: one decode step of B sequences; logits [B][vocab] (or arg-max ids)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        logits = np.empty((t.size, vocab), np.float32) if want_logits else None
+        amax = None if want_logits else np.empty(t.size, np.uint32)
+        check(self.L.nano_forward_batch(self.ctx, t, p, t.size, logits.ctypes.data if want_logits else None,
+                                        None if want_logits else amax.ctypes.data))
+        return logits if want_logits else amax
+
+    def forward_batch_sample(self, tokens: Sequence[int], pos: Sequence[int], samplers, histories) -> np.ndarray:
+        """nano_forward_batch_sample: one decode step of B sequences, sequence i sampled with samplers[i] (from build_sampler)
+        over histories[i] (the ids its repetition penalty marks); returns the B sampled ids."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        B = t.size
+        hs = [np.ascontiguousarray(h if h is not None else [], np.uint32).reshape(-1) for h in histories]
+        sp = (C.POINTER(SamplerC) * B)(*samplers)
+        hp = (C.POINTER(C.c_uint32) * B)(*[h.ctypes.data_as(C.POINTER(C.c_uint32)) if h.size else None for h in hs])
+        nh = np.array([h.size for h in hs], np.uint32)
+        out = np.empty(B, np.uint32)
+        check(self.L.nano_forward_batch_sample(self.ctx, t, p, B, C.cast(sp, C.c_void_p), C.cast(hp, C.c_void_p),
+                                               nh.ctypes.data, out.ctypes.data))
+        return out
+
     def run_session(self, prompt: Sequence[int], max_steps: int):
         """nano_session_init_ids + nano_session_step_ids until stop; returns (generated ids, last status)."""
         p = np.ascontiguousarray(prompt, np.uint32)
@@ -490,6 +566,12 @@ class Engine:
                 break
         self.L.llm_session_free(s)
         return out, status
+
+
+class SamplerC(C.Structure):
+    """Sampler (include/nano_infer_abi.h = reference infer/infer.h)."""
+    _fields_ = [("vocab_size", C.c_int), ("probindex", C.c_void_p), ("repetition_penalty", C.c_float), ("temperature", C.c_float),
+                ("top_p", C.c_float), ("top_k", C.c_uint32), ("rng_state", C.c_uint64)]
 
 
 class NanoSession(C.Structure):

@@ -64,6 +64,18 @@ struct SamplerState {
     std::vector<uint32_t> applied;                        // ids already marked in `seen`, in history order
 };
 
+// the sampler over rows (nano_hip_forward_sample_batch): max_batch rows of scratch at a fixed stride, created on first use
+struct SamplerRowsState {
+    uint8_t *block = nullptr;                             // [maxB] rows (y, e, seen, approx, spec, fn, cells, pmax, bins, cand) + params + results + ids
+    SampleRows b{};
+    SampleRowParams *params = nullptr, *h_params = nullptr;
+    NanoHipSample *h_res = nullptr;
+    uint32_t *ids = nullptr, *h_ids = nullptr; size_t ids_cap = 0;     // new history ids of all rows, as byte offsets from row 0's seen plane
+    uint8_t *wide = nullptr; void *wide_temp = nullptr; size_t wide_temp_bytes = 0;      // second phase, shared by the rows one after another
+    SampleArgs wide_a{};                                  // its buffers
+    std::vector<std::vector<uint32_t>> applied;           // per slot: ids already marked in that row's `seen`, in history order
+};
+
 struct NanoHipModel {
     NanoModelDesc d{};
     int device = 0, cus = 0;
@@ -114,6 +126,7 @@ struct NanoHipModel {
     uint32_t last_dev_err = 0;                            // the code bits of the last give-up (diagnostics)
     std::vector<uint32_t> fw_tokens, fw_pos; uint32_t fw_causal = 0; int fw_logits = 0, fw_argmax = 0;   // the step queued by nano_hip_forward_begin (for its re-issue)
     struct SamplerState *smp = nullptr;                   // device-side sampler scratch, created on first use
+    struct SamplerRowsState *smpr = nullptr;              // ... of the batched sampler (max_batch rows), created on first use
     uint32_t rope_rows = 0;       // rows of the RoPE tables on the device: positions >= rope_rows are rejected
     uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
     bool kv_half = false;         // opt-in FP16 KV cache: rows hold __half, v passes through vraw like k through kraw
@@ -197,6 +210,14 @@ static int peek(void *host_dst, const uint8_t *src, size_t bytes, int src_on_dev
     return 0;
 }
 
+static void sampler_rows_free(SamplerRowsState *sr) {
+    if (!sr) return;
+    if (sr->block) (void)hipFree(sr->block);
+    if (sr->wide) (void)hipFree(sr->wide);
+    if (sr->h_params) (void)hipHostFree(sr->h_params);       // (one pinned block: params, results, ids)
+    delete sr;
+}
+
 static void destroy(NanoHipModel *m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
@@ -218,6 +239,7 @@ static void destroy(NanoHipModel *m) {
         if (m->smp->h_res) (void)hipHostFree(m->smp->h_res);
         delete m->smp;
     }
+    sampler_rows_free(m->smpr);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     if (m->ev2) (void)hipEventDestroy(m->ev2);
@@ -1222,6 +1244,176 @@ extern "C" int nano_hip_op_sample(NanoHipModel *m, const float *logits, const ui
     memcpy(m->h_logits, logits, V * 4);
     HIP_TRY(hipMemcpyAsync(m->logits, m->h_logits, V * 4, hipMemcpyHostToDevice, m->st));
     const int rc2 = sample_run(m, m->logits, history, n_history, repetition_penalty, temperature, top_p, coin, out);
+    return rc2 == SAMPLE_RC_CHECK ? dev_err_check(m) : rc2;
+}
+
+// ---- the sampler over rows: slots 0 .. batch-1 of one decode step, each with its own parameters and history --------------------
+// Every row has the single-row sampler's scratch at a fixed stride (about 1.5 MB at V = 151 936); the six kernels run once for all rows
+// (sampler.hip launch_sample_rows).  Rows at temperature 0 take the penalised arg-max over their `y` row; rows whose nucleus does not
+// fit the LDS sorter go through the wide phase one after another, on one shared scratch.
+static int sampler_rows_init(NanoHipModel *m) {
+    if (m->smpr) return 0;
+    const uint32_t V = m->d.vocab_size, R = m->maxB;
+    const uint32_t nch = (((V + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK) + 3u) & ~3u;
+    if (nch > SAMPLE_MAX_CHUNKS) FAIL(NANO_HIP_EINVAL, "vocabulary %u too large for the device sampler (max %u)", V, SAMPLE_MAX_CHUNKS * SAMPLE_CHUNK);
+    const size_t npad = (size_t)nch * SAMPLE_CHUNK;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_y = take(npad * 4), o_e = take(npad * 4), o_seen = take(npad), o_approx = take(nch * 4), o_spec = take(nch * 4),
+                 o_fn = take(nch * 8), o_cells = take(256), o_pmax = take(nch), o_bins = take(SAMPLE_BINS * 12), o_cand = take((size_t)SAMPLE_MAX_CANDIDATES * 8);
+    const size_t rstride = off;
+    // the seen_set kernel marks byte offsets from row 0's seen plane: every row's plane must lie below 4 GiB of it
+    if ((uint64_t)rstride * R >= (1ull << 32)) FAIL(NANO_HIP_EINVAL, "batched sampler scratch of %u rows exceeds 4 GiB", R);
+    off = rstride * R;
+    const size_t ids_cap = (size_t)R * (m->S + 1);
+    const size_t o_params = take((size_t)R * sizeof(SampleRowParams)), o_res = take((size_t)R * sizeof(NanoHipSample)), o_ids = take(ids_cap * 4);
+    const size_t h_params = 0, h_res = align_up((size_t)R * sizeof(SampleRowParams), 256), h_ids = h_res + align_up((size_t)R * sizeof(NanoHipSample), 256);
+    SamplerRowsState *sr = new SamplerRowsState();
+    uint8_t *hb = nullptr;
+    if (hipMalloc(&sr->block, off) != hipSuccess || hipMemset(sr->block, 0, off) != hipSuccess ||
+        hipHostMalloc((void **)&hb, h_ids + ids_cap * 4) != hipSuccess) {
+        sr->h_params = (SampleRowParams *)hb;
+        sampler_rows_free(sr);
+        (void)hipGetLastError();                                            // (the model stays usable)
+        FAIL(NANO_HIP_ENOMEM, "batched sampler scratch allocation failed (%zu bytes for %u rows)", off, R);
+    }
+    uint8_t *b = sr->block;
+    SampleArgs &a = sr->b.a;
+    a.V = V; a.nch = nch;
+    a.y = (float *)(b + o_y); a.e = (float *)(b + o_e); a.seen = b + o_seen;
+    a.approx = (float *)(b + o_approx); a.spec = (uint32_t *)(b + o_spec); a.fn = (uint2 *)(b + o_fn);
+    uint32_t *cells = (uint32_t *)(b + o_cells);
+    a.ncand = cells + 1; a.sum = (float *)(cells + 2); a.ndrop = cells + 3; a.dropmax = cells + 4; a.bstar = cells + 5;
+    a.pmax = (float *)(b + o_pmax);
+    a.bin_mass = (unsigned long long *)(b + o_bins); a.bin_cnt = (uint32_t *)(b + o_bins + SAMPLE_BINS * 8);
+    a.cand = (unsigned long long *)(b + o_cand); a.cap = SAMPLE_MAX_CANDIDATES; a.res = (NanoHipSample *)(b + o_res);
+    sr->b.rstride = rstride; sr->b.lstride = V;
+    sr->params = (SampleRowParams *)(b + o_params); sr->b.rp = sr->params;
+    sr->ids = (uint32_t *)(b + o_ids); sr->ids_cap = ids_cap;
+    sr->h_params = (SampleRowParams *)(hb + h_params); sr->h_res = (NanoHipSample *)(hb + h_res); sr->h_ids = (uint32_t *)(hb + h_ids);
+    sr->applied.assign(R, {});
+    m->smpr = sr;
+    return 0;
+}
+
+// the checks of the single-row entry points, for every row (before anything is queued)
+static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampleParams *params, const NanoHipSample *out) {
+    if (!m || !params || !out) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH) FAIL(NANO_HIP_EINVAL, "batch %u out of range (max_batch %u)", batch, m->maxB);
+    const uint32_t V = m->d.vocab_size;
+    for (uint32_t i = 0; i < batch; i++) {
+        const NanoHipSampleParams &p = params[i];
+        if (p.n_history && !p.history) FAIL(NANO_HIP_EINVAL, "null history of row %u", i);
+        if (p.repetition_penalty == 1.0f) continue;                        // (the history is not read)
+        if (p.n_history > m->S + 1) FAIL(NANO_HIP_EINVAL, "history of %u ids of row %u exceeds max_seq_len + 1", p.n_history, i);
+        for (uint32_t k = 0; k < p.n_history; k++) if (p.history[k] >= V) FAIL(NANO_HIP_EINVAL, "history id %u of row %u out of vocabulary", p.history[k], i);
+    }
+    return 0;
+}
+
+// queue the rows' sampler behind whatever produced logits[batch][V] (device) on the model's stream, wait, fill out[batch].  Returns
+// SAMPLE_RC_CHECK on every exit that synchronised the stream (as sample_run).
+static int sample_rows_run(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+    SamplerRowsState *sr = m->smpr;
+    SampleRows b = sr->b;
+    b.a.logits = logits;
+    const uint32_t V = b.a.V;
+    const size_t npad = (size_t)b.a.nch * SAMPLE_CHUNK;
+    bool any_softmax = false, any_argmax = false;
+    // the seen sets: per slot, start over when the history is not an extension of what the slot holds; all rows' new ids in one copy
+    size_t n_ids = 0;
+    for (uint32_t i = 0; i < batch; i++) {
+        const NanoHipSampleParams &p = params[i];
+        SampleRowParams &q = sr->h_params[i];
+        q.penalty = p.repetition_penalty; q.temperature = p.temperature; q.top_p = p.top_p; q.coin = p.coin;
+        q.cutoff = (1.0f - p.top_p) / (float)((int)V - 1);                  // (1.0f - top_p) / (n - 1), infer.c:1064
+        (p.temperature == 0.0f ? any_argmax : any_softmax) = true;
+        if (p.repetition_penalty == 1.0f) continue;                        // x / 1.0f is exact: no set needed
+        std::vector<uint32_t> &ap = sr->applied[i];
+        if (ap.size() > p.n_history || memcmp(ap.data(), p.history, ap.size() * 4) != 0) {
+            HIP_TRY(hipMemsetAsync(const_cast<uint8_t *>(b.a.seen) + (size_t)i * b.rstride, 0, npad, m->st));
+            ap.clear();
+        }
+        for (uint32_t k = (uint32_t)ap.size(); k < p.n_history; k++) sr->h_ids[n_ids++] = (uint32_t)((uint64_t)i * b.rstride + p.history[k]);
+        ap.insert(ap.end(), p.history + ap.size(), p.history + p.n_history);
+    }
+    if (n_ids) {
+        HIP_TRY(hipMemcpyAsync(sr->ids, sr->h_ids, n_ids * 4, hipMemcpyHostToDevice, m->st));
+        HIP_TRY(launch_seen_set(sr->ids, (uint32_t)n_ids, const_cast<uint8_t *>(b.a.seen), m->st));
+    }
+    HIP_TRY(hipMemcpyAsync(sr->params, sr->h_params, batch * sizeof(SampleRowParams), hipMemcpyHostToDevice, m->st));
+    HIP_TRY(launch_sample_rows(b, batch, any_softmax, m->st));
+    if (any_argmax) {                                                      // penalised arg-max (infer.c:1169-1171) over every row's y
+        ArgmaxArgs aa{ b.a.y, V, (uint32_t)(b.rstride / 4), m->amax, nullptr, m->pos, nullptr, m->pos0, batch, nullptr, 0 };
+        HIP_TRY(launch_argmax(aa, batch, m->st));
+        HIP_TRY(hipMemcpyAsync(m->h_amax, m->amax, batch * 4, hipMemcpyDeviceToHost, m->st));
+    }
+    if (any_softmax) HIP_TRY(hipMemcpyAsync(sr->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipStreamSynchronize(m->st));
+    // nuclei beyond the LDS sorter: the wide phase (sampler_wide.hip) on that row's numerators and denominator, one row after another
+    bool wide_ran = false;
+    for (uint32_t i = 0; i < batch && any_softmax; i++) {
+        if (params[i].temperature == 0.0f || sr->h_res[i].status != NANO_SAMPLE_FALLBACK || sr->h_res[i].n_candidates == 0) continue;
+        if (!sr->wide) {
+            sr->wide_temp_bytes = sample_wide_temp_bytes((uint32_t)npad);
+            const size_t tb = (sr->wide_temp_bytes + 255) & ~(size_t)255;
+            if (!sr->wide_temp_bytes || hipMalloc(&sr->wide, npad * 20 + tb) != hipSuccess) { sr->wide = nullptr; (void)hipGetLastError(); break; }   // (the caller's host loops)
+            sr->wide_a.wide_in = (unsigned long long *)sr->wide; sr->wide_a.wide_out = sr->wide_a.wide_in + npad;
+            sr->wide_a.wide_p = (float *)(sr->wide_a.wide_out + npad); sr->wide_a.wide_cap = (uint32_t)npad;
+            sr->wide_temp = sr->wide + npad * 20;
+        }
+        SampleArgs a = sample_row(b, i, sr->h_params[i]);
+        a.wide_in = sr->wide_a.wide_in; a.wide_out = sr->wide_a.wide_out; a.wide_p = sr->wide_a.wide_p; a.wide_cap = sr->wide_a.wide_cap;
+        HIP_TRY(launch_sample_wide(a, sr->wide_temp, sr->wide_temp_bytes, m->st));
+        wide_ran = true;
+    }
+    if (wide_ran) {
+        HIP_TRY(hipMemcpyAsync(sr->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
+        HIP_TRY(hipStreamSynchronize(m->st));
+    }
+    for (uint32_t i = 0; i < batch; i++) {
+        if (params[i].temperature == 0.0f) { memset(&out[i], 0, sizeof out[i]); out[i].token = m->h_amax[i]; out[i].status = NANO_SAMPLE_OK; }
+        else out[i] = sr->h_res[i];
+    }
+    return SAMPLE_RC_CHECK;
+}
+
+extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                             const NanoHipSampleParams *params, NanoHipSample *out) {
+    int rc;
+    if ((rc = check_sample_rows(m, batch, params, out))) return rc;
+    if ((rc = check_batch(m, tokens, pos, batch, 0))) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((rc = sampler_rows_init(m))) return rc;
+    if ((rc = kv_ensure_batch(m, pos, batch, 0, false))) return rc;
+    memcpy(m->h_tokens, tokens, batch * 4); memcpy(m->h_pos, pos, batch * 4);
+    uint32_t max_pos = 0;
+    for (uint32_t i = 0; i < batch; i++) if (pos[i] > max_pos) max_pos = pos[i];
+    HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, batch * 4, hipMemcpyHostToDevice, m->st));
+    HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
+    for (int attempt = 0;; attempt++) {
+        if ((rc = run_step(m, batch, 1u, MODE_LOGITS, max_pos))) return rc;
+        rc = sample_rows_run(m, m->logits, batch, params, out);
+        if (rc != SAMPLE_RC_CHECK) return rc;
+        const uint32_t code = dev_err_take(m);
+        if (!code) return 0;
+        if (attempt || !handoff_recoverable(m, code)) return dev_err_fail(code);
+        handoff_fallback(m);                                                // the same step again, through the plain launches
+        HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, batch * 4, hipMemcpyHostToDevice, m->st));
+        HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
+    }
+}
+
+extern "C" int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+    int rc;
+    if ((rc = check_sample_rows(m, batch, params, out))) return rc;
+    if (!logits) FAIL(NANO_HIP_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(m->device));
+    if ((rc = sampler_rows_init(m))) return rc;
+    const size_t V = m->d.vocab_size;
+    memcpy(m->h_logits, logits, batch * V * 4);
+    HIP_TRY(hipMemcpyAsync(m->logits, m->h_logits, batch * V * 4, hipMemcpyHostToDevice, m->st));
+    const int rc2 = sample_rows_run(m, m->logits, batch, params, out);
     return rc2 == SAMPLE_RC_CHECK ? dev_err_check(m) : rc2;
 }
 

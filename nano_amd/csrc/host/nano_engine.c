@@ -623,6 +623,63 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
     return host_sample(ctx, sp, logits, output_ids, pos, coin);
 }
 
+/* One decode step of `batch` sequences sampled with each sequence's own Sampler (include/nano_infer_abi.h).  The rows are sampled on
+ * the device (nano_hip_forward_sample_batch); a row the device declines goes through the host loops on that slot's logits, and
+ * NANO_HOST_SAMPLER=1 sends every row there.  With replicas, each replica's share (sequence i -> replica i mod G, slot i / G, as
+ * nano_forward_batch) is served by its own batched call, one replica after another. */
+int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                              Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history, uint32_t *out_ids) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || !tokens || !pos || !samplers || !out_ids || batch == 0) return NANO_HIP_EINVAL;
+    const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
+    if (batch > NANO_MAX_BATCH * G) return NANO_HIP_EINVAL;
+    for (uint32_t i = 0; i < batch; i++) if (!samplers[i] || (n_history && n_history[i] && (!histories || !histories[i]))) return NANO_HIP_EINVAL;
+    if (g_host_sampler < 0) { const char *e = getenv("NANO_HOST_SAMPLER"); g_host_sampler = (e && *e && *e != '0') ? 1 : 0; }
+    const int V = ctx->llm->config.vocab_size;
+    /* the coin of each sequence, drawn exactly when generate_next_token draws it (only on the softmax branch, infer.c:1181) */
+    float coin[NANO_MAX_BATCH * NANO_MAX_REPLICAS];
+    for (uint32_t i = 0; i < batch; i++) coin[i] = samplers[i]->temperature != 0.0f ? xorshift_f32(&samplers[i]->rng_state) : 0.0f;
+    float *lbuf = (float *)malloc((size_t)NANO_MAX_BATCH * V * sizeof(float));
+    if (!lbuf) return NANO_HIP_ENOMEM;
+    int rc = NANO_HIP_OK;
+    for (uint32_t r = 0; r < G && rc == NANO_HIP_OK; r++) {
+        NanoHipModel *dev = G > 1 ? me->replica[r] : me->dev;
+        uint32_t tk[NANO_MAX_BATCH], ps[NANO_MAX_BATCH], idx[NANO_MAX_BATCH], n = 0;
+        for (uint32_t i = r; i < batch; i += G) {
+            if (n >= NANO_MAX_BATCH) { rc = NANO_HIP_EINVAL; break; }
+            tk[n] = tokens[i]; ps[n] = pos[i]; idx[n++] = i;
+        }
+        if (rc != NANO_HIP_OK || n == 0) continue;
+        lora_select(dev, ctx->lora);
+        if (g_host_sampler) {
+            if ((rc = nano_hip_forward(dev, tk, ps, n, 1, lbuf, NULL)) != NANO_HIP_OK) break;
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t i = idx[k];
+                out_ids[i] = host_sample(NULL, samplers[i], lbuf + (size_t)k * V, histories ? histories[i] : NULL, n_history ? n_history[i] : 0, coin[i]);
+            }
+            continue;
+        }
+        NanoHipSampleParams prm[NANO_MAX_BATCH];
+        NanoHipSample res[NANO_MAX_BATCH];
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t i = idx[k];
+            const Sampler *sp = samplers[i];
+            prm[k].repetition_penalty = sp->repetition_penalty; prm[k].temperature = sp->temperature; prm[k].top_p = sp->top_p; prm[k].coin = coin[i];
+            prm[k].history = histories ? histories[i] : NULL; prm[k].n_history = n_history ? n_history[i] : 0;
+        }
+        if ((rc = nano_hip_forward_sample_batch(dev, tk, ps, n, prm, res)) != NANO_HIP_OK) break;
+        for (uint32_t k = 0; k < n && rc == NANO_HIP_OK; k++) {
+            const uint32_t i = idx[k];
+            if (res[k].status == NANO_SAMPLE_OK) { out_ids[i] = res[k].token; continue; }
+            /* the device declined this row (no candidate, or no memory for the wide phase): host loops on the slot's logits */
+            if ((rc = nano_hip_read_state(dev, k, 4, 0, 0, lbuf, (size_t)V)) != NANO_HIP_OK) break;
+            out_ids[i] = host_sample(NULL, samplers[i], lbuf, prm[k].history, prm[k].n_history, coin[i]);
+        }
+    }
+    free(lbuf);
+    return rc;
+}
+
 /* =====================================================================================================
  * sessions (reference infer/infer.c:1196-1361)
  * =================================================================================================== */

@@ -313,6 +313,32 @@ struct SampleArgs {
     // second phase, wide nuclei (sampler_wide.hip): every candidate as a key, the sorted keys, the sorted probabilities
     unsigned long long *wide_in, *wide_out; float *wide_p; uint32_t wide_cap;
 };
+// Several rows at once (nano_hip_forward_sample_batch): `a` is row 0's view -- its scratch pointers (y, e, seen, pmax, cells, bins,
+// approx, spec, fn, cand) are row 0's, and row r's lie `rstride` bytes further per row; row r's logits are `lstride` floats further,
+// its result is res[r], its parameters rp[r].  The wide-phase pointers of `a` are not used.
+struct SampleRowParams { float penalty, temperature, top_p, cutoff, coin; };
+struct SampleRows {
+    SampleArgs a;
+    const SampleRowParams *rp;
+    uint64_t rstride;
+    uint32_t lstride, _pad;
+};
+// row r's single-row view (device: the kernels; host: the wide phase of one row); the seen plane only when the penalty is not 1
+__host__ __device__ inline SampleArgs sample_row(const SampleRows &b, uint32_t r, const SampleRowParams &p) {
+    SampleArgs a = b.a;
+    const uint64_t o = (uint64_t)r * b.rstride;
+    auto mv = [o](auto *ptr) { return reinterpret_cast<decltype(ptr)>(reinterpret_cast<uintptr_t>(ptr) + o); };
+    a.logits = b.a.logits + (size_t)r * b.lstride;
+    a.y = mv(a.y); a.e = mv(a.e); a.pmax = mv(a.pmax);
+    a.ncand = mv(a.ncand); a.ndrop = mv(a.ndrop); a.dropmax = mv(a.dropmax); a.bstar = mv(a.bstar); a.sum = mv(a.sum);
+    a.bin_cnt = mv(a.bin_cnt); a.bin_mass = mv(a.bin_mass);
+    a.approx = mv(a.approx); a.spec = mv(a.spec); a.fn = mv(a.fn); a.cand = mv(a.cand);
+    a.seen = p.penalty != 1.0f ? mv(b.a.seen) : nullptr;
+    a.res = b.a.res + r;
+    a.penalty = p.penalty; a.temperature = p.temperature; a.top_p = p.top_p; a.cutoff = p.cutoff; a.coin = p.coin;
+    return a;
+}
+hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st);
 hipError_t launch_seen_set(const uint32_t *ids, uint32_t n, uint8_t *seen, hipStream_t st);
 hipError_t launch_sample_prep(const SampleArgs &a, hipStream_t st);   // penalty (and temperature) only
 hipError_t launch_sample(const SampleArgs &a, hipStream_t st);

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void seen_set_kernel(const uint32_t *ids, uint
 }
 
 // K1: y = (seen ? l / penalty : l) / temperature over the padded range (padding = -inf -> numerator 0), one max per workgroup
-__global__ __launch_bounds__(256) void samp_prep_kernel(const SampleArgs a) {
+__device__ __forceinline__ void samp_prep(const SampleArgs &a) {
     const uint32_t i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     float v[4];
     float mx = -INFINITY;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void samp_prep_kernel(const SampleArgs a) {
 }
 
 // K2: numerators e = expf(y - max) and one approximate float sum per chunk (used only to guess each chunk's binade)
-__global__ __launch_bounds__(256) void samp_exp_kernel(const SampleArgs a) {
+__device__ __forceinline__ void samp_exp(const SampleArgs &a) {
     const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= a.nch) return;
     float m = -INFINITY;                                           // max over the nch/4 workgroup maxima of K1 (<= 256)
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void samp_exp_kernel(const SampleArgs a) {
 }
 
 // K3: the chunk function of every chunk, for the binade its approximate prefix falls in
-__global__ __launch_bounds__(256) void samp_chunkfn_kernel(const SampleArgs a) {
+__device__ __forceinline__ void samp_chunkfn(const SampleArgs &a) {
     const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= a.nch) return;
     float pre = 0.0f;
@@ -161,7 +161,7 @@ __device__ __forceinline__ void wave_scan_fn(ChunkFn &f, uint32_t &valid) {
     scan_step<0x143, 0xC>(f, valid);          // row_bcast:31 -> rows 2, 3
 }
 
-__global__ __launch_bounds__(64) void samp_propagate_kernel(const SampleArgs a) {
+__device__ __forceinline__ void samp_propagate(const SampleArgs &a) {
     __shared__ uint32_t s_dE[SAMPLE_MAX_CHUNKS + 64], s_dO[SAMPLE_MAX_CHUNKS + 64], s_spec[SAMPLE_MAX_CHUNKS + 64];
     const uint32_t lane = threadIdx.x;
     for (uint32_t c = lane; c < a.nch + 64; c += 64) {
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64) void samp_propagate_kernel(const SampleArgs a) 
 // reference's order (probability descending, then index ascending — glibc's qsort is a stable merge sort).
 // Candidates in bins after `bstar` (chosen by the propagate kernel) are only counted, and their largest probability
 // recorded for the check in the pick kernel.
-__global__ __launch_bounds__(256) void samp_filter_kernel(const SampleArgs a) {
+__device__ __forceinline__ void samp_filter(const SampleArgs &a) {
     const uint32_t i0 = (blockIdx.x * 256 + threadIdx.x) * 4, lane = threadIdx.x & 63;
     const float sum = a.sum[0];
     const uint32_t bstar = *a.bstar;
@@ -254,8 +254,7 @@ __global__ __launch_bounds__(256) void samp_filter_kernel(const SampleArgs a) {
 }
 
 // K6: sort the candidates, cut the nucleus, draw.  Also re-arms the two cells the next call's K1/K5 accumulate into.
-__global__ __launch_bounds__(1024) void samp_pick_kernel(const SampleArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long pick_lds[];     // keys [SAMPLE_MAX_CANDIDATES] + four scalars
+__device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long long *pick_lds) {     // keys [SAMPLE_MAX_CANDIDATES] + four scalars
     unsigned long long *key = pick_lds;
     float *s_rp = reinterpret_cast<float *>(pick_lds + SAMPLE_MAX_CANDIDATES);
     uint32_t *s_u = reinterpret_cast<uint32_t *>(s_rp + 1);
@@ -341,6 +340,43 @@ __global__ __launch_bounds__(1024) void samp_pick_kernel(const SampleArgs a) {
     a.res->status = NANO_SAMPLE_OK;
     a.res->nucleus = s_last + 1;
     for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < n0 ? 0xffffffffu - (uint32_t)key[i] : 0u;
+}
+
+// One row (nano_hip_forward_sample, nano_hip_op_sample, the wide phase's chunk functions): the kernels as they always were.
+__global__ __launch_bounds__(256) void samp_prep_kernel(const SampleArgs a) { samp_prep(a); }
+__global__ __launch_bounds__(256) void samp_exp_kernel(const SampleArgs a) { samp_exp(a); }
+__global__ __launch_bounds__(256) void samp_chunkfn_kernel(const SampleArgs a) { samp_chunkfn(a); }
+__global__ __launch_bounds__(64) void samp_propagate_kernel(const SampleArgs a) { samp_propagate(a); }
+__global__ __launch_bounds__(256) void samp_filter_kernel(const SampleArgs a) { samp_filter(a); }
+__global__ __launch_bounds__(1024) void samp_pick_kernel(const SampleArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long pick_lds[];
+    samp_pick(a, pick_lds);
+}
+
+// Rows (nano_hip_forward_sample_batch): the same bodies on row `r`'s view (kernels.h sample_row).  The chunk-parallel kernels take
+// the row from blockIdx.y, the one-workgroup kernels from blockIdx.x; a workgroup never spans two rows, so every early exit
+// (temperature 0: no softmax for that row) stays workgroup-uniform.
+__global__ __launch_bounds__(256) void samp_prep_rows_kernel(const SampleRows b) { samp_prep(sample_row(b, blockIdx.y, b.rp[blockIdx.y])); }
+__global__ __launch_bounds__(256) void samp_exp_rows_kernel(const SampleRows b) {
+    const SampleRowParams p = b.rp[blockIdx.y];
+    if (p.temperature != 0.0f) samp_exp(sample_row(b, blockIdx.y, p));
+}
+__global__ __launch_bounds__(256) void samp_chunkfn_rows_kernel(const SampleRows b) {
+    const SampleRowParams p = b.rp[blockIdx.y];
+    if (p.temperature != 0.0f) samp_chunkfn(sample_row(b, blockIdx.y, p));
+}
+__global__ __launch_bounds__(64) void samp_propagate_rows_kernel(const SampleRows b) {
+    const SampleRowParams p = b.rp[blockIdx.x];
+    if (p.temperature != 0.0f) samp_propagate(sample_row(b, blockIdx.x, p));
+}
+__global__ __launch_bounds__(256) void samp_filter_rows_kernel(const SampleRows b) {
+    const SampleRowParams p = b.rp[blockIdx.y];
+    if (p.temperature != 0.0f) samp_filter(sample_row(b, blockIdx.y, p));
+}
+__global__ __launch_bounds__(1024) void samp_pick_rows_kernel(const SampleRows b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long pick_lds[];
+    const SampleRowParams p = b.rp[blockIdx.x];
+    if (p.temperature != 0.0f) samp_pick(sample_row(b, blockIdx.x, p), pick_lds);
 }
 
 // ---- wide nuclei (second phase, sampler_wide.hip): the cut and the draw over ALL candidates, sorted by a device radix sort ---------------
@@ -513,6 +549,30 @@ hipError_t launch_sample(const SampleArgs &a, hipStream_t st) {
         if (dev >= 0 && dev < 64) armed.fetch_or(1ull << dev, std::memory_order_release);
     }
     hipLaunchKernelGGL(samp_pick_kernel, dim3(1), dim3(1024), pick_lds_bytes, st, a);
+    return hipGetLastError();
+}
+
+// Rows 0 .. rows-1 of `b`.  prep runs for every row (a temperature-0 row's arg-max reads its `y`); the softmax kernels only when some row
+// samples (`softmax`), and skip the temperature-0 rows themselves.  Pick holds 64 KB + 64 B of LDS: two of its workgroups per CU
+// (160 KB), so 64 rows are one wave of workgroups on the 256 CUs; the chunk-parallel kernels are rows x (nch / 4) workgroups of 256.
+hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st) {
+    const SampleArgs &a = b.a;
+    if (rows == 0) return hipSuccess;
+    const uint32_t wgs = a.nch * CH / 1024;
+    hipLaunchKernelGGL(samp_prep_rows_kernel, dim3(wgs, rows), dim3(256), 0, st, b);
+    if (!softmax) return hipGetLastError();
+    hipLaunchKernelGGL(samp_exp_rows_kernel, dim3(a.nch / 4, rows), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(samp_chunkfn_rows_kernel, dim3(a.nch / 4, rows), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(samp_propagate_rows_kernel, dim3(rows), dim3(64), 0, st, b);
+    hipLaunchKernelGGL(samp_filter_rows_kernel, dim3(wgs, rows), dim3(256), 0, st, b);
+    constexpr size_t pick_lds_bytes = (size_t)SAMPLE_MAX_CANDIDATES * 8 + 64;
+    static std::atomic<unsigned long long> armed{0};
+    int dev = 0; (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !((armed.load(std::memory_order_acquire) >> dev) & 1ull)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(samp_pick_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pick_lds_bytes);
+        if (dev >= 0 && dev < 64) armed.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(samp_pick_rows_kernel, dim3(rows), dim3(1024), pick_lds_bytes, st, b);
     return hipGetLastError();
 }
 
