@@ -182,14 +182,17 @@ int nano_hip_op_sample(NanoHipModel *m, const float *logits, const uint32_t *his
                        float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out);
 
 /* ---- device-side sampling of a batched step -------------------------------------------------------------
- * The sampler above over rows: row i gets its own penalty, temperature, top_p, coin and history, and its result equals what
- * nano_hip_op_sample returns for that row's logits alone, field by field.  The six kernels run once for all rows; temperature-0
- * rows take the penalised arg-max; a row whose nucleus does not fit the LDS sorter goes through the wide phase (rows one after
- * another); NANO_SAMPLE_FALLBACK means the same as above (the row's logits: nano_hip_read_state(m, i, 4, ...)).
- * Each slot keeps its own record of the ids already marked: when row i's history extends slot i's last one only the new ids are
- * uploaded, otherwise the slot's set starts over.  The scratch (about 1.5 MB per row at V = 151 936, sized to max_batch rows) is
- * allocated on the first call; NANO_HIP_ENOMEM if it cannot be, and the model stays usable.  batch <= max_batch; histories are
- * checked as by the single-row calls (null pointers, length <= max_seq_len + 1, ids < V). */
+ * The sampler above over rows; the one-row calls above are a batch of one (slot 0).  Row i gets its own penalty, temperature,
+ * top_p, coin and history, and its result equals what a batch of that row alone returns for its logits, field by field.  The six
+ * kernels run once for all rows; temperature-0 rows take the penalised arg-max; a row whose nucleus does not fit the LDS sorter goes
+ * through the wide phase (rows one after another); NANO_SAMPLE_FALLBACK means the same as above (the row's logits:
+ * nano_hip_read_state(m, i, 4, ...)).
+ * Each slot keeps its own record of the ids already marked (slot 0's serves one-row and batched calls alike): when row i's history
+ * extends slot i's last one only the new ids are uploaded, otherwise the slot's set starts over.  The scratch, about 1.5 MB per row
+ * at V = 151 936, is sized to max_batch rows and allocated on the first sampled call of any kind, one-row calls included: small next
+ * to one sequence's KV cache, and one row for a model opened with max_batch = 1 (the engine's default).  NANO_HIP_ENOMEM if it
+ * cannot be allocated, and the model stays usable.  batch <= max_batch; every row's history is checked before anything is queued
+ * (null pointers, length <= max_seq_len + 1, ids < V). */
 typedef struct NanoHipSampleParams {
     float repetition_penalty, temperature, top_p, coin;
     const uint32_t *history; uint32_t n_history;     /* the ids the penalty marks (reference infer.c:1158-1166) */

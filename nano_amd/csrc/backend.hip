@@ -53,27 +53,20 @@ constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs k
 
 struct TensorRef { const void *w = nullptr; const float *s = nullptr; };
 
-// device-side sampler (sampler.hip): one device block + pinned staging + the host's record of the `seen` set
-struct SamplerState {
-    uint8_t *block = nullptr;
-    SampleArgs a{};
-    uint8_t *seen = nullptr;
-    uint32_t *hist = nullptr, hist_cap = 0;
-    uint32_t *h_hist = nullptr; NanoHipSample *h_res = nullptr;
-    uint8_t *wide = nullptr; void *wide_temp = nullptr; size_t wide_temp_bytes = 0;      // second phase (wide nuclei), allocated on first need
-    std::vector<uint32_t> applied;                        // ids already marked in `seen`, in history order
-};
-
-// the sampler over rows (nano_hip_forward_sample_batch): max_batch rows of scratch at a fixed stride, created on first use
-struct SamplerRowsState {
-    uint8_t *block = nullptr;                             // [maxB] rows (y, e, seen, approx, spec, fn, cells, pmax, bins, cand) + params + results + ids
+// device-side sampler (sampler.hip): max_batch rows of scratch at a fixed stride + pinned staging + the host's record of every
+// row's `seen` set, created on first use
+struct Sampler {
+    uint8_t *block = nullptr;                             // [maxB] rows (y, e, seen, approx, spec, fn, cells, pmax, bins, cand) + results + params|ids
     SampleRows b{};
-    SampleRowParams *params = nullptr, *h_params = nullptr;
+    SampleRowParams *params = nullptr, *h_params = nullptr;   // the rows' parameters, then their new history ids (byte offsets from
+                                                              // row 0's seen plane): one upload per call
     NanoHipSample *h_res = nullptr;
-    uint32_t *ids = nullptr, *h_ids = nullptr; size_t ids_cap = 0;     // new history ids of all rows, as byte offsets from row 0's seen plane
     uint8_t *wide = nullptr; void *wide_temp = nullptr; size_t wide_temp_bytes = 0;      // second phase, shared by the rows one after another
     SampleArgs wide_a{};                                  // its buffers
-    std::vector<std::vector<uint32_t>> applied;           // per slot: ids already marked in that row's `seen`, in history order
+    // per slot: ids already marked in that row's `seen`, in history order.  A one-row call is slot 0 of a batch of one, so slot 0's
+    // record serves one-row and batched calls alike; that is sound because a record is only used as a prefix of the incoming history
+    // (anything else starts the set over), whichever call wrote it.
+    std::vector<std::vector<uint32_t>> applied;
 };
 
 struct NanoHipModel {
@@ -125,8 +118,7 @@ struct NanoHipModel {
     bool reissue = true;                                  // (nano_hip_debug_fault bit 1 clears it: the give-up then surfaces as NANO_HIP_ERUNTIME)
     uint32_t last_dev_err = 0;                            // the code bits of the last give-up (diagnostics)
     std::vector<uint32_t> fw_tokens, fw_pos; uint32_t fw_causal = 0; int fw_logits = 0, fw_argmax = 0;   // the step queued by nano_hip_forward_begin (for its re-issue)
-    struct SamplerState *smp = nullptr;                   // device-side sampler scratch, created on first use
-    struct SamplerRowsState *smpr = nullptr;              // ... of the batched sampler (max_batch rows), created on first use
+    struct Sampler *smp = nullptr;                        // device-side sampler scratch (max_batch rows), created on first use
     uint32_t rope_rows = 0;       // rows of the RoPE tables on the device: positions >= rope_rows are rejected
     uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
     bool kv_half = false;         // opt-in FP16 KV cache: rows hold __half, v passes through vraw like k through kraw
@@ -210,12 +202,12 @@ static int peek(void *host_dst, const uint8_t *src, size_t bytes, int src_on_dev
     return 0;
 }
 
-static void sampler_rows_free(SamplerRowsState *sr) {
-    if (!sr) return;
-    if (sr->block) (void)hipFree(sr->block);
-    if (sr->wide) (void)hipFree(sr->wide);
-    if (sr->h_params) (void)hipHostFree(sr->h_params);       // (one pinned block: params, results, ids)
-    delete sr;
+static void sampler_free(Sampler *sp) {
+    if (!sp) return;
+    if (sp->block) (void)hipFree(sp->block);
+    if (sp->wide) (void)hipFree(sp->wide);
+    if (sp->h_params) (void)hipHostFree(sp->h_params);       // (one pinned block: params, ids, results)
+    delete sp;
 }
 
 static void destroy(NanoHipModel *m) {
@@ -232,14 +224,7 @@ static void destroy(NanoHipModel *m) {
     if (m->q4x) (void)hipFree(m->q4x);
     if (m->pf_stage) (void)hipFree(m->pf_stage);
     if (m->h_err) (void)hipHostFree(m->h_err);
-    if (m->smp) {
-        if (m->smp->block) (void)hipFree(m->smp->block);
-        if (m->smp->wide) (void)hipFree(m->smp->wide);
-        if (m->smp->h_hist) (void)hipHostFree(m->smp->h_hist);
-        if (m->smp->h_res) (void)hipHostFree(m->smp->h_res);
-        delete m->smp;
-    }
-    sampler_rows_free(m->smpr);
+    sampler_free(m->smp);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     if (m->ev2) (void)hipEventDestroy(m->ev2);
@@ -579,7 +564,7 @@ static RouteKind kind_of(const NanoHipModel *m, GemvArgs a) { a.ordered = m->str
 // the results of the call are not valid.  Read after a stream synchronisation; the word lives in host-mapped memory, so the check
 // is one load.  dev_err_take() returns the code bits and clears the word (m->last_dev_err keeps them); dev_err_check() turns
 // them into NANO_HIP_ERUNTIME.  Every public entry point that synchronises ends with one of the two (round-5 advice: the
-// arg-max sampling path and an allocation-failure exit of sample_run() returned without looking).
+// arg-max sampling path and an allocation-failure exit of the sampler returned without looking).
 static uint32_t dev_err_take(NanoHipModel *m) {
     const uint32_t c = m->h_err ? *reinterpret_cast<volatile uint32_t *>(m->h_err) : 0u;
     if (!c) return 0u;
@@ -1114,145 +1099,12 @@ extern "C" int nano_hip_forward(NanoHipModel *m, const uint32_t *tokens, const u
 }
 
 // ---- device-side sampling (reference infer.c:1156-1189) ------------------------------------------------
+// Slots 0 .. batch-1 of one decode step, each with its own parameters and history; a one-row call is a batch of one.  Every row has
+// its own scratch at a fixed stride (about 1.5 MB at V = 151 936); the six kernels run once for all rows (sampler.hip
+// launch_sample_rows).  Rows at temperature 0 take the penalised arg-max over their `y` row; rows whose nucleus does not fit the LDS
+// sorter go through the wide phase one after another, on one shared scratch.
 static int sampler_init(NanoHipModel *m) {
     if (m->smp) return 0;
-    const uint32_t V = m->d.vocab_size;
-    const uint32_t nch = (((V + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK) + 3u) & ~3u;
-    if (nch > SAMPLE_MAX_CHUNKS) FAIL(NANO_HIP_EINVAL, "vocabulary %u too large for the device sampler (max %u)", V, SAMPLE_MAX_CHUNKS * SAMPLE_CHUNK);
-    SamplerState *sp = new SamplerState();
-    const size_t npad = (size_t)nch * SAMPLE_CHUNK;
-    sp->hist_cap = m->S + 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_y = take(npad * 4), o_e = take(npad * 4), o_seen = take(npad), o_approx = take(nch * 4), o_spec = take(nch * 4),
-                 o_fn = take(nch * 8), o_cells = take(256), o_pmax = take(nch), o_bins = take(SAMPLE_BINS * 12), o_cand = take((size_t)SAMPLE_MAX_CANDIDATES * 8), o_res = take(sizeof(NanoHipSample)),
-                 o_hist = take((size_t)sp->hist_cap * 4);
-    if (hipMalloc(&sp->block, off) != hipSuccess || hipMemset(sp->block, 0, off) != hipSuccess ||
-        hipHostMalloc(&sp->h_hist, (size_t)sp->hist_cap * 4) != hipSuccess || hipHostMalloc(&sp->h_res, sizeof(NanoHipSample)) != hipSuccess) {
-        if (sp->block) (void)hipFree(sp->block);
-        if (sp->h_hist) (void)hipHostFree(sp->h_hist);
-        delete sp;
-        FAIL(NANO_HIP_ENOMEM, "device sampler scratch allocation failed");
-    }
-    uint8_t *b = sp->block;
-    SampleArgs &a = sp->a;
-    a.V = V; a.nch = nch;
-    a.y = (float *)(b + o_y); a.e = (float *)(b + o_e); sp->seen = b + o_seen;
-    a.approx = (float *)(b + o_approx); a.spec = (uint32_t *)(b + o_spec); a.fn = (uint2 *)(b + o_fn);
-    uint32_t *cells = (uint32_t *)(b + o_cells);
-    a.ncand = cells + 1; a.sum = (float *)(cells + 2); a.ndrop = cells + 3; a.dropmax = cells + 4; a.bstar = cells + 5;
-    a.pmax = (float *)(b + o_pmax);
-    a.bin_mass = (unsigned long long *)(b + o_bins); a.bin_cnt = (uint32_t *)(b + o_bins + SAMPLE_BINS * 8);
-    a.cand = (unsigned long long *)(b + o_cand); a.cap = SAMPLE_MAX_CANDIDATES; a.res = (NanoHipSample *)(b + o_res);
-    sp->hist = (uint32_t *)(b + o_hist);
-    m->smp = sp;
-    return 0;
-}
-
-// queue the sampler behind whatever produced `logits` (device pointer) on the model's stream, wait, fill *out.  Returns SAMPLE_RC_CHECK
-// (> 0) on every exit that synchronised the stream: the caller then looks at the sticky error word (and may re-issue the forward).
-constexpr int SAMPLE_RC_CHECK = 1;
-static int sample_run(NanoHipModel *m, const float *logits, const uint32_t *history, uint32_t n_history,
-                      float penalty, float temperature, float top_p, float coin, NanoHipSample *out) {
-    SamplerState *sp = m->smp;
-    SampleArgs a = sp->a;
-    a.logits = logits; a.penalty = penalty; a.temperature = temperature; a.top_p = top_p; a.coin = coin;
-    a.cutoff = (1.0f - top_p) / (float)((int)a.V - 1);                     // (1.0f - top_p) / (n - 1), infer.c:1064
-    a.seen = nullptr;
-    if (penalty != 1.0f) {                                                 // x / 1.0f is exact: no set needed
-        if (n_history > sp->hist_cap) FAIL(NANO_HIP_EINVAL, "history of %u ids exceeds max_seq_len + 1", n_history);
-        for (uint32_t i = 0; i < n_history; i++) if (history[i] >= a.V) FAIL(NANO_HIP_EINVAL, "history id %u out of vocabulary", history[i]);
-        std::vector<uint32_t> &ap = sp->applied;
-        if (ap.size() > n_history || memcmp(ap.data(), history, ap.size() * 4) != 0) {     // another sequence: start the set over
-            HIP_TRY(hipMemsetAsync(sp->seen, 0, (size_t)a.nch * SAMPLE_CHUNK, m->st));
-            ap.clear();
-        }
-        const uint32_t n_new = n_history - (uint32_t)ap.size();
-        if (n_new) {
-            memcpy(sp->h_hist, history + ap.size(), (size_t)n_new * 4);
-            HIP_TRY(hipMemcpyAsync(sp->hist, sp->h_hist, (size_t)n_new * 4, hipMemcpyHostToDevice, m->st));
-            HIP_TRY(launch_seen_set(sp->hist, n_new, sp->seen, m->st));
-            ap.insert(ap.end(), history + ap.size(), history + n_history);
-        }
-        a.seen = sp->seen;
-    }
-    if (temperature == 0.0f) {                                             // penalised arg-max (infer.c:1169-1171)
-        HIP_TRY(launch_sample_prep(a, m->st));
-        ArgmaxArgs aa{ a.y, a.V, a.V, m->amax, nullptr, m->pos, nullptr, m->pos0, 1, nullptr, 0 };
-        HIP_TRY(launch_argmax(aa, 1, m->st));
-        HIP_TRY(hipMemcpyAsync(m->h_amax, m->amax, 4, hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
-        memset(out, 0, sizeof *out);
-        out->token = m->h_amax[0]; out->status = NANO_SAMPLE_OK;
-        return SAMPLE_RC_CHECK;
-    }
-    HIP_TRY(launch_sample(a, m->st));
-    HIP_TRY(hipMemcpyAsync(sp->h_res, a.res, sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipStreamSynchronize(m->st));
-    if (sp->h_res->status == NANO_SAMPLE_FALLBACK && sp->h_res->n_candidates != 0) {
-        // The nucleus does not fit the LDS sorter (near-uniform distributions): second phase on the device (sampler_wide.hip) from the
-        // numerators and the denominator the first phase left there -- every candidate sorted by a device radix sort, the same cut and draw.
-        if (!sp->wide) {
-            const size_t npad = (size_t)a.nch * SAMPLE_CHUNK;
-            sp->wide_temp_bytes = sample_wide_temp_bytes((uint32_t)npad);
-            const size_t tb = (sp->wide_temp_bytes + 255) & ~(size_t)255;
-            if (!sp->wide_temp_bytes || hipMalloc(&sp->wide, npad * 20 + tb) != hipSuccess) { sp->wide = nullptr; *out = *sp->h_res; return SAMPLE_RC_CHECK; }   // (the caller's host loops)
-            sp->a.wide_in = (unsigned long long *)sp->wide; sp->a.wide_out = sp->a.wide_in + npad;
-            sp->a.wide_p = (float *)(sp->a.wide_out + npad); sp->a.wide_cap = (uint32_t)npad;
-            sp->wide_temp = sp->wide + npad * 20;
-        }
-        a.wide_in = sp->a.wide_in; a.wide_out = sp->a.wide_out; a.wide_p = sp->a.wide_p; a.wide_cap = sp->a.wide_cap;
-        HIP_TRY(launch_sample_wide(a, sp->wide_temp, sp->wide_temp_bytes, m->st));
-        HIP_TRY(hipMemcpyAsync(sp->h_res, a.res, sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
-    }
-    *out = *sp->h_res;
-    return SAMPLE_RC_CHECK;
-}
-
-extern "C" int nano_hip_forward_sample(NanoHipModel *m, uint32_t token, uint32_t pos, const uint32_t *history, uint32_t n_history,
-                                       float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out) {
-    int rc;
-    if (!out || (n_history && !history)) FAIL(NANO_HIP_EINVAL, "null argument");
-    if ((rc = check_batch(m, &token, &pos, 1, 0))) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    if ((rc = sampler_init(m))) return rc;
-    if ((rc = kv_ensure_batch(m, &pos, 1, 0, false))) return rc;
-    m->h_tokens[0] = token; m->h_pos[0] = pos;
-    HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, 4, hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, 4, hipMemcpyHostToDevice, m->st));
-    for (int attempt = 0;; attempt++) {
-        if ((rc = run_step(m, 1, 1u, MODE_LOGITS, pos))) return rc;
-        rc = sample_run(m, m->logits, history, n_history, repetition_penalty, temperature, top_p, coin, out);
-        if (rc != SAMPLE_RC_CHECK) return rc;
-        const uint32_t code = dev_err_take(m);
-        if (!code) return 0;
-        if (attempt || !handoff_recoverable(m, code)) return dev_err_fail(code);
-        handoff_fallback(m);                                                // the same step again, through the plain launches
-        HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, 4, hipMemcpyHostToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, 4, hipMemcpyHostToDevice, m->st));
-    }
-}
-
-extern "C" int nano_hip_op_sample(NanoHipModel *m, const float *logits, const uint32_t *history, uint32_t n_history,
-                                  float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out) {
-    int rc;
-    if (!m || !logits || !out || (n_history && !history)) FAIL(NANO_HIP_EINVAL, "null argument");
-    HIP_TRY(hipSetDevice(m->device));
-    if ((rc = sampler_init(m))) return rc;
-    const size_t V = m->d.vocab_size;
-    memcpy(m->h_logits, logits, V * 4);
-    HIP_TRY(hipMemcpyAsync(m->logits, m->h_logits, V * 4, hipMemcpyHostToDevice, m->st));
-    const int rc2 = sample_run(m, m->logits, history, n_history, repetition_penalty, temperature, top_p, coin, out);
-    return rc2 == SAMPLE_RC_CHECK ? dev_err_check(m) : rc2;
-}
-
-// ---- the sampler over rows: slots 0 .. batch-1 of one decode step, each with its own parameters and history --------------------
-// Every row has the single-row sampler's scratch at a fixed stride (about 1.5 MB at V = 151 936); the six kernels run once for all rows
-// (sampler.hip launch_sample_rows).  Rows at temperature 0 take the penalised arg-max over their `y` row; rows whose nucleus does not
-// fit the LDS sorter go through the wide phase one after another, on one shared scratch.
-static int sampler_rows_init(NanoHipModel *m) {
-    if (m->smpr) return 0;
     const uint32_t V = m->d.vocab_size, R = m->maxB;
     const uint32_t nch = (((V + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK) + 3u) & ~3u;
     if (nch > SAMPLE_MAX_CHUNKS) FAIL(NANO_HIP_EINVAL, "vocabulary %u too large for the device sampler (max %u)", V, SAMPLE_MAX_CHUNKS * SAMPLE_CHUNK);
@@ -1263,22 +1115,23 @@ static int sampler_rows_init(NanoHipModel *m) {
                  o_fn = take(nch * 8), o_cells = take(256), o_pmax = take(nch), o_bins = take(SAMPLE_BINS * 12), o_cand = take((size_t)SAMPLE_MAX_CANDIDATES * 8);
     const size_t rstride = off;
     // the seen_set kernel marks byte offsets from row 0's seen plane: every row's plane must lie below 4 GiB of it
-    if ((uint64_t)rstride * R >= (1ull << 32)) FAIL(NANO_HIP_EINVAL, "batched sampler scratch of %u rows exceeds 4 GiB", R);
+    if ((uint64_t)rstride * R >= (1ull << 32)) FAIL(NANO_HIP_EINVAL, "sampler scratch of %u rows exceeds 4 GiB", R);
     off = rstride * R;
-    const size_t ids_cap = (size_t)R * (m->S + 1);
-    const size_t o_params = take((size_t)R * sizeof(SampleRowParams)), o_res = take((size_t)R * sizeof(NanoHipSample)), o_ids = take(ids_cap * 4);
-    const size_t h_params = 0, h_res = align_up((size_t)R * sizeof(SampleRowParams), 256), h_ids = h_res + align_up((size_t)R * sizeof(NanoHipSample), 256);
-    SamplerRowsState *sr = new SamplerRowsState();
+    // params[batch] and behind them at most batch * (max_seq_len + 1) new history ids, uploaded together
+    const size_t up_bytes = (size_t)R * sizeof(SampleRowParams) + (size_t)R * (m->S + 1) * 4;
+    const size_t o_res = take((size_t)R * sizeof(NanoHipSample)), o_up = take(up_bytes);
+    const size_t h_res = align_up(up_bytes, 256);
+    Sampler *sp = new Sampler();
     uint8_t *hb = nullptr;
-    if (hipMalloc(&sr->block, off) != hipSuccess || hipMemset(sr->block, 0, off) != hipSuccess ||
-        hipHostMalloc((void **)&hb, h_ids + ids_cap * 4) != hipSuccess) {
-        sr->h_params = (SampleRowParams *)hb;
-        sampler_rows_free(sr);
+    if (hipMalloc(&sp->block, off) != hipSuccess || hipMemset(sp->block, 0, off) != hipSuccess ||
+        hipHostMalloc((void **)&hb, h_res + (size_t)R * sizeof(NanoHipSample)) != hipSuccess) {
+        sp->h_params = (SampleRowParams *)hb;
+        sampler_free(sp);
         (void)hipGetLastError();                                            // (the model stays usable)
-        FAIL(NANO_HIP_ENOMEM, "batched sampler scratch allocation failed (%zu bytes for %u rows)", off, R);
+        FAIL(NANO_HIP_ENOMEM, "sampler scratch allocation failed (%zu bytes for %u rows)", off, R);
     }
-    uint8_t *b = sr->block;
-    SampleArgs &a = sr->b.a;
+    uint8_t *b = sp->block;
+    SampleArgs &a = sp->b.a;
     a.V = V; a.nch = nch;
     a.y = (float *)(b + o_y); a.e = (float *)(b + o_e); a.seen = b + o_seen;
     a.approx = (float *)(b + o_approx); a.spec = (uint32_t *)(b + o_spec); a.fn = (uint2 *)(b + o_fn);
@@ -1287,16 +1140,15 @@ static int sampler_rows_init(NanoHipModel *m) {
     a.pmax = (float *)(b + o_pmax);
     a.bin_mass = (unsigned long long *)(b + o_bins); a.bin_cnt = (uint32_t *)(b + o_bins + SAMPLE_BINS * 8);
     a.cand = (unsigned long long *)(b + o_cand); a.cap = SAMPLE_MAX_CANDIDATES; a.res = (NanoHipSample *)(b + o_res);
-    sr->b.rstride = rstride; sr->b.lstride = V;
-    sr->params = (SampleRowParams *)(b + o_params); sr->b.rp = sr->params;
-    sr->ids = (uint32_t *)(b + o_ids); sr->ids_cap = ids_cap;
-    sr->h_params = (SampleRowParams *)(hb + h_params); sr->h_res = (NanoHipSample *)(hb + h_res); sr->h_ids = (uint32_t *)(hb + h_ids);
-    sr->applied.assign(R, {});
-    m->smpr = sr;
+    sp->b.rstride = rstride; sp->b.lstride = V;
+    sp->params = (SampleRowParams *)(b + o_up); sp->b.rp = sp->params;
+    sp->h_params = (SampleRowParams *)hb; sp->h_res = (NanoHipSample *)(hb + h_res);
+    sp->applied.assign(R, {});
+    m->smp = sp;
     return 0;
 }
 
-// the checks of the single-row entry points, for every row (before anything is queued)
+// the checks of every row (before anything is queued)
 static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampleParams *params, const NanoHipSample *out) {
     if (!m || !params || !out) FAIL(NANO_HIP_EINVAL, "null argument");
     if (batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH) FAIL(NANO_HIP_EINVAL, "batch %u out of range (max_batch %u)", batch, m->maxB);
@@ -1311,69 +1163,71 @@ static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampl
     return 0;
 }
 
-// queue the rows' sampler behind whatever produced logits[batch][V] (device) on the model's stream, wait, fill out[batch].  Returns
-// SAMPLE_RC_CHECK on every exit that synchronised the stream (as sample_run).
-static int sample_rows_run(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
-    SamplerRowsState *sr = m->smpr;
-    SampleRows b = sr->b;
+// queue the sampler behind whatever produced logits[batch][V] (device) on the model's stream, wait, fill out[batch].  Returns
+// SAMPLE_RC_CHECK (> 0) on every exit that synchronised the stream: the caller then looks at the sticky error word (and may re-issue
+// the forward).
+constexpr int SAMPLE_RC_CHECK = 1;
+static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+    Sampler *sp = m->smp;
+    SampleRows b = sp->b;
     b.a.logits = logits;
     const uint32_t V = b.a.V;
     const size_t npad = (size_t)b.a.nch * SAMPLE_CHUNK;
     bool any_softmax = false, any_argmax = false;
-    // the seen sets: per slot, start over when the history is not an extension of what the slot holds; all rows' new ids in one copy
+    // the seen sets: per slot, start over when the history is not an extension of what the slot holds.  The new ids of all rows
+    // follow the rows' parameters, and both go up in one copy.
+    uint32_t *h_ids = reinterpret_cast<uint32_t *>(sp->h_params + batch);
     size_t n_ids = 0;
     for (uint32_t i = 0; i < batch; i++) {
         const NanoHipSampleParams &p = params[i];
-        SampleRowParams &q = sr->h_params[i];
+        SampleRowParams &q = sp->h_params[i];
         q.penalty = p.repetition_penalty; q.temperature = p.temperature; q.top_p = p.top_p; q.coin = p.coin;
         q.cutoff = (1.0f - p.top_p) / (float)((int)V - 1);                  // (1.0f - top_p) / (n - 1), infer.c:1064
         (p.temperature == 0.0f ? any_argmax : any_softmax) = true;
         if (p.repetition_penalty == 1.0f) continue;                        // x / 1.0f is exact: no set needed
-        std::vector<uint32_t> &ap = sr->applied[i];
+        std::vector<uint32_t> &ap = sp->applied[i];
         if (ap.size() > p.n_history || memcmp(ap.data(), p.history, ap.size() * 4) != 0) {
             HIP_TRY(hipMemsetAsync(const_cast<uint8_t *>(b.a.seen) + (size_t)i * b.rstride, 0, npad, m->st));
             ap.clear();
         }
-        for (uint32_t k = (uint32_t)ap.size(); k < p.n_history; k++) sr->h_ids[n_ids++] = (uint32_t)((uint64_t)i * b.rstride + p.history[k]);
+        for (uint32_t k = (uint32_t)ap.size(); k < p.n_history; k++) h_ids[n_ids++] = (uint32_t)((uint64_t)i * b.rstride + p.history[k]);
         ap.insert(ap.end(), p.history + ap.size(), p.history + p.n_history);
     }
-    if (n_ids) {
-        HIP_TRY(hipMemcpyAsync(sr->ids, sr->h_ids, n_ids * 4, hipMemcpyHostToDevice, m->st));
-        HIP_TRY(launch_seen_set(sr->ids, (uint32_t)n_ids, const_cast<uint8_t *>(b.a.seen), m->st));
-    }
-    HIP_TRY(hipMemcpyAsync(sr->params, sr->h_params, batch * sizeof(SampleRowParams), hipMemcpyHostToDevice, m->st));
+    HIP_TRY(hipMemcpyAsync(sp->params, sp->h_params, batch * sizeof(SampleRowParams) + n_ids * 4, hipMemcpyHostToDevice, m->st));
+    HIP_TRY(launch_seen_set(reinterpret_cast<const uint32_t *>(sp->params + batch), (uint32_t)n_ids, const_cast<uint8_t *>(b.a.seen), m->st));
     HIP_TRY(launch_sample_rows(b, batch, any_softmax, m->st));
     if (any_argmax) {                                                      // penalised arg-max (infer.c:1169-1171) over every row's y
         ArgmaxArgs aa{ b.a.y, V, (uint32_t)(b.rstride / 4), m->amax, nullptr, m->pos, nullptr, m->pos0, batch, nullptr, 0 };
         HIP_TRY(launch_argmax(aa, batch, m->st));
         HIP_TRY(hipMemcpyAsync(m->h_amax, m->amax, batch * 4, hipMemcpyDeviceToHost, m->st));
     }
-    if (any_softmax) HIP_TRY(hipMemcpyAsync(sr->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
+    if (any_softmax) HIP_TRY(hipMemcpyAsync(sp->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipStreamSynchronize(m->st));
-    // nuclei beyond the LDS sorter: the wide phase (sampler_wide.hip) on that row's numerators and denominator, one row after another
+    // nuclei beyond the LDS sorter (near-uniform distributions): the wide phase (sampler_wide.hip) on that row's numerators and
+    // denominator -- every candidate sorted by a device radix sort, the same cut and draw -- one row after another
     bool wide_ran = false;
     for (uint32_t i = 0; i < batch && any_softmax; i++) {
-        if (params[i].temperature == 0.0f || sr->h_res[i].status != NANO_SAMPLE_FALLBACK || sr->h_res[i].n_candidates == 0) continue;
-        if (!sr->wide) {
-            sr->wide_temp_bytes = sample_wide_temp_bytes((uint32_t)npad);
-            const size_t tb = (sr->wide_temp_bytes + 255) & ~(size_t)255;
-            if (!sr->wide_temp_bytes || hipMalloc(&sr->wide, npad * 20 + tb) != hipSuccess) { sr->wide = nullptr; (void)hipGetLastError(); break; }   // (the caller's host loops)
-            sr->wide_a.wide_in = (unsigned long long *)sr->wide; sr->wide_a.wide_out = sr->wide_a.wide_in + npad;
-            sr->wide_a.wide_p = (float *)(sr->wide_a.wide_out + npad); sr->wide_a.wide_cap = (uint32_t)npad;
-            sr->wide_temp = sr->wide + npad * 20;
+        if (params[i].temperature == 0.0f || sp->h_res[i].status != NANO_SAMPLE_FALLBACK || sp->h_res[i].n_candidates == 0) continue;
+        if (!sp->wide) {
+            sp->wide_temp_bytes = sample_wide_temp_bytes((uint32_t)npad);
+            const size_t tb = (sp->wide_temp_bytes + 255) & ~(size_t)255;
+            if (!sp->wide_temp_bytes || hipMalloc(&sp->wide, npad * 20 + tb) != hipSuccess) { sp->wide = nullptr; (void)hipGetLastError(); break; }   // (the caller's host loops)
+            sp->wide_a.wide_in = (unsigned long long *)sp->wide; sp->wide_a.wide_out = sp->wide_a.wide_in + npad;
+            sp->wide_a.wide_p = (float *)(sp->wide_a.wide_out + npad); sp->wide_a.wide_cap = (uint32_t)npad;
+            sp->wide_temp = sp->wide + npad * 20;
         }
-        SampleArgs a = sample_row(b, i, sr->h_params[i]);
-        a.wide_in = sr->wide_a.wide_in; a.wide_out = sr->wide_a.wide_out; a.wide_p = sr->wide_a.wide_p; a.wide_cap = sr->wide_a.wide_cap;
-        HIP_TRY(launch_sample_wide(a, sr->wide_temp, sr->wide_temp_bytes, m->st));
+        SampleArgs a = sample_row(b, i, sp->h_params[i]);
+        a.wide_in = sp->wide_a.wide_in; a.wide_out = sp->wide_a.wide_out; a.wide_p = sp->wide_a.wide_p; a.wide_cap = sp->wide_a.wide_cap;
+        HIP_TRY(launch_sample_wide(a, sp->wide_temp, sp->wide_temp_bytes, m->st));
         wide_ran = true;
     }
     if (wide_ran) {
-        HIP_TRY(hipMemcpyAsync(sr->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
+        HIP_TRY(hipMemcpyAsync(sp->h_res, b.a.res, batch * sizeof(NanoHipSample), hipMemcpyDeviceToHost, m->st));
         HIP_TRY(hipStreamSynchronize(m->st));
     }
     for (uint32_t i = 0; i < batch; i++) {
         if (params[i].temperature == 0.0f) { memset(&out[i], 0, sizeof out[i]); out[i].token = m->h_amax[i]; out[i].status = NANO_SAMPLE_OK; }
-        else out[i] = sr->h_res[i];
+        else out[i] = sp->h_res[i];
     }
     return SAMPLE_RC_CHECK;
 }
@@ -1384,7 +1238,7 @@ extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *to
     if ((rc = check_sample_rows(m, batch, params, out))) return rc;
     if ((rc = check_batch(m, tokens, pos, batch, 0))) return rc;
     HIP_TRY(hipSetDevice(m->device));
-    if ((rc = sampler_rows_init(m))) return rc;
+    if ((rc = sampler_init(m))) return rc;
     if ((rc = kv_ensure_batch(m, pos, batch, 0, false))) return rc;
     memcpy(m->h_tokens, tokens, batch * 4); memcpy(m->h_pos, pos, batch * 4);
     uint32_t max_pos = 0;
@@ -1393,7 +1247,7 @@ extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *to
     HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
     for (int attempt = 0;; attempt++) {
         if ((rc = run_step(m, batch, 1u, MODE_LOGITS, max_pos))) return rc;
-        rc = sample_rows_run(m, m->logits, batch, params, out);
+        rc = sampler_run(m, m->logits, batch, params, out);
         if (rc != SAMPLE_RC_CHECK) return rc;
         const uint32_t code = dev_err_take(m);
         if (!code) return 0;
@@ -1409,12 +1263,25 @@ extern "C" int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, ui
     if ((rc = check_sample_rows(m, batch, params, out))) return rc;
     if (!logits) FAIL(NANO_HIP_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(m->device));
-    if ((rc = sampler_rows_init(m))) return rc;
+    if ((rc = sampler_init(m))) return rc;
     const size_t V = m->d.vocab_size;
     memcpy(m->h_logits, logits, batch * V * 4);
     HIP_TRY(hipMemcpyAsync(m->logits, m->h_logits, batch * V * 4, hipMemcpyHostToDevice, m->st));
-    const int rc2 = sample_rows_run(m, m->logits, batch, params, out);
+    const int rc2 = sampler_run(m, m->logits, batch, params, out);
     return rc2 == SAMPLE_RC_CHECK ? dev_err_check(m) : rc2;
+}
+
+// one row: slot 0, a batch of one
+extern "C" int nano_hip_forward_sample(NanoHipModel *m, uint32_t token, uint32_t pos, const uint32_t *history, uint32_t n_history,
+                                       float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out) {
+    const NanoHipSampleParams p{ repetition_penalty, temperature, top_p, coin, history, n_history };
+    return nano_hip_forward_sample_batch(m, &token, &pos, 1, &p, out);
+}
+
+extern "C" int nano_hip_op_sample(NanoHipModel *m, const float *logits, const uint32_t *history, uint32_t n_history,
+                                  float repetition_penalty, float temperature, float top_p, float coin, NanoHipSample *out) {
+    const NanoHipSampleParams p{ repetition_penalty, temperature, top_p, coin, history, n_history };
+    return nano_hip_op_sample_batch(m, logits, 1, &p, out);
 }
 
 // ---- LoRA ---------------------------------------------------------------------------------------------

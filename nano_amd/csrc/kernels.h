@@ -313,7 +313,7 @@ struct SampleArgs {
     // second phase, wide nuclei (sampler_wide.hip): every candidate as a key, the sorted keys, the sorted probabilities
     unsigned long long *wide_in, *wide_out; float *wide_p; uint32_t wide_cap;
 };
-// Several rows at once (nano_hip_forward_sample_batch): `a` is row 0's view -- its scratch pointers (y, e, seen, pmax, cells, bins,
+// The sampler's rows (a one-row call is a batch of one): `a` is row 0's view -- its scratch pointers (y, e, seen, pmax, cells, bins,
 // approx, spec, fn, cand) are row 0's, and row r's lie `rstride` bytes further per row; row r's logits are `lstride` floats further,
 // its result is res[r], its parameters rp[r].  The wide-phase pointers of `a` are not used.
 struct SampleRowParams { float penalty, temperature, top_p, cutoff, coin; };
@@ -323,11 +323,12 @@ struct SampleRows {
     uint64_t rstride;
     uint32_t lstride, _pad;
 };
-// row r's single-row view (device: the kernels; host: the wide phase of one row); the seen plane only when the penalty is not 1
+// row r's own view, a SampleArgs (device: the kernels; host: the wide phase of one row); the seen plane only when the penalty is not 1
 __host__ __device__ inline SampleArgs sample_row(const SampleRows &b, uint32_t r, const SampleRowParams &p) {
     SampleArgs a = b.a;
     const uint64_t o = (uint64_t)r * b.rstride;
-    auto mv = [o](auto *ptr) { return reinterpret_cast<decltype(ptr)>(reinterpret_cast<uintptr_t>(ptr) + o); };
+    // offset as a byte pointer, not through an integer: the compiler then still sees a global pointer (global_*, not flat_* accesses)
+    auto mv = [o](auto *ptr) { return reinterpret_cast<decltype(ptr)>(const_cast<char *>(reinterpret_cast<const char *>(ptr)) + o); };
     a.logits = b.a.logits + (size_t)r * b.lstride;
     a.y = mv(a.y); a.e = mv(a.e); a.pmax = mv(a.pmax);
     a.ncand = mv(a.ncand); a.ndrop = mv(a.ndrop); a.dropmax = mv(a.dropmax); a.bstar = mv(a.bstar); a.sum = mv(a.sum);
@@ -340,10 +341,8 @@ __host__ __device__ inline SampleArgs sample_row(const SampleRows &b, uint32_t r
 }
 hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st);
 hipError_t launch_seen_set(const uint32_t *ids, uint32_t n, uint8_t *seen, hipStream_t st);
-hipError_t launch_sample_prep(const SampleArgs &a, hipStream_t st);   // penalty (and temperature) only
-hipError_t launch_sample(const SampleArgs &a, hipStream_t st);
 size_t sample_wide_temp_bytes(uint32_t n);                            // scratch of the device sort of n keys
 hipError_t launch_sample_wide(const SampleArgs &a, void *temp, size_t temp_bytes, hipStream_t st);
-hipError_t launch_sample_wide_cut(const SampleArgs &a, hipStream_t st);   // (its last three kernels: sampler.hip)   // after launch_sample reported NANO_SAMPLE_FALLBACK
+hipError_t launch_sample_wide_cut(const SampleArgs &a, hipStream_t st);   // (its last three kernels: sampler.hip)   // after the row's pick reported NANO_SAMPLE_FALLBACK
 
 }  // namespace nano

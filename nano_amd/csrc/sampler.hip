@@ -16,7 +16,8 @@
 //                 (counts + fixed-point masses) tells at which bin the mass passes top_p, tokens in later bins are
 //                 dropped, and the cut is accepted only if it fell strictly above every dropped token;
 //   * the cut and the draw   one thread, sequential, over the sorted nucleus.
-// Six dependent kernels, ~V*4 B each way through L2; nothing but a 52-byte result crosses PCIe.
+// Six dependent kernels over all rows of a call, ~V*4 B per row each way through L2; across PCIe only the rows' parameters and new
+// history ids go up and a 52-byte result per row comes back.
 #include "kernels.h"
 #include "exact_math.h"
 #include <hip/hip_runtime.h>
@@ -342,20 +343,9 @@ __device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long lon
     for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < n0 ? 0xffffffffu - (uint32_t)key[i] : 0u;
 }
 
-// One row (nano_hip_forward_sample, nano_hip_op_sample, the wide phase's chunk functions): the kernels as they always were.
-__global__ __launch_bounds__(256) void samp_prep_kernel(const SampleArgs a) { samp_prep(a); }
-__global__ __launch_bounds__(256) void samp_exp_kernel(const SampleArgs a) { samp_exp(a); }
-__global__ __launch_bounds__(256) void samp_chunkfn_kernel(const SampleArgs a) { samp_chunkfn(a); }
-__global__ __launch_bounds__(64) void samp_propagate_kernel(const SampleArgs a) { samp_propagate(a); }
-__global__ __launch_bounds__(256) void samp_filter_kernel(const SampleArgs a) { samp_filter(a); }
-__global__ __launch_bounds__(1024) void samp_pick_kernel(const SampleArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long pick_lds[];
-    samp_pick(a, pick_lds);
-}
-
-// Rows (nano_hip_forward_sample_batch): the same bodies on row `r`'s view (kernels.h sample_row).  The chunk-parallel kernels take
-// the row from blockIdx.y, the one-workgroup kernels from blockIdx.x; a workgroup never spans two rows, so every early exit
-// (temperature 0: no softmax for that row) stays workgroup-uniform.
+// The six kernels over rows 0 .. rows-1 (a one-row call is a batch of one): each body runs on row `r`'s view (kernels.h sample_row).
+// The chunk-parallel kernels take the row from blockIdx.y, the one-workgroup kernels from blockIdx.x; a workgroup never spans two rows,
+// so every early exit (temperature 0: no softmax for that row) stays workgroup-uniform.
 __global__ __launch_bounds__(256) void samp_prep_rows_kernel(const SampleRows b) { samp_prep(sample_row(b, blockIdx.y, b.rp[blockIdx.y])); }
 __global__ __launch_bounds__(256) void samp_exp_rows_kernel(const SampleRows b) {
     const SampleRowParams p = b.rp[blockIdx.y];
@@ -402,6 +392,9 @@ __global__ __launch_bounds__(256) void samp_wide_unpack_kernel(const SampleArgs 
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (lane == 0) a.approx[c] = s;
 }
+
+// W4: the chunk function of every chunk of the sorted probabilities (K3's body, reading its addends from `e` = wide_p)
+__global__ __launch_bounds__(256) void samp_chunkfn_kernel(const SampleArgs a) { samp_chunkfn(a); }
 
 // one chunk element by element, every running sum kept: lane k gets the sums after its four elements (4k .. 4k+3)
 __device__ __attribute__((noinline)) uint32_t samp_walk_chunk_sums(const float *e, uint32_t c, uint32_t lane, uint32_t sb, float &r0, float &r1, float &r2, float &r3) {
@@ -529,29 +522,6 @@ hipError_t launch_seen_set(const uint32_t *ids, uint32_t n, uint8_t *seen, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_sample_prep(const SampleArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL(samp_prep_kernel, dim3(a.nch * CH / 1024), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_sample(const SampleArgs &a, hipStream_t st) {
-    const uint32_t wgs = a.nch * CH / 1024;       // nch is a multiple of 4
-    hipLaunchKernelGGL(samp_prep_kernel, dim3(wgs), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(samp_exp_kernel, dim3(a.nch / 4), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(samp_chunkfn_kernel, dim3(a.nch / 4), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(samp_propagate_kernel, dim3(1), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(samp_filter_kernel, dim3(wgs), dim3(256), 0, st, a);
-    constexpr size_t pick_lds_bytes = (size_t)SAMPLE_MAX_CANDIDATES * 8 + 64;
-    static std::atomic<unsigned long long> armed{0};                  // bit per device: the attribute call is a host round trip
-    int dev = 0; (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !((armed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(samp_pick_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pick_lds_bytes);
-        if (dev >= 0 && dev < 64) armed.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(samp_pick_kernel, dim3(1), dim3(1024), pick_lds_bytes, st, a);
-    return hipGetLastError();
-}
-
 // Rows 0 .. rows-1 of `b`.  prep runs for every row (a temperature-0 row's arg-max reads its `y`); the softmax kernels only when some row
 // samples (`softmax`), and skip the temperature-0 rows themselves.  Pick holds 64 KB + 64 B of LDS: two of its workgroups per CU
 // (160 KB), so 64 rows are one wave of workgroups on the 256 CUs; the chunk-parallel kernels are rows x (nch / 4) workgroups of 256.
@@ -566,7 +536,7 @@ hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, 
     hipLaunchKernelGGL(samp_propagate_rows_kernel, dim3(rows), dim3(64), 0, st, b);
     hipLaunchKernelGGL(samp_filter_rows_kernel, dim3(wgs, rows), dim3(256), 0, st, b);
     constexpr size_t pick_lds_bytes = (size_t)SAMPLE_MAX_CANDIDATES * 8 + 64;
-    static std::atomic<unsigned long long> armed{0};
+    static std::atomic<unsigned long long> armed{0};                  // bit per device: the attribute call is a host round trip
     int dev = 0; (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !((armed.load(std::memory_order_acquire) >> dev) & 1ull)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(samp_pick_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pick_lds_bytes);

@@ -1,6 +1,6 @@
 """GPU tests of the batched device sampler (nano_hip_forward_sample_batch / nano_hip_op_sample_batch / nano_forward_batch_sample):
-every row of a batched step is sampled on the device, and each row's result is the single-row sampler's for that row's logits,
-field by field -- which the single-row tests hold to the reference."""
+every row of a batched step is sampled on the device, and each row's result is what a one-row call returns for that row's logits
+alone, field by field -- which test_gpu_sampler.py holds to the reference."""
 import ctypes as C
 import os
 
@@ -164,6 +164,38 @@ def test_history_cache_starts_over(model_dir):
     want = f.op_sample_batch(L, rows)
     f.close()
     assert [fields(r) for r in got] == [fields(r) for r in want]
+
+
+def test_history_record_shared_by_one_row_and_batched_calls(model_dir):
+    """A one-row call is slot 0 of a batch of one, so slot 0's record of the marked ids serves both entry points.  Interleaved
+    calls -- one row on history A, a batch with slot 0 on B and slot 1 on C, one row on an extension of A, one row (arg-max) on a
+    further extension, a batch extending that and C -- each give what a freshly loaded model gives for the same call."""
+    path, spec = synth_model(model_dir, "tiny-qwen3", "f32", 0)
+    V = spec.vocab_size
+    rng = np.random.default_rng(21)
+    L = (3.0 * rng.standard_normal((2, V))).astype(np.float32)
+    ids = lambda n: rng.integers(0, V, size=n).astype(np.uint32)
+    A, B, C = ids(12), ids(9), ids(15)
+    A2 = np.concatenate([A, ids(3)]); A3 = np.concatenate([A2, ids(2)])
+    calls = [(L[0], [(1.5, 0.8, 0.9, 0.4, A)]),
+             (L, [(1.5, 0.8, 0.9, 0.4, B), (1.3, 1.0, 0.9, 0.7, C)]),
+             (L[1], [(1.5, 0.8, 0.9, 0.2, A2)]),
+             (L[0], [(1.2, 0.0, 0.9, 0.0, A3)]),
+             (L, [(1.5, 0.8, 0.9, 0.6, np.concatenate([A3, ids(4)])), (1.3, 1.0, 0.9, 0.3, np.concatenate([C, ids(2)]))])]
+
+    def call(m, l, rows):
+        if l.ndim == 1:
+            return [fields(single(m, l, rows[0]))]
+        return [fields(r) for r in m.op_sample_batch(l, rows)]
+
+    m = nb.load_model_file(path, max_seq_len=32, max_batch=2)
+    got = [call(m, l, rows) for l, rows in calls]
+    m.close()
+    for k, ((l, rows), g) in enumerate(zip(calls, got)):
+        f = nb.load_model_file(path, max_seq_len=32, max_batch=2)
+        assert call(f, l, rows) == g, k
+        assert all(r[1] == 0 for r in g), k
+        f.close()
 
 
 def xorshift_f32(state):
