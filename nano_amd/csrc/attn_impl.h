@@ -191,6 +191,13 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
         first_of_group = (h0 % kv_mul) == 0;
     }
     constexpr bool G = MODE == 0;
+    // FAST: the Qwen3 body of the fused one-sequence launches (q|k|v + attention, Q80 and Q4K).  Its leg from the last granule to the last
+    // store is latency, one wave per SIMD, so three things are cut from it; the arithmetic and its association are untouched (same bits):
+    // the give-up vote is one word per wave and ONE barrier (__syncthreads_or compiles to three barriers, an LDS atomic and a dispatch-packet
+    // load), the fresh k / v row replaces the cache row in the one block and the lanes that hold t == pos (a wave-uniform branch; the other
+    // blocks and waves pay no selects), and a wave's sub-groups meet through a wave-private LDS block as in the KVM > 1 kernels (the same
+    // ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)) as xsub_sum) instead of 16 three-step cross-lane chains.
+    constexpr bool FAST = FUSE && MODE == 1 && KVM == 1 && LPR == 8 && QV == 4 && NPT == 2 && !KVH && !PG && !W16;
     constexpr int VR = (KVM + 1 + 3) / 4;                      // rounds of vectors per wave (q heads + the k row over 4 waves)
     constexpr int JJ = (LPR == 16) ? 2 : 1;                    // RoPE pairs per lane (head_dim > 128 needs two)
     const bool fresh_k = G ? a.kraw != nullptr : true;
@@ -409,7 +416,16 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
             if ((uint32_t)tid < 128u) { qh[t7] = __uint_as_float((uint32_t)g0); vh[t7] = __uint_as_float((uint32_t)g1); }
             else kh[t7] = __uint_as_float((uint32_t)g0);
         }
-        if (__syncthreads_or(got ? 0 : 1)) {                   // (the staging barrier; a wave that gave up takes the whole workgroup out)
+        if constexpr (FAST) {                                  // (`got` is wave-uniform: one word per wave, behind the fresh v row)
+            uint32_t *gave = reinterpret_cast<uint32_t *>(vh + hd4);
+            if (lane == 0) gave[wid] = got ? 0u : 1u;
+            __syncthreads();                                   // (the staging barrier)
+            const uint4 gv = *reinterpret_cast<const uint4 *>(gave);
+            if (gv.x | gv.y | gv.z | gv.w) {
+                if (!got && lane == 0) hand_give_up(hh, a.err);
+                return;
+            }
+        } else if (__syncthreads_or(got ? 0 : 1)) {            // (the staging barrier; a wave that gave up takes the whole workgroup out)
             if (!got && lane == 0) hand_give_up(hh, a.err);
             return;
         }
@@ -637,11 +653,21 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     const uint32_t nround = (limit + per_round - 1) / per_round;
     for (uint32_t round = 0; round < nround; round++) {
         if (round) issue_kv(round);
+        if constexpr (FAST) {                                  // the fresh k / v row into the registers of the one block that holds t == pos
+#pragma unroll
+            for (int p = 0; p < NPT; p++) {
+                const uint32_t t = ((round * NPT + p) * nsplit + split) * R + sub;
+                if (__any(t == pos) && t == pos) {             // (the first test is wave-uniform; an `a ? b : c` of the float4 lvalues
+#pragma unroll                                                 // would select ADDRESSES and put the arrays in scratch)
+                    for (int q = 0; q < QV; q++) { kreg[p][q].v = kfresh[q]; vreg[p][q].v = vfresh[q]; }
+                }
+            }
+        }
         float sc[KVM][NPT];
 #pragma unroll
         for (int p = 0; p < NPT; p++) {
             const uint32_t t = ((round * NPT + p) * nsplit + split) * R + sub;
-            const bool fresh = fresh_k && t == pos;
+            const bool fresh = !FAST && fresh_k && t == pos;
 #pragma unroll
             for (int m = 0; m < KVM; m++) {
                 float d = 0.0f;
@@ -668,7 +694,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
                 const float e = (sc[m][p] == -INFINITY) ? 0.0f : expf(sc[m][p] - mx);
                 l += e;
                 const uint32_t tv = ((round * NPT + p) * nsplit + split) * R + sub;
-                const bool vf = (FUSE || (KVH && fresh_v)) && tv == pos;       // FP16 cache / fused launch: the fresh v row is not in the cache yet
+                const bool vf = !FAST && (FUSE || (KVH && fresh_v)) && tv == pos;   // FP16 cache / fused launch: the fresh v row is not in the cache yet
 #pragma unroll
                 for (int q = 0; q < QV; q++) {
                     const float4 vv = vf ? vfresh[q] : kv_cvt(vreg[p][q]);
@@ -686,14 +712,15 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     //     l % LPR, so the wave's maximum, its exp-sum and its weighted-V slices are three cross-lane steps each (VALU only);
     // (b) across the four waves through LDS: 4 partial rows per head instead of one per sub-group.
     // (round 3: the former layout -- every sub-group's row through LDS, 32-term sums -- cost 1.7 of the kernel's 4.8 us)
-    if constexpr (KVM > 1) {
+    if constexpr (KVM > 1 || FAST) {
         // Round 6, several heads per workgroup (the batched steps): the weighted accumulators of a wave's sub-groups meet through a
         // wave-private LDS block instead of three cross-lane steps per value (KVM x QV x 4 values x ~7 instructions = ~450 of a wave's VALU
         // instructions at KVM = 4, in a launch that is VALU bound): every lane parks its KVM x QV float4 products acc * w, then a lane
         // adds the NS sub-groups' values of two output elements in the SAME association the cross-lane tree has --
         // ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)), fp addition commutes -- so the bits are those of the KVM = 1 kernels.
         constexpr int NS = 64 / LPR, HP = LPR * QV * 4;          // sub-groups per wave; floats a sub-group holds per head (>= head_dim)
-        float *tr = part + 4 * KVM * hd4 + (size_t)wid * NS * HP; // [sub-group][HP], wave-private: no barrier (a wave's LDS operations are in order)
+        // (FAST: behind the fresh v row and the give-up words)
+        float *tr = part + 4 * KVM * hd4 + (FAST ? hd4 + 4 : 0) + (size_t)wid * NS * HP;   // [sub-group][HP], wave-private: no barrier (a wave's LDS operations are in order)
         const uint32_t sw = (uint32_t)lane / LPR;                 // sub-group inside the wave
 #pragma unroll
         for (int m = 0; m < KVM; m++) {

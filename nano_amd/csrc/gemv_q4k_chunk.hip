@@ -314,7 +314,7 @@ hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, uns
     SlabHand h{};
     h.buf = hand; h.tick = tick; h.layer1 = layer1;
     h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
-    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4) * sizeof(float);            // as gemv_q80_impl.h launch_qkv_attn_fused
+    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + 4 + 4 * 8 * hd4) * sizeof(float);    // as gemv_q80_impl.h launch_qkv_attn_fused
     const size_t lds = p.lds > lds_a ? p.lds : lds_a;
     Q4FusedArgs fa{};
     fa.g = d; fa.a = a; fa.hand = h; fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head; fa.ngemv = p.grid;

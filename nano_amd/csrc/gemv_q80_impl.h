@@ -841,7 +841,8 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
     const uint32_t n_attn = a.n_head * a.nsplit;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
     const size_t lds_g = n16 + ng4 * 4 + 64 + (size_t)(d.tpw * 4) * pitch * 4;
-    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4) * sizeof(float);            // q | k | maxima | sums | 4 waves' partials | the fresh v row
+    // q | k | maxima | sums | 4 waves' partials | the fresh v row | 4 give-up words | 4 waves x 8 sub-groups' weighted rows (attn_impl.h FAST)
+    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + 4 + 4 * 8 * hd4) * sizeof(float);
     const size_t lds = lds_g > lds_a ? lds_g : lds_a;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
