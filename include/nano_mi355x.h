@@ -278,6 +278,36 @@ int nano_hip_op_rope(int device, float *head, uint32_t head_dim, const float *fc
 /* q[n_head*hd] (already normed+roped), k/v caches [range][kv_dim]; out[n_head*hd] */
 int nano_hip_op_attention(int device, float *out, const float *q, const float *k_cache, const float *v_cache,
                           uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t range);
+/* One decode attention launch exactly as a step issues it (the non-fused path of a decode step, or with `chunk` the two passes of a
+ * batched prefill chunk): q / k rmsnorm and RoPE of the raw rows, the finished k row (FP16 cache: and the v row) stored at pos, causal
+ * attention over rows 0..pos, split partials combined by the batched / prefill combine.  Replaces infer/infer.c:810-879.  The op stages
+ * each sequence's RoPE row (and, paged, its pool row) as the step's embed kernel does.  All pointers are host pointers; the caches are
+ * copied in and back whole, so the caller sees every element the launch wrote. */
+typedef struct NanoAttnDecodeDesc {
+    uint32_t nb;                /* sequences (1..NANO_MAX_BATCH); chunk: tokens of the one sequence */
+    uint32_t n_head, n_kv_head, hd, n_layer, layer, S;     /* S: cache rows per layer of a slot, and rows of the RoPE tables */
+    uint32_t range_hint;        /* max(pos) + 1 <= range_hint <= S */
+    uint32_t nsplit;            /* 0: attention_nsplit(range_hint, hd); else forced (<= 64) */
+    uint32_t rope_qwen3;        /* 1: (i, i + hd/2) pairs, 0: adjacent pairs */
+    uint32_t kv_half;           /* 1: FP16 cache elements (k_cache / v_cache hold uint16 bit patterns) */
+    uint32_t chunk;             /* 1: the nb rows are consecutive positions of ONE sequence: pass 1 (prep_only), then pass 2 */
+    uint32_t want_frag;         /* 1: also the Q80 groups of 64 in fragment order (nsplit == 1, hd % 64 == 0 only) */
+    uint32_t pool_rows;         /* paged cache: rows of one layer plane (a multiple of 64); 0: contiguous cache */
+    uint32_t pt_stride;         /* paged: page-table entries per sequence */
+    const float *q;             /* [nb][n_head * hd] raw q */
+    const float *k;             /* [nb][n_kv_head * hd] raw k of pos */
+    const float *vraw;          /* FP16 cache: [nb][kv_dim] v of pos (FP32), or NULL; FP32 cache: the v rows of pos are in v_cache already */
+    const uint32_t *pos;        /* [nb] */
+    const float *q_norm, *k_norm;          /* [hd] (Qwen3) or NULL */
+    const float *rope_cos, *rope_sin;      /* [S][hd / 2] */
+    const uint32_t *pt_rows;    /* paged: [sequences (chunk: 1)][pt_stride] first pool row of each 64-position page, 0xffffffff = none */
+    void *k_cache, *v_cache;    /* in / out: contiguous [sequences (chunk: 1)][n_layer][S][kv_dim], paged [n_layer][pool_rows][kv_dim] */
+    float *out;                 /* [nb][n_head * hd] head outputs */
+    int8_t *xf;                 /* want_frag: [ceil(nb / 16)][n_head * hd / 64][1024] */
+    float *xsf;                 /* want_frag: [ceil(nb / 16)][n_head * hd / 64][16] */
+    uint32_t *plan;             /* optional [2][10]: {mode, lpr, qv, kvm, npt, w16, paged, kv_half, nsplit, xcd} of the launch (chunk: pass 1, pass 2) */
+} NanoAttnDecodeDesc;
+int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc *d);
 int nano_hip_op_swiglu(int device, float *hb, const float *hb2, uint32_t n);
 int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32_t *idx);
 

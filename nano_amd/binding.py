@@ -36,6 +36,18 @@ class NanoFusedGemvDesc(C.Structure):
                 ("attn_hd", C.c_uint32), ("use_gemm", C.c_uint32), ("ordered", C.c_uint32), ("route_out", C.c_void_p), ("out", C.c_void_p)]
 
 
+class NanoAttnDecodeDesc(C.Structure):
+    """include/nano_mi355x.h NanoAttnDecodeDesc: one decode attention launch (or a prefill chunk's two passes) as a step issues it."""
+    _fields_ = [(n, C.c_uint32) for n in ("nb", "n_head", "n_kv_head", "hd", "n_layer", "layer", "S", "range_hint", "nsplit", "rope_qwen3",
+                                          "kv_half", "chunk", "want_frag", "pool_rows", "pt_stride")] + \
+               [(n, C.c_void_p) for n in ("q", "k", "vraw", "pos", "q_norm", "k_norm", "rope_cos", "rope_sin", "pt_rows", "k_cache", "v_cache",
+                                          "out", "xf", "xsf", "plan")]
+
+
+# the fields of an attention plan (nano_amd/csrc/kernels.h AttnPlan; xcd: workgroups of a KV head on one XCD)
+ATTN_PLAN_FIELDS = ("mode", "lpr", "qv", "kvm", "npt", "w16", "paged", "kv_half", "nsplit", "xcd")
+
+
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
 ROUTE_NAMES = ("gemv", "gemv_preq", "gemv_sliced", "q4k", "reserved", "frag_g6", "frag_old", "frag_g7")
 
@@ -102,6 +114,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_swiglu", C.c_int, [C.c_int, f32p, f32p, C.c_uint32])
     fn("nano_hip_op_argmax", C.c_int, [C.c_int, f32p, C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_op_fused_gemv", C.c_int, [C.c_int, C.POINTER(NanoFusedGemvDesc)])
+    fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
@@ -441,6 +454,48 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     if want_route:
         return out, (ROUTE_NAMES[route.value] if route.value < len(ROUTE_NAMES) else "?")
     return out
+
+
+def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n_layer, layer, S, range_hint, rope_cos, rope_sin,
+                        rope_qwen3, q_norm=None, k_norm=None, vraw=None, kv_half=False, chunk=False, nsplit=0, want_frag=False,
+                        pt_rows=None, pool_rows=0, device=0):
+    """One decode attention launch as a step issues it (nano_hip_op_attention_decode); chunk: the two passes of a prefill chunk.
+    q [nb, n_head*hd], k [nb, kv_dim] raw rows; pos [nb]; caches float32 (kv_half: float16) contiguous [seqs, n_layer, S, kv_dim]
+    or paged (pt_rows [seqs, pt_stride], pool_rows) [n_layer, pool_rows, kv_dim]; rope tables [S, hd/2].
+    Returns dict(out [nb, n_head*hd], k_cache, v_cache (new arrays, same shape / dtype), plan (one dict; chunk: [pass 1, pass 2]),
+    xf / xsf when want_frag)."""
+    d = NanoAttnDecodeDesc()
+    q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); pos = np.ascontiguousarray(pos, np.uint32)
+    nb_ = q.shape[0]
+    cdt = np.float16 if kv_half else np.float32
+    kc = np.array(k_cache, cdt, copy=True, order="C"); vc = np.array(v_cache, cdt, copy=True, order="C")
+    rope_cos = np.ascontiguousarray(rope_cos, np.float32); rope_sin = np.ascontiguousarray(rope_sin, np.float32)
+    out = np.zeros((nb_, n_head * hd), np.float32)
+    plan = np.zeros((2, len(ATTN_PLAN_FIELDS)), np.uint32)
+    keep = [q, k, pos, kc, vc, rope_cos, rope_sin, out, plan]
+    d.nb, d.n_head, d.n_kv_head, d.hd, d.n_layer, d.layer, d.S = nb_, n_head, n_kv_head, hd, n_layer, layer, S
+    d.range_hint, d.nsplit, d.rope_qwen3, d.kv_half, d.chunk, d.want_frag = range_hint, nsplit, int(rope_qwen3), int(kv_half), int(chunk), int(want_frag)
+    d.q, d.k, d.pos, d.k_cache, d.v_cache, d.out, d.plan = (x.ctypes.data for x in (q, k, pos, kc, vc, out, plan))
+    d.rope_cos, d.rope_sin = rope_cos.ctypes.data, rope_sin.ctypes.data
+    if q_norm is not None:
+        q_norm = np.ascontiguousarray(q_norm, np.float32); k_norm = np.ascontiguousarray(k_norm, np.float32); keep += [q_norm, k_norm]
+        d.q_norm, d.k_norm = q_norm.ctypes.data, k_norm.ctypes.data
+    if vraw is not None:
+        vraw = np.ascontiguousarray(vraw, np.float32); keep.append(vraw); d.vraw = vraw.ctypes.data
+    if pt_rows is not None:
+        pt_rows = np.ascontiguousarray(pt_rows, np.uint32); keep.append(pt_rows)
+        d.pt_rows, d.pt_stride, d.pool_rows = pt_rows.ctypes.data, pt_rows.shape[-1], pool_rows
+    xf = xsf = None
+    if want_frag:
+        tiles, ng = (nb_ + 15) // 16, n_head * hd // 64
+        xf = np.zeros((tiles, ng, 1024), np.int8); xsf = np.zeros((tiles, ng, 16), np.float32); keep += [xf, xsf]
+        d.xf, d.xsf = xf.ctypes.data, xsf.ctypes.data
+    check(lib().nano_hip_op_attention_decode(device, C.byref(d)))
+    plans = [dict(zip(ATTN_PLAN_FIELDS, (int(v) for v in row))) for row in plan]
+    res = {"out": out, "k_cache": kc, "v_cache": vc, "plan": plans if chunk else plans[0]}
+    if want_frag:
+        res["xf"], res["xsf"] = xf, xsf
+    return res
 
 
 def op_rope(head, fcr, fci, qwen3, device=0):

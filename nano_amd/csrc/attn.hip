@@ -25,59 +25,37 @@ namespace nano {
 namespace {
 
 template <int LPR, int QV, int MODE, bool KVH>
-static hipError_t launch_mode_kv(const AttnArgs &a_in, uint32_t nb, hipStream_t st) {
-    const uint32_t kv_mul = a_in.n_head / a_in.n_kv_head;
+static hipError_t launch_mode_kv(const AttnArgs &a_in, const AttnPlan &p, uint32_t nb, hipStream_t st) {
     const uint32_t hd4 = (a_in.hd + 3) & ~3u;
-    constexpr uint32_t R = 256 / LPR;                          // timesteps per block
     // (+ several heads per workgroup: the waves' transposition blocks of the sub-group combine, 4 waves x 64 / LPR sub-groups x LPR * QV * 4 floats)
     auto lds_for = [&](uint32_t kvm) { return (size_t)(kvm * hd4 + hd4 + 4 * kvm + 4 * kvm + (size_t)4 * kvm * hd4 + (kvm > 1 ? (size_t)4 * (64 / LPR) * (LPR * QV * 4) : 0)) * sizeof(float); };
-    // q heads per workgroup (KVM; h0 = KVM grp, KV head h0 / kv_mul): fewer heads = more workgroups with less dependent work each,
-    // the K/V rows' repeated reads come from L2 (and the KV head's fresh k row is written by each of its workgroups: same
-    // bits).  Same per-head arithmetic whatever the choice.  One head per workgroup while that leaves at most one workgroup
-    // per CU, two while at most two, else the whole KV group (measured: Qwen3-0.6B batch 1 6.15 -> 5.35 us per launch = +3.7 %
-    // tokens/s; Qwen3-4B's kv_mul 4: 8.65 -> 6.03 us at batch 1, 10.05 -> 7.22 with two heads at 16 sequences, where one head
-    // per workgroup costs 10.3; at 64 sequences the KV rows' bandwidth rules and four heads share them: 13.7 vs 16.4).
     AttnArgs a = a_in;
-    a.kv_log2 = 0xffffffffu; a.kvmul_log2 = 0;
-    const bool kv_pow2 = (a.n_kv_head & (a.n_kv_head - 1)) == 0, mul_pow2 = (kv_mul & (kv_mul - 1)) == 0;
-    if (kv_pow2 && (MODE != 0 || a.n_kv_head >= 8)) { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
-    if (mul_pow2) { uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
-    if (MODE != 0 && !(kv_pow2 && mul_pow2)) return hipErrorInvalidValue;       // launch_lpr() sends such shapes to the generic mode
-    const uint64_t head_wgs = (uint64_t)a.n_head * nb * a.nsplit;
-    uint32_t kvm = (head_wgs <= 256u || kv_mul % 2 != 0) ? 1u : (head_wgs <= 1024u || kv_mul % 4 != 0) ? 2u : 4u;
-    // A workgroup that would walk exactly two rounds of NP blocks (513 .. 1024 positions at 8 splits) keeps four blocks in flight
-    // instead: every row of the launch requested at kernel entry (Qwen3-0.6B at position 1023: 639 -> 632 us per step).  Measured
-    // and NOT taken beyond: four rounds -> two at 2047 positions 754 -> 759 us, two -> one at 4095 with 32 splits 819 -> 836 (the
-    // issue phase grows from 3.1 to 5.9 us: `profiles/r04_long_ctx_np4.txt`).  Decided by the range and the split count alone --
-    // never by the batch: a token's attention is the same expression in a decode step and in a prefill chunk (the four-head
-    // workgroups of large batches give way to two heads).
-    const bool np4 = !a.prep_only && a.nsplit <= 8u && a.range_hint > a.nsplit * (uint32_t)NP * R && a.range_hint <= 2u * a.nsplit * (uint32_t)NP * R;
-    if (np4 && kvm == 4) kvm = 2;
+    a.kv_log2 = p.kv_log2; a.kvmul_log2 = p.kvmul_log2;
     constexpr bool CAN16 = KVH && QV % 4 == 0;
-    const bool w16 = CAN16 && a.hd % 8u == 0u;
+    const bool w16 = CAN16 && p.w16;
+    const bool np4 = p.npt == 4u;
 #define ATTN_GO3(KVM_, NP_, PG_) do { if constexpr (CAN16) { if (w16) { hipLaunchKernelGGL((attention_kernel<LPR, QV, KVM_, MODE, KVH, PG_, NP_, CAN16>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); break; } } \
                          hipLaunchKernelGGL((attention_kernel<LPR, QV, KVM_, MODE, KVH, PG_, NP_, false>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); } while (0)
-#define ATTN_GO2(KVM_, NP_) do { if (a.pt_rows) ATTN_GO3(KVM_, NP_, true); else ATTN_GO3(KVM_, NP_, false); } while (0)
+#define ATTN_GO2(KVM_, NP_) do { if (p.paged) ATTN_GO3(KVM_, NP_, true); else ATTN_GO3(KVM_, NP_, false); } while (0)
 #define ATTN_GO(KVM_) do { if (np4) ATTN_GO2(KVM_, 4); else ATTN_GO2(KVM_, NP); } while (0)
-    if (kvm == 4) ATTN_GO2(4, NP); else if (kvm == 2) ATTN_GO(2); else ATTN_GO(1);
+    if (p.kvm == 4) {
+        if constexpr (LPR == 16) return hipErrorInvalidValue;  // (attention_plan() caps head_dim > 128 at two heads: no such kernel)
+        else ATTN_GO2(4, NP);
+    } else if (p.kvm == 2) ATTN_GO(2); else ATTN_GO(1);
 #undef ATTN_GO
 #undef ATTN_GO2
 #undef ATTN_GO3
     return hipGetLastError();
 }
 template <int LPR, int QV, int MODE>
-static hipError_t launch_mode(const AttnArgs &a, uint32_t nb, hipStream_t st) {
-    return a.kv_half ? launch_mode_kv<LPR, QV, MODE, true>(a, nb, st) : launch_mode_kv<LPR, QV, MODE, false>(a, nb, st);
+static hipError_t launch_mode(const AttnArgs &a, const AttnPlan &p, uint32_t nb, hipStream_t st) {
+    return a.kv_half ? launch_mode_kv<LPR, QV, MODE, true>(a, p, nb, st) : launch_mode_kv<LPR, QV, MODE, false>(a, p, nb, st);
 }
 template <int LPR, int QV>
-static hipError_t launch_lpr(const AttnArgs &a, uint32_t nb, hipStream_t st) {
-    // the decode modes index with shifts and masks: power-of-two head counts (every BASELINE shape: 16 / 8 and 32 / 8 heads)
-    const uint32_t kv_mul = a.n_kv_head ? a.n_head / a.n_kv_head : 0;
-    const bool pow2 = a.n_kv_head && (a.n_kv_head & (a.n_kv_head - 1)) == 0 && kv_mul && (kv_mul & (kv_mul - 1)) == 0;
-    const bool decode = pow2 && a.kraw && a.rope_cos && a.rope_cur && !a.fixed_range && a.is_causal && !a.q_out;
-    if (decode && a.q_norm && a.rope_qwen3 && a.hd % 64 == 0 && a.hd == (uint32_t)(QV * LPR * 4)) return launch_mode<LPR, QV, 1>(a, nb, st);
-    if (decode && !a.q_norm && !a.rope_qwen3) return launch_mode<LPR, QV, 2>(a, nb, st);
-    return launch_mode<LPR, QV, 0>(a, nb, st);
+static hipError_t launch_lpr(const AttnArgs &a, const AttnPlan &p, uint32_t nb, hipStream_t st) {
+    if (p.mode == 1) return launch_mode<LPR, QV, 1>(a, p, nb, st);
+    if (p.mode == 2) return launch_mode<LPR, QV, 2>(a, p, nb, st);
+    return launch_mode<LPR, QV, 0>(a, p, nb, st);
 }
 
 }  // namespace
@@ -103,13 +81,59 @@ uint32_t attention_nsplit(uint32_t range_hint, uint32_t hd) {
     return n;
 }
 
+bool attention_plan(const AttnArgs &a, uint32_t nb, AttnPlan *out) {
+    if (a.hd % 4 || a.hd > 256 || a.hd < 4 || a.nsplit == 0 || a.nsplit > ATTN_MAX_NSPLIT || !a.n_kv_head) return false;
+    if (a.nsplit == 1 && !a.xba_out) return false;
+    AttnPlan p{};
+    p.lpr = a.hd <= 128 ? 8u : 16u;                            // lanes per KV row and float4 slots per lane: the head fills a sub-group
+    p.qv = a.hd <= 32 ? 1u : a.hd <= 64 ? 2u : 4u;
+    // the decode modes index with shifts and masks: power-of-two head counts (every BASELINE shape: 16 / 8 and 32 / 8 heads)
+    const uint32_t kv_mul = a.n_head / a.n_kv_head;
+    const bool kv_pow2 = (a.n_kv_head & (a.n_kv_head - 1)) == 0, mul_pow2 = (kv_mul & (kv_mul - 1)) == 0;
+    const bool decode = kv_pow2 && kv_mul && mul_pow2 && a.kraw && a.rope_cos && a.rope_cur && !a.fixed_range && a.is_causal && !a.q_out;
+    p.mode = (decode && a.q_norm && a.rope_qwen3 && a.hd % 64 == 0 && a.hd == p.qv * p.lpr * 4u) ? 1u : (decode && !a.q_norm && !a.rope_qwen3) ? 2u : 0u;
+    p.kv_log2 = 0xffffffffu; p.kvmul_log2 = 0;
+    if (kv_pow2 && (p.mode != 0 || a.n_kv_head >= 8)) { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; p.kv_log2 = l2; }
+    if (mul_pow2) { uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; p.kvmul_log2 = l2; }
+    // q heads per workgroup (KVM; h0 = KVM grp, KV head h0 / kv_mul): fewer heads = more workgroups with less dependent work each,
+    // the K/V rows' repeated reads come from L2 (and the KV head's fresh k row is written by each of its workgroups: same
+    // bits).  Same per-head arithmetic whatever the choice.  One head per workgroup while that leaves at most one workgroup
+    // per CU, two while at most two, else the whole KV group (measured: Qwen3-0.6B batch 1 6.15 -> 5.35 us per launch = +3.7 %
+    // tokens/s; Qwen3-4B's kv_mul 4: 8.65 -> 6.03 us at batch 1, 10.05 -> 7.22 with two heads at 16 sequences, where one head
+    // per workgroup costs 10.3; at 64 sequences the KV rows' bandwidth rules and four heads share them: 13.7 vs 16.4).
+    const uint64_t head_wgs = (uint64_t)a.n_head * nb * a.nsplit;
+    uint32_t kvm = (head_wgs <= 256u || kv_mul % 2 != 0) ? 1u : (head_wgs <= 1024u || kv_mul % 4 != 0) ? 2u : 4u;
+    // A workgroup that would walk exactly two rounds of NP blocks (513 .. 1024 positions at 8 splits) keeps four blocks in flight
+    // instead: every row of the launch requested at kernel entry (Qwen3-0.6B at position 1023: 639 -> 632 us per step).  Measured
+    // and NOT taken beyond: four rounds -> two at 2047 positions 754 -> 759 us, two -> one at 4095 with 32 splits 819 -> 836 (the
+    // issue phase grows from 3.1 to 5.9 us: `profiles/r04_long_ctx_np4.txt`).  Decided by the range and the split count alone --
+    // never by the batch: a token's attention is the same expression in a decode step and in a prefill chunk (the four-head
+    // workgroups of large batches give way to two heads).
+    const uint32_t R = 256u / p.lpr;                           // timesteps per block
+    const bool np4 = !a.prep_only && a.nsplit <= 8u && a.range_hint > a.nsplit * (uint32_t)NP * R && a.range_hint <= 2u * a.nsplit * (uint32_t)NP * R;
+    if (np4 && kvm == 4) kvm = 2;
+    // head_dim > 128: at most two heads.  The decode modes' shared q / k preparation (attention_body SHARE) gives wave 0's sub-groups one
+    // vector each -- KVM q heads and the k row -- and a wave holds 64 / LPR = 4 sub-groups of 16 lanes: with four heads the k row had no
+    // sub-group, was never stored, and every lane read stale LDS as the fresh k (tests/test_gpu_attention_decode.py).  No measured
+    // configuration runs head_dim > 128, so the cap costs nothing known.
+    if (p.lpr == 16 && kvm == 4) kvm = 2;
+    p.kvm = kvm;
+    p.npt = np4 ? 4u : (uint32_t)NP;
+    p.w16 = (a.kv_half && p.qv % 4 == 0 && a.hd % 8u == 0u) ? 1u : 0u;
+    p.paged = a.pt_rows ? 1u : 0u;
+    p.kv_half = a.kv_half ? 1u : 0u;
+    p.nsplit = a.nsplit;
+    *out = p;
+    return true;
+}
+
 hipError_t launch_attention(const AttnArgs &a, uint32_t nb, hipStream_t st) {
-    if (a.hd % 4 || a.hd > 256 || a.hd < 4 || a.nsplit == 0 || a.nsplit > ATTN_MAX_NSPLIT) return hipErrorInvalidValue;
-    if (a.nsplit == 1 && !a.xba_out) return hipErrorInvalidValue;
-    if (a.hd <= 32) return launch_lpr<8, 1>(a, nb, st);
-    if (a.hd <= 64) return launch_lpr<8, 2>(a, nb, st);
-    if (a.hd <= 128) return launch_lpr<8, 4>(a, nb, st);
-    return launch_lpr<16, 4>(a, nb, st);
+    AttnPlan p;
+    if (!attention_plan(a, nb, &p)) return hipErrorInvalidValue;
+    if (p.lpr == 16) return launch_lpr<16, 4>(a, p, nb, st);
+    if (p.qv == 1) return launch_lpr<8, 1>(a, p, nb, st);
+    if (p.qv == 2) return launch_lpr<8, 2>(a, p, nb, st);
+    return launch_lpr<8, 4>(a, p, nb, st);
 }
 
 // stand-alone combine (operator tests, state read-back; the forward folds this into the Wo GEMV's prologue)

@@ -250,8 +250,10 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     // exactly the per-lane arithmetic below (same slots per lane, same DPP tree: same bits), parks it in LDS, and every lane reads the
     // finished vectors back.  Round 5 had all 32 sub-groups of a workgroup do all KVM + 1 vectors: at KVM = 4 that was 36 of a lane's 52
     // load instructions and ~500 of a wave's ~2300 VALU instructions in a launch that is VALU bound at 64 sequences (SQ_ACTIVE_INST_VALU
-    // 64 % of the SIMD cycles, profiles/r06_4b_b64_pmc_before.txt).
+    // 64 % of the SIMD cycles, profiles/r06_4b_b64_pmc_before.txt).  Wave 0 has 64 / LPR sub-groups, so KVM + 1 <= 64 / LPR: at head_dim > 128
+    // (LPR 16: four sub-groups) attention_plan() caps KVM at 2.
     constexpr bool SHARE = REGQK && !FUSE && KVM > 1;
+    static_assert(!SHARE || KVM + 1 <= 64 / LPR, "SHARE: wave 0 needs a sub-group for each q head and one for the k row");
     float4 qv[KVM][QV], kfresh[QV], vfresh[QV];
     float4 sv[SHARE ? QV : 1], snw[SHARE ? QV : 1];            // SHARE: this sub-group's vector and its norm weight
     float4 qnw[QV], knw[QV], rcs[QV], rsn[QV];

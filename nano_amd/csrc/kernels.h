@@ -182,6 +182,10 @@ struct AttnArgs {
     unsigned long long *stamps;   // measurement builds only (NANO_STAMPS): per-workgroup phase stamps, or nullptr
 };
 hipError_t launch_attention(const AttnArgs &a, uint32_t nb, hipStream_t st);
+// the attention_kernel<LPR, QV, KVM, MODE, KVH, PG, NPT, W16> launch_attention() runs for `a` and nb sequences, and the workgroup order
+// it fills in (kv_log2 / kvmul_log2 of AttnArgs); the launcher takes every choice from here.  false: the arguments are refused.
+struct AttnPlan { uint32_t mode, lpr, qv, kvm, npt, w16, paged, kv_half, nsplit, kv_log2, kvmul_log2; };
+bool attention_plan(const AttnArgs &a, uint32_t nb, AttnPlan *p);
 // q | k | v projection (Q80 group size 64, one sequence) + Qwen3 decode attention as ONE launch (gemv_q80_impl.h): the attention workgroups wait
 // for q / k / v as 8-byte {tag, value} granules in `hand` (q_dim + 2 kv_dim entries); tag = the step's tick * 128 + layer1 (device_common.h)
 bool qkv_attn_fused_supports(const GemvArgs &ga, const AttnArgs &aa);

@@ -246,3 +246,105 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     OP_HIP(hipMemcpy(d.out, dout, (size_t)d.nb * rows_total * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// One decode attention launch as enqueue_step() issues it without the fused q|k|v launch (backend.hip: the AttnArgs block before
+// launch_attention), or with `chunk` the two passes of a batched prefill chunk; split partials are combined by the batched / prefill
+// combine.  The plan that ran comes from attention_plan(), the function the launcher itself follows.
+extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc *dp) {
+    int rc; if ((rc = begin(device))) return rc;
+    if (!dp) { nano_hip_set_error_("null descriptor"); return NANO_HIP_EINVAL; }
+    const NanoAttnDecodeDesc &d = *dp;
+#define OP_ARG(cond, msg) do { if (!(cond)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; } } while (0)
+    OP_ARG(d.nb >= 1 && d.nb <= NANO_MAX_BATCH, "nb out of range");
+    OP_ARG(d.n_kv_head && d.n_head && d.n_head % d.n_kv_head == 0 && d.hd >= 4 && d.hd % 4 == 0 && d.hd <= 256, "bad attention shape");
+    OP_ARG(d.n_layer && d.layer < d.n_layer && d.S, "bad layer / S");
+    OP_ARG(d.q && d.k && d.pos && d.rope_cos && d.rope_sin && d.k_cache && d.v_cache && d.out, "missing tensor");
+    OP_ARG(!d.q_norm == !d.k_norm, "q_norm and k_norm go together");
+    const uint32_t nb = d.nb, QD = d.n_head * d.hd, KD = d.n_kv_head * d.hd, half = d.hd / 2;
+    uint32_t maxpos = 0;
+    for (uint32_t b = 0; b < nb; b++) {
+        maxpos = d.pos[b] > maxpos ? d.pos[b] : maxpos;
+        OP_ARG(!d.chunk || d.pos[b] == d.pos[0] + b, "chunk: positions must be consecutive");
+    }
+    OP_ARG(d.range_hint >= maxpos + 1 && d.range_hint <= d.S, "range_hint must cover max(pos) + 1 and stay <= S");
+    const uint32_t nsplit = d.nsplit ? d.nsplit : attention_nsplit(d.range_hint, d.hd);
+    OP_ARG(nsplit >= 1 && nsplit <= ATTN_MAX_NSPLIT, "nsplit out of range");
+    OP_ARG(!d.want_frag || (nsplit == 1 && d.hd % 64 == 0 && d.xf && d.xsf), "fragment output: nsplit 1 and hd % 64 == 0 only");
+    const bool paged = d.pool_rows != 0;
+    const uint32_t seqs = d.chunk ? 1u : nb;                       // cache slots / page-table rows
+    const size_t esz = d.kv_half ? 2 : 4;
+    const size_t cache_elems = paged ? (size_t)d.n_layer * d.pool_rows * KD : (size_t)seqs * d.n_layer * d.S * KD;
+    std::vector<uint32_t> kvrow(nb, 0u);
+    if (paged) {
+        OP_ARG(d.pool_rows % 64 == 0 && d.pt_rows && d.pt_stride, "paged: pool_rows % 64, page table");
+        for (size_t i = 0; i < (size_t)seqs * d.pt_stride; i++)
+            OP_ARG(d.pt_rows[i] == 0xffffffffu || (d.pt_rows[i] % 64 == 0 && d.pt_rows[i] < d.pool_rows && d.pool_rows - d.pt_rows[i] >= 64), "paged: a page-table entry lies outside the pool");
+        for (uint32_t b = 0; b < nb; b++) {                        // (as the embed kernel stages it)
+            const uint32_t blk = d.pos[b] >> 6, e = d.pt_rows[(size_t)(d.chunk ? 0 : b) * d.pt_stride + (blk < d.pt_stride ? blk : 0)];
+            OP_ARG(blk < d.pt_stride && e != 0xffffffffu, "paged: no page holds pos");
+            kvrow[b] = e + (d.pos[b] & 63u);
+        }
+    }
+    std::vector<float> rope_cur((size_t)nb * 2 * half);             // rope_cur[b] = { cos[pos[b]], sin[pos[b]] } (launch_embed)
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t i = 0; i < half; i++) {
+            rope_cur[(size_t)b * 2 * half + i] = d.rope_cos[(size_t)d.pos[b] * half + i];
+            rope_cur[(size_t)b * 2 * half + half + i] = d.rope_sin[(size_t)d.pos[b] * half + i];
+        }
+    DevBufs B;
+    float *dq = B.upload(d.q, (size_t)nb * QD), *dk = B.upload(d.k, (size_t)nb * KD);
+    uint32_t *dpos = B.upload(d.pos, nb);
+    float *dcos = B.upload(d.rope_cos, (size_t)d.S * half), *dsin = B.upload(d.rope_sin, (size_t)d.S * half), *dcur = B.upload(rope_cur.data(), rope_cur.size());
+    unsigned char *dkc = B.upload(reinterpret_cast<const unsigned char *>(d.k_cache), cache_elems * esz);
+    unsigned char *dvc = B.upload(reinterpret_cast<const unsigned char *>(d.v_cache), cache_elems * esz);
+    float *dout = B.alloc<float>((size_t)nb * QD), *dpart = B.alloc<float>((size_t)nb * nsplit * QD), *dml = B.alloc<float>((size_t)nb * d.n_head * nsplit * 2);
+    OP_CHECK(dq && dk && dpos && dcos && dsin && dcur && dkc && dvc && dout && dpart && dml, "device alloc failed");
+    AttnArgs a{};
+    if (d.q_norm) { a.q_norm = B.upload(d.q_norm, d.hd); a.k_norm = B.upload(d.k_norm, d.hd); OP_CHECK(a.q_norm && a.k_norm, "device alloc failed"); }
+    if (d.kv_half && d.vraw) { a.vraw = B.upload(d.vraw, (size_t)nb * KD); OP_CHECK(a.vraw, "device alloc failed"); }
+    const size_t ntile = (nb + 15) / 16, ng = QD / 64;
+    if (d.want_frag) {
+        a.xf_out = B.alloc<int8_t>(ntile * ng * 1024); a.xsf_out = B.alloc<float>(ntile * ng * 16);
+        OP_CHECK(a.xf_out && a.xsf_out, "device alloc failed");
+        OP_HIP(hipMemset(a.xf_out, 0, ntile * ng * 1024)); OP_HIP(hipMemset(a.xsf_out, 0, ntile * ng * 16 * 4));
+    }
+    if (paged) {
+        a.pt_rows = B.upload(d.pt_rows, (size_t)seqs * d.pt_stride); a.kvrow = B.upload(kvrow.data(), nb);
+        OP_CHECK(a.pt_rows && a.kvrow, "device alloc failed");
+        a.pt_stride = d.pt_stride; a.pt_bstride = d.chunk ? 0u : d.pt_stride; a.pool_rows = d.pool_rows;
+    }
+    a.q = dq; a.q_out = nullptr; a.kraw = dk; a.kcache = reinterpret_cast<float *>(dkc); a.vcache = reinterpret_cast<float *>(dvc); a.pos = dpos;
+    a.rope_cos = dcos; a.rope_sin = dsin; a.rope_cur = dcur; a.out = dpart; a.ml = dml; a.xba_out = dout; a.nsplit = nsplit; a.range_hint = d.range_hint;
+    a.layer = d.layer; a.n_layer = d.n_layer; a.S = d.S; a.hd = d.hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
+    a.q_dim = QD; a.kv_dim = KD; a.rope_qwen3 = d.rope_qwen3 ? 1u : 0u; a.is_causal = 1;
+    a.cache_bstride_rows = d.chunk ? 0u : d.n_layer * d.S; a.fixed_range = 0;
+    a.kv_half = d.kv_half ? 1u : 0u;
+    uint32_t plan[2][10] = {};
+    auto record = [&](const AttnArgs &x, uint32_t *row) -> bool {
+        AttnPlan p;
+        if (!attention_plan(x, nb, &p)) return false;
+        const uint32_t v[10] = { p.mode, p.lpr, p.qv, p.kvm, p.npt, p.w16, p.paged, p.kv_half, p.nsplit, p.kv_log2 != 0xffffffffu ? 1u : 0u };
+        memcpy(row, v, sizeof(v));
+        return true;
+    };
+    if (d.chunk) {                                                   // batched prefill, pass 1: every token's k row into the cache
+        a.prep_only = 1;
+        OP_ARG(record(a, plan[0]), "attention arguments refused");
+        OP_HIP(launch_attention(a, nb, 0));
+        a.prep_only = 0;
+    }
+    OP_ARG(record(a, plan[d.chunk ? 1 : 0]), "attention arguments refused");
+    OP_HIP(launch_attention(a, nb, 0));
+    if (nsplit > 1) OP_HIP(launch_attn_combine_tokens(dpart, dml, dout, d.n_head, d.hd, nsplit, nb, nullptr, nullptr, 0));
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(d.out, dout, (size_t)nb * QD * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(d.k_cache, dkc, cache_elems * esz, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(d.v_cache, dvc, cache_elems * esz, hipMemcpyDeviceToHost));
+    if (d.want_frag) {
+        OP_HIP(hipMemcpy(d.xf, a.xf_out, ntile * ng * 1024, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(d.xsf, a.xsf_out, ntile * ng * 16 * 4, hipMemcpyDeviceToHost));
+    }
+    if (d.plan) memcpy(d.plan, plan, sizeof(plan));
+#undef OP_ARG
+    return 0;
+}

@@ -108,6 +108,9 @@ def preset(name: str, quant: str = "f32", group_size: int = 0, block_size: Optio
         "qwen3-0.6b-3l": (ARCH_QWEN3, 256, 20000, 3, 1024, 16, 8, 3072, 128),       # Qwen3-0.6B's layer shapes, an ODD layer count (round 5's granule buffers alternated by layer parity)
         # a toy network under Qwen3's full vocabulary: the sampler's 151 936-entry softmax / nucleus at real size
         "bigvocab-qwen3": (ARCH_QWEN3, 64, 151936, 1, 64, 2, 1, 128, 32),
+        # head_dim 256 (the attention kernel's 16-lanes-per-row half); 32 q heads over 8 KV heads, so that a batched decode step of
+        # > 32 sequences (one split) and a 64-token prefill chunk reach the launcher's four-heads-per-workgroup threshold
+        "hd256-qwen3": (ARCH_QWEN3, 512, 2048, 2, 512, 32, 8, 1024, 256),
     }
     a, bs, V, L, E, nh, nkv, H, hd = table[name]
     if block_size is not None:

@@ -125,6 +125,28 @@ def test_large_batch_mfma_gemm_path(model_dir, B):
     assert worst < TOL["q80"]
 
 
+def test_head_dim_256_batched_decode_vs_oracle(oracle, model_dir):
+    """head_dim 256 (16 lanes per KV row), 33 sequences per step: one split, 32 heads x 33 sequences = 1056 head workgroups, which asks
+    for four q heads per workgroup -- where the shared q / k preparation has room for only three q heads next to the k row (the
+    launcher caps it at two).  Every sequence's logits against the oracle at every position."""
+    path, spec = synth_model(model_dir, "hd256-qwen3", "q80", 64)
+    from nano_amd import modelfile as mf
+    B, T = 33, 10
+    seqs = [mf.prompt_ids(2600 + b, T, spec.vocab_size) for b in range(B)]
+    m = nb.load_model_file(path, max_seq_len=64, max_batch=B)
+    ocs = [ob.OracleCtx(oracle, path, max_seq_len=64) for _ in range(B)]
+    worst = 0.0
+    for pos in range(T):
+        lg, _ = m.forward([int(s[pos]) for s in seqs], [pos] * B)
+        for b in range(B):
+            worst = max(worst, rel_err(lg[b], ocs[b].forward(int(seqs[b][pos]), pos)))
+    m.close()
+    for o in ocs:
+        o.close()
+    print(f"head_dim 256, {B} sequences per step: worst max|dlogit|/max|logit| vs the oracle {worst:.3e}")
+    assert worst < TOL["q80"]
+
+
 def test_small_batch_on_large_layers_takes_the_gemm_with_a_split_attention(model_dir):
     """Qwen3-4B's layer sizes, 3 sequences per step, positions past 64: the weight launches take the batched GEMM from 2
     sequences on, the attention is split, so its partials are combined by the kernel that also writes Wo's Q80 fragments.
@@ -287,7 +309,7 @@ def test_batched_steps_on_wide_rows_equal_one_by_one_decoding(model_dir, B):
 
 
 @pytest.mark.parametrize("preset,quant,gs,T", [("tiny-qwen3", "q80", 64, 5), ("tiny-qwen3", "q80", 64, 23), ("tiny-qwen3", "q80", 64, 70), ("tiny-qwen3", "q80", 64, 93),
-                                               ("tiny-nano", "f32", 0, 11), ("tiny-nano-odd", "q4k", 0, 13), ("tiny-qwen3", "f32", 0, 9)])
+                                               ("hd256-qwen3", "q80", 64, 64), ("tiny-nano", "f32", 0, 11), ("tiny-nano-odd", "q4k", 0, 13), ("tiny-qwen3", "f32", 0, 9)])
 def test_batched_prefill_equals_token_by_token(model_dir, preset, quant, gs, T):
     """nano_hip_prefill (<= 64 / 8 prompt tokens per weight read) leaves the KV cache and the next logits exactly as
     feeding the prompt one token at a time does (same kernels per token; Q80 chunks > 8 take the MFMA GEMM)."""
