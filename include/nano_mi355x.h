@@ -219,6 +219,23 @@ typedef void (*nano_hip_phase_fn)(void *env, int32_t layer, int32_t phase);
 int nano_hip_set_strict(NanoHipModel *m, int on);
 int nano_hip_set_phase_hook(NanoHipModel *m, nano_hip_phase_fn fn, void *env);
 
+/* ---- exact mode: the reference's bits from graph-replayed steps --------------------------------------------------
+ * nano_hip_set_exact(m, 1): every later step (forward, forward_begin/_end, decode_greedy, prefill, forward_sample[_batch],
+ * time_step) returns what strict mode returns -- the reference CPU engine's logits, arg-max ids and sampled tokens, bit for bit,
+ * for F32, Q80 and Q4K models -- from a step that is captured once per (batch, mode, is_causal) and replayed as a HIP graph,
+ * the on-device greedy loop included.  Its float chains are exact.hip's: rmsnorm with the sum of squares in index order out of
+ * LDS; q / k preparation + scores + softmax + weighted V of a layer in ONE launch with att[range] in LDS.  That launch needs att[max_seq_len] to fit
+ * its 64 KiB of LDS: models created with max_seq_len > 7168 keep strict mode's three attention launches (att in global memory)
+ * inside the captured step -- same bits, no context length is refused.  Prefill runs token by token (MODE_NOCLS replays).
+ * Also switched on by NANO_EXACT=1 in the environment at model creation.
+ * Interplay: strict mode wins when both are on; with a phase hook installed an exact-mode step is served by the strict step
+ * (same bits; the hook needs the eager per-operator replay); LoRA side branches, the FP16 and the paged KV cache are refused with
+ * NANO_HIP_EINVAL as in strict mode; the in-launch hand-offs (NANO_FUSE_LAUNCHES) are not used, so the mode has no give-up path.
+ * nano_hip_exact_state: *on = the switch, *graphs = exact-mode graphs instantiated, *launches_per_step = kernel nodes of the
+ * last enqueued exact step (0 before the first one, and with NANO_HIP_NO_GRAPH).  Any pointer may be NULL. */
+int nano_hip_set_exact(NanoHipModel *m, int on);
+int nano_hip_exact_state(const NanoHipModel *m, uint32_t *on, uint32_t *graphs, uint32_t *launches_per_step);
+
 /* Blocks until all work queued on the model's stream has finished. */
 int nano_hip_sync(NanoHipModel *m);
 
@@ -309,6 +326,22 @@ typedef struct NanoAttnDecodeDesc {
 } NanoAttnDecodeDesc;
 int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc *d);
 int nano_hip_op_swiglu(int device, float *hb, const float *hb2, uint32_t n);
+/* exact mode's two kernels on caller inputs (exact.hip).  rmsnorm: infer.c:601-614.  Attention: infer.c:842-879 for one sequence and
+ * one layer -- q finished (norm + RoPE), caches [S][kv_dim]; is_causal: rows 0 .. range - 1, else all S rows; long_form = 1 runs the
+ * three strict-mode launches an exact step keeps where att[S] does not fit the one-launch kernel's LDS. */
+int nano_hip_op_exact_rmsnorm(int device, float *out, const float *x, const float *w, uint32_t n);
+typedef struct NanoExactAttnDesc {
+    uint32_t n_head, n_kv_head, hd, S;
+    uint32_t range;             /* is_causal: positions attended (1 .. S) */
+    uint32_t is_causal;
+    uint32_t long_form;         /* 1: scores / softmax / weighted V as three launches, att in global memory */
+    uint32_t _pad;
+    const float *q;             /* [n_head * hd] */
+    const float *k_cache, *v_cache;        /* [S][n_kv_head * hd] */
+    float *out;                 /* [n_head * hd] */
+} NanoExactAttnDesc;
+int nano_hip_op_exact_attention(int device, const NanoExactAttnDesc *d);
+
 int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32_t *idx);
 
 /* One FUSED decode GEMV launch exactly as a decode step issues it (the role-specialised kernels: rmsnorm + activation

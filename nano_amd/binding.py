@@ -44,6 +44,12 @@ class NanoAttnDecodeDesc(C.Structure):
                                           "out", "xf", "xsf", "plan")]
 
 
+class NanoExactAttnDesc(C.Structure):
+    """include/nano_mi355x.h NanoExactAttnDesc: exact mode's attention of one sequence and one layer."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_head", "n_kv_head", "hd", "S", "range", "is_causal", "long_form", "_pad")] + \
+               [(n, C.c_void_p) for n in ("q", "k_cache", "v_cache", "out")]
+
+
 # the fields of an attention plan (nano_amd/csrc/kernels.h AttnPlan; xcd: workgroups of a KV head on one XCD)
 ATTN_PLAN_FIELDS = ("mode", "lpr", "qv", "kvm", "npt", "w16", "paged", "kv_half", "nsplit", "xcd")
 
@@ -98,6 +104,10 @@ def lib() -> C.CDLL:
     fn("nano_hip_sync", C.c_int, [vp])
     fn("nano_hip_set_strict", C.c_int, [vp, C.c_int])
     fn("nano_hip_set_phase_hook", C.c_int, [vp, PHASE_FN, vp])
+    fn("nano_hip_set_exact", C.c_int, [vp, C.c_int])
+    fn("nano_hip_exact_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
+    fn("nano_hip_op_exact_rmsnorm", C.c_int, [C.c_int, f32p, f32p, f32p, C.c_uint32])
+    fn("nano_hip_op_exact_attention", C.c_int, [C.c_int, C.POINTER(NanoExactAttnDesc)])
     fn("nano_hip_time_classifier", C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint64)])
     fn("nano_hip_time_classifier_in_step", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float)])
     fn("nano_hip_time_step", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)])
@@ -301,6 +311,16 @@ class DeviceModel:
     def set_strict(self, on: bool = True):
         """Strict-parity mode: eager, reference summation order, logits bit-identical to the reference CPU engine."""
         check(lib().nano_hip_set_strict(self.h, 1 if on else 0))
+
+    def set_exact(self, on: bool = True):
+        """Exact mode: strict mode's bits (the reference CPU engine's) from steps that are captured once and replayed as HIP graphs."""
+        check(lib().nano_hip_set_exact(self.h, 1 if on else 0))
+
+    def exact_state(self) -> dict:
+        """{'on', 'graphs' (exact-mode graphs instantiated), 'launches_per_step' (kernel nodes of the last enqueued exact step)}"""
+        on, graphs, launches = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().nano_hip_exact_state(self.h, C.byref(on), C.byref(graphs), C.byref(launches)))
+        return {"on": bool(on.value), "graphs": int(graphs.value), "launches_per_step": int(launches.value)}
 
     def set_phase_hook(self, fn=None):
         """fn(layer, phase) at the reference's twelve observation points of a strict-mode forward; None removes it."""
@@ -508,6 +528,25 @@ def op_attention(q, k_cache, v_cache, n_head, n_kv_head, head_dim, device=0):
     out = np.empty(n_head * head_dim, np.float32)
     check(lib().nano_hip_op_attention(device, out, np.ascontiguousarray(q, np.float32), np.ascontiguousarray(k_cache, np.float32),
                                       np.ascontiguousarray(v_cache, np.float32), n_head, n_kv_head, head_dim, rng)); return out
+
+
+def op_exact_rmsnorm(x, w, device=0):
+    x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+    out = np.empty_like(x)
+    check(lib().nano_hip_op_exact_rmsnorm(device, out, x, w, x.size)); return out
+
+
+def op_exact_attention(q, k_cache, v_cache, n_head, n_kv_head, head_dim, rng=None, is_causal=True, long_form=False, device=0):
+    """exact mode's attention (infer.c:842-879) of one sequence: caches [S][kv_dim]; is_causal: rows 0 .. rng - 1, else all S rows;
+    long_form: the three-launch form an exact step keeps where att[S] does not fit the one-launch kernel's LDS."""
+    q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k_cache, np.float32); v = np.ascontiguousarray(v_cache, np.float32)
+    out = np.empty(n_head * head_dim, np.float32)
+    d = NanoExactAttnDesc()
+    d.n_head, d.n_kv_head, d.hd, d.S = n_head, n_kv_head, head_dim, k.shape[0]
+    d.range = k.shape[0] if rng is None else rng
+    d.is_causal, d.long_form = int(bool(is_causal)), int(bool(long_form))
+    d.q, d.k_cache, d.v_cache, d.out = q.ctypes.data, k.ctypes.data, v.ctypes.data, out.ctypes.data
+    check(lib().nano_hip_op_exact_attention(device, C.byref(d))); return out
 
 
 def op_swiglu(hb, hb2, device=0):

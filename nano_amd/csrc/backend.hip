@@ -137,6 +137,10 @@ struct NanoHipModel {
     bool strict = false;
     float *xn = nullptr, *hb2 = nullptr, *att = nullptr;   // normalised x [Bs][E], W3 output [Bs][H], attention scores [Bs][n_head][S]
     nano_hip_phase_fn phase_fn = nullptr; void *phase_env = nullptr;
+    // exact mode (exact.hip): strict mode's bits from a step that is captured once per (batch, mode, is_causal[, prefill slot]) and replayed
+    bool exact = false;
+    std::map<uint64_t, uint32_t> exact_nodes;             // kernel nodes of each exact-mode graph (same keys as `graphs`)
+    uint32_t exact_launches = 0;                          // ... of the last enqueued exact step (0: graphs are off, nothing was counted)
     // measurement (stamps build, tools/stamp_probe.py): per-launch, per-workgroup phase stamps of the steps run after nano_hip_stamps_begin
     unsigned long long *stamps = nullptr; uint32_t stamp_launches = 0; bool stamps_on = false;
     std::vector<uint32_t> stamp_kinds;
@@ -466,6 +470,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     }
     HIP_TRY(hipDeviceSynchronize());
     *out = m;
+    if (const char *xm = getenv("NANO_EXACT")) if (*xm && *xm != '0') { const int rc = nano_hip_set_exact(m, 1); if (rc) return rc; }
     if (const char *sm = getenv("NANO_STRICT")) if (*sm && *sm != '0') return nano_hip_set_strict(m, 1);
     return NANO_HIP_OK;
 }
@@ -558,7 +563,7 @@ static Q80Route route_of(const NanoHipModel *m) {
     r.gq = m->gq; r.gxs = m->gxs; r.q4x = m->q4x; r.q4x_bytes = m->q4x_bytes;
     return r;
 }
-static RouteKind kind_of(const NanoHipModel *m, GemvArgs a) { a.ordered = m->strict ? 1u : 0u; a.cus = (uint32_t)m->cus; return route_kind(route_of(m), a); }
+static RouteKind kind_of(const NanoHipModel *m, GemvArgs a) { a.ordered = (m->strict || m->exact) ? 1u : 0u; a.cus = (uint32_t)m->cus; return route_kind(route_of(m), a); }
 
 // A kernel gave up a bounded wait since the last check (G6's finisher, a fused launch's hand-off):
 // the results of the call are not valid.  Read after a stream synchronisation; the word lives in host-mapped memory, so the check
@@ -589,7 +594,7 @@ static bool handoff_recoverable(const NanoHipModel *m, uint32_t code) {
 }
 static void drop_graphs(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    m->graphs.clear(); m->pf_graph_keys.clear();
+    m->graphs.clear(); m->pf_graph_keys.clear(); m->exact_nodes.clear();
 }
 static void handoff_fallback(NanoHipModel *m) {
     (void)hipStreamSynchronize(m->st);
@@ -599,7 +604,7 @@ static void handoff_fallback(NanoHipModel *m) {
 }
 
 static hipError_t gemv(NanoHipModel *m, GemvArgs &a) {
-    a.ordered = m->strict ? 1u : 0u;                                   // strict mode: the reference's group order in every kernel
+    a.ordered = (m->strict || m->exact) ? 1u : 0u;                     // strict / exact mode: the reference's group order in every kernel
     a.err = m->dev_err;
     a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes;
     return route_projection(route_of(m), a, m->st);
@@ -950,16 +955,156 @@ static hipError_t enqueue_step_strict(NanoHipModel *m, uint32_t nb, uint32_t is_
     return hipSuccess;
 }
 
+// scratch of the un-fused steps (strict and exact mode): normalised x, the W3 output, att in global memory
+static int strict_scratch(NanoHipModel *m) {
+    if (m->xn) return 0;
+    const size_t Bs = m->Bs;
+    if (hipMalloc(&m->xn, Bs * m->d.n_embd * 4) != hipSuccess || hipMalloc(&m->hb2, Bs * m->d.n_hidden * 4) != hipSuccess ||
+        hipMalloc(&m->att, Bs * (size_t)m->d.n_head * m->S * 4) != hipSuccess)
+        FAIL(NANO_HIP_ENOMEM, "hipMalloc for the strict-mode scratch failed");
+    return 0;
+}
+
 extern "C" int nano_hip_set_strict(NanoHipModel *m, int on) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
-    if (on && !m->xn) {
-        const size_t Bs = m->Bs;
-        if (hipMalloc(&m->xn, Bs * m->d.n_embd * 4) != hipSuccess || hipMalloc(&m->hb2, Bs * m->d.n_hidden * 4) != hipSuccess ||
-            hipMalloc(&m->att, Bs * (size_t)m->d.n_head * m->S * 4) != hipSuccess)
-            FAIL(NANO_HIP_ENOMEM, "hipMalloc for the strict-mode scratch failed");
-    }
+    if (on) { const int rc = strict_scratch(m); if (rc) return rc; }
     m->strict = on != 0;
+    return NANO_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact-mode step (exact.hip): enqueue_step_strict's operators and bits without the phase calls, so that it can be captured:
+// embed -> L x [exact rmsnorm -> q|k|v -> exact attention (q/k prep inside) -> Wo (+residual) -> exact rmsnorm -> W1|W3 -> SwiGLU ->
+// W2 (+residual)] -> exact rmsnorm -> classifier -> arg-max / loop feedback.  Every kernel reads pos[b] from device memory: one graph
+// serves every position.  Where att[max_seq_len] does not fit the one-launch attention's LDS (exact_attention_fits) the layer keeps
+// strict mode's three attention launches with att in global memory.
+// ------------------------------------------------------------------------------------------------
+static bool strict_serves(const NanoHipModel *m) { return m->strict || (m->exact && m->phase_fn); }   // strict wins; the hook needs the eager per-operator replay
+static bool exact_serves(const NanoHipModel *m) { return m->exact && !strict_serves(m); }
+
+static hipError_t enqueue_step_exact(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
+    const NanoModelDesc &d = m->d;
+    const uint32_t E = d.n_embd, H = d.n_hidden, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
+    const bool one_launch = exact_attention_fits(m->hd, S) && KD % 4u == 0;
+    hipError_t e;
+#define ST(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
+    if (m->lora_on || m->kv_half) return hipErrorNotSupported;
+    m->nsplit = 1;
+    EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
+                  m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0 };
+    ST(launch_embed(ea, nb, m->st));
+    const size_t slot_off = (size_t)slot0 * L * S * KD;
+    for (uint32_t l = 0; l < L; l++) {
+        const size_t layer_rows = (size_t)l * S;
+        ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_attn + (size_t)l * E, E, nb, E, E, m->st));          // infer.c:755-758
+        {                                                                                                 // infer.c:768-786
+            GemvArgs a{};
+            a.nseg = 3;
+            a.seg[0] = mkseg(m->W[WQ][l], m->q, QD, QD);
+            a.seg[1] = mkseg(m->W[WK][l], m->kraw, KD, KD);
+            a.seg[2] = mkseg(m->W[WV][l], m->vcache + slot_off + layer_rows * KD, KD, (uint32_t)((size_t)L * S * KD), KD);
+            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
+            ST(strict_project(m, a));
+        }
+        StrictAttnArgs sa{};
+        sa.q = m->q; sa.kraw = m->kraw; sa.kcache = m->kcache; sa.vcache = m->vcache; sa.pos = m->pos;
+        sa.q_norm = m->q_norm ? m->q_norm + (size_t)l * m->hd : nullptr;
+        sa.k_norm = m->k_norm ? m->k_norm + (size_t)l * m->hd : nullptr;
+        sa.rope_cos = m->rope_cos; sa.rope_sin = m->rope_sin; sa.att = m->att; sa.xba = m->xba;
+        sa.n_head = d.n_head; sa.n_kv_head = d.n_kv_head; sa.hd = m->hd; sa.q_dim = QD; sa.kv_dim = KD;
+        sa.layer = l; sa.n_layer = L; sa.S = S; sa.slot0 = slot0; sa.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); sa.is_causal = is_causal;
+        if (one_launch) {                                                                                 // infer.c:812-879
+            sa.fold_prep = 1;
+            ST(launch_exact_attention(sa, nb, m->st));
+        } else {
+            ST(launch_strict_qk(sa, nb, m->st));
+            ST(launch_strict_attention(sa, nb, m->st));
+        }
+        {                                                                                                 // infer.c:883-908
+            GemvArgs a{};
+            a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, E, E);
+            a.n = QD; a.gs = d.group_size; a.nb = nb; a.xin = m->xba; a.xin_bstride = QD; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
+            ST(strict_project(m, a));
+        }
+        ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_ffn + (size_t)l * E, E, nb, E, E, m->st));           // infer.c:912-914
+        {                                                                                                 // infer.c:919-944
+            GemvArgs a{};
+            a.nseg = 2; a.seg[0] = mkseg(m->W[W1][l], m->hb, H, H); a.seg[1] = mkseg(m->W[W3][l], m->hb2, H, H);
+            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
+            ST(strict_project(m, a));
+            ST(launch_strict_swiglu(m->hb, m->hb2, H, nb, H, m->st));
+        }
+        {                                                                                                 // infer.c:948-965
+            GemvArgs a{};
+            a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, E, E);
+            a.n = H; a.gs = d.group_size; a.nb = nb; a.xin = m->hb; a.xin_bstride = H; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
+            ST(strict_project(m, a));
+        }
+    }
+    if (mode == MODE_NOCLS) return hipSuccess;
+    ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_final, E, nb, E, E, m->st));                              // infer.c:997-999
+    {                                                                                                     // infer.c:1003-1015
+        GemvArgs a = classifier_args(m, nb);
+        a.xin = m->xn; a.norm_w = nullptr;
+        ST(strict_project(m, a));
+    }
+    if (mode == MODE_ARGMAX || mode == MODE_LOOP) {
+        ArgmaxArgs aa{ m->logits, d.vocab_size, d.vocab_size, m->amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
+        if (mode == MODE_LOOP) { aa.tokens = m->tokens; aa.trace = m->trace; }
+        ST(launch_argmax(aa, nb, m->st));
+    }
+#undef ST
+    return hipSuccess;
+}
+
+// one exact-mode step of sequences in KV slots slot0 .. slot0 + nb - 1: the first use of a (batch, mode, is_causal, slot0) runs eagerly
+// (the launchers validate their arguments outside any capture), then the same enqueue is captured; later uses replay
+static int run_step_exact(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
+    if (m->kv_paged) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with exact mode");
+    if (m->lora_on || m->kv_half) FAIL(NANO_HIP_EINVAL, "exact mode covers neither the LoRA side branches nor the FP16 KV cache");
+    if (!m->use_graph) { HIP_TRY(enqueue_step_exact(m, nb, is_causal, mode, slot0)); m->exact_launches = 0; return 0; }
+    const uint64_t key = (1ull << 61) | ((uint64_t)slot0 << 32) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
+    auto it = m->graphs.find(key);
+    if (it == m->graphs.end()) {
+        HIP_TRY(enqueue_step_exact(m, nb, is_causal, mode, slot0));
+        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+        HIP_TRY(hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed));
+        hipError_t e = enqueue_step_exact(m, nb, is_causal, mode, slot0);
+        hipError_t e2 = hipStreamEndCapture(m->st, &g);
+        if (e != hipSuccess || e2 != hipSuccess) {
+            if (g) (void)hipGraphDestroy(g);
+            FAIL(NANO_HIP_ERUNTIME, "graph capture of the exact step failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
+        }
+        size_t nodes = 0;
+        (void)hipGraphGetNodes(g, nullptr, &nodes);
+        hipError_t e3 = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        HIP_TRY(e3);
+        m->graphs.emplace(key, ge);
+        m->exact_nodes[key] = (uint32_t)nodes;
+        m->exact_launches = (uint32_t)nodes;
+        return 0;
+    }
+    m->nsplit = 1;
+    m->exact_launches = m->exact_nodes[key];
+    HIP_TRY(hipGraphLaunch(it->second, m->st));
+    return 0;
+}
+
+extern "C" int nano_hip_set_exact(NanoHipModel *m, int on) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null model");
+    HIP_TRY(hipSetDevice(m->device));
+    if (on) { const int rc = strict_scratch(m); if (rc) return rc; }
+    m->exact = on != 0;
+    return NANO_HIP_OK;
+}
+
+extern "C" int nano_hip_exact_state(const NanoHipModel *m, uint32_t *on, uint32_t *graphs, uint32_t *launches_per_step) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null model");
+    if (on) *on = m->exact ? 1u : 0u;
+    if (graphs) *graphs = (uint32_t)m->exact_nodes.size();
+    if (launches_per_step) *launches_per_step = m->exact_launches;
     return NANO_HIP_OK;
 }
 
@@ -987,7 +1132,9 @@ static int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t m
     uint32_t range_hint = is_causal ? ((max_pos + hint_step) / hint_step) * hint_step : m->S;
     if (range_hint > m->S) range_hint = m->S;
     if (m->kv_paged && (m->strict || m->lora_on)) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with strict mode or the LoRA side branches");
-    if (m->strict) {
+    if (exact_serves(m)) return run_step_exact(m, nb, is_causal, mode, 0);
+    if (strict_serves(m)) {
+        if (m->kv_paged) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with exact mode");
         const hipError_t e = enqueue_step_strict(m, nb, is_causal, mode, 0);
         if (e == hipErrorNotSupported) FAIL(NANO_HIP_EINVAL, "strict mode covers neither the LoRA side branches nor the FP16 KV cache");
         HIP_TRY(e);
@@ -1298,7 +1445,7 @@ extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alp
     HIP_TRY(hipStreamSynchronize(m->st));
     // graphs captured with the previous module carry its device pointers and rank in their kernel arguments
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    m->graphs.clear(); m->pf_graph_keys.clear();
+    m->graphs.clear(); m->pf_graph_keys.clear(); m->exact_nodes.clear();
     if (m->lora_buf) { (void)hipFree(m->lora_buf); m->lora_buf = nullptr; }
     if (!m->lora_o1) HIP_TRY(hipMalloc(&m->lora_o1, (size_t)m->Bs * E * 4));
     HIP_TRY(hipMalloc(&m->lora_buf, total * 4));
@@ -1327,12 +1474,12 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
     for (uint32_t i = 0; i < count; i++) if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
     HIP_TRY(hipSetDevice(m->device));
     if (m->kv_paged && count) {
-        if (m->strict || m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with strict mode or the LoRA side branches");
+        if (m->strict || m->exact || m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with strict / exact mode or the LoRA side branches");
         const uint32_t need = pos0 + count - 1;
         int rc = kv_ensure(m, &slot, &need, 1);
         if (rc) return rc;
     }
-    if (m->strict) {                                                        // strict mode: one reference-order forward per prompt token
+    if (strict_serves(m)) {                                                 // strict mode: one reference-order forward per prompt token
         for (uint32_t i = 0; i < count; i++) {
             m->h_tokens[0] = tokens[i]; m->h_pos[0] = pos0 + i;
             HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, 4, hipMemcpyHostToDevice, m->st));
@@ -1359,6 +1506,16 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         HIP_TRY(hipMemcpyAsync(m->pf_stage, tokens, (size_t)count * 4, hipMemcpyHostToDevice, m->st));          // (pageable sources: staged by the runtime before the call returns)
         HIP_TRY(hipMemcpyAsync(m->pf_stage + m->pf_cap, hp.data(), (size_t)count * 4, hipMemcpyHostToDevice, m->st));
         HIP_TRY(hipStreamSynchronize(m->st));                              // hp leaves scope; one wait per prompt
+    }
+    if (exact_serves(m)) {                                                  // exact mode: token by token too, each a MODE_NOCLS replay; one wait per prompt
+        for (uint32_t i = 0; i < count; i++) {
+            HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + i, 4, hipMemcpyDeviceToDevice, m->st));
+            HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + i, 4, hipMemcpyDeviceToDevice, m->st));
+            const int rc = run_step_exact(m, 1, 1, MODE_NOCLS, slot);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(m->st));
+        return dev_err_check(m);
     }
     for (uint32_t done = 0; done < count;) {
         uint32_t nb = (count - done < chunk_max) ? count - done : chunk_max;
@@ -1442,7 +1599,7 @@ static int decode_greedy_once(NanoHipModel *m, const uint32_t *tokens, const uin
     uint32_t max_pos = 0;
     for (uint32_t i = 0; i < batch; i++) if (pos[i] > max_pos) max_pos = pos[i];
     for (uint32_t s = 0; s < steps; s++) {
-        m->skip_embed = s > 0 && !m->strict;          // the fused path's arg-max kernel of step s - 1 embedded this step's token
+        m->skip_embed = s > 0 && !m->strict && !m->exact;   // the fused path's arg-max kernel of step s - 1 embedded this step's token
         rc = run_step(m, batch, 1, MODE_LOOP, max_pos + s);
         m->skip_embed = false;
         if (rc) return rc;

@@ -236,7 +236,8 @@ struct StrictAttnArgs {
     float *xba;             // [nb][q_dim] head outputs
     uint32_t n_head, n_kv_head, hd, q_dim, kv_dim, layer, n_layer, S;
     uint32_t slot0;         // KV slot of sequence 0 of this step (sequence b lives in slot0 + b)
-    uint32_t rope_qwen3, is_causal, _pad;
+    uint32_t rope_qwen3, is_causal;
+    uint32_t fold_prep;     // exact.hip's one-launch attention only: 1 = it also does launch_strict_qk's work (q / k [norm] + RoPE, k row store)
 };
 hipError_t launch_strict_rmsnorm(float *o, const float *x, const float *w, uint32_t n, uint32_t nvec, uint32_t x_stride, uint32_t o_stride, hipStream_t st);
 hipError_t launch_strict_qk(const StrictAttnArgs &a, uint32_t nb, hipStream_t st);
@@ -244,6 +245,14 @@ hipError_t launch_strict_attention(const StrictAttnArgs &a, uint32_t nb, hipStre
 hipError_t launch_strict_swiglu(float *hb, const float *hb2, uint32_t n, uint32_t nb, uint32_t bstride, hipStream_t st);
 hipError_t launch_strict_matmul_f32(float *out, const float *x, const float *w, uint32_t n, uint32_t d, uint32_t nb, uint32_t x_bstride,
                                     uint32_t out_bstride, uint32_t out_pstride, const uint32_t *pos, int resid, hipStream_t st);
+
+// ---- exact-mode kernels (exact.hip): strict.hip's bits from kernels made to be replayed -----------------
+// rmsnorm with the sum of squares in index order (the terms staged in LDS); scores + softmax + weighted V of one layer in ONE launch
+// with att[range] in LDS.  exact_attention_fits(): att[max_range] fits that launch's LDS -- where it does not, the step keeps
+// launch_strict_attention (att in global memory).  StrictAttnArgs as for strict.hip (att is not read by the one-launch kernel).
+hipError_t launch_exact_rmsnorm(float *o, const float *x, const float *w, uint32_t n, uint32_t nvec, uint32_t x_stride, uint32_t o_stride, hipStream_t st);
+bool exact_attention_fits(uint32_t hd, uint32_t max_range);
+hipError_t launch_exact_attention(const StrictAttnArgs &a, uint32_t nb, hipStream_t st);
 
 // ---- LoRA side branches (lora.hip) -------------------------------------------------------------------
 struct LoraArgs {

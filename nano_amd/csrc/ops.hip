@@ -163,6 +163,36 @@ extern "C" int nano_hip_op_swiglu(int device, float *hb, const float *hb2, uint3
     return 0;
 }
 
+extern "C" int nano_hip_op_exact_rmsnorm(int device, float *out, const float *x, const float *w, uint32_t n) {
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B; float *dx = B.upload(x, n), *dw = B.upload(w, n), *dout = B.alloc<float>(n);
+    OP_CHECK(dx && dw && dout, "device alloc failed");
+    OP_HIP(launch_exact_rmsnorm(dout, dx, dw, n, 1, n, n, 0));
+    OP_HIP(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nano_hip_op_exact_attention(int device, const NanoExactAttnDesc *d) {
+    int rc; if ((rc = begin(device))) return rc;
+    if (!d || !d->q || !d->k_cache || !d->v_cache || !d->out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    if (!d->n_head || !d->n_kv_head || d->n_head % d->n_kv_head || !d->hd || d->hd % 4 || d->hd > 256 || !d->S ||
+        (d->is_causal && (d->range == 0 || d->range > d->S))) { nano_hip_set_error_("bad attention shape"); return NANO_HIP_EINVAL; }
+    if (!d->long_form && !exact_attention_fits(d->hd, d->S)) { nano_hip_set_error_("S rows do not fit the one-launch kernel's LDS: set long_form"); return NANO_HIP_EINVAL; }
+    const uint32_t qd = d->n_head * d->hd, kvd = d->n_kv_head * d->hd, pos = d->is_causal ? d->range - 1u : 0u;
+    DevBufs B;
+    float *dq = B.upload(d->q, qd), *dk = B.upload(d->k_cache, (size_t)d->S * kvd), *dv = B.upload(d->v_cache, (size_t)d->S * kvd);
+    float *dout = B.alloc<float>(qd), *datt = d->long_form ? B.alloc<float>((size_t)d->n_head * d->S) : nullptr;
+    uint32_t *dpos = B.upload(&pos, 1);
+    OP_CHECK(dq && dk && dv && dout && dpos && (datt || !d->long_form), "device alloc failed");
+    StrictAttnArgs sa{};
+    sa.q = dq; sa.kcache = dk; sa.vcache = dv; sa.pos = dpos; sa.att = datt; sa.xba = dout;
+    sa.n_head = d->n_head; sa.n_kv_head = d->n_kv_head; sa.hd = d->hd; sa.q_dim = qd; sa.kv_dim = kvd;
+    sa.layer = 0; sa.n_layer = 1; sa.S = d->S; sa.slot0 = 0; sa.is_causal = d->is_causal ? 1u : 0u;
+    OP_HIP(d->long_form ? launch_strict_attention(sa, 1, 0) : launch_exact_attention(sa, 1, 0));
+    OP_HIP(hipMemcpy(d->out, dout, (size_t)qd * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32_t *idx) {
     int rc; if ((rc = begin(device))) return rc;
     DevBufs B; float *dx = B.upload(x, n); uint32_t *di = B.alloc<uint32_t>(1);
