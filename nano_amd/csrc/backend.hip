@@ -123,10 +123,10 @@ struct NanoHipModel {
     uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
     bool kv_half = false;         // opt-in FP16 KV cache: rows hold __half, v passes through vraw like k through kraw
     float *vraw = nullptr;        // [Bs][KD] fresh v rows (FP16 cache only)
-    // paged KV cache (opt-in, SURVEY 8f-3): kcache / vcache are pools [L][pages][64][KD]; pt = first pool row of every 64-position block
     // greedy loop (nano_hip_decode_greedy): from the second step on the previous step's arg-max kernel has already embedded this
     // step's token (misc.hip argmax_kernel) -- the step then starts at layer 0's QKV launch
     bool skip_embed = false;
+    // paged KV cache (opt-in, SURVEY 8f-3): kcache / vcache are pools [L][pages][64][KD]; pt = first pool row of every 64-position block
     bool kv_paged = false;
     uint32_t kv_pages = 0, pt_stride = 0;                 // pages in the pool; page-table entries per slot = ceil(S / 64)
     uint32_t *pt = nullptr, *kvrow = nullptr;             // device: [maxB][pt_stride] (0xffffffff = no page), [Bs] pool row of the step's position
@@ -640,15 +640,47 @@ static uint32_t step_nsplit(const NanoHipModel *m, uint32_t nb, uint32_t range_h
     return ns ? ns : 1;
 }
 
-// the Wo launch of a step of nb sequences: with the plain (combined, normalised) attention output as its input, and -- a split
-// attention -- with the splits' partials as its input (combined in its prologue: SLAB GEMV)
-static GemvArgs wo_args(const NanoHipModel *m, uint32_t nb, uint32_t nsplit) {
-    GemvArgs wa{};
-    wa.nseg = 1; wa.seg[0] = mkseg(m->W[WO][0], m->x, m->d.n_embd, m->d.n_embd); wa.n = m->QD; wa.gs = m->d.group_size; wa.nb = nb;
-    wa.xin = m->xba; wa.xin_bstride = m->QD; wa.epi = GEMV_EPI_RESID;
-    if (m->lora_on) { wa.resid_add = m->lora_o1; wa.resid_add_bstride = m->d.n_embd; }
-    if (nsplit > 1) { wa.attn_part = m->attn_part; wa.attn_ml = m->attn_ml; wa.attn_nsplit = nsplit; wa.attn_n_head = m->d.n_head; wa.attn_hd = m->hd; }
-    return wa;
+// ---- the four projection launches of layer l: ONE builder each, for the fast step, the reference-order step and the routing
+// questions alike.  The arguments are what differs between the callers; what a caller adds afterwards (stamps, frag_ready, the
+// fused launches' ordered / cus / err) stays with that caller.  route_kind() reads only shapes, nb, epi, attn_part, resid_add and
+// xq_in (route.hip), none of which depends on the layer: a question asked with layer 0's tensor is answered as for layer l's launch.
+static GemvArgs proj_args(const NanoHipModel *m, uint32_t nb, uint32_t n, const float *xin, uint32_t epi) {
+    GemvArgs a{};
+    a.n = n; a.gs = m->d.group_size; a.nb = nb; a.xin = xin; a.xin_bstride = n; a.epi = epi; a.pos = m->pos;
+    return a;
+}
+// q | raw k | v from xin (norm_w: the rmsnorm its prologue applies, or nullptr for an input that is normalised already); v goes to
+// v_out + b * v_bstride + pos[b] * v_pstride   reference infer.c:758-786
+static GemvArgs qkv_args(const NanoHipModel *m, uint32_t l, uint32_t nb, const float *xin, const float *norm_w, float *v_out, uint32_t v_bstride, uint32_t v_pstride) {
+    GemvArgs a = proj_args(m, nb, m->d.n_embd, xin, GEMV_EPI_STORE);
+    a.nseg = 3;
+    a.seg[0] = mkseg(m->W[WQ][l], m->q, m->QD, m->QD);
+    a.seg[1] = mkseg(m->W[WK][l], m->kraw, m->KD, m->KD);
+    a.seg[2] = mkseg(m->W[WV][l], v_out, m->KD, v_bstride, v_pstride);
+    a.norm_w = norm_w;
+    return a;
+}
+// x += Wo . xba (+ the LoRA o-branch's o1): with the plain (combined, normalised) attention output as its input, and -- nsplit > 1 --
+// with the splits' partials as its input (combined in its prologue: SLAB GEMV)   reference infer.c:885-908
+static GemvArgs wo_args(const NanoHipModel *m, uint32_t l, uint32_t nb, uint32_t nsplit) {
+    GemvArgs a = proj_args(m, nb, m->QD, m->xba, GEMV_EPI_RESID);
+    a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, m->d.n_embd, m->d.n_embd);
+    if (m->lora_on) { a.resid_add = m->lora_o1; a.resid_add_bstride = m->d.n_embd; }
+    if (nsplit > 1) { a.attn_part = m->attn_part; a.attn_ml = m->attn_ml; a.attn_nsplit = nsplit; a.attn_n_head = m->d.n_head; a.attn_hd = m->hd; }
+    return a;
+}
+// W1 | W3 from xin: epi SWIGLU leaves hb = silu(W1 . xn) * (W3 . xn) (w3_out = hb), epi STORE the two products (w3_out = hb2)   infer.c:914-944
+static GemvArgs w13_args(const NanoHipModel *m, uint32_t l, uint32_t nb, const float *xin, const float *norm_w, float *w3_out, uint32_t epi) {
+    GemvArgs a = proj_args(m, nb, m->d.n_embd, xin, epi);
+    a.nseg = 2; a.seg[0] = mkseg(m->W[W1][l], m->hb, m->d.n_hidden, m->d.n_hidden); a.seg[1] = mkseg(m->W[W3][l], w3_out, m->d.n_hidden, m->d.n_hidden);
+    a.norm_w = norm_w;
+    return a;
+}
+// x += W2 . hb   reference infer.c:950-965
+static GemvArgs w2_args(const NanoHipModel *m, uint32_t l, uint32_t nb) {
+    GemvArgs a = proj_args(m, nb, m->d.n_hidden, m->hb, GEMV_EPI_RESID);
+    a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, m->d.n_embd, m->d.n_embd);
+    return a;
 }
 // does the Wo launch combine the `nsplit` partials itself?  (else: a combine kernel of its own in front of it)
 static bool wo_takes_parts(const NanoHipModel *m, uint32_t nb, uint32_t nsplit) {
@@ -656,8 +688,8 @@ static bool wo_takes_parts(const NanoHipModel *m, uint32_t nb, uint32_t nsplit) 
     // the plain-activation route first: a Wo launch the batched GEMM would take (Qwen3-4B at 2..8 sequences) keeps it -- the splits are
     // then combined by a kernel of its own.  (Asking only about the launch WITH the partials attached always answered "GEMV": the
     // batched routes refuse partials, and 4 sequences beyond 64 positions ran the 8-sequence SLAB GEMV: 2.6 ms against 2.0.)
-    if (route_takes_fragments(kind_of(m, wo_args(m, nb, 1)))) return false;
-    return route_takes_attn_parts(kind_of(m, wo_args(m, nb, nsplit)));
+    if (route_takes_fragments(kind_of(m, wo_args(m, 0, nb, 1)))) return false;
+    return route_takes_attn_parts(kind_of(m, wo_args(m, 0, nb, nsplit)));
 }
 // splits nano_hip_read_state still has to combine xba from after a decode step (1: the step left it final)
 static uint32_t xba_nsplit(const NanoHipModel *m, uint32_t nb, uint32_t range_hint) {
@@ -668,7 +700,7 @@ static uint32_t xba_nsplit(const NanoHipModel *m, uint32_t nb, uint32_t range_hi
 // range_hint: host-side upper bound of the attended range of every sequence (a multiple of 64, <= S)
 static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint) {
     const NanoModelDesc &d = m->d;
-    const uint32_t E = d.n_embd, H = d.n_hidden, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
+    const uint32_t E = d.n_embd, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
     hipError_t e;
     // Batched prefill splits every token's attention exactly as that token's own decode step would (chunks start on
     // multiples of the 64-position bucket, so one range_hint covers them) and combines with a kernel of its own: the KV
@@ -678,7 +710,8 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
     // GEMV's prologue combines?  Then a split attention is combined by a kernel of its own (as in batched prefill) -- for
     // <= 8 splits the same arithmetic, same bits.
     const bool pf_combine = nsplit > 1 && !wo_takes_parts(m, nb, nsplit);
-    const bool wo_gemm = route_takes_fragments(kind_of(m, wo_args(m, nb, pf_combine ? 1u : nsplit)));
+    const uint32_t wo_nsplit = pf_combine ? 1u : nsplit;                     // splits the Wo launch combines in its prologue
+    const bool wo_gemm = route_takes_fragments(kind_of(m, wo_args(m, 0, nb, wo_nsplit)));
     m->nsplit = pf_combine ? 1 : nsplit;
     // Single-split attention (or the combine kernel) of a step whose Wo launch goes to the batched GEMM: that kernel writes
     // Wo's quantized input itself (Q80 groups of 64 inside a head, fragment order) -- one quantizer launch less per layer.
@@ -696,19 +729,14 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
 
     for (uint32_t l = 0; l < L; l++) {
         const size_t layer_rows = (size_t)l * S;                    // cache row offset of this layer within a slot
-        GemvArgs qa{};
         AttnArgs a{};
-        // q | raw k | v (straight into the cache row)   reference infer.c:758-786
-        qa.nseg = 3;
-        qa.seg[0] = mkseg(m->W[WQ][l], m->q, QD, QD);
-        qa.seg[1] = mkseg(m->W[WK][l], m->kraw, KD, KD);
-        // v goes straight to its cache row; prefill: every token of the step is a position of KV slot pf_slot
-        qa.seg[2] = m->kv_half ? mkseg(m->W[WV][l], m->vraw, KD, KD)          // FP16 cache: the attention kernel rounds and stores the row
-                  : m->kv_paged ? mkseg(m->W[WV][l], m->vcache + (size_t)l * plane, KD, 0, KD)      // paged: row kvrow[b] of this layer's plane
-                  : m->pf ? mkseg(m->W[WV][l], m->vcache + ((size_t)m->pf_slot * L * S + layer_rows) * KD, KD, 0, KD)
-                          : mkseg(m->W[WV][l], m->vcache + layer_rows * KD, KD, (uint32_t)((size_t)L * S * KD), KD);
-        qa.n = E; qa.gs = d.group_size; qa.nb = nb; qa.xin = m->x; qa.xin_bstride = E; qa.epi = GEMV_EPI_STORE;
-        qa.norm_w = m->rms_attn + (size_t)l * E; qa.pos = (m->kv_paged && !m->kv_half) ? m->kvrow : m->pos;     // (the only position-indexed output)
+        // q | raw k | v; v goes straight to its cache row; prefill: every token of the step is a position of KV slot pf_slot
+        const float *xn_w = m->rms_attn + (size_t)l * E;
+        GemvArgs qa = m->kv_half ? qkv_args(m, l, nb, m->x, xn_w, m->vraw, KD, 0)      // FP16 cache: the attention kernel rounds and stores the row
+                    : m->kv_paged ? qkv_args(m, l, nb, m->x, xn_w, m->vcache + (size_t)l * plane, 0, KD)      // paged: row kvrow[b] of this layer's plane
+                    : m->pf ? qkv_args(m, l, nb, m->x, xn_w, m->vcache + ((size_t)m->pf_slot * L * S + layer_rows) * KD, 0, KD)
+                            : qkv_args(m, l, nb, m->x, xn_w, m->vcache + layer_rows * KD, (uint32_t)((size_t)L * S * KD), KD);
+        if (m->kv_paged && !m->kv_half) qa.pos = m->kvrow;                  // (v's is the only position-indexed output)
         // qk-norm, rope, k-cache write, attention   reference infer.c:810-879
         a.err = m->dev_err;
         a.q = m->q; a.q_out = nullptr; a.kraw = m->kraw; a.kcache = m->kcache; a.vcache = m->vcache; a.pos = m->pos;
@@ -771,23 +799,16 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
             if (pf_combine && (e = launch_attn_combine_tokens(m->attn_part, m->attn_ml, m->xba, d.n_head, m->hd, nsplit, nb, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
         }
         {   // x += Wo . xba   reference infer.c:885-908
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, E, E);
-            a.n = QD; a.gs = d.group_size; a.nb = nb; a.xin = m->xba; a.xin_bstride = QD; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
             if (m->lora_on) {       // o1 = (alpha/rank) B_o (A_o xba), added by the Wo epilogue: x += (Wo xba + o1)   infer.c:898-908
                 LoraArgs la_{};
                 la_.x = m->xba; la_.qa = m->lora_t[6] + (size_t)l * m->lora_rank * E; la_.qb = m->lora_t[7] + (size_t)l * E * m->lora_rank;
                 la_.q = m->lora_o1; la_.E = E; la_.KD = KD; la_.rank = m->lora_rank; la_.alpha = m->lora_alpha;
                 if ((e = launch_lora_o(la_, nb, m->st)) != hipSuccess) return e;
-                a.resid_add = m->lora_o1; a.resid_add_bstride = E;
             }
-            if (nsplit > 1 && !pf_combine) { a.attn_part = m->attn_part; a.attn_ml = m->attn_ml; a.attn_nsplit = nsplit; a.attn_n_head = d.n_head; a.attn_hd = m->hd; }
+            GemvArgs a = wo_args(m, l, nb, wo_nsplit);
             a.frag_ready = wo_frag ? 1u : 0u;
             // hb = silu(W1 . xn) * (W3 . xn)   reference infer.c:914-944
-            GemvArgs b{};
-            b.nseg = 2; b.seg[0] = mkseg(m->W[W1][l], m->hb, H, H); b.seg[1] = mkseg(m->W[W3][l], m->hb, H, H);
-            b.n = E; b.gs = d.group_size; b.nb = nb; b.xin = m->x; b.xin_bstride = E; b.epi = GEMV_EPI_SWIGLU;
-            b.norm_w = m->rms_ffn + (size_t)l * E; b.pos = m->pos;
+            GemvArgs b = w13_args(m, l, nb, m->x, m->rms_ffn + (size_t)l * E, m->hb, GEMV_EPI_SWIGLU);
             // ONE launch for both (one sequence, Q80 group size 64; gemv_q80_impl.h wo_w13_fused_kernel): W1|W3's workgroups take x from Wo's as
             // granules of the same launch (epoch tags like the q | k | v + attention launch's).
             a.ordered = 0; a.cus = (uint32_t)m->cus; a.err = m->dev_err; b.ordered = 0; b.cus = (uint32_t)m->cus; b.err = m->dev_err;
@@ -809,9 +830,7 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
             }
         }
         {   // x += W2 . hb   reference infer.c:950-965
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, E, E);
-            a.n = H; a.gs = d.group_size; a.nb = nb; a.xin = m->hb; a.xin_bstride = H; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
+            GemvArgs a = w2_args(m, l, nb);
             a.stamps = next_stamps(m, 5);
             if ((e = gemv(m, a)) != hipSuccess) return e;
         }
@@ -848,11 +867,17 @@ static hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal,
 }
 
 // ------------------------------------------------------------------------------------------------
-// strict-parity step (strict.hip): eager, one kernel per reference operator, every float chain in the reference's order.
-// Quantizers, quantized GEMVs, embedding, RoPE, residual adds and arg-max are the fast path's own (bit-exact) kernels, fed
-// with un-normalised launches (norm_w = nullptr); rmsnorm / attention / SwiGLU / the FP32 matmul are strict.hip's.
-// Sequence b of the step lives in KV slot slot0 + b.  The optional phase hook fires where the reference fires its
-// observation callback (infer.c:755-949, 985-1003), after everything queued before it has finished.
+// the reference-order step of strict mode (strict.hip) and exact mode (exact.hip): one kernel per reference operator, every float
+// chain in the reference's order.  Quantizers, quantized GEMVs, embedding, RoPE, residual adds and arg-max are the fast path's own
+// (bit-exact) kernels, fed with un-normalised launches (norm_w = nullptr); rmsnorm / attention / SwiGLU / the FP32 matmul are
+// strict.hip's or exact.hip's.  Sequence b of the step lives in KV slot slot0 + b.
+//   strict mode (exact_kernels = false): eager.  The optional phase hook fires where the reference fires its observation callback
+//     (infer.c:755-949, 985-1003), after everything queued before it has finished.
+//   exact mode (exact_kernels = true): the same operators and bits with no phase call in between, so that the step can be captured:
+//     embed -> L x [exact rmsnorm -> q|k|v -> exact attention (q/k prep inside) -> Wo (+residual) -> exact rmsnorm -> W1|W3 -> SwiGLU ->
+//     W2 (+residual)] -> exact rmsnorm -> classifier -> arg-max / loop feedback.  Every kernel reads pos[b] from device memory: one graph
+//     serves every position.  Where att[max_seq_len] does not fit the one-launch attention's LDS (exact_attention_fits) the layer keeps
+//     strict mode's attention launches with att in global memory.
 // ------------------------------------------------------------------------------------------------
 static hipError_t strict_phase(NanoHipModel *m, int32_t layer, int32_t phase) {
     if (!m->phase_fn) return hipSuccess;
@@ -864,7 +889,7 @@ static hipError_t strict_phase(NanoHipModel *m, int32_t layer, int32_t phase) {
 
 // out = W . act for one weight tensor / a run of them, strict flavour: FP32 -> sequential matmul per segment (residual
 // added in place), Q80 / Q4K -> the bit-exact GEMV kernels on the un-normalised input
-static hipError_t strict_project(NanoHipModel *m, GemvArgs &a) {
+static hipError_t strict_project(NanoHipModel *m, GemvArgs a) {
     if (m->d.quant_type != NANO_QUANT_F32) return gemv(m, a);
     for (uint32_t s = 0; s < a.nseg; s++) {
         const GemvSeg &g = a.seg[s];
@@ -875,33 +900,29 @@ static hipError_t strict_project(NanoHipModel *m, GemvArgs &a) {
     return hipSuccess;
 }
 
-static hipError_t enqueue_step_strict(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
+// (the caller has asked step_served(): neither the LoRA side branches nor the FP16 / paged KV cache are on)
+static hipError_t enqueue_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0, bool exact_kernels) {
     const NanoModelDesc &d = m->d;
     const uint32_t E = d.n_embd, H = d.n_hidden, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
+    const bool one_launch = exact_kernels && exact_attention_fits(m->hd, S) && KD % 4u == 0;
     hipError_t e;
 #define ST(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
-    if (m->lora_on || m->kv_half) return hipErrorNotSupported;
+    // the two things the modes do differently between operators.  A step that is captured makes no phase call at all, not even the
+    // early-out one: nothing that could synchronise may sit in a capture.
+    auto phase = [&](int32_t layer, int32_t ph) { return exact_kernels ? hipSuccess : strict_phase(m, layer, ph); };
+    auto rmsnorm = [&](const float *w) { return exact_kernels ? launch_exact_rmsnorm(m->xn, m->x, w, E, nb, E, E, m->st) : launch_strict_rmsnorm(m->xn, m->x, w, E, nb, E, E, m->st); };
     m->nsplit = 1;                                                      // xba holds final head outputs (nano_hip_read_state, also from inside the hook)
-    ST(strict_phase(m, -1, 1));                                         // NANO_LLM_PHASE_EMBEDDING
+    ST(phase(-1, 1));                                                   // NANO_LLM_PHASE_EMBEDDING
     EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
                   m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0 };
     ST(launch_embed(ea, nb, m->st));
     const size_t slot_off = (size_t)slot0 * L * S * KD;
     for (uint32_t l = 0; l < L; l++) {
-        const size_t layer_rows = (size_t)l * S;
-        ST(strict_phase(m, (int32_t)l, 2));                             // ATTN_NORM   infer.c:755-758
-        ST(launch_strict_rmsnorm(m->xn, m->x, m->rms_attn + (size_t)l * E, E, nb, E, E, m->st));
-        ST(strict_phase(m, (int32_t)l, 3));                             // QKV         infer.c:768-786
-        {
-            GemvArgs a{};
-            a.nseg = 3;
-            a.seg[0] = mkseg(m->W[WQ][l], m->q, QD, QD);
-            a.seg[1] = mkseg(m->W[WK][l], m->kraw, KD, KD);
-            a.seg[2] = mkseg(m->W[WV][l], m->vcache + slot_off + layer_rows * KD, KD, (uint32_t)((size_t)L * S * KD), KD);
-            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
-            ST(strict_project(m, a));
-        }
-        ST(strict_phase(m, (int32_t)l, 4));                             // QK_ROPE     infer.c:812-835
+        ST(phase(l, 2));                                                // ATTN_NORM   infer.c:755-758
+        ST(rmsnorm(m->rms_attn + (size_t)l * E));
+        ST(phase(l, 3));                                                // QKV         infer.c:768-786
+        ST(strict_project(m, qkv_args(m, l, nb, m->xn, nullptr, m->vcache + slot_off + (size_t)l * S * KD, (uint32_t)((size_t)L * S * KD), KD)));
+        ST(phase(l, 4));                                                // QK_ROPE     infer.c:812-835
         StrictAttnArgs sa{};
         sa.q = m->q; sa.kraw = m->kraw; sa.kcache = m->kcache; sa.vcache = m->vcache; sa.pos = m->pos;
         sa.q_norm = m->q_norm ? m->q_norm + (size_t)l * m->hd : nullptr;
@@ -909,38 +930,28 @@ static hipError_t enqueue_step_strict(NanoHipModel *m, uint32_t nb, uint32_t is_
         sa.rope_cos = m->rope_cos; sa.rope_sin = m->rope_sin; sa.att = m->att; sa.xba = m->xba;
         sa.n_head = d.n_head; sa.n_kv_head = d.n_kv_head; sa.hd = m->hd; sa.q_dim = QD; sa.kv_dim = KD;
         sa.layer = l; sa.n_layer = L; sa.S = S; sa.slot0 = slot0; sa.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); sa.is_causal = is_causal;
-        ST(launch_strict_qk(sa, nb, m->st));
-        ST(strict_phase(m, (int32_t)l, 5));                             // MHA         infer.c:839-879
-        ST(launch_strict_attention(sa, nb, m->st));
-        ST(strict_phase(m, (int32_t)l, 6));                             // O           infer.c:883-908
-        {
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, E, E);
-            a.n = QD; a.gs = d.group_size; a.nb = nb; a.xin = m->xba; a.xin_bstride = QD; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
-            ST(strict_project(m, a));
+        if (one_launch) {                                               // exact.hip: both in one launch
+            sa.fold_prep = 1;
+            ST(launch_exact_attention(sa, nb, m->st));
+        } else {
+            ST(launch_strict_qk(sa, nb, m->st));
+            ST(phase(l, 5));                                            // MHA         infer.c:839-879
+            ST(launch_strict_attention(sa, nb, m->st));
         }
-        ST(strict_phase(m, (int32_t)l, 7));                             // FFN_NORM    infer.c:912-914
-        ST(launch_strict_rmsnorm(m->xn, m->x, m->rms_ffn + (size_t)l * E, E, nb, E, E, m->st));
-        ST(strict_phase(m, (int32_t)l, 8));                             // W1W3        infer.c:919-944
-        {
-            GemvArgs a{};
-            a.nseg = 2; a.seg[0] = mkseg(m->W[W1][l], m->hb, H, H); a.seg[1] = mkseg(m->W[W3][l], m->hb2, H, H);
-            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
-            ST(strict_project(m, a));
-            ST(launch_strict_swiglu(m->hb, m->hb2, H, nb, H, m->st));
-        }
-        ST(strict_phase(m, (int32_t)l, 9));                             // W2          infer.c:948-965
-        {
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, E, E);
-            a.n = H; a.gs = d.group_size; a.nb = nb; a.xin = m->hb; a.xin_bstride = H; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
-            ST(strict_project(m, a));
-        }
+        ST(phase(l, 6));                                                // O           infer.c:883-908
+        ST(strict_project(m, wo_args(m, l, nb, 1)));
+        ST(phase(l, 7));                                                // FFN_NORM    infer.c:912-914
+        ST(rmsnorm(m->rms_ffn + (size_t)l * E));
+        ST(phase(l, 8));                                                // W1W3        infer.c:919-944
+        ST(strict_project(m, w13_args(m, l, nb, m->xn, nullptr, m->hb2, GEMV_EPI_STORE)));
+        ST(launch_strict_swiglu(m->hb, m->hb2, H, nb, H, m->st));
+        ST(phase(l, 9));                                                // W2          infer.c:948-965
+        ST(strict_project(m, w2_args(m, l, nb)));
     }
     if (mode == MODE_NOCLS) return hipSuccess;
-    ST(strict_phase(m, (int32_t)L, 10));                                // FINAL_NORM  infer.c:997-999
-    ST(launch_strict_rmsnorm(m->xn, m->x, m->rms_final, E, nb, E, E, m->st));
-    ST(strict_phase(m, (int32_t)L, 11));                                // CLASSIFY    infer.c:1003-1015
+    ST(phase(L, 10));                                                   // FINAL_NORM  infer.c:997-999
+    ST(rmsnorm(m->rms_final));
+    ST(phase(L, 11));                                                   // CLASSIFY    infer.c:1003-1015
     {
         GemvArgs a = classifier_args(m, nb);
         a.xin = m->xn; a.norm_w = nullptr;
@@ -955,147 +966,28 @@ static hipError_t enqueue_step_strict(NanoHipModel *m, uint32_t nb, uint32_t is_
     return hipSuccess;
 }
 
-// scratch of the un-fused steps (strict and exact mode): normalised x, the W3 output, att in global memory
-static int strict_scratch(NanoHipModel *m) {
+// scratch of the reference-order step (strict and exact mode): normalised x, the W3 output, att in global memory
+static int ordered_scratch(NanoHipModel *m) {
     if (m->xn) return 0;
     const size_t Bs = m->Bs;
     if (hipMalloc(&m->xn, Bs * m->d.n_embd * 4) != hipSuccess || hipMalloc(&m->hb2, Bs * m->d.n_hidden * 4) != hipSuccess ||
         hipMalloc(&m->att, Bs * (size_t)m->d.n_head * m->S * 4) != hipSuccess)
-        FAIL(NANO_HIP_ENOMEM, "hipMalloc for the strict-mode scratch failed");
+        FAIL(NANO_HIP_ENOMEM, "hipMalloc for the scratch of strict / exact mode failed");
     return 0;
 }
 
 extern "C" int nano_hip_set_strict(NanoHipModel *m, int on) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
-    if (on) { const int rc = strict_scratch(m); if (rc) return rc; }
+    if (on) { const int rc = ordered_scratch(m); if (rc) return rc; }
     m->strict = on != 0;
     return NANO_HIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// exact-mode step (exact.hip): enqueue_step_strict's operators and bits without the phase calls, so that it can be captured:
-// embed -> L x [exact rmsnorm -> q|k|v -> exact attention (q/k prep inside) -> Wo (+residual) -> exact rmsnorm -> W1|W3 -> SwiGLU ->
-// W2 (+residual)] -> exact rmsnorm -> classifier -> arg-max / loop feedback.  Every kernel reads pos[b] from device memory: one graph
-// serves every position.  Where att[max_seq_len] does not fit the one-launch attention's LDS (exact_attention_fits) the layer keeps
-// strict mode's three attention launches with att in global memory.
-// ------------------------------------------------------------------------------------------------
-static bool strict_serves(const NanoHipModel *m) { return m->strict || (m->exact && m->phase_fn); }   // strict wins; the hook needs the eager per-operator replay
-static bool exact_serves(const NanoHipModel *m) { return m->exact && !strict_serves(m); }
-
-static hipError_t enqueue_step_exact(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
-    const NanoModelDesc &d = m->d;
-    const uint32_t E = d.n_embd, H = d.n_hidden, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
-    const bool one_launch = exact_attention_fits(m->hd, S) && KD % 4u == 0;
-    hipError_t e;
-#define ST(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
-    if (m->lora_on || m->kv_half) return hipErrorNotSupported;
-    m->nsplit = 1;
-    EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
-                  m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0 };
-    ST(launch_embed(ea, nb, m->st));
-    const size_t slot_off = (size_t)slot0 * L * S * KD;
-    for (uint32_t l = 0; l < L; l++) {
-        const size_t layer_rows = (size_t)l * S;
-        ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_attn + (size_t)l * E, E, nb, E, E, m->st));          // infer.c:755-758
-        {                                                                                                 // infer.c:768-786
-            GemvArgs a{};
-            a.nseg = 3;
-            a.seg[0] = mkseg(m->W[WQ][l], m->q, QD, QD);
-            a.seg[1] = mkseg(m->W[WK][l], m->kraw, KD, KD);
-            a.seg[2] = mkseg(m->W[WV][l], m->vcache + slot_off + layer_rows * KD, KD, (uint32_t)((size_t)L * S * KD), KD);
-            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
-            ST(strict_project(m, a));
-        }
-        StrictAttnArgs sa{};
-        sa.q = m->q; sa.kraw = m->kraw; sa.kcache = m->kcache; sa.vcache = m->vcache; sa.pos = m->pos;
-        sa.q_norm = m->q_norm ? m->q_norm + (size_t)l * m->hd : nullptr;
-        sa.k_norm = m->k_norm ? m->k_norm + (size_t)l * m->hd : nullptr;
-        sa.rope_cos = m->rope_cos; sa.rope_sin = m->rope_sin; sa.att = m->att; sa.xba = m->xba;
-        sa.n_head = d.n_head; sa.n_kv_head = d.n_kv_head; sa.hd = m->hd; sa.q_dim = QD; sa.kv_dim = KD;
-        sa.layer = l; sa.n_layer = L; sa.S = S; sa.slot0 = slot0; sa.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); sa.is_causal = is_causal;
-        if (one_launch) {                                                                                 // infer.c:812-879
-            sa.fold_prep = 1;
-            ST(launch_exact_attention(sa, nb, m->st));
-        } else {
-            ST(launch_strict_qk(sa, nb, m->st));
-            ST(launch_strict_attention(sa, nb, m->st));
-        }
-        {                                                                                                 // infer.c:883-908
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, E, E);
-            a.n = QD; a.gs = d.group_size; a.nb = nb; a.xin = m->xba; a.xin_bstride = QD; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
-            ST(strict_project(m, a));
-        }
-        ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_ffn + (size_t)l * E, E, nb, E, E, m->st));           // infer.c:912-914
-        {                                                                                                 // infer.c:919-944
-            GemvArgs a{};
-            a.nseg = 2; a.seg[0] = mkseg(m->W[W1][l], m->hb, H, H); a.seg[1] = mkseg(m->W[W3][l], m->hb2, H, H);
-            a.n = E; a.gs = d.group_size; a.nb = nb; a.xin = m->xn; a.xin_bstride = E; a.epi = GEMV_EPI_STORE; a.pos = m->pos;
-            ST(strict_project(m, a));
-            ST(launch_strict_swiglu(m->hb, m->hb2, H, nb, H, m->st));
-        }
-        {                                                                                                 // infer.c:948-965
-            GemvArgs a{};
-            a.nseg = 1; a.seg[0] = mkseg(m->W[W2][l], m->x, E, E);
-            a.n = H; a.gs = d.group_size; a.nb = nb; a.xin = m->hb; a.xin_bstride = H; a.epi = GEMV_EPI_RESID; a.pos = m->pos;
-            ST(strict_project(m, a));
-        }
-    }
-    if (mode == MODE_NOCLS) return hipSuccess;
-    ST(launch_exact_rmsnorm(m->xn, m->x, m->rms_final, E, nb, E, E, m->st));                              // infer.c:997-999
-    {                                                                                                     // infer.c:1003-1015
-        GemvArgs a = classifier_args(m, nb);
-        a.xin = m->xn; a.norm_w = nullptr;
-        ST(strict_project(m, a));
-    }
-    if (mode == MODE_ARGMAX || mode == MODE_LOOP) {
-        ArgmaxArgs aa{ m->logits, d.vocab_size, d.vocab_size, m->amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
-        if (mode == MODE_LOOP) { aa.tokens = m->tokens; aa.trace = m->trace; }
-        ST(launch_argmax(aa, nb, m->st));
-    }
-#undef ST
-    return hipSuccess;
-}
-
-// one exact-mode step of sequences in KV slots slot0 .. slot0 + nb - 1: the first use of a (batch, mode, is_causal, slot0) runs eagerly
-// (the launchers validate their arguments outside any capture), then the same enqueue is captured; later uses replay
-static int run_step_exact(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
-    if (m->kv_paged) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with exact mode");
-    if (m->lora_on || m->kv_half) FAIL(NANO_HIP_EINVAL, "exact mode covers neither the LoRA side branches nor the FP16 KV cache");
-    if (!m->use_graph) { HIP_TRY(enqueue_step_exact(m, nb, is_causal, mode, slot0)); m->exact_launches = 0; return 0; }
-    const uint64_t key = (1ull << 61) | ((uint64_t)slot0 << 32) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
-    auto it = m->graphs.find(key);
-    if (it == m->graphs.end()) {
-        HIP_TRY(enqueue_step_exact(m, nb, is_causal, mode, slot0));
-        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-        HIP_TRY(hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed));
-        hipError_t e = enqueue_step_exact(m, nb, is_causal, mode, slot0);
-        hipError_t e2 = hipStreamEndCapture(m->st, &g);
-        if (e != hipSuccess || e2 != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            FAIL(NANO_HIP_ERUNTIME, "graph capture of the exact step failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
-        }
-        size_t nodes = 0;
-        (void)hipGraphGetNodes(g, nullptr, &nodes);
-        hipError_t e3 = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        HIP_TRY(e3);
-        m->graphs.emplace(key, ge);
-        m->exact_nodes[key] = (uint32_t)nodes;
-        m->exact_launches = (uint32_t)nodes;
-        return 0;
-    }
-    m->nsplit = 1;
-    m->exact_launches = m->exact_nodes[key];
-    HIP_TRY(hipGraphLaunch(it->second, m->st));
-    return 0;
 }
 
 extern "C" int nano_hip_set_exact(NanoHipModel *m, int on) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
-    if (on) { const int rc = strict_scratch(m); if (rc) return rc; }
+    if (on) { const int rc = ordered_scratch(m); if (rc) return rc; }
     m->exact = on != 0;
     return NANO_HIP_OK;
 }
@@ -1114,8 +1006,83 @@ extern "C" int nano_hip_set_phase_hook(NanoHipModel *m, nano_hip_phase_fn fn, vo
     return NANO_HIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// which step serves the model's switches, and which combinations none does
+// ------------------------------------------------------------------------------------------------
+static bool strict_serves(const NanoHipModel *m) { return m->strict || (m->exact && m->phase_fn); }   // strict wins; the hook needs the eager per-operator replay
+static bool exact_serves(const NanoHipModel *m) { return m->exact && !strict_serves(m); }
+
+// THE place that says which combinations of (strict, exact, phase hook, LoRA, FP16 KV, paged KV) are served: asked by run_step and
+// nano_hip_prefill before they queue anything.  The reference-order step has neither the LoRA side branches nor the FP16 or paged
+// cache; the fast step has no LoRA side branches on a paged or FP16 cache (they write FP32 v rows of the contiguous cache).
+// prefill: batched prefill has never refused LoRA on the FP16 cache; kept as it is.
+static int step_served(const NanoHipModel *m, bool prefill) {
+    if (strict_serves(m) || exact_serves(m)) {
+        const char *mode = m->strict ? "strict mode" : exact_serves(m) ? "exact mode" : "exact mode with a phase hook";
+        if (m->kv_paged) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with %s", mode);
+        if (m->lora_on || m->kv_half) FAIL(NANO_HIP_EINVAL, "%s covers neither the LoRA side branches nor the FP16 KV cache", mode);
+        return 0;
+    }
+    if (m->kv_paged && m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with the LoRA side branches");
+    if (m->kv_half && m->lora_on && !prefill) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// HIP graphs of a step: replay the graph stored under `key`, or -- first use -- run enqueue() eagerly (the launchers set their kernel
+// attributes and validate their arguments outside any capture), capture the same enqueue() for the replays to come, instantiate and
+// store it.  Reports and leaves the policy to the caller: `step` is the error of the work this call had to queue (the replay or the
+// eager run), `capture` that of making the graph (the step itself has run), `stored` / `nodes` a graph made by this call.
+// enqueue is a template parameter: a replay pays the map lookup and hipGraphLaunch, nothing for the callable.
+// ------------------------------------------------------------------------------------------------
+struct GraphRun { hipError_t step = hipSuccess, capture = hipSuccess; bool stored = false; uint32_t nodes = 0; };
+template <class Enqueue>
+static GraphRun graph_step(NanoHipModel *m, uint64_t key, Enqueue enqueue) {
+    GraphRun r;
+    auto it = m->graphs.find(key);
+    if (it != m->graphs.end()) { r.step = hipGraphLaunch(it->second, m->st); return r; }
+    if ((r.step = enqueue()) != hipSuccess) return r;
+    if ((r.capture = hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed)) != hipSuccess) return r;
+    hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+    r.capture = enqueue();
+    const hipError_t e2 = hipStreamEndCapture(m->st, &g);               // (always: the stream must leave capture mode)
+    if (r.capture == hipSuccess) r.capture = e2;
+    size_t nodes = 0;
+    if (r.capture == hipSuccess) (void)hipGraphGetNodes(g, nullptr, &nodes);
+    if (r.capture == hipSuccess) r.capture = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    if (r.capture == hipSuccess) { m->graphs.emplace(key, ge); r.stored = true; r.nodes = (uint32_t)nodes; }
+    return r;
+}
+// the policy of the decode steps: either failure fails the call
+static int graph_step_check(const GraphRun &r) {
+    if (r.step != hipSuccess) FAIL(NANO_HIP_ERUNTIME, "queueing a decode step failed: %s", hipGetErrorString(r.step));
+    if (r.capture != hipSuccess) FAIL(NANO_HIP_ERUNTIME, "graph capture of a decode step failed: %s", hipGetErrorString(r.capture));
+    return 0;
+}
+
+// one reference-order step of the sequences in KV slots slot0 .. slot0 + nb - 1 (the caller has asked step_served()).  Strict mode
+// runs eagerly; exact mode replays one graph per (batch, mode, is_causal, slot0).
+static int run_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
+    const bool exact = exact_serves(m);
+    m->nsplit = 1;
+    if (!exact || !m->use_graph) {
+        HIP_TRY(enqueue_step_ordered(m, nb, is_causal, mode, slot0, exact));
+        if (exact) m->exact_launches = 0;
+        return 0;
+    }
+    const uint64_t key = (1ull << 61) | ((uint64_t)slot0 << 32) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
+    const GraphRun r = graph_step(m, key, [&] { return enqueue_step_ordered(m, nb, is_causal, mode, slot0, true); });
+    if (const int rc = graph_step_check(r)) return rc;
+    if (r.stored) m->exact_nodes[key] = r.nodes;
+    m->exact_launches = m->exact_nodes[key];
+    return 0;
+}
+
 // max_pos: largest position among the sequences of this step (host knowledge; the device reads the exact pos[b])
 static int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos) {
+    if (const int rc = step_served(m, false)) return rc;
+    if (strict_serves(m) || exact_serves(m)) return run_step_ordered(m, nb, is_causal, mode, 0);
     // The attention kernel issues its K / V loads before it knows pos (one memory round trip saved): it loads the rows below
     // range_hint and masks those beyond pos.  The hint is rounded up to the 64 positions of a split's range.  Round 3 measured
     // a hint rounded to 16 (the last block's rows beyond it are not fetched; four times as many graphs): 1845.9 vs 1846.0 tok/s
@@ -1131,16 +1098,6 @@ static int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t m
     const uint32_t hint_step = (nb >= 9u && !(m->pf && m->hd > 128u)) ? 16u : 64u;
     uint32_t range_hint = is_causal ? ((max_pos + hint_step) / hint_step) * hint_step : m->S;
     if (range_hint > m->S) range_hint = m->S;
-    if (m->kv_paged && (m->strict || m->lora_on)) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with strict mode or the LoRA side branches");
-    if (exact_serves(m)) return run_step_exact(m, nb, is_causal, mode, 0);
-    if (strict_serves(m)) {
-        if (m->kv_paged) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with exact mode");
-        const hipError_t e = enqueue_step_strict(m, nb, is_causal, mode, 0);
-        if (e == hipErrorNotSupported) FAIL(NANO_HIP_EINVAL, "strict mode covers neither the LoRA side branches nor the FP16 KV cache");
-        HIP_TRY(e);
-        return 0;
-    }
-    if (m->kv_half && m->lora_on) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");
     // (measurement builds: NANO_STAMPS_GRAPH=1 captures the stamped step too -- the stamp slots are baked into a graph of its own key)
 #if NANO_STAMPS
     static const bool stamps_graph = getenv("NANO_STAMPS_GRAPH") && *getenv("NANO_STAMPS_GRAPH") == '1';
@@ -1150,28 +1107,9 @@ static int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t m
     if (!m->use_graph || (m->stamps_on && !stamps_graph)) { HIP_TRY(enqueue_step(m, nb, is_causal, mode, range_hint)); m->nsplit = xba_nsplit(m, nb, range_hint); return 0; }
     const uint64_t key = ((uint64_t)(m->stamps_on ? 1 : 0) << 50) | ((uint64_t)((m->skip_embed && mode == MODE_LOOP) ? 1 : 0) << 49) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) |
                          ((uint64_t)range_hint << 16) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
-    auto it = m->graphs.find(key);
-    if (it == m->graphs.end()) {
-        // first use: THIS step runs eagerly (the launchers set their kernel attributes and validate their arguments outside
-        // any capture), then the same enqueue is captured for the replays to come
-        HIP_TRY(enqueue_step(m, nb, is_causal, mode, range_hint));
-        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-        HIP_TRY(hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed));
-        hipError_t e = enqueue_step(m, nb, is_causal, mode, range_hint);
-        hipError_t e2 = hipStreamEndCapture(m->st, &g);
-        if (e != hipSuccess || e2 != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            FAIL(NANO_HIP_ERUNTIME, "graph capture failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
-        }
-        HIP_TRY(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        m->graphs.emplace(key, ge);
-        m->nsplit = xba_nsplit(m, nb, range_hint);
-        return 0;
-    }
+    const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, is_causal, mode, range_hint); });
     m->nsplit = xba_nsplit(m, nb, range_hint);
-    HIP_TRY(hipGraphLaunch(it->second, m->st));
-    return 0;
+    return graph_step_check(r);
 }
 
 extern "C" int nano_hip_sync(NanoHipModel *m) {
@@ -1444,8 +1382,7 @@ extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alp
     if (n_floats < total) FAIL(NANO_HIP_EINVAL, "LoRA parameter block too small: %zu floats, need %zu", n_floats, total);
     HIP_TRY(hipStreamSynchronize(m->st));
     // graphs captured with the previous module carry its device pointers and rank in their kernel arguments
-    for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    m->graphs.clear(); m->pf_graph_keys.clear(); m->exact_nodes.clear();
+    drop_graphs(m);
     if (m->lora_buf) { (void)hipFree(m->lora_buf); m->lora_buf = nullptr; }
     if (!m->lora_o1) HIP_TRY(hipMalloc(&m->lora_o1, (size_t)m->Bs * E * 4));
     HIP_TRY(hipMalloc(&m->lora_buf, total * 4));
@@ -1473,8 +1410,8 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
     if ((uint64_t)pos0 + count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed the model's RoPE table (%u rows = block_size)", pos0, pos0 + count, m->rope_rows);
     for (uint32_t i = 0; i < count; i++) if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
     HIP_TRY(hipSetDevice(m->device));
+    if (count) { const int rc = step_served(m, true); if (rc) return rc; }     // (an empty prompt queues nothing: there is nothing to refuse)
     if (m->kv_paged && count) {
-        if (m->strict || m->exact || m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with strict / exact mode or the LoRA side branches");
         const uint32_t need = pos0 + count - 1;
         int rc = kv_ensure(m, &slot, &need, 1);
         if (rc) return rc;
@@ -1484,9 +1421,8 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
             m->h_tokens[0] = tokens[i]; m->h_pos[0] = pos0 + i;
             HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, 4, hipMemcpyHostToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, 4, hipMemcpyHostToDevice, m->st));
-            const hipError_t e = enqueue_step_strict(m, 1, 1, MODE_NOCLS, slot);
-            if (e == hipErrorNotSupported) FAIL(NANO_HIP_EINVAL, "strict mode does not cover the LoRA side branches");
-            HIP_TRY(e);
+            const int rc = run_step_ordered(m, 1, 1, MODE_NOCLS, slot);
+            if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(m->st));
         }
         return 0;
@@ -1511,7 +1447,7 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         for (uint32_t i = 0; i < count; i++) {
             HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + i, 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + i, 4, hipMemcpyDeviceToDevice, m->st));
-            const int rc = run_step_exact(m, 1, 1, MODE_NOCLS, slot);
+            const int rc = run_step_ordered(m, 1, 1, MODE_NOCLS, slot);
             if (rc) return rc;
         }
         HIP_TRY(hipStreamSynchronize(m->st));
@@ -1531,32 +1467,18 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
             // a full 64-token chunk recurs in every long prompt: one HIP graph per (KV slot, range bucket) -- positions and
             // tokens are device data, the slot's cache addresses are baked into the nodes.  Other chunk lengths run eagerly
             // (a capture costs more than the ~300 launches it would save once).
+            // The chunk that meets a (slot, bucket) first runs eagerly and is captured for the next prompt that reaches it; a failed
+            // capture only costs the replays (r.capture is not looked at).  The cache of chunk graphs is bounded (oldest out).
             const uint64_t key = (1ull << 62) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
-            auto it = m->graphs.find(key);
-            if (it == m->graphs.end()) {
-                // first use: the chunk itself runs eagerly (kernel attributes are set outside the capture), then it is captured
-                // for the next prompt that reaches this (slot, bucket).  The cache of chunk graphs is bounded (oldest out).
-                e = enqueue_step(m, nb, 1, MODE_NOCLS, range_hint);
-                hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-                hipError_t ec = e == hipSuccess ? hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed) : e;
-                if (ec == hipSuccess) {
-                    ec = enqueue_step(m, nb, 1, MODE_NOCLS, range_hint);
-                    const hipError_t e2 = hipStreamEndCapture(m->st, &g);
-                    if (ec == hipSuccess) ec = e2;
+            const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, MODE_NOCLS, range_hint); });
+            e = r.step;
+            if (r.stored) {
+                if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
+                    auto old = m->graphs.find(m->pf_graph_keys.front());
+                    if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
+                    m->pf_graph_keys.erase(m->pf_graph_keys.begin());
                 }
-                if (ec == hipSuccess) ec = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-                if (g) (void)hipGraphDestroy(g);
-                if (ec == hipSuccess) {
-                    if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
-                        auto old = m->graphs.find(m->pf_graph_keys.front());
-                        if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
-                        m->pf_graph_keys.erase(m->pf_graph_keys.begin());
-                    }
-                    m->graphs.emplace(key, ge);
-                    m->pf_graph_keys.push_back(key);
-                }                                                              // (a failed capture only costs the replays)
-            } else {
-                e = hipGraphLaunch(it->second, m->st);
+                m->pf_graph_keys.push_back(key);
             }
         } else {
             e = enqueue_step(m, nb, 1, MODE_NOCLS, range_hint);            // eager: one pass per chunk
@@ -1646,6 +1568,11 @@ extern "C" int nano_hip_debug_fault(NanoHipModel *m, uint32_t flags) {
 // ------------------------------------------------------------------------------------------------
 // measurement
 // ------------------------------------------------------------------------------------------------
+static uint64_t classifier_bytes(const NanoHipModel *m) {
+    const uint64_t VE = (uint64_t)m->d.vocab_size * m->d.n_embd;
+    return (m->d.quant_type == NANO_QUANT_F32) ? 4 * VE : (m->d.quant_type == NANO_QUANT_Q80) ? VE + 4 * (VE / m->d.group_size) : VE * 160 / 256;
+}
+
 extern "C" int nano_hip_time_classifier(NanoHipModel *m, uint32_t batch, uint32_t iters, float *ms_per_launch, uint64_t *bytes_per_launch) {
     if (!m || !iters || batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH) FAIL(NANO_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(m->device));
@@ -1656,17 +1583,18 @@ extern "C" int nano_hip_time_classifier(NanoHipModel *m, uint32_t batch, uint32_
     HIP_TRY(hipEventSynchronize(m->ev1));
     float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, m->ev0, m->ev1));
     if (ms_per_launch) *ms_per_launch = ms / iters;
-    if (bytes_per_launch) {
-        const uint64_t VE = (uint64_t)m->d.vocab_size * m->d.n_embd;
-        *bytes_per_launch = (m->d.quant_type == NANO_QUANT_F32) ? 4 * VE
-                          : (m->d.quant_type == NANO_QUANT_Q80) ? VE + 4 * (VE / m->d.group_size) : VE * 160 / 256;
-    }
+    if (bytes_per_launch) *bytes_per_launch = classifier_bytes(m);
     return 0;
 }
 
-static uint64_t classifier_bytes(const NanoHipModel *m) {
-    const uint64_t VE = (uint64_t)m->d.vocab_size * m->d.n_embd;
-    return (m->d.quant_type == NANO_QUANT_F32) ? 4 * VE : (m->d.quant_type == NANO_QUANT_Q80) ? VE + 4 * (VE / m->d.group_size) : VE * 160 / 256;
+// the batch the step probes time: `batch` sequences, each token 1 at position pos (their pages taken, tokens and positions queued)
+static int stage_probe_batch(NanoHipModel *m, uint32_t batch, uint32_t pos) {
+    for (uint32_t i = 0; i < batch; i++) { m->h_tokens[i] = 1 % m->d.vocab_size; m->h_pos[i] = pos; }
+    const int rc = kv_ensure_batch(m, m->h_pos, batch, 0, false);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, batch * 4, hipMemcpyHostToDevice, m->st));
+    HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
+    return 0;
 }
 
 // The classifier launch timed INSIDE whole decode steps (its weights are cold: the layers' 468 MB went through the
@@ -1676,10 +1604,7 @@ extern "C" int nano_hip_time_classifier_in_step(NanoHipModel *m, uint32_t batch,
                                                 uint64_t *bytes_per_launch, float *ms_empty_pair) {
     if (!m || !iters || batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH || pos >= m->S) FAIL(NANO_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(m->device));
-    for (uint32_t i = 0; i < batch; i++) { m->h_tokens[i] = 1 % m->d.vocab_size; m->h_pos[i] = pos; }
-    { const int rc = kv_ensure_batch(m, m->h_pos, batch, 0, false); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, batch * 4, hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
+    { const int rc = stage_probe_batch(m, batch, pos); if (rc) return rc; }
     uint32_t range_hint = ((pos + 1 + 63) / 64) * 64;
     if (range_hint > m->S) range_hint = m->S;
     double cls = 0.0, empty = 0.0;
@@ -1704,11 +1629,8 @@ extern "C" int nano_hip_time_classifier_in_step(NanoHipModel *m, uint32_t batch,
 extern "C" int nano_hip_time_step(NanoHipModel *m, uint32_t batch, uint32_t pos, uint32_t iters, float *ms_per_step) {
     if (!m || !iters || batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH || pos >= m->S) FAIL(NANO_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(m->device));
-    for (uint32_t i = 0; i < batch; i++) { m->h_tokens[i] = 1 % m->d.vocab_size; m->h_pos[i] = pos; }
     int rc;
-    if ((rc = kv_ensure_batch(m, m->h_pos, batch, 0, false))) return rc;
-    HIP_TRY(hipMemcpyAsync(m->tokens, m->h_tokens, batch * 4, hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(m->pos, m->h_pos, batch * 4, hipMemcpyHostToDevice, m->st));
+    if ((rc = stage_probe_batch(m, batch, pos))) return rc;
     if ((rc = run_step(m, batch, 1, MODE_ARGMAX, pos))) return rc;       // warm / capture
     HIP_TRY(hipEventRecord(m->ev0, m->st));
     for (uint32_t i = 0; i < iters; i++) if ((rc = run_step(m, batch, 1, MODE_ARGMAX, pos))) return rc;
