@@ -219,6 +219,12 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
 int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                               Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
                               uint32_t *out_ids);
+/* Ingest prefix_ids[0..n_prefix) once per device and make it the first n_prefix positions of sequences 0..batch-1 of the
+ * context (the sequences nano_forward_batch addresses): N continuations of one prompt, or N questions behind one instruction
+ * prefix, pay the prompt once.  With replicas (sequence i -> replica i mod G, slot i / G) each replica ingests the prefix into
+ * its slot 0 and forks it into the other slots of its share (nano_hip_kv_fork, nano_mi355x.h: a copy, or shared pages on a paged
+ * cache).  Applies the context's LoRA selection as nano_forward_batch does.  Returns 0 or a NANO_HIP_E* code. */
+int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch);
 /* Replicas of the context's model on the listed further GPUs of the node, in this process: nano_forward_batch then serves
  * sequence i from replica i mod (1 + n_devices) (replica 0 = the context's own device) and the replicas decode their
  * shares concurrently -- independent sequences shard trivially, no collective.  The one-process-per-GPU

@@ -92,7 +92,11 @@ int  nano_hip_model_create(NanoHipModel **out, const NanoModelDesc *desc, const 
  * nano_hip_kv_release(); a step that finds no free page fails with NANO_HIP_ENOMEM and changes nothing.  The pool holds
  * NANO_KV_PAGES pages (environment; default max_batch * ceil(max_seq_len / 64) = what the slots would have held), so more
  * slots than the memory for full-length sequences can be open when most are short.  Combinable with NANO_HIP_KV_F16; not with
- * strict mode or LoRA.  nano_hip_model_create() applies it when NANO_KV_PAGED=1 is set in the environment. */
+ * strict mode or LoRA.  nano_hip_model_create() applies it when NANO_KV_PAGED=1 is set in the environment.
+ * Pages can have several owners: nano_hip_kv_fork() below points the destinations' table entries at the source's full pages (no byte
+ * moves) and every page keeps an owner count.  A page with more than one owner is read-only: a step that is about to write into one
+ * first gives the writing slot a copy of its own (copy-on-write: one free page per such block, NANO_HIP_ENOMEM and nothing changed when
+ * the pool has none), and nano_hip_kv_release() returns a page to the pool only when its last owner leaves. */
 #define NANO_HIP_KV_PAGED 2u
 int  nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc *desc, const void *params, size_t params_bytes,
                               int params_on_device, int device, uint32_t max_seq_len, uint32_t max_batch, uint32_t flags);
@@ -101,6 +105,21 @@ void nano_hip_model_destroy(NanoHipModel *m);
  * use / in the pool.  Both fail with NANO_HIP_EINVAL on a model without NANO_HIP_KV_PAGED. */
 int  nano_hip_kv_release(NanoHipModel *m, uint32_t slot);
 int  nano_hip_kv_pages(const NanoHipModel *m, uint32_t *in_use, uint32_t *total);
+/* Share a prefix between slots.  Make positions 0 .. n_pos-1 of every slot in dst_slots[0..n_dst) hold the K / V rows that
+ * src_slot holds there, in every layer.  Afterwards each destination behaves exactly like a slot that was fed the same n_pos tokens
+ * itself (bit for bit: batched prefill does not depend on the slot).  Both cache layouts, FP32 and FP16 rows, every mode.
+ * Contiguous cache: the rows are copied (one launch for all destinations; the source is read once); rows >= n_pos of a destination
+ * stay as they are.  Paged cache: a destination first gives back what it holds; every full 64-position block below n_pos is SHARED
+ * (the destination's table entry points at the source's page, see NANO_HIP_KV_PAGED); a partial last block is copied into a page of
+ * the destination's own whose rows from n_pos % 64 on are zero; blocks the source has not mapped stay unmapped.
+ * NANO_HIP_EINVAL: null model / list, a slot >= max_batch, n_pos > max_seq_len, the source or a duplicate in dst_slots.
+ * n_pos == 0 is valid (paged: the destinations end up empty).  NANO_HIP_ENOMEM: the pool cannot supply the partial-block pages
+ * from its free pages plus the pages only the destinations own; nothing has changed then.  The work is queued on the model's
+ * stream behind what is already there.  The reference has no counterpart (one cache per context, infer/infer.c:46-51). */
+int  nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_pos, const uint32_t *dst_slots, uint32_t n_dst);
+/* paged models: pages that currently have more than one owner; page copies made so far because a slot wrote into a page it
+ * shared (copy-on-write), since the model was created.  NANO_HIP_EINVAL on a model without NANO_HIP_KV_PAGED. */
+int  nano_hip_kv_sharing(const NanoHipModel *m, uint32_t *shared_pages, uint64_t *cow_copies);
 /* number of parameter-blob bytes the backend expects for `desc` (0 if it cannot be derived
  * without reading the blob, i.e. Q4K whose tensor frames carry their own sizes) */
 size_t nano_hip_params_bytes(const NanoModelDesc *desc);

@@ -127,6 +127,9 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
+    fn("nano_hip_kv_fork", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32])
+    fn("nano_hip_kv_sharing", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)])
+    fn("nano_prefill_shared", C.c_int, [vp, u32p, C.c_uint32, C.c_uint32])
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_set_fusion", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_debug_fault", C.c_int, [vp, C.c_uint32])
@@ -352,6 +355,18 @@ class DeviceModel:
         """paged KV cache: (pages in use, pages in the pool)"""
         a, b = C.c_uint32(0), C.c_uint32(0)
         check(lib().nano_hip_kv_pages(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def kv_fork(self, src: int, n_pos: int, dsts: Sequence[int]):
+        """Make positions 0..n_pos-1 of every slot in dsts hold slot src's K / V rows (nano_hip_kv_fork): a copy on the contiguous
+        cache; on the paged cache the full 64-position pages are shared (copy-on-write) and a partial last block is copied."""
+        d = np.ascontiguousarray(dsts, np.uint32).reshape(-1)
+        check(lib().nano_hip_kv_fork(self.h, src, n_pos, d, d.size))
+
+    def kv_sharing(self):
+        """paged KV cache: (pages with more than one owner, copy-on-write page copies made so far)"""
+        a, b = C.c_uint32(0), C.c_uint64(0)
+        check(lib().nano_hip_kv_sharing(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
     def handoff_state(self):
@@ -629,6 +644,11 @@ class Engine:
         check(self.L.nano_forward_batch(self.ctx, t, p, t.size, logits.ctypes.data if want_logits else None,
                                         None if want_logits else amax.ctypes.data))
         return logits if want_logits else amax
+
+    def prefill_shared(self, prefix: Sequence[int], batch: int):
+        """nano_prefill_shared: ingest the prefix once per device and make it positions 0..len(prefix)-1 of sequences 0..batch-1."""
+        t = np.ascontiguousarray(prefix, np.uint32).reshape(-1)
+        check(self.L.nano_prefill_shared(self.ctx, t, t.size, batch))
 
     def forward_batch_sample(self, tokens: Sequence[int], pos: Sequence[int], samplers, histories) -> np.ndarray:
         """nano_forward_batch_sample: one decode step of B sequences, sequence i sampled with samplers[i] (from build_sampler)

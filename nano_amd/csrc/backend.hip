@@ -132,7 +132,12 @@ struct NanoHipModel {
     uint32_t *pt = nullptr, *kvrow = nullptr;             // device: [maxB][pt_stride] (0xffffffff = no page), [Bs] pool row of the step's position
     uint32_t *h_pt = nullptr;                             // pinned host mirror of pt
     std::vector<uint32_t> free_pages;
-    std::vector<std::vector<uint32_t>> pt_stage;           // staging copies of page-table rows whose upload may still be queued (kv_ensure)
+    std::vector<uint32_t> page_owners;                     // slots whose table points at each page (0: free; > 1: shared, read-only until copied on write)
+    uint64_t cow_copies = 0;                               // pages copied because a slot was about to write into a page it shared
+    std::vector<std::vector<uint32_t>> pt_stage;           // staging copies of page-table rows / copy jobs whose upload may still be queued (kv_ensure, nano_hip_kv_fork)
+    // row copies between slots / pages (kv_copy.hip): the device job list of the launch being queued, grown on demand
+    uint32_t *kv_jobs = nullptr; size_t kv_jobs_cap = 0;   // capacity in 32-bit words
+    bool kv_copy_nt = false;                               // NANO_KV_COPY_NT=1: non-temporal stores in the copy kernel (measurement, tools/prefix_probe.py)
     // strict-parity / per-phase mode (strict.hip): eager, one kernel per reference operator, reference summation order
     bool strict = false;
     float *xn = nullptr, *hb2 = nullptr, *att = nullptr;   // normalised x [Bs][E], W3 output [Bs][H], attention scores [Bs][n_head][S]
@@ -221,7 +226,7 @@ static void destroy(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
-                    m->xn, m->hb2, m->att, m->vraw, m->stamps, m->pt, m->kvrow, m->hand, m->hand2, m->tick };
+                    m->xn, m->hb2, m->att, m->vraw, m->stamps, m->pt, m->kvrow, m->hand, m->hand2, m->tick, m->kv_jobs };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->h_pt };
     for (void *p : host) if (p) (void)hipHostFree(p);
@@ -437,6 +442,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
         if (ok) {
             memset(m->h_pt, 0xff, ptn * 4);
             for (uint32_t pg = m->kv_pages; pg-- > 0;) m->free_pages.push_back(pg);           // pages are handed out in ascending order
+            m->page_owners.assign(m->kv_pages, 0u);
         }
     }
     if (!ok) { destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc for KV cache / scratch failed (batch %zu, seq %u)", B, max_seq_len); }
@@ -454,6 +460,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     if (hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&m->ev0) != hipSuccess ||
         hipEventCreate(&m->ev1) != hipSuccess || hipEventCreate(&m->ev2) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ERUNTIME, "stream/event creation failed"); }
     if (getenv("NANO_HIP_NO_GRAPH")) m->use_graph = false;
+    if (const char *nt = getenv("NANO_KV_COPY_NT")) m->kv_copy_nt = *nt && *nt != '0';
     if (const char *mm = getenv("NANO_MFMA_MIN_NB")) { const uint32_t v = (uint32_t)strtoul(mm, nullptr, 0); if (v >= 2) m->mfma_min_nb = v; }
     // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch (higher bits are ignored).
     // Default 3; 0 = the five launches per layer; same bits in every setting
@@ -483,40 +490,91 @@ extern "C" uint64_t nano_hip_weight_bytes_per_step(const NanoHipModel *m) { retu
 // ------------------------------------------------------------------------------------------------
 enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3 };
 
+// ---- row copies between slots / pages (kv_copy.hip) ---------------------------------------------------------------------------
+// Queues ONE copy launch for `jobs` on the model's stream.  gstart cuts the list into groups that share a source (kernels.h KvCopyArgs);
+// plane_rows = cache rows of one layer plane in the layout the rows are counted in (contiguous: max_seq_len, with slot s starting at row
+// s * L * S of "plane 0"; paged: pages * 64).  The list goes to the device from a staging copy of its own, like the page-table rows.
+static hipError_t kv_copy_enqueue(NanoHipModel *m, const std::vector<KvCopyJob> &jobs, const std::vector<uint32_t> &gstart, size_t plane_rows) {
+    if (jobs.empty()) return hipSuccess;
+    const size_t head = (gstart.size() + 3) & ~(size_t)3, words = head + jobs.size() * 4;       // jobs start 16-byte aligned
+    if (words > m->kv_jobs_cap) {
+        hipError_t e = hipStreamSynchronize(m->st);                        // (a queued launch may still read the old list)
+        if (e != hipSuccess) return e;
+        if (m->kv_jobs) { (void)hipFree(m->kv_jobs); m->kv_jobs = nullptr; m->kv_jobs_cap = 0; }
+        const size_t cap = words < 1024 ? 1024 : 2 * words;
+        if ((e = hipMalloc(reinterpret_cast<void **>(&m->kv_jobs), cap * 4)) != hipSuccess) return e;
+        m->kv_jobs_cap = cap;
+    }
+    m->pt_stage.emplace_back(words, 0u);
+    std::vector<uint32_t> &stage = m->pt_stage.back();
+    memcpy(stage.data(), gstart.data(), gstart.size() * 4);
+    memcpy(stage.data() + head, jobs.data(), jobs.size() * sizeof(KvCopyJob));
+    hipError_t e = hipMemcpyAsync(m->kv_jobs, stage.data(), words * 4, hipMemcpyHostToDevice, m->st);
+    if (e != hipSuccess) return e;
+    uint32_t max_rows = 0;
+    for (const KvCopyJob &j : jobs) if (j.rows > max_rows) max_rows = j.rows;
+    const size_t esz = m->kv_half ? 2 : 4;
+    KvCopyArgs a{};
+    a.k = m->kcache; a.v = m->vcache;
+    a.row_bytes = (uint32_t)(m->KD * esz); a.plane_bytes = (uint64_t)plane_rows * a.row_bytes;
+    a.n_groups = (uint32_t)gstart.size() - 1;
+    a.gstart = m->kv_jobs; a.jobs = reinterpret_cast<const KvCopyJob *>(m->kv_jobs + head);
+    return launch_kv_copy(a, m->d.n_layer, max_rows, (uint32_t)m->cus, m->kv_copy_nt, m->st);
+}
+// staging rows of copies long done: drop them behind a sync
+static int kv_stage_trim(NanoHipModel *m) {
+    if (m->pt_stage.size() > 256) {
+        HIP_TRY(hipStreamSynchronize(m->st));
+        m->pt_stage.clear();
+    }
+    return 0;
+}
+
 // ---- paged KV cache: pages for the positions a call is about to touch ------------------------------------------------------
-// need[i] = last position slot slots[i] will hold after the call.  All or nothing: when the pool cannot cover every missing block
-// the call fails before taking a page.  New pages are zero-filled in every layer plane (the reference callocs its cache,
-// infer.c:33,47) and the slots' table rows go to the device behind everything queued so far.
-static int kv_ensure(NanoHipModel *m, const uint32_t *slots, const uint32_t *need, uint32_t n) {
+// first[i] / need[i] = first position slot slots[i] WRITES in the call / last position it will hold after it.  All or nothing: when the
+// pool cannot cover every block the call fails before taking a page.  A block without a page gets one, zero-filled in every layer plane
+// (the reference callocs its cache, infer.c:33,47).  A block the call writes into whose page has other owners as well (nano_hip_kv_fork)
+// gets a page of this slot's own with the 64 rows copied in all planes -- copy-on-write, one launch for all such blocks of the call -- and
+// the old page loses an owner; when several owners write in one call the last one keeps the page.  The slots' table rows go to the
+// device behind everything queued so far.
+static int kv_ensure(NanoHipModel *m, const uint32_t *slots, const uint32_t *first, const uint32_t *need, uint32_t n) {
     if (!m->kv_paged) return 0;
-    size_t missing = 0;
-    for (uint32_t i = 0; i < n; i++)
-        for (uint32_t blk = 0; blk <= need[i] >> 6 && blk < m->pt_stride; blk++)
-            if (m->h_pt[(size_t)slots[i] * m->pt_stride + blk] == 0xffffffffu) {
-                bool dup = false;                                  // (the same slot twice in one call: count its block once)
-                for (uint32_t k = 0; k < i && !dup; k++) dup = slots[k] == slots[i] && blk <= need[k] >> 6;
-                if (!dup) missing++;
-            }
-    if (missing > m->free_pages.size())
-        FAIL(NANO_HIP_ENOMEM, "paged KV cache: %zu more pages needed, %zu free of %u (nano_hip_kv_release() returns a finished sequence's pages)", missing, m->free_pages.size(), m->kv_pages);
-    if (!missing) return 0;
-    const size_t esz = m->kv_half ? 2 : 4, page_bytes = (size_t)64 * m->KD * esz, plane_bytes = (size_t)m->kv_pages * page_bytes;
-    // Take the pages, zero them, send the table rows; COMMIT (host table, free list) only when every call succeeded -- a failing memset or
-    // copy gives the pages back and leaves the host table as it was (round-3 advice: pages leaked / host and device tables diverged).
-    // Each changed row goes to the device from a staging copy of its own: a later kv_ensure may rewrite the pinned mirror before an
-    // earlier queued copy has run.
-    struct Take { uint32_t slot, blk, page; };
+    constexpr uint32_t NONE = 0xffffffffu;
+    struct Take { uint32_t slot, blk, page, from; };                       // from: the shared page the new one is a copy of, or NONE (zero-filled)
     std::vector<Take> takes;
-    size_t avail = m->free_pages.size();
     auto has = [&](uint32_t slot, uint32_t blk) { for (const Take &t : takes) if (t.slot == slot && t.blk == blk) return true; return false; };
+    auto owners_left = [&](uint32_t page) { uint32_t c = m->page_owners[page]; for (const Take &t : takes) if (t.from == page) c--; return c; };
     for (uint32_t i = 0; i < n; i++)
-        for (uint32_t blk = 0; blk <= need[i] >> 6 && blk < m->pt_stride; blk++)
-            if (m->h_pt[(size_t)slots[i] * m->pt_stride + blk] == 0xffffffffu && !has(slots[i], blk)) takes.push_back(Take{slots[i], blk, m->free_pages[--avail]});
+        for (uint32_t blk = 0; blk <= need[i] >> 6 && blk < m->pt_stride; blk++) {
+            const uint32_t e = m->h_pt[(size_t)slots[i] * m->pt_stride + blk];
+            if (has(slots[i], blk)) continue;                              // (the same slot twice in one call: its block once)
+            if (e == NONE) takes.push_back(Take{slots[i], blk, 0, NONE});
+            else if (blk >= first[i] >> 6 && owners_left(e / 64u) > 1) takes.push_back(Take{slots[i], blk, 0, e / 64u});
+        }
+    if (takes.empty()) return 0;
+    if (takes.size() > m->free_pages.size()) {
+        size_t ncow = 0;
+        for (const Take &t : takes) ncow += t.from != NONE;
+        FAIL(NANO_HIP_ENOMEM, "paged KV cache: %zu more pages needed (%zu of them copies of shared pages the call writes into), %zu free of %u (nano_hip_kv_release() returns a finished sequence's pages)",
+             takes.size(), ncow, m->free_pages.size(), m->kv_pages);
+    }
+    const size_t esz = m->kv_half ? 2 : 4, page_bytes = (size_t)64 * m->KD * esz, plane_bytes = (size_t)m->kv_pages * page_bytes;
+    // Take the pages, zero or fill them, send the table rows; COMMIT (host table, owner counts, free list) only when every call succeeded --
+    // a failing memset or copy gives the pages back and leaves the host table as it was (round-3 advice: pages leaked / host and device
+    // tables diverged).  Each changed row goes to the device from a staging copy of its own: a later kv_ensure may rewrite the pinned
+    // mirror before an earlier queued copy has run.
+    size_t avail = m->free_pages.size();
+    for (Take &t : takes) t.page = m->free_pages[--avail];
     hipError_t err = hipSuccess;
+    std::vector<KvCopyJob> jobs;
+    std::vector<uint32_t> gstart;
     for (const Take &t : takes) {
+        if (t.from != NONE) { gstart.push_back((uint32_t)jobs.size()); jobs.push_back(KvCopyJob{t.from * 64u, t.page * 64u, 64u, 64u}); continue; }
         if (err == hipSuccess) err = hipMemset2DAsync(reinterpret_cast<uint8_t *>(m->kcache) + (size_t)t.page * page_bytes, plane_bytes, 0, page_bytes, m->d.n_layer, m->st);
         if (err == hipSuccess) err = hipMemset2DAsync(reinterpret_cast<uint8_t *>(m->vcache) + (size_t)t.page * page_bytes, plane_bytes, 0, page_bytes, m->d.n_layer, m->st);
     }
+    gstart.push_back((uint32_t)jobs.size());
+    if (err == hipSuccess) err = kv_copy_enqueue(m, jobs, gstart, (size_t)m->kv_pages * 64);
     std::vector<uint32_t> rows_done;
     for (size_t k = 0; k < takes.size() && err == hipSuccess; k++) {
         const uint32_t slot = takes[k].slot;
@@ -535,20 +593,21 @@ static int kv_ensure(NanoHipModel *m, const uint32_t *slots, const uint32_t *nee
         g_err = b;
         return NANO_HIP_ERUNTIME;
     }
-    for (const Take &t : takes) m->h_pt[(size_t)t.slot * m->pt_stride + t.blk] = t.page * 64u;
-    m->free_pages.resize(avail);
-    if (m->pt_stage.size() > 256) {                                    // staging rows of copies long done: drop them behind a sync
-        HIP_TRY(hipStreamSynchronize(m->st));
-        m->pt_stage.clear();
+    for (const Take &t : takes) {
+        m->h_pt[(size_t)t.slot * m->pt_stride + t.blk] = t.page * 64u;
+        m->page_owners[t.page] = 1;
+        if (t.from != NONE) { m->page_owners[t.from]--; m->cow_copies++; }
     }
-    return 0;
+    m->free_pages.resize(avail);
+    return kv_stage_trim(m);
 }
-// sequences 0..batch-1 of a step live in slots 0..batch-1; each needs its pages up to position pos[i] + extra
+// sequences 0..batch-1 of a step live in slots 0..batch-1; each writes positions pos[i] .. pos[i] + extra and needs its pages up to there
+// (whole_context: a non-causal step reads every row of the context, so every block is mapped; it still writes position pos[i] only)
 static int kv_ensure_batch(NanoHipModel *m, const uint32_t *pos, uint32_t batch, uint32_t extra, bool whole_context) {
     if (!m->kv_paged) return 0;
     uint32_t slots[NANO_MAX_BATCH], need[NANO_MAX_BATCH];
     for (uint32_t i = 0; i < batch; i++) { slots[i] = i; need[i] = whole_context ? m->S - 1 : pos[i] + extra; if (need[i] > m->S - 1) need[i] = m->S - 1; }
-    return kv_ensure(m, slots, need, batch);
+    return kv_ensure(m, slots, pos, need, batch);
 }
 
 static GemvSeg mkseg(const TensorRef &t, float *out, uint32_t rows, uint32_t bstride, uint32_t pstride = 0) {
@@ -1413,7 +1472,7 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
     if (count) { const int rc = step_served(m, true); if (rc) return rc; }     // (an empty prompt queues nothing: there is nothing to refuse)
     if (m->kv_paged && count) {
         const uint32_t need = pos0 + count - 1;
-        int rc = kv_ensure(m, &slot, &need, 1);
+        int rc = kv_ensure(m, &slot, &pos0, &need, 1);
         if (rc) return rc;
     }
     if (strict_serves(m)) {                                                 // strict mode: one reference-order forward per prompt token
@@ -1750,7 +1809,11 @@ extern "C" int nano_hip_kv_release(NanoHipModel *m, uint32_t slot) {
     HIP_TRY(hipStreamSynchronize(m->st));                                 // nothing queued may still read the pages
     uint32_t *row = m->h_pt + (size_t)slot * m->pt_stride;
     for (uint32_t blk = 0; blk < m->pt_stride; blk++)
-        if (row[blk] != 0xffffffffu) { m->free_pages.push_back(row[blk] / 64u); row[blk] = 0xffffffffu; }
+        if (row[blk] != 0xffffffffu) {                                    // a page goes back to the pool when its last owner leaves
+            const uint32_t page = row[blk] / 64u;
+            if (--m->page_owners[page] == 0) m->free_pages.push_back(page);
+            row[blk] = 0xffffffffu;
+        }
     HIP_TRY(hipMemcpyAsync(m->pt + (size_t)slot * m->pt_stride, row, (size_t)m->pt_stride * 4, hipMemcpyHostToDevice, m->st));
     HIP_TRY(hipStreamSynchronize(m->st));
     return 0;
@@ -1760,4 +1823,94 @@ extern "C" int nano_hip_kv_pages(const NanoHipModel *m, uint32_t *in_use, uint32
     if (in_use) *in_use = m->kv_pages - (uint32_t)m->free_pages.size();
     if (total) *total = m->kv_pages;
     return 0;
+}
+extern "C" int nano_hip_kv_sharing(const NanoHipModel *m, uint32_t *shared_pages, uint64_t *cow_copies) {
+    if (!m || !m->kv_paged) FAIL(NANO_HIP_EINVAL, "not a paged-KV model");
+    if (shared_pages) {
+        uint32_t n = 0;
+        for (uint32_t c : m->page_owners) n += c > 1;
+        *shared_pages = n;
+    }
+    if (cow_copies) *cow_copies = m->cow_copies;
+    return 0;
+}
+
+// ---- a prefix shared between slots ---------------------------------------------------------------------------------------------
+// Contiguous cache: one copy launch, rows [0, n_pos) of the source slot to every destination in all 2 L planes (the source is read once).
+// Paged cache: the destinations give back what they hold, take the source's FULL pages below n_pos as co-owners (no byte moves) and get
+// a page of their own for a partial last block: its first n_pos % 64 rows copied, the rest zero (a fresh page is zero-filled, and
+// non-causal attention reads unwritten rows).  Everything is planned first and committed after the queueing succeeded: a call that
+// fails (arguments, pool) leaves tables, owner counts and the destinations' contents as they were.  The pages a fork can draw on are
+// the free ones plus those only its destinations own.
+extern "C" int nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_pos, const uint32_t *dst_slots, uint32_t n_dst) {
+    if (!m || !dst_slots) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (src_slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "source slot %u out of range (max_batch %u)", src_slot, m->maxB);
+    if (n_pos > m->S) FAIL(NANO_HIP_EINVAL, "%u positions exceed max_seq_len %u", n_pos, m->S);
+    {
+        std::vector<bool> listed(m->maxB, false);
+        for (uint32_t i = 0; i < n_dst; i++) {
+            const uint32_t d = dst_slots[i];
+            if (d >= m->maxB) FAIL(NANO_HIP_EINVAL, "destination slot %u out of range (max_batch %u)", d, m->maxB);
+            if (d == src_slot) FAIL(NANO_HIP_EINVAL, "slot %u is the source and a destination", d);
+            if (listed[d]) FAIL(NANO_HIP_EINVAL, "destination slot %u listed twice", d);
+            listed[d] = true;
+        }
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    if (n_dst == 0) return 0;
+    std::vector<KvCopyJob> jobs;
+    std::vector<uint32_t> gstart{0u};
+    if (!m->kv_paged) {
+        if (n_pos == 0) return 0;
+        const uint32_t slot_rows = m->d.n_layer * m->S;                    // rows of one slot: [slot][layer][S][kv_dim]
+        if ((uint64_t)m->maxB * slot_rows > 0xffffffffull) FAIL(NANO_HIP_EINVAL, "cache of %u slots x %u rows is beyond the copy kernel's 32-bit row index", m->maxB, slot_rows);
+        for (uint32_t i = 0; i < n_dst; i++) jobs.push_back(KvCopyJob{src_slot * slot_rows, dst_slots[i] * slot_rows, n_pos, n_pos});
+        gstart.push_back(n_dst);
+        HIP_TRY(kv_copy_enqueue(m, jobs, gstart, m->S));
+        return kv_stage_trim(m);
+    }
+    constexpr uint32_t NONE = 0xffffffffu;
+    const uint32_t P = m->pt_stride, nfull = n_pos >> 6, part = n_pos & 63u;
+    const uint32_t *srow = m->h_pt + (size_t)src_slot * P;
+    const bool copy_part = part && srow[nfull] != NONE;                    // (part != 0 implies nfull < P: n_pos <= max_seq_len)
+    // what the destinations' own release returns: pages that lose their last owner, in release order
+    std::map<uint32_t, uint32_t> leaving;
+    std::vector<uint32_t> pool = m->free_pages;
+    for (uint32_t i = 0; i < n_dst; i++)
+        for (uint32_t blk = 0; blk < P; blk++) {
+            const uint32_t e = m->h_pt[(size_t)dst_slots[i] * P + blk];
+            if (e != NONE && ++leaving[e / 64u] == m->page_owners[e / 64u]) pool.push_back(e / 64u);
+        }
+    const size_t wanted = copy_part ? n_dst : 0;
+    if (wanted > pool.size())
+        FAIL(NANO_HIP_ENOMEM, "paged KV cache: a fork of %u positions into %u slots needs %zu pages for the partial block, %zu available (%zu free + the destinations' own) of %u",
+             n_pos, n_dst, wanted, pool.size(), m->free_pages.size(), m->kv_pages);
+    std::vector<std::vector<uint32_t>> rows(n_dst, std::vector<uint32_t>(P, NONE));
+    for (uint32_t i = 0; i < n_dst; i++) {
+        for (uint32_t blk = 0; blk < nfull && blk < P; blk++) rows[i][blk] = srow[blk];
+        if (copy_part) {
+            const uint32_t page = pool.back(); pool.pop_back();
+            rows[i][nfull] = page * 64u;
+            jobs.push_back(KvCopyJob{srow[nfull], page * 64u, 64u, part});
+        }
+    }
+    gstart.push_back((uint32_t)jobs.size());
+    hipError_t err = kv_copy_enqueue(m, jobs, gstart, (size_t)m->kv_pages * 64);
+    for (uint32_t i = 0; i < n_dst && err == hipSuccess; i++) {
+        m->pt_stage.push_back(rows[i]);
+        err = hipMemcpyAsync(m->pt + (size_t)dst_slots[i] * P, m->pt_stage.back().data(), (size_t)P * 4, hipMemcpyHostToDevice, m->st);
+    }
+    if (err != hipSuccess) {
+        char b[256];
+        snprintf(b, sizeof b, "paged KV cache: queueing the fork failed: %s (nothing committed)", hipGetErrorString(err));
+        g_err = b;
+        return NANO_HIP_ERUNTIME;
+    }
+    for (const auto &lv : leaving) m->page_owners[lv.first] -= lv.second;
+    for (uint32_t i = 0; i < n_dst; i++) {
+        for (uint32_t blk = 0; blk < P; blk++) if (rows[i][blk] != NONE) m->page_owners[rows[i][blk] / 64u]++;
+        memcpy(m->h_pt + (size_t)dst_slots[i] * P, rows[i].data(), (size_t)P * 4);
+    }
+    m->free_pages.swap(pool);
+    return kv_stage_trim(m);
 }

@@ -471,6 +471,26 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
     return rc;
 }
 
+/* One prompt prefix for `batch` sequences: each replica ingests it once (batched prefill into its slot 0) and forks the rows into the
+ * other slots of its share -- sequence i lives in slot i / G of replica i mod G, as in nano_forward_batch. */
+int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || (!prefix_ids && n_prefix) || batch == 0) return NANO_HIP_EINVAL;
+    const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
+    if (batch > NANO_MAX_BATCH * G) return NANO_HIP_EINVAL;
+    for (uint32_t r = 0; r < G && r < batch; r++) {
+        NanoHipModel *dev = me->n_replica > 0 ? me->replica[r] : me->dev;
+        const uint32_t share = (batch - r + G - 1) / G;                  /* sequences r, r + G, ... below batch */
+        uint32_t dst[NANO_MAX_BATCH];
+        lora_select(dev, ctx->lora);
+        int rc = n_prefix ? nano_hip_prefill(dev, 0, prefix_ids, 0, n_prefix) : NANO_HIP_OK;
+        if (rc != NANO_HIP_OK) return rc;
+        for (uint32_t k = 1; k < share; k++) dst[k - 1] = k;
+        if (share > 1 && (rc = nano_hip_kv_fork(dev, 0, n_prefix, dst, share - 1)) != NANO_HIP_OK) return rc;
+    }
+    return NANO_HIP_OK;
+}
+
 /* =====================================================================================================
  * sampling (reference infer/infer.c:1026-1127; RNG infer/utils.c:959-970)
  * =================================================================================================== */

@@ -305,6 +305,20 @@ hipError_t launch_rope(float *head, uint32_t hd, const float *fcr, const float *
 hipError_t launch_stream_read(const void *buf, size_t bytes, float *sink, hipStream_t st);
 hipError_t launch_stream_read_masked(const void *buf, size_t bytes, float *sink, uint32_t xcd_mask, uint32_t wgs, hipStream_t st);
 
+// ---- KV-cache row copies (kv_copy.hip): the contiguous fork, the partial block of a paged fork, copy-on-write of a shared page ----
+// A job moves `rows` cache rows inside every layer plane of K and of V from src_row to dst_row; the trailing rows - keep_rows rows of the
+// destination are written as zero.  gstart[0 .. n_groups] cuts the job list into groups that share src_row / rows / keep_rows: a
+// workgroup loads the source once and stores it to every destination of its group.  Layer plane l starts l * plane_bytes into k / v.
+struct KvCopyJob { uint32_t src_row, dst_row, rows, keep_rows; };
+struct KvCopyArgs {
+    void *k, *v;
+    uint64_t plane_bytes;
+    uint32_t row_bytes;                          // a multiple of 8; 16-byte vectors when a multiple of 16
+    uint32_t n_groups, cx, _pad;                 // cx: workgroups per group and plane (set by the launcher)
+    const KvCopyJob *jobs; const uint32_t *gstart;            // device memory
+};
+hipError_t launch_kv_copy(KvCopyArgs a, uint32_t n_layer, uint32_t max_rows, uint32_t cus, bool nt_stores, hipStream_t st);
+
 // ---- device-side sampler (sampler.hip) ----
 constexpr uint32_t SAMPLE_CHUNK = 256;            // softmax numerators per chunk function (one wave x float4)
 constexpr uint32_t SAMPLE_MAX_CHUNKS = 1024;      // vocabularies up to 262144
