@@ -23,6 +23,8 @@
 //          no exec-masked branches, no dependent scalar loads) -- so the whole kernel costs ONE memory
 //          round trip.  rmsnorm + quantization run from registers while the weights are in flight; the
 //          group products land in an LDS table and one thread per (row, sequence) folds them in order.
+//          (Rows of ONE chunk -- n == 1024, one sequence, the rmsnorm roles: the wave that holds a row's products folds it itself,
+//          wave_fold_canon16 below; no table, no barrier behind the dots.)
 //   STREAM (classifier: vocab x n_embd).  1024 persistent workgroups; a wave owns 16-row tiles,
 //          tile = wave + k * nwaves, so the chip sweeps memory linearly; four waves per SIMD keep 16 KiB each in
 //          flight while one of them is consuming.  Lane l loads bytes [16l,16l+16) of each row chunk
@@ -278,15 +280,39 @@ __device__ __forceinline__ float fold_row_canon_ng(const float *p, uint32_t ng) 
     return fold_row_canon_any(p, ng);
 }
 
+// The same fold INSIDE a wave, for rows of one 1 KiB chunk (n == 1024, group size 64: 16 groups = two whole units).  After the integer dots
+// lane 4 g + r holds the product of (row r, group g) of the wave's four-row unit; the table, the workgroup barrier and the one fold thread
+// per row are a detour there.  S_0 (groups 0..7) lives in lanes 0..31, S_1 (groups 8..15) in lanes 32..63, both chains in the same
+// instructions, all four rows at once (lanes r mod 4):
+//   lanes r | 32 + r       ((p_0 + p_1) + p_2) + p_3          the later groups of the 16-lane row by DPP row_shl:4 / 8 / 12 (three moves that
+//                                                             depend on the product only: off the chain)
+//   lanes 16 + r | 48 + r  that value carried one row up (v_permlane16_swap: odd rows <- even rows), then + p_4 + p_5 + p_6 + p_7 with the
+//                          SAME three moved registers (in these lanes they hold groups 5..7)
+//   lanes 48 + r           S_0 from lanes 16 + r (v_permlane32_swap: upper half <- lower half), row = S_0 + S_1
+// Every add is one v_add_f32 with the running value first: the float of fold_row_canon<4> for every input (tests/test_wave_fold_order.py
+// restates this schedule lane by lane).  The row results are in lanes 48..51.
+__device__ __forceinline__ float wave_fold_canon16(float p) {
+    const float p1 = DPP_F(p, 0x104), p2 = DPP_F(p, 0x108), p3 = DPP_F(p, 0x10C);
+    float s = fadd(p, p1); s = fadd(s, p2); s = fadd(s, p3);
+    const uint32_t sb = __float_as_uint(s);
+    const float c = __uint_as_float(__builtin_amdgcn_permlane16_swap(sb, sb, false, false)[0]);
+    s = fadd(c, p); s = fadd(s, p1); s = fadd(s, p2); s = fadd(s, p3);
+    const uint32_t tb = __float_as_uint(s);
+    const float s0 = __uint_as_float(__builtin_amdgcn_permlane32_swap(tb, tb, false, false)[0]);
+    return fadd(s0, s);
+}
+constexpr int WF_LANE0 = 48;          // wave_fold_canon16(): lane WF_LANE0 + r holds row r
+
 // ------------------------------------------------------------------------------------------------------------
 // SLAB kernel
 // ------------------------------------------------------------------------------------------------------------
 // Hand-off of a launch's results to consumers INSIDE the same launch (the fused kernels below): every result is also stored as an 8-byte
 // {tag, value} granule (ONE write-through store: the data is the flag); SlabHand and the epoch tags: device_common.h.
-template <int ROLE, int GS, int B, int NV, int UPW, int EARLY = 0>
+template <int ROLE, int GS, int B, int NV, int UPW, int EARLY = 0, int WF = 0>
 __global__ __launch_bounds__(1024) void gemv_q80_slab_kernel(const GemvDev a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #define SLAB_EARLY EARLY
+#define SLAB_WF WF
 #define SLAB_A a
 #define SLAB_BID blockIdx.x
 #define SLAB_HAND 0
@@ -307,6 +333,7 @@ __global__ __launch_bounds__(1024) void gemv_q80_slab_kernel(const GemvDev a) {
 #undef SLAB_CTAG
 #undef SLAB_PART
 #undef SLAB_EARLY
+#undef SLAB_WF
 }
 
 #if NANO_Q80_GS == 64
@@ -326,34 +353,16 @@ namespace {
 struct FusedArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
 template <int NV, int UPW>
 __global__ __launch_bounds__(256) void qkv_attn_fused_kernel(const FusedArgs fa) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint2 tk_ = hand_tick(fa.hand);                       // the step's epoch: the first load of every workgroup
-    if (blockIdx.x >= fa.ngemv) {
-        const uint32_t ab = blockIdx.x - fa.ngemv;
-        const uint32_t split = ab / fa.head_wgs, grp = ab - split * fa.head_wgs;
-        attention_body<8, 4, 1, 1, false, false, 2, false, true>(fa.a, smem, grp, 0u, split, fa.hand, hand_ctag(tk_, fa.hand), fa.wait16);
-        return;
-    }
-    constexpr int ROLE = R_NORM_STORE, GS = 64, B = 1;
-#define SLAB_A fa.g
-#define SLAB_BID blockIdx.x
-#define SLAB_HAND 1
-#define SLAB_HANDV fa.hand
-#define SLAB_PTAG hand_ptag(tk_, fa.hand)
-#define SLAB_XHAND 0
-#define SLAB_XHANDV (SlabHand{})
-#define SLAB_CTAG 0u
-#define SLAB_PART 0
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_A
-#undef SLAB_BID
-#undef SLAB_HAND
-#undef SLAB_HANDV
-#undef SLAB_PTAG
-#undef SLAB_XHAND
-#undef SLAB_XHANDV
-#undef SLAB_CTAG
-#undef SLAB_PART
+#define SLAB_WF 0
+#include "qkv_attn_fused_body.inc"
+#undef SLAB_WF
+}
+// ... its form for n == 1024 (rows of one chunk): no product table, no barrier between the dots and the granules the attention workgroups wait for
+template <int NV, int UPW>
+__global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const FusedArgs fa) {
+#define SLAB_WF 1
+#include "qkv_attn_fused_body.inc"
+#undef SLAB_WF
 }
 
 // ---- Wo + W1|W3 in ONE launch (round 5): the first all-to-all edge of the block as an in-launch all-gather -------------------------------
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(256) void qkv_attn_fused_kernel(const FusedArgs fa)
 // workgroups of the grid and never wait for consumers; a grid of <= one workgroup per CU is resident as a whole.  Same bodies, same bits
 // (test_fused_wo_w13_launch_equals_the_two_launches).  Reference: infer/infer.c:885-944.
 struct Wo13Args { GemvDev wo; GemvDev w13; SlabHand hand; uint32_t wo_wgs, wait16; };   // wait16: naps of 16 x 64 cycles before a non-producer workgroup starts polling
-template <int ROLE_A, int NV_A, int UPW_A, int NV_B, int UPW_B, int NT>
+template <int ROLE_A, int NV_A, int UPW_A, int NV_B, int UPW_B, int NT, int WF = 0>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF
 __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int GS = 64, B = 1;
@@ -410,6 +419,7 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #define SLAB_CTAG hand_ctag(tk_, fa.hand)
 #define SLAB_XHAND_WAIT (blockIdx.x >= fa.wo_wgs ? fa.wait16 : 0u)
 #define SLAB_XHAND_NAP 2
+#define SLAB_WF WF
 #define SLAB_PART 1
 #include "gemv_q80_slab_body.inc"
 #undef SLAB_PART
@@ -427,6 +437,7 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #undef SLAB_CTAG
 #undef SLAB_XHAND_WAIT
 #undef SLAB_XHAND_NAP
+#undef SLAB_WF
         }
 #undef SLAB_BID
     }
@@ -647,6 +658,11 @@ static SlabPlan plan_slab(const GemvArgs &a, int B) {
     return p;
 }
 
+// a launch whose rows are one 1 KiB chunk of group size 64: the in-wave fold (SLAB_WF) takes it (the callers add: one sequence, an rmsnorm role,
+// a canonical launch).  W1|W3 is never position indexed in a decode step; such a launch would keep the table.
+static bool slab_wave_fold(const GemvDev &d) {
+    return d.n == 1024u && d.ng == 16u && !d.early && (d.epi == GEMV_EPI_STORE || (d.epi == GEMV_EPI_SWIGLU && !d.out_pstride[0]));
+}
 template <int ROLE, int GS, int B, int NV, int UPW>
 static hipError_t launch_slab_t(const GemvDev &d, const SlabPlan &p, uint32_t nwg, hipStream_t st) {
     const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
@@ -660,6 +676,14 @@ static hipError_t launch_slab_t(const GemvDev &d, const SlabPlan &p, uint32_t nw
         auto kern = &gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 1>;
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * p.nw), lds, st, dd);
+        return hipGetLastError();
+    }
+    // rows of ONE chunk (n == 1024), one sequence, the rmsnorm roles (canonical launches only at this group size: launch_slab_b): every wave
+    // folds its own rows -- no product table in the LDS budget, no barrier behind the dots (gemv_q80_slab_body.inc SLAB_WF).  W1|W3: units of
+    // two rows of each matrix, so that a wave holds both halves of its SwiGLU pairs
+    if constexpr (GS == 64 && B == 1 && (ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU) && (NV == 1 || NV == 2)) if (slab_wave_fold(d)) {
+        if (ROLE == R_NORM_SWIGLU) dd.units = (d.rw + 1) / 2;
+        hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 1>), dim3(nwg), dim3(64 * p.nw), n16 + ng4 * 4 + 64, st, dd);
         return hipGetLastError();
     }
     auto kern = &gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW>;
@@ -790,10 +814,10 @@ static void slab_dev_fill(GemvDev &d, const GemvArgs &a, const SlabPlan &p, uint
     d.wg_c0 = 0xffffffffu; d.wg_c1 = 0xffffffffu;
     d.nthr = nthr;
 }
-static size_t slab_lds(const GemvDev &d) {
+static size_t slab_lds(const GemvDev &d, bool table = true) {
     const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
-    return n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + (size_t)nmat * (d.tpw * 4) * pitch * 4;
+    return n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + (table ? (size_t)nmat * (d.tpw * 4) * pitch * 4 : 0);
 }
 
 #endif
@@ -840,7 +864,8 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
     h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
     const uint32_t n_attn = a.n_head * a.nsplit;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
-    const size_t lds_g = n16 + ng4 * 4 + 64 + (size_t)(d.tpw * 4) * pitch * 4;
+    const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
+    const size_t lds_g = n16 + ng4 * 4 + 64 + (wf ? 0 : (size_t)(d.tpw * 4) * pitch * 4);
     // q | k | maxima | sums | 4 waves' partials | the fresh v row | 4 give-up words | 4 waves x 8 sub-groups' weighted rows (attn_impl.h FAST)
     const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + 4 + 4 * 8 * hd4) * sizeof(float);
     const size_t lds = lds_g > lds_a ? lds_g : lds_a;
@@ -854,7 +879,8 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
     // 1961 / 1919, 1977 / 1986 / 1958 / 1920, 1982 / 1981 / 1960 / 1912 tok/s; positions 31..510: 1878 / 1880 / 1859 / 1821
     // (profiles/r06_handoff_naps.txt).
     fa.wait16 = 1u;
-#define FUSED_GO(NV_, UPW_) do { hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(n_attn + ngemv), dim3(256), lds, st, fa); return hipGetLastError(); } while (0)
+#define FUSED_GO(NV_, UPW_) do { if (wf && NV_ == 1) hipLaunchKernelGGL((qkv_attn_fused_wf_kernel<1, UPW_>), dim3(n_attn + ngemv), dim3(256), lds, st, fa); \
+                                 else hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(n_attn + ngemv), dim3(256), lds, st, fa); return hipGetLastError(); } while (0)
 #define FUSED_NV(NV_) do { if (upw == 1) FUSED_GO(NV_, 1); if (upw == 2) FUSED_GO(NV_, 2); FUSED_GO(NV_, 4); } while (0)
     if (p.nv == 1u) FUSED_NV(1);
     if (p.nv == 2u) FUSED_NV(2);
@@ -879,10 +905,14 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     h.buf = hand; h.tick = tick; h.layer1 = layer1;
     h.base[0] = 0; h.base[1] = 0; h.base[2] = 0;
     fa.hand = h;
-    const size_t la = slab_lds(fa.wo), lb = slab_lds(fa.w13), lds = la > lb ? la : lb;
+    // W1|W3's rows of one chunk (n == 1024): pair units (two rows of W1 and the same two of W3), folded by the wave that holds them
+    const bool wf = slab_wave_fold(fa.w13);
+    if (wf) fa.w13.units = (fa.w13.rw + 1) / 2;
+    const size_t la = slab_lds(fa.wo), lb = slab_lds(fa.w13, !wf), lds = la > lb ? la : lb;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     const bool comb = (fa.wo.flags & F_COMBINE) != 0;
-#define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_>), dim3(q.wb), dim3(NT_), lds, st, fa); return hipGetLastError(); } while (0)
+#define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { if (wf) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1>), dim3(q.wb), dim3(NT_), lds, st, fa); \
+                                                     else hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_>), dim3(q.wb), dim3(NT_), lds, st, fa); return hipGetLastError(); } while (0)
     if (q.sig == 1) { if (comb) WO13_GO(R_RESID_COMBINE, 2, 1, 1, 2, 256); WO13_GO(R_RESID, 2, 1, 1, 2, 256); }
     if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 1, 512);           // (sig 3)
     WO13_GO(R_RESID, 1, 1, 1, 1, 512);

@@ -17,7 +17,15 @@
 //               after (0 = all before)
 //   SLAB_PART   0: the whole body; 1: declarations + every load of the launch (sections 0-3) only; 2: the rest (sections 4-6) -- a kernel
 //               that runs two bodies issues the second one's weight loads (part 1) before it computes the first (wo_w13_fused_kernel)
+//   SLAB_WF     (optional, default 0) a compile-time 0 | 1: rows of ONE chunk (n == 1024, group size 64, one sequence, the rmsnorm roles, canonical
+//               launches -- the host selects it): every wave folds the rows of its units itself (wave_fold_canon16, gemv_q80_impl.h) and stores
+//               them; no product table in LDS, no workgroup barrier after the dots, waves end independently.  R_NORM_SWIGLU: a unit is two rows
+//               of W1 plus the same two rows of W3 (the host passes units = ceil(rw / 2)), so the wave has both halves of its SwiGLU pairs
 // and has ROLE, GS, B, NV, UPW, smem, in scope.
+#ifndef SLAB_WF
+#define SLAB_WF 0
+#define SLAB_WF_DEFAULTED 1
+#endif
 #ifndef SLAB_EARLY
 #define SLAB_EARLY 0
 #define SLAB_EARLY_DEFAULTED 1
@@ -29,6 +37,21 @@
 #endif
 // (a unit's weight and scale loads; used by section 2 and -- SLAB_EARLY -- by section 4)
 #define SLAB_ISSUE_UNIT(k) do { \
+      if constexpr (WFPAIR_) { \
+        /* pair unit u: rows 2u, 2u + 1 of W1 (r = 0, 1) and of W3 (r = 2, 3); the lane's scale comes from ONE of the two arrays: both are */ \
+        /* asked for, the other one out of range (no traffic, reads as 0), and the bit patterns are OR-ed -- no divergent descriptor */ \
+        const uint32_t u = (uint32_t)wid + (uint32_t)k * NW; \
+        const bool live = u < SLAB_A.units; \
+        const __amdgpu_buffer_rsrc_t rw0_ = mkrsrc(w0, live ? rows0 * n : 0u), rw1_ = mkrsrc(SLAB_A.w[1], live ? rows0 * n : 0u); \
+        const __amdgpu_buffer_rsrc_t rs0_ = mkrsrc(ws0, live ? rows0 * ng * 4u : 0u), rs1_ = mkrsrc(SLAB_A.ws[1], live ? rows0 * ng * 4u : 0u); \
+        const uint32_t lrow = lrow0 + u * 2u, base = lrow * n + (uint32_t)lane * 16u; \
+        _Pragma("unroll") \
+        for (int r = 0; r < TR; r++) wv[k][r] = bload_w(r < 2 ? rw0_ : rw1_, (u * 2u + (uint32_t)(r & 1) < RW) ? base + (uint32_t)(r & 1) * n : OOB); \
+        const uint32_t r_ = (uint32_t)lane & 3u, rr_ = r_ & 1u; \
+        const uint32_t so_ = (u * 2u + rr_ < RW) ? ((lrow + rr_) * ng + ((uint32_t)lane >> 2)) * 4u : OOB; \
+        const float s0_ = bload_f(rs0_, r_ < 2u ? so_ : OOB), s1_ = bload_f(rs1_, r_ < 2u ? OOB : so_); \
+        sv[k][0] = __uint_as_float(__float_as_uint(s0_) | __float_as_uint(s1_)); \
+      } else { \
         const uint32_t u = (uint32_t)wid + (uint32_t)k * NW; \
         const uint32_t t = (u * SLAB_A.magic_nchunk) >> 16; \
         const uint32_t c = u - t * SLAB_A.nchunk; \
@@ -47,6 +70,7 @@
             const uint32_t r = ((uint32_t)lane % LPG) + s * LPG; \
             sv[k][s] = bload_f(rs_, (r < TR && tl * TR + r < RW && g < ng) ? ((lrow + r) * ng + g) * 4u : OOB); \
         } \
+      } \
     } while (0)
 #if SLAB_PART != 2
     constexpr int TR = 4;
@@ -55,7 +79,9 @@
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int NW = (int)(SLAB_A.nthr >> 6);
-    const uint32_t n = SLAB_A.n, ng = SLAB_A.ng;
+    constexpr bool WF_ = (SLAB_WF) != 0, WFPAIR_ = WF_ && ROLE == R_NORM_SWIGLU;
+    static_assert(!WF_ || (GS == 64 && B == 1 && (SLAB_EARLY) == 0 && (ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU)), "SLAB_WF: one-chunk rows of the rmsnorm roles");
+    const uint32_t n = WF_ ? 1024u : SLAB_A.n, ng = WF_ ? 16u : SLAB_A.ng;
     const uint32_t n16 = (n + 15) & ~15u, ng4 = (ng + 3) & ~3u;
     const uint32_t PITCH = (GC == 16) ? (((ng + 47) / 64) * 64 + 16) : (ng4 + 4);
     const uint32_t RW = SLAB_A.rw, TPW = SLAB_A.tpw, RWP = TPW * TR;         // rows of this workgroup, its four-row tiles, rows of the product table
@@ -115,6 +141,9 @@
     // the position of a pos-indexed output (v-cache row) is fetched now and used only by the final store: no wait
     // here (a wait on it would also wait for every weight load issued above -- vmcnt counts in order)
     uint32_t opos = 0;
+    if constexpr (WF_) {        // (the lanes that will hold the row results ask; a buffer load: in order behind the weights, no traffic elsewhere)
+        if constexpr (ROLE == R_NORM_STORE) opos = __float_as_uint(bload_f(mkrsrc(SLAB_A.pos, ops ? 4u : 0u), ((uint32_t)lane & ~3u) == (uint32_t)WF_LANE0 ? 0u : OOB));
+    } else
     if (ops && fold_live) opos = SLAB_A.pos[fb];
     float oldv = 0.0f;
     if (epi == GEMV_EPI_RESID && fold_live) oldv = out0[(size_t)fb * obs + lrow0 + frl];      // residual stream: never pos-indexed
@@ -162,6 +191,49 @@
     }
     NANO_STAMP(SLAB_A.stamps, 3, xs[0]);                                 // activation normalised + quantized in LDS (stamp 2: inside, the activation arrived)
 
+    if constexpr (WF_) {
+    // ---- 5 + 6, rows of one chunk (SLAB_WF): integer dots, the product stays in its lane, the wave folds and stores its own rows --------
+    float pw_[UPW];
+    const int4 xv_ = *reinterpret_cast<const int4 *>(xq + lane * 16);
+    const float xsc_ = xs[lane >> 2];
+    asm volatile("" :: "v"(xsc_));                                       // (read next to the activation bytes, not behind the dots: one LDS round trip)
+#pragma unroll
+    for (int k = 0; k < UPW; k++) {
+        int iv[TR];
+#pragma unroll
+        for (int r = 0; r < TR; r++) {
+            int d = __builtin_amdgcn_sdot4(wv[k][r].x, xv_.x, 0, false);
+            d = __builtin_amdgcn_sdot4(wv[k][r].y, xv_.y, d, false);
+            d = __builtin_amdgcn_sdot4(wv[k][r].z, xv_.z, d, false);
+            d = __builtin_amdgcn_sdot4(wv[k][r].w, xv_.w, d, false);
+            iv[r] = dpp_group_sum<LPG>(d);
+        }
+        int v = iv[0];
+#pragma unroll
+        for (int q = 1; q < TR; q++) v = (q == (lane & 3)) ? iv[q] : v;
+        pw_[k] = ((float)v * sv[k][0]) * xsc_;                                                  // infer.c:672 (units beyond the last, rows beyond RW: weights and scales read as 0)
+    }
+    NANO_STAMP(SLAB_A.stamps, 4, pw_[UPW - 1]);                          // this wave's weights arrived, its dots are done
+    NANO_STAMP(SLAB_A.stamps, 5, pw_[UPW - 1]);                          // (no table, no barrier: the same moment)
+#pragma unroll
+    for (int k = 0; k < UPW; k++) {
+        const uint32_t u = (uint32_t)wid + (uint32_t)k * NW;
+        if (u < SLAB_A.units) {
+            const float v0 = wave_fold_canon16(pw_[k]);                                       // lanes WF_LANE0 + r: row r of the unit
+            const float v1 = WFPAIR_ ? DPP_F(v0, 0x102) : 0.0f;                               // (row_shl:2: W3's row next to W1's)
+            const uint32_t rl_ = WFPAIR_ ? u * 2u + ((uint32_t)lane & 1u) : u * (uint32_t)TR + ((uint32_t)lane & 3u);
+            const bool mine_ = WFPAIR_ ? ((uint32_t)lane & ~1u) == (uint32_t)WF_LANE0 : ((uint32_t)lane & ~3u) == (uint32_t)WF_LANE0;
+            if (mine_ && rl_ < RW && lrow0 + rl_ < rows0) {
+                float *dst = out0 + (size_t)opos * ops + lrow0 + rl_;
+                const float val = finish_epi(epi, v0, v1, 0.0f);
+                if constexpr (SLAB_HAND == 1)                             // (the granule first: a waiting workgroup sits behind it)
+                    __hip_atomic_store(SLAB_HANDV.buf + (sel == 0 ? SLAB_HANDV.base[0] : sel == 1 ? SLAB_HANDV.base[1] : SLAB_HANDV.base[2]) + lrow0 + rl_,
+                                       ((unsigned long long)(SLAB_PTAG) << 32) | (unsigned long long)__float_as_uint(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (NANO_STAMPS && (SLAB_A.dbg & 4u)) *dst = val; else __hip_atomic_store(dst, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through, as below
+            }
+        }
+    }
+    } else {
     // ---- 5. integer dots, group products into the LDS table ----------------------------------------------------
 #pragma unroll
     for (int k = 0; k < UPW; k++) {
@@ -296,9 +368,14 @@
             if (NANO_STAMPS && (SLAB_A.dbg & 4u)) *dst = val; else __hip_atomic_store(dst, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    }   // !SLAB_WF
     NANO_STAMP_END(SLAB_A.stamps, 6);                                    // folded and stored: the workgroup's last wave ends
 #endif   // SLAB_PART != 1
 #undef SLAB_ISSUE_UNIT
+#ifdef SLAB_WF_DEFAULTED
+#undef SLAB_WF
+#undef SLAB_WF_DEFAULTED
+#endif
 #ifdef SLAB_EARLY_DEFAULTED
 #undef SLAB_EARLY
 #undef SLAB_EARLY_DEFAULTED
