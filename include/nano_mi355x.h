@@ -385,8 +385,16 @@ typedef struct NanoFusedGemvDesc {
     uint32_t ordered;           /* 1: strict mode -- the reference's ascending group order in every kernel (bit-exact fp32); 0: the fast path */
     uint32_t *route_out;        /* optional: the route the launch took (RouteKind of nano_amd/csrc/kernels.h), or NULL */
     float *out;                 /* [nb][sum of rows] (kind 2: [nb][rows[0]]); kind 1: holds the residual stream on entry */
+    uint32_t out_slots;         /* 0: nb.  Else out holds out_slots >= nb sequence slots; a launch must leave those beyond nb alone */
+    uint32_t out_stride;        /* 0: sum of rows.  Else floats between the slots of out (>= sum of rows; the rest are guard elements) */
 } NanoFusedGemvDesc;
 int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
+/* The FP32 launch the router issues for descriptor d (quant = NANO_QUANT_F32), from the functions the launcher and the router follow:
+ * out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0} -- gemv_f32_slab_kernel<role, B, nv, upw> on
+ * nw waves x grid workgroups owning rw rows each, of the first of `launches` slices of seqs_per_launch sequences.  takes = 0: the
+ * shape is refused before any launch (a row of more than 16384 floats, 8192 with SwiGLU; one sequence that does not fit a CU's LDS).
+ * Host arithmetic on the shape fields: works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
+int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[12]);
 
 /* One device-resident copy of a model's parameter bytes per GPU from ONE host upload (replicate.hip; SURVEY 8e "broadcast(weights) at
  * load"): the bytes go to `root_device` over PCIe once and from there to the other devices over xGMI -- an RCCL broadcast (librccl.so

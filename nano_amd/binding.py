@@ -33,7 +33,8 @@ class NanoFusedGemvDesc(C.Structure):
     _fields_ = [("quant", C.c_uint32), ("gs", C.c_uint32), ("kind", C.c_uint32), ("n", C.c_uint32), ("nb", C.c_uint32), ("nseg", C.c_uint32),
                 ("rows", C.c_uint32 * 3), ("w", C.c_void_p * 3), ("ws", C.c_void_p * 3), ("x", C.c_void_p), ("norm_w", C.c_void_p),
                 ("attn_part", C.c_void_p), ("attn_ml", C.c_void_p), ("attn_nsplit", C.c_uint32), ("attn_n_head", C.c_uint32),
-                ("attn_hd", C.c_uint32), ("use_gemm", C.c_uint32), ("ordered", C.c_uint32), ("route_out", C.c_void_p), ("out", C.c_void_p)]
+                ("attn_hd", C.c_uint32), ("use_gemm", C.c_uint32), ("ordered", C.c_uint32), ("route_out", C.c_void_p), ("out", C.c_void_p),
+                ("out_slots", C.c_uint32), ("out_stride", C.c_uint32)]
 
 
 class NanoAttnDecodeDesc(C.Structure):
@@ -52,6 +53,11 @@ class NanoExactAttnDesc(C.Structure):
 
 # the fields of an attention plan (nano_amd/csrc/kernels.h AttnPlan; xcd: workgroups of a KV head on one XCD)
 ATTN_PLAN_FIELDS = ("mode", "lpr", "qv", "kvm", "npt", "w16", "paged", "kv_half", "nsplit", "xcd")
+
+
+# what nano_hip_f32_gemv_plan reports (nano_amd/csrc/kernels.h F32GemvPlan + route_f32_slices), and the kernel roles of gemv_common.h
+F32_PLAN_FIELDS = ("role", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "launches", "seqs_per_launch", "takes")
+F32_ROLES = ("generic", "norm_store", "resid", "resid_combine", "norm_swiglu")
 
 
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
@@ -125,6 +131,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_argmax", C.c_int, [C.c_int, f32p, C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_op_fused_gemv", C.c_int, [C.c_int, C.POINTER(NanoFusedGemvDesc)])
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
+    fn("nano_hip_f32_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_fork", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32])
@@ -452,14 +459,38 @@ def op_matmul_q4k(x_blocks, w_blocks, n, d, device=0):
     check(lib().nano_hip_op_matmul_q4k(device, out, np.ascontiguousarray(x_blocks), np.ascontiguousarray(w_blocks), n, d)); return out
 
 
+_FLAG = np.zeros(1, np.float32)         # stands for "a norm weight / attention partials are given" where only the shape is read
+
+
+def f32_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
+    """The FP32 launch the router issues for a fused-gemv shape (nano_hip_f32_gemv_plan; needs no GPU).  rows: the row count of each
+    weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
+    Returns a dict of F32_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
+    d = NanoFusedGemvDesc()
+    d.quant, d.kind, d.n, d.nb, d.nseg = 0x00, kind, n, nb, len(rows)
+    for i, r in enumerate(rows):
+        d.rows[i] = r
+    if norm:
+        d.norm_w = _FLAG.ctypes.data
+    if attn is not None:
+        d.attn_part = _FLAG.ctypes.data
+        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
+    out = (C.c_uint32 * 12)()
+    check(lib().nano_hip_f32_gemv_plan(C.byref(d), cus, out))
+    return dict(zip(F32_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, resid=None, attn=None, use_gemm=False, ordered=False,
-                  want_route=False, device=0):
+                  want_route=False, guard=None, device=0):
     """One fused decode GEMV launch exactly as a decode step issues it (nano_hip_op_fused_gemv).
     quant: 0x00 F32 / 0x80 Q80 / 0x42 Q4K; kind: 0 store, 1 residual add, 2 SwiGLU.
     weights: list of (w, ws_or_None, rows) -- F32 float[rows, n]; Q80 int8[rows*n] + float scales; Q4K uint8 blocks (no frame).
     x: [nb, n] fp32; resid: [nb, rows] old residual values (kind 1); attn = (part[nb, nsplit, n], ml[nb, n_head, nsplit, 2], n_head, hd).
     ordered: strict mode (the reference's ascending group order; bit-exact fp32 against the oracle); default: the fast path, whose
     Q80 kernels of group size 64 fold canonically (unit sums of 8 groups, units ascending -- tests/canon.py restates it).
+    guard: None, or a float32 array [slots >= nb, stride >= rows_total] that IS the output buffer (slot b's result in [b, :rows_total];
+    kind 1: it holds the residual stream there on entry) -- it goes to the device whole and comes back whole, so the caller sees whatever
+    a launch wrote beyond its rows or its sequences; the returned out is that array.
     Returns out[nb, rows_total] (want_route: (out, route name))."""
     d = NanoFusedGemvDesc()
     d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = quant, gs, kind, n, nb, len(weights)
@@ -479,7 +510,12 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
         part = np.ascontiguousarray(part, np.float32); ml = np.ascontiguousarray(ml, np.float32); keep += [part, ml]
         d.attn_part, d.attn_ml = part.ctypes.data, ml.ctypes.data
         d.attn_nsplit, d.attn_n_head, d.attn_hd = part.shape[-2], n_head, hd
-    out = np.zeros((nb, rows_total), np.float32) if resid is None else np.array(resid, np.float32, copy=True).reshape(nb, rows_total)
+    if guard is not None:
+        assert resid is None and guard.dtype == np.float32 and guard.flags.c_contiguous and guard.ndim == 2
+        out = guard
+        d.out_slots, d.out_stride = guard.shape
+    else:
+        out = np.zeros((nb, rows_total), np.float32) if resid is None else np.array(resid, np.float32, copy=True).reshape(nb, rows_total)
     d.use_gemm = 1 if use_gemm else 0
     d.ordered = 1 if ordered else 0
     route = C.c_uint32(0xffffffff)

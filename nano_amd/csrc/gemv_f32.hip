@@ -197,53 +197,45 @@ static F32Plan plan_f32(const GemvArgs &a, int B) {
 }
 
 template <int ROLE, int B, int NV, int UPW>
-static hipError_t launch_f32_t(const GemvDev &d, const F32Plan &p, uint32_t rows, hipStream_t st) {
-    const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
-    const size_t n4 = (d.n + 3) & ~3u, pc = (d.nchunk + 3) & ~3u;
-    const size_t lds = (B * n4 + B * 16 + ((d.flags & F_COMBINE) ? (size_t)B * d.attn_n_head * 8 : 0) + (size_t)B * nmat * p.rw * pc) * 4;
+static hipError_t launch_f32_t(const GemvDev &d, const F32GemvPlan &p, hipStream_t st) {
     auto kern = &gemv_f32_slab_kernel<ROLE, B, NV, UPW>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (p.lds_bytes > 64 * 1024) {          // opt-in LDS; gemv_f32_plan() has refused what a CU does not have
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
     GemvDev dd = d; dd.nthr = 64 * p.nw;
-    hipLaunchKernelGGL(kern, dim3((rows + p.rw - 1) / p.rw), dim3(64 * p.nw), lds, st, dd);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), p.lds_bytes, st, dd);
     return hipGetLastError();
 }
+// the instantiations: every (NV, UPW) of {0, 1, 2, 4} x {1, 2, 4} with B * NV <= 8 (tests/test_f32_gemv_plan.py restates the set)
 template <int ROLE, int B>
-static hipError_t launch_f32_r(const GemvDev &d, const F32Plan &p, uint32_t rows, hipStream_t st) {
-    if (p.upw > 4) return hipErrorInvalidValue;
-#define F32_GO(NV_, UPW_) do { if constexpr (B * NV_ <= 8) return launch_f32_t<ROLE, B, NV_, UPW_>(d, p, rows, st); } while (0)
-    int nv = p.nv <= 1 ? 1 : p.nv <= 2 ? 2 : p.nv <= 4 ? 4 : 0;
-    const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-    if (B * nv > 8) nv = 0;
-    if (nv == 1) { if (upw == 1) F32_GO(1, 1); if (upw == 2) F32_GO(1, 2); F32_GO(1, 4); }
-    if (nv == 2) { if (upw == 1) F32_GO(2, 1); if (upw == 2) F32_GO(2, 2); F32_GO(2, 4); }
-    if (nv == 4) { if (upw == 1) F32_GO(4, 1); if (upw == 2) F32_GO(4, 2); F32_GO(4, 4); }
-    if (upw == 1) F32_GO(0, 1);
-    if (upw == 2) F32_GO(0, 2);
-    F32_GO(0, 4);
+static hipError_t launch_f32_r(const GemvDev &d, const F32GemvPlan &p, hipStream_t st) {
+#define F32_GO(NV_, UPW_) do { if constexpr (B * NV_ <= 8) { if (p.nv == NV_ && p.upw == UPW_) return launch_f32_t<ROLE, B, NV_, UPW_>(d, p, st); } } while (0)
+    F32_GO(1, 1); F32_GO(1, 2); F32_GO(1, 4);
+    F32_GO(2, 1); F32_GO(2, 2); F32_GO(2, 4);
+    F32_GO(4, 1); F32_GO(4, 2); F32_GO(4, 4);
+    F32_GO(0, 1); F32_GO(0, 2); F32_GO(0, 4);
     return hipErrorInvalidValue;
 #undef F32_GO
 }
 template <int B>
-static hipError_t launch_f32_b(const GemvArgs &a, hipStream_t st) {
+static hipError_t launch_f32_b(const GemvArgs &a, const F32GemvPlan &p, hipStream_t st) {
     GemvDev d = to_dev(a);
     d.tile_max = nullptr;
-    const F32Plan p = plan_f32(a, B);
     d.nchunk = (a.n + 255) / 256;
     d.magic_nchunk = (65536 + d.nchunk - 1) / d.nchunk;
     d.rw = p.rw;
     uint32_t l2 = 0; while ((1u << l2) < p.rw / 4) l2++;
     d.log2_tiles = l2;
     d.units = (p.rw / 4) * d.nchunk * (d.epi == GEMV_EPI_SWIGLU ? 2 : 1);
-    uint32_t rows = 0;
-    if (a.epi == GEMV_EPI_SWIGLU) rows = a.seg[0].rows; else for (uint32_t s = 0; s < a.nseg; s++) rows += a.seg[s].rows;
-    if constexpr (B == 1) {
-        const uint32_t f = d.flags;
-        if (f == F_NORM && d.epi == GEMV_EPI_STORE) return launch_f32_r<R_NORM_STORE, B>(d, p, rows, st);
-        if (f == 0 && d.epi == GEMV_EPI_RESID) return launch_f32_r<R_RESID, B>(d, p, rows, st);
-        if (f == F_COMBINE && d.epi == GEMV_EPI_RESID) return launch_f32_r<R_RESID_COMBINE, B>(d, p, rows, st);
-        if (f == F_NORM && d.epi == GEMV_EPI_SWIGLU) return launch_f32_r<R_NORM_SWIGLU, B>(d, p, rows, st);
+    if constexpr (B == 1) {                 // the role-specialised kernels exist for one sequence only
+        if (p.role == R_NORM_STORE) return launch_f32_r<R_NORM_STORE, B>(d, p, st);
+        if (p.role == R_RESID) return launch_f32_r<R_RESID, B>(d, p, st);
+        if (p.role == R_RESID_COMBINE) return launch_f32_r<R_RESID_COMBINE, B>(d, p, st);
+        if (p.role == R_NORM_SWIGLU) return launch_f32_r<R_NORM_SWIGLU, B>(d, p, st);
     }
-    return launch_f32_r<R_GENERIC, B>(d, p, rows, st);
+    if (p.role != R_GENERIC) return hipErrorInvalidValue;
+    return launch_f32_r<R_GENERIC, B>(d, p, st);
 }
 
 // the fused launch's plan: the projection's own, on 256 threads (four waves like the attention's workgroups; same bits -- the float4 items sit
@@ -303,15 +295,56 @@ hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, uns
 #undef F32F_GO
 }
 
-hipError_t launch_gemv_f32(const GemvArgs &a, hipStream_t st) {
-    if (a.nb == 0 || a.nb > 8 || a.n % 4 || a.nseg == 0 || a.nseg > 3 || a.xq_in) return hipErrorInvalidValue;
-    if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd % 4)) return hipErrorInvalidValue;
+// The launch of `a`: which gemv_f32_slab_kernel<ROLE, B, NV, UPW>, on how many waves and workgroups, with how much LDS.  Every choice
+// launch_gemv_f32() makes is made here.  false: the arguments are refused (malformed, more than 4 units per wave -- rows beyond 16384
+// floats, 8192 with SwiGLU -- or more LDS than a CU has: gemv_f32_fit_batch() tells the router how many sequences fit).
+bool gemv_f32_plan(const GemvArgs &a, F32GemvPlan *out) {
+    if (a.nb == 0 || a.nb > 8 || a.n == 0 || a.n % 4 || a.nseg == 0 || a.nseg > 3 || a.xq_in) return false;
+    if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd == 0 || a.attn_hd % 4)) return false;
+    if (a.epi == GEMV_EPI_SWIGLU && a.nseg != 2) return false;
     if (a.epi != GEMV_EPI_SWIGLU && a.nseg > 1)
-        for (uint32_t s = 0; s < a.nseg; s++) if (a.seg[s].rows % 4) return hipErrorInvalidValue;
-    if (a.nb <= 1) return launch_f32_b<1>(a, st);
-    if (a.nb <= 2) return launch_f32_b<2>(a, st);
-    if (a.nb <= 4) return launch_f32_b<4>(a, st);
-    return launch_f32_b<8>(a, st);
+        for (uint32_t s = 0; s < a.nseg; s++) if (a.seg[s].rows % 4) return false;
+    const uint32_t B = a.nb <= 1 ? 1 : a.nb <= 2 ? 2 : a.nb <= 4 ? 4 : 8;
+    const F32Plan p = plan_f32(a, (int)B);
+    if (p.upw > 4) return false;
+    const uint32_t f = (a.norm_w ? F_NORM : 0u) | (a.attn_part ? F_COMBINE : 0u);
+    uint32_t role = R_GENERIC;
+    if (B == 1) {
+        if (f == F_NORM && a.epi == GEMV_EPI_STORE) role = R_NORM_STORE;
+        else if (f == 0 && a.epi == GEMV_EPI_RESID) role = R_RESID;
+        else if (f == F_COMBINE && a.epi == GEMV_EPI_RESID) role = R_RESID_COMBINE;
+        else if (f == F_NORM && a.epi == GEMV_EPI_SWIGLU) role = R_NORM_SWIGLU;
+    }
+    uint32_t nv = p.nv <= 1 ? 1 : p.nv <= 2 ? 2 : p.nv <= 4 ? 4 : 0;     // float4 items a thread stages in registers; 0: the loop form
+    if (B * nv > 8) nv = 0;
+    const uint32_t upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
+    uint32_t rows = 0;
+    if (a.epi == GEMV_EPI_SWIGLU) rows = a.seg[0].rows; else for (uint32_t s = 0; s < a.nseg; s++) rows += a.seg[s].rows;
+    if (rows == 0) return false;
+    const uint32_t nmat = a.epi == GEMV_EPI_SWIGLU ? 2 : 1, nchunk = (a.n + 255) / 256;
+    const uint64_t n4 = (a.n + 3) & ~3u, pc = (nchunk + 3) & ~3u;
+    // activations [B][n4] | norm partials [B][16] | combine weights [B][n_head][8] | chunk partials [B][nmat][rw][pc]
+    const uint64_t lds = ((uint64_t)B * n4 + (uint64_t)B * 16 + ((f & F_COMBINE) ? (uint64_t)B * a.attn_n_head * 8 : 0) + (uint64_t)B * nmat * p.rw * pc) * 4;
+    if (lds > GEMV_F32_LDS_MAX) return false;
+    if (out) *out = F32GemvPlan{role, B, nv, upw, p.rw, p.nw, (rows + p.rw - 1) / p.rw, (uint32_t)lds};
+    return true;
+}
+
+// sequences per launch whose LDS request a CU can meet (8 | 4 | 2 | 1; 0: not even one sequence, or a refused shape).  LDS grows
+// with the capacity and nothing else of a refusal depends on it, so every smaller batch fits as well.
+uint32_t gemv_f32_fit_batch(const GemvArgs &a) {
+    GemvArgs t = a;
+    for (uint32_t c = 8; c >= 1; c >>= 1) { t.nb = c; if (gemv_f32_plan(t, nullptr)) return c; }
+    return 0;
+}
+
+hipError_t launch_gemv_f32(const GemvArgs &a, hipStream_t st) {
+    F32GemvPlan p;
+    if (!gemv_f32_plan(a, &p)) return hipErrorInvalidValue;
+    if (p.B == 1) return launch_f32_b<1>(a, p, st);
+    if (p.B == 2) return launch_f32_b<2>(a, p, st);
+    if (p.B == 4) return launch_f32_b<4>(a, p, st);
+    return launch_f32_b<8>(a, p, st);
 }
 
 }  // namespace nano

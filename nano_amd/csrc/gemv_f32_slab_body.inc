@@ -38,6 +38,7 @@
         const uint32_t c = u - t * nchunk;
         const uint32_t tl = t & tmask, mat = t >> F32_A.log2_tiles;
         const bool live = u < F32_A.units;
+        // (byte offsets and the descriptor's size are 32-bit: a weight tensor of rows * n * 4 >= 2^32 bytes is beyond this kernel)
         const __amdgpu_buffer_rsrc_t rw_ = mkrsrc(mat ? reinterpret_cast<const float *>(F32_A.w[1]) : w0, live ? rows0 * n * 4u : 0u);
         const uint32_t lrow = lrow0 + tl * TR;
         const uint32_t col = (c << 8) + (uint32_t)lane * 4u;

@@ -86,6 +86,12 @@ hipError_t launch_gemv_q4k_chunk(GemvArgs &a, hipStream_t st);
 uint32_t gemv_q4k_fit_batch(const GemvArgs &a);            // sequences per Q4K launch that fit in LDS (8 | 4 | 2 | 1)
 hipError_t launch_gemv_q80(const GemvArgs &a, hipStream_t st);      // gemv_q80.hip
 hipError_t launch_gemv_f32(const GemvArgs &a, hipStream_t st);      // gemv_f32.hip
+// the gemv_f32_slab_kernel<ROLE, B, NV, UPW> launch_gemv_f32() runs for `a` (nb <= 8), its waves, workgroups and LDS bytes; the launcher
+// takes every choice from here.  false: the arguments are refused -- malformed, more than 4 units per wave, or more LDS than a CU has.
+constexpr uint32_t GEMV_F32_LDS_MAX = 160 * 1024;
+struct F32GemvPlan { uint32_t role, B, nv, upw, rw, nw, grid, lds_bytes; };
+bool gemv_f32_plan(const GemvArgs &a, F32GemvPlan *p);
+uint32_t gemv_f32_fit_batch(const GemvArgs &a);            // sequences per FP32 launch that fit in LDS (8 | 4 | 2 | 1; 0: none -- the shape is refused)
 // 9..64 tokens per weight read on the int8 matrix cores.  G2 (gemm_q80.hip): the general kernel in the reference's ascending group order --
 // strict mode's batched route, and the launches the canonical-fold kernels do not take (group sizes other than 64, rows that are no multiple
 // of 256); activations in MFMA B-fragment order (a.xq_in / a.xs_in = launch_quant_rows_frag's output)
@@ -130,6 +136,9 @@ struct Q80Route {
     uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of 2 .. 8 sequences (gemv_q4k_chunk.hip), or nullptr
 };
 RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
+// FP32: the slices route_projection() cuts a launch of a.nb sequences into -- per = sequences of every slice but the last, launches = their
+// number; false: the shape is refused (hipErrorInvalidValue before any launch)
+bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
 uint32_t route_norm_order(const Q80Route &r, const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);

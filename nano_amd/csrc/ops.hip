@@ -203,23 +203,59 @@ extern "C" int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32
     return 0;
 }
 
+// what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part, read as flags), or nullptr
+static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
+    if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || d.n % 4) return "bad fused-gemv descriptor";
+    if (d.quant == NANO_QUANT_Q80 && (!(d.gs == 32 || d.gs == 64 || d.gs == 128 || d.gs == 256) || d.n % d.gs || d.n % 16)) return "bad n / group size";
+    for (uint32_t s = 0; s < d.nseg; s++) if (!d.rows[s]) return "missing weight tensor";
+    if (d.kind == 2 && d.rows[0] != d.rows[1]) return "W1 / W3 row counts differ";
+    if (d.attn_part && (!d.attn_nsplit || d.attn_nsplit > 8 || !d.attn_n_head || d.attn_n_head * d.attn_hd != d.n || d.kind != 1 || d.nb > 8)) return "bad attention partials";
+    return nullptr;
+}
+
+// The FP32 launch route_projection() issues for a descriptor (its first slice when it cuts the batch): gemv_f32_plan() and
+// route_f32_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
+// the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed.
+// out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0}; takes = 0: the router refuses the shape
+// (hipErrorInvalidValue before any launch) and the other entries are 0.
+extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[12]) {
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    const NanoFusedGemvDesc &d = *dp;
+    if (d.quant != NANO_QUANT_F32) { nano_hip_set_error_("not an FP32 launch"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    GemvArgs a{};
+    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
+    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus;
+    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    a.norm_w = d.norm_w;
+    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    memset(out, 0, 12 * sizeof(uint32_t));
+    uint32_t per = 0, launches = 0;
+    F32GemvPlan p;
+    if (!route_f32_slices(a, &per, &launches)) return 0;
+    a.nb = per;
+    if (!gemv_f32_plan(a, &p)) return 0;
+    const uint32_t v[12] = { p.role, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, launches, per, 1u, 0u };
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+
 // One fused GEMV launch as enqueue_step() issues it (backend.hip): the role-specialised kernels on caller-chosen inputs.
 extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     int rc; if ((rc = begin(device))) return rc;
     if (!dp) { nano_hip_set_error_("null descriptor"); return NANO_HIP_EINVAL; }
     const NanoFusedGemvDesc &d = *dp;
-    if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || !d.out || d.n % 4) {
-        nano_hip_set_error_("bad fused-gemv descriptor"); return NANO_HIP_EINVAL;
-    }
+    if (!d.out) { nano_hip_set_error_("bad fused-gemv descriptor"); return NANO_HIP_EINVAL; }
     if (!d.x && !d.attn_part) { nano_hip_set_error_("no activation"); return NANO_HIP_EINVAL; }
-    if (d.quant == NANO_QUANT_Q80 && (!(d.gs == 32 || d.gs == 64 || d.gs == 128 || d.gs == 256) || d.n % d.gs || d.n % 16)) { nano_hip_set_error_("bad n / group size"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    if (d.attn_part && !d.attn_ml) { nano_hip_set_error_("bad attention partials"); return NANO_HIP_EINVAL; }
     DevBufs B;
     GemvArgs a{};
     const size_t bpl = (d.n + 255) / 256;
     uint32_t rows_total = 0;
     for (uint32_t s = 0; s < d.nseg; s++) {
         const size_t rows = d.rows[s];
-        if (!d.w[s] || !rows) { nano_hip_set_error_("missing weight tensor"); return NANO_HIP_EINVAL; }
+        if (!d.w[s]) { nano_hip_set_error_("missing weight tensor"); return NANO_HIP_EINVAL; }
         if (d.quant == NANO_QUANT_Q80) {
             a.seg[s].w = B.upload(reinterpret_cast<const int8_t *>(d.w[s]), rows * d.n);
             a.seg[s].ws = B.upload(d.ws[s], rows * d.n / d.gs);
@@ -230,13 +266,16 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         a.seg[s].rows = d.rows[s];
         if (d.kind != 2 || s == 0) rows_total += d.rows[s];
     }
-    if (d.kind == 2 && d.rows[0] != d.rows[1]) { nano_hip_set_error_("W1 / W3 row counts differ"); return NANO_HIP_EINVAL; }
-    float *dout = B.upload(d.out, (size_t)d.nb * rows_total);       // (kind 1: the residual stream; otherwise overwritten)
+    // out_slots / out_stride (operator tests): out holds more sequence slots than nb and more floats per slot than rows -- guard
+    // elements that go to the device and come back with the result, so the caller sees every element the launch wrote
+    const uint32_t slots = d.out_slots ? d.out_slots : d.nb, stride = d.out_stride ? d.out_stride : rows_total;
+    if (slots < d.nb || stride < rows_total) { nano_hip_set_error_("out_slots / out_stride smaller than the result"); return NANO_HIP_EINVAL; }
+    float *dout = B.upload(d.out, (size_t)slots * stride);          // (kind 1: the residual stream; otherwise overwritten)
     OP_CHECK(dout, "device alloc failed");
     uint32_t off = 0;
     for (uint32_t s = 0; s < d.nseg; s++) {
         a.seg[s].out = d.kind == 2 ? dout : dout + off;
-        a.seg[s].out_bstride = rows_total;
+        a.seg[s].out_bstride = stride;
         if (d.kind != 2) off += d.rows[s];
     }
     a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb;
@@ -244,7 +283,6 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     if (d.x) { a.xin = B.upload(d.x, (size_t)d.nb * d.n); OP_CHECK(a.xin, "device alloc failed"); a.xin_bstride = d.n; }
     if (d.norm_w) { a.norm_w = B.upload(d.norm_w, d.n); OP_CHECK(a.norm_w, "device alloc failed"); }
     if (d.attn_part) {
-        if (!d.attn_ml || !d.attn_nsplit || d.attn_nsplit > 8 || !d.attn_n_head || d.attn_n_head * d.attn_hd != d.n || d.kind != 1 || d.nb > 8) { nano_hip_set_error_("bad attention partials"); return NANO_HIP_EINVAL; }
         a.attn_part = B.upload(d.attn_part, (size_t)d.nb * d.attn_nsplit * d.n);
         a.attn_ml = B.upload(d.attn_ml, (size_t)d.nb * d.attn_n_head * d.attn_nsplit * 2);
         OP_CHECK(a.attn_part && a.attn_ml, "device alloc failed");
@@ -273,7 +311,7 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     const hipError_t e = route_projection(r, a, 0);
     OP_HIP(e);
     OP_HIP(hipDeviceSynchronize());
-    OP_HIP(hipMemcpy(d.out, dout, (size_t)d.nb * rows_total * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(d.out, dout, (size_t)slots * stride * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -2,7 +2,7 @@
 // ONE router for the decode step (backend.hip), batched prefill and the operator entry points (ops.hip), so that the operator tests
 // exercise exactly the launches a step issues.
 //
-//   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more than 8 sequences in groups
+//   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more sequences than fit a launch's LDS (at most 8) in groups
 //   Q80, fast path          SLAB GEMV (1..8 sequences on the small per-layer matrices; 1..2 on those of >= 8 M weights)   gemv_q80_impl.h
 //                           G6 (fragment-order activations: MODE S staged in LDS, MODE F per item; 2..64 tokens) gemm_q80_g6.hip
 //                           G7 (17..64 tokens: loader / consumer engine, both operands through LDS) gemm_q80_g7.hip
@@ -77,10 +77,32 @@ static GemvArgs gemv_slice(const GemvArgs &a, uint32_t b0, uint32_t cnt) {
     return s;
 }
 
+// FP32: every workgroup holds the activations of all its sequences in LDS, so long rows take fewer sequences per launch
+// (gemv_f32_fit_batch(): 8 wherever 8 fit -- the groups of 8 a batch beyond 8 has always run in)
+bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
+    if (a.nb == 0) return false;
+    GemvArgs one = a; one.nb = a.nb < 8u ? a.nb : 8u;
+    const uint32_t fit = gemv_f32_fit_batch(one);
+    if (fit == 0) return false;
+    *per = a.nb < fit ? a.nb : fit;
+    *launches = (a.nb + fit - 1) / fit;
+    return true;
+}
+
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     const uint32_t max_wg = (r.cus ? (uint32_t)r.cus : 256u) * 8u;
     a.cus = (uint32_t)r.cus;
     const RouteKind k = route_kind(r, a);
+    if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) {      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
+        uint32_t per = 0, launches = 0;
+        if (!route_f32_slices(a, &per, &launches)) return hipErrorInvalidValue;
+        if (launches == 1) return launch_gemv_f32(a, st);
+        for (uint32_t b0 = 0; b0 < a.nb; b0 += per) {
+            const hipError_t e = launch_gemv_f32(gemv_slice(a, b0, a.nb - b0 < per ? a.nb - b0 : per), st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
     switch (k) {
     case ROUTE_Q4K: {
         // every workgroup stages the whole quantized activation of each sequence in LDS: long rows (Qwen3-4B's hidden size)

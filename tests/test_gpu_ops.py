@@ -115,7 +115,16 @@ def test_matmul_f32(oracle, n, d):
     rng = np.random.default_rng(n + d)
     w = (0.02 * rng.standard_normal((d, n))).astype(np.float32)
     x = rng.standard_normal(n).astype(np.float32)
-    assert rel_err(nb.op_matmul_f32(x, w), oracle.matmul_f32(x, w)) < 1e-5      # tree vs sequential sum
+    out = nb.op_matmul_f32(x, w)
+    assert rel_err(out, oracle.matmul_f32(x, w)) < 1e-5      # tree vs sequential sum
+    # ... and row by row against float64 under the bound of the kernel's summation order (derived in test_gpu_f32_gemv.py: 4
+    # roundings in a lane's float4 chain, 6 tree levels, the ordered chunk adds, the final rounding), which a small row that
+    # lost a chunk cannot hide under
+    ref = w.astype(np.float64) @ x.astype(np.float64)
+    S = np.abs(w.astype(np.float64)) @ np.abs(x.astype(np.float64))
+    bound = (10 + (n + 255) // 256) * 2.0 ** -24 * S + 2.0 ** -24 * np.abs(ref)
+    d = np.abs(out.astype(np.float64) - ref)
+    assert np.all(d <= bound), (np.flatnonzero(d > bound)[:8], float((d / bound).max()))
 
 
 @pytest.mark.parametrize("n", [128, 768, 1024, 2560])
