@@ -1,0 +1,235 @@
+// backend_model.h -- the model struct of the C-ABI device backend and what its translation units share.  Internal: nothing here is part
+// of the C ABI (include/nano_mi355x.h), and nothing declared here is exported by the library.
+//   backend.hip          create / destroy / layout, the forward / prefill / greedy entry points, the sticky error word and the re-issue policy
+//   backend_step.hip     the argument builders, the fast step, the reference-order step, graphs, run_step, the strict / exact switches
+//   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
+//   backend_sampler.hip  the device-side sampler's scratch and its four entry points
+//   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
+#pragma once
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <hip/hip_fp16.h>
+#include "../../include/nano_mi355x.h"
+#include "kernels.h"
+
+using namespace nano;
+extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the thread's nano_hip_last_error() text
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            char _b[512];                                                                          \
+            snprintf(_b, sizeof _b, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            nano_hip_set_error_(_b);                                                               \
+            return NANO_HIP_ERUNTIME;                                                              \
+        }                                                                                          \
+    } while (0)
+#define FAIL(code, ...)                                                                            \
+    do {                                                                                           \
+        char _b[512];                                                                              \
+        snprintf(_b, sizeof _b, __VA_ARGS__);                                                      \
+        nano_hip_set_error_(_b);                                                                   \
+        return (code);                                                                             \
+    } while (0)
+
+#pragma GCC visibility push(hidden)
+
+enum { WQ = 0, WK, WV, WO, W1, W2, W3, WCOUNT };
+enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3 };
+constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs kept per model (keyed by KV slot x range bucket)
+constexpr uint32_t STAMP_MAX_LAUNCHES = 512, STAMP_WGS = 2048;
+constexpr uint32_t KV_NO_PAGE = 0xffffffffu;           // a page-table entry without a page
+
+struct TensorRef { const void *w = nullptr; const float *s = nullptr; };
+struct Sampler;                                        // backend_sampler.hip
+
+struct NanoHipModel {
+    NanoModelDesc d{};
+    int device = 0, cus = 0;
+    uint32_t S = 0, maxB = 0, hd = 0, QD = 0, KD = 0;
+    uint32_t Bs = 0;                                      // rows of the per-token scratch (>= maxB: a prefill chunk processes Bs prompt tokens of ONE sequence)
+    uint32_t pf_slot = 0; bool pf = false;                // prefill in progress: every token of the step lives in KV slot pf_slot
+    hipStream_t st = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    bool probe_cls = false, probe_ext = false;                               // record ev0 / ev1 / ev2 around the classifier launch of the next eager step
+    uint8_t *arena = nullptr;
+    size_t arena_bytes = 0;
+    const float *rms_attn = nullptr, *rms_ffn = nullptr, *rms_final = nullptr;
+    const float *q_norm = nullptr, *k_norm = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
+    TensorRef tok, cls;
+    std::vector<TensorRef> W[WCOUNT];
+    // per-sequence state
+    float *x = nullptr, *q = nullptr, *kraw = nullptr, *xba = nullptr, *hb = nullptr, *logits = nullptr;
+    float *attn_part = nullptr, *attn_ml = nullptr;       // split-attention partials [B][nsplit][QD], [B][n_head][nsplit][2]
+    float *tile_max = nullptr;                            // classifier arg-max partials [B][<=V][2]
+    // LoRA module (Nano architecture, reference infer.c:434-498): 8 FP32 tensors in one device buffer + o1 scratch
+    float *lora_buf = nullptr, *lora_o1 = nullptr;
+    const float *lora_t[8] = {nullptr};                   // qa qb ka kb va vb oa ob, each [L][...]
+    uint32_t lora_rank = 0, lora_alpha = 0; bool lora_on = false;
+    int8_t *gq = nullptr; float *gxs = nullptr;           // MFMA GEMM path (batch > 8, Q80): quantized activations of all sequences
+    uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 8 sequences: the staged activation groups (gemv_q4k_chunk.hip)
+    float *rope_cur = nullptr;                            // RoPE rows of the current positions [B][2][hd/2], staged by the embed kernel
+    float *kcache = nullptr, *vcache = nullptr;
+    uint32_t *tokens = nullptr, *pos = nullptr, *amax = nullptr, *trace = nullptr, *pos0 = nullptr;
+    uint32_t trace_cap = 0, nsplit = 1;                  // nsplit: splits xba still has to be combined from after the LAST enqueued step (1: final)
+    uint32_t nsplit_cap = 8;                             // the partial buffers are sized for it (32 beyond 2048 positions)
+    // pinned host staging
+    uint32_t *h_tokens = nullptr, *h_pos = nullptr, *h_amax = nullptr;
+    uint32_t *pf_stage = nullptr; uint32_t pf_cap = 0;    // batched prefill: the prompt's tokens | positions on the device (the chunks copy from here: no host round trip per chunk)
+    uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
+    float *h_logits = nullptr;
+    std::map<uint64_t, hipGraphExec_t> graphs;
+    std::vector<uint64_t> pf_graph_keys;                  // prefill-chunk graphs in creation order (bounded: PF_GRAPH_CAP)
+    uint64_t weight_bytes_per_step = 0;
+    bool use_graph = true;
+    uint32_t mfma_min_nb = 9;                             // sequences per step from which Q80 GEMVs go to the MFMA GEMM (NANO_MFMA_MIN_NB: measurement)
+    // the in-launch hand-offs of the fused one-sequence launches
+    struct Handoff {
+        bool fuse_qkv_attn = true;                        // one sequence, Q80 gs 64, Qwen3 head_dim 128: q|k|v projection + attention in one launch; NANO_FUSE_LAUNCHES bit 0
+        unsigned long long *hand = nullptr;               // its granule buffer (q_dim + 2 kv_dim entries of {tag, value}; tags are epochs: device_common.h)
+        bool fuse_wo_w13 = true;                          // one sequence, Q80 gs 64: Wo + W1|W3 in one launch (x as granules); NANO_FUSE_LAUNCHES bit 1
+        unsigned long long *hand2 = nullptr;              // its granule buffer (n_embd entries)
+        uint32_t *tick = nullptr;                         // device words of the in-launch hand-offs: [0] step counter (the epoch), [1] fault word, [2] abort flag, [3] spare
+        uint32_t fallbacks = 0;                           // times a hand-off gave up and the call was re-issued through the plain launches (fusion stays off after the first)
+        bool reissue = true;                              // (nano_hip_debug_fault bit 1 clears it: the give-up then surfaces as NANO_HIP_ERUNTIME)
+        uint32_t last_dev_err = 0;                        // the code bits of the last give-up (diagnostics)
+    } ho;
+    std::vector<uint32_t> fw_tokens, fw_pos; uint32_t fw_causal = 0; int fw_logits = 0, fw_argmax = 0;   // the step queued by nano_hip_forward_begin (for its re-issue)
+    Sampler *smp = nullptr;                               // device-side sampler scratch (max_batch rows), created on first use
+    uint32_t rope_rows = 0;       // rows of the RoPE tables on the device: positions >= rope_rows are rejected
+    uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
+    bool kv_half = false;         // opt-in FP16 KV cache: rows hold __half, v passes through vraw like k through kraw
+    float *vraw = nullptr;        // [Bs][KD] fresh v rows (FP16 cache only)
+    // greedy loop (nano_hip_decode_greedy): from the second step on the previous step's arg-max kernel has already embedded this
+    // step's token (misc.hip argmax_kernel) -- the step then starts at layer 0's QKV launch
+    bool skip_embed = false;
+    // paged KV cache (opt-in): kcache / vcache are pools [L][pages][64][KD]; pt = first pool row of every 64-position block
+    struct PagedKv {
+        bool paged = false;
+        uint32_t pages = 0, pt_stride = 0;                // pages in the pool; page-table entries per slot = ceil(S / 64)
+        uint32_t *pt = nullptr, *kvrow = nullptr;         // device: [maxB][pt_stride] (KV_NO_PAGE = no page), [Bs] pool row of the step's position
+        uint32_t *h_pt = nullptr;                         // pinned host mirror of pt
+        std::vector<uint32_t> free_pages;
+        std::vector<uint32_t> page_owners;                // slots whose table points at each page (0: free; > 1: shared, read-only until copied on write)
+        uint64_t cow_copies = 0;                          // pages copied because a slot was about to write into a page it shared
+        std::vector<std::vector<uint32_t>> pt_stage;      // staging copies of page-table rows / copy jobs whose upload may still be queued (backend_kv.hip)
+        // row copies between slots / pages (kv_copy.hip): the device job list of the launch being queued, grown on demand
+        uint32_t *jobs = nullptr; size_t jobs_cap = 0;    // capacity in 32-bit words
+        bool copy_nt = false;                             // NANO_KV_COPY_NT=1: non-temporal stores in the copy kernel (measurement, tools/prefix_probe.py)
+    } kv;
+    // strict-parity / per-phase mode (strict.hip): eager, one kernel per reference operator, reference summation order
+    bool strict = false;
+    float *xn = nullptr, *hb2 = nullptr, *att = nullptr;   // normalised x [Bs][E], W3 output [Bs][H], attention scores [Bs][n_head][S]
+    nano_hip_phase_fn phase_fn = nullptr; void *phase_env = nullptr;
+    // exact mode (exact.hip): strict mode's bits from a step that is captured once per (batch, mode, is_causal[, prefill slot]) and replayed
+    bool exact = false;
+    std::map<uint64_t, uint32_t> exact_nodes;             // kernel nodes of each exact-mode graph (same keys as `graphs`)
+    uint32_t exact_launches = 0;                          // ... of the last enqueued exact step (0: graphs are off, nothing was counted)
+    // measurement (stamps build, tools/stamp_probe.py): per-launch, per-workgroup phase stamps of the steps run after nano_hip_stamps_begin
+    struct Stamps {
+        unsigned long long *buf = nullptr; uint32_t launches = 0; bool on = false;
+        std::vector<uint32_t> kinds;
+    } stamp;
+};
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline size_t kv_esz(const NanoHipModel *m) { return m->kv_half ? 2 : 4; }      // bytes of a KV cache element
+// bytes of n_weights weights in a format: FP32 | Q80 int8 + one FP32 scale per group | Q4K 160-byte blocks of 256
+inline uint64_t weight_bytes(uint32_t quant, uint32_t gs, uint64_t n_weights) {
+    return quant == NANO_QUANT_F32 ? 4 * n_weights : quant == NANO_QUANT_Q80 ? n_weights + 4 * (n_weights / gs) : n_weights * 160 / 256;
+}
+
+// ---- backend.hip: the sticky error word and the hand-offs' fallback ----
+uint32_t dev_err_take(NanoHipModel *m);
+int dev_err_fail(uint32_t c);
+int dev_err_check(NanoHipModel *m);
+void handoff_fallback(NanoHipModel *m);
+void drop_graphs(NanoHipModel *m);
+int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps);
+// THE re-issue policy of every entry point that hands results over (round-6 advice: correctness after a give-up depends on every one of
+// them re-issuing at the same positions).  attempt(again) queues the call's work and synchronises the stream; an error it returns is
+// the call's, without a look at the sticky word.  A hand-off that gave up gets the same work once more (again = true: same tokens,
+// same positions, the KV rows are rewritten) through the plain launches: the caller sees the results, not an error.  Any other code, a
+// second give-up, or re-issue switched off fails the call.
+template <class Attempt>
+static int with_reissue(NanoHipModel *m, Attempt attempt) {
+    for (int again = 0;; again++) {
+        if (const int rc = attempt(again != 0)) return rc;
+        const uint32_t code = dev_err_take(m);
+        if (!code) return 0;
+        if (again || !m->ho.reissue || code != NANO_DEVERR_HANDOFF) return dev_err_fail(code);
+        handoff_fallback(m);
+    }
+}
+
+// ---- backend_kv.hip ----
+// The KV rows of one step, built once per enqueue_step / enqueue_step_ordered: sequence b lives in KV slot `slot` + b, or -- one_slot,
+// batched prefill -- every token is a position of `slot`.  Contiguous cache: [slot][layer][S][kv_dim].  Paged cache: pools
+// [layer][page][64][kv_dim], a slot's table names the first pool row of each of its 64-position blocks.  Elements are FP32, or FP16
+// (kv_half); the caches are held as float *, so an offset into an FP16 cache goes through at() -- float * arithmetic counts 4-byte units.
+struct KvRows {
+    const NanoHipModel *m; uint32_t slot; bool one_slot;
+    size_t layer_elems() const { return (size_t)m->S * m->KD; }                                   // contiguous: one layer of one slot
+    size_t slot_elems() const { return (size_t)m->d.n_layer * layer_elems(); }
+    size_t plane_elems() const { return (size_t)m->kv.pages * 64 * m->KD; }                       // paged: one layer plane of the pool
+    float *at(float *cache, size_t elems) const { return reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(cache) + elems * kv_esz(m)); }
+    // FP32 rows of layer l of `slot`, contiguous layout, and the floats between the step's sequences: the LoRA branch's v / v_bstride on every cache it is let near (step_served())
+    float *v_flat(uint32_t l) const { return m->vcache + (size_t)slot * slot_elems() + l * layer_elems(); }
+    uint32_t v_flat_bstride() const { return one_slot ? 0u : (uint32_t)slot_elems(); }
+    // where the q | k | v launch puts layer l's fresh v row: out + b * bstride + pos[b] * pstride
+    struct VTarget { float *out; uint32_t bstride, pstride; const uint32_t *pos; };
+    VTarget v_target(uint32_t l) const;
+    // the attention launch's K / V bases and the rows between its sequences (the kernel adds the layer itself)
+    void attention(AttnArgs &a) const;
+    // element offset of the row of (layer, pos) of `slot` in kcache / vcache (nano_hip_read_state); false: paged, and no page holds it yet
+    bool row(uint32_t layer, uint32_t pos, size_t *elems) const;
+};
+int kv_ensure(NanoHipModel *m, const uint32_t *slots, const uint32_t *first, const uint32_t *need, uint32_t n);
+int kv_ensure_batch(NanoHipModel *m, const uint32_t *pos, uint32_t batch, uint32_t extra, bool whole_context);
+void sampler_free(Sampler *sp);                        // backend_sampler.hip
+
+// ---- backend_step.hip ----
+hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr);
+hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint);
+bool strict_serves(const NanoHipModel *m);
+bool exact_serves(const NanoHipModel *m);
+int step_served(const NanoHipModel *m, bool prefill);
+int run_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0);
+int stage_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, bool also_pos0, uint32_t *max_pos = nullptr);
+uint32_t range_hint_of(const NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t max_pos);
+int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos);
+// HIP graphs of a step: replay the graph stored under `key`, or -- first use -- run enqueue() eagerly (the launchers set their kernel
+// attributes and validate their arguments outside any capture), capture the same enqueue() for the replays to come, instantiate and
+// store it.  Reports and leaves the policy to the caller: `step` is the error of the work this call had to queue (the replay or the
+// eager run), `capture` that of making the graph (the step itself has run), `stored` / `nodes` a graph made by this call.
+// enqueue is a template parameter: a replay pays the map lookup and hipGraphLaunch, nothing for the callable.
+struct GraphRun { hipError_t step = hipSuccess, capture = hipSuccess; bool stored = false; uint32_t nodes = 0; };
+template <class Enqueue>
+static GraphRun graph_step(NanoHipModel *m, uint64_t key, Enqueue enqueue) {
+    GraphRun r;
+    auto it = m->graphs.find(key);
+    if (it != m->graphs.end()) { r.step = hipGraphLaunch(it->second, m->st); return r; }
+    if ((r.step = enqueue()) != hipSuccess) return r;
+    if ((r.capture = hipStreamBeginCapture(m->st, hipStreamCaptureModeRelaxed)) != hipSuccess) return r;
+    hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+    r.capture = enqueue();
+    const hipError_t e2 = hipStreamEndCapture(m->st, &g);               // (always: the stream must leave capture mode)
+    if (r.capture == hipSuccess) r.capture = e2;
+    size_t nodes = 0;
+    if (r.capture == hipSuccess) (void)hipGraphGetNodes(g, nullptr, &nodes);
+    if (r.capture == hipSuccess) r.capture = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    if (r.capture == hipSuccess) { m->graphs.emplace(key, ge); r.stored = true; r.nodes = (uint32_t)nodes; }
+    return r;
+}
+
+#pragma GCC visibility pop

@@ -20,7 +20,7 @@
 //
 // The attention launch holds att[range] in the workgroup's LDS; range can reach the model's max_seq_len (one graph serves every
 // position).  exact_attention_fits() says whether that fits XA_LDS_BYTES; where it does not (max_seq_len > 7168) the step keeps
-// strict.hip's three attention launches with att in global memory (backend.hip enqueue_step_ordered), so no context length is refused.
+// strict.hip's three attention launches with att in global memory (backend_step.hip enqueue_step_ordered), so no context length is refused.
 #include "device_common.h"
 #include "exact_math.h"
 #include "kernels.h"

@@ -445,7 +445,7 @@ static hipError_t launch_g2(const GemvArgs &a, hipStream_t st) {
 }  // namespace
 
 // Host-side predicate: does the GEMM take this launch?  (What it does not take goes through the GEMV kernels in groups
-// of 8 sequences, backend.hip gemv().)  Not taken: interior segments that are not multiples of the 16-row tile, a
+// of 8 sequences, route.hip route_projection().)  Not taken: interior segments that are not multiples of the 16-row tile, a
 // split-attention input, the LoRA o-branch addend.
 bool gemm_q80_g2_supports(const GemvArgs &a) {
     if (a.nb == 0 || a.nb > 64 || a.gs == 0 || a.n % a.gs || a.n % 16 || a.nseg == 0 || a.nseg > 3 || a.attn_part || a.resid_add) return false;
@@ -484,7 +484,7 @@ hipError_t launch_quant_rows_frag(const float *x, uint32_t x_bstride, const floa
     return hipGetLastError();
 }
 
-// rmsnorm (optional) + Q80 quantization of nb activation rows, row-major (the quantize-once GEMV path of backend.hip)
+// rmsnorm (optional) + Q80 quantization of nb activation rows, row-major (the quantize-once GEMV path of route.hip)
 hipError_t launch_quant_rows(const float *x, uint32_t x_bstride, const float *norm_w, uint32_t n, uint32_t gs, uint32_t nb,
                              int8_t *xq, float *xs, hipStream_t st) {
     if (!nb || gs == 0 || n % gs || n % 4) return hipErrorInvalidValue;

@@ -12,7 +12,7 @@
 //     its transposition buffer (wave-private LDS, pitch 528: conflict-free ds_read_b128 of the MFMA A fragments);
 //   * one v_mfma_i32_16x16x64_i8 per (group, token tile) -> exact int32 group sums -> ((float)ival * ws) * xs (infer.c:672) added
 //     to the running value of (row, token) in ascending group order: bit-identical to the GEMV path and to the reference.
-// Takes: group size 64, one STORE segment of >= 16384 rows, group count a multiple of 8 or 4.  (backend.hip routes the classifier
+// Takes: group size 64, one STORE segment of >= 16384 rows, group count a multiple of 8 or 4.  (route.hip routes the classifier
 // of batched steps here.)
 #include <atomic>
 #include "gemv_common.h"

@@ -6,8 +6,7 @@
 
 namespace nano {
 
-hipError_t launch_gemv(uint32_t quant, GemvArgs &a, uint32_t max_wg, hipStream_t st) {
-    (void)max_wg;
+hipError_t launch_gemv(uint32_t quant, GemvArgs &a, hipStream_t st) {
     if (quant == 0x80u) return launch_gemv_q80(a, st);
     return launch_gemv_f32(a, st);
 }
@@ -18,6 +17,23 @@ uint32_t gemv_tiles(uint32_t quant, const GemvArgs &a) {
     if (quant == 0x80u) return gemv_q80_partials(a);
     if (quant == 0x42u) return gemv_q4k_partials(a);
     return 0;
+}
+
+// ---- the fused q | k | v + attention launch: each format's pair lives with its kernel ----
+#define NANO_FUSED_PAIR(F) bool qkv_attn_fused_##F##_supports(const GemvArgs &, const AttnArgs &); \
+                           hipError_t launch_qkv_attn_fused_##F(const GemvArgs &, const AttnArgs &, unsigned long long *, uint32_t *, uint32_t, hipStream_t);
+NANO_FUSED_PAIR(q80) NANO_FUSED_PAIR(q4k) NANO_FUSED_PAIR(f32)
+#undef NANO_FUSED_PAIR
+
+bool qkv_attn_fused_supports(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa) {
+    if (quant == 0x80u) return qkv_attn_fused_q80_supports(ga, aa);
+    if (quant == 0x42u) return qkv_attn_fused_q4k_supports(ga, aa);
+    return qkv_attn_fused_f32_supports(ga, aa);
+}
+hipError_t launch_qkv_attn_fused(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
+    if (quant == 0x80u) return launch_qkv_attn_fused_q80(ga, aa, hand, tick, layer1, st);
+    if (quant == 0x42u) return launch_qkv_attn_fused_q4k(ga, aa, hand, tick, layer1, st);
+    return launch_qkv_attn_fused_f32(ga, aa, hand, tick, layer1, st);
 }
 
 }  // namespace nano

@@ -90,6 +90,26 @@ struct GemvDev {
     uint32_t *err;                  // sticky error word (host-mapped; nullptr in operator tests): a kernel that gives up a bounded wait ORs its code in
 };
 
+// ---- the fused q | k | v + attention launches (Q80: gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip, FP32: gemv_f32.hip) ----
+// Their argument block: the projection's, the attention's, the granule buffer; the first `ngemv` workgroups are the projection's, the last
+// `n_attn` the attention's (head_wgs per split), which nap wait16 x 16 x 64 cycles before their first poll.
+struct QkvAttnArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
+// The attention side's host set-up, the same for every format: the workgroup order of fa.a (both head counts are powers of two:
+// fused_attn_side_ok()), the granule bases of q | k | v in `hand`, the attention workgroups.  Returns the LDS bytes of an attention
+// workgroup: q | k | maxima | sums | 4 waves' partials | the fresh v row, and -- the Qwen3 mode, attn_impl.h FAST -- | 4 give-up words |
+// 4 waves x 8 sub-groups' weighted rows.
+static size_t fused_attn_setup(QkvAttnArgs &fa, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, bool plain) {
+    AttnArgs &a = fa.a;
+    a = aa;
+    { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
+    { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
+    fa.hand.buf = hand; fa.hand.tick = tick; fa.hand.layer1 = layer1;
+    fa.hand.base[0] = 0; fa.hand.base[1] = a.q_dim; fa.hand.base[2] = a.q_dim + a.kv_dim;
+    fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head;
+    const size_t hd4 = (a.hd + 3) & ~3u;
+    return (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + (plain ? 0 : 4 + 4 * 8 * hd4)) * sizeof(float);
+}
+
 template <int ROLE> __device__ __forceinline__ bool has_flag(const GemvDev &a, uint32_t f) {
     if (ROLE == R_GENERIC) return (a.flags & f) != 0;
     if (f == F_NORM) return ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU;

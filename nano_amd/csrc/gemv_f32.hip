@@ -149,9 +149,8 @@ namespace {
 // The first `ngemv` workgroups run the projection's SLAB body (results stored as usual AND as granules), the last n_attn the attention's
 // plain decode mode (attention_body MODE 2), 256 threads for both.  Epoch tags, give-up and re-issue: device_common.h, backend.hip.
 // Reference: infer/infer.c:637-651, 758-879.
-struct F32FusedArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
 template <int NV, int UPW, int QV>            // QV: float4 slots per lane of the attention's 8-lane sub-groups (1: head_dim <= 32, 2: <= 64 -- launch_attention's choice)
-__global__ __launch_bounds__(256) void f32_qkv_attn_fused_kernel(const F32FusedArgs fa) {
+__global__ __launch_bounds__(256) void f32_qkv_attn_fused_kernel(const QkvAttnArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint2 tk_ = hand_tick(fa.hand);
     if (blockIdx.x >= fa.ngemv) {
@@ -250,7 +249,7 @@ static bool f32_fused_shape(const GemvArgs &ga, const AttnArgs &aa, F32Plan &p) 
     const uint32_t units = (p.rw / 4) * ((ga.n + 255) / 256);
     p.upw = (units + 3u) / 4u;
     if (p.upw > 4u) return false;
-    return fused_attn_side_ok_plain(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows);
+    return fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, true);
 }
 
 }  // namespace
@@ -272,22 +271,16 @@ hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, uns
     uint32_t rows = 0;
     for (uint32_t s2 = 0; s2 < 3; s2++) rows += ga.seg[s2].rows;
     const uint32_t ngemv = (rows + p.rw - 1) / p.rw;
-    AttnArgs a = aa;
-    { uint32_t k2 = 0; while ((1u << k2) < a.n_kv_head) k2++; a.kv_log2 = k2; }
-    { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t k2 = 0; while ((1u << k2) < kv_mul) k2++; a.kvmul_log2 = k2; }
-    SlabHand h{};
-    h.buf = hand; h.tick = tick; h.layer1 = layer1;
-    h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
+    QkvAttnArgs fa{};
+    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, true);
     const size_t n4 = (d.n + 3) & ~3u, pc = (d.nchunk + 3) & ~3u;
     const size_t lds_g = (n4 + 16 + (size_t)p.rw * pc) * 4;
-    const size_t hd4 = (a.hd + 3) & ~3u, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4) * sizeof(float);    // q | k | maxima | sums | 4 waves' partials | the fresh v row
     const size_t lds = lds_g > lds_a ? lds_g : lds_a;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    F32FusedArgs fa{};
-    fa.g = d; fa.a = a; fa.hand = h; fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head; fa.ngemv = ngemv;
+    fa.g = d; fa.ngemv = ngemv;
     fa.wait16 = 1u;             // naps of 16 x 64 cycles before the attention's first poll: Nano-168M, one box, 0 / 1 / 2 / 3 naps: 2387 / 2384 / 2380 / 2364 and 2383 / 2381 / 2380 / 2366 tok/s
     const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-#define F32F_GO(UPW_) do { if (a.hd <= 32u) hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 1>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa); \
+#define F32F_GO(UPW_) do { if (aa.hd <= 32u) hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 1>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa); \
                            else hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 2>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa); return hipGetLastError(); } while (0)
     if (upw == 1) F32F_GO(1);
     if (upw == 2) F32F_GO(2);

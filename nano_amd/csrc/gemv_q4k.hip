@@ -353,15 +353,14 @@ static hipError_t launch_q4k_b(const GemvArgs &a, hipStream_t st) {
 }  // namespace
 
 // Sequences per launch that fit the 160 KB of LDS (every workgroup holds the whole quantized activation of each sequence):
-// 8 for Qwen3-0.6B's row lengths, 2 for Qwen3-4B's hidden size 9728.  The caller slices larger steps (backend.hip gemv()).
+// 8 for Qwen3-0.6B's row lengths, 2 for Qwen3-4B's hidden size 9728.  The router slices larger steps (route.hip route_projection()).
 uint32_t gemv_q4k_fit_batch(const GemvArgs &a) {
     for (uint32_t c = 8; c > 1; c >>= 1)
         if (q4k_lds_bytes(a.n, a.epi, a.attn_part != nullptr, a.attn_n_head, plan_q4k(a, (int)c).rw, c) <= 160 * 1024) return c;
     return 1;
 }
 
-hipError_t launch_gemv_q4k(GemvArgs &a, uint32_t max_wg, hipStream_t st) {
-    (void)max_wg;
+hipError_t launch_gemv_q4k(GemvArgs &a, hipStream_t st) {
     if (a.nb >= 1 && a.nb <= 8 && gemv_q4k_chunk_takes(a)) return launch_gemv_q4k_chunk(a, st);     // whole blocks: gemv_q4k_chunk.hip (2 .. 8 sequences: with scratch)
     if (a.nb == 0 || a.nb > 8 || a.n % 4 || a.nseg == 0 || a.nseg > 3) return hipErrorInvalidValue;
     if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd % 4)) return hipErrorInvalidValue;

@@ -63,9 +63,8 @@ namespace {
 // The first `ngemv` workgroups are the projection's chunk GEMV (role: rmsnorm + block quantizer + store), whose fold threads also store every
 // result as an 8-byte {tag, value} granule; the LAST n_attn workgroups are the attention's (head x split): they ask for their K / V rows at
 // entry, nap, then poll for q, the raw k row and the fresh v row of their KV group.  256 threads for both kinds (q4k_fused_shape).  Epoch tags, give-up and re-issue: device_common.h, backend.hip.  Reference: infer/infer.c:758-879.
-struct Q4FusedArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
 template <int NV, int D>
-__global__ __launch_bounds__(256) void q4k_qkv_attn_fused_kernel(const Q4FusedArgs fa) {
+__global__ __launch_bounds__(256) void q4k_qkv_attn_fused_kernel(const QkvAttnArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint2 tk_ = hand_tick(fa.hand);                       // the step's epoch: the first load of every workgroup
     if (blockIdx.x >= fa.ngemv) {
@@ -295,7 +294,7 @@ static bool q4k_fused_shape(const GemvArgs &ga, const AttnArgs &aa, ChunkPlan &p
     // per thread on threads 0 .. n / 4 - 1 either way, a Q4K block is one wave's, the waves beyond add +0.0 to the norm's sum.
     if (ga.n > 1024u || !plan_chunk(ga, p, 4u) || p.loop || p.nthr != 256u || p.nv != 1u) return false;
     if (p.lds > 64u * 1024u) return false;
-    return fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows);
+    return fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false);
 }
 bool qkv_attn_fused_q4k_supports(const GemvArgs &ga, const AttnArgs &aa) { ChunkPlan p; return q4k_fused_shape(ga, aa, p); }
 
@@ -308,16 +307,9 @@ hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, uns
     d.rw = p.rw; d.nthr = p.nthr; d.units = p.rounds;
     d.magic_nchunk = (uint32_t)(((1ull << 32) + bpl - 1) / bpl);
     d.wg_c0 = p.wg[0]; d.wg_c1 = p.wg[0] + p.wg[1];
-    AttnArgs a = aa;
-    { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
-    { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
-    SlabHand h{};
-    h.buf = hand; h.tick = tick; h.layer1 = layer1;
-    h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
-    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + 4 + 4 * 8 * hd4) * sizeof(float);    // as gemv_q80_impl.h launch_qkv_attn_fused
-    const size_t lds = p.lds > lds_a ? p.lds : lds_a;
-    Q4FusedArgs fa{};
-    fa.g = d; fa.a = a; fa.hand = h; fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head; fa.ngemv = p.grid;
+    QkvAttnArgs fa{};
+    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, false), lds = p.lds > lds_a ? p.lds : lds_a;
+    fa.g = d; fa.ngemv = p.grid;
     // naps of 16 x 64 cycles between the K / V requests and the first poll.  Same box, driver's flags (profiles/r06_q4k_fused.txt): the five
     // launches per layer 1733 / 1755 tok/s; fused with 2 naps 1773 / 1818, 4: 1782 / 1779, 6: 1742 / 1739, 8: 1684 / 1688
     // (re-swept at the end of round 6, producers first in the grid: 0 / 1 / 2 / 3 naps 1789 / 1761 / 1782 / 1780 and 1784 / 1778 / 1779 / 1775 tok/s: flat; none)

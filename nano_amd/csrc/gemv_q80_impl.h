@@ -350,16 +350,15 @@ namespace {
 // Round 6: the PRODUCERS come first in the grid (round-5 advice: with the consumers in front, a chip that other work keeps busy could seat
 // the pollers and leave the projection waiting for their slots); granules carry epoch tags (device_common.h), a consumer that gives up
 // skips its stores.  Reference: infer/infer.c:758-879.
-struct FusedArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
 template <int NV, int UPW>
-__global__ __launch_bounds__(256) void qkv_attn_fused_kernel(const FusedArgs fa) {
+__global__ __launch_bounds__(256) void qkv_attn_fused_kernel(const QkvAttnArgs fa) {
 #define SLAB_WF 0
 #include "qkv_attn_fused_body.inc"
 #undef SLAB_WF
 }
 // ... its form for n == 1024 (rows of one chunk): no product table, no barrier between the dots and the granules the attention workgroups wait for
 template <int NV, int UPW>
-__global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const FusedArgs fa) {
+__global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const QkvAttnArgs fa) {
 #define SLAB_WF 1
 #include "qkv_attn_fused_body.inc"
 #undef SLAB_WF
@@ -771,7 +770,7 @@ static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, SlabPlan &p) {
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
     p = plan_slab(ga, 1);
     if (p.nw != 4u || p.upw > 4u || !(p.nv == 1u || p.nv == 2u || p.nv == 4u)) return false;        // 256 threads, like the attention workgroups
-    if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows)) return false;          // (kernels.h)
+    if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;   // (kernels.h)
     return true;
 }
 
@@ -842,9 +841,9 @@ static hipError_t launch_gs(const GemvArgs &a, hipStream_t st) {
 hipError_t NANO_Q80_ENTRY(const GemvArgs &a, hipStream_t st) { return launch_gs<NANO_Q80_GS>(a, st); }
 
 #if NANO_Q80_GS == 64
-bool qkv_attn_fused_supports(const GemvArgs &ga, const AttnArgs &aa) { SlabPlan p; return fused_shape(ga, aa, p); }
+bool qkv_attn_fused_q80_supports(const GemvArgs &ga, const AttnArgs &aa) { SlabPlan p; return fused_shape(ga, aa, p); }
 
-hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
+hipError_t launch_qkv_attn_fused_q80(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
     SlabPlan p;
     if (!hand || !tick || !layer1 || layer1 > 127u || !fused_shape(ga, aa, p)) return hipErrorInvalidValue;
     GemvDev d = to_dev(ga);
@@ -856,23 +855,16 @@ hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigne
     d.wg_c0 = wg[0]; d.wg_c1 = wg[0] + wg[1];
     const uint32_t ngemv = wg[0] + wg[1] + wg[2];
     d.nthr = 256;
-    AttnArgs a = aa;
-    { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
-    { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
-    SlabHand h{};
-    h.buf = hand; h.tick = tick; h.layer1 = layer1;
-    h.base[0] = 0; h.base[1] = a.q_dim; h.base[2] = a.q_dim + a.kv_dim;
-    const uint32_t n_attn = a.n_head * a.nsplit;
+    QkvAttnArgs fa{};
+    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, false);
+    const uint32_t n_attn = fa.n_attn;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
     const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
     const size_t lds_g = n16 + ng4 * 4 + 64 + (wf ? 0 : (size_t)(d.tpw * 4) * pitch * 4);
-    // q | k | maxima | sums | 4 waves' partials | the fresh v row | 4 give-up words | 4 waves x 8 sub-groups' weighted rows (attn_impl.h FAST)
-    const size_t hd4 = a.hd, lds_a = (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + 4 + 4 * 8 * hd4) * sizeof(float);
     const size_t lds = lds_g > lds_a ? lds_g : lds_a;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-    FusedArgs fa{};
-    fa.g = d; fa.a = a; fa.hand = h; fa.n_attn = n_attn; fa.head_wgs = a.n_head; fa.ngemv = ngemv;
+    fa.g = d; fa.ngemv = ngemv;
     // The attention workgroups nap `wait16` x 16 x 64 cycles between asking for their K / V rows and the first poll.  Round 5 (consumers FIRST in
     // the grid: they started before the projection) tuned 3: 1881-1887 tok/s without, 1899-1901 with 3, 1851 with 5.  Round 6 put the PRODUCERS
     // first -- the attention workgroups start last and the nap is mostly dead time: same box, driver's flags, 0 / 1 / 2 / 3 naps: 1984 / 1983 /

@@ -76,8 +76,8 @@ inline bool q80_canonical(const GemvArgs &a) {
     return true;
 }
 uint32_t gemv_tiles(uint32_t quant, const GemvArgs &a);   // tiles launch_gemv() will use (sizes tile_max)
-hipError_t launch_gemv(uint32_t quant, GemvArgs &a, uint32_t max_wg, hipStream_t st);
-hipError_t launch_gemv_q4k(GemvArgs &a, uint32_t max_wg, hipStream_t st);
+hipError_t launch_gemv(uint32_t quant, GemvArgs &a, hipStream_t st);
+hipError_t launch_gemv_q4k(GemvArgs &a, hipStream_t st);
 bool gemv_q4k_chunk_supports(const GemvArgs &a);            // gemv_q4k_chunk.hip: one sequence, whole 256-value blocks
 bool gemv_q4k_chunk_takes(const GemvArgs &a);               // ... or 2 .. 8 sequences where the chunk form is the faster one (gemv_q4k.hip)
 bool gemv_q4k_chunk_loops(const GemvArgs &a);               // ... and the launch is the looping (classifier) variant
@@ -140,7 +140,7 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
 // number; false: the shape is refused (hipErrorInvalidValue before any launch)
 bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
-uint32_t route_norm_order(const Q80Route &r, const GemvArgs &a);
+uint32_t route_norm_order(const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);
 
 // ---- attention ------------------------------------------------------------------------------------
@@ -195,17 +195,20 @@ hipError_t launch_attention(const AttnArgs &a, uint32_t nb, hipStream_t st);
 // it fills in (kv_log2 / kvmul_log2 of AttnArgs); the launcher takes every choice from here.  false: the arguments are refused.
 struct AttnPlan { uint32_t mode, lpr, qv, kvm, npt, w16, paged, kv_half, nsplit, kv_log2, kvmul_log2; };
 bool attention_plan(const AttnArgs &a, uint32_t nb, AttnPlan *p);
-// q | k | v projection (Q80 group size 64, one sequence) + Qwen3 decode attention as ONE launch (gemv_q80_impl.h): the attention workgroups wait
-// for q / k / v as 8-byte {tag, value} granules in `hand` (q_dim + 2 kv_dim entries); tag = the step's tick * 128 + layer1 (device_common.h)
-bool qkv_attn_fused_supports(const GemvArgs &ga, const AttnArgs &aa);
-hipError_t launch_qkv_attn_fused(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
+// q | k | v projection of one sequence + decode attention as ONE launch (gemv.hip dispatches on the weight format -- Q80 group size 64:
+// gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip, round 6, both with Qwen3 attention; FP32: gemv_f32.hip, the plain mode): the attention workgroups
+// wait for q / k / v as 8-byte {tag, value} granules in `hand` (q_dim + 2 kv_dim entries); tag = the step's tick * 128 + layer1 (device_common.h)
+bool qkv_attn_fused_supports(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa);
+hipError_t launch_qkv_attn_fused(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
 // Wo + W1|W3 of one sequence in ONE launch (gemv_q80_impl.h wo_w13_fused_kernel): x reaches W1|W3 as granules of the same launch
 bool wo_w13_fused_supports(const GemvArgs &wo, const GemvArgs &w13);
 hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
-// the attention side of the fused one-sequence launches (Q80: gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip): Qwen3 decode attention on an FP32
-// contiguous cache, head_dim 128, one head per workgroup, two timestep blocks in flight; qr / kr / vr = rows of the q | k | v segments
-inline bool fused_attn_side_ok(const AttnArgs &aa, uint32_t qr, uint32_t kr, uint32_t vr) {
-    if (aa.hd != 128u || !aa.q_norm || !aa.k_norm || !aa.rope_qwen3 || !aa.rope_cos || !aa.rope_cur || !aa.kraw || aa.fixed_range || !aa.is_causal || aa.q_out) return false;
+// the attention side of the fused one-sequence launches: decode attention on an FP32 contiguous cache, one head per workgroup, two timestep
+// blocks in flight -- Qwen3's at head_dim 128 (Q80, Q4K), or `plain` (FP32 models): no q / k norm, adjacent-pair RoPE (Nano), head_dim <= 64;
+// qr / kr / vr = rows of the q | k | v segments
+inline bool fused_attn_side_ok(const AttnArgs &aa, uint32_t qr, uint32_t kr, uint32_t vr, bool plain) {
+    if (plain ? (aa.hd < 4u || aa.hd > 64u || aa.hd % 4u || aa.q_norm || aa.k_norm || aa.rope_qwen3) : (aa.hd != 128u || !aa.q_norm || !aa.k_norm || !aa.rope_qwen3)) return false;
+    if (!aa.rope_cos || !aa.rope_cur || !aa.kraw || aa.fixed_range || !aa.is_causal || aa.q_out) return false;
     if (aa.kv_half || aa.pt_rows || aa.prep_only || aa.xf_out || aa.nsplit == 0 || aa.nsplit > 8u) return false;
     const uint32_t kv_mul = aa.n_kv_head ? aa.n_head / aa.n_kv_head : 0u;
     if (!aa.n_kv_head || (aa.n_kv_head & (aa.n_kv_head - 1u)) || !kv_mul || (kv_mul & (kv_mul - 1u))) return false;
@@ -213,21 +216,6 @@ inline bool fused_attn_side_ok(const AttnArgs &aa, uint32_t qr, uint32_t kr, uin
     if (aa.range_hint > aa.nsplit * 2u * 32u) return false;                     // (more than one round: the launcher may pick four blocks in flight)
     return aa.q_dim == qr && aa.kv_dim == kr && aa.kv_dim == vr && aa.q_dim == aa.n_head * aa.hd;
 }
-// ... and of the fused launch of FP32 models (gemv_f32.hip): the plain decode mode (no q / k norm, adjacent-pair RoPE: Nano), head_dim <= 64
-inline bool fused_attn_side_ok_plain(const AttnArgs &aa, uint32_t qr, uint32_t kr, uint32_t vr) {
-    if (aa.hd < 4u || aa.hd > 64u || aa.hd % 4u || aa.q_norm || aa.k_norm || aa.rope_qwen3 || !aa.rope_cos || !aa.rope_cur || !aa.kraw || aa.fixed_range || !aa.is_causal || aa.q_out) return false;
-    if (aa.kv_half || aa.pt_rows || aa.prep_only || aa.xf_out || aa.nsplit == 0 || aa.nsplit > 8u) return false;
-    const uint32_t kv_mul = aa.n_kv_head ? aa.n_head / aa.n_kv_head : 0u;
-    if (!aa.n_kv_head || (aa.n_kv_head & (aa.n_kv_head - 1u)) || !kv_mul || (kv_mul & (kv_mul - 1u))) return false;
-    if ((uint64_t)aa.n_head * aa.nsplit > 256u) return false;
-    if (aa.range_hint > aa.nsplit * 2u * 32u) return false;
-    return aa.q_dim == qr && aa.kv_dim == kr && aa.kv_dim == vr && aa.q_dim == aa.n_head * aa.hd;
-}
-bool qkv_attn_fused_f32_supports(const GemvArgs &ga, const AttnArgs &aa);
-hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
-// the same launch for Q4K (gemv_q4k_chunk.hip q4k_qkv_attn_fused_kernel, round 6)
-bool qkv_attn_fused_q4k_supports(const GemvArgs &ga, const AttnArgs &aa);
-hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
 uint32_t attention_nsplit(uint32_t range_hint, uint32_t hd);
 hipError_t launch_attn_combine(const float *part, const float *ml, float *out, uint32_t n_head, uint32_t hd, uint32_t nsplit, hipStream_t st);
 hipError_t launch_attn_combine_tokens(const float *part, const float *ml, float *out, uint32_t n_head, uint32_t hd, uint32_t nsplit, uint32_t nb,

@@ -1,5 +1,5 @@
 // kv_copy.hip -- the one kernel that moves KV-cache rows between slots / pages: the contiguous fork (rows [0, n_pos) of a slot to every
-// destination slot), the partial-block copy of a paged fork and the copy-on-write of a shared page (backend.hip nano_hip_kv_fork,
+// destination slot), the partial-block copy of a paged fork and the copy-on-write of a shared page (backend_kv.hip nano_hip_kv_fork,
 // kv_ensure).  The reference has no counterpart: it keeps one cache per context (infer/infer.c:46-51) and never copies rows.
 //
 // Work is a JOB LIST in device memory, {src_row, dst_row, rows, keep_rows} in cache rows inside a layer plane, cut into GROUPS of jobs that

@@ -55,7 +55,7 @@ extern "C" int nano_hip_op_rmsnorm(int device, float *out, const float *x, const
 }
 
 static int run_gemv(uint32_t quant, GemvArgs &a) {
-    hipError_t e = (quant == NANO_QUANT_Q4K) ? launch_gemv_q4k(a, 2048, 0) : launch_gemv(quant, a, 2048, 0);
+    hipError_t e = (quant == NANO_QUANT_Q4K) ? launch_gemv_q4k(a, 0) : launch_gemv(quant, a, 0);
     OP_HIP(e);
     OP_HIP(hipDeviceSynchronize());
     return 0;
@@ -240,7 +240,7 @@ extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     return 0;
 }
 
-// One fused GEMV launch as enqueue_step() issues it (backend.hip): the role-specialised kernels on caller-chosen inputs.
+// One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs.
 extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     int rc; if ((rc = begin(device))) return rc;
     if (!dp) { nano_hip_set_error_("null descriptor"); return NANO_HIP_EINVAL; }
@@ -315,7 +315,7 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     return 0;
 }
 
-// One decode attention launch as enqueue_step() issues it without the fused q|k|v launch (backend.hip: the AttnArgs block before
+// One decode attention launch as enqueue_step() issues it without the fused q|k|v launch (backend_step.hip: the AttnArgs block before
 // launch_attention), or with `chunk` the two passes of a batched prefill chunk; split partials are combined by the batched / prefill
 // combine.  The plan that ran comes from attention_plan(), the function the launcher itself follows.
 extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc *dp) {

@@ -1,5 +1,5 @@
 // route.hip -- which kernel a projection launch (out = W . act, one weight tensor or a run of them sharing the activation) goes to.
-// ONE router for the decode step (backend.hip), batched prefill and the operator entry points (ops.hip), so that the operator tests
+// ONE router for the decode step (backend_step.hip), batched prefill and the operator entry points (ops.hip), so that the operator tests
 // exercise exactly the launches a step issues.
 //
 //   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more sequences than fit a launch's LDS (at most 8) in groups
@@ -28,8 +28,7 @@ bool route_is_wide(const GemvArgs &a) { const uint32_t rows = route_rows(a); ret
 // the rmsnorm sum-of-squares tree the activation quantizer launch must repeat for this matrix (launch_quant_rows_frag order)
 // (512 threads on the wide matrices -- the order the >= 3-sequence launches of Qwen3-4B have had since round 4; the one- and
 // two-sequence SLAB launches of those matrices run the tree of their own thread count, see kernels.h "what a batch shares")
-uint32_t route_norm_order(const Q80Route &r, const GemvArgs &a) {
-    (void)r;
+uint32_t route_norm_order(const GemvArgs &a) {
     return (q80_canonical(a) && route_is_wide(a) && a.n <= 10240u) ? 512u : 256u;
 }
 
@@ -90,7 +89,6 @@ bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
 }
 
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
-    const uint32_t max_wg = (r.cus ? (uint32_t)r.cus : 256u) * 8u;
     a.cus = (uint32_t)r.cus;
     const RouteKind k = route_kind(r, a);
     if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) {      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
@@ -113,10 +111,10 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
             GemvArgs probe = a; probe.nb = a.nb < 8u ? a.nb : 8u;
             if (gemv_q4k_chunk_takes(probe)) fit = 8u;
         }
-        if (a.nb <= fit) return launch_gemv_q4k(a, max_wg, st);
+        if (a.nb <= fit) return launch_gemv_q4k(a, st);
         for (uint32_t b0 = 0; b0 < a.nb; b0 += fit) {
             GemvArgs s = gemv_slice(a, b0, a.nb - b0 < fit ? a.nb - b0 : fit);
-            const hipError_t e = launch_gemv_q4k(s, max_wg, st);
+            const hipError_t e = launch_gemv_q4k(s, st);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -127,7 +125,7 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
         // quantize every sequence's activation once, straight into MFMA fragment order (unless the producing kernel already did), then
         // the GEMM
         if (!a.frag_ready) {
-            const hipError_t e = launch_quant_rows_frag(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st, route_norm_order(r, a));
+            const hipError_t e = launch_quant_rows_frag(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st, route_norm_order(a));
             if (e != hipSuccess) return e;
         }
         a.xq_in = r.gq; a.xs_in = r.gxs;
@@ -143,7 +141,7 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
         // per sequence, the weights are read once per group.
         for (uint32_t b0 = 0; b0 < a.nb; b0 += 8) {
             GemvArgs s = gemv_slice(a, b0, a.nb - b0 < 8 ? a.nb - b0 : 8u);
-            const hipError_t e = launch_gemv(r.quant, s, max_wg, st);
+            const hipError_t e = launch_gemv(r.quant, s, st);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -153,11 +151,11 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
         const hipError_t e = launch_quant_rows(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st);
         if (e != hipSuccess) return e;
         a.xq_in = r.gq; a.xs_in = r.gxs; a.norm_w = nullptr;
-        return launch_gemv(r.quant, a, max_wg, st);
+        return launch_gemv(r.quant, a, st);
     }
     case ROUTE_GEMV:
     default:
-        return launch_gemv(r.quant, a, max_wg, st);
+        return launch_gemv(r.quant, a, st);
     }
 }
 
