@@ -25,6 +25,9 @@
 //          group products land in an LDS table and one thread per (row, sequence) folds them in order.
 //          (Rows of ONE chunk -- n == 1024, one sequence, the rmsnorm roles: the wave that holds a row's products folds it itself,
 //          wave_fold_canon16 below; no table, no barrier behind the dots.)
+//          (Rows of 2..4 whole chunks -- n == 2048 / 3072 / 4096, one sequence, the residual roles, Wo and W2: the wave of a unit folds its
+//          chunk to two unit sums, wave_fold_canon16_units below; 8 floats per unit in LDS instead of 64 products, and the fold thread of a row
+//          adds 2 x chunks unit sums behind the barrier instead of 16 x chunks products.)
 //   STREAM (classifier: vocab x n_embd).  1024 persistent workgroups; a wave owns 16-row tiles,
 //          tile = wave + k * nwaves, so the chip sweeps memory linearly; four waves per SIMD keep 16 KiB each in
 //          flight while one of them is consuming.  Lane l loads bytes [16l,16l+16) of each row chunk
@@ -302,17 +305,31 @@ __device__ __forceinline__ float wave_fold_canon16(float p) {
     return fadd(s0, s);
 }
 constexpr int WF_LANE0 = 48;          // wave_fold_canon16(): lane WF_LANE0 + r holds row r
+// Its sibling for rows of SEVERAL chunks (SLAB_WFC), one chunk per wave: the same schedule up to the v_permlane32_swap, both unit sums of the
+// chunk returned -- in lanes WF_LANE0 + r, s0 = S_2c and s1 = S_2c+1 of row r.  The fold thread of the row adds the units in ascending order:
+// (S_0 + S_1), then (v + S_2c) + S_2c+1 per later chunk -- fold_row_canon<4 NCH>'s float for every input (tests/test_wave_fold_chunks_order.py).
+__device__ __forceinline__ void wave_fold_canon16_units(float p, float &s0, float &s1) {
+    const float p1 = DPP_F(p, 0x104), p2 = DPP_F(p, 0x108), p3 = DPP_F(p, 0x10C);
+    float s = fadd(p, p1); s = fadd(s, p2); s = fadd(s, p3);
+    const uint32_t sb = __float_as_uint(s);
+    const float c = __uint_as_float(__builtin_amdgcn_permlane16_swap(sb, sb, false, false)[0]);
+    s = fadd(c, p); s = fadd(s, p1); s = fadd(s, p2); s = fadd(s, p3);
+    const uint32_t tb = __float_as_uint(s);
+    s0 = __uint_as_float(__builtin_amdgcn_permlane32_swap(tb, tb, false, false)[0]);
+    s1 = s;
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // SLAB kernel
 // ------------------------------------------------------------------------------------------------------------
 // Hand-off of a launch's results to consumers INSIDE the same launch (the fused kernels below): every result is also stored as an 8-byte
 // {tag, value} granule (ONE write-through store: the data is the flag); SlabHand and the epoch tags: device_common.h.
-template <int ROLE, int GS, int B, int NV, int UPW, int EARLY = 0, int WF = 0>
+template <int ROLE, int GS, int B, int NV, int UPW, int EARLY = 0, int WF = 0, int WFC = 0>
 __global__ __launch_bounds__(1024) void gemv_q80_slab_kernel(const GemvDev a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #define SLAB_EARLY EARLY
 #define SLAB_WF WF
+#define SLAB_WFC WFC
 #define SLAB_A a
 #define SLAB_BID blockIdx.x
 #define SLAB_HAND 0
@@ -334,6 +351,7 @@ __global__ __launch_bounds__(1024) void gemv_q80_slab_kernel(const GemvDev a) {
 #undef SLAB_PART
 #undef SLAB_EARLY
 #undef SLAB_WF
+#undef SLAB_WFC
 }
 
 #if NANO_Q80_GS == 64
@@ -374,7 +392,7 @@ __global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const QkvAttnArg
 // workgroups of the grid and never wait for consumers; a grid of <= one workgroup per CU is resident as a whole.  Same bodies, same bits
 // (test_fused_wo_w13_launch_equals_the_two_launches).  Reference: infer/infer.c:885-944.
 struct Wo13Args { GemvDev wo; GemvDev w13; SlabHand hand; uint32_t wo_wgs, wait16; };   // wait16: naps of 16 x 64 cycles before a non-producer workgroup starts polling
-template <int ROLE_A, int NV_A, int UPW_A, int NV_B, int UPW_B, int NT, int WF = 0>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF
+template <int ROLE_A, int NV_A, int UPW_A, int NV_B, int UPW_B, int NT, int WF = 0, int WFA = 0>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF; WFA: Wo's rows are that many whole chunks: SLAB_WFC
 __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int GS = 64, B = 1;
@@ -392,6 +410,7 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #define SLAB_XHAND 0
 #define SLAB_XHANDV (SlabHand{})
 #define SLAB_CTAG 0u
+#define SLAB_WFC WFA
 #define SLAB_PART 1
 #include "gemv_q80_slab_body.inc"
 #undef SLAB_PART
@@ -400,6 +419,7 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #include "gemv_q80_slab_body.inc"
 #undef SLAB_PART
         };
+#undef SLAB_WFC
 #undef SLAB_A
 #undef SLAB_HAND
 #undef SLAB_HANDV
@@ -662,6 +682,15 @@ static SlabPlan plan_slab(const GemvArgs &a, int B) {
 static bool slab_wave_fold(const GemvDev &d) {
     return d.n == 1024u && d.ng == 16u && !d.early && (d.epi == GEMV_EPI_STORE || (d.epi == GEMV_EPI_SWIGLU && !d.out_pstride[0]));
 }
+// a residual launch (Wo, W2) whose rows are 2..4 WHOLE chunks of group size 64: the chunk count when the in-wave fold of a unit's chunk
+// (SLAB_WFC) takes it, else 0 (the callers add: one sequence, a residual role, a canonical launch).  A LoRA addend or a position-indexed output
+// keeps the table.
+static uint32_t slab_wave_fold_chunks(const GemvDev &d) {
+    if (d.nb != 1u || d.early || d.epi != GEMV_EPI_RESID || d.resid_add || d.out_pstride[0] || d.rows[1] || (d.flags & ~F_COMBINE)) return 0u;
+    if (d.n % 1024u || d.n < 2048u || d.n > 4096u || d.ng * 64u != d.n) return 0u;
+    return d.n / 1024u;
+}
+static size_t slab_unit_table(const GemvDev &d, uint32_t nch) { return (size_t)(d.tpw * 4) * (nch <= 2u ? 4u : 8u) * 4u; }      // [rows of the tiles][unit sums] floats
 template <int ROLE, int GS, int B, int NV, int UPW>
 static hipError_t launch_slab_t(const GemvDev &d, const SlabPlan &p, uint32_t nwg, hipStream_t st) {
     const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
@@ -684,6 +713,19 @@ static hipError_t launch_slab_t(const GemvDev &d, const SlabPlan &p, uint32_t nw
         if (ROLE == R_NORM_SWIGLU) dd.units = (d.rw + 1) / 2;
         hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 1>), dim3(nwg), dim3(64 * p.nw), n16 + ng4 * 4 + 64, st, dd);
         return hipGetLastError();
+    }
+    // rows of 2..4 whole chunks, one sequence, the residual roles (Wo, W2; canonical launches only at this group size: launch_slab_b): every
+    // wave folds the chunk of its unit to two unit sums -- 8 floats per unit in LDS instead of the product table, 2 nch - 1 adds behind the
+    // barrier (gemv_q80_slab_body.inc SLAB_WFC).  (The plans of such matrices have <= 8 units on >= 6 waves: one or two units per wave.)
+    if constexpr (GS == 64 && B == 1 && (ROLE == R_RESID || ROLE == R_RESID_COMBINE) && (NV == 1 || NV == 2) && UPW <= 2) {
+        const uint32_t nch = slab_wave_fold_chunks(d);
+        if (nch) {
+            const size_t lds_c = n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + slab_unit_table(d, nch);
+            if (nch == 2u) hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 2>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
+            else if (nch == 3u) hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 3>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
+            else hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 4>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
+            return hipGetLastError();
+        }
     }
     auto kern = &gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -900,10 +942,14 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     // W1|W3's rows of one chunk (n == 1024): pair units (two rows of W1 and the same two of W3), folded by the wave that holds them
     const bool wf = slab_wave_fold(fa.w13);
     if (wf) fa.w13.units = (fa.w13.rw + 1) / 2;
-    const size_t la = slab_lds(fa.wo), lb = slab_lds(fa.w13, !wf), lds = la > lb ? la : lb;
+    // Wo's rows of two whole chunks (n == 2048, the widest these signatures take): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
+    const bool wfa = slab_wave_fold_chunks(fa.wo) == 2u;
+    const size_t la = slab_lds(fa.wo, !wfa) + (wfa ? slab_unit_table(fa.wo, 2u) : 0), lb = slab_lds(fa.w13, !wf), lds = la > lb ? la : lb;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     const bool comb = (fa.wo.flags & F_COMBINE) != 0;
-#define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { if (wf) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1>), dim3(q.wb), dim3(NT_), lds, st, fa); \
+#define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { if (wf && wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \
+                                                     else if (wf) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1>), dim3(q.wb), dim3(NT_), lds, st, fa); \
+                                                     else if (wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 0, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \
                                                      else hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_>), dim3(q.wb), dim3(NT_), lds, st, fa); return hipGetLastError(); } while (0)
     if (q.sig == 1) { if (comb) WO13_GO(R_RESID_COMBINE, 2, 1, 1, 2, 256); WO13_GO(R_RESID, 2, 1, 1, 2, 256); }
     if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 1, 512);           // (sig 3)

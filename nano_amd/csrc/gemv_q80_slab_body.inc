@@ -21,10 +21,21 @@
 //               launches -- the host selects it): every wave folds the rows of its units itself (wave_fold_canon16, gemv_q80_impl.h) and stores
 //               them; no product table in LDS, no workgroup barrier after the dots, waves end independently.  R_NORM_SWIGLU: a unit is two rows
 //               of W1 plus the same two rows of W3 (the host passes units = ceil(rw / 2)), so the wave has both halves of its SwiGLU pairs
+//   SLAB_WFC   (optional, default 0) a compile-time 0 | 2 | 3 | 4: rows of that many WHOLE chunks (n == 1024 SLAB_WFC, group size 64, one sequence,
+//               the residual roles -- Wo, W2 --, one weight segment, canonical launches -- the host selects it).  Units, loads and fold threads
+//               are the table form's; but every wave folds the chunk of its unit itself to the chunk's two unit sums (wave_fold_canon16_units)
+//               and leaves 8 floats (4 rows x 2 sums) in LDS instead of 64 products: behind the barrier the fold thread of a row reads its
+//               2 SLAB_WFC unit sums (one or two LDS reads) and adds them in ascending order -- 2 SLAB_WFC - 1 adds where the table's fold
+//               has 16 SLAB_WFC - 1 behind 4 SLAB_WFC reads.  (A wave per tile with ALL of its chunks -- no barrier at all -- was built first and
+//               lost: the dots and folds of two or three chunks in ONE wave cost more than the barrier, profiles/wave_fold_chunks.txt.)
 // and has ROLE, GS, B, NV, UPW, smem, in scope.
 #ifndef SLAB_WF
 #define SLAB_WF 0
 #define SLAB_WF_DEFAULTED 1
+#endif
+#ifndef SLAB_WFC
+#define SLAB_WFC 0
+#define SLAB_WFC_DEFAULTED 1
 #endif
 #ifndef SLAB_EARLY
 #define SLAB_EARLY 0
@@ -81,7 +92,11 @@
     const int NW = (int)(SLAB_A.nthr >> 6);
     constexpr bool WF_ = (SLAB_WF) != 0, WFPAIR_ = WF_ && ROLE == R_NORM_SWIGLU;
     static_assert(!WF_ || (GS == 64 && B == 1 && (SLAB_EARLY) == 0 && (ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU)), "SLAB_WF: one-chunk rows of the rmsnorm roles");
-    const uint32_t n = WF_ ? 1024u : SLAB_A.n, ng = WF_ ? 16u : SLAB_A.ng;
+    constexpr int NCH_ = (SLAB_WFC);                                  // SLAB_WFC: chunks of a row
+    constexpr bool WFC_ = NCH_ != 0;
+    constexpr uint32_t UP_ = NCH_ <= 2 ? 4u : 8u;                     // ... floats per row of the unit-sum table (a row's sums: one or two 16-byte reads)
+    static_assert(!WFC_ || (!WF_ && NCH_ >= 2 && NCH_ <= 4 && GS == 64 && B == 1 && (SLAB_EARLY) == 0 && (ROLE == R_RESID || ROLE == R_RESID_COMBINE)), "SLAB_WFC: whole-chunk rows of the residual roles");
+    const uint32_t n = WF_ ? 1024u : WFC_ ? (uint32_t)NCH_ * 1024u : SLAB_A.n, ng = WF_ ? 16u : WFC_ ? (uint32_t)NCH_ * 16u : SLAB_A.ng;
     const uint32_t n16 = (n + 15) & ~15u, ng4 = (ng + 3) & ~3u;
     const uint32_t PITCH = (GC == 16) ? (((ng + 47) / 64) * 64 + 16) : (ng4 + 4);
     const uint32_t RW = SLAB_A.rw, TPW = SLAB_A.tpw, RWP = TPW * TR;         // rows of this workgroup, its four-row tiles, rows of the product table
@@ -91,7 +106,7 @@
     int8_t *xq = reinterpret_cast<int8_t *>(smem);                 // [B][n16]
     float *xs = reinterpret_cast<float *>(smem + B * n16);         // [B][ng4]
     float *red = xs + B * ng4;                                     // [B][16] (+ combine weights [B][n_head][8])
-    float *P = red + B * 16 + (has_flag<ROLE>(SLAB_A, F_COMBINE) ? B * SLAB_A.attn_n_head * 8 : 0);   // [B][nmat][RWP][PITCH]
+    float *P = red + B * 16 + (has_flag<ROLE>(SLAB_A, F_COMBINE) ? B * SLAB_A.attn_n_head * 8 : 0);   // [B][nmat][RWP][PITCH] (SLAB_WFC: unit sums [RWP][UP_])
 
     // every argument the chain below reads late (output slots, strides, positions, the residual addend) is fetched NOW, with
     // the first ones (karg_touch, gemv_common.h)
@@ -244,6 +259,28 @@
             const uint32_t mat = t >= TPW ? 1u : 0u, tl = t - mat * TPW;
             const uint32_t col = (c << 10) + (uint32_t)lane * 16u;
             const uint32_t g = c * GC + (uint32_t)lane / LPG;
+            if constexpr (WFC_) {
+                // the product stays in the lane that formed it (lane 4 g + r: row r, group g of the chunk); the wave folds the chunk to its two
+                // unit sums and lanes WF_LANE0 + r leave them in the row's slots 2 c, 2 c + 1 (rows beyond RW: weights and scales read as 0)
+                const int4 xv = *reinterpret_cast<const int4 *>(xq + col);
+                const float xsc = xs[g];
+                int iv[TR];
+#pragma unroll
+                for (int r = 0; r < TR; r++) {
+                    int d = __builtin_amdgcn_sdot4(wv[k][r].x, xv.x, 0, false);
+                    d = __builtin_amdgcn_sdot4(wv[k][r].y, xv.y, d, false);
+                    d = __builtin_amdgcn_sdot4(wv[k][r].z, xv.z, d, false);
+                    d = __builtin_amdgcn_sdot4(wv[k][r].w, xv.w, d, false);
+                    iv[r] = dpp_group_sum<LPG>(d);
+                }
+                int v = iv[0];
+#pragma unroll
+                for (int q = 1; q < TR; q++) v = (q == (lane & 3)) ? iv[q] : v;
+                float s0_, s1_;
+                wave_fold_canon16_units(((float)v * sv[k][0]) * xsc, s0_, s1_);                                    // infer.c:672
+                if (((uint32_t)lane & ~3u) == (uint32_t)WF_LANE0)
+                    *reinterpret_cast<float2 *>(P + (tl * TR + ((uint32_t)lane & 3u)) * UP_ + 2u * c) = make_float2(s0_, s1_);
+            } else {
 #pragma unroll
             for (int b = 0; b < B; b++) {
                 if (b < (int)SLAB_A.nb) {
@@ -269,6 +306,7 @@
                     }
                 }
             }
+            }   // !SLAB_WFC
         }
     }
     NANO_STAMP(SLAB_A.stamps, 4, wv[UPW - 1][TR - 1].w);                 // this wave's weights arrived, its products are in the table
@@ -305,6 +343,14 @@
         // choice and no ordered chain in their code (round 4 left both folds behind a run-time flag in every kernel: the one-sequence step
         // of Qwen3-0.6B went 1880 -> 1826 tok/s with it, bisected in round 5: profiles/r05_headline_bisect.txt).
         constexpr bool ROLE_CANON = ROLE != R_GENERIC && GS == 64;
+        if constexpr (WFC_) {                                        // the row's unit sums, ascending: ((S_0 + S_1) + S_2) + ...
+            const float4 a_ = *reinterpret_cast<const float4 *>(P + (uint32_t)frl * UP_);
+            float4 b_ = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (NCH_ > 2) b_ = *reinterpret_cast<const float4 *>(P + (uint32_t)frl * UP_ + 4u);
+            v0 = fadd(fadd(fadd(a_.x, a_.y), a_.z), a_.w);
+            if constexpr (NCH_ > 2) v0 = fadd(fadd(v0, b_.x), b_.y);
+            if constexpr (NCH_ > 3) v0 = fadd(fadd(v0, b_.z), b_.w);
+        } else
         if (PFOLD && pfold_) {                                       // units ascending; the first unit is the row's starting value
             const uint32_t nu_ = ng >> 3;
             v0 = p0[0];
@@ -375,6 +421,10 @@
 #ifdef SLAB_WF_DEFAULTED
 #undef SLAB_WF
 #undef SLAB_WF_DEFAULTED
+#endif
+#ifdef SLAB_WFC_DEFAULTED
+#undef SLAB_WFC
+#undef SLAB_WFC_DEFAULTED
 #endif
 #ifdef SLAB_EARLY_DEFAULTED
 #undef SLAB_EARLY
