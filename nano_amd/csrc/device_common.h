@@ -117,6 +117,50 @@ __device__ __forceinline__ int q80_quant1(float x, float scale) {
     return (r != r) ? 0 : (int)r;
 }
 
+// Four values of one group: the integers of q80_quant1, bit for bit, without four IEEE division expansions.  All values of a group
+// divide by the same scale, and only the INTEGER roundf(x / scale) is kept: the quotient's low bits decide it only next to a
+// half-integer.  Fast path: ri = v_rcp_f32(scale) once; per value t = x * ri, a = |t|, f = fract(a); the value is SAFE when
+// |f - 0.5| > delta and a < 128 (both comparisons false for NaN), and its integer is then trunc(t + copysign(0.5, t)) in float32.
+// delta = 2^-14, because for a < 128:
+//   * v_rcp_f32 is good to 1 ulp and the product rounds once: |t - x/scale| <= 128 * 1.5 * 2^-23 < 2^-15;
+//   * the correctly rounded quotient q is within 2^-18 of x/scale, and the float32 add of 0.5 errs by at most 2^-18;
+//   * every half-integer below 128 is a float;
+//   so outside delta t, q and x/scale lie strictly between the same two half-integers (and t + 0.5, rounded, strictly between the
+//   same two integers): roundf(q) is the integer computed from t.
+// Whatever is not safe takes q80_quant1 itself -- one exact division per such VALUE, in one loop over a lane's missed slots that a
+// wave without a miss jumps over (s_cbranch_execz): a near-tie (2.5e-5 of values on wide random data), a zero scale (0 * inf = NaN),
+// a denormal scale whose reciprocal overflows or is flushed (t = inf or NaN), infinities and NaN.  A denormal t is safe and gives 0,
+// as the division does.  tests/test_q80_quant_fast_order.py restates this in float32 against roundf of the float32 quotient.
+__device__ __forceinline__ int4 q80_quant4(const float4 v, const float scale) {
+    constexpr float delta = 0x1p-14f;
+    const float ri = __builtin_amdgcn_rcpf(scale);
+    const float t0 = v.x * ri, t1 = v.y * ri, t2 = v.z * ri, t3 = v.w * ri;
+    int q0 = (int)(t0 + __builtin_copysignf(0.5f, t0)), q1 = (int)(t1 + __builtin_copysignf(0.5f, t1));
+    int q2 = (int)(t2 + __builtin_copysignf(0.5f, t2)), q3 = (int)(t3 + __builtin_copysignf(0.5f, t3));
+    const float a0 = fabsf(t0), a1 = fabsf(t1), a2 = fabsf(t2), a3 = fabsf(t3);
+    const float g0 = fabsf(__builtin_amdgcn_fractf(a0) - 0.5f), g1 = fabsf(__builtin_amdgcn_fractf(a1) - 0.5f);
+    const float g2 = fabsf(__builtin_amdgcn_fractf(a2) - 0.5f), g3 = fabsf(__builtin_amdgcn_fractf(a3) - 0.5f);
+    // "every value of the lane is safe", straight-line: the four tie tests and ONE range test on the largest a (a maximum drops a NaN,
+    // but a NaN a has a NaN g and fails its own tie test; an infinite a fails the range test whatever its fract is)
+    const bool all_safe = (g0 > delta) & (g1 > delta) & (g2 > delta) & (g3 > delta) & (fmaxf(fmaxf(a0, a1), fmaxf(a2, a3)) < 128.0f);
+    if (!all_safe) {                       // rarely entered, never by a wave without a miss
+        bool m0 = !((g0 > delta) & (a0 < 128.0f)), m1 = !((g1 > delta) & (a1 < 128.0f));
+        bool m2 = !((g2 > delta) & (a2 < 128.0f)), m3 = !((g3 > delta) & (a3 < 128.0f));
+        while (m0 | m1 | m2 | m3) {        // the lane's first missed slot, exactly
+            const float x = m0 ? v.x : m1 ? v.y : m2 ? v.z : v.w;
+            const int e = q80_quant1(x, scale);
+            if (m0) { q0 = e; m0 = false; } else if (m1) { q1 = e; m1 = false; } else if (m2) { q2 = e; m2 = false; } else { q3 = e; m3 = false; }
+        }
+    }
+    return make_int4(q0, q1, q2, q3);
+}
+// the low bytes of four integers in one word: three v_perm_b32
+__device__ __forceinline__ uint32_t q80_pack4(const int4 q) {
+    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)q.y, (uint32_t)q.x, 0x0c0c0400u);      // bytes: q.x, q.y, 0, 0
+    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)q.w, (uint32_t)q.z, 0x04000c0cu);      // bytes: 0, 0, q.z, q.w
+    return lo | hi;
+}
+
 // ---- Q4K helpers (reference infer/tensor.c:4-9,113-141) -------------------------------------------
 __device__ __forceinline__ int nearest_int_magic(float v) {
     float t = v + 12582912.f;

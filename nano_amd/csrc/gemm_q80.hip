@@ -46,9 +46,7 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const float *x, uint32_
         float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
         m = dpp_group_max<GS / 4>(m);
         const float scale = div_const<127>(m);
-        const int q0 = q80_quant1(v.x, scale), q1 = q80_quant1(v.y, scale), q2 = q80_quant1(v.z, scale), q3 = q80_quant1(v.w, scale);
-        *reinterpret_cast<uint32_t *>(xq + (size_t)t * n16 + i) =
-            (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
+        *reinterpret_cast<uint32_t *>(xq + (size_t)t * n16 + i) = q80_pack4(q80_quant4(v, scale));
         if ((tid % (GS / 4)) == 0) xs[(size_t)t * ng + i / GS] = scale;
     }
 }
@@ -395,12 +393,10 @@ __global__ __launch_bounds__(256) void quant_rows_frag_kernel(const float *x, ui
     mx = dpp_group_max<GS / 4>(mx);                       // n % GS == 0 and 1024 % GS == 0: groups are whole
     if (!live) return;
     const float scale = div_const<127>(mx);
-    const int q0 = q80_quant1(v.x, scale), q1 = q80_quant1(v.y, scale), q2 = q80_quant1(v.z, scale), q3 = q80_quant1(v.w, scale);
     const uint32_t g = i / GS, j = i % GS;                                  // byte j of group g
     const uint32_t ks = GS >= 64 ? j / 64u : 0u, jj = GS >= 64 ? j % 64u : j, kq = jj / KB, b = jj % KB;
     const size_t dst = ((size_t)(tt * ng + g) * FR + ks) * FB + (size_t)(kq * 16u + nn) * KB + b;
-    *reinterpret_cast<uint32_t *>(xf + dst) =
-        (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
+    *reinterpret_cast<uint32_t *>(xf + dst) = q80_pack4(q80_quant4(v, scale));
     if ((tid % (GS / 4)) == 0) xsf[(size_t)(tt * ng + g) * 16u + nn] = scale;
 }
 

@@ -49,8 +49,7 @@ namespace {
 
 
 __device__ __forceinline__ void quant_store4(float4 v, float scale, int8_t *dst) {
-    const int q0 = q80_quant1(v.x, scale), q1 = q80_quant1(v.y, scale), q2 = q80_quant1(v.z, scale), q3 = q80_quant1(v.w, scale);
-    *reinterpret_cast<uint32_t *>(dst) = (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
+    *reinterpret_cast<uint32_t *>(dst) = q80_pack4(q80_quant4(v, scale));
 }
 
 template <int ROLE, int GS, int B, int NV>

@@ -172,8 +172,7 @@ __global__ __launch_bounds__(256) void quantize_q80_kernel(const float *x, uint3
         m = group_max(m, tpg);
         const float scale = div_const<127>(m);
         if (act) {
-            q[i] = (int8_t)q80_quant1(v.x, scale); q[i + 1] = (int8_t)q80_quant1(v.y, scale);
-            q[i + 2] = (int8_t)q80_quant1(v.z, scale); q[i + 3] = (int8_t)q80_quant1(v.w, scale);
+            *reinterpret_cast<uint32_t *>(q + i) = q80_pack4(q80_quant4(v, scale));         // (i % 4 == 0, q from hipMalloc: aligned)
             if ((tid % tpg) == 0) s[i / (int)gs] = scale;
         }
     }
