@@ -157,10 +157,15 @@ int nano_hip_decode_greedy(NanoHipModel *m, const uint32_t *tokens, const uint32
                            uint32_t steps, uint32_t *out_ids);
 
 /* Batched prefill: feed `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot`, up
- * to 64 (Q80) / 8 tokens per weight read instead of one forward per token; no logits are produced (the reference
+ * to nano_hip_prefill_chunk_tokens() tokens per weight read instead of one forward per token; no logits are produced (the reference
  * computes and discards them for prompt positions, infer.c:1146-1149, 1258-1260).  KV rows and all later outputs equal
  * those of `count` nano_hip_forward() calls.  Replaces the prompt loop around llm_forward (infer.c:1258-1260). */
 int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count);
+/* Prompt tokens nano_hip_prefill() feeds per weight read in the model's current mode -- what a caller sizing prompt pieces needs:
+ * 64 for Q80 and for a Q4K model whose seven per-layer projections all go to the int8 MFMA GEMM (whole 256-value blocks, row counts in
+ * multiples of 16; NANO_MFMA_MIN_NB <= 64), 8 for every other Q4K model and for FP32, 1 in strict or exact mode (one reference-order
+ * forward per token), 0 for a null model. */
+uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m);
 
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words

@@ -61,7 +61,7 @@ F32_ROLES = ("generic", "norm_store", "resid", "resid_combine", "norm_swiglu")
 
 
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
-ROUTE_NAMES = ("gemv", "gemv_preq", "gemv_sliced", "q4k", "reserved", "frag_g6", "frag_old", "frag_g7")
+ROUTE_NAMES = ("gemv", "gemv_preq", "gemv_sliced", "q4k", "reserved", "frag_g6", "frag_old", "frag_g7", "q4k_gemm")
 
 
 class NanoHipError(RuntimeError):
@@ -101,6 +101,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_forward", C.c_int, [vp, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp])
     fn("nano_hip_decode_greedy", C.c_int, [vp, u32p, u32p, C.c_uint32, C.c_uint32, vp])
     fn("nano_hip_prefill", C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32])
+    fn("nano_hip_prefill_chunk_tokens", C.c_uint32, [vp])
     fn("nano_hip_lora_attach", C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t])
     fn("nano_hip_lora_enable", C.c_int, [vp, C.c_int])
     fn("nano_hip_forward_sample", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
@@ -267,6 +268,10 @@ class DeviceModel:
         """Batched prefill of one sequence: tokens at positions pos0.. (no logits)."""
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         check(lib().nano_hip_prefill(self.h, slot, t, pos0, t.size))
+
+    def prefill_chunk_tokens(self) -> int:
+        """Prompt tokens prefill() feeds per weight read in the model's current mode (64 | 8; strict / exact mode: 1)."""
+        return int(lib().nano_hip_prefill_chunk_tokens(self.h))
 
     def forward_sample(self, token: int, pos: int, history: Sequence[int], repetition_penalty: float, temperature: float,
                        top_p: float, coin: float) -> NanoHipSample:

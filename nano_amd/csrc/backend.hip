@@ -227,8 +227,23 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
 
     // ---- state ---------------------------------------------------------------------------------------
     const size_t B = max_batch;
-    // per-token scratch also serves batched prefill: up to 64 (Q80: int8 MFMA GEMM) / 8 prompt tokens per pass
-    const size_t PF = d.quant_type == NANO_QUANT_Q80 ? 64 : 8;
+    if (const char *mm = getenv("NANO_MFMA_MIN_NB")) { const uint32_t v = (uint32_t)strtoul(mm, nullptr, 0); if (v >= 2) m->mfma_min_nb = v; }
+    // per-token scratch also serves batched prefill: up to 64 (Q80, and Q4K where gemm_q4k.hip takes all seven per-layer projections:
+    // int8 MFMA GEMMs) / 8 prompt tokens per pass.  Decided here, once, from the shapes and mfma_min_nb.
+    m->pf_chunk = d.quant_type == NANO_QUANT_Q80 ? 64u : 8u;
+    if (d.quant_type == NANO_QUANT_Q4K && m->mfma_min_nb <= 64u) {
+        auto takes = [&](uint32_t n, uint32_t epi, uint32_t r0, uint32_t r1, uint32_t r2) {
+            GemvArgs a{};
+            a.n = n; a.nb = 64; a.epi = epi; a.cus = (uint32_t)m->cus;
+            const uint32_t rows[3] = { r0, r1, r2 };
+            for (uint32_t s = 0; s < 3 && rows[s]; s++) { a.seg[s].rows = rows[s]; a.nseg = s + 1; }
+            if (epi != GEMV_EPI_RESID) a.norm_w = m->rms_attn;                  // (a flag here: q | k | v and W1|W3 normalise in their prologue)
+            return gemm_q4k_supports(a);
+        };
+        if (takes((uint32_t)E, GEMV_EPI_STORE, QD, KD, KD) && takes(QD, GEMV_EPI_RESID, (uint32_t)E, 0, 0) &&
+            takes((uint32_t)E, GEMV_EPI_SWIGLU, (uint32_t)H, (uint32_t)H, 0) && takes((uint32_t)H, GEMV_EPI_RESID, (uint32_t)E, 0, 0)) m->pf_chunk = 64u;
+    }
+    const size_t PF = m->pf_chunk;
     const size_t Bs = B > PF ? B : PF;
     m->Bs = (uint32_t)Bs;
     size_t kvn = B * L * max_seq_len * KD;
@@ -267,7 +282,8 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     }
     if (ok && Bs > 1 && d.quant_type == NANO_QUANT_Q4K) {
         size_t nmax = E > QD ? E : QD; if (H > nmax) nmax = H;
-        m->q4x_bytes = 8 * ((nmax + 255) & ~(size_t)255);                 // 32 bytes per 32-value group, up to 8 sequences per launch
+        // 32 bytes per 32-value group: up to 8 sequences per chunk launch, up to 64 per GEMM launch (gemm_q4k.hip)
+        m->q4x_bytes = (Bs > 8 ? (Bs < 64 ? Bs : (size_t)64) : (size_t)8) * ((nmax + 255) & ~(size_t)255);
         ok = hipMalloc(&m->q4x, m->q4x_bytes) == hipSuccess;
     }
     if (ok && m->kv.paged) {
@@ -296,7 +312,6 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
         hipEventCreate(&m->ev1) != hipSuccess || hipEventCreate(&m->ev2) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ERUNTIME, "stream/event creation failed"); }
     if (getenv("NANO_HIP_NO_GRAPH")) m->use_graph = false;
     if (const char *nt = getenv("NANO_KV_COPY_NT")) m->kv.copy_nt = *nt && *nt != '0';
-    if (const char *mm = getenv("NANO_MFMA_MIN_NB")) { const uint32_t v = (uint32_t)strtoul(mm, nullptr, 0); if (v >= 2) m->mfma_min_nb = v; }
     // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch (higher bits are ignored).
     // Default 3; 0 = the five launches per layer; same bits in every setting
     if (const char *fz = getenv("NANO_FUSE_LAUNCHES")) { const uint32_t v = (uint32_t)strtoul(fz, nullptr, 0); m->ho.fuse_qkv_attn = (v & 1u) != 0; m->ho.fuse_wo_w13 = (v & 2u) != 0; }
@@ -362,7 +377,7 @@ extern "C" int nano_hip_sync(NanoHipModel *m) {
 
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps) {
     if (!m || !tokens || !pos) FAIL(NANO_HIP_EINVAL, "null argument");
-    const uint32_t cap = NANO_MAX_BATCH;               // > 8 sequences: Q80 through the int8 MFMA GEMMs, FP32 / Q4K through their GEMV kernels in groups
+    const uint32_t cap = NANO_MAX_BATCH;               // > 8 sequences: Q80 and Q4K through their int8 MFMA GEMMs, FP32 (and Q4K shapes the GEMM refuses) through the GEMV kernels in groups
     if (batch == 0 || batch > m->maxB || batch > cap) FAIL(NANO_HIP_EINVAL, "batch %u out of range (max %u, kernel capacity %u)", batch, m->maxB, cap);
     for (uint32_t i = 0; i < batch; i++) {
         if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
@@ -447,7 +462,7 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     return 0;
 }
 // Batched prefill: feeds `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot` in
-// passes of up to 64 (Q80, int8 MFMA GEMM) / 8 tokens per weight read instead of one decode step per token; no
+// passes of up to 64 (Q80 and Q4K through their int8 MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
 // logits (the reference computes and discards them for prompt positions, infer.c:1146-1149).  The KV rows and every
 // later logit are the ones token-by-token feeding produces, bit for bit (same kernels and the same attention split per token).
 extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count) {
@@ -473,7 +488,7 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         }
         return 0;
     }
-    const uint32_t chunk_max = m->d.quant_type == NANO_QUANT_Q80 ? 64u : 8u;
+    const uint32_t chunk_max = m->pf_chunk;
     // the whole prompt's tokens and positions go to the device ONCE; a chunk takes its share by device-to-device copies on the stream, the host waits only at the end
     if (count > m->pf_cap) {
         if (m->pf_stage) { HIP_TRY(hipStreamSynchronize(m->st)); (void)hipFree(m->pf_stage); m->pf_stage = nullptr; m->pf_cap = 0; }
@@ -534,6 +549,10 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
     }
     HIP_TRY(hipStreamSynchronize(m->st));
     return dev_err_check(m);
+}
+extern "C" uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m) {
+    if (!m) return 0u;
+    return (strict_serves(m) || exact_serves(m)) ? 1u : m->pf_chunk;
 }
 // one pass of the greedy loop: queued, waited for, the ids handed over
 static int decode_greedy_once(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t steps, uint32_t *out_ids) {

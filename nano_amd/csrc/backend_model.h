@@ -76,7 +76,8 @@ struct NanoHipModel {
     const float *lora_t[8] = {nullptr};                   // qa qb ka kb va vb oa ob, each [L][...]
     uint32_t lora_rank = 0, lora_alpha = 0; bool lora_on = false;
     int8_t *gq = nullptr; float *gxs = nullptr;           // MFMA GEMM path (batch > 8, Q80): quantized activations of all sequences
-    uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 8 sequences: the staged activation groups (gemv_q4k_chunk.hip)
+    uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 64 sequences: the staged activation groups (gemv_q4k_chunk.hip, gemm_q4k.hip)
+    uint32_t pf_chunk = 8;                                // prompt tokens per weight read of batched prefill: 64 (Q80; Q4K whose per-layer projections the MFMA GEMM takes) | 8
     float *rope_cur = nullptr;                            // RoPE rows of the current positions [B][2][hd/2], staged by the embed kernel
     float *kcache = nullptr, *vcache = nullptr;
     uint32_t *tokens = nullptr, *pos = nullptr, *amax = nullptr, *trace = nullptr, *pos0 = nullptr;
@@ -91,7 +92,7 @@ struct NanoHipModel {
     std::vector<uint64_t> pf_graph_keys;                  // prefill-chunk graphs in creation order (bounded: PF_GRAPH_CAP)
     uint64_t weight_bytes_per_step = 0;
     bool use_graph = true;
-    uint32_t mfma_min_nb = 9;                             // sequences per step from which Q80 GEMVs go to the MFMA GEMM (NANO_MFMA_MIN_NB: measurement)
+    uint32_t mfma_min_nb = 9;                             // sequences per step from which Q80 and Q4K projections go to their MFMA GEMMs (NANO_MFMA_MIN_NB: measurement; 65 = never)
     // the in-launch hand-offs of the fused one-sequence launches
     struct Handoff {
         bool fuse_qkv_attn = true;                        // one sequence, Q80 gs 64, Qwen3 head_dim 128: q|k|v projection + attention in one launch; NANO_FUSE_LAUNCHES bit 0

@@ -254,21 +254,35 @@ uint32_t gemv_q4k_chunk_partials(const GemvArgs &a) {
     return p.grid;
 }
 
-// 2 .. 8 sequences: the quantizer launch (one workgroup per sequence, the one-sequence launch's prologue), then the projection
+// The quantizer launch of a several-sequence projection (2 .. 8 sequences: the chunk kernel below; 9 .. 64: gemm_q4k.hip): one workgroup
+// per sequence running the prologue of the one-sequence chunk launch of the same matrix, the staged groups of sequence b left at
+// a.q4_scratch + b * n bytes.  _supports: that one-sequence launch is a chunk launch (its plan gives the quantizer its thread count).
+bool q4k_quant_rows_supports(const GemvArgs &a) {
+    ChunkPlan p1;
+    GemvArgs one = a; one.nb = 1; one.tile_max = nullptr;
+    return a.nb >= 1 && a.nb <= NANO_MAX_BATCH && !a.x4_in && !a.xq_in && plan_chunk(one, p1);
+}
+hipError_t launch_q4k_quant_rows(const GemvArgs &a, hipStream_t st) {
+    ChunkPlan p1;
+    GemvArgs one = a; one.nb = 1; one.tile_max = nullptr;
+    if (!q4k_quant_rows_supports(a) || !plan_chunk(one, p1)) return hipErrorInvalidValue;
+    if (!a.q4_scratch || (size_t)a.nb * (a.n >> 5) * sizeof(XGroup) > a.q4_scratch_bytes) return hipErrorInvalidValue;
+    const uint32_t bpl = a.n >> 8, GT = bpl * 8u;
+    GemvDev q = to_dev(a);                                           // flags: norm / combine as the launch asks
+    q.nthr = p1.nthr; q.tile_max = nullptr;
+    const size_t lds = (size_t)GT * sizeof(XGroup) + (16 + (a.attn_part ? (size_t)a.attn_n_head * 8 : 0)) * 4 + 16;
+    XGroup *xg = reinterpret_cast<XGroup *>(a.q4_scratch);
+    return p1.nv <= 1 ? launch_quant_rows_r<1>(q, xg, a.nb, lds, st) : p1.nv <= 2 ? launch_quant_rows_r<2>(q, xg, a.nb, lds, st) : launch_quant_rows_r<4>(q, xg, a.nb, lds, st);
+}
+
+// 2 .. 8 sequences: the quantizer launch, then the projection
 static hipError_t launch_gemv_q4k_chunk_batched(GemvArgs &a, hipStream_t st) {
     if (!gemv_q4k_chunk_supports(a)) return hipErrorInvalidValue;
-    ChunkPlan p1, p;
-    GemvArgs one = a; one.nb = 1;
-    if (!plan_chunk(one, p1) || !plan_chunk(a, p)) return hipErrorInvalidValue;
-    const uint32_t bpl = a.n >> 8, GT = bpl * 8u;
+    ChunkPlan p;
+    if (!plan_chunk(a, p)) return hipErrorInvalidValue;
+    const uint32_t bpl = a.n >> 8;
     XGroup *xg = reinterpret_cast<XGroup *>(a.q4_scratch);
-    {
-        GemvDev q = to_dev(a);                                       // flags: norm / combine as the launch asks
-        q.nthr = p1.nthr; q.tile_max = nullptr;
-        const size_t lds = (size_t)GT * sizeof(XGroup) + (16 + (a.attn_part ? (size_t)a.attn_n_head * 8 : 0)) * 4 + 16;
-        const hipError_t e = p1.nv <= 1 ? launch_quant_rows_r<1>(q, xg, a.nb, lds, st) : p1.nv <= 2 ? launch_quant_rows_r<2>(q, xg, a.nb, lds, st) : launch_quant_rows_r<4>(q, xg, a.nb, lds, st);
-        if (e != hipSuccess) return e;
-    }
+    { const hipError_t e = launch_q4k_quant_rows(a, st); if (e != hipSuccess) return e; }
     GemvArgs g = a;
     g.norm_w = nullptr; g.attn_part = nullptr; g.attn_ml = nullptr; g.tile_max = nullptr;
     GemvDev d = to_dev(g);

@@ -39,7 +39,7 @@ struct GemvArgs {
     const int8_t *xq_in;    // Q80 int8[n] (batched GEMM path with frag_ready: all tokens, MFMA B-fragment order)
     const float *xs_in;     // Q80 float[n/gs]
     const uint8_t *x4_in;   // Q4K blocks[ceil(n/256)*160]
-    uint8_t *q4_scratch; size_t q4_scratch_bytes;   // Q4K, 2 .. 8 sequences: room for the staged groups of every sequence (nb * n bytes), or nullptr
+    uint8_t *q4_scratch; size_t q4_scratch_bytes;   // Q4K, 2 .. 64 sequences: room for the staged groups of every sequence (nb * n bytes), or nullptr
     // input = combination of split attention partials (attn.hip) instead of xin:
     //   x[b][i] = sum_s part[b][s][i] * w[b][head(i)][s],  w from the (max, sum) pairs in attn_ml
     const float *attn_part; // [nb][nsplit][n] unnormalised partial outputs, or nullptr
@@ -84,6 +84,12 @@ bool gemv_q4k_chunk_loops(const GemvArgs &a);               // ... and the launc
 uint32_t gemv_q4k_chunk_partials(const GemvArgs &a);
 hipError_t launch_gemv_q4k_chunk(GemvArgs &a, hipStream_t st);
 uint32_t gemv_q4k_fit_batch(const GemvArgs &a);            // sequences per Q4K launch that fit in LDS (8 | 4 | 2 | 1)
+// Q4K, 9..64 tokens per weight read on the int8 matrix cores (gemm_q4k.hip): the quantizer launch of the several-sequence chunk launches
+// (one workgroup per token, a.q4_scratch = nb * n bytes) + one MFMA per (group, token tile), the reference's float order -- bit for bit
+// the chunk GEMV's results.  Takes: whole blocks (n % 256 == 0, n <= 16384), segment rows in multiples of 16, no LoRA addend, no
+// caller-quantized activation, no arg-max partials; split-attention partials where the one-sequence chunk launch takes them.
+bool gemm_q4k_supports(const GemvArgs &a);                  // host predicate (shapes and features; the scratch is the router's question)
+hipError_t launch_gemm_q4k(const GemvArgs &a, hipStream_t st);
 hipError_t launch_gemv_q80(const GemvArgs &a, hipStream_t st);      // gemv_q80.hip
 hipError_t launch_gemv_f32(const GemvArgs &a, hipStream_t st);      // gemv_f32.hip
 // the gemv_f32_slab_kernel<ROLE, B, NV, UPW> launch_gemv_f32() runs for `a` (nb <= 8), its waves, workgroups and LDS bytes; the launcher
@@ -126,14 +132,15 @@ enum RouteKind : uint32_t {
     ROUTE_FRAG_G6,         // fragment-order activations (quantizer launch unless frag_ready) + G6 MODE F
     ROUTE_FRAG_OLD,        // fragment-order activations + GC (the classifier) | G2 (the reference's group order)
     ROUTE_FRAG_G7,         // fragment-order activations + G7 (17..64 tokens, the fast path)
+    ROUTE_Q4K_GEMM,        // Q4K, 9..64 tokens: the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip)
 };
 inline bool route_takes_fragments(RouteKind k) { return k == ROUTE_FRAG_G6 || k == ROUTE_FRAG_OLD || k == ROUTE_FRAG_G7; }
-inline bool route_takes_attn_parts(RouteKind k) { return k == ROUTE_GEMV || k == ROUTE_Q4K; }
+inline bool route_takes_attn_parts(RouteKind k) { return k == ROUTE_GEMV || k == ROUTE_Q4K || k == ROUTE_Q4K_GEMM; }     // (Q4K GEMM: its quantizer launch combines)
 struct Q80Route {
     uint32_t quant; int cus;
-    uint32_t mfma_min_nb;  // sequences from which the small Q80 matrices take the batched route (9; NANO_MFMA_MIN_NB)
+    uint32_t mfma_min_nb;  // sequences from which the small Q80 matrices and every Q4K matrix take the batched (MFMA GEMM) route (9; NANO_MFMA_MIN_NB)
     int8_t *gq; float *gxs;  // fragment-order activation scratch (nullptr: no batched route)
-    uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of 2 .. 8 sequences (gemv_q4k_chunk.hip), or nullptr
+    uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of a launch's sequences (n bytes each: 2 .. 8 gemv_q4k_chunk.hip, 9 .. 64 gemm_q4k.hip), or nullptr
 };
 RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
 // FP32: the slices route_projection() cuts a launch of a.nb sequences into -- per = sequences of every slice but the last, launches = their

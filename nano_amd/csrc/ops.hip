@@ -209,7 +209,7 @@ static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     if (d.quant == NANO_QUANT_Q80 && (!(d.gs == 32 || d.gs == 64 || d.gs == 128 || d.gs == 256) || d.n % d.gs || d.n % 16)) return "bad n / group size";
     for (uint32_t s = 0; s < d.nseg; s++) if (!d.rows[s]) return "missing weight tensor";
     if (d.kind == 2 && d.rows[0] != d.rows[1]) return "W1 / W3 row counts differ";
-    if (d.attn_part && (!d.attn_nsplit || d.attn_nsplit > 8 || !d.attn_n_head || d.attn_n_head * d.attn_hd != d.n || d.kind != 1 || d.nb > 8)) return "bad attention partials";
+    if (d.attn_part && (!d.attn_nsplit || d.attn_nsplit > 8 || !d.attn_n_head || d.attn_n_head * d.attn_hd != d.n || d.kind != 1 || (d.nb > 8 && d.quant != NANO_QUANT_Q4K))) return "bad attention partials";
     return nullptr;
 }
 
@@ -301,8 +301,8 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         r.gq = B.alloc<int8_t>(tt * 16 * n16); r.gxs = B.alloc<float>(tt * 16 * (d.n / d.gs));
         OP_CHECK(r.gq && r.gxs, "device alloc failed");
     }
-    if (d.quant == NANO_QUANT_Q4K && d.nb > 1) {                       // the several-sequence chunk launch's staged groups
-        r.q4x_bytes = (size_t)8 * ((d.n + 255) & ~(size_t)255);
+    if (d.quant == NANO_QUANT_Q4K && d.nb > 1) {                       // the staged groups of a several-sequence chunk launch (<= 8) or of the GEMM's tokens
+        r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);
         r.q4x = B.alloc<uint8_t>(r.q4x_bytes);
         OP_CHECK(r.q4x, "device alloc failed");
     }

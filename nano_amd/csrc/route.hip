@@ -3,6 +3,7 @@
 // exercise exactly the launches a step issues.
 //
 //   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more sequences than fit a launch's LDS (at most 8) in groups
+//   Q4K, 9..64 sequences    the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip) where it takes the launch: same bits
 //   Q80, fast path          SLAB GEMV (1..8 sequences on the small per-layer matrices; 1..2 on those of >= 8 M weights)   gemv_q80_impl.h
 //                           G6 (fragment-order activations: MODE S staged in LDS, MODE F per item; 2..64 tokens) gemm_q80_g6.hip
 //                           G7 (17..64 tokens: loader / consumer engine, both operands through LDS) gemm_q80_g7.hip
@@ -33,7 +34,12 @@ uint32_t route_norm_order(const GemvArgs &a) {
 }
 
 RouteKind route_kind(const Q80Route &r, const GemvArgs &a) {
-    if (r.quant == NANO_QUANT_Q4K) return ROUTE_Q4K;
+    if (r.quant == NANO_QUANT_Q4K) {
+        // from mfma_min_nb sequences on (9; NANO_MFMA_MIN_NB=65 restores the slices of 8: the A/B switch Q80 has) every weight byte is read
+        // once per launch; what the GEMM refuses (gemm_q4k_supports()) keeps the slices
+        if (a.nb >= r.mfma_min_nb && r.q4x && (uint64_t)a.nb * a.n <= r.q4x_bytes && gemm_q4k_supports(a)) return ROUTE_Q4K_GEMM;
+        return ROUTE_Q4K;
+    }
     if (r.quant != NANO_QUANT_Q80) return a.nb > 8 ? ROUTE_GEMV_SLICED : ROUTE_GEMV;
     const bool scratch = r.gq && r.gxs;
     const bool canon = q80_canonical(a);
@@ -119,6 +125,9 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
         }
         return hipSuccess;
     }
+    case ROUTE_Q4K_GEMM:
+        a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
+        return launch_gemm_q4k(a, st);
     case ROUTE_FRAG_G6:
     case ROUTE_FRAG_G7:
     case ROUTE_FRAG_OLD: {
