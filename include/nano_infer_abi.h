@@ -225,6 +225,12 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
  * its slot 0 and forks it into the other slots of its share (nano_hip_kv_fork, nano_mi355x.h: a copy, or shared pages on a paged
  * cache).  Applies the context's LoRA selection as nano_forward_batch does.  Returns 0 or a NANO_HIP_E* code. */
 int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch);
+/* Feed ids[0..n_ids-1) into sequence 0 from position 0 and score ids[1..n_ids): logprobs / argmax hold n_ids-1 entries (either may be NULL),
+ * *nll_sum = -(sum of the logprobs), added in double in index order.  Applies the context's LoRA selection as nano_forward_batch does.
+ * logprobs[i] = log p(ids[i + 1] | ids[0..i]) and argmax[i] = the model's own choice there, both taken on the device from a batched
+ * prefill whose logits never reach the host (nano_hip_prefill_score, nano_mi355x.h); perplexity = exp(nll_sum / (n_ids - 1)).
+ * Uses the context's own device, not its replicas; n_ids < 2 scores nothing and returns 0.  Returns 0 or a NANO_HIP_E* code. */
+int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum);
 /* Replicas of the context's model on the listed further GPUs of the node, in this process: nano_forward_batch then serves
  * sequence i from replica i mod (1 + n_devices) (replica 0 = the context's own device) and the replicas decode their
  * shares concurrently -- independent sequences shard trivially, no collective.  The one-process-per-GPU

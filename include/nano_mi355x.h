@@ -167,6 +167,35 @@ int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uin
  * forward per token), 0 for a null model. */
 uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m);
 
+/* ---- scoring prefill: the log-probability of given tokens, from batched prefill -------------------------------
+ * What the model thought of one fed position, reduced on the device from that position's V logits (score.hip):
+ * the logits never leave the device.  The reduction shape depends on V only, so a position's six words are the same
+ * bits however the prompt was cut into calls and chunks.  -inf logits add 0 to the sum and count in `rank` like any
+ * float; a -inf target has logprob -inf.  Rows with NaN or +inf, and rows of -inf only, are unspecified. */
+typedef struct NanoHipTokenScore {
+    float    logprob;       /* target_logit - lse, that one float32 subtraction */
+    float    target_logit;  /* logits[target], the stored float */
+    float    max_logit;     /* the row's maximum, the stored float */
+    float    lse;           /* max_logit + logf(sum_j expf(logits[j] - max_logit)) */
+    uint32_t argmax;        /* first maximum, strict '>' in index order: what nano_hip_forward's argmax_out holds */
+    uint32_t rank;          /* #{j : l_j > l_t} + #{j < t : l_j == l_t}; 0 exactly when target == argmax */
+} NanoHipTokenScore;        /* 24 bytes */
+/* Everything nano_hip_prefill(m, slot, tokens, pos0, count) does -- same chunking, same KV rows, same later outputs, bit for
+ * bit -- and out[i] = the logits produced by feeding tokens[i] at pos0 + i, scored for targets[i] (targets == NULL: for
+ * each row's own arg-max, so rank is 0).  Perplexity of ids[0..n): tokens = ids, targets = ids + 1, count = n - 1.
+ * A chunk runs the classifier over all its rows into a buffer of chunk x V floats (allocated on the first scoring call;
+ * NANO_HIP_ENOMEM leaves the model usable) and the statistics kernel behind it; the scores come back in one copy behind
+ * the call's final wait.  Strict and exact mode feed token by token as nano_hip_prefill does there: each token is a
+ * reference-order step with logits, so the selections are the reference's bits.  LoRA, FP16 rows and the paged cache as
+ * in nano_hip_prefill.  NANO_HIP_EINVAL before anything is queued (a refused call feeds nothing): null m / tokens / out,
+ * slot or position range, a token or target >= vocab.  count == 0 returns 0 and touches nothing. */
+int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
+                           const uint32_t *targets, NanoHipTokenScore *out);
+/* The statistics kernel alone on caller logits [rows][V] (host pointers; targets may be NULL); NANO_HIP_EINVAL: a null
+ * logits / out pointer, rows or V of 0, a target >= V. */
+int nano_hip_op_score_rows(int device, const float *logits, uint32_t rows, uint32_t V,
+                           const uint32_t *targets, NanoHipTokenScore *out);
+
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words
  * 6 / 7.  Attaching enables the module; nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.

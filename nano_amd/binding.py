@@ -68,6 +68,17 @@ class NanoHipError(RuntimeError):
     pass
 
 
+class NanoHipTokenScore(C.Structure):
+    """include/nano_mi355x.h NanoHipTokenScore: what the model thought of one fed position, for one target token (24 bytes)."""
+    _fields_ = [("logprob", C.c_float), ("target_logit", C.c_float), ("max_logit", C.c_float), ("lse", C.c_float),
+                ("argmax", C.c_uint32), ("rank", C.c_uint32)]
+
+
+# the same record as a numpy structured dtype: prefill_score() / op_score_rows() return arrays of it
+TOKEN_SCORE_DTYPE = np.dtype([("logprob", "<f4"), ("target_logit", "<f4"), ("max_logit", "<f4"), ("lse", "<f4"), ("argmax", "<u4"), ("rank", "<u4")])
+assert TOKEN_SCORE_DTYPE.itemsize == C.sizeof(NanoHipTokenScore)
+
+
 PHASE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)        # nano_hip_phase_fn(env, layer, phase)
 
 
@@ -102,6 +113,8 @@ def lib() -> C.CDLL:
     fn("nano_hip_decode_greedy", C.c_int, [vp, u32p, u32p, C.c_uint32, C.c_uint32, vp])
     fn("nano_hip_prefill", C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32])
     fn("nano_hip_prefill_chunk_tokens", C.c_uint32, [vp])
+    fn("nano_hip_prefill_score", C.c_int, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp])
+    fn("nano_hip_op_score_rows", C.c_int, [C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp])
     fn("nano_hip_lora_attach", C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t])
     fn("nano_hip_lora_enable", C.c_int, [vp, C.c_int])
     fn("nano_hip_forward_sample", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
@@ -268,6 +281,18 @@ class DeviceModel:
         """Batched prefill of one sequence: tokens at positions pos0.. (no logits)."""
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         check(lib().nano_hip_prefill(self.h, slot, t, pos0, t.size))
+
+    def prefill_score(self, tokens: Sequence[int], targets: Optional[Sequence[int]] = None, pos0: int = 0, slot: int = 0) -> np.ndarray:
+        """prefill() that also scores every fed position on the device (nano_hip_prefill_score): entry i of the returned
+        TOKEN_SCORE_DTYPE array describes the logits of tokens[i] at pos0 + i for targets[i] (None: for that row's own arg-max).
+        Perplexity of ids: prefill_score(ids[:-1], ids[1:])."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        if g is not None and g.size != t.size:
+            raise ValueError(f"{t.size} tokens but {g.size} targets")
+        out = np.zeros(t.size, TOKEN_SCORE_DTYPE)
+        check(lib().nano_hip_prefill_score(self.h, slot, t.ctypes.data, pos0, t.size, None if g is None else g.ctypes.data, out.ctypes.data))
+        return out
 
     def prefill_chunk_tokens(self) -> int:
         """Prompt tokens prefill() feeds per weight read in the model's current mode (64 | 8; strict / exact mode: 1)."""
@@ -610,6 +635,20 @@ def op_swiglu(hb, hb2, device=0):
     check(lib().nano_hip_op_swiglu(device, h, np.ascontiguousarray(hb2, np.float32), h.size)); return h
 
 
+def op_score_rows(logits, targets=None, device=0) -> np.ndarray:
+    """The row-statistics kernel alone (nano_hip_op_score_rows): logits [rows, V] float32, targets [rows] or None (each row's own
+    arg-max); one TOKEN_SCORE_DTYPE entry per row.  Device only: without a GPU this raises."""
+    l = np.ascontiguousarray(logits, np.float32)
+    if l.ndim != 2:
+        raise ValueError("logits must be [rows, V]")
+    g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+    if g is not None and g.size != l.shape[0]:
+        raise ValueError(f"{l.shape[0]} rows but {g.size} targets")
+    out = np.zeros(l.shape[0], TOKEN_SCORE_DTYPE)
+    check(lib().nano_hip_op_score_rows(device, l.ctypes.data, l.shape[0], l.shape[1], None if g is None else g.ctypes.data, out.ctypes.data))
+    return out
+
+
 def op_argmax(x, device=0):
     i = C.c_uint32(0)
     x = np.ascontiguousarray(x, np.float32)
@@ -639,6 +678,8 @@ class Engine:
         L.llm_session_free.argtypes = [vp]
         L.nano_forward_batch.restype = C.c_int
         L.nano_forward_batch.argtypes = [vp, u32p, u32p, C.c_uint32, vp, vp]
+        L.nano_score_ids.restype = C.c_int
+        L.nano_score_ids.argtypes = [vp, u32p, C.c_uint32, vp, vp, C.POINTER(C.c_double)]
         L.nano_forward_batch_sample.restype = C.c_int
         L.nano_forward_batch_sample.argtypes = [vp, u32p, u32p, C.c_uint32, vp, vp, vp, vp]
         L.build_sampler.restype = C.POINTER(SamplerC)
@@ -685,6 +726,14 @@ class Engine:
         check(self.L.nano_forward_batch(self.ctx, t, p, t.size, logits.ctypes.data if want_logits else None,
                                         None if want_logits else amax.ctypes.data))
         return logits if want_logits else amax
+
+    def score_ids(self, ids: Sequence[int]):
+        """nano_score_ids: (logprobs[n - 1] float32, argmax[n - 1] uint32, nll_sum) of ids[1:] given what precedes each."""
+        t = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        n = max(t.size - 1, 0)
+        lp, am, nll = np.zeros(n, np.float32), np.zeros(n, np.uint32), C.c_double(0.0)
+        check(self.L.nano_score_ids(self.ctx, t, t.size, lp.ctypes.data, am.ctypes.data, C.byref(nll)))
+        return lp, am, float(nll.value)
 
     def prefill_shared(self, prefix: Sequence[int], batch: int):
         """nano_prefill_shared: ingest the prefix once per device and make it positions 0..len(prefix)-1 of sequences 0..batch-1."""

@@ -67,7 +67,8 @@ static void destroy(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
-                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->pf_stage };
+                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->pf_stage,
+                    m->score.logits, m->score.part, m->score.targets, m->score.rows, m->score.stage, m->score.out };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
     for (void *p : host) if (p) (void)hipHostFree(p);
@@ -461,18 +462,52 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     m->lora_on = on != 0;
     return 0;
 }
+// scratch of the scoring prefill, on its first call: the chunk's logits, the statistics kernel's partials, the chunk's targets and scores,
+// and the call's targets and scores (a call feeds at most max_seq_len tokens).  All or nothing: a failure leaves the model as it was.
+static int score_scratch(NanoHipModel *m) {
+    if (m->score.logits) return 0;
+    const size_t V = m->d.vocab_size, PF = m->pf_chunk, cap = m->S;
+    NanoHipModel::Score s;
+    const bool ok = hipMalloc(reinterpret_cast<void **>(&s.logits), PF * V * 4) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void **>(&s.part), PF * score_tiles((uint32_t)V) * sizeof(ScorePartial)) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void **>(&s.targets), PF * 4) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void **>(&s.rows), PF * sizeof(NanoHipTokenScore)) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void **>(&s.stage), cap * 4) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void **>(&s.out), cap * sizeof(NanoHipTokenScore)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        void *got[] = { s.logits, s.part, s.targets, s.rows, s.stage, s.out };
+        for (void *p : got) if (p) (void)hipFree(p);
+        FAIL(NANO_HIP_ENOMEM, "hipMalloc of the scoring prefill's buffers failed (%zu x %zu logits)", PF, V);
+    }
+    m->score = s;
+    return 0;
+}
 // Batched prefill: feeds `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot` in
 // passes of up to 64 (Q80 and Q4K through their int8 MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
 // logits (the reference computes and discards them for prompt positions, infer.c:1146-1149).  The KV rows and every
 // later logit are the ones token-by-token feeding produces, bit for bit (same kernels and the same attention split per token).
-extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count) {
-    if (!m || !tokens) FAIL(NANO_HIP_EINVAL, "null argument");
+// score (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);
+// out[i] scores the logits of tokens[i] for targets[i] (targets == nullptr: for the row's own arg-max).  Nothing else differs.
+static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out) {
+    if (!m || !tokens || (score && !out)) FAIL(NANO_HIP_EINVAL, "null argument");
     if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "slot %u out of range (max_batch %u)", slot, m->maxB);
     if ((uint64_t)pos0 + count > m->S) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed max_seq_len %u", pos0, pos0 + count, m->S);
     if ((uint64_t)pos0 + count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed the model's RoPE table (%u rows = block_size)", pos0, pos0 + count, m->rope_rows);
     for (uint32_t i = 0; i < count; i++) if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
+    if (score && targets) for (uint32_t i = 0; i < count; i++) if (targets[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", targets[i]);
+    if (score && !count) return 0;
     HIP_TRY(hipSetDevice(m->device));
     if (count) { const int rc = step_served(m, true); if (rc) return rc; }     // (an empty prompt queues nothing: there is nothing to refuse)
+    if (score) {
+        if (const int rc = score_scratch(m)) return rc;
+        m->score.use_targets = targets != nullptr;
+        if (targets) HIP_TRY(hipMemcpyAsync(m->score.stage, targets, (size_t)count * 4, hipMemcpyHostToDevice, m->st));      // (a pageable source, like the tokens below)
+    }
+    // token i's logits are in row 0 of m->logits (strict / exact mode: one reference-order step per token): their statistics
+    auto score_token = [&](uint32_t i) { return enqueue_score_rows(m, m->logits, 1, targets ? m->score.stage + i : nullptr, m->score.out + i); };
+    // the call's scores: one copy, behind the work queued so far and in front of the call's last wait
+    auto scores_back = [&]() { return score ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess; };
     if (m->kv.paged && count) {
         const uint32_t need = pos0 + count - 1;
         int rc = kv_ensure(m, &slot, &pos0, &need, 1);
@@ -482,10 +517,12 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         for (uint32_t i = 0; i < count; i++) {
             const uint32_t p = pos0 + i;
             int rc = stage_batch(m, tokens + i, &p, 1, false);
-            if (!rc) rc = run_step_ordered(m, 1, 1, MODE_NOCLS, slot);
+            if (!rc) rc = run_step_ordered(m, 1, 1, score ? MODE_LOGITS : MODE_NOCLS, slot);
             if (rc) return rc;
+            if (score) HIP_TRY(score_token(i));
             HIP_TRY(hipStreamSynchronize(m->st));
         }
+        if (score) { HIP_TRY(scores_back()); HIP_TRY(hipStreamSynchronize(m->st)); }
         return 0;
     }
     const uint32_t chunk_max = m->pf_chunk;
@@ -507,9 +544,11 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         for (uint32_t i = 0; i < count; i++) {
             HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + i, 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + i, 4, hipMemcpyDeviceToDevice, m->st));
-            const int rc = run_step_ordered(m, 1, 1, MODE_NOCLS, slot);
+            const int rc = run_step_ordered(m, 1, 1, score ? MODE_LOGITS : MODE_NOCLS, slot);
             if (rc) return rc;
+            if (score) HIP_TRY(score_token(i));
         }
+        HIP_TRY(scores_back());
         HIP_TRY(hipStreamSynchronize(m->st));
         return dev_err_check(m);
     }
@@ -519,7 +558,9 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
         if (nb > to_bucket_end) nb = to_bucket_end;
         HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
         HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
+        if (score && targets) HIP_TRY(hipMemcpyAsync(m->score.targets, m->score.stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
         const uint32_t range_hint = range_hint_of(m, 1, 1, pos0 + done + nb - 1);      // of the chunk's last token's own decode step
+        const uint32_t mode = score ? MODE_SCORE : MODE_NOCLS;
         m->pf = true; m->pf_slot = slot;
         hipError_t e = hipSuccess;
         if (m->use_graph && nb == chunk_max && chunk_max == 64u) {
@@ -528,8 +569,10 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
             // (a capture costs more than the ~300 launches it would save once).
             // The chunk that meets a (slot, bucket) first runs eagerly and is captured for the next prompt that reaches it; a failed
             // capture only costs the replays (r.capture is not looked at).  The cache of chunk graphs is bounded (oldest out).
-            const uint64_t key = (1ull << 62) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
-            const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, MODE_NOCLS, range_hint); });
+            // A scoring chunk has more nodes, and reads its targets or not: bits 56-57 of the key = 0 plain, 1 scored for targets, 2 scored
+            // for the arg-max, so neither ever replays the other's graph.
+            const uint64_t key = (1ull << 62) | ((uint64_t)(score ? (targets ? 1 : 2) : 0) << 56) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
+            const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, mode, range_hint); });
             e = r.step;
             if (r.stored) {
                 if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
@@ -540,15 +583,24 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
                 m->pf_graph_keys.push_back(key);
             }
         } else {
-            e = enqueue_step(m, nb, 1, MODE_NOCLS, range_hint);            // eager: one pass per chunk
+            e = enqueue_step(m, nb, 1, mode, range_hint);                  // eager: one pass per chunk
         }
         m->pf = false;
         m->nsplit = 1;                                                     // a prefill chunk leaves xba final (single split or the combine kernel), replayed or not
         HIP_TRY(e);
+        if (score) HIP_TRY(hipMemcpyAsync(m->score.out + done, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
         done += nb;
     }
+    HIP_TRY(scores_back());
     HIP_TRY(hipStreamSynchronize(m->st));
     return dev_err_check(m);
+}
+extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count) {
+    return prefill_run(m, slot, tokens, pos0, count, false, nullptr, nullptr);
+}
+extern "C" int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
+                                      const uint32_t *targets, NanoHipTokenScore *out) {
+    return prefill_run(m, slot, tokens, pos0, count, true, targets, out);
 }
 extern "C" uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m) {
     if (!m) return 0u;

@@ -44,7 +44,8 @@ extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the t
 #pragma GCC visibility push(hidden)
 
 enum { WQ = 0, WK, WV, WO, W1, W2, W3, WCOUNT };
-enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3 };
+enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3,
+                           MODE_SCORE = 4 };   // a prefill chunk that goes on into the classifier for all its rows (-> score.logits) and the row statistics
 constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs kept per model (keyed by KV slot x range bucket)
 constexpr uint32_t STAMP_MAX_LAUNCHES = 512, STAMP_WGS = 2048;
 constexpr uint32_t KV_NO_PAGE = 0xffffffffu;           // a page-table entry without a page
@@ -86,6 +87,16 @@ struct NanoHipModel {
     // pinned host staging
     uint32_t *h_tokens = nullptr, *h_pos = nullptr, *h_amax = nullptr;
     uint32_t *pf_stage = nullptr; uint32_t pf_cap = 0;    // batched prefill: the prompt's tokens | positions on the device (the chunks copy from here: no host round trip per chunk)
+    // scoring prefill (nano_hip_prefill_score), allocated on its first call: the chunk's logits never leave the device
+    struct Score {
+        float *logits = nullptr;                          // [pf_chunk][V]: m->logits holds max_batch rows, not chunk rows
+        ScorePartial *part = nullptr;                     // [pf_chunk][score_tiles(V)] tile partials of the statistics kernel
+        uint32_t *targets = nullptr;                      // [pf_chunk] the chunk's targets (a chunk graph reads them here, like m->tokens)
+        NanoHipTokenScore *rows = nullptr;                // [pf_chunk] the chunk's scores
+        bool use_targets = false;                         // of the call in progress: false = each row's own arg-max
+        uint32_t *stage = nullptr;                        // [max_seq_len] the call's targets on the device
+        NanoHipTokenScore *out = nullptr;                 // [max_seq_len] the call's scores, copied back once
+    } score;
     uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
     float *h_logits = nullptr;
     std::map<uint64_t, hipGraphExec_t> graphs;
@@ -199,7 +210,8 @@ int kv_ensure_batch(NanoHipModel *m, const uint32_t *pos, uint32_t batch, uint32
 void sampler_free(Sampler *sp);                        // backend_sampler.hip
 
 // ---- backend_step.hip ----
-hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr);
+hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr, float *dst = nullptr);    // dst: nullptr = m->logits
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out);
 hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint);
 bool strict_serves(const NanoHipModel *m);
 bool exact_serves(const NanoHipModel *m);

@@ -30,16 +30,16 @@ static hipError_t gemv(NanoHipModel *m, GemvArgs &a) {
     return route_projection(route_of(m), a, m->st);
 }
 
-static GemvArgs classifier_args(const NanoHipModel *m, uint32_t nb) {
+static GemvArgs classifier_args(const NanoHipModel *m, uint32_t nb, float *dst) {
     GemvArgs a{};
-    a.nseg = 1; a.seg[0] = mkseg(m->cls, m->logits, m->d.vocab_size, m->d.vocab_size);
+    a.nseg = 1; a.seg[0] = mkseg(m->cls, dst, m->d.vocab_size, m->d.vocab_size);
     a.n = m->d.n_embd; a.gs = m->d.group_size; a.nb = nb; a.xin = m->x; a.xin_bstride = m->d.n_embd;
     a.epi = GEMV_EPI_STORE; a.norm_w = m->rms_final; a.pos = m->pos;
     return a;
 }
 
-hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out) {
-    GemvArgs a = classifier_args(m, nb);
+hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out, float *dst) {
+    GemvArgs a = classifier_args(m, nb, dst ? dst : m->logits);
     a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes;           // (what route_projection() will set: the partial count must match the launch)
     if (ntiles_out && nb <= 8 && !route_takes_fragments(kind_of(m, a)) &&
         (m->d.quant_type != NANO_QUANT_Q4K || nb <= (nb > 1 ? gemv_q4k_fit_batch(a) : 1u))) {      // per-tile arg-max partials for the sampler (Q4K: not for sliced launches)
@@ -47,6 +47,12 @@ hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out
         *ntiles_out = gemv_tiles(m->d.quant_type, a);
     }
     return gemv(m, a);
+}
+// the row statistics of `rows` rows of logits (row stride V) for targets[rows] (nullptr: each row's own arg-max) -> out[rows]  (score.hip)
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out) {
+    ScoreArgs a{};
+    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.targets = targets; a.part = m->score.part; a.out = out;
+    return launch_score_rows(a, rows, m->st);
 }
 // attention splits of a step: batches bring their own parallelism (nb x KV groups workgroups per split) and every
 // split costs the Wo prologue nb x nsplit partial reads, so larger batches split less
@@ -233,13 +239,17 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
         }
     }
     if (mode == MODE_NOCLS) return hipSuccess;
+    if (mode == MODE_SCORE) {       // a scoring prefill chunk: the classifier over all nb rows (final rmsnorm in its prologue), then their statistics
+        if ((e = enqueue_classifier(m, nb, nullptr, m->score.logits)) != hipSuccess) return e;
+        return enqueue_score_rows(m, m->score.logits, nb, m->score.use_targets ? m->score.targets : nullptr, m->score.rows);
+    }
     const bool sample = (mode == MODE_ARGMAX || mode == MODE_LOOP);
     uint32_t ntiles = 0;
     // probe: Q80 STREAM classifier (batch <= 8) -> the kernel's own start / stop timestamps (hipExtLaunchKernelGGL);
     // other classifiers -> events recorded around the launch (ev1..ev2 = an empty pair, the event overhead)
-    bool probe_ext = m->probe_cls && d.quant_type == NANO_QUANT_Q80 && nb <= 8 && d.vocab_size >= 16384 && !route_takes_fragments(kind_of(m, classifier_args(m, nb)));
+    bool probe_ext = m->probe_cls && d.quant_type == NANO_QUANT_Q80 && nb <= 8 && d.vocab_size >= 16384 && !route_takes_fragments(kind_of(m, classifier_args(m, nb, m->logits)));
     if (m->probe_cls && d.quant_type == NANO_QUANT_Q4K && nb == 1 && d.vocab_size >= 65536) {      // gemv_q4k_chunk.hip's looping launch
-        GemvArgs ca = classifier_args(m, nb);
+        GemvArgs ca = classifier_args(m, nb, m->logits);
         probe_ext = gemv_q4k_chunk_loops(ca);
     }
     if (probe_ext) { g_q80_probe_start = m->ev0; g_q80_probe_stop = m->ev1; }
@@ -345,7 +355,7 @@ static hipError_t enqueue_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is
     ST(rmsnorm(m->rms_final));
     ST(phase(L, 11));                                                   // CLASSIFY    infer.c:1003-1015
     {
-        GemvArgs a = classifier_args(m, nb);
+        GemvArgs a = classifier_args(m, nb, m->logits);
         a.xin = m->xn; a.norm_w = nullptr;
         ST(strict_project(m, a));
     }

@@ -471,6 +471,32 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
     return rc;
 }
 
+/* The log-probability of ids[1..n_ids) given what precedes each: one scoring prefill of ids[0..n_ids-1) into sequence 0 of the context's own
+ * device, targets ids + 1 (nano_hip_prefill_score); the logits stay on the device. */
+int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || (!ids && n_ids)) return NANO_HIP_EINVAL;
+    if (nll_sum) *nll_sum = 0.0;
+    if (n_ids < 2) return NANO_HIP_OK;
+    const uint32_t n = n_ids - 1;
+    NanoHipTokenScore *sc = (NanoHipTokenScore *)malloc((size_t)n * sizeof *sc);
+    if (!sc) return NANO_HIP_ENOMEM;
+    lora_select(me->dev, ctx->lora);
+    me->pf_session = NULL;                                    /* sequence 0's rows are this text's now */
+    const int rc = nano_hip_prefill_score(me->dev, 0, ids, 0, n, ids + 1, sc);
+    if (rc == NANO_HIP_OK) {
+        double nll = 0.0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (logprobs) logprobs[i] = sc[i].logprob;
+            if (argmax) argmax[i] = sc[i].argmax;
+            nll -= (double)sc[i].logprob;
+        }
+        if (nll_sum) *nll_sum = nll;
+    }
+    free(sc);
+    return rc;
+}
+
 /* One prompt prefix for `batch` sequences: each replica ingests it once (batched prefill into its slot 0) and forks the rows into the
  * other slots of its share -- sequence i lives in slot i / G of replica i mod G, as in nano_forward_batch. */
 int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch) {

@@ -301,6 +301,19 @@ struct ArgmaxArgs {
 };
 hipError_t launch_argmax(const ArgmaxArgs &a, uint32_t nb, hipStream_t st);
 
+// ---- row statistics of logits for given targets (score.hip): one NanoHipTokenScore per row ----
+constexpr uint32_t SCORE_TILE = 4096;                      // logits per tile: the reduction shape is a function of V alone
+struct ScorePartial { float m, s; uint32_t idx, cnt; };    // of one tile: maximum, sum of expf(l - m), first index of m, the tile's share of rank
+struct ScoreArgs {
+    const float *logits; uint32_t V, ntiles;               // [rows][V], row stride V; ntiles = score_tiles(V)
+    const uint32_t *targets;                               // [rows], every one < V; nullptr: each row's own arg-max
+    ScorePartial *part;                                    // scratch [rows][ntiles]
+    NanoHipTokenScore *out;                                // [rows]
+};
+uint32_t score_tiles(uint32_t V);
+// two launches: the tiles, then one wave per row
+hipError_t launch_score_rows(const ScoreArgs &a, uint32_t rows, hipStream_t st);
+
 hipError_t launch_rmsnorm(float *out, const float *x, const float *w, uint32_t n, hipStream_t st);
 hipError_t launch_quantize_q80(const float *x, uint32_t n, uint32_t gs, int8_t *q, float *s, hipStream_t st);
 hipError_t launch_quantize_q4k(const float *x, uint32_t n, uint8_t *blocks, hipStream_t st);

@@ -203,6 +203,23 @@ extern "C" int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32
     return 0;
 }
 
+// the row-statistics kernel alone (score.hip).  The arguments are checked before a device is asked for.
+extern "C" int nano_hip_op_score_rows(int device, const float *logits, uint32_t rows, uint32_t V, const uint32_t *targets, NanoHipTokenScore *out) {
+    if (!logits || !out || !rows || !V) { nano_hip_set_error_("score_rows: null logits / out, or no rows / no vocabulary"); return NANO_HIP_EINVAL; }
+    if (targets) for (uint32_t r = 0; r < rows; r++) if (targets[r] >= V) { nano_hip_set_error_("score_rows: target out of vocabulary"); return NANO_HIP_EINVAL; }
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B;
+    ScoreArgs a{};
+    a.V = V; a.ntiles = score_tiles(V);
+    a.logits = B.upload(logits, (size_t)rows * V);
+    a.targets = targets ? B.upload(targets, rows) : nullptr;
+    a.part = B.alloc<ScorePartial>((size_t)rows * a.ntiles); a.out = B.alloc<NanoHipTokenScore>(rows);
+    OP_CHECK(a.logits && (a.targets || !targets) && a.part && a.out, "device alloc failed");
+    OP_HIP(launch_score_rows(a, rows, 0));
+    OP_HIP(hipMemcpy(out, a.out, (size_t)rows * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part, read as flags), or nullptr
 static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || d.n % 4) return "bad fused-gemv descriptor";
