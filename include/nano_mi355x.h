@@ -429,6 +429,16 @@ int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
  * shape is refused before any launch (a row of more than 16384 floats, 8192 with SwiGLU; one sequence that does not fit a CU's LDS).
  * Host arithmetic on the shape fields: works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
 int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[12]);
+/* The Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, role, gs, B, nv, upw, rw, nw,
+ * grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}.  route: the router's choice with the step's scratch present (the value
+ * route_out of nano_hip_op_fused_gemv reports).  Routes that end in the Q80 GEMV: kernel 1 = gemv_q80_slab_kernel<role, gs, B, nv, upw>
+ * in its form `variant` (0 plain, 1 early, 2 wf, 3..5 wfc2..4), 2 = gemv_q80_stream_kernel<role, gs, B, nv>; nw waves x grid workgroups,
+ * rw rows per workgroup, lds_bytes of dynamic LDS; pre = 1: the activation reaches the kernel quantized; the plan is that of the first
+ * of `launches` slices of seqs_per_launch sequences.  The batched routes (G6 / G7 / G2 / GC): the route, launches = 1,
+ * seqs_per_launch = nb, zeros for the kernel fields.  takes = 0: the shape is refused before any launch (a SLAB row of more than 65536
+ * values, 32768 with SwiGLU; one sequence that does not fit a CU's LDS) and every other entry is 0.  Host arithmetic on the shape fields:
+ * works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
+int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[16]);
 
 /* One device-resident copy of a model's parameter bytes per GPU from ONE host upload (replicate.hip; SURVEY 8e "broadcast(weights) at
  * load"): the bytes go to `root_device` over PCIe once and from there to the other devices over xGMI -- an RCCL broadcast (librccl.so

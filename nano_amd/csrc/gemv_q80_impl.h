@@ -599,208 +599,95 @@ __global__ __launch_bounds__(256) void gemv_q80_stream_kernel(const GemvDev a) {
 // host side
 // ------------------------------------------------------------------------------------------------------------
 
-// rows per workgroup / waves per workgroup of a slab launch (tuned on Qwen3-0.6B with the round-1 kernel laboratory: the chain
-// time is flat within 3 % around these choices -- the kernels are latency bound)
-struct SlabPlan { uint32_t rw, nw, upw, nv; };
-static SlabPlan plan_slab(const GemvArgs &a, int B) {
-    const uint32_t nchunk = (a.n + 1023) / 1024, nmat = a.epi == GEMV_EPI_SWIGLU ? 2 : 1;
-    const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
-    uint32_t align = 0;                                   // a workgroup's rows must lie inside one segment
-    if (nseg > 1) for (uint32_t s = 0; s < nseg; s++) align |= a.seg[s].rows;
-    const uint32_t rows = total_rows(a);
-    // Every workgroup re-stages the activations (B x n elements), so the row slab grows until one wave of workgroups
-    // covers the chip: the largest power of two with >= 256 workgroups (small matrices: ~4 units = 16 KiB of weights per
-    // matrix and >= 128 workgroups, the tuned batch-1 optimum), bounded by the LDS product table.
-    uint32_t rw = 4;
-    while (rw < 32 && (align % (rw * 2)) == 0 && (rw * 2 / 4) * nchunk <= 4 && rows / (rw * 2) >= 128) rw *= 2;
-    while (rw < 64 && (align % (rw * 2)) == 0 && rows / (rw * 2) >= 256) rw *= 2;
-    {
-        const uint32_t ng = a.n / a.gs, pitch = ((ng + 47) / 64) * 64 + 16;
-        while (rw > 4 && (size_t)B * nmat * rw * pitch * 4 > 64 * 1024) rw /= 2;
-        while (rw > 4 && (rw / 4) * nchunk * nmat > 64) rw /= 2;          // <= 16 waves x 4 units
-    }
-    // One workgroup per CU when the power of two leaves CUs idle (round 3, Qwen3-0.6B's W1|W3: 3072 rows as 192 slabs of 16 ->
-    // 256 slabs of 12: 1871-1879 -> 1896 tok/s; the slab kernel takes any row count).  One-segment launches only.
-    if (B == 1 && nseg == 1) {
-        const uint32_t cus = a.cus ? a.cus : 256u, c = (rows + cus - 1) / cus;
-        if (c >= 5 && c < rw && rows / rw < cus && ((c + 3) / 4) * nchunk * nmat <= 64) rw = c;
-    }
-    // Large matrices (Qwen3-4B's layers: 10-50 MB each) are bandwidth rather than latency bound, and a CU pulls ~25 GB/s whatever
-    // it runs: the launch ends when the CU with the most rows ends.  BALANCED slabs (round 3): rw = ANY row count, chosen to
-    // minimise (rounds of `cus` workgroups) x rw = the rows the busiest CU streams; a power-of-two slab left 160 of 256 CUs
-    // busy on a 2560-row matrix (rw 16) where rw = 10 gives every CU one workgroup.  On a tie the larger slab (fewer
-    // workgroups re-staging the activation).
-    uint32_t large_nw = 0;
-    // (round 5: TWO sequences on these matrices take the same balanced slabs, the product table twice as large -- Qwen3-4B at 2 sequences
-    //  1.833 ms per step against 1.923 through G6 MODE P, same box; four sequences: 2.80 against 1.99 through G6, so two is where it ends)
-    if (B <= 2 && (uint64_t)rows * a.n * nmat >= (8u << 20)) {
-        const uint32_t cus = a.cus ? a.cus : 256u;
-        uint32_t best = 0, best_cost = ~0u;
-        const uint32_t ng = a.n / a.gs, pitch = (1024 / a.gs == 16) ? (((ng + 47) / 64) * 64 + 16) : (((ng + 3) & ~3u) + 4);
-        for (uint32_t c = 4; c <= 64; c++) {
-            const uint32_t tpw = (c + 3) / 4;
-            if (tpw * nchunk * nmat > 64) break;                           // <= 16 waves x 4 units
-            if ((size_t)B * nmat * tpw * 4 * pitch * 4 > 96 * 1024) break;     // product table
-            uint32_t wgs = 0;
-            if (nseg > 1) for (uint32_t s2 = 0; s2 < nseg; s2++) wgs += (a.seg[s2].rows + c - 1) / c; else wgs = (rows + c - 1) / c;
-            // rows of the busiest CU; more than one workgroup per CU pays its prologue several times over on shared issue
-            // slots (measured: QKV of Qwen3-4B, 768 workgroups of 8 rows 7.4 us vs 192 of 32 rows 6.9), so x 1.15 then
-            uint32_t cost = ((wgs + cus - 1) / cus) * c * 100u;
-            if (wgs > cus) cost += cost * 15u / 100u;
-            if (cost <= best_cost) { best_cost = cost; best = c; }
-        }
-        if (best) {
-            rw = best;
-            const uint32_t u = ((rw + 3) / 4) * nchunk * nmat;
-            large_nw = u / 2 < 8 ? 8 : (u / 2 > 16 ? 16 : u / 2);
-        }
-    }
-    const uint32_t units = ((rw + 3) / 4) * nchunk * nmat;
-    uint32_t nw = units < 4 ? units : 4;
-    // (one sequence, re-swept on round 6's last day with the three-launch layer: a wave per 384 activation values -- W2 of Qwen3-0.6B on 8 waves
-    //  instead of 6 -- 1994 / 1978 tok/s against 1979 / 1966 with 512, 1984 / 1972 with 448, 1952 / 1959 with 320; the five-launch form and Qwen3-4B: even)
-    const uint32_t want_div = B == 1 ? 384u : 512u;
-    uint32_t want = (a.n * (uint32_t)(B > 2 ? B / 2 : 1) + want_div - 1) / want_div;     // idle waves still help the activation prologue
-    if (want > 16) want = 16;
-    if (nw < want) nw = want;
-    if (nw * 64 < rw * (uint32_t)B) nw = (rw * (uint32_t)B + 63) / 64;      // one fold thread per (row, sequence)
-    if (nw < 2) nw = 2;
-    uint32_t upw = (units + nw - 1) / nw;
-    while (upw > 4 && nw < 16) { nw++; upw = (units + nw - 1) / nw; }
-    if (large_nw) { nw = large_nw; upw = (units + nw - 1) / nw; while (upw > 4 && nw < 16) { nw++; upw = (units + nw - 1) / nw; } }
-    // (Round 4 tried a raw barrier between the activation loads and the weight loads of the large slabs, so that every wave's activation
-    // is asked for before any weight -- round 3 had measured the activation of Qwen3-4B's W1|W3 "arriving" with the end of the 52.9 MB
-    // burst.  Measured on one box: 1.4707 ms per step with it, 1.4594 without.  The launch is bound by latency + stream + tail, not by
-    // where the activation sits in the queue.  Removed.)
-    SlabPlan p{rw, nw, upw, (a.n + 256 * nw - 1) / (256 * nw)};
-    return p;
-}
-
-// a launch whose rows are one 1 KiB chunk of group size 64: the in-wave fold (SLAB_WF) takes it (the callers add: one sequence, an rmsnorm role,
-// a canonical launch).  W1|W3 is never position indexed in a decode step; such a launch would keep the table.
-static bool slab_wave_fold(const GemvDev &d) {
-    return d.n == 1024u && d.ng == 16u && !d.early && (d.epi == GEMV_EPI_STORE || (d.epi == GEMV_EPI_SWIGLU && !d.out_pstride[0]));
-}
-// a residual launch (Wo, W2) whose rows are 2..4 WHOLE chunks of group size 64: the chunk count when the in-wave fold of a unit's chunk
-// (SLAB_WFC) takes it, else 0 (the callers add: one sequence, a residual role, a canonical launch).  A LoRA addend or a position-indexed output
-// keeps the table.
-static uint32_t slab_wave_fold_chunks(const GemvDev &d) {
-    if (d.nb != 1u || d.early || d.epi != GEMV_EPI_RESID || d.resid_add || d.out_pstride[0] || d.rows[1] || (d.flags & ~F_COMBINE)) return 0u;
-    if (d.n % 1024u || d.n < 2048u || d.n > 4096u || d.ng * 64u != d.n) return 0u;
-    return d.n / 1024u;
-}
-static size_t slab_unit_table(const GemvDev &d, uint32_t nch) { return (size_t)(d.tpw * 4) * (nch <= 2u ? 4u : 8u) * 4u; }      // [rows of the tiles][unit sums] floats
+// Every choice of a launch -- kernel, role, capacity, template values, waves, rows per workgroup, grid, LDS bytes, the special form -- is
+// gemv_q80_plan()'s (gemv_q80.hip, kernels.h Q80GemvPlan): the launchers below only turn a plan into the instantiation it names.
 template <int ROLE, int GS, int B, int NV, int UPW>
-static hipError_t launch_slab_t(const GemvDev &d, const SlabPlan &p, uint32_t nwg, hipStream_t st) {
-    const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
-    const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u;
-    const size_t pitch = (1024 / GS == 16) ? (((d.ng + 47) / 64) * 64 + 16) : (ng4 + 4);
-    const size_t lds = B * n16 + B * ng4 * 4 + B * 64 + ((d.flags & F_COMBINE) ? (size_t)B * d.attn_n_head * 32 : 0) + (size_t)B * nmat * (d.tpw * 4) * pitch * 4;
+static hipError_t launch_slab_t(const GemvDev &d, const Q80GemvPlan &p, hipStream_t st) {
     GemvDev dd = d; dd.nthr = 64 * p.nw;
-    // the matrices of >= 8 M weights (d.early, one or two sequences, group size 64): the first unit of every wave before the activation is
+    const size_t lds = p.lds_bytes;
+    // the matrices of >= 8 M weights (one or two sequences, group size 64): the first unit of every wave before the activation is
     // quantized, the others after (gemv_q80_slab_body.inc SLAB_EARLY)
-    if constexpr (GS == 64 && B <= 2 && UPW >= 2 && NV >= 1) if (d.early) {
+    if constexpr (GS == 64 && B <= 2 && UPW >= 2 && NV >= 1) if (p.variant == Q80_VAR_EARLY) {
         auto kern = &gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 1>;
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * p.nw), lds, st, dd);
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), lds, st, dd);
         return hipGetLastError();
     }
-    // rows of ONE chunk (n == 1024), one sequence, the rmsnorm roles (canonical launches only at this group size: launch_slab_b): every wave
+    // rows of ONE chunk (n == 1024), one sequence, the rmsnorm roles (canonical launches only at this group size): every wave
     // folds its own rows -- no product table in the LDS budget, no barrier behind the dots (gemv_q80_slab_body.inc SLAB_WF).  W1|W3: units of
-    // two rows of each matrix, so that a wave holds both halves of its SwiGLU pairs
-    if constexpr (GS == 64 && B == 1 && (ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU) && (NV == 1 || NV == 2)) if (slab_wave_fold(d)) {
-        if (ROLE == R_NORM_SWIGLU) dd.units = (d.rw + 1) / 2;
-        hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 1>), dim3(nwg), dim3(64 * p.nw), n16 + ng4 * 4 + 64, st, dd);
+    // two rows of each matrix, so that a wave holds both halves of its SwiGLU pairs (the plan's units)
+    if constexpr (GS == 64 && B == 1 && (ROLE == R_NORM_STORE || ROLE == R_NORM_SWIGLU) && (NV == 1 || NV == 2)) if (p.variant == Q80_VAR_WF) {
+        hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 1>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd);
         return hipGetLastError();
     }
-    // rows of 2..4 whole chunks, one sequence, the residual roles (Wo, W2; canonical launches only at this group size: launch_slab_b): every
+    // rows of 2..4 whole chunks, one sequence, the residual roles (Wo, W2; canonical launches only at this group size): every
     // wave folds the chunk of its unit to two unit sums -- 8 floats per unit in LDS instead of the product table, 2 nch - 1 adds behind the
     // barrier (gemv_q80_slab_body.inc SLAB_WFC).  (The plans of such matrices have <= 8 units on >= 6 waves: one or two units per wave.)
     if constexpr (GS == 64 && B == 1 && (ROLE == R_RESID || ROLE == R_RESID_COMBINE) && (NV == 1 || NV == 2) && UPW <= 2) {
-        const uint32_t nch = slab_wave_fold_chunks(d);
-        if (nch) {
-            const size_t lds_c = n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + slab_unit_table(d, nch);
-            if (nch == 2u) hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 2>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
-            else if (nch == 3u) hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 3>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
-            else hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 4>), dim3(nwg), dim3(64 * p.nw), lds_c, st, dd);
-            return hipGetLastError();
-        }
+        if (p.variant == Q80_VAR_WFC2) { hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 2>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
+        if (p.variant == Q80_VAR_WFC3) { hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 3>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
+        if (p.variant == Q80_VAR_WFC4) { hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 0, 4>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
     }
+    if (p.variant != Q80_VAR_PLAIN) return hipErrorInvalidValue;          // (a form this instantiation does not have: the plan and the templates disagree)
     auto kern = &gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * p.nw), lds, st, dd);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), lds, st, dd);
     return hipGetLastError();
 }
+// the instantiations: every (NV, UPW) of {0, 1, 2, 4} x {1, 2, 4} with B * NV <= 8 (tests/test_q80_gemv_plan.py restates the set)
 template <int ROLE, int GS, int B>
-static hipError_t launch_slab_r(const GemvDev &d, const SlabPlan &p, uint32_t rows, hipStream_t st) {
-    if (p.upw > 4) return hipErrorInvalidValue;
-#define SLAB_GO(NV_, UPW_) do { if constexpr (B * NV_ <= 8) return launch_slab_t<ROLE, GS, B, NV_, UPW_>(d, p, rows, st); } while (0)
-    int nv = p.nv <= 1 ? 1 : p.nv <= 2 ? 2 : p.nv <= 4 ? 4 : 0;
-    const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-    if (B * nv > 8) nv = 0;          // too many staged registers: loop path
-    if (nv == 1) { if (upw == 1) SLAB_GO(1, 1); if (upw == 2) SLAB_GO(1, 2); SLAB_GO(1, 4); }
-    if (nv == 2) { if (upw == 1) SLAB_GO(2, 1); if (upw == 2) SLAB_GO(2, 2); SLAB_GO(2, 4); }
-    if (nv == 4) { if (upw == 1) SLAB_GO(4, 1); if (upw == 2) SLAB_GO(4, 2); SLAB_GO(4, 4); }
-    if (upw == 1) SLAB_GO(0, 1);
-    if (upw == 2) SLAB_GO(0, 2);
-    SLAB_GO(0, 4);
+static hipError_t launch_slab_r(const GemvDev &d, const Q80GemvPlan &p, hipStream_t st) {
+#define SLAB_GO(NV_, UPW_) do { if constexpr (B * NV_ <= 8) { if (p.nv == NV_ && p.upw == UPW_) return launch_slab_t<ROLE, GS, B, NV_, UPW_>(d, p, st); } } while (0)
+    SLAB_GO(1, 1); SLAB_GO(1, 2); SLAB_GO(1, 4);
+    SLAB_GO(2, 1); SLAB_GO(2, 2); SLAB_GO(2, 4);
+    SLAB_GO(4, 1); SLAB_GO(4, 2); SLAB_GO(4, 4);
+    SLAB_GO(0, 1); SLAB_GO(0, 2); SLAB_GO(0, 4);
     return hipErrorInvalidValue;
 #undef SLAB_GO
 }
 template <int GS, int B>
-static hipError_t launch_slab_b(GemvDev &d, const GemvArgs &a, hipStream_t st) {
-    const SlabPlan p = plan_slab(a, B);
+static hipError_t launch_slab_b(GemvDev &d, const Q80GemvPlan &p, hipStream_t st) {
     d.rw = p.rw;
-    // the matrices of >= 8 M weights, one or two sequences: the first unit of every wave's weights before the activation is quantized, the others
-    // after (SLAB_EARLY).  Same box, interleaved (profiles/r06_slab_early_units.txt): Qwen3-4B one sequence 1.471 -> 1.427 ms per step, two
-    // sequences 1.956 -> 1.825; the first TWO units early: no gain over none (one sequence), the same as one (two sequences).
-    d.early = (B <= 2 && p.upw >= 2 && (uint64_t)total_rows(a) * a.n * (a.epi == GEMV_EPI_SWIGLU ? 2 : 1) >= (8u << 20)) ? 1u : 0u;
+    d.early = p.early;
     d.tpw = (p.rw + 3) / 4;
     d.magic_rw = 65536u / p.rw + 1u;                                   // (tid * magic_rw) >> 16 == tid / rw for tid < 1024 <= 65536 / rw
     d.log2_tiles = 0;
-    const bool sw = d.epi == GEMV_EPI_SWIGLU;
-    d.units = d.tpw * d.nchunk * (sw ? 2 : 1);
-    // workgroups per segment (a workgroup's rows lie inside one segment; the last one of a segment may be ragged)
-    uint32_t wg[3] = {0, 0, 0};
-    const uint32_t nseg = sw ? 1u : a.nseg;
-    for (uint32_t s2 = 0; s2 < nseg; s2++) wg[s2] = (a.seg[s2].rows + p.rw - 1) / p.rw;
-    d.wg_c0 = nseg > 1 ? wg[0] : 0xffffffffu;
-    d.wg_c1 = nseg > 2 ? wg[0] + wg[1] : 0xffffffffu;
-    const uint32_t rows = wg[0] + wg[1] + wg[2];                       // the grid
+    d.units = p.units;
+    d.wg_c0 = p.wg_c0; d.wg_c1 = p.wg_c1;                              // workgroups up to the end of segment 0 / 1 (a workgroup's rows lie inside one segment)
     // the per-layer launches of a batch-1 step: flags resolved at compile time.  Group size 64: the role kernels carry the canonical fold
-    // only, so a launch that is not canonical (strict mode; a row length that is no multiple of 256) takes the generic kernel
-    if constexpr (B == 1) if (GS != 64 || d.canon) {
-        const uint32_t f = d.flags;
-        if (f == F_NORM && d.epi == GEMV_EPI_STORE) return launch_slab_r<R_NORM_STORE, GS, B>(d, p, rows, st);
-        if (f == 0 && d.epi == GEMV_EPI_RESID) return launch_slab_r<R_RESID, GS, B>(d, p, rows, st);
-        if (f == F_COMBINE && d.epi == GEMV_EPI_RESID) return launch_slab_r<R_RESID_COMBINE, GS, B>(d, p, rows, st);
-        if (f == F_NORM && d.epi == GEMV_EPI_SWIGLU) return launch_slab_r<R_NORM_SWIGLU, GS, B>(d, p, rows, st);
+    // only, so a launch that is not canonical (strict mode; a row length that is no multiple of 256) has the generic kernel in its plan
+    if constexpr (B == 1) {
+        if (p.role == R_NORM_STORE) return launch_slab_r<R_NORM_STORE, GS, B>(d, p, st);
+        if (p.role == R_RESID) return launch_slab_r<R_RESID, GS, B>(d, p, st);
+        if (p.role == R_RESID_COMBINE) return launch_slab_r<R_RESID_COMBINE, GS, B>(d, p, st);
+        if (p.role == R_NORM_SWIGLU) return launch_slab_r<R_NORM_SWIGLU, GS, B>(d, p, st);
     }
-    return launch_slab_r<R_GENERIC, GS, B>(d, p, rows, st);
+    if (p.role != R_GENERIC) return hipErrorInvalidValue;
+    return launch_slab_r<R_GENERIC, GS, B>(d, p, st);
 }
 
 template <int ROLE, int GS, int B>
-static hipError_t launch_stream_r(GemvDev &d, hipStream_t st) {
-    d.ntiles = STREAM_WGS * 4; d.nthr = 256;
-    const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u;
-    const size_t lds = B * n16 + B * ng4 * 4 + B * 64 + 4 * 16 * (1024 / GS) * 4;
-    const uint32_t nv = (d.n + 1023) / 1024;
+static hipError_t launch_stream_r(GemvDev &d, const Q80GemvPlan &p, hipStream_t st) {
+    d.ntiles = p.grid * 4; d.nthr = 64 * p.nw;
+    const size_t lds = p.lds_bytes;
     hipEvent_t e0 = g_q80_probe_start, e1 = g_q80_probe_stop;
     g_q80_probe_start = g_q80_probe_stop = nullptr;
-#define STREAM_GO(NV_) do { if (e0 && e1) hipExtLaunchKernelGGL((gemv_q80_stream_kernel<ROLE, GS, B, NV_>), dim3(STREAM_WGS), dim3(256), (uint32_t)lds, st, e0, e1, 0, d); \
-                            else hipLaunchKernelGGL((gemv_q80_stream_kernel<ROLE, GS, B, NV_>), dim3(STREAM_WGS), dim3(256), lds, st, d); } while (0)
-    bool done = false;
-    if (nv <= 1) { STREAM_GO(1); done = true; }
-    if constexpr (B <= 4) { if (!done && nv <= 2) { STREAM_GO(2); done = true; } }
-    if constexpr (B <= 2) { if (!done && nv <= 4) { STREAM_GO(4); done = true; } }
-    if (!done) { STREAM_GO(0); }
+#define STREAM_GO(NV_) do { auto kern = &gemv_q80_stream_kernel<ROLE, GS, B, NV_>; \
+                            if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+                            if (e0 && e1) hipExtLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), (uint32_t)lds, st, e0, e1, 0, d); \
+                            else hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), lds, st, d); return hipGetLastError(); } while (0)
+    if (p.nv == 1) STREAM_GO(1);
+    if constexpr (B <= 4) { if (p.nv == 2) STREAM_GO(2); }
+    if constexpr (B <= 2) { if (p.nv == 4) STREAM_GO(4); }
+    if (p.nv == 0) STREAM_GO(0);
 #undef STREAM_GO
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 template <int GS, int B>
-static hipError_t launch_stream_b(GemvDev &d, hipStream_t st) {
-    if (d.flags == F_NORM) return launch_stream_r<R_NORM_STORE, GS, B>(d, st);      // the classifier
-    return launch_stream_r<R_GENERIC, GS, B>(d, st);
+static hipError_t launch_stream_b(GemvDev &d, const Q80GemvPlan &p, hipStream_t st) {
+    if (p.role == R_NORM_STORE) return launch_stream_r<R_NORM_STORE, GS, B>(d, p, st);      // the classifier
+    if (p.role != R_GENERIC) return hipErrorInvalidValue;
+    return launch_stream_r<R_GENERIC, GS, B>(d, p, st);
 }
 
 #if NANO_Q80_GS == 64
@@ -809,7 +696,7 @@ static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, SlabPlan &p) {
     if (ga.gs != 64 || ga.nb != 1 || ga.nseg != 3 || ga.epi != GEMV_EPI_STORE || !ga.norm_w || ga.xq_in || ga.attn_part || ga.tile_max || ga.resid_add) return false;
     if (ga.n % 64u || ga.n > 4096u || use_stream(ga) || !q80_canonical(ga)) return false;        // (the role kernels of group size 64 carry the canonical fold only)
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
-    p = plan_slab(ga, 1);
+    p = q80_plan_slab(ga, 1);
     if (p.nw != 4u || p.upw > 4u || !(p.nv == 1u || p.nv == 2u || p.nv == 4u)) return false;        // 256 threads, like the attention workgroups
     if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;   // (kernels.h)
     return true;
@@ -826,7 +713,7 @@ static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (wo.attn_part && (wo.attn_nsplit > 8u || wo.attn_hd % 4u)) return false;
     if (w13.nseg != 2 || w13.epi != GEMV_EPI_SWIGLU || !w13.norm_w || w13.xq_in || w13.attn_part || w13.tile_max || w13.resid_add) return false;
     if (use_stream(wo) || use_stream(w13) || w13.n != wo.seg[0].rows || w13.xin != wo.seg[0].out || w13.n % 4u) return false;
-    q.a = plan_slab(wo, 1); q.b = plan_slab(w13, 1);
+    q.a = q80_plan_slab(wo, 1); q.b = q80_plan_slab(w13, 1);
     q.nw = q.b.nw;
     const uint32_t units_a = ((q.a.rw + 3) / 4) * ((wo.n + 1023) / 1024);
     q.upw_a = (units_a + q.nw - 1) / q.nw;
@@ -863,23 +750,24 @@ static size_t slab_lds(const GemvDev &d, bool table = true) {
 #endif
 
 template <int GS, int B>
-static hipError_t launch_b(const GemvArgs &a, hipStream_t st) {
+static hipError_t launch_b(const GemvArgs &a, const Q80GemvPlan &p, hipStream_t st) {
     GemvDev d = to_dev(a);
-    if (use_stream(a)) return launch_stream_b<GS, B>(d, st);
+    if (p.kernel == Q80_KERNEL_STREAM) return launch_stream_b<GS, B>(d, p, st);
     d.tile_max = nullptr;
-    return launch_slab_b<GS, B>(d, a, st);
+    return launch_slab_b<GS, B>(d, p, st);
 }
 template <int GS>
-static hipError_t launch_gs(const GemvArgs &a, hipStream_t st) {
-    if (a.nb <= 1) return launch_b<GS, 1>(a, st);
-    if (a.nb <= 2) return launch_b<GS, 2>(a, st);
-    if (a.nb <= 4) return launch_b<GS, 4>(a, st);
-    return launch_b<GS, 8>(a, st);
+static hipError_t launch_gs(const GemvArgs &a, const Q80GemvPlan &p, hipStream_t st) {
+    if (p.gs != (uint32_t)GS) return hipErrorInvalidValue;
+    if (p.B == 1) return launch_b<GS, 1>(a, p, st);
+    if (p.B == 2) return launch_b<GS, 2>(a, p, st);
+    if (p.B == 4) return launch_b<GS, 4>(a, p, st);
+    return launch_b<GS, 8>(a, p, st);
 }
 
 }  // namespace
 
-hipError_t NANO_Q80_ENTRY(const GemvArgs &a, hipStream_t st) { return launch_gs<NANO_Q80_GS>(a, st); }
+hipError_t NANO_Q80_ENTRY(const GemvArgs &a, const Q80GemvPlan &p, hipStream_t st) { return launch_gs<NANO_Q80_GS>(a, p, st); }
 
 #if NANO_Q80_GS == 64
 bool qkv_attn_fused_q80_supports(const GemvArgs &ga, const AttnArgs &aa) { SlabPlan p; return fused_shape(ga, aa, p); }

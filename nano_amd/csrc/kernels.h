@@ -92,6 +92,24 @@ bool gemm_q4k_supports(const GemvArgs &a);                  // host predicate (s
 hipError_t launch_gemm_q4k(const GemvArgs &a, hipStream_t st);
 hipError_t launch_gemv_q80(const GemvArgs &a, hipStream_t st);      // gemv_q80.hip
 hipError_t launch_gemv_f32(const GemvArgs &a, hipStream_t st);      // gemv_f32.hip
+// The kernel launch_gemv_q80() runs for `a` (nb <= 8) -- gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, EARLY, WF, WFC> or
+// gemv_q80_stream_kernel<ROLE, GS, B, NV> (gemv_q80_impl.h) -- with its waves, rows per workgroup, workgroups and LDS bytes; the launchers
+// take every choice from here.  false: the arguments are refused -- malformed, a SwiGLU launch without its two matrices, several weight
+// tensors whose row counts are no multiples of 4, more than 4 work units per wave, or more LDS than a CU has (gemv_q80_fit_batch() tells
+// the router how many sequences fit).
+constexpr uint32_t GEMV_Q80_LDS_MAX = 160 * 1024;
+enum : uint32_t { Q80_KERNEL_NONE = 0, Q80_KERNEL_SLAB = 1, Q80_KERNEL_STREAM = 2 };
+// the special forms of the slab kernel: EARLY (the first unit of each wave before the activation is quantized), WF (in-wave fold of
+// one-chunk rows), WFC2..4 (in-wave fold of the 2..4 chunks of a residual row)
+enum : uint32_t { Q80_VAR_PLAIN = 0, Q80_VAR_EARLY = 1, Q80_VAR_WF = 2, Q80_VAR_WFC2 = 3, Q80_VAR_WFC3 = 4, Q80_VAR_WFC4 = 5 };
+struct Q80GemvPlan {
+    uint32_t kernel, role, gs, B, nv, upw;      // nv, upw: the NV and UPW template values (STREAM: upw = 0)
+    uint32_t rw, nw, grid, lds_bytes;           // rows per workgroup (STREAM: the 16 rows of a wave's tile), waves, workgroups, dynamic LDS
+    uint32_t variant, pre;                      // Q80_VAR_*; pre: the activation arrives quantized (F_PRE)
+    uint32_t early, units, wg_c0, wg_c1;        // the launchers' device block: GemvDev::early, units, workgroups up to the end of segment 0 / 1
+};
+bool gemv_q80_plan(const GemvArgs &a, Q80GemvPlan *p);
+uint32_t gemv_q80_fit_batch(const GemvArgs &a);            // sequences per Q80 GEMV launch that fit in LDS (8 | 4 | 2 | 1; 0: none -- the shape is refused)
 // the gemv_f32_slab_kernel<ROLE, B, NV, UPW> launch_gemv_f32() runs for `a` (nb <= 8), its waves, workgroups and LDS bytes; the launcher
 // takes every choice from here.  false: the arguments are refused -- malformed, more than 4 units per wave, or more LDS than a CU has.
 constexpr uint32_t GEMV_F32_LDS_MAX = 160 * 1024;
@@ -146,6 +164,9 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
 // FP32: the slices route_projection() cuts a launch of a.nb sequences into -- per = sequences of every slice but the last, launches = their
 // number; false: the shape is refused (hipErrorInvalidValue before any launch)
 bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
+// Q80, the routes that end in the GEMV kernels (ROUTE_GEMV, ROUTE_GEMV_PREQ, ROUTE_GEMV_SLICED): the same question -- groups of 8 wherever 8
+// fit a CU's LDS (gemv_q80_fit_batch()), fewer per launch on long rows; false: not even one sequence fits, or the shape is refused
+bool route_q80_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
 uint32_t route_norm_order(const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);

@@ -257,6 +257,46 @@ extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     return 0;
 }
 
+// The Q80 launch route_projection() issues for a descriptor: route_kind() -- assuming the step's activation scratch is present, as in
+// nano_hip_op_fused_gemv below --, then for the routes that end in the Q80 GEMV kernels gemv_q80_plan() of the first slice and
+// route_q80_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
+// the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
+// out = {route, kernel, role, gs, B, nv, upw, rw, nw, grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}; the batched routes
+// (G6 / G7 / G2 / GC) report the route, one launch of nb sequences and zeros for the kernel fields.  takes = 0: the router refuses the
+// shape (hipErrorInvalidValue before any launch) and every other entry is 0.
+extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[16]) {
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    const NanoFusedGemvDesc &d = *dp;
+    if (d.quant != NANO_QUANT_Q80) { nano_hip_set_error_("not a Q80 launch"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    static int8_t scratch_flag[4];                  // stands for the scratch and the quantized rows: compared with null, never followed
+    GemvArgs a{};
+    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
+    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb; a.cus = cus ? cus : 256u;
+    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    a.norm_w = d.norm_w;
+    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    a.ordered = d.ordered ? 1u : 0u;
+    Q80Route r{};
+    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
+    r.gq = scratch_flag; r.gxs = reinterpret_cast<float *>(scratch_flag);
+    memset(out, 0, 16 * sizeof(uint32_t));
+    const RouteKind k = route_kind(r, a);
+    if (route_takes_fragments(k)) {
+        out[0] = (uint32_t)k; out[13] = 1u; out[14] = d.nb; out[15] = 1u;
+        return 0;
+    }
+    if (k == ROUTE_GEMV_PREQ) { a.xq_in = scratch_flag; a.xs_in = r.gxs; a.norm_w = nullptr; }      // (as route_projection() hands it on)
+    uint32_t per = 0, launches = 0;
+    Q80GemvPlan p;
+    if (!route_q80_slices(a, &per, &launches)) return 0;
+    a.nb = per;
+    if (!gemv_q80_plan(a, &p)) return 0;
+    const uint32_t v[16] = { (uint32_t)k, p.kernel, p.role, p.gs, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, p.variant, p.pre, launches, per, 1u };
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+
 // One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs.
 extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     int rc; if ((rc = begin(device))) return rc;

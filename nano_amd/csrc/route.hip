@@ -94,6 +94,31 @@ bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
     return true;
 }
 
+// Q80: every workgroup of a GEMV launch holds the quantized activations of all its sequences AND their product table in LDS, so long rows
+// take fewer sequences per launch (gemv_q80_fit_batch(): 8 wherever 8 fit -- the groups of 8 a batch beyond 8 has always run in).  Per
+// sequence nothing changes: the kernels are bit for bit per sequence whatever the capacity.
+bool route_q80_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
+    if (a.nb == 0) return false;
+    GemvArgs one = a; one.nb = a.nb < 8u ? a.nb : 8u;
+    const uint32_t fit = gemv_q80_fit_batch(one);
+    if (fit == 0) return false;
+    *per = a.nb < fit ? a.nb : fit;
+    *launches = (a.nb + fit - 1) / fit;
+    return true;
+}
+// the Q80 GEMV launches of a.nb sequences, cut where route_q80_slices() says so; a shape of which not even one sequence fits is refused
+// before any launch
+static hipError_t launch_q80_sliced(GemvArgs &a, hipStream_t st) {
+    uint32_t per = 0, launches = 0;
+    if (!route_q80_slices(a, &per, &launches)) return hipErrorInvalidValue;
+    if (launches == 1) return launch_gemv_q80(a, st);
+    for (uint32_t b0 = 0; b0 < a.nb; b0 += per) {
+        const hipError_t e = launch_gemv_q80(gemv_slice(a, b0, a.nb - b0 < per ? a.nb - b0 : per), st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     a.cus = (uint32_t)r.cus;
     const RouteKind k = route_kind(r, a);
@@ -147,24 +172,19 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     case ROUTE_GEMV_SLICED:
         // More sequences than a GEMV launch takes and a launch the GEMM does not take (row length / group size not a multiple of 4
         // groups, segment rows not multiples of 16, the LoRA o-branch addend): groups of 8 through the GEMV kernels.  Same arithmetic
-        // per sequence, the weights are read once per group.
-        for (uint32_t b0 = 0; b0 < a.nb; b0 += 8) {
-            GemvArgs s = gemv_slice(a, b0, a.nb - b0 < 8 ? a.nb - b0 : 8u);
-            const hipError_t e = launch_gemv(r.quant, s, st);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+        // per sequence, the weights are read once per group (of fewer than 8 where 8 do not fit a CU's LDS).
+        return launch_q80_sliced(a, st);
     case ROUTE_GEMV_PREQ: {
         // when the redundant quantization outweighs a launch (~3 us) the activations are quantized once (quant_rows_kernel) and the GEMV
         // reads them back
         const hipError_t e = launch_quant_rows(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st);
         if (e != hipSuccess) return e;
         a.xq_in = r.gq; a.xs_in = r.gxs; a.norm_w = nullptr;
-        return launch_gemv(r.quant, a, st);
+        return launch_q80_sliced(a, st);
     }
     case ROUTE_GEMV:
     default:
-        return launch_gemv(r.quant, a, st);
+        return launch_q80_sliced(a, st);
     }
 }
 

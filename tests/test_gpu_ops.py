@@ -21,8 +21,7 @@ def test_device_is_gfx950():
     assert info["arch"].startswith("gfx950"), info
 
 
-@pytest.mark.parametrize("gs", [32, 64, 128])
-@pytest.mark.parametrize("n", [128, 768, 1024, 3072])
+@pytest.mark.parametrize("n,gs", [(n, gs) for gs in (32, 64, 128) for n in (128, 768, 1024, 3072)] + [(768, 256), (1024, 256), (3072, 256)])
 def test_quantize_q80_bit_exact(oracle, gs, n):
     rng = np.random.default_rng(n + gs)
     x = (rng.standard_normal(n) * rng.uniform(0.01, 30)).astype(np.float32)
@@ -41,7 +40,7 @@ def test_quantize_q80_golden(gold_ops):
         assert np.array_equal(q, gold_ops[f"q80_quant_gs{gs}_q"]) and np.array_equal(bits(s), bits(gold_ops[f"q80_quant_gs{gs}_s"]))
 
 
-@pytest.mark.parametrize("n,d,gs", [(1024, 96, 64), (2048, 64, 64), (3072, 40, 128), (768, 33, 32), (128, 7, 32), (1408, 12, 64)])
+@pytest.mark.parametrize("n,d,gs", [(1024, 96, 64), (2048, 64, 64), (3072, 40, 128), (768, 33, 32), (128, 7, 32), (1408, 12, 64), (1024, 33, 256), (768, 12, 256)])
 def test_matmul_q80_bit_exact(oracle, n, d, gs):
     rng = np.random.default_rng(n * 7 + d)
     w = (0.02 * rng.standard_normal(d * n)).astype(np.float32)
@@ -53,7 +52,7 @@ def test_matmul_q80_bit_exact(oracle, n, d, gs):
     assert np.array_equal(bits(ref), bits(out)), float(np.abs(ref - out).max())
 
 
-@pytest.mark.parametrize("n,d,gs", [(1024, 20000, 64), (1024, 16391, 128), (512, 16384, 32), (2560, 17000, 64), (1408, 16400, 64)])
+@pytest.mark.parametrize("n,d,gs", [(1024, 20000, 64), (1024, 16391, 128), (512, 16384, 32), (2560, 17000, 64), (1408, 16400, 64), (768, 16391, 256)])
 def test_matmul_q80_tall_bit_exact(oracle, n, d, gs):
     """rows >= 16384 take the STREAM kernel (the classifier's path): same bit-exact bar."""
     rng = np.random.default_rng(n * 3 + d)
