@@ -439,6 +439,18 @@ int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * values, 32768 with SwiGLU; one sequence that does not fit a CU's LDS) and every other entry is 0.  Host arithmetic on the shape fields:
  * works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
 int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[16]);
+/* The Q4K launch the router issues for descriptor d (quant = NANO_QUANT_Q4K), likewise: out = {route, kernel, role, B, nv, ipt, d, loop,
+ * rounds, wg[3], rw, nthr, grid, lds_bytes, pre, quant_rows, quant_nthr, quant_nv, partials, launches, seqs_per_launch, takes}.  route: the
+ * router's choice with the step's scratch present.  The GEMV route: kernel 1 = gemv_q4k_slab_kernel<role, B, nv, ipt>, 2 =
+ * gemv_q4k_chunk_kernel<role, nv, d, loop, B> (whole 256-value blocks; `rounds` passes of the looping form, wg[s] workgroups on tensor s);
+ * nthr threads x grid workgroups of rw rows, lds_bytes of dynamic LDS; pre = 1: the activation reaches the kernel quantized; quant_rows = 1:
+ * a q4k_quant_rows_kernel<., quant_nv> launch of quant_nthr threads per sequence goes first (the chunk kernel's 2..8 sequences); partials:
+ * arg-max pairs per sequence the launch writes when asked (a launch of one STORE tensor is planned with the request, as the step's
+ * classifier makes it); the plan is that of the first of `launches` slices of seqs_per_launch sequences.  The GEMM route (9..64 tokens):
+ * the route, launches = 1, seqs_per_launch = nb, zeros for the kernel fields.  takes = 0: the shape is refused before any launch (several
+ * tensors whose rows are no multiples of 4 or more than 4 items per thread on the slab kernel; one sequence that does not fit a CU's LDS)
+ * and every other entry is 0.  Host arithmetic on the shape fields: works without a device, and no pointer of d is followed. */
+int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[24]);
 
 /* One device-resident copy of a model's parameter bytes per GPU from ONE host upload (replicate.hip; SURVEY 8e "broadcast(weights) at
  * load"): the bytes go to `root_device` over PCIe once and from there to the other devices over xGMI -- an RCCL broadcast (librccl.so

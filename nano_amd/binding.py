@@ -55,18 +55,25 @@ class NanoExactAttnDesc(C.Structure):
 ATTN_PLAN_FIELDS = ("mode", "lpr", "qv", "kvm", "npt", "w16", "paged", "kv_half", "nsplit", "xcd")
 
 
-# what nano_hip_f32_gemv_plan reports (nano_amd/csrc/kernels.h F32GemvPlan + route_f32_slices), and the kernel roles of gemv_common.h
+# what nano_hip_f32_gemv_plan reports (nano_amd/csrc/kernels.h F32GemvPlan + route_gemv_slices), and the kernel roles of gemv_common.h
 F32_PLAN_FIELDS = ("role", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "launches", "seqs_per_launch", "takes")
 F32_ROLES = ("generic", "norm_store", "resid", "resid_combine", "norm_swiglu")
 
 
-# what nano_hip_q80_gemv_plan reports (nano_amd/csrc/kernels.h Q80GemvPlan + route_kind + route_q80_slices): route is an index into
+# what nano_hip_q80_gemv_plan reports (nano_amd/csrc/kernels.h Q80GemvPlan + route_kind + route_gemv_slices): route is an index into
 # ROUTE_NAMES, kernel into Q80_KERNELS, role into Q80_ROLES, variant into Q80_VARIANTS
 Q80_PLAN_FIELDS = ("route", "kernel", "role", "gs", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "variant", "pre", "launches",
                    "seqs_per_launch", "takes")
 Q80_ROLES = F32_ROLES
 Q80_KERNELS = ("none", "slab", "stream")
 Q80_VARIANTS = ("plain", "early", "wf", "wfc2", "wfc3", "wfc4")
+
+
+# what nano_hip_q4k_gemv_plan reports (nano_amd/csrc/kernels.h Q4kGemvPlan + route_kind + route_gemv_slices): route is an index into
+# ROUTE_NAMES, kernel into Q4K_KERNELS, role into Q80_ROLES
+Q4K_PLAN_FIELDS = ("route", "kernel", "role", "B", "nv", "ipt", "d", "loop", "rounds", "wg0", "wg1", "wg2", "rw", "nthr", "grid", "lds_bytes",
+                   "pre", "quant_rows", "quant_nthr", "quant_nv", "partials", "launches", "seqs_per_launch", "takes")
+Q4K_KERNELS = ("none", "slab", "chunk")
 
 
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
@@ -156,6 +163,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_f32_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q80_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_q4k_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_fork", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32])
@@ -538,6 +546,24 @@ def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=
     out = (C.c_uint32 * 16)()
     check(lib().nano_hip_q80_gemv_plan(C.byref(d), cus, out))
     return dict(zip(Q80_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
+    """The Q4K launch the router issues for a fused-gemv shape (nano_hip_q4k_gemv_plan; needs no GPU).  rows: the row count of each
+    weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
+    Returns a dict of Q4K_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
+    d = NanoFusedGemvDesc()
+    d.quant, d.kind, d.n, d.nb, d.nseg = 0x42, kind, n, nb, len(rows)
+    for i, r in enumerate(rows):
+        d.rows[i] = r
+    if norm:
+        d.norm_w = _FLAG.ctypes.data
+    if attn is not None:
+        d.attn_part = _FLAG.ctypes.data
+        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
+    out = (C.c_uint32 * 24)()
+    check(lib().nano_hip_q4k_gemv_plan(C.byref(d), cus, out))
+    return dict(zip(Q4K_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, resid=None, attn=None, use_gemm=False, ordered=False,

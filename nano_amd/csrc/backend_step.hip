@@ -40,9 +40,10 @@ static GemvArgs classifier_args(const NanoHipModel *m, uint32_t nb, float *dst) 
 
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out, float *dst) {
     GemvArgs a = classifier_args(m, nb, dst ? dst : m->logits);
-    a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes;           // (what route_projection() will set: the partial count must match the launch)
+    a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes; a.cus = (uint32_t)m->cus;      // (what route_projection() will set: the partial count must match the launch)
+    uint32_t per = 0, launches = 0;
     if (ntiles_out && nb <= 8 && !route_takes_fragments(kind_of(m, a)) &&
-        (m->d.quant_type != NANO_QUANT_Q4K || nb <= (nb > 1 ? gemv_q4k_fit_batch(a) : 1u))) {      // per-tile arg-max partials for the sampler (Q4K: not for sliced launches)
+        (m->d.quant_type != NANO_QUANT_Q4K || (route_gemv_slices(m->d.quant_type, a, &per, &launches) && launches == 1))) {      // per-tile arg-max partials for the sampler (Q4K: not for sliced launches)
         a.tile_max = m->tile_max;
         *ntiles_out = gemv_tiles(m->d.quant_type, a);
     }
@@ -250,7 +251,8 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
     bool probe_ext = m->probe_cls && d.quant_type == NANO_QUANT_Q80 && nb <= 8 && d.vocab_size >= 16384 && !route_takes_fragments(kind_of(m, classifier_args(m, nb, m->logits)));
     if (m->probe_cls && d.quant_type == NANO_QUANT_Q4K && nb == 1 && d.vocab_size >= 65536) {      // gemv_q4k_chunk.hip's looping launch
         GemvArgs ca = classifier_args(m, nb, m->logits);
-        probe_ext = gemv_q4k_chunk_loops(ca);
+        Q4kGemvPlan cp;
+        probe_ext = gemv_q4k_plan(ca, &cp) && cp.kernel == Q4K_KERNEL_CHUNK && cp.loop;
     }
     if (probe_ext) { g_q80_probe_start = m->ev0; g_q80_probe_stop = m->ev1; }
     else if (m->probe_cls && (e = hipEventRecord(m->ev0, m->st)) != hipSuccess) return e;

@@ -15,7 +15,7 @@ hipError_t launch_gemv(uint32_t quant, GemvArgs &a, hipStream_t st) {
 // 0 = none written, the arg-max kernel scans the logits)
 uint32_t gemv_tiles(uint32_t quant, const GemvArgs &a) {
     if (quant == 0x80u) return gemv_q80_partials(a);
-    if (quant == 0x42u) return gemv_q4k_partials(a);
+    if (quant == 0x42u) { Q4kGemvPlan p; return gemv_q4k_plan(a, &p) ? p.partials : 0u; }
     return 0;
 }
 

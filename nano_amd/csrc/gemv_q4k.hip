@@ -21,6 +21,7 @@
 #include <float.h>
 
 #include "gemv_q4k_impl.h"
+#include "gemv_q4k_host.h"
 
 namespace nano {
 
@@ -240,14 +241,31 @@ __global__ __launch_bounds__(1024) void gemv_q4k_slab_kernel(const GemvDev a) {
     NANO_STAMP_END(a.stamps, 6);
 }
 
-struct Q4kPlan { uint32_t rw, nthr, ipt, nv; };
-static Q4kPlan plan_q4k(const GemvArgs &a, int B) {
+template <int ROLE, int B, int NV, int IPT>
+static hipError_t launch_q4k_t(const GemvDev &d, const Q4kGemvPlan &p, hipStream_t st) {
+    auto kern = &gemv_q4k_slab_kernel<ROLE, B, NV, IPT>;
+    if (p.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), p.lds_bytes, st, d);
+    return hipGetLastError();
+}
+// the instantiations: every (NV, IPT) of {0, 1, 2, 4} x {1, 2, 4} with B * NV <= 8 (tests/test_q4k_gemv_plan.py restates the set)
+template <int ROLE, int B>
+static hipError_t launch_q4k_r(const GemvDev &d, const Q4kGemvPlan &p, hipStream_t st) {
+#define Q4K_GO(NV_, IPT_) do { if constexpr (B * NV_ <= 8) if (p.nv == NV_ && p.ipt == IPT_) return launch_q4k_t<ROLE, B, NV_, IPT_>(d, p, st); } while (0)
+#define Q4K_NV(NV_) do { Q4K_GO(NV_, 1); Q4K_GO(NV_, 2); Q4K_GO(NV_, 4); } while (0)
+    Q4K_NV(0); Q4K_NV(1); Q4K_NV(2); Q4K_NV(4);
+    return hipErrorInvalidValue;
+#undef Q4K_NV
+#undef Q4K_GO
+}
+}  // namespace
+
+Q4kSlabPlan plan_q4k(const GemvArgs &a, int B) {
     const uint32_t GT = ((a.n + 255) / 256) * 8, nmat = a.epi == GEMV_EPI_SWIGLU ? 2 : 1;
     const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
     uint32_t align = 0;
     if (nseg > 1) for (uint32_t s = 0; s < nseg; s++) align |= a.seg[s].rows;
-    uint32_t rows = 0;
-    if (a.epi == GEMV_EPI_SWIGLU) rows = a.seg[0].rows; else for (uint32_t s = 0; s < a.nseg; s++) rows += a.seg[s].rows;
+    const uint32_t rows = gemv_total_rows(a);
     // ~512 items (8 KB of nibbles) per workgroup, >= 128 workgroups; tall matrices: up to 2048 items
     uint32_t rw = 4;
     // Every workgroup quantizes the whole activation before its first product, so large matrices (Qwen3-4B's layers, >= 8 M
@@ -268,108 +286,120 @@ static Q4kPlan plan_q4k(const GemvArgs &a, int B) {
         if (nthr < want) nthr = want;
         if (nthr < rw * (uint32_t)B) nthr = ((rw * (uint32_t)B + 63) / 64) * 64;
         const uint32_t ipt = (items + nthr - 1) / nthr;
-        if (ipt <= 4 || rw <= 4) return Q4kPlan{rw, nthr, ipt, (a.n + 4 * nthr - 1) / (4 * nthr)};   // the kernel is instantiated for <= 4 items per thread
+        if (ipt <= 4 || rw <= 4) return Q4kSlabPlan{rw, nthr, ipt, (a.n + 4 * nthr - 1) / (4 * nthr)};   // the kernel is instantiated for <= 4 items per thread
     }
 }
 
+
 // dynamic LDS of a launch with capacity B: quantized groups, the activations, block / sequence scratch, combine weights, products
-static size_t q4k_lds_bytes(uint32_t n, uint32_t epi, bool combine, uint32_t attn_n_head, uint32_t rw, uint32_t B) {
+size_t q4k_lds_bytes(uint32_t n, uint32_t epi, bool combine, uint32_t attn_n_head, uint32_t rw, uint32_t B) {
     const uint32_t nmat = epi == GEMV_EPI_SWIGLU ? 2 : 1;
     const size_t n4 = (n + 3) & ~3u, bpl = (n + 255) / 256, GT = bpl * 8;
     return (size_t)B * GT * sizeof(XGroup) + (B * n4 + B * bpl * 16 + B * 16 + (combine ? (size_t)B * attn_n_head * 8 : 0) + (size_t)B * nmat * rw * (GT + 4)) * 4 + 16;
 }
 
-template <int ROLE, int B, int NV, int IPT>
-static hipError_t launch_q4k_t(const GemvDev &d, const Q4kPlan &p, uint32_t rows, hipStream_t st) {
-    const size_t lds = q4k_lds_bytes(d.n, d.epi, (d.flags & F_COMBINE) != 0, d.attn_n_head, p.rw, B);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;                 // gemv_q4k_fit_batch() tells the caller how many sequences fit
-    auto kern = &gemv_q4k_slab_kernel<ROLE, B, NV, IPT>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    GemvDev dd = d; dd.nthr = p.nthr;
-    { const uint32_t GT = ((d.n + 255) / 256) * 8; dd.magic_nchunk = (uint32_t)(((1ull << 32) + GT - 1) / GT); dd.log2_tiles = 0; while ((1u << dd.log2_tiles) < p.rw) dd.log2_tiles++;
-      dd.units = ((p.rw * GT) % 64u == 0u && p.nthr % 64u == 0u) ? 1u : 0u; }   // kernel: item -> (row, group), thread -> (sequence, row)
-    hipLaunchKernelGGL(kern, dim3((rows + p.rw - 1) / p.rw), dim3(p.nthr), lds, st, dd);
-    return hipGetLastError();
+// Sequences per launch of this file's kernel that fit the 160 KB of LDS (every workgroup holds the whole quantized activation of each
+// sequence): 8 for Qwen3-0.6B's row lengths, 2 for Qwen3-4B's hidden size 9728.  The router slices larger steps (route.hip).
+uint32_t gemv_q4k_fit_batch(const GemvArgs &a) {
+    for (uint32_t c = 8; c > 1; c >>= 1)
+        if (q4k_lds_bytes(a.n, a.epi, a.attn_part != nullptr, a.attn_n_head, plan_q4k(a, (int)c).rw, c) <= GEMV_Q4K_LDS_MAX) return c;
+    GemvArgs one = a; one.nb = 1;
+    return gemv_q4k_plan(one, nullptr) ? 1u : 0u;
 }
-template <int ROLE, int B>
-static hipError_t launch_q4k_r(const GemvDev &d, const Q4kPlan &p, uint32_t rows, hipStream_t st) {
-    if (p.ipt > 4) return hipErrorInvalidValue;
-#define Q4K_GO(NV_, IPT_) do { if constexpr (B * NV_ <= 8) return launch_q4k_t<ROLE, B, NV_, IPT_>(d, p, rows, st); } while (0)
-    int nv = p.nv <= 1 ? 1 : p.nv <= 2 ? 2 : p.nv <= 4 ? 4 : 0;
-    const int ipt = p.ipt <= 1 ? 1 : p.ipt <= 2 ? 2 : 4;
-    if (B * nv > 8) nv = 0;
-    if (nv == 1) { if (ipt == 1) Q4K_GO(1, 1); if (ipt == 2) Q4K_GO(1, 2); Q4K_GO(1, 4); }
-    if (nv == 2) { if (ipt == 1) Q4K_GO(2, 1); if (ipt == 2) Q4K_GO(2, 2); Q4K_GO(2, 4); }
-    if (nv == 4) { if (ipt == 1) Q4K_GO(4, 1); if (ipt == 2) Q4K_GO(4, 2); Q4K_GO(4, 4); }
-    if (ipt == 1) Q4K_GO(0, 1);
-    if (ipt == 2) Q4K_GO(0, 2);
-    Q4K_GO(0, 4);
-    return hipErrorInvalidValue;
-#undef Q4K_GO
+
+// the role kernel of a one-sequence launch with prologue flags f (gemv_common.h), else the generic one
+static uint32_t q4k_role(uint32_t f, uint32_t epi) {
+    if (f == F_NORM && epi == GEMV_EPI_STORE) return R_NORM_STORE;
+    if (f == 0 && epi == GEMV_EPI_RESID) return R_RESID;
+    if (f == F_COMBINE && epi == GEMV_EPI_RESID) return R_RESID_COMBINE;
+    if (f == F_NORM && epi == GEMV_EPI_SWIGLU) return R_NORM_SWIGLU;
+    return R_GENERIC;
 }
-}  // namespace
-// (max, row) arg-max partials a STORE launch with tile_max writes per sequence: one per workgroup of a one-segment launch
-// (the classifier); 0 = none, the arg-max kernel scans the logits
+
+// THE planner: which kernel takes the launch, and every template value and launch dimension of it.
+// One sequence: the chunk kernel wherever it takes the shape (whole blocks: gemv_q4k_chunk.hip).
 // 2 .. 8 sequences: which kernel takes the launch.  The chunk kernel's several-sequence form pays an extra launch (the quantizer) and
 // wins where the weights are what the step moves or where this file's kernel cannot hold the sequences in LDS; measured on one box
 // (round 5, ms per step, this file's kernel -> the chunk form): Qwen3-4B 2 / 4 / 8 sequences 3.96 -> 2.13, 6.85 -> 2.60, 13.46 -> 3.54
 // (its rows fit one or two sequences per launch here: no weight sharing); Qwen3-0.6B 0.89 -> 1.18, 1.13 -> 1.30, 1.73 -> 1.49.
-bool gemv_q4k_chunk_takes(const GemvArgs &a) {
-    if (a.nb <= 1) return gemv_q4k_chunk_supports(a);
-    if (a.nb > 8 || !gemv_q4k_chunk_supports(a)) return false;
-    return a.nb >= 5u || route_is_wide(a) || gemv_q4k_fit_batch(a) < a.nb;
+// The several-sequence chunk form needs the caller's scratch for the staged groups (GemvArgs::q4_scratch) and a one-sequence launch of
+// the same matrix that is a chunk launch too (its plan gives the quantizer its thread count); it writes no arg-max partials (the arg-max
+// kernel scans the logits).
+bool gemv_q4k_plan(const GemvArgs &a, Q4kGemvPlan *out) {
+    if (a.nb == 0 || a.nb > 8) return false;
+    Q4kGemvPlan p{};
+    p.B = q4k_capacity(a.nb);
+    p.pre = (a.x4_in || a.xq_in) ? 1u : 0u;
+    const uint32_t f = (a.norm_w ? F_NORM : 0u) | (p.pre ? F_PRE : 0u) | (a.attn_part ? F_COMBINE : 0u);
+    const bool wants_partials = a.tile_max && a.epi == GEMV_EPI_STORE && a.nseg == 1 && !a.seg[0].out_pstride;
+    ChunkPlan c, c1;
+    bool chunk = plan_chunk(a, c);
+    if (chunk && a.nb > 1) {
+        GemvArgs one = a; one.nb = 1;
+        chunk = a.q4_scratch && (size_t)a.nb * (a.n >> 5) * sizeof(XGroup) <= a.q4_scratch_bytes && plan_chunk(one, c1) &&
+                (a.nb >= 5u || route_is_wide(a) || gemv_q4k_fit_batch(a) < a.nb);
+    }
+    if (chunk) {
+        p.kernel = Q4K_KERNEL_CHUNK;
+        p.rw = c.rw; p.nthr = c.nthr; p.d = c.d; p.loop = c.loop; p.rounds = c.rounds; p.grid = c.grid; p.lds_bytes = (uint32_t)c.lds;
+        for (int s = 0; s < 3; s++) p.wg[s] = c.wg[s];
+        p.nv = c.nv <= 1 ? 1u : c.nv <= 2 ? 2u : 4u;
+        if (a.nb > 1) { p.quant_rows = 1; p.quant_nthr = c1.nthr; p.quant_nv = c1.nv <= 1 ? 1u : c1.nv <= 2 ? 2u : 4u; }
+        else {
+            p.role = q4k_role(f, a.epi);
+            if (wants_partials) p.partials = p.grid;
+        }
+    } else {
+        if (a.n % 4 || a.nseg == 0 || a.nseg > 3) return false;
+        if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd % 4)) return false;
+        if (a.epi != GEMV_EPI_SWIGLU && a.nseg > 1)
+            for (uint32_t s = 0; s < a.nseg; s++) if (a.seg[s].rows % 4) return false;
+        const Q4kSlabPlan s = plan_q4k(a, (int)p.B);
+        if (s.ipt > 4) return false;
+        p.kernel = Q4K_KERNEL_SLAB;
+        p.rw = s.rw; p.nthr = s.nthr;
+        p.ipt = s.ipt <= 1 ? 1u : s.ipt <= 2 ? 2u : 4u;
+        p.nv = s.nv <= 1 ? 1u : s.nv <= 2 ? 2u : s.nv <= 4 ? 4u : 0u;
+        if (p.B * p.nv > 8) p.nv = 0;
+        p.grid = (gemv_total_rows(a) + s.rw - 1) / s.rw;
+        const size_t lds = q4k_lds_bytes(a.n, a.epi, a.attn_part != nullptr, a.attn_n_head, s.rw, p.B);
+        if (lds > GEMV_Q4K_LDS_MAX) return false;
+        p.lds_bytes = (uint32_t)lds;
+        const uint32_t GT = ((a.n + 255) / 256) * 8;
+        if (p.B == 1) p.role = q4k_role(f, a.epi);
+        if (p.role == R_NORM_SWIGLU && ((s.rw * GT) % 64u || s.nthr % 64u)) p.role = R_GENERIC;      // whole waves per matrix only (the kernel's issue_item)
+        if (wants_partials) p.partials = p.grid;
+    }
+    if (out) *out = p;
+    return true;
 }
 
-uint32_t gemv_q4k_partials(const GemvArgs &a) {
-    if (a.nb == 1 && gemv_q4k_chunk_supports(a)) return gemv_q4k_chunk_partials(a);
-    if (a.nb > 1 && gemv_q4k_chunk_takes(a)) return 0;                 // (the several-sequence chunk launch writes no partials: the arg-max kernel scans the logits)
-    if (!a.tile_max || a.epi != GEMV_EPI_STORE || a.nseg != 1 || a.nb == 0 || a.nb > 8 || a.seg[0].out_pstride) return 0;
-    const int B = a.nb <= 1 ? 1 : a.nb <= 2 ? 2 : a.nb <= 4 ? 4 : 8;
-    const Q4kPlan p = plan_q4k(a, B);
-    return (a.seg[0].rows + p.rw - 1) / p.rw;
-}
-namespace {
-template <int B>
-static hipError_t launch_q4k_b(const GemvArgs &a, hipStream_t st) {
+hipError_t launch_q4k_slab(const GemvArgs &a, const Q4kGemvPlan &p, hipStream_t st) {
     GemvDev d = to_dev(a);
     if (a.x4_in) { d.flags |= F_PRE; d.xq_in = reinterpret_cast<const int8_t *>(a.x4_in); }
-    const Q4kPlan p = plan_q4k(a, B);
-    d.rw = p.rw;
-    uint32_t rows = 0;
-    if (a.epi == GEMV_EPI_SWIGLU) rows = a.seg[0].rows; else for (uint32_t s = 0; s < a.nseg; s++) rows += a.seg[s].rows;
-    d.ntiles = gemv_q4k_partials(a);                                // arg-max partials: one per workgroup (0: none)
-    if (!d.ntiles || d.ntiles != (rows + p.rw - 1) / p.rw) { d.tile_max = nullptr; d.ntiles = 0; }
-    if constexpr (B == 1) {
-        const uint32_t f = d.flags;
-        if (f == F_NORM && d.epi == GEMV_EPI_STORE) return launch_q4k_r<R_NORM_STORE, B>(d, p, rows, st);
-        if (f == 0 && d.epi == GEMV_EPI_RESID) return launch_q4k_r<R_RESID, B>(d, p, rows, st);
-        if (f == F_COMBINE && d.epi == GEMV_EPI_RESID) return launch_q4k_r<R_RESID_COMBINE, B>(d, p, rows, st);
-        const uint32_t GT = ((d.n + 255) / 256) * 8;
-        if (f == F_NORM && d.epi == GEMV_EPI_SWIGLU && (p.rw * GT) % 64u == 0u && p.nthr % 64u == 0u) return launch_q4k_r<R_NORM_SWIGLU, B>(d, p, rows, st);
+    d.rw = p.rw; d.nthr = p.nthr;
+    const uint32_t GT = ((a.n + 255) / 256) * 8;                        // kernel: item -> (row, group), thread -> (sequence, row)
+    d.magic_nchunk = (uint32_t)(((1ull << 32) + GT - 1) / GT);
+    d.log2_tiles = 0; while ((1u << d.log2_tiles) < p.rw) d.log2_tiles++;
+    d.units = ((p.rw * GT) % 64u == 0u && p.nthr % 64u == 0u) ? 1u : 0u;
+    d.ntiles = p.partials;                                              // arg-max partials: one per workgroup (0: none)
+    if (!p.partials) d.tile_max = nullptr;
+    if (p.B == 1) {
+        if (p.role == R_NORM_STORE) return launch_q4k_r<R_NORM_STORE, 1>(d, p, st);
+        if (p.role == R_RESID) return launch_q4k_r<R_RESID, 1>(d, p, st);
+        if (p.role == R_RESID_COMBINE) return launch_q4k_r<R_RESID_COMBINE, 1>(d, p, st);
+        if (p.role == R_NORM_SWIGLU) return launch_q4k_r<R_NORM_SWIGLU, 1>(d, p, st);
+        return launch_q4k_r<R_GENERIC, 1>(d, p, st);
     }
-    return launch_q4k_r<R_GENERIC, B>(d, p, rows, st);
+    if (p.B == 2) return launch_q4k_r<R_GENERIC, 2>(d, p, st);
+    if (p.B == 4) return launch_q4k_r<R_GENERIC, 4>(d, p, st);
+    return launch_q4k_r<R_GENERIC, 8>(d, p, st);
 }
 
-}  // namespace
-
-// Sequences per launch that fit the 160 KB of LDS (every workgroup holds the whole quantized activation of each sequence):
-// 8 for Qwen3-0.6B's row lengths, 2 for Qwen3-4B's hidden size 9728.  The router slices larger steps (route.hip route_projection()).
-uint32_t gemv_q4k_fit_batch(const GemvArgs &a) {
-    for (uint32_t c = 8; c > 1; c >>= 1)
-        if (q4k_lds_bytes(a.n, a.epi, a.attn_part != nullptr, a.attn_n_head, plan_q4k(a, (int)c).rw, c) <= 160 * 1024) return c;
-    return 1;
-}
-
-hipError_t launch_gemv_q4k(GemvArgs &a, hipStream_t st) {
-    if (a.nb >= 1 && a.nb <= 8 && gemv_q4k_chunk_takes(a)) return launch_gemv_q4k_chunk(a, st);     // whole blocks: gemv_q4k_chunk.hip (2 .. 8 sequences: with scratch)
-    if (a.nb == 0 || a.nb > 8 || a.n % 4 || a.nseg == 0 || a.nseg > 3) return hipErrorInvalidValue;
-    if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd % 4)) return hipErrorInvalidValue;
-    if (a.epi != GEMV_EPI_SWIGLU && a.nseg > 1)
-        for (uint32_t s = 0; s < a.nseg; s++) if (a.seg[s].rows % 4) return hipErrorInvalidValue;
-    if (a.nb <= 1) return launch_q4k_b<1>(a, st);
-    if (a.nb <= 2) return launch_q4k_b<2>(a, st);
-    if (a.nb <= 4) return launch_q4k_b<4>(a, st);
-    return launch_q4k_b<8>(a, st);
+hipError_t launch_gemv_q4k(const GemvArgs &a, hipStream_t st) {
+    Q4kGemvPlan p;
+    if (!gemv_q4k_plan(a, &p)) return hipErrorInvalidValue;
+    return p.kernel == Q4K_KERNEL_CHUNK ? launch_q4k_chunk(a, p, st) : launch_q4k_slab(a, p, st);
 }
 
 }  // namespace nano

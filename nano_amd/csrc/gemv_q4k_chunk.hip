@@ -28,6 +28,7 @@
 // the staged groups (XGroup: packed nibbles, sq, bq, nibble sum) in global memory; the projection workgroups copy them to LDS, read every
 // weight byte once and multiply it against all NB sequences -- per wave-load the weight-only half once, the activation half per sequence.
 #include "gemv_q4k_impl.h"
+#include "gemv_q4k_host.h"
 #include <hip/hip_ext.h>
 
 namespace nano {
@@ -112,23 +113,22 @@ __global__ __launch_bounds__(1024) void q4k_quant_rows_kernel(const GemvDev a, X
     for (uint32_t i = tid; i < GT * 2u; i += nthr) dst[i] = src[i];
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------------------
-struct ChunkPlan { uint32_t rw, nthr, d, loop, rounds, nv, wg[3], grid; size_t lds; };
+}  // namespace
 
-size_t chunk_lds_bytes(uint32_t n, bool combine, uint32_t attn_n_head, uint32_t nmat, uint32_t rw, uint32_t nw, uint32_t sl, uint32_t nbq = 1) {
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+static size_t chunk_lds_bytes(uint32_t n, bool combine, uint32_t attn_n_head, uint32_t nmat, uint32_t rw, uint32_t nw, uint32_t sl, uint32_t nbq = 1) {
     const size_t bpl = n >> 8, GT = bpl * 8;
     return nbq * GT * sizeof(XGroup) + (16 + (combine ? (size_t)attn_n_head * 8 : 0) + (size_t)nw * sl * 64 + 2 * (size_t)nw + (size_t)nmat * nbq * rw * (bpl | 1)) * 4 + 16;
 }
 
-bool plan_chunk(const GemvArgs &a, ChunkPlan &p, uint32_t force_nw = 0) {      // force_nw: the fused launch's 256 threads (same bits: see q4k_fused_shape)
+bool plan_chunk(const GemvArgs &a, ChunkPlan &p, uint32_t force_nw) {      // force_nw: the fused launch's 256 threads (same bits: see q4k_fused_shape)
     if (a.nb == 0 || a.nb > 8 || a.n == 0 || (a.n & 255u) || a.n > 16384u || a.nseg == 0 || a.nseg > 3) return false;
     if (a.attn_part && (a.norm_w || a.attn_nsplit > 8 || a.attn_hd % 4)) return false;
     const uint32_t nbq = a.nb <= 1 ? 1u : a.nb <= 2 ? 2u : a.nb <= 4 ? 4u : 8u;     // the kernel's NB (sequences beyond a.nb are skipped)
     if (nbq > 1 && (a.x4_in || a.xq_in)) return false;                              // (caller-quantized activations: one sequence)
     const bool sw = a.epi == GEMV_EPI_SWIGLU;
     const uint32_t nmat = sw ? 2u : 1u, nseg = sw ? 1u : a.nseg, bpl = a.n >> 8;
-    uint32_t rows = 0;
-    for (uint32_t s = 0; s < nseg; s++) rows += a.seg[s].rows;
+    const uint32_t rows = gemv_total_rows(a);
     if (rows == 0) return false;
     constexpr uint32_t want_div = 4u;
     uint32_t want = ((a.n / want_div + 63) / 64) * 64;                 // the block quantizer: four elements per thread and pass
@@ -145,7 +145,7 @@ bool plan_chunk(const GemvArgs &a, ChunkPlan &p, uint32_t force_nw = 0) {      /
     uint32_t best = 0, best_cost = ~0u;
     for (uint32_t c = 1; c <= 1024; c++) {
         if ((uint64_t)c * bpl >= 65536u) break;                          // the kernel's ceil(nblk / 6) and b / bpl by multiplication
-        if (chunk_lds_bytes(a.n, nbq == 1 && a.attn_part != nullptr, a.attn_n_head, nmat, c, 16, 8, nbq) * k > 150u * 1024u) break;
+        if (chunk_lds_bytes(a.n, nbq == 1 && a.attn_part != nullptr, a.attn_n_head, nmat, c, 16, 8, nbq) * k > GEMV_Q4K_CHUNK_SEARCH_LDS) break;
         uint32_t wgs = 0;
         for (uint32_t s = 0; s < nseg; s++) wgs += (a.seg[s].rows + c - 1) / c;
         // rows of the busiest CU slot; several rounds of workgroups pay the prologue (activation, norm, block quantizer) once per round
@@ -174,51 +174,50 @@ bool plan_chunk(const GemvArgs &a, ChunkPlan &p, uint32_t force_nw = 0) {      /
     for (uint32_t s = 0; s < 3; s++) { p.wg[s] = s < nseg ? (a.seg[s].rows + best - 1) / best : 0; p.grid += p.wg[s]; }
     p.lds = chunk_lds_bytes(a.n, nbq == 1 && a.attn_part != nullptr, a.attn_n_head, nmat, best, nw, nbq > 1 ? nbq : p.loop ? 1u : p.d, nbq);
     if (nbq > 1) p.nv = 1;                                              // (nothing staged in registers)
-    return p.lds <= 160u * 1024u;
+    return p.lds <= GEMV_Q4K_LDS_MAX;
 }
 
-template <int ROLE, int NV, int D, bool LOOP>
-hipError_t launch_chunk_t(const GemvDev &d, const ChunkPlan &p, hipStream_t st) {
-    auto kern = &gemv_q4k_chunk_kernel<ROLE, NV, D, LOOP>;
-    if (p.lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+namespace {
+
+// the device block of a chunk launch (kernel: block -> (row, block of the row) by multiplication, workgroup -> tensor); no arg-max partials
+GemvDev chunk_dev(const GemvArgs &a, uint32_t rw, uint32_t nthr, uint32_t rounds, const uint32_t wg[3]) {
+    GemvDev d = to_dev(a);
+    const uint32_t bpl = a.n >> 8, nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
+    d.rw = rw; d.nthr = nthr; d.units = rounds;
+    d.magic_nchunk = (uint32_t)(((1ull << 32) + bpl - 1) / bpl);
+    d.wg_c0 = nseg > 1 ? wg[0] : 0xffffffffu;
+    d.wg_c1 = nseg > 2 ? wg[0] + wg[1] : 0xffffffffu;
+    d.tile_max = nullptr; d.ntiles = 0;
+    return d;
+}
+
+// NB = 1: the role kernels; NB = 2 | 4 | 8: generic role, activations from q4k_quant_rows_kernel
+template <int ROLE, int NV, int D, bool LOOP, int NB>
+hipError_t launch_chunk_t(const GemvDev &d, const Q4kGemvPlan &p, hipStream_t st) {
+    auto kern = &gemv_q4k_chunk_kernel<ROLE, NV, D, LOOP, NB>;
+    if (p.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     // measurement (bench.py's `best_kernel`): the classifier launch between the kernel's own start / stop timestamps, as the Q80 STREAM
-    // launch is timed (gemv_q80_impl.h); the backend arms the pair for the looping launch of one decode step only
-    hipEvent_t e0 = LOOP ? g_q80_probe_start : nullptr, e1 = LOOP ? g_q80_probe_stop : nullptr;
+    // launch is timed (gemv_q80_impl.h); the backend arms the pair for the looping launch of one decode step (one sequence) only
+    hipEvent_t e0 = (LOOP && NB == 1) ? g_q80_probe_start : nullptr, e1 = (LOOP && NB == 1) ? g_q80_probe_stop : nullptr;
     if (e0 && e1) {
         g_q80_probe_start = g_q80_probe_stop = nullptr;
-        hipExtLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), (uint32_t)p.lds, st, e0, e1, 0, d);
-    } else hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), p.lds, st, d);
+        hipExtLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), p.lds_bytes, st, e0, e1, 0, d);
+    } else hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), p.lds_bytes, st, d);
     return hipGetLastError();
 }
-template <int ROLE, int NV>
-hipError_t launch_chunk_d(const GemvDev &d, const ChunkPlan &p, hipStream_t st) {
-    if (p.loop) return launch_chunk_t<ROLE, NV, 8, true>(d, p, st);
-    if (p.d == 1) return launch_chunk_t<ROLE, NV, 1, false>(d, p, st);
-    if (p.d == 2) return launch_chunk_t<ROLE, NV, 2, false>(d, p, st);
-    if (p.d == 4) return launch_chunk_t<ROLE, NV, 4, false>(d, p, st);
-    return launch_chunk_t<ROLE, NV, 8, false>(d, p, st);
+template <int ROLE, int NV, int NB>
+hipError_t launch_chunk_d(const GemvDev &d, const Q4kGemvPlan &p, hipStream_t st) {
+    if (p.loop) return launch_chunk_t<ROLE, NV, 8, true, NB>(d, p, st);
+    if (p.d == 1) return launch_chunk_t<ROLE, NV, 1, false, NB>(d, p, st);
+    if (p.d == 2) return launch_chunk_t<ROLE, NV, 2, false, NB>(d, p, st);
+    if (p.d == 4) return launch_chunk_t<ROLE, NV, 4, false, NB>(d, p, st);
+    return launch_chunk_t<ROLE, NV, 8, false, NB>(d, p, st);
 }
 template <int ROLE>
-hipError_t launch_chunk_r(const GemvDev &d, const ChunkPlan &p, hipStream_t st) {
-    if (p.nv <= 1) return launch_chunk_d<ROLE, 1>(d, p, st);
-    if (p.nv <= 2) return launch_chunk_d<ROLE, 2>(d, p, st);
-    return launch_chunk_d<ROLE, 4>(d, p, st);
-}
-// 2 .. 8 sequences: generic role, activations from q4k_quant_rows_kernel
-template <int D, bool LOOP, int NB>
-hipError_t launch_chunk_nb_t(const GemvDev &d, const ChunkPlan &p, hipStream_t st) {
-    auto kern = &gemv_q4k_chunk_kernel<R_GENERIC, 1, D, LOOP, NB>;
-    if (p.lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nthr), p.lds, st, d);
-    return hipGetLastError();
-}
-template <int NB>
-hipError_t launch_chunk_nb(const GemvDev &d, const ChunkPlan &p, hipStream_t st) {
-    if (p.loop) return launch_chunk_nb_t<8, true, NB>(d, p, st);
-    if (p.d == 1) return launch_chunk_nb_t<1, false, NB>(d, p, st);
-    if (p.d == 2) return launch_chunk_nb_t<2, false, NB>(d, p, st);
-    if (p.d == 4) return launch_chunk_nb_t<4, false, NB>(d, p, st);
-    return launch_chunk_nb_t<8, false, NB>(d, p, st);
+hipError_t launch_chunk_r(const GemvDev &d, const Q4kGemvPlan &p, hipStream_t st) {
+    if (p.nv <= 1) return launch_chunk_d<ROLE, 1, 1>(d, p, st);
+    if (p.nv <= 2) return launch_chunk_d<ROLE, 2, 1>(d, p, st);
+    return launch_chunk_d<ROLE, 4, 1>(d, p, st);
 }
 template <int ROLE, int NV>
 hipError_t launch_quant_rows_t(const GemvDev &d, XGroup *out, uint32_t nb, size_t lds, hipStream_t st) {
@@ -235,67 +234,54 @@ hipError_t launch_quant_rows_r(const GemvDev &d, XGroup *out, uint32_t nb, size_
     if (d.flags == F_COMBINE) return launch_quant_rows_t<R_RESID_COMBINE, NV>(d, out, nb, lds, st);
     return launch_quant_rows_t<R_GENERIC, NV>(d, out, nb, lds, st);
 }
+// the quantizer launch with the threads and NV of the one-sequence chunk plan of the same matrix; refuses a missing or short scratch
+hipError_t launch_quant_rows_planned(const GemvArgs &a, uint32_t nthr, uint32_t nv, hipStream_t st) {
+    if (!a.q4_scratch || (size_t)a.nb * (a.n >> 5) * sizeof(XGroup) > a.q4_scratch_bytes) return hipErrorInvalidValue;
+    const uint32_t bpl = a.n >> 8, GT = bpl * 8u;
+    GemvDev q = to_dev(a);                                           // flags: norm / combine as the launch asks
+    q.nthr = nthr; q.tile_max = nullptr;
+    const size_t lds = (size_t)GT * sizeof(XGroup) + (16 + (a.attn_part ? (size_t)a.attn_n_head * 8 : 0)) * 4 + 16;
+    XGroup *xg = reinterpret_cast<XGroup *>(a.q4_scratch);
+    return nv <= 1 ? launch_quant_rows_r<1>(q, xg, a.nb, lds, st) : nv <= 2 ? launch_quant_rows_r<2>(q, xg, a.nb, lds, st) : launch_quant_rows_r<4>(q, xg, a.nb, lds, st);
+}
+// the one-sequence chunk plan behind a quantizer launch of 1 .. 64 sequences, where there is one
+bool quant_rows_plan(const GemvArgs &a, ChunkPlan &p1) {
+    GemvArgs one = a; one.nb = 1; one.tile_max = nullptr;
+    return a.nb >= 1 && a.nb <= NANO_MAX_BATCH && !a.x4_in && !a.xq_in && plan_chunk(one, p1);
+}
 
 }  // namespace
-
-// one sequence; 2 .. 8 sequences when the caller brings scratch for the staged groups (GemvArgs::q4_scratch) and the one-sequence launch of
-// the same matrix is a chunk launch too (its plan gives the quantizer its thread count)
-bool gemv_q4k_chunk_supports(const GemvArgs &a) {
-    ChunkPlan p;
-    if (a.nb <= 1) return plan_chunk(a, p);
-    GemvArgs one = a; one.nb = 1;
-    return a.q4_scratch && (size_t)a.nb * (a.n >> 5) * sizeof(XGroup) <= a.q4_scratch_bytes && plan_chunk(one, p) && plan_chunk(a, p);
-}
-bool gemv_q4k_chunk_loops(const GemvArgs &a) { ChunkPlan p; return a.nb == 1 && plan_chunk(a, p) && p.loop; }     // the persistent (classifier) variant
-// (max, row) arg-max partials a classifier launch writes: one per workgroup (0: none, the arg-max kernel scans the logits)
-uint32_t gemv_q4k_chunk_partials(const GemvArgs &a) {
-    ChunkPlan p;
-    if (a.nb != 1 || !a.tile_max || a.epi != GEMV_EPI_STORE || a.nseg != 1 || a.seg[0].out_pstride || !plan_chunk(a, p)) return 0;
-    return p.grid;
-}
 
 // The quantizer launch of a several-sequence projection (2 .. 8 sequences: the chunk kernel below; 9 .. 64: gemm_q4k.hip): one workgroup
 // per sequence running the prologue of the one-sequence chunk launch of the same matrix, the staged groups of sequence b left at
 // a.q4_scratch + b * n bytes.  _supports: that one-sequence launch is a chunk launch (its plan gives the quantizer its thread count).
-bool q4k_quant_rows_supports(const GemvArgs &a) {
-    ChunkPlan p1;
-    GemvArgs one = a; one.nb = 1; one.tile_max = nullptr;
-    return a.nb >= 1 && a.nb <= NANO_MAX_BATCH && !a.x4_in && !a.xq_in && plan_chunk(one, p1);
-}
+bool q4k_quant_rows_supports(const GemvArgs &a) { ChunkPlan p1; return quant_rows_plan(a, p1); }
 hipError_t launch_q4k_quant_rows(const GemvArgs &a, hipStream_t st) {
     ChunkPlan p1;
-    GemvArgs one = a; one.nb = 1; one.tile_max = nullptr;
-    if (!q4k_quant_rows_supports(a) || !plan_chunk(one, p1)) return hipErrorInvalidValue;
-    if (!a.q4_scratch || (size_t)a.nb * (a.n >> 5) * sizeof(XGroup) > a.q4_scratch_bytes) return hipErrorInvalidValue;
-    const uint32_t bpl = a.n >> 8, GT = bpl * 8u;
-    GemvDev q = to_dev(a);                                           // flags: norm / combine as the launch asks
-    q.nthr = p1.nthr; q.tile_max = nullptr;
-    const size_t lds = (size_t)GT * sizeof(XGroup) + (16 + (a.attn_part ? (size_t)a.attn_n_head * 8 : 0)) * 4 + 16;
-    XGroup *xg = reinterpret_cast<XGroup *>(a.q4_scratch);
-    return p1.nv <= 1 ? launch_quant_rows_r<1>(q, xg, a.nb, lds, st) : p1.nv <= 2 ? launch_quant_rows_r<2>(q, xg, a.nb, lds, st) : launch_quant_rows_r<4>(q, xg, a.nb, lds, st);
+    if (!quant_rows_plan(a, p1)) return hipErrorInvalidValue;
+    return launch_quant_rows_planned(a, p1.nthr, p1.nv, st);
 }
 
-// 2 .. 8 sequences: the quantizer launch, then the projection
-static hipError_t launch_gemv_q4k_chunk_batched(GemvArgs &a, hipStream_t st) {
-    if (!gemv_q4k_chunk_supports(a)) return hipErrorInvalidValue;
-    ChunkPlan p;
-    if (!plan_chunk(a, p)) return hipErrorInvalidValue;
-    const uint32_t bpl = a.n >> 8;
-    XGroup *xg = reinterpret_cast<XGroup *>(a.q4_scratch);
-    { const hipError_t e = launch_q4k_quant_rows(a, st); if (e != hipSuccess) return e; }
+// one sequence; 2 .. 8 sequences: the quantizer launch, then the projection on the staged groups
+hipError_t launch_q4k_chunk(const GemvArgs &a, const Q4kGemvPlan &p, hipStream_t st) {
     GemvArgs g = a;
-    g.norm_w = nullptr; g.attn_part = nullptr; g.attn_ml = nullptr; g.tile_max = nullptr;
-    GemvDev d = to_dev(g);
-    d.flags = F_PRE; d.xq_in = reinterpret_cast<const int8_t *>(xg);
-    d.rw = p.rw; d.nthr = p.nthr; d.units = p.rounds;
-    d.magic_nchunk = (uint32_t)(((1ull << 32) + bpl - 1) / bpl);
-    const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
-    d.wg_c0 = nseg > 1 ? p.wg[0] : 0xffffffffu;
-    d.wg_c1 = nseg > 2 ? p.wg[0] + p.wg[1] : 0xffffffffu;
-    d.ntiles = 0;
-    if (a.nb <= 2) return launch_chunk_nb<2>(d, p, st);
-    if (a.nb <= 4) return launch_chunk_nb<4>(d, p, st);
-    return launch_chunk_nb<8>(d, p, st);
+    if (p.quant_rows) {
+        const hipError_t e = launch_quant_rows_planned(a, p.quant_nthr, p.quant_nv, st);
+        if (e != hipSuccess) return e;
+        g.norm_w = nullptr; g.attn_part = nullptr; g.attn_ml = nullptr;
+    }
+    GemvDev d = chunk_dev(g, p.rw, p.nthr, p.rounds, p.wg);
+    if (p.quant_rows) { d.flags = F_PRE; d.xq_in = reinterpret_cast<const int8_t *>(a.q4_scratch); }
+    else if (a.x4_in) { d.flags |= F_PRE; d.xq_in = reinterpret_cast<const int8_t *>(a.x4_in); }
+    if (p.partials) { d.tile_max = a.tile_max; d.ntiles = p.partials; }
+    if (p.B == 2) return launch_chunk_d<R_GENERIC, 1, 2>(d, p, st);
+    if (p.B == 4) return launch_chunk_d<R_GENERIC, 1, 4>(d, p, st);
+    if (p.B == 8) return launch_chunk_d<R_GENERIC, 1, 8>(d, p, st);
+    if (p.role == R_NORM_STORE) return launch_chunk_r<R_NORM_STORE>(d, p, st);
+    if (p.role == R_RESID) return launch_chunk_r<R_RESID>(d, p, st);
+    if (p.role == R_RESID_COMBINE) return launch_chunk_r<R_RESID_COMBINE>(d, p, st);
+    if (p.role == R_NORM_SWIGLU) return launch_chunk_r<R_NORM_SWIGLU>(d, p, st);
+    return launch_chunk_r<R_GENERIC>(d, p, st);
 }
 
 // ---- the fused q | k | v + attention launch: host side -----------------------------------------------------------------------------------
@@ -315,12 +301,7 @@ bool qkv_attn_fused_q4k_supports(const GemvArgs &ga, const AttnArgs &aa) { Chunk
 hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
     ChunkPlan p;
     if (!hand || !tick || !layer1 || layer1 > 127u || !q4k_fused_shape(ga, aa, p)) return hipErrorInvalidValue;
-    GemvDev d = to_dev(ga);
-    d.tile_max = nullptr; d.ntiles = 0;
-    const uint32_t bpl = ga.n >> 8;
-    d.rw = p.rw; d.nthr = p.nthr; d.units = p.rounds;
-    d.magic_nchunk = (uint32_t)(((1ull << 32) + bpl - 1) / bpl);
-    d.wg_c0 = p.wg[0]; d.wg_c1 = p.wg[0] + p.wg[1];
+    const GemvDev d = chunk_dev(ga, p.rw, p.nthr, p.rounds, p.wg);
     QkvAttnArgs fa{};
     const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, false), lds = p.lds > lds_a ? p.lds : lds_a;
     fa.g = d; fa.ngemv = p.grid;
@@ -335,28 +316,6 @@ hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, uns
     Q4F_NV(4);
 #undef Q4F_NV
 #undef Q4F_GO
-}
-
-hipError_t launch_gemv_q4k_chunk(GemvArgs &a, hipStream_t st) {
-    if (a.nb > 1) return launch_gemv_q4k_chunk_batched(a, st);
-    ChunkPlan p;
-    if (!plan_chunk(a, p)) return hipErrorInvalidValue;
-    GemvDev d = to_dev(a);
-    if (a.x4_in) { d.flags |= F_PRE; d.xq_in = reinterpret_cast<const int8_t *>(a.x4_in); }
-    const uint32_t bpl = a.n >> 8;
-    d.rw = p.rw; d.nthr = p.nthr; d.units = p.rounds;
-    d.magic_nchunk = (uint32_t)(((1ull << 32) + bpl - 1) / bpl);
-    const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
-    d.wg_c0 = nseg > 1 ? p.wg[0] : 0xffffffffu;
-    d.wg_c1 = nseg > 2 ? p.wg[0] + p.wg[1] : 0xffffffffu;
-    d.ntiles = gemv_q4k_chunk_partials(a);
-    if (!d.ntiles) d.tile_max = nullptr;
-    const uint32_t f = d.flags;
-    if (f == F_NORM && d.epi == GEMV_EPI_STORE) return launch_chunk_r<R_NORM_STORE>(d, p, st);
-    if (f == 0 && d.epi == GEMV_EPI_RESID) return launch_chunk_r<R_RESID>(d, p, st);
-    if (f == F_COMBINE && d.epi == GEMV_EPI_RESID) return launch_chunk_r<R_RESID_COMBINE>(d, p, st);
-    if (f == F_NORM && d.epi == GEMV_EPI_SWIGLU) return launch_chunk_r<R_NORM_SWIGLU>(d, p, st);
-    return launch_chunk_r<R_GENERIC>(d, p, st);
 }
 
 }  // namespace nano

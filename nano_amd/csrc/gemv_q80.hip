@@ -21,7 +21,7 @@ SlabPlan q80_plan_slab(const GemvArgs &a, int B) {
     const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
     uint32_t align = 0;                                   // a workgroup's rows must lie inside one segment
     if (nseg > 1) for (uint32_t s = 0; s < nseg; s++) align |= a.seg[s].rows;
-    const uint32_t rows = total_rows(a);
+    const uint32_t rows = gemv_total_rows(a);
     // Every workgroup re-stages the activations (B x n elements), so the row slab grows until one wave of workgroups
     // covers the chip: the largest power of two with >= 256 workgroups (small matrices: ~4 units = 16 KiB of weights per
     // matrix and >= 128 workgroups, the tuned batch-1 optimum), bounded by the LDS product table.
@@ -98,7 +98,7 @@ bool gemv_q80_plan(const GemvArgs &a, Q80GemvPlan *out) {
     if (a.epi == GEMV_EPI_SWIGLU && a.nseg != 2) return false;
     if (a.epi != GEMV_EPI_SWIGLU && a.nseg > 1)
         for (uint32_t s = 0; s < a.nseg; s++) if (a.seg[s].rows % 4) return false;
-    const uint32_t rows = total_rows(a);
+    const uint32_t rows = gemv_total_rows(a);
     if (rows == 0) return false;
     const uint32_t B = a.nb <= 1 ? 1 : a.nb <= 2 ? 2 : a.nb <= 4 ? 4 : 8;
     const uint32_t f = (a.norm_w ? F_NORM : 0u) | (a.xq_in ? F_PRE : 0u) | (a.attn_part ? F_COMBINE : 0u);

@@ -77,13 +77,34 @@ inline bool q80_canonical(const GemvArgs &a) {
 }
 uint32_t gemv_tiles(uint32_t quant, const GemvArgs &a);   // tiles launch_gemv() will use (sizes tile_max)
 hipError_t launch_gemv(uint32_t quant, GemvArgs &a, hipStream_t st);
-hipError_t launch_gemv_q4k(GemvArgs &a, hipStream_t st);
-bool gemv_q4k_chunk_supports(const GemvArgs &a);            // gemv_q4k_chunk.hip: one sequence, whole 256-value blocks
-bool gemv_q4k_chunk_takes(const GemvArgs &a);               // ... or 2 .. 8 sequences where the chunk form is the faster one (gemv_q4k.hip)
-bool gemv_q4k_chunk_loops(const GemvArgs &a);               // ... and the launch is the looping (classifier) variant
-uint32_t gemv_q4k_chunk_partials(const GemvArgs &a);
-hipError_t launch_gemv_q4k_chunk(GemvArgs &a, hipStream_t st);
-uint32_t gemv_q4k_fit_batch(const GemvArgs &a);            // sequences per Q4K launch that fit in LDS (8 | 4 | 2 | 1)
+// rows of a launch: the tensors of a STORE / residual launch one after the other (SwiGLU: the two matrices share theirs)
+inline uint32_t gemv_total_rows(const GemvArgs &a) {
+    if (a.epi == GEMV_EPI_SWIGLU) return a.seg[0].rows;
+    uint32_t r = 0;
+    for (uint32_t s = 0; s < a.nseg; s++) r += a.seg[s].rows;
+    return r;
+}
+hipError_t launch_gemv_q4k(const GemvArgs &a, hipStream_t st);
+// The launch launch_gemv_q4k() issues for `a` (nb <= 8): the item kernel gemv_q4k_slab_kernel<role, B, nv, ipt> (gemv_q4k.hip) or the chunk
+// kernel gemv_q4k_chunk_kernel<role, nv, d, loop, B> (gemv_q4k_chunk.hip: whole 256-value blocks, n <= 16384; 2 .. 8 sequences with
+// GemvArgs::q4_scratch, behind a q4k_quant_rows_kernel<., quant_nv> launch of quant_nthr threads per sequence), with its threads, rows per
+// workgroup, workgroups and LDS bytes; the launchers take every choice from here.  false: the arguments are refused -- malformed, several
+// weight tensors whose row counts are no multiples of 4 on the item kernel, more than 4 items per thread, or more LDS than a CU has
+// (gemv_q4k_fit_batch() tells the router how many sequences fit).
+constexpr uint32_t GEMV_Q4K_LDS_MAX = 160 * 1024;
+constexpr uint32_t GEMV_Q4K_CHUNK_SEARCH_LDS = 150 * 1024;  // the chunk planner's search stops at slabs whose workgroups (k per CU) would ask for more
+enum : uint32_t { Q4K_KERNEL_NONE = 0, Q4K_KERNEL_SLAB = 1, Q4K_KERNEL_CHUNK = 2 };
+struct Q4kGemvPlan {
+    uint32_t kernel, role, B;                   // B: the template capacity 1 | 2 | 4 | 8 (the chunk kernel's NB)
+    uint32_t nv, ipt;                           // the NV template value (0 | 1 | 2 | 4; chunk: 1 | 2 | 4); slab: items per thread 1 | 2 | 4
+    uint32_t d, loop, rounds, wg[3];            // chunk: wave-loads in flight per wave, the persistent (classifier) form and its rounds, workgroups per tensor
+    uint32_t rw, nthr, grid, lds_bytes;         // rows per workgroup, threads, workgroups, dynamic LDS
+    uint32_t pre;                               // the caller brings the quantized activation (F_PRE)
+    uint32_t quant_rows, quant_nthr, quant_nv;  // 1: a q4k_quant_rows_kernel launch goes first, with the one-sequence chunk plan's threads and NV
+    uint32_t partials;                          // (max, row) arg-max pairs per sequence the launch writes into tile_max, one per workgroup; 0: none
+};
+bool gemv_q4k_plan(const GemvArgs &a, Q4kGemvPlan *p);
+uint32_t gemv_q4k_fit_batch(const GemvArgs &a);            // sequences per item-kernel launch that fit in LDS (8 | 4 | 2 | 1; 0: not even the one-sequence launch is taken)
 // Q4K, 9..64 tokens per weight read on the int8 matrix cores (gemm_q4k.hip): the quantizer launch of the several-sequence chunk launches
 // (one workgroup per token, a.q4_scratch = nb * n bytes) + one MFMA per (group, token tile), the reference's float order -- bit for bit
 // the chunk GEMV's results.  Takes: whole blocks (n % 256 == 0, n <= 16384), segment rows in multiples of 16, no LoRA addend, no
@@ -138,7 +159,6 @@ hipError_t launch_quant_rows_frag(const float *x, uint32_t x_bstride, const floa
 hipError_t launch_quant_rows(const float *x, uint32_t x_bstride, const float *norm_w, uint32_t n, uint32_t gs, uint32_t nb,
                              int8_t *xq, float *xs, hipStream_t st);
 uint32_t gemv_q80_partials(const GemvArgs &a);
-uint32_t gemv_q4k_partials(const GemvArgs &a);   // Q4K: one (max, row) partial per workgroup of a one-segment STORE launch with tile_max
 
 // ---- routing (route.hip): which kernel a projection launch goes to ------------------------------------------------------------
 enum RouteKind : uint32_t {
@@ -161,12 +181,13 @@ struct Q80Route {
     uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of a launch's sequences (n bytes each: 2 .. 8 gemv_q4k_chunk.hip, 9 .. 64 gemm_q4k.hip), or nullptr
 };
 RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
-// FP32: the slices route_projection() cuts a launch of a.nb sequences into -- per = sequences of every slice but the last, launches = their
-// number; false: the shape is refused (hipErrorInvalidValue before any launch)
-bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
-// Q80, the routes that end in the GEMV kernels (ROUTE_GEMV, ROUTE_GEMV_PREQ, ROUTE_GEMV_SLICED): the same question -- groups of 8 wherever 8
-// fit a CU's LDS (gemv_q80_fit_batch()), fewer per launch on long rows; false: not even one sequence fits, or the shape is refused
-bool route_q80_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches);
+// The slices route_projection() cuts a GEMV launch of a.nb sequences into (FP32; Q4K; Q80, the routes that end in the GEMV kernels:
+// ROUTE_GEMV, ROUTE_GEMV_PREQ, ROUTE_GEMV_SLICED): per = sequences of every slice but the last, launches = their number.  Every
+// workgroup holds the activations of all its sequences in LDS, so groups of 8 wherever 8 fit a CU's LDS (gemv_*_fit_batch()), fewer per
+// launch on long rows; Q4K: 8 where the chunk form takes min(nb, 8) sequences, whose activations are staged once.  Per sequence nothing
+// changes: the kernels are bit for bit per sequence whatever the capacity.  false: not even one sequence fits, or the shape is refused
+// (hipErrorInvalidValue before any launch)
+bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_t *launches);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
 uint32_t route_norm_order(const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);

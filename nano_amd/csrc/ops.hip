@@ -231,7 +231,7 @@ static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
 }
 
 // The FP32 launch route_projection() issues for a descriptor (its first slice when it cuts the batch): gemv_f32_plan() and
-// route_f32_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
+// route_gemv_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
 // the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed.
 // out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0}; takes = 0: the router refuses the shape
 // (hipErrorInvalidValue before any launch) and the other entries are 0.
@@ -249,7 +249,7 @@ extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     memset(out, 0, 12 * sizeof(uint32_t));
     uint32_t per = 0, launches = 0;
     F32GemvPlan p;
-    if (!route_f32_slices(a, &per, &launches)) return 0;
+    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
     a.nb = per;
     if (!gemv_f32_plan(a, &p)) return 0;
     const uint32_t v[12] = { p.role, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, launches, per, 1u, 0u };
@@ -259,7 +259,7 @@ extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
 
 // The Q80 launch route_projection() issues for a descriptor: route_kind() -- assuming the step's activation scratch is present, as in
 // nano_hip_op_fused_gemv below --, then for the routes that end in the Q80 GEMV kernels gemv_q80_plan() of the first slice and
-// route_q80_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
+// route_gemv_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
 // the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
 // out = {route, kernel, role, gs, B, nv, upw, rw, nw, grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}; the batched routes
 // (G6 / G7 / G2 / GC) report the route, one launch of nb sequences and zeros for the kernel fields.  takes = 0: the router refuses the
@@ -289,10 +289,53 @@ extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     if (k == ROUTE_GEMV_PREQ) { a.xq_in = scratch_flag; a.xs_in = r.gxs; a.norm_w = nullptr; }      // (as route_projection() hands it on)
     uint32_t per = 0, launches = 0;
     Q80GemvPlan p;
-    if (!route_q80_slices(a, &per, &launches)) return 0;
+    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
     a.nb = per;
     if (!gemv_q80_plan(a, &p)) return 0;
     const uint32_t v[16] = { (uint32_t)k, p.kernel, p.role, p.gs, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, p.variant, p.pre, launches, per, 1u };
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+
+// The Q4K launch route_projection() issues for a descriptor: route_kind() -- assuming the step's scratch for the staged groups is present,
+// as in nano_hip_op_fused_gemv below --, then for the GEMV route gemv_q4k_plan() of the first slice and route_gemv_slices(), the
+// functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of the descriptor's
+// pointers only norm_w and attn_part are looked at (null or not), never followed.  A launch of one STORE tensor is planned as the
+// step's classifier asks for it: with a request for arg-max partials.
+// out = {route, kernel, role, B, nv, ipt, d, loop, rounds, wg[3], rw, nthr, grid, lds_bytes, pre, quant_rows, quant_nthr, quant_nv,
+// partials, launches, seqs_per_launch, takes}; the GEMM route reports the route, one launch of nb sequences and zeros for the kernel
+// fields.  takes = 0: the router refuses the shape (hipErrorInvalidValue before any launch) and every other entry is 0.
+extern "C" int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[24]) {
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    const NanoFusedGemvDesc &d = *dp;
+    if (d.quant != NANO_QUANT_Q4K) { nano_hip_set_error_("not a Q4K launch"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    static uint8_t scratch_flag[4];                 // stands for the scratch and the partials' buffer: compared with null, never followed
+    GemvArgs a{};
+    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
+    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus ? cus : 256u;
+    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    a.norm_w = d.norm_w;
+    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    if (d.kind == 0 && d.nseg == 1) a.tile_max = reinterpret_cast<float *>(scratch_flag);
+    Q80Route r{};
+    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = 9u;
+    r.q4x = scratch_flag; r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);       // (as nano_hip_op_fused_gemv sizes it)
+    memset(out, 0, 24 * sizeof(uint32_t));
+    const RouteKind k = route_kind(r, a);
+    if (k == ROUTE_Q4K_GEMM) {
+        out[0] = (uint32_t)k; out[21] = 1u; out[22] = d.nb; out[23] = 1u;
+        return 0;
+    }
+    a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;          // (as route_projection() hands it on)
+    uint32_t per = 0, launches = 0;
+    Q4kGemvPlan p;
+    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
+    a.nb = per;
+    if (launches > 1) a.tile_max = nullptr;                          // (gemv_slice(): a sliced launch writes no partials)
+    if (!gemv_q4k_plan(a, &p)) return 0;
+    const uint32_t v[24] = { (uint32_t)k, p.kernel, p.role, p.B, p.nv, p.ipt, p.d, p.loop, p.rounds, p.wg[0], p.wg[1], p.wg[2], p.rw, p.nthr, p.grid,
+                             p.lds_bytes, p.pre, p.quant_rows, p.quant_nthr, p.quant_nv, p.partials, launches, per, 1u };
     memcpy(out, v, sizeof(v));
     return 0;
 }

@@ -15,16 +15,10 @@
 
 namespace nano {
 
-static uint32_t route_rows(const GemvArgs &a) {
-    if (a.epi == GEMV_EPI_SWIGLU) return a.seg[0].rows;
-    uint32_t r = 0;
-    for (uint32_t s = 0; s < a.nseg; s++) r += a.seg[s].rows;
-    return r;
-}
 // every workgroup of a multi-sequence GEMV launch re-quantizes the nb x n activations: ~ workgroups x elements of redundant work
-static bool gemv_is_heavy(const GemvArgs &a) { return (uint64_t)(route_rows(a) / 16) * a.nb * a.n > (4u << 20); }
+static bool gemv_is_heavy(const GemvArgs &a) { return (uint64_t)(gemv_total_rows(a) / 16) * a.nb * a.n > (4u << 20); }
 // per-layer matrices of >= 8 M weights (Qwen3-4B's): bandwidth rather than latency bound
-bool route_is_wide(const GemvArgs &a) { const uint32_t rows = route_rows(a); return rows < 65536u && (uint64_t)rows * a.n >= (8u << 20); }
+bool route_is_wide(const GemvArgs &a) { const uint32_t rows = gemv_total_rows(a); return rows < 65536u && (uint64_t)rows * a.n >= (8u << 20); }
 
 // the rmsnorm sum-of-squares tree the activation quantizer launch must repeat for this matrix (launch_quant_rows_frag order)
 // (512 threads on the wide matrices -- the order the >= 3-sequence launches of Qwen3-4B have had since round 4; the one- and
@@ -82,38 +76,34 @@ static GemvArgs gemv_slice(const GemvArgs &a, uint32_t b0, uint32_t cnt) {
     return s;
 }
 
-// FP32: every workgroup holds the activations of all its sequences in LDS, so long rows take fewer sequences per launch
-// (gemv_f32_fit_batch(): 8 wherever 8 fit -- the groups of 8 a batch beyond 8 has always run in)
-bool route_f32_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
+// sequences of one launch: what the format's kernels fit in a CU's LDS (8 | 4 | 2 | 1; 0: not even one); a.nb = min(sequences, 8)
+static uint32_t gemv_fit_batch(uint32_t quant, const GemvArgs &a) {
+    if (quant == NANO_QUANT_Q80) return gemv_q80_fit_batch(a);
+    if (quant != NANO_QUANT_Q4K) return gemv_f32_fit_batch(a);
+    // the chunk form stages every sequence's activation once and shares every weight byte among up to 8 sequences (round 5); the item
+    // kernel's workgroups stage the whole quantized activation of each sequence: long rows (Qwen3-4B's hidden size) take fewer per launch
+    Q4kGemvPlan p;
+    if (gemv_q4k_plan(a, &p) && p.kernel == Q4K_KERNEL_CHUNK) return 8u;
+    return gemv_q4k_fit_batch(a);
+}
+bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_t *launches) {
     if (a.nb == 0) return false;
     GemvArgs one = a; one.nb = a.nb < 8u ? a.nb : 8u;
-    const uint32_t fit = gemv_f32_fit_batch(one);
+    const uint32_t fit = gemv_fit_batch(quant, one);
     if (fit == 0) return false;
     *per = a.nb < fit ? a.nb : fit;
     *launches = (a.nb + fit - 1) / fit;
     return true;
 }
-
-// Q80: every workgroup of a GEMV launch holds the quantized activations of all its sequences AND their product table in LDS, so long rows
-// take fewer sequences per launch (gemv_q80_fit_batch(): 8 wherever 8 fit -- the groups of 8 a batch beyond 8 has always run in).  Per
-// sequence nothing changes: the kernels are bit for bit per sequence whatever the capacity.
-bool route_q80_slices(const GemvArgs &a, uint32_t *per, uint32_t *launches) {
-    if (a.nb == 0) return false;
-    GemvArgs one = a; one.nb = a.nb < 8u ? a.nb : 8u;
-    const uint32_t fit = gemv_q80_fit_batch(one);
-    if (fit == 0) return false;
-    *per = a.nb < fit ? a.nb : fit;
-    *launches = (a.nb + fit - 1) / fit;
-    return true;
-}
-// the Q80 GEMV launches of a.nb sequences, cut where route_q80_slices() says so; a shape of which not even one sequence fits is refused
+// the GEMV launches of a.nb sequences, cut where route_gemv_slices() says so; a shape of which not even one sequence fits is refused
 // before any launch
-static hipError_t launch_q80_sliced(GemvArgs &a, hipStream_t st) {
+static hipError_t launch_gemv_sliced(uint32_t quant, const GemvArgs &a, hipStream_t st) {
     uint32_t per = 0, launches = 0;
-    if (!route_q80_slices(a, &per, &launches)) return hipErrorInvalidValue;
-    if (launches == 1) return launch_gemv_q80(a, st);
+    if (!route_gemv_slices(quant, a, &per, &launches)) return hipErrorInvalidValue;
+    const auto launch = quant == NANO_QUANT_Q80 ? launch_gemv_q80 : quant == NANO_QUANT_Q4K ? launch_gemv_q4k : launch_gemv_f32;
+    if (launches == 1) return launch(a, st);
     for (uint32_t b0 = 0; b0 < a.nb; b0 += per) {
-        const hipError_t e = launch_gemv_q80(gemv_slice(a, b0, a.nb - b0 < per ? a.nb - b0 : per), st);
+        const hipError_t e = launch(gemv_slice(a, b0, a.nb - b0 < per ? a.nb - b0 : per), st);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -122,34 +112,11 @@ static hipError_t launch_q80_sliced(GemvArgs &a, hipStream_t st) {
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     a.cus = (uint32_t)r.cus;
     const RouteKind k = route_kind(r, a);
-    if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) {      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
-        uint32_t per = 0, launches = 0;
-        if (!route_f32_slices(a, &per, &launches)) return hipErrorInvalidValue;
-        if (launches == 1) return launch_gemv_f32(a, st);
-        for (uint32_t b0 = 0; b0 < a.nb; b0 += per) {
-            const hipError_t e = launch_gemv_f32(gemv_slice(a, b0, a.nb - b0 < per ? a.nb - b0 : per), st);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+    if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) return launch_gemv_sliced(r.quant, a, st);      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
     switch (k) {
-    case ROUTE_Q4K: {
-        // every workgroup stages the whole quantized activation of each sequence in LDS: long rows (Qwen3-4B's hidden size)
-        // take fewer sequences per launch
+    case ROUTE_Q4K:
         a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
-        uint32_t fit = a.nb > 1 ? gemv_q4k_fit_batch(a) : 1u;
-        if (a.nb > 1) {                                                  // round 5: whole-block launches share every weight byte among up to 8 sequences
-            GemvArgs probe = a; probe.nb = a.nb < 8u ? a.nb : 8u;
-            if (gemv_q4k_chunk_takes(probe)) fit = 8u;
-        }
-        if (a.nb <= fit) return launch_gemv_q4k(a, st);
-        for (uint32_t b0 = 0; b0 < a.nb; b0 += fit) {
-            GemvArgs s = gemv_slice(a, b0, a.nb - b0 < fit ? a.nb - b0 : fit);
-            const hipError_t e = launch_gemv_q4k(s, st);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+        return launch_gemv_sliced(r.quant, a, st);
     case ROUTE_Q4K_GEMM:
         a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
         return launch_gemm_q4k(a, st);
@@ -173,18 +140,18 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
         // More sequences than a GEMV launch takes and a launch the GEMM does not take (row length / group size not a multiple of 4
         // groups, segment rows not multiples of 16, the LoRA o-branch addend): groups of 8 through the GEMV kernels.  Same arithmetic
         // per sequence, the weights are read once per group (of fewer than 8 where 8 do not fit a CU's LDS).
-        return launch_q80_sliced(a, st);
+        return launch_gemv_sliced(r.quant, a, st);
     case ROUTE_GEMV_PREQ: {
         // when the redundant quantization outweighs a launch (~3 us) the activations are quantized once (quant_rows_kernel) and the GEMV
         // reads them back
         const hipError_t e = launch_quant_rows(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st);
         if (e != hipSuccess) return e;
         a.xq_in = r.gq; a.xs_in = r.gxs; a.norm_w = nullptr;
-        return launch_q80_sliced(a, st);
+        return launch_gemv_sliced(r.quant, a, st);
     }
     case ROUTE_GEMV:
     default:
-        return launch_q80_sliced(a, st);
+        return launch_gemv_sliced(r.quant, a, st);
     }
 }
 

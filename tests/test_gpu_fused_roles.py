@@ -387,6 +387,33 @@ def test_batched_roles_q4k_bit_exact(oracle, nb_, kind, n, rows):
         assert np.array_equal(bits(out[b]), bits(alone)), ("alone", b)
 
 
+@pytest.mark.parametrize("kind,n,rows,nb_,per,launches", [(1, 9732, (64,), 5, 2, 3), (0, 4100, (64, 32, 32), 7, 4, 2)])
+def test_sliced_partial_block_rows_q4k_bit_exact(oracle, kind, n, rows, nb_, per, launches):
+    """gemv_q4k.hip's kernel on long partial-block rows, where every workgroup stages each sequence's whole activation (56.5 KB per sequence at
+    9732 values, 24.1 KB at 4100) and the router cuts the batch to what a CU's LDS holds: 5 sequences as 2 + 2 + 1 (the last a one-sequence
+    launch of the same kernel: no whole blocks), 7 as 4 + 3 (the second at capacity 4).  Every sequence bit for bit the oracle's, and bit for
+    bit what it gets alone."""
+    plan = nb.q4k_gemv_plan(kind, n, rows, nb_, norm=kind == 0)
+    assert (nb.Q4K_KERNELS[plan["kernel"]], plan["seqs_per_launch"], plan["launches"], plan["B"]) == ("slab", per, launches, per), plan
+    last = nb.q4k_gemv_plan(kind, n, rows, nb_ - per * (launches - 1), norm=kind == 0)
+    assert (nb.Q4K_KERNELS[last["kernel"]], last["launches"], last["B"]) == ("slab", 1, 1 if kind == 1 else 4), last
+    rng = np.random.default_rng(nb_ * 31 + n + kind)
+    x = order_free(rng, (nb_, n))
+    nw = (1 + 0.1 * rng.standard_normal(n)).astype(np.float32) if kind != 1 else None
+    WTs = [(q4k_weights(oracle, rng, r, n), r) for r in rows]
+    segs = [(WT[44:], None, r) for WT, r in WTs]
+    old = rng.standard_normal((nb_, sum(rows))).astype(np.float32) if kind == 1 else None
+    out, route = nb.op_fused_gemv(Q4K, kind, n, segs, x, nw, nb=nb_, resid=old, want_route=True)
+    assert route == "q4k"
+    for b in range(nb_):
+        ref = ref_q4k(oracle, oracle.rmsnorm(x[b], nw) if nw is not None else x[b], WTs, n)
+        if kind == 1:
+            ref = (old[b] + ref).astype(np.float32)
+        assert np.array_equal(bits(out[b]), bits(ref)), (b, float(np.abs(out[b] - ref).max()))
+        alone = nb.op_fused_gemv(Q4K, kind, n, segs, x[b:b + 1], nw, nb=1, resid=old[b:b + 1] if old is not None else None)[0]
+        assert np.array_equal(bits(out[b]), bits(alone)), ("alone", b)
+
+
 def test_classifier_q4k_persistent_workgroups_bit_exact(oracle):
     # rows >= 65536, one STORE segment: gemv_q4k_chunk.hip's looping workgroups (ring of 8 loads per wave), last workgroup ragged
     n, rows = 1024, 65536 + 37
