@@ -439,6 +439,15 @@ int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * values, 32768 with SwiGLU; one sequence that does not fit a CU's LDS) and every other entry is 0.  Host arithmetic on the shape fields:
  * works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
 int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[16]);
+/* The batched Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, tt, nv, r, ms, tp, pp,
+ * gs, sw, threads, grid, lds_bytes, norm_order, hh, ntiles, tc0, tc1, tpw, full, nu, nk, ttl, nw, rounds, tts, magic, nsa, pre, a_stage, a_ws,
+ * b_base, b_stage, b_xs, ks, ncw, nss, tab, ring, nl, waves, lt, nhc, nwaves, ng, npass, takes}.  kernel: 1 G6 MODE S, 2 G6 MODE F, 3 G7,
+ * 4 G7K, 5 GC, 6 G2 with its template values (G6: nv, r, ms, tt; G7: tp, pp, ms; GC: tt; G2: gs, sw, tt), threads x grid workgroups,
+ * lds_bytes of dynamic LDS, norm_order = the tree width of the activation quantizer launch in front, and the fields the kernel's
+ * argument block is filled from (fields of other kernels: 0).  A descriptor whose route ends in the GEMV kernels: the route, takes = 1,
+ * zeros for the rest (nano_hip_q80_gemv_plan reports that launch).  Same assumptions, flags and promises as nano_hip_q80_gemv_plan. */
+#define NANO_Q80_GEMM_PLAN_WORDS 47
+int nano_hip_q80_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_Q80_GEMM_PLAN_WORDS]);
 /* The Q4K launch the router issues for descriptor d (quant = NANO_QUANT_Q4K), likewise: out = {route, kernel, role, B, nv, ipt, d, loop,
  * rounds, wg[3], rw, nthr, grid, lds_bytes, pre, quant_rows, quant_nthr, quant_nv, partials, launches, seqs_per_launch, takes}.  route: the
  * router's choice with the step's scratch present.  The GEMV route: kernel 1 = gemv_q4k_slab_kernel<role, B, nv, ipt>, 2 =

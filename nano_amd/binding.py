@@ -69,6 +69,15 @@ Q80_KERNELS = ("none", "slab", "stream")
 Q80_VARIANTS = ("plain", "early", "wf", "wfc2", "wfc3", "wfc4")
 
 
+# what nano_hip_q80_gemm_plan reports (route_kind + nano_amd/csrc/kernels.h Q80GemmPlan, field for field): route is an index into ROUTE_NAMES,
+# kernel into Q80_GEMM_KERNELS
+Q80_GEMM_PLAN_FIELDS = ("route", "kernel", "tt", "nv", "r", "ms", "tp", "pp", "gs", "sw", "threads", "grid", "lds_bytes", "norm_order",
+                        "hh", "ntiles", "tc0", "tc1", "tpw", "full", "nu", "nk", "ttl", "nw", "rounds", "tts", "magic",
+                        "nsa", "pre", "a_stage", "a_ws", "b_base", "b_stage", "b_xs", "ks", "ncw", "nss", "tab", "ring", "nl",
+                        "waves", "lt", "nhc", "nwaves", "ng", "npass", "takes")
+Q80_GEMM_KERNELS = ("none", "g6s", "g6f", "g7", "g7k", "gc", "g2")
+
+
 # what nano_hip_q4k_gemv_plan reports (nano_amd/csrc/kernels.h Q4kGemvPlan + route_kind + route_gemv_slices): route is an index into
 # ROUTE_NAMES, kernel into Q4K_KERNELS, role into Q80_ROLES
 Q4K_PLAN_FIELDS = ("route", "kernel", "role", "B", "nv", "ipt", "d", "loop", "rounds", "wg0", "wg1", "wg2", "rw", "nthr", "grid", "lds_bytes",
@@ -163,6 +172,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_f32_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q80_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_q80_gemm_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q4k_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
@@ -546,6 +556,25 @@ def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=
     out = (C.c_uint32 * 16)()
     check(lib().nano_hip_q80_gemv_plan(C.byref(d), cus, out))
     return dict(zip(Q80_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def q80_gemm_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):
+    """The batched Q80 launch (G6 / G7 / G7K / GC / G2) the router issues for a fused-gemv shape (nano_hip_q80_gemm_plan; needs no GPU);
+    arguments as q80_gemv_plan.  Returns a dict of Q80_GEMM_PLAN_FIELDS; a shape whose route ends in the GEMV kernels: the route and zeros."""
+    d = NanoFusedGemvDesc()
+    d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = 0x80, gs, kind, n, nb, len(rows)
+    for i, r in enumerate(rows):
+        d.rows[i] = r
+    if norm:
+        d.norm_w = _FLAG.ctypes.data
+    if attn is not None:
+        d.attn_part = _FLAG.ctypes.data
+        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
+    d.ordered = 1 if ordered else 0
+    d.use_gemm = 1 if use_gemm else 0
+    out = (C.c_uint32 * len(Q80_GEMM_PLAN_FIELDS))()
+    check(lib().nano_hip_q80_gemm_plan(C.byref(d), cus, out))
+    return dict(zip(Q80_GEMM_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):

@@ -9,6 +9,7 @@
 // A[m = l%16][k = 16*(l/16) .. +15], B[k = same][n = l%16]; result c[i] = C[m = 4*(l/16) + i][n = l%16].
 #include <type_traits>
 #include "gemv_common.h"
+#include "gemm_q80_host.h"
 
 namespace nano {
 
@@ -99,7 +100,6 @@ struct G2Dev {
     const int8_t *xf; const float *xsf; const uint32_t *pos;
 };
 
-constexpr uint32_t G2_PK = 512, G2_PITCH = 528;
 // Ring depth: passes in flight per wave.  Loads complete in issue order (one vmcnt counter), so the activation
 // fragments of a pass must be issued no later than the weight pieces that should still be in flight when the pass
 // waits for them: BOTH rings run D passes ahead.  More token tiles = more fragment registers per pass = a shorter ring.
@@ -400,19 +400,16 @@ __global__ __launch_bounds__(256) void quant_rows_frag_kernel(const float *x, ui
     if ((tid % (GS / 4)) == 0) xsf[(size_t)(tt * ng + g) * 16u + nn] = scale;
 }
 
+// every choice is the plan's (q80_gemm_plan_g2(), gemm_q80_host.h)
 template <int GS, bool SW, int TT>
-static hipError_t launch_g2_t(const G2Dev &d, uint32_t rows, hipStream_t st) {
-    constexpr uint32_t GPP = G2_PK / (uint32_t)GS, nmat = SW ? 2u : 1u, NTP = 16u * TT + 1u;
-    constexpr bool PIPE = !(TT == 4 && SW);                                  // see the kernel: two product tables
-    const size_t lds = (size_t)2 * nmat * 16 * G2_PITCH + (size_t)nmat * 16 * (d.ng | 1u) * 4 + (size_t)(PIPE ? 2 : 1) * nmat * GPP * 16 * NTP * 4;
+static hipError_t launch_g2_t(const G2Dev &d, const Q80GemmPlan &p, hipStream_t st) {
     auto kern = &gemm_q80_g2_kernel<GS, SW, TT>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3((rows + 15) / 16), dim3(512), lds, st, d);
+    if (p.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, d);
     return hipGetLastError();
 }
 template <int GS>
-static hipError_t launch_g2(const GemvArgs &a, hipStream_t st) {
+static hipError_t launch_g2(const GemvArgs &a, const Q80GemmPlan &p, hipStream_t st) {
     G2Dev d{};
     for (int i = 0; i < 3; i++) {
         const bool live = i < (int)a.nseg;
@@ -423,45 +420,25 @@ static hipError_t launch_g2(const GemvArgs &a, hipStream_t st) {
         d.out_bstride[i] = live ? a.seg[i].out_bstride : 0;
         d.out_pstride[i] = live ? a.seg[i].out_pstride : 0;
     }
-    if (a.epi == GEMV_EPI_SWIGLU) { d.rows[1] = 0; d.rows[2] = 0; }
-    d.n = a.n; d.ng = a.n / a.gs; d.epi = a.epi; d.nb = a.nb; d.npass = (a.n + G2_PK - 1) / G2_PK;
-    d.magic_ng = ((1u << 20) + d.ng - 1) / d.ng;
+    if (p.sw) { d.rows[1] = 0; d.rows[2] = 0; }
+    d.n = a.n; d.ng = p.ng; d.epi = a.epi; d.nb = a.nb; d.npass = p.npass;
+    d.magic_ng = p.magic;
     d.xf = a.xq_in; d.xsf = a.xs_in; d.pos = a.pos;
-    uint32_t rows = 0;
-    if (a.epi == GEMV_EPI_SWIGLU) rows = a.seg[0].rows; else for (uint32_t s = 0; s < a.nseg; s++) rows += a.seg[s].rows;
-    const uint32_t tt = (a.nb + 15) / 16;
-    const bool sw = a.epi == GEMV_EPI_SWIGLU;
-#define G2_GO(TT_) do { return sw ? launch_g2_t<GS, true, TT_>(d, rows, st) : launch_g2_t<GS, false, TT_>(d, rows, st); } while (0)
-    if (tt <= 1) G2_GO(1);
-    if (tt <= 2) G2_GO(2);
+#define G2_GO(TT_) do { return p.sw ? launch_g2_t<GS, true, TT_>(d, p, st) : launch_g2_t<GS, false, TT_>(d, p, st); } while (0)
+    if (p.tt == 1u) G2_GO(1);
+    if (p.tt == 2u) G2_GO(2);
     G2_GO(4);
 #undef G2_GO
 }
 
 }  // namespace
 
-// Host-side predicate: does the GEMM take this launch?  (What it does not take goes through the GEMV kernels in groups
-// of 8 sequences, route.hip route_projection().)  Not taken: interior segments that are not multiples of the 16-row tile, a
-// split-attention input, the LoRA o-branch addend.
-bool gemm_q80_g2_supports(const GemvArgs &a) {
-    if (a.nb == 0 || a.nb > 64 || a.gs == 0 || a.n % a.gs || a.n % 16 || a.nseg == 0 || a.nseg > 3 || a.attn_part || a.resid_add) return false;
-    if (!(a.gs == 32 || a.gs == 64 || a.gs == 128 || a.gs == 256)) return false;
-    if (a.epi != GEMV_EPI_SWIGLU && a.nseg > 1)
-        for (uint32_t s = 0; s + 1 < a.nseg; s++) if (a.seg[s].rows % 16) return false;     // a 16-row tile stays inside one segment
-    const uint32_t ng = a.n / a.gs;
-    const uint32_t magic = ((1u << 20) + ng - 1) / ng;
-    for (uint32_t e = 0; e < 16 * ng + 4096; e++) if (((e * magic) >> 20) != e / ng) return false;
-    return true;
-}
-// a.xq_in / a.xs_in: the activations in fragment order (launch_quant_rows_frag)
-hipError_t launch_gemm_q80_g2(const GemvArgs &a, hipStream_t st) {
-    if (!a.xq_in || !a.xs_in || !gemm_q80_g2_supports(a)) return hipErrorInvalidValue;
-    switch (a.gs) {
-    case 32: return launch_g2<32>(a, st);
-    case 64: return launch_g2<64>(a, st);
-    case 128: return launch_g2<128>(a, st);
-    case 256: return launch_g2<256>(a, st);
-    default: return hipErrorInvalidValue;
+hipError_t launch_gemm_q80_g2(const GemvArgs &a, const Q80GemmPlan &p, hipStream_t st) {
+    switch (p.gs) {
+    case 32: return launch_g2<32>(a, p, st);
+    case 64: return launch_g2<64>(a, p, st);
+    case 128: return launch_g2<128>(a, p, st);
+    default: return launch_g2<256>(a, p, st);
     }
 }
 // bytes of the fragment-order activation scratch for up to `tokens` tokens of row length n

@@ -14,8 +14,8 @@
 //     to the running value of (row, token) in ascending group order: bit-identical to the GEMV path and to the reference.
 // Takes: group size 64, one STORE segment of >= 16384 rows, group count a multiple of 8 or 4.  (route.hip routes the classifier
 // of batched steps here.)
-#include <atomic>
 #include "gemv_common.h"
+#include "gemm_q80_host.h"
 
 namespace nano {
 
@@ -29,9 +29,7 @@ struct GCDev {
     const int8_t *xf; const float *xsf;
 };
 
-constexpr uint32_t GC_PITCH = 528, GC_WBUF = 16 * GC_PITCH;             // transposition buffer of one wave: 16 rows x 512 B
-constexpr uint32_t GC_LDS_WAVE = GC_WBUF + 512;                         // + weight scales [8 groups][16 rows]
-
+// (the LDS sizes GC_*: gemm_q80_host.h)
 template <int TT>
 __global__ __launch_bounds__(512, 2) void gemm_q80_cls_kernel(const GCDev a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -162,62 +160,25 @@ __global__ __launch_bounds__(512, 2) void gemm_q80_cls_kernel(const GCDev a) {
 }
 
 template <int TT>
-static void launch_gc_tt(const GCDev &d, uint32_t nwg, uint32_t waves, size_t lds, hipStream_t st) {
-    auto kern = &gemm_q80_cls_kernel<TT>;
-    static std::atomic<unsigned long long> armed{0};
-    int dev = 0; (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !((armed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) armed.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(waves * 64), lds, st, d);
+static void launch_gc_tt(const GCDev &d, const Q80GemmPlan &p, hipStream_t st) {
+    constexpr auto kern = &gemm_q80_cls_kernel<TT>;
+    q80_gemm_lds_limit_once<kern>();
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, d);
 }
 
 }  // namespace
 
-// host predicate: the launches GC takes (the classifier of a batched step)
-bool gemm_q80_cls_supports(const GemvArgs &a) {
-    if (a.gs != 64 || a.nseg != 1 || a.epi != GEMV_EPI_STORE || a.seg[0].out_pstride != 0 || a.attn_part || a.resid_add) return false;
-    if (a.nb < 2 || a.nb > 64 || a.n % 64 || (a.n / 64) % 4 != 0 || a.n > 8192) return false;
-    if (a.seg[0].rows < 16384 || (a.seg[0].out_bstride % 4) != 0) return false;          // tall matrices; 16-byte output stores
-    if ((uint64_t)a.seg[0].rows * a.n >= (1ull << 32) - (1u << 20)) return false;         // 32-bit buffer offsets
-    const uint32_t ng = a.n / 64, tt = (a.nb + 15) / 16;
-    // LDS: at least min(tt, 2) token tiles staged next to 4 waves' buffers
-    const size_t need = (size_t)(tt < 2 ? tt : 2) * ng * 1088u + 4u * GC_LDS_WAVE;
-    return need <= 160u * 1024u;
-}
-
-// a.xq_in / a.xs_in: the activations in fragment order (launch_quant_rows_frag)
-hipError_t launch_gemm_q80_cls(const GemvArgs &a, hipStream_t st) {
-    if (!a.xq_in || !a.xs_in || !gemm_q80_cls_supports(a)) return hipErrorInvalidValue;
+// every choice is the plan's (q80_gemm_plan_gc(), gemm_q80_host.h)
+hipError_t launch_gemm_q80_cls(const GemvArgs &a, const Q80GemmPlan &p, hipStream_t st) {
     GCDev d{};
     d.w = reinterpret_cast<const int8_t *>(a.seg[0].w); d.ws = a.seg[0].ws; d.out = a.seg[0].out;
     d.rows = a.seg[0].rows; d.out_bstride = a.seg[0].out_bstride;
-    d.n = a.n; d.ng = a.n / 64; d.nb = a.nb; d.nhc = (d.ng + 7) / 8;
-    d.ntiles = (d.rows + 15) / 16; d.tt = (a.nb + 15) / 16;
+    d.n = a.n; d.ng = p.ng; d.nb = a.nb; d.nhc = p.nhc;
+    d.ntiles = p.ntiles; d.tt = p.ttl; d.lt = p.lt; d.nwaves = p.nwaves;
     d.xf = a.xq_in; d.xsf = a.xs_in;
-    const uint32_t TTc = d.tt <= 1 ? 1u : d.tt == 2 ? 2u : 4u;
-    // waves per workgroup (one workgroup per CU): as many as leave room to stage every token tile, or at least two of them (the
-    // kernel keeps at most two unstaged tiles in registers)
-    const size_t tile_lds = (size_t)d.ng * 1088u;
-    uint32_t waves = 8, lt = 0;
-    for (; waves >= 4; waves -= 2) {
-        const size_t room = 160u * 1024u - (size_t)waves * GC_LDS_WAVE - 256u;
-        lt = (uint32_t)(room / tile_lds);
-        if (lt > d.tt) lt = d.tt;
-        if (lt == d.tt || (lt >= 2 && d.tt - lt <= 2)) break;
-    }
-    if (waves < 4) return hipErrorInvalidValue;
-    if (lt < d.tt && lt > 2) lt = 2;                                    // unstaged tiles are tiles 2 and 3 (kernel)
-    if (lt < d.tt && (lt != 2 || d.tt > 4)) return hipErrorInvalidValue;
-    d.lt = lt;
-    const uint32_t cus = a.cus ? a.cus : 256u;
-    const uint32_t nwg = cus;                                           // one persistent workgroup per CU
-    d.nwaves = nwg * waves;
-    const size_t lds = (size_t)lt * tile_lds + (size_t)waves * GC_LDS_WAVE + 64u;
-    if (TTc == 1) launch_gc_tt<1>(d, nwg, waves, lds, st);
-    else if (TTc == 2) launch_gc_tt<2>(d, nwg, waves, lds, st);
-    else launch_gc_tt<4>(d, nwg, waves, lds, st);
+    if (p.tt == 1u) launch_gc_tt<1>(d, p, st);
+    else if (p.tt == 2u) launch_gc_tt<2>(d, p, st);
+    else launch_gc_tt<4>(d, p, st);
     return hipGetLastError();
 }
 

@@ -1,9 +1,9 @@
 // gemm_q80_g6_impl.h -- the G6 kernel (see gemm_q80_g6.hip for the design); included by the translation units that instantiate it
 // (gemm_q80_g6.hip).
 #pragma once
-#include <atomic>
 #include <type_traits>
 #include "gemv_common.h"
+#include "gemm_q80_host.h"
 
 namespace nano {
 
@@ -11,10 +11,7 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-enum : int { G6_F = 0, G6_S = 2 };
-constexpr uint32_t G6_PITCH = 528, G6_WBUF = 16 * G6_PITCH;
-constexpr uint32_t G6_LDS_WAVE = G6_WBUF + 512 + 512;          // + weight scales [8 groups][16 rows] + (F) activation scales [8][16 tokens]
-constexpr uint32_t G6_NW = 8;                                   // waves of a workgroup (launches with fewer items use fewer)
+enum : int { G6_F = 0, G6_S = 2 };          // (the LDS sizes G6_*: gemm_q80_host.h)
 
 struct G6Dev {
     GemvDev g;                          // segments, n, ng, epi, flags, nb
@@ -383,13 +380,8 @@ __global__ __launch_bounds__(512, 2) void gemm_q80_g6_kernel(const G6Dev d) {
 // ---- launch plumbing shared by the translation units ---------------------------------------------------------------------------------
 template <int MODE, int NV, int R, bool MS, int TT = 1>
 static hipError_t g6_launch_t(const G6Dev &d, size_t lds, hipStream_t st) {
-    auto kern = &gemm_q80_g6_kernel<MODE, NV, R, MS, TT>;
-    static std::atomic<bool> armed[64];
-    int dev = 0; (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !armed[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) armed[dev].store(true, std::memory_order_release);
-    }
+    constexpr auto kern = &gemm_q80_g6_kernel<MODE, NV, R, MS, TT>;
+    q80_gemm_lds_limit_once<kern>();
     hipLaunchKernelGGL(kern, dim3(d.grid), dim3(d.nw * 64u), lds, st, d);
     return hipGetLastError();
 }

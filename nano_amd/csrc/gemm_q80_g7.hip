@@ -3,7 +3,7 @@
 // activation fragments are staged in LDS once per workgroup by the consumer waves themselves, eight consumer waves multiply out of LDS
 // and keep the canonical fold in registers.
 //
-// Why (round 5).  G6 MODE F / G5 at 2..4 token tiles spent 2.3 us per (8 KB of weights, token tile): a wave fetched the 8 KB of
+// Why (round 5).  G6 MODE F at 2..4 token tiles spent 2.3 us per (8 KB of weights, token tile): a wave fetched the 8 KB of
 // activation fragments of every (item, token tile) from L2 into registers with one tile of look-ahead (4 x 8 KB of fragments per 8 KB
 // of weights, latency bound), and Qwen3-4B's W1|W3 did not fit G6 at all (100 KB of unit sums).  Here
 //   * one workgroup per CU owns `tpw` row tiles (<= 16 rows each, fitted to the chip like G6's) and walks the row length in STEPS of
@@ -25,9 +25,9 @@
 // Reference: matmul_quant infer/infer.c:654-679 (the arithmetic), the prompt loop :1258-1260 (what batched prefill replaces).
 // MFMA operand layout as in gemm_q80.hip (verified on gfx950): lane l holds A[m = l%16][k = 16 (l/16) .. +15], B[k][n = l%16],
 // c[i] = C[m = 4 (l/16) + i][n = l%16].
-#include <atomic>
 #include <type_traits>
 #include "gemv_common.h"
+#include "gemm_q80_host.h"
 
 namespace nano {
 
@@ -35,11 +35,7 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t G7_NCW = 14;                     // consumer waves
-constexpr uint32_t G7_NLA = 2;                      // weight loader waves (steps k % 2)
-constexpr uint32_t G7_NW = G7_NCW + G7_NLA;         // 16 waves: four per SIMD (<= 128 registers each)
-constexpr uint32_t G7_MAXNSA = 32;
-constexpr uint32_t G7_LDS = 160u * 1024u;
+// (the wave counts and LDS sizes G7_*: gemm_q80_host.h)
 constexpr int G7_BD = 2;                            // steps of activation fragments a consumer wave keeps in flight (registers): asked for one whole step (>= 0.6 us: an
                                                     // L2 round trip is ~0.15 us) before they are parked; 2 = the steps of a unit, so slot and unit phase unroll together
 
@@ -363,7 +359,6 @@ __global__ __launch_bounds__(G7_NW * 64) void gemm_q80_g7_kernel(const G7Dev d) 
 //   * the unit sums S_u go to an LDS table [unit][token tile][lane]; after the last super-step the phase-0 wave of a token tile adds them
 //     in ascending order (the row's starting value is S_0) and runs the epilogue: the CANONICAL fold, bit for bit G7's / G6's.
 // Reference: matmul_quant infer/infer.c:654-679.
-constexpr uint32_t G7K_STAGE = 4096u + 256u;        // a stage: the tile's 16 rows x 256 B, then its 16 x 4 weight scales
 struct G7KDev {
     GemvDev g;
     const int8_t *xf; const float *xsf;
@@ -525,171 +520,36 @@ __global__ __launch_bounds__(G7_NW * 64) void gemm_q80_g7k_kernel(const G7KDev d
     NANO_STAMP_END(a.stamps, 6);
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------------------------------
-struct G7Plan { uint32_t hh, ntiles, tc0, tc1, grid, tpw, nk, ttl, nsa, a_stage, a_ws, b_base, b_stage, b_xs, tp, pp; bool ms; size_t lds; };
-
-static uint32_t g7_rows(const GemvArgs &a) {
-    if (a.epi == GEMV_EPI_SWIGLU) return a.seg[0].rows;
-    uint32_t r = 0;
-    for (uint32_t s = 0; s < a.nseg; s++) r += a.seg[s].rows;
-    return r;
-}
-
-// Tile height.  At 17..64 tokens a launch is bound by the consumers' VALU work as much as by its bytes (measured, round 5: ~120 SIMD-cycles
-// per matrix-core result of 16 rows x 16 tokens x one group -- cvt, two multiplies and an add per output -- i.e. ~0.23 us per row tile and
-// step at four token tiles, where the tile's 16 x 256 B stream in ~0.18 us), and a tile costs that whatever its live rows: minimise
-// (tiles per CU) x max(VALU, bytes), ties to the taller tile (Qwen3-4B's q|k|v: 384 tiles of 16 rows, 2 on the busiest CU, instead of G6's
-// 768 tiles of 8 rows, 3 per CU).
-static bool g7_plan(const GemvArgs &a, G7Plan &p) {
-    const bool sw = a.epi == GEMV_EPI_SWIGLU;
-    const uint32_t cus = a.cus ? a.cus : 256u, nseg = sw ? 1u : a.nseg;
-    const uint32_t ttl0 = (a.nb + 15u) / 16u;
-    uint32_t best = 0, best_cost = ~0u;
-    for (uint32_t hh = 1; hh <= 8; hh++) {
-        const uint32_t trw = sw ? hh : 2u * hh;
-        uint32_t tiles = 0;
-        for (uint32_t s = 0; s < nseg; s++) tiles += (a.seg[s].rows + trw - 1) / trw;
-        const uint32_t grid = tiles < cus ? tiles : cus, tpw = (tiles + grid - 1) / grid;
-        const uint32_t valu = 6u * ttl0, bytes = trw * (sw ? 2u : 1u) + 2u;
-        const uint32_t cost = tpw * (valu > bytes ? valu : bytes);
-        if (cost <= best_cost) { best_cost = cost; best = hh; }       // ties: the taller tile
-    }
-    p.hh = best;
-    const uint32_t trw = sw ? best : 2u * best;
-    uint32_t tiles = 0, tc[2] = {0xffffffffu, 0xffffffffu};
-    for (uint32_t s = 0; s < nseg; s++) { tiles += (a.seg[s].rows + trw - 1) / trw; if (s < 2) tc[s] = tiles; }
-    p.ntiles = tiles; p.tc0 = nseg > 1 ? tc[0] : 0xffffffffu; p.tc1 = nseg > 2 ? tc[1] : 0xffffffffu;
-    p.grid = tiles < cus ? tiles : cus; p.tpw = (tiles + p.grid - 1) / p.grid;
-    p.ms = !sw && a.nseg > 1;
-    p.nk = a.n / 256u; p.ttl = (a.nb + 15u) / 16u;
-    p.tp = p.tpw <= 1 ? 1u : p.tpw == 2 ? 2u : p.tpw == 3 ? 3u : p.tpw <= 5 ? 5u : p.tpw <= 8 ? 8u : 0u;
-    if (!p.tp) return false;
-    p.pp = 0;
-    for (uint32_t pp = 1; pp <= 2u && !p.pp; pp *= 2u) if (p.tpw * ((p.ttl + pp - 1u) / pp) <= G7_NCW) p.pp = pp;
-    if (!p.pp) return false;
-    // LDS: the weight ring (a stage = the tiles' 16 rows x 256 B + their scales, one 1-KB DMA instruction per four tiles), then the two
-    // fragment stages (token tiles x 4 KB + 1 KB of activation scales)
-    p.a_ws = p.tpw * 4096u; p.a_stage = p.a_ws + ((p.tpw + 3u) / 4u) * 1024u;
-    p.b_xs = ((p.ttl + p.pp - 1u) / p.pp) * p.pp * 4096u; p.b_stage = p.b_xs + 1024u;    // (token tiles rounded up to the waves' PP: a wave reads all of its PP)
-    if (2u * p.b_stage + 1024u + 2u * p.a_stage > G7_LDS) return false;
-    uint32_t nsa = (G7_LDS - 2u * p.b_stage - 1024u) / p.a_stage;
-    // vmcnt is a 6-bit counter per wave: a loader's steps in flight behind the one it waits for (every second step is its own)
-    const uint32_t ips = 4u * p.tpw + (p.tpw + 3u) / 4u;
-    if (nsa > 1u + 2u * (63u / ips)) nsa = 1u + 2u * (63u / ips);
-    if (nsa > G7_MAXNSA) nsa = G7_MAXNSA;
-    if (nsa > p.nk + 1u) nsa = p.nk + 1u;
-    if (nsa < 2u) return false;
-    p.nsa = nsa;
-    p.b_base = nsa * p.a_stage;
-    p.lds = (size_t)p.b_base + 2u * p.b_stage + 1024u;                  // + the dummy kilobyte dead chunks are parked in
-    return true;
-}
-
+// ---- host side: every choice is the plan's (q80_gemm_plan_g7() / q80_gemm_plan_g7k(), gemm_q80_host.h) -------------------------------
 template <int TP, int PP, bool MS>
 static hipError_t g7_launch_t(const G7Dev &d, size_t lds, hipStream_t st) {
-    auto kern = &gemm_q80_g7_kernel<TP, PP, MS>;
-    static std::atomic<bool> armed[64];
-    int dev = 0; (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !armed[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G7_LDS);
-        if (dev >= 0 && dev < 64) armed[dev].store(true, std::memory_order_release);
-    }
+    constexpr auto kern = &gemm_q80_g7_kernel<TP, PP, MS>;
+    q80_gemm_lds_limit_once<kern>();
     hipLaunchKernelGGL(kern, dim3(d.grid), dim3(G7_NW * 64u), lds, st, d);
     return hipGetLastError();
 }
 
-
-
-// ---- G7K: plan ----------------------------------------------------------------------------------------------------------------------------
-struct G7KPlan { uint32_t hh, ntiles, nk, nu, ttl, ks, ncw, nss, tab, ring, nl; size_t lds; };
-static bool g7k_plan(const GemvArgs &a, G7KPlan &p) {
-    if (a.gs != 64 || a.nb < 3u || a.nb > 64u || a.n % 256u || a.nseg != 1 || a.epi == GEMV_EPI_SWIGLU) return false;
-    if (a.ordered || a.resid_add || a.tile_max || a.attn_part) return false;
-    if ((uint64_t)a.seg[0].rows * a.n >= (1ull << 32) - (1u << 20) || a.seg[0].rows >= 65536u) return false;
-    const uint32_t cus = a.cus ? a.cus : 256u, rows = a.seg[0].rows;
-    p.hh = 0;
-    // tile height: a workgroup's time does not depend on its live rows (a matrix-core tile and its VALU work cost the same): the lowest tile
-    // that still gives every workgroup a CU of its own = the most CUs at work (Qwen3-0.6B's Wo / W2: 256 workgroups of 4 rows instead of 64 of 16:
-    // 1.437 -> 1.413 ms per 64-sequence step; Qwen3-4B's: 256 of 10 rows instead of 160 of 16: 3.215 -> 3.19)
-    for (uint32_t hh = 1; hh <= 8 && !p.hh; hh++) if ((rows + 2u * hh - 1u) / (2u * hh) <= cus) p.hh = hh;
-    if (!p.hh) return false;
-    p.ntiles = (rows + 2u * p.hh - 1u) / (2u * p.hh);
-    p.nk = a.n / 256u; p.nu = (p.nk + 1u) / 2u; p.ttl = (a.nb + 15u) / 16u;
-    if (p.nk < 8u) return false;                                       // short rows: G7 / G6
-    // Where it pays (same-box A/Bs against G6 MODE F, profiles/r06_g7k.txt): up to three token tiles.  Qwen3-0.6B at 32 sequences 1.253 ->
-    // 1.18-1.23 ms per step, Qwen3-4B at 48: 3.012 -> 2.981, at 32: even; with FOUR token tiles (49..64 tokens) it LOSES: Qwen3-4B at 64
-    // sequences 3.127 -> 3.19 ms, Qwen3-0.6B even -- both kernels then sit at the same ~0.1 us per (16 rows x 16 tokens x 256 B) of a CU.
-    if (p.ttl > 3u) return false;
-    // (3..16 tokens, round 6: Qwen3-0.6B at 16 sequences 1.068 -> 1.016 ms per step, Qwen3-4B at 4 / 8 / 16: -0.9 % each; the loaders are the
-    //  waves the consumers leave, up to six -- at 32..48 tokens four loaders instead of two changed nothing)
-    // phases: as many as the fourteen consumer waves and the ring + table allow
-    // the ring comes first: THREE super-steps (the weights of super-step s + 2 go out at barrier s; with two, every super-step pays a DMA issue
-    // + an HBM round trip -- Qwen3-4B at 64 sequences 3.24-3.27 ms against 3.195-3.215), then as many phases as still fit; two only when no
-    // phase count leaves room for three (the most phases first, the ring second, measured 0.6-0.8 % slower on Qwen3-4B at 8 / 16 / 32 sequences)
-    const uint32_t ks_max = G7_NCW / p.ttl < 6u ? G7_NCW / p.ttl : 6u;
-    auto fits = [&](uint32_t ks, uint32_t rg) {
-        const uint32_t nl = G7_NW - ks * p.ttl < 6u ? G7_NW - ks * p.ttl : 6u;     // the waves the consumers leave load
-        const size_t ring = (size_t)rg * 2u * ks * G7K_STAGE, tab = (size_t)p.nu * p.ttl * 1024u;
-        if (ks > p.nu || ring + tab > G7_LDS) return false;
-        if (rg * ((2u * ks + nl - 1u) / nl) * 5u > 60u) return false;  // a loader's instructions in flight (ring super-steps x its steps x <= 5) fit vmcnt's six bits
-        p.ks = ks; p.ncw = ks * p.ttl; p.nss = (p.nu + ks - 1u) / ks; p.ring = rg; p.nl = nl;
-        p.tab = (uint32_t)ring; p.lds = ring + tab;
-        return true;
-    };
-    for (uint32_t rg = 3u; rg >= 2u; rg--) for (uint32_t ks = ks_max; ks >= 2u; ks--) if (fits(ks, rg)) return true;
-    return false;
-}
-
 }  // namespace
 
-bool gemm_q80_g7_supports(const GemvArgs &a) {
-    { G7KPlan kp; if (g7k_plan(a, kp)) return true; }                   // one row tile per CU and a long row: the K-phase form
-    if (a.gs != 64 || a.nb < 17u || a.nb > 64u || a.n % 256u || a.nseg == 0 || a.nseg > 3) return false;
-    if (a.ordered || a.resid_add || a.tile_max || a.attn_part) return false;
-    if (a.epi == GEMV_EPI_SWIGLU && (a.nseg != 2 || a.seg[0].rows != a.seg[1].rows)) return false;
-    const uint32_t nseg = a.epi == GEMV_EPI_SWIGLU ? 1u : a.nseg;
-    for (uint32_t s = 0; s < nseg; s++) if ((uint64_t)a.seg[s].rows * a.n >= (1ull << 32) - (1u << 20)) return false;   // 32-bit row offsets per segment
-    if (g7_rows(a) >= 65536u) return false;                            // (the classifier has kernels of its own: STREAM / GC)
-    G7Plan p;
-    if (!g7_plan(a, p)) return false;
-    // Where it pays (round 5, same-box A/B against G6 MODE F / G5, profiles/r05_g7_stamps.txt): launches with several row tiles per CU
-    // (q|k|v, W1|W3: one weight stage feeds 8..20 matrix-core pairs) and very short rows.  A launch of ONE row tile per CU and a long
-    // row (Wo, W2 of Qwen3-4B: 16 / 38 steps of ~0.6 us with four of the fourteen consumer waves at work) stays with G6, whose eight
-    // waves split the row length: 8.3 / 15.8 us there against 13.9 / 27.9 here.
-    return p.tpw * p.ttl >= 8u || p.nk <= 4u;
-}
-
-hipError_t launch_gemm_q80_g7(const GemvArgs &a, hipStream_t st) {
-    if (!a.xq_in || !a.xs_in || !gemm_q80_g7_supports(a)) return hipErrorInvalidValue;
-    G7KPlan kp;
-    if (g7k_plan(a, kp)) {
+hipError_t launch_gemm_q80_g7(const GemvArgs &a, const Q80GemmPlan &p, hipStream_t st) {
+    if (p.kernel == Q80_GEMM_G7K) {
         G7KDev d{};
         d.g = to_dev(a);
-        d.g.nthr = (kp.ncw + kp.nl) * 64u;
+        d.g.nthr = p.threads;
         d.xf = a.xq_in; d.xsf = a.xs_in;
-        d.hh = kp.hh; d.ntiles = kp.ntiles; d.nk = kp.nk; d.nu = kp.nu; d.ttl = kp.ttl; d.ks = kp.ks; d.ncw = kp.ncw; d.nss = kp.nss; d.tab = kp.tab; d.ring = kp.ring; d.nl = kp.nl;
-        static std::atomic<bool> armed_k[64];
-        int dev = 0; (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !armed_k[dev].load(std::memory_order_acquire)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_q80_g7k_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G7_LDS);
-            if (dev >= 0 && dev < 64) armed_k[dev].store(true, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(gemm_q80_g7k_kernel, dim3(kp.ntiles), dim3((kp.ncw + kp.nl) * 64u), kp.lds, st, d);
+        d.hh = p.hh; d.ntiles = p.ntiles; d.nk = p.nk; d.nu = p.nu; d.ttl = p.ttl; d.ks = p.ks; d.ncw = p.ncw; d.nss = p.nss; d.tab = p.tab; d.ring = p.ring; d.nl = p.nl;
+        q80_gemm_lds_limit_once<&gemm_q80_g7k_kernel>();
+        hipLaunchKernelGGL(gemm_q80_g7k_kernel, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, d);
         return hipGetLastError();
     }
-    G7Plan p;
-    if (!g7_plan(a, p)) return hipErrorInvalidValue;
     G7Dev d{};
     d.g = to_dev(a);
-    d.g.nthr = G7_NW * 64u;
+    d.g.nthr = p.threads;
     d.xf = a.xq_in; d.xsf = a.xs_in;
-    d.hh = p.hh; d.ntiles = p.ntiles; d.tc0 = p.tc0; d.tc1 = p.tc1; d.grid = p.grid; d.tpw = p.tpw;
-    d.full = p.ntiles - (p.tpw - 1u) * p.grid;
-    d.nk = p.nk; d.ttl = p.ttl; d.nsa = p.nsa;
-    d.pre = p.nsa - 1u < p.nk ? p.nsa - 1u : p.nk;
-    if (d.pre > 3u) d.pre = 3u;         // (2 / 3 / all nsa - 1 before the first barrier: 3.249 / 3.248 / 3.279 ms per 64-sequence Qwen3-4B step, one box, two runs each)
+    d.hh = p.hh; d.ntiles = p.ntiles; d.tc0 = p.tc0; d.tc1 = p.tc1; d.grid = p.grid; d.tpw = p.tpw; d.full = p.full;
+    d.nk = p.nk; d.ttl = p.ttl; d.nsa = p.nsa; d.pre = p.pre;
     d.a_stage = p.a_stage; d.a_ws = p.a_ws; d.b_base = p.b_base; d.b_stage = p.b_stage; d.b_xs = p.b_xs;
-#define G7_GO(TP_, PP_) do { return p.ms ? g7_launch_t<TP_, PP_, true>(d, p.lds, st) : g7_launch_t<TP_, PP_, false>(d, p.lds, st); } while (0)
+#define G7_GO(TP_, PP_) do { return p.ms ? g7_launch_t<TP_, PP_, true>(d, p.lds_bytes, st) : g7_launch_t<TP_, PP_, false>(d, p.lds_bytes, st); } while (0)
 #define G7_TP(PP_) do { if (p.tp == 1u) G7_GO(1, PP_); if (p.tp == 2u) G7_GO(2, PP_); if (p.tp == 3u) G7_GO(3, PP_); if (p.tp == 5u) G7_GO(5, PP_); G7_GO(8, PP_); } while (0)
     if (p.pp == 1u) G7_TP(1);
     G7_TP(2);

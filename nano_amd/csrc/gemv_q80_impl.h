@@ -199,7 +199,7 @@ template <int NQ> __device__ __forceinline__ void fold_row2(const float *p0, con
 }
 
 // CANONICAL fold of the fast path (kernels.h q80_canonical(); group size 64): unit sums S_u = the 8 group products of unit u added in
-// ascending order, row = ((S_0 + S_1) + S_2) + ... -- the one reduction shape the split-K kernels (gemm_q80_g6.hip, G5) share, so
+// ascending order, row = ((S_0 + S_1) + S_2) + ... -- the one reduction shape the batched kernels (G6, G7, G7K: gemm_q80_g6.hip, gemm_q80_g7.hip) share, so
 // that a batch stays bit for bit its sequences alone whichever kernel a batch size is routed to.  NQ float4 = 4 NQ groups.
 __device__ __forceinline__ float unit_sum(const float4 &t0, const float4 &t1) {
     float s = t0.x; s += t0.y; s += t0.z; s += t0.w; s += t1.x; s += t1.y; s += t1.z; s += t1.w;

@@ -137,22 +137,38 @@ constexpr uint32_t GEMV_F32_LDS_MAX = 160 * 1024;
 struct F32GemvPlan { uint32_t role, B, nv, upw, rw, nw, grid, lds_bytes; };
 bool gemv_f32_plan(const GemvArgs &a, F32GemvPlan *p);
 uint32_t gemv_f32_fit_batch(const GemvArgs &a);            // sequences per FP32 launch that fit in LDS (8 | 4 | 2 | 1; 0: none -- the shape is refused)
-// 9..64 tokens per weight read on the int8 matrix cores.  G2 (gemm_q80.hip): the general kernel in the reference's ascending group order --
-// strict mode's batched route, and the launches the canonical-fold kernels do not take (group sizes other than 64, rows that are no multiple
-// of 256); activations in MFMA B-fragment order (a.xq_in / a.xs_in = launch_quant_rows_frag's output)
-bool gemm_q80_g2_supports(const GemvArgs &a);                       // host predicate: shapes / features the GEMM takes
-hipError_t launch_gemm_q80_g2(const GemvArgs &a, hipStream_t st);
-// G6 (gemm_q80_g6.hip): the fast path's split-K kernel, canonical fold, group size 64, fragment-order activations (MODE S: staged in LDS
-// once per workgroup, <= 16 tokens; MODE F: fetched per item, 1 / 2 / 4 token tiles)
-bool gemm_q80_g6_supports(const GemvArgs &a);
-hipError_t launch_gemm_q80_g6(const GemvArgs &a, hipStream_t st);
-// G7 (gemm_q80_g7.hip): the fast path's kernel for 17..64 tokens -- LDS-DMA loader waves stream weights AND activation fragments through an
-// LDS ring, consumer waves own (row tile, token tile) pairs for the whole row length (canonical fold in registers); same inputs as MODE F
-bool gemm_q80_g7_supports(const GemvArgs &a);
-hipError_t launch_gemm_q80_g7(const GemvArgs &a, hipStream_t st);
-// GC, tall matrices with short rows (the classifier): persistent waves, activation fragments staged in LDS (gemm_q80_cls.hip)
-bool gemm_q80_cls_supports(const GemvArgs &a);
-hipError_t launch_gemm_q80_cls(const GemvArgs &a, hipStream_t st);
+// 2..64 tokens per weight read on the int8 matrix cores, activations in MFMA B-fragment order (a.xq_in / a.xs_in = launch_quant_rows_frag's
+// output, or the attention kernel's).  The canonical fold (q80_canonical()):
+//   G6 (gemm_q80_g6.hip)   split-K over (tile, unit) items; MODE S: the activation staged in LDS once per workgroup (<= 16 tokens, rows of
+//                          <= 4096 values), MODE F: fetched per item, 1 / 2 / 4 token tiles
+//   G7 (gemm_q80_g7.hip)   17..64 tokens, several row tiles per CU or very short rows: LDS-DMA loader waves stream the weights through an
+//                          LDS ring, consumer waves own (row tile, token tile) pairs for the whole row length
+//   G7K (gemm_q80_g7.hip)  3..48 tokens, one row tile per CU and rows of >= 2048 values: the waves split the row length by units
+// The reference's ascending group order (strict mode, group sizes other than 64, rows that are no multiple of 256, the classifier):
+//   GC (gemm_q80_cls.hip)  tall matrices with short rows (the classifier): persistent waves, activation fragments staged in LDS
+//   G2 (gemm_q80.hip)      the general kernel
+// gemm_q80_plan() names the whole launch of `a` -- the kernel in this order of preference: canonical launches G7K, G7, G6; the others
+// GC, G2 -- with its template values, threads, workgroups, dynamic LDS bytes and the fields the kernel's device block is filled from;
+// the launchers (gemm_q80_host.h) take every choice from it and cannot refuse.  false: no batched kernel takes the launch (a shape or
+// feature none of them has, or more LDS than a CU has) and nothing is launched -- the router then cuts it into GEMV launches.
+enum : uint32_t { Q80_GEMM_NONE, Q80_GEMM_G6S, Q80_GEMM_G6F, Q80_GEMM_G7, Q80_GEMM_G7K, Q80_GEMM_GC, Q80_GEMM_G2 };
+struct Q80GemmPlan {
+    uint32_t kernel;
+    // template values -- G6: MODE (the kernel), NV, R, MS, TT; G7: TP, PP, MS; GC: TT; G2: GS, SW, TT
+    uint32_t tt, nv, r, ms, tp, pp, gs, sw;
+    uint32_t threads, grid, lds_bytes;
+    uint32_t norm_order;                        // tree width of the quant_rows_frag launch in front (route_norm_order())
+    // row tiles (G6, G7, G7K; GC: ntiles): live rows per half tile, tiles, tiles up to the end of segment 0 / 1, tiles per workgroup (max),
+    // workgroups that own tpw tiles; units of 8 groups, steps of 256 B, live token tiles
+    uint32_t hh, ntiles, tc0, tc1, tpw, full, nu, nk, ttl;
+    uint32_t nw, rounds, tts;                   // G6: waves, the most items a wave owns, token tiles spread over the waves
+    uint32_t magic;                             // G6: G6Dev::magic_nu; G2: G2Dev::magic_ng
+    uint32_t nsa, pre, a_stage, a_ws, b_base, b_stage, b_xs;    // G7: ring stages, steps asked for before the first barrier, the LDS layout (G7Dev)
+    uint32_t ks, ncw, nss, tab, ring, nl;       // G7K: phases, consumer waves, super-steps, LDS offset of the unit-sum table, ring super-steps, loader waves
+    uint32_t waves, lt, nhc, nwaves;            // GC: waves per workgroup, token tiles staged in LDS, half chunks per row, waves of the launch
+    uint32_t ng, npass;                         // GC, G2: groups per row; G2: passes of 512 B
+};
+bool gemm_q80_plan(const GemvArgs &a, Q80GemmPlan *p);
 // order: threads of the rmsnorm sum-of-squares tree -- 256 (the SLAB GEMV prologue's of the small matrices) or 512 (the wide matrices' batched launches, route_norm_order())
 hipError_t launch_quant_rows_frag(const float *x, uint32_t x_bstride, const float *norm_w, uint32_t n, uint32_t gs, uint32_t nb,
                                   int8_t *xf, float *xsf, hipStream_t st, uint32_t order = 256);
@@ -167,9 +183,10 @@ enum RouteKind : uint32_t {
     ROUTE_GEMV_SLICED,     // more than 8 sequences through the GEMV kernels in groups of 8
     ROUTE_Q4K,
     ROUTE_RESERVED,        // (round 4's G6 MODE P; the value stays so that the route numbers the tests read do not move)
-    ROUTE_FRAG_G6,         // fragment-order activations (quantizer launch unless frag_ready) + G6 MODE F
-    ROUTE_FRAG_OLD,        // fragment-order activations + GC (the classifier) | G2 (the reference's group order)
-    ROUTE_FRAG_G7,         // fragment-order activations + G7 (17..64 tokens, the fast path)
+    // the batched Q80 routes: fragment-order activations (quantizer launch unless frag_ready) + the kernel gemm_q80_plan() names
+    ROUTE_FRAG_G6,         // Q80_GEMM_G6S | Q80_GEMM_G6F
+    ROUTE_FRAG_OLD,        // Q80_GEMM_GC | Q80_GEMM_G2: the reference's group order
+    ROUTE_FRAG_G7,         // Q80_GEMM_G7 | Q80_GEMM_G7K
     ROUTE_Q4K_GEMM,        // Q4K, 9..64 tokens: the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip)
 };
 inline bool route_takes_fragments(RouteKind k) { return k == ROUTE_FRAG_G6 || k == ROUTE_FRAG_OLD || k == ROUTE_FRAG_G7; }
@@ -180,7 +197,7 @@ struct Q80Route {
     int8_t *gq; float *gxs;  // fragment-order activation scratch (nullptr: no batched route)
     uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of a launch's sequences (n bytes each: 2 .. 8 gemv_q4k_chunk.hip, 9 .. 64 gemm_q4k.hip), or nullptr
 };
-RouteKind route_kind(const Q80Route &r, const GemvArgs &a);
+RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp = nullptr);   // gp: the plan behind a ROUTE_FRAG_* answer
 // The slices route_projection() cuts a GEMV launch of a.nb sequences into (FP32; Q4K; Q80, the routes that end in the GEMV kernels:
 // ROUTE_GEMV, ROUTE_GEMV_PREQ, ROUTE_GEMV_SLICED): per = sequences of every slice but the last, launches = their number.  Every
 // workgroup holds the activations of all its sequences in LDS, so groups of 8 wherever 8 fit a CU's LDS (gemv_*_fit_batch()), fewer per

@@ -297,6 +297,36 @@ extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     return 0;
 }
 
+// The batched Q80 launch route_projection() issues for a descriptor: route_kind() under the assumptions of nano_hip_q80_gemv_plan above
+// and the Q80GemmPlan (kernels.h) it hands to the launcher.  Host arithmetic only -- no device is touched, and of the descriptor's
+// pointers only norm_w and attn_part are looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
+// out = {route, the plan's fields in the order of the struct, takes}; a descriptor whose route ends in the GEMV kernels reports the route,
+// takes = 1 and zeros for the plan (nano_hip_q80_gemv_plan reports those launches, and their refusals).
+extern "C" int nano_hip_q80_gemm_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_Q80_GEMM_PLAN_WORDS]) {
+    static_assert(sizeof(Q80GemmPlan) == (NANO_Q80_GEMM_PLAN_WORDS - 2) * sizeof(uint32_t), "the query reports every field of the plan");
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    const NanoFusedGemvDesc &d = *dp;
+    if (d.quant != NANO_QUANT_Q80) { nano_hip_set_error_("not a Q80 launch"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    static int8_t scratch_flag[4];                  // stands for the scratch: compared with null, never followed
+    GemvArgs a{};
+    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
+    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb; a.cus = cus ? cus : 256u;
+    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    a.norm_w = d.norm_w;
+    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    a.ordered = d.ordered ? 1u : 0u;
+    Q80Route r{};
+    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
+    r.gq = scratch_flag; r.gxs = reinterpret_cast<float *>(scratch_flag);
+    Q80GemmPlan p{};
+    const RouteKind k = route_kind(r, a, &p);
+    out[0] = (uint32_t)k;
+    memcpy(out + 1, &p, sizeof(p));
+    out[NANO_Q80_GEMM_PLAN_WORDS - 1] = 1u;
+    return 0;
+}
+
 // The Q4K launch route_projection() issues for a descriptor: route_kind() -- assuming the step's scratch for the staged groups is present,
 // as in nano_hip_op_fused_gemv below --, then for the GEMV route gemv_q4k_plan() of the first slice and route_gemv_slices(), the
 // functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of the descriptor's

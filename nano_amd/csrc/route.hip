@@ -5,13 +5,15 @@
 //   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more sequences than fit a launch's LDS (at most 8) in groups
 //   Q4K, 9..64 sequences    the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip) where it takes the launch: same bits
 //   Q80, fast path          SLAB GEMV (1..8 sequences on the small per-layer matrices; 1..2 on those of >= 8 M weights)   gemv_q80_impl.h
-//                           G6 (fragment-order activations: MODE S staged in LDS, MODE F per item; 2..64 tokens) gemm_q80_g6.hip
-//                           G7 (17..64 tokens: loader / consumer engine, both operands through LDS) gemm_q80_g7.hip
-//                           G2 (group sizes other than 64, rows no multiple of 256: the reference's order) gemm_q80.hip
-//                           STREAM GEMV / GC for the classifier                                   gemv_q80_impl.h, gemm_q80_cls.hip
+//                           the batched kernels, fragment-order activations: whichever gemm_q80_plan() names      gemm_q80_host.h
+//                             canonical launches (group size 64, rows a multiple of 256): G7K (3..48 tokens, one row tile per CU, long
+//                             rows), G7 (17..64 tokens: loader / consumer engine), G6 (2..64 tokens: MODE S staged in LDS, MODE F per item)
+//                             the others (other group sizes and row lengths, the classifier): GC (the classifier, 2..64 tokens), G2
+//                           STREAM GEMV for the classifier of up to 7 sequences                           gemv_q80_impl.h
 //   Q80, strict mode        the kernels that keep the reference's ascending group order: SLAB, GC, G2 (a.ordered = 1)
+//   what no batched kernel takes runs through the GEMV kernels in groups that fit a CU's LDS (ROUTE_GEMV_SLICED)
 #include <stdlib.h>
-#include "kernels.h"
+#include "gemm_q80_host.h"
 
 namespace nano {
 
@@ -27,7 +29,22 @@ uint32_t route_norm_order(const GemvArgs &a) {
     return (q80_canonical(a) && route_is_wide(a) && a.n <= 10240u) ? 512u : 256u;
 }
 
-RouteKind route_kind(const Q80Route &r, const GemvArgs &a) {
+// The batched Q80 launch of `a`, whole, or false.  The order of preference lives here: canonical launches G7K, G7, G6 (each where its
+// planner says it pays); the others GC, then G2.  (A CANONICAL launch none of the three takes does not go to G2, whose fold is the
+// reference's: it would no longer be bit for bit its sequences alone.)
+bool gemm_q80_plan(const GemvArgs &a, Q80GemmPlan *p) {
+    using Section = bool (*)(const GemvArgs &, Q80GemmPlan &);
+    static const Section canon[] = {q80_gemm_plan_g7k, q80_gemm_plan_g7, q80_gemm_plan_g6}, other[] = {q80_gemm_plan_gc, q80_gemm_plan_g2};
+    const bool c = q80_canonical(a);
+    for (uint32_t i = 0; i < (c ? 3u : 2u); i++) {
+        *p = Q80GemmPlan{};
+        if ((c ? canon : other)[i](a, *p)) { p->norm_order = route_norm_order(a); return true; }
+    }
+    *p = Q80GemmPlan{};
+    return false;
+}
+
+RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp) {
     if (r.quant == NANO_QUANT_Q4K) {
         // from mfma_min_nb sequences on (9; NANO_MFMA_MIN_NB=65 restores the slices of 8: the A/B switch Q80 has) every weight byte is read
         // once per launch; what the GEMM refuses (gemm_q4k_supports()) keeps the slices
@@ -41,21 +58,16 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a) {
     // two sequences on wide matrices: the balanced SLAB GEMV (capacity 2) -- measured against G6 MODE P on one box, round 5: Qwen3-4B 1.833 vs
     // 1.923 ms per step (profiles/r05_wide_two_sequences.txt); from three sequences on the batched route is the faster one (four: 1.99 vs 2.80)
     if (canon && wide && a.nb == 2 && !a.xq_in) return ROUTE_GEMV;
-    if (canon) {
-        const bool batched = a.nb >= r.mfma_min_nb || (r.mfma_min_nb == 9 && ((a.nb == 8 && gemv_is_heavy(a)) || (wide && a.nb >= 2)));
-        if (batched && scratch && gemm_q80_g7_supports(a)) return ROUTE_FRAG_G7;      // 17..64 tokens, where it pays
-        if (batched && scratch && !a.attn_part && !a.resid_add && gemm_q80_g6_supports(a)) return ROUTE_FRAG_G6;
+    // the batched route: 9..64 sequences always (mfma_min_nb); 8 sequences when the matrix is large; per-layer matrices of >= 8 M weights
+    // from 2 sequences on; the classifier keeps its STREAM GEMV up to 7 sequences
+    const bool batched = scratch && (a.nb >= r.mfma_min_nb || (r.mfma_min_nb == 9 && ((a.nb == 8 && gemv_is_heavy(a)) || (wide && a.nb >= 2))));
+    Q80GemmPlan own;
+    Q80GemmPlan &p = gp ? *gp : own;
+    if (batched && gemm_q80_plan(a, &p)) {
+        if (p.kernel == Q80_GEMM_G7 || p.kernel == Q80_GEMM_G7K) return ROUTE_FRAG_G7;
+        if (!a.attn_part && !a.resid_add) return p.kernel == Q80_GEMM_GC || p.kernel == Q80_GEMM_G2 ? ROUTE_FRAG_OLD : ROUTE_FRAG_G6;
     }
-    // launches that are not canonical (strict mode, other group sizes, the classifier): 9..64 sequences always; 8 sequences when the matrix is
-    // large; per-layer matrices of >= 8 M weights from 2 sequences on; the classifier keeps its STREAM GEMV up to 7 sequences
-    bool mfma = false;
-    if (scratch) {
-        if (a.nb >= r.mfma_min_nb) mfma = true;
-        else if (r.mfma_min_nb == 9) mfma = (a.nb == 8 && gemv_is_heavy(a)) || (a.nb >= 2 && wide);
-    }
-    // (a CANONICAL launch neither G6 nor G7 takes does not go to G2, whose fold is the reference's: it would no longer be bit for bit its
-    //  sequences alone -- it runs through the GEMV kernels in groups of 8 below)
-    if (mfma && !canon && !a.attn_part && !a.resid_add && gemm_q80_g2_supports(a)) return ROUTE_FRAG_OLD;
+    p = Q80GemmPlan{};                                                  // (a plan leaves here only behind a ROUTE_FRAG_* answer)
     if (a.nb > 8) return ROUTE_GEMV_SLICED;
     if (a.nb > 1 && !a.attn_part && !a.xq_in && scratch && gemv_is_heavy(a)) return ROUTE_GEMV_PREQ;
     return ROUTE_GEMV;
@@ -111,7 +123,8 @@ static hipError_t launch_gemv_sliced(uint32_t quant, const GemvArgs &a, hipStrea
 
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     a.cus = (uint32_t)r.cus;
-    const RouteKind k = route_kind(r, a);
+    Q80GemmPlan gp{};
+    const RouteKind k = route_kind(r, a, &gp);
     if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) return launch_gemv_sliced(r.quant, a, st);      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
     switch (k) {
     case ROUTE_Q4K:
@@ -124,22 +137,23 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     case ROUTE_FRAG_G7:
     case ROUTE_FRAG_OLD: {
         // quantize every sequence's activation once, straight into MFMA fragment order (unless the producing kernel already did), then
-        // the GEMM
+        // the GEMM the plan names
         if (!a.frag_ready) {
-            const hipError_t e = launch_quant_rows_frag(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st, route_norm_order(a));
+            const hipError_t e = launch_quant_rows_frag(a.xin, a.xin_bstride, a.norm_w, a.n, a.gs, a.nb, r.gq, r.gxs, st, gp.norm_order);
             if (e != hipSuccess) return e;
         }
         a.xq_in = r.gq; a.xs_in = r.gxs;
-        if (k == ROUTE_FRAG_G6) return launch_gemm_q80_g6(a, st);
-        if (k == ROUTE_FRAG_G7) return launch_gemm_q80_g7(a, st);
-        // the classifier of a batched step: GC (persistent waves, the activation fragments staged in LDS once per workgroup)
-        if (gemm_q80_cls_supports(a)) return launch_gemm_q80_cls(a, st);
-        return launch_gemm_q80_g2(a, st);
+        switch (gp.kernel) {
+        case Q80_GEMM_G6S: case Q80_GEMM_G6F: return launch_gemm_q80_g6(a, gp, st);
+        case Q80_GEMM_G7: case Q80_GEMM_G7K: return launch_gemm_q80_g7(a, gp, st);
+        case Q80_GEMM_GC: return launch_gemm_q80_cls(a, gp, st);
+        default: return launch_gemm_q80_g2(a, gp, st);
+        }
     }
     case ROUTE_GEMV_SLICED:
-        // More sequences than a GEMV launch takes and a launch the GEMM does not take (row length / group size not a multiple of 4
-        // groups, segment rows not multiples of 16, the LoRA o-branch addend): groups of 8 through the GEMV kernels.  Same arithmetic
-        // per sequence, the weights are read once per group (of fewer than 8 where 8 do not fit a CU's LDS).
+        // More sequences than a GEMV launch takes and a launch no batched kernel takes (row length / group size not a multiple of 4
+        // groups, segment rows not multiples of 16, the LoRA o-branch addend, product tables beyond a CU's LDS): groups of 8 through the
+        // GEMV kernels.  Same arithmetic per sequence, the weights are read once per group (of fewer than 8 where 8 do not fit a CU's LDS).
         return launch_gemv_sliced(r.quant, a, st);
     case ROUTE_GEMV_PREQ: {
         // when the redundant quantization outweighs a launch (~3 us) the activations are quantized once (quant_rows_kernel) and the GEMV

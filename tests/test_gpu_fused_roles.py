@@ -182,8 +182,8 @@ def test_batched_wide_roles_q80(oracle, nb_, kind):
             assert np.allclose(out[b], want, rtol=3e-6, atol=1e-9), b
         return
     old = rng.standard_normal((nb_, sum(rows))).astype(np.float32)
-    # (round 6: one weight segment and a long row -> G7's K-phase form from three sequences on; g7k_takes is defined below)
-    check_q80(oracle, kind, n, segs, x, nw, old, nb_, routes=("gemv",) if nb_ <= 2 else ("frag_g7",) if g7k_takes(n, rows, nb_) else ("frag_g6",))
+    # (round 6: one weight segment and a long row -- Wo, kind 1 -- -> G7's K-phase form from three sequences on; q|k|v stays with G6)
+    check_q80(oracle, kind, n, segs, x, nw, old, nb_, routes=("gemv",) if nb_ <= 2 else ("frag_g7",) if kind == 1 else ("frag_g6",))
 
 
 GEMM_CASES = [(16, 0, 1024, (2048, 1024, 1024)), (17, 0, 2560, (4096, 1024, 1024)), (32, 1, 9728, (2560,)), (64, 1, 9728, (2560,)), (48, 0, 2560, (4096, 1024, 1024)),
@@ -204,25 +204,23 @@ GEMM_CASES = [(16, 0, 1024, (2048, 1024, 1024)), (17, 0, 2560, (4096, 1024, 1024
               (16, 0, 1024, (16400,)), (64, 0, 1024, (16391,)), (8, 0, 2560, (16512,)), (64, 0, 2560, (16390,)), (33, 0, 768, (16384,))]
 
 
-def g7_pays(n, rows, nb_, kind, cus=256):
-    """gemm_q80_g7.hip's rule, restated: row tiles per workgroup x token tiles >= 8, or at most four 256-byte steps"""
-    best, best_cost = 0, None
-    for hh in range(1, 9):
-        trw = 2 * hh
-        tiles = sum((r + trw - 1) // trw for r in rows)
-        tpw = (tiles + min(tiles, cus) - 1) // min(tiles, cus)
-        cost = tpw * max(6 * ((nb_ + 15) // 16), trw + 2)
-        if best_cost is None or cost <= best_cost:
-            best, best_cost = hh, cost
-    tiles = sum((r + 2 * best - 1) // (2 * best) for r in rows)
-    tpw = (tiles + min(tiles, cus) - 1) // min(tiles, cus)
-    return tpw * ((nb_ + 15) // 16) >= 8 or n // 256 <= 4
-
-
-def g7k_takes(n, rows, nb_, cus=256):
-    """round 6, the K-phase form (gemm_q80_g7k_kernel), restated: 3..48 tokens, ONE weight segment (no SwiGLU), a row of >= 8 steps, and a
-    tile height <= 8 that gives every row tile a CU of its own"""
-    return 3 <= nb_ <= 48 and len(rows) == 1 and n % 256 == 0 and n // 256 >= 8 and (rows[0] + 15) // 16 <= cus
+# the fast path's route of every case above, written out (gemm_q80_plan()'s choice, nb.q80_gemm_plan reports it without a device): G7 at
+# 17..64 tokens where row tiles per workgroup x token tiles >= 8 or the row has at most four 256-byte steps; G7's K-phase form at 3..48
+# tokens on one weight segment with a row of >= 8 steps and a CU for every row tile; else G6; tall matrices and rows that are no multiple
+# of 256: the reference's order (GC / G2)
+G6, G7, OLD = "frag_g6", "frag_g7", "frag_old"
+GEMM_ROUTES = {
+    (16, 0, 1024, (2048, 1024, 1024)): G6, (17, 0, 2560, (4096, 1024, 1024)): G6, (32, 1, 9728, (2560,)): G7, (64, 1, 9728, (2560,)): G6,
+    (48, 0, 2560, (4096, 1024, 1024)): G6, (30, 0, 2560, (9728, 9728)): G7, (9, 1, 3072, (1024,)): G7, (40, 1, 2048, (1024,)): G7,
+    (64, 0, 1024, (2048, 1024, 1024)): G7, (8, 1, 9728, (2560,)): G7, (16, 0, 2560, (4096, 1024, 1024)): G6, (33, 1, 4096, (2560,)): G7,
+    (64, 0, 2560, (9728, 9728)): G7, (64, 0, 1024, (3072, 3072)): G7, (64, 1, 2048, (1024,)): G6, (57, 1, 3072, (1024,)): G6,
+    (19, 1, 768, (512,)): G7, (47, 0, 1024, (2064, 1040, 1008)): G7, (64, 1, 4096, (2560,)): G6, (64, 1, 3072, (8192,)): G7,
+    (32, 1, 2048, (16000,)): G7, (25, 0, 2560, (4096, 1024, 1024)): G6, (3, 1, 9728, (2560,)): G7, (1, 0, 2560, (4096, 1024, 1024)): G6,
+    (17, 1, 2304, (1000,)): G7, (48, 1, 2816, (2550,)): G7, (5, 1, 2304, (520,)): G7, (17, 1, 4096, (2560,)): G7, (48, 1, 9728, (2560,)): G7,
+    (16, 0, 1024, (16400,)): OLD, (64, 0, 1024, (16391,)): OLD, (8, 0, 2560, (16512,)): OLD, (64, 0, 2560, (16390,)): OLD,
+    (33, 0, 768, (16384,)): OLD,
+}
+assert set(GEMM_ROUTES) == set(GEMM_CASES)
 
 
 def gemm_route_case(oracle, nb_, kind, n, rows):
@@ -238,10 +236,7 @@ def gemm_route_case(oracle, nb_, kind, n, rows):
             ref = ref_q80(oracle, oracle.rmsnorm(x[b], nw), segs, n, 64)
             assert np.array_equal(bits(out[b]), bits(ref)), (b, float(np.abs(out[b] - ref).max()))
         return "frag_old"
-    # 17..64 tokens: G7 where it pays (several row tiles per CU, or very short rows: gemm_q80_g7_supports), else G6 MODE F
-    g7 = (nb_ >= 17 and n % 256 == 0 and g7_pays(n, rows, nb_, kind)) or g7k_takes(n, rows, nb_)
-    want = ("frag_old",) if n % 256 else ("frag_g7",) if g7 else ("frag_g6",)
-    return check_q80(oracle, kind, n, segs, x, nw, old, nb_, use_gemm=True, routes=want)
+    return check_q80(oracle, kind, n, segs, x, nw, old, nb_, use_gemm=True, routes=(GEMM_ROUTES[(nb_, kind, n, rows)],))
 
 
 @pytest.mark.parametrize("nb_,n,rows", [(40, 2560, 9728), (64, 1024, 3072)])

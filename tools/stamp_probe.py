@@ -37,7 +37,7 @@ phases = {1: ["issue", "x arrives(+norm sum)", "quantize", "w arrive+dots", "bar
 G6 = quant == "q80" and (B >= 9 or (B >= 3 and model in ("qwen3-4b", "wide-qwen3")))     # gemm_q80_g6.hip's stamps
 g6_phases = ["issue", "x arrives, norm, quantize (P)", "first weights land", "first item multiplied", "this wave's other items", "finish tiles + last wave"]
 # gemm_q80_g7.hip (17..64 tokens, q|k|v and W1|W3): consumer wave 0's stamps
-G7 = quant == "q80" and B >= 17                  # (where gemm_q80_g7_supports() says it pays; the other launches stay G6's)
+G7 = quant == "q80" and B >= 17                  # (where gemm_q80_plan() names G7 or G7K; the other launches stay G6's)
 g7_phases = ["prologue (fragments of step 0 parked)", "first weights land", "step 0 multiplied", "the other steps", "stores issued", "last wave"]
 # gemm_q80_g7k_kernel (round 6: Wo / W2 at 3..48 tokens where the batched route runs): consumer wave 0's stamps
 G7K = quant == "q80" and 3 <= B <= 48 and (B >= 9 or model in ("qwen3-4b", "wide-qwen3"))
