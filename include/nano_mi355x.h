@@ -415,7 +415,8 @@ typedef struct NanoFusedGemvDesc {
     const float *attn_part;     /* optional, kind 1: [nb][nsplit][n] unnormalised attention partials, combined in the prologue */
     const float *attn_ml;       /* [nb][n_head][nsplit][2] (max, exp-sum) per split */
     uint32_t attn_nsplit, attn_n_head, attn_hd;
-    uint32_t use_gemm;          /* 1 (Q80): the batched route of a step -- activation quantizer launch + int8 MFMA GEMM */
+    uint32_t use_gemm;          /* 1 (Q80): the batched route of a step -- activation quantizer launch + int8 MFMA GEMM; 1 (FP32, 9..64 sequences):
+                                 * the activation prologue launch + the FP32 MFMA GEMM where it takes the shape, else the sliced GEMV route */
     uint32_t ordered;           /* 1: strict mode -- the reference's ascending group order in every kernel (bit-exact fp32); 0: the fast path */
     uint32_t *route_out;        /* optional: the route the launch took (RouteKind of nano_amd/csrc/kernels.h), or NULL */
     float *out;                 /* [nb][sum of rows] (kind 2: [nb][rows[0]]); kind 1: holds the residual stream on entry */
@@ -429,6 +430,18 @@ int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
  * shape is refused before any launch (a row of more than 16384 floats, 8192 with SwiGLU; one sequence that does not fit a CU's LDS).
  * Host arithmetic on the shape fields: works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
 int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[12]);
+/* The FP32 MFMA GEMM launch (9..64 sequences per weight read) the router issues for descriptor d (quant = NANO_QUANT_F32) in a model, or
+ * through nano_hip_op_fused_gemv with use_gemm = 1: out = {route, sw, threads, grid, lds_bytes, rt, nw, nt, nu, upw, tp, stage_bytes, tab_off,
+ * pro_threads, pro_lds, xs_floats, takes}.  route 9: gemm_f32_kernel<sw> (sw = 1: the W1 and W3 tiles of SwiGLU in one workgroup) on
+ * threads = 64 nw threads x grid workgroups of one rt = 16 row tile each and lds_bytes of dynamic LDS; nt token tiles of 16; a row is nu
+ * units of 128 floats, unit u belongs to wave u % nw (at most upw per wave); LDS = nw transposition buffers of stage_bytes, then at tab_off
+ * the unit-sum table [sw + 1][nu][rt][tp] floats; in front of it the activation prologue launch of pro_threads threads (the thread count
+ * of the sliced route's launch for the shape: its rmsnorm tree) x nb workgroups with pro_lds bytes, which writes xs_floats floats of
+ * operand-order scratch.  A descriptor the GEMM refuses (nb outside 9..64, a row the GEMV plan refuses, segment rows no multiple of 16,
+ * split-attention partials, more LDS than a CU has, a tensor of 2^32 bytes or more): the route of the sliced GEMV launches
+ * (nano_hip_f32_gemv_plan reports them), takes = 1 and zeros for the plan.  Same promises as nano_hip_f32_gemv_plan. */
+#define NANO_F32_GEMM_PLAN_WORDS 17
+int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_F32_GEMM_PLAN_WORDS]);
 /* The Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, role, gs, B, nv, upw, rw, nw,
  * grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}.  route: the router's choice with the step's scratch present (the value
  * route_out of nano_hip_op_fused_gemv reports).  Routes that end in the Q80 GEMV: kernel 1 = gemv_q80_slab_kernel<role, gs, B, nv, upw>

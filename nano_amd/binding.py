@@ -60,6 +60,11 @@ F32_PLAN_FIELDS = ("role", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "l
 F32_ROLES = ("generic", "norm_store", "resid", "resid_combine", "norm_swiglu")
 
 
+# what nano_hip_f32_gemm_plan reports (route_kind + nano_amd/csrc/kernels.h F32GemmPlan, field for field): route is an index into ROUTE_NAMES
+F32_GEMM_PLAN_FIELDS = ("route", "sw", "threads", "grid", "lds_bytes", "rt", "nw", "nt", "nu", "upw", "tp", "stage_bytes", "tab_off",
+                        "pro_threads", "pro_lds", "xs_floats", "takes")
+
+
 # what nano_hip_q80_gemv_plan reports (nano_amd/csrc/kernels.h Q80GemvPlan + route_kind + route_gemv_slices): route is an index into
 # ROUTE_NAMES, kernel into Q80_KERNELS, role into Q80_ROLES, variant into Q80_VARIANTS
 Q80_PLAN_FIELDS = ("route", "kernel", "role", "gs", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "variant", "pre", "launches",
@@ -86,7 +91,7 @@ Q4K_KERNELS = ("none", "slab", "chunk")
 
 
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
-ROUTE_NAMES = ("gemv", "gemv_preq", "gemv_sliced", "q4k", "reserved", "frag_g6", "frag_old", "frag_g7", "q4k_gemm")
+ROUTE_NAMES = ("gemv", "gemv_preq", "gemv_sliced", "q4k", "reserved", "frag_g6", "frag_old", "frag_g7", "q4k_gemm", "f32_gemm")
 
 
 class NanoHipError(RuntimeError):
@@ -171,6 +176,7 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_fused_gemv", C.c_int, [C.c_int, C.POINTER(NanoFusedGemvDesc)])
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_f32_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_f32_gemm_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q80_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q80_gemm_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q4k_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
@@ -536,6 +542,23 @@ def f32_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
     out = (C.c_uint32 * 12)()
     check(lib().nano_hip_f32_gemv_plan(C.byref(d), cus, out))
     return dict(zip(F32_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def f32_gemm_plan(kind, n, rows, nb=9, *, norm=False, attn=None, cus=256):
+    """The FP32 MFMA GEMM launch the router issues for a fused-gemv shape of 9..64 sequences (nano_hip_f32_gemm_plan; needs no GPU);
+    arguments as f32_gemv_plan.  Returns a dict of F32_GEMM_PLAN_FIELDS; a shape the GEMM refuses: the sliced route and zeros."""
+    d = NanoFusedGemvDesc()
+    d.quant, d.kind, d.n, d.nb, d.nseg = 0x00, kind, n, nb, len(rows)
+    for i, r in enumerate(rows):
+        d.rows[i] = r
+    if norm:
+        d.norm_w = _FLAG.ctypes.data
+    if attn is not None:
+        d.attn_part = _FLAG.ctypes.data
+        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
+    out = (C.c_uint32 * len(F32_GEMM_PLAN_FIELDS))()
+    check(lib().nano_hip_f32_gemm_plan(C.byref(d), cus, out))
+    return dict(zip(F32_GEMM_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):

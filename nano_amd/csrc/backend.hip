@@ -67,7 +67,7 @@ static void destroy(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
-                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->pf_stage,
+                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->pf_stage,
                     m->score.logits, m->score.part, m->score.targets, m->score.rows, m->score.stage, m->score.out };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
@@ -229,17 +229,20 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     // ---- state ---------------------------------------------------------------------------------------
     const size_t B = max_batch;
     if (const char *mm = getenv("NANO_MFMA_MIN_NB")) { const uint32_t v = (uint32_t)strtoul(mm, nullptr, 0); if (v >= 2) m->mfma_min_nb = v; }
-    // per-token scratch also serves batched prefill: up to 64 (Q80, and Q4K where gemm_q4k.hip takes all seven per-layer projections:
-    // int8 MFMA GEMMs) / 8 prompt tokens per pass.  Decided here, once, from the shapes and mfma_min_nb.
+    // FP32's own minimum for its MFMA GEMM (gemm_f32.hip); NANO_MFMA_MIN_NB can only raise it (65: the slices of 8, the A/B switch)
+    if (m->mfma_min_nb > m->f32_min_nb) m->f32_min_nb = m->mfma_min_nb;
+    // per-token scratch also serves batched prefill: up to 64 (Q80, and Q4K / FP32 where gemm_q4k.hip / gemm_f32.hip takes all seven
+    // per-layer projections: MFMA GEMMs) / 8 prompt tokens per pass.  Decided here, once, from the shapes and the minimum.
     m->pf_chunk = d.quant_type == NANO_QUANT_Q80 ? 64u : 8u;
-    if (d.quant_type == NANO_QUANT_Q4K && m->mfma_min_nb <= 64u) {
+    const bool f32 = d.quant_type == NANO_QUANT_F32;
+    if ((d.quant_type == NANO_QUANT_Q4K && m->mfma_min_nb <= 64u) || (f32 && m->f32_min_nb <= 64u)) {
         auto takes = [&](uint32_t n, uint32_t epi, uint32_t r0, uint32_t r1, uint32_t r2) {
             GemvArgs a{};
             a.n = n; a.nb = 64; a.epi = epi; a.cus = (uint32_t)m->cus;
             const uint32_t rows[3] = { r0, r1, r2 };
             for (uint32_t s = 0; s < 3 && rows[s]; s++) { a.seg[s].rows = rows[s]; a.nseg = s + 1; }
             if (epi != GEMV_EPI_RESID) a.norm_w = m->rms_attn;                  // (a flag here: q | k | v and W1|W3 normalise in their prologue)
-            return gemm_q4k_supports(a);
+            return f32 ? gemm_f32_supports(a) : gemm_q4k_supports(a);
         };
         if (takes((uint32_t)E, GEMV_EPI_STORE, QD, KD, KD) && takes(QD, GEMV_EPI_RESID, (uint32_t)E, 0, 0) &&
             takes((uint32_t)E, GEMV_EPI_SWIGLU, (uint32_t)H, (uint32_t)H, 0) && takes((uint32_t)H, GEMV_EPI_RESID, (uint32_t)E, 0, 0)) m->pf_chunk = 64u;
@@ -286,6 +289,12 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
         // 32 bytes per 32-value group: up to 8 sequences per chunk launch, up to 64 per GEMM launch (gemm_q4k.hip)
         m->q4x_bytes = (Bs > 8 ? (Bs < 64 ? Bs : (size_t)64) : (size_t)8) * ((nmax + 255) & ~(size_t)255);
         ok = hipMalloc(&m->q4x, m->q4x_bytes) == hipSuccess;
+    }
+    if (ok && Bs > 8 && f32 && m->f32_min_nb <= 64u) {
+        size_t nmax = E > QD ? E : QD; if (H > nmax) nmax = H;
+        // up to 64 tokens per GEMM launch, every row padded to whole 128-float units (gemm_f32.hip)
+        m->f32x_floats = (size_t)64 * ((nmax + 127) & ~(size_t)127);
+        ok = hipMalloc(&m->f32x, m->f32x_floats * 4) == hipSuccess;
     }
     if (ok && m->kv.paged) {
         const size_t ptn = B * m->kv.pt_stride;
@@ -378,7 +387,7 @@ extern "C" int nano_hip_sync(NanoHipModel *m) {
 
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps) {
     if (!m || !tokens || !pos) FAIL(NANO_HIP_EINVAL, "null argument");
-    const uint32_t cap = NANO_MAX_BATCH;               // > 8 sequences: Q80 and Q4K through their int8 MFMA GEMMs, FP32 (and Q4K shapes the GEMM refuses) through the GEMV kernels in groups
+    const uint32_t cap = NANO_MAX_BATCH;               // > 8 sequences: Q80, Q4K and FP32 through their MFMA GEMMs, shapes a GEMM refuses through the GEMV kernels in groups
     if (batch == 0 || batch > m->maxB || batch > cap) FAIL(NANO_HIP_EINVAL, "batch %u out of range (max %u, kernel capacity %u)", batch, m->maxB, cap);
     for (uint32_t i = 0; i < batch; i++) {
         if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
@@ -484,7 +493,7 @@ static int score_scratch(NanoHipModel *m) {
     return 0;
 }
 // Batched prefill: feeds `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot` in
-// passes of up to 64 (Q80 and Q4K through their int8 MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
+// passes of up to 64 (Q80, Q4K and FP32 through their MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
 // logits (the reference computes and discards them for prompt positions, infer.c:1146-1149).  The KV rows and every
 // later logit are the ones token-by-token feeding produces, bit for bit (same kernels and the same attention split per token).
 // score (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);

@@ -78,7 +78,9 @@ struct NanoHipModel {
     uint32_t lora_rank = 0, lora_alpha = 0; bool lora_on = false;
     int8_t *gq = nullptr; float *gxs = nullptr;           // MFMA GEMM path (batch > 8, Q80): quantized activations of all sequences
     uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 64 sequences: the staged activation groups (gemv_q4k_chunk.hip, gemm_q4k.hip)
-    uint32_t pf_chunk = 8;                                // prompt tokens per weight read of batched prefill: 64 (Q80; Q4K whose per-layer projections the MFMA GEMM takes) | 8
+    float *f32x = nullptr; size_t f32x_floats = 0;        // FP32, 9 .. 64 sequences: the operand-order activations of a GEMM launch (gemm_f32.hip)
+    uint32_t f32_min_nb = 9;                              // FP32: sequences per step from which projections go to the MFMA GEMM: max(its own measured minimum, mfma_min_nb)
+    uint32_t pf_chunk = 8;                                // prompt tokens per weight read of batched prefill: 64 (Q80; Q4K and FP32 whose per-layer projections the MFMA GEMM takes) | 8
     float *rope_cur = nullptr;                            // RoPE rows of the current positions [B][2][hd/2], staged by the embed kernel
     float *kcache = nullptr, *vcache = nullptr;
     uint32_t *tokens = nullptr, *pos = nullptr, *amax = nullptr, *trace = nullptr, *pos0 = nullptr;

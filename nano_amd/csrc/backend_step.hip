@@ -20,6 +20,7 @@ static Q80Route route_of(const NanoHipModel *m) {
     Q80Route r{};
     r.quant = m->d.quant_type; r.cus = m->cus; r.mfma_min_nb = m->mfma_min_nb;
     r.gq = m->gq; r.gxs = m->gxs; r.q4x = m->q4x; r.q4x_bytes = m->q4x_bytes;
+    r.f32_min_nb = m->f32_min_nb; r.f32x = m->f32x; r.f32x_floats = m->f32x_floats;
     return r;
 }
 static RouteKind kind_of(const NanoHipModel *m, GemvArgs a) { a.ordered = (m->strict || m->exact) ? 1u : 0u; a.cus = (uint32_t)m->cus; return route_kind(route_of(m), a); }

@@ -40,6 +40,7 @@ struct GemvArgs {
     const float *xs_in;     // Q80 float[n/gs]
     const uint8_t *x4_in;   // Q4K blocks[ceil(n/256)*160]
     uint8_t *q4_scratch; size_t q4_scratch_bytes;   // Q4K, 2 .. 64 sequences: room for the staged groups of every sequence (nb * n bytes), or nullptr
+    float *f32_scratch; size_t f32_scratch_floats;  // FP32, 9 .. 64 tokens: room for the operand-order activations of gemm_f32.hip (F32GemmPlan::xs_floats), or nullptr
     // input = combination of split attention partials (attn.hip) instead of xin:
     //   x[b][i] = sum_s part[b][s][i] * w[b][head(i)][s],  w from the (max, sum) pairs in attn_ml
     const float *attn_part; // [nb][nsplit][n] unnormalised partial outputs, or nullptr
@@ -137,6 +138,24 @@ constexpr uint32_t GEMV_F32_LDS_MAX = 160 * 1024;
 struct F32GemvPlan { uint32_t role, B, nv, upw, rw, nw, grid, lds_bytes; };
 bool gemv_f32_plan(const GemvArgs &a, F32GemvPlan *p);
 uint32_t gemv_f32_fit_batch(const GemvArgs &a);            // sequences per FP32 launch that fit in LDS (8 | 4 | 2 | 1; 0: none -- the shape is refused)
+// FP32, 9..64 tokens per weight read on the FP32 matrix cores (gemm_f32.hip): an activation prologue launch (one workgroup per token: the
+// GEMV's own rmsnorm on the thread count of the sliced route's launch, the result in MFMA operand order in a.f32_scratch) + the GEMM, whose
+// v_mfma_f32_16x16x4_f32 per float4 item, pairwise tree per 128-float unit and ascending chunk fold are the GEMV's reduction shape: bit for
+// bit its results.  gemm_f32_plan() (gemm_f32_host.h) names the whole launch; the launcher takes every choice from it and cannot refuse.
+// false: the shape is refused (nb outside 9..64, n % 4, a row the GEMV plan refuses, segment rows no multiple of 16, the LoRA addend,
+// split-attention partials, arg-max partials, more LDS than a CU has, a tensor of 2^32 bytes or more) and the sliced route keeps it.
+constexpr uint32_t GEMM_F32_LDS_MAX = 160 * 1024;
+struct F32GemmPlan {
+    uint32_t sw;                                // template value: 1 = the W1 and the W3 tile of the same rows in one workgroup (SwiGLU)
+    uint32_t threads, grid, lds_bytes;          // 64 * nw threads x grid workgroups (one per row tile), dynamic LDS
+    uint32_t rt, nw, nt, nu, upw, tp;           // rows of a tile (16), waves, token tiles of 16, units of 128 floats per row, units of a wave (max), floats between table rows
+    uint32_t stage_bytes, tab_off;              // LDS: a wave's transposition buffer; byte offset of the unit-sum table [matrix][unit][row][tp]
+    uint32_t pro_threads, pro_lds;              // the prologue launch: threads per token (the sliced route's launch of this shape), its LDS bytes
+    uint32_t xs_floats;                         // floats of operand-order scratch the launch needs
+};
+bool gemm_f32_plan(const GemvArgs &a, F32GemmPlan *p);
+inline bool gemm_f32_supports(const GemvArgs &a) { return gemm_f32_plan(a, nullptr); }
+hipError_t launch_gemm_f32(const GemvArgs &a, hipStream_t st);
 // 2..64 tokens per weight read on the int8 matrix cores, activations in MFMA B-fragment order (a.xq_in / a.xs_in = launch_quant_rows_frag's
 // output, or the attention kernel's).  The canonical fold (q80_canonical()):
 //   G6 (gemm_q80_g6.hip)   split-K over (tile, unit) items; MODE S: the activation staged in LDS once per workgroup (<= 16 tokens, rows of
@@ -188,6 +207,7 @@ enum RouteKind : uint32_t {
     ROUTE_FRAG_OLD,        // Q80_GEMM_GC | Q80_GEMM_G2: the reference's group order
     ROUTE_FRAG_G7,         // Q80_GEMM_G7 | Q80_GEMM_G7K
     ROUTE_Q4K_GEMM,        // Q4K, 9..64 tokens: the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip)
+    ROUTE_F32_GEMM,        // FP32, 9..64 tokens: the activation prologue launch + the FP32 MFMA GEMM (gemm_f32.hip)
 };
 inline bool route_takes_fragments(RouteKind k) { return k == ROUTE_FRAG_G6 || k == ROUTE_FRAG_OLD || k == ROUTE_FRAG_G7; }
 inline bool route_takes_attn_parts(RouteKind k) { return k == ROUTE_GEMV || k == ROUTE_Q4K || k == ROUTE_Q4K_GEMM; }     // (Q4K GEMM: its quantizer launch combines)
@@ -196,6 +216,8 @@ struct Q80Route {
     uint32_t mfma_min_nb;  // sequences from which the small Q80 matrices and every Q4K matrix take the batched (MFMA GEMM) route (9; NANO_MFMA_MIN_NB)
     int8_t *gq; float *gxs;  // fragment-order activation scratch (nullptr: no batched route)
     uint8_t *q4x; size_t q4x_bytes;   // Q4K: scratch for the staged groups of a launch's sequences (n bytes each: 2 .. 8 gemv_q4k_chunk.hip, 9 .. 64 gemm_q4k.hip), or nullptr
+    uint32_t f32_min_nb;   // FP32: sequences from which a projection takes the MFMA GEMM (gemm_f32.hip); 0 or > 64: never
+    float *f32x; size_t f32x_floats;  // FP32: scratch for the operand-order activations of a GEMM launch, or nullptr
 };
 RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp = nullptr);   // gp: the plan behind a ROUTE_FRAG_* answer
 // The slices route_projection() cuts a GEMV launch of a.nb sequences into (FP32; Q4K; Q80, the routes that end in the GEMV kernels:

@@ -257,6 +257,36 @@ extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
     return 0;
 }
 
+// The FP32 MFMA GEMM launch route_projection() issues for a descriptor of 9..64 sequences in a model (the scratch present, f32_min_nb = 9;
+// nano_hip_op_fused_gemv reaches it with use_gemm = 1): route_kind() and the F32GemmPlan (kernels.h) the launcher consumes.  Host
+// arithmetic only -- no device is touched, and of the descriptor's pointers only norm_w and attn_part are looked at (null or not).
+// out = {route, the plan's fields in the order of the struct, takes}; a descriptor the GEMM refuses reports the sliced route, takes = 1 and
+// zeros for the plan (nano_hip_f32_gemv_plan reports those launches, and their refusals).
+extern "C" int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_F32_GEMM_PLAN_WORDS]) {
+    static_assert(sizeof(F32GemmPlan) == (NANO_F32_GEMM_PLAN_WORDS - 2) * sizeof(uint32_t), "the query reports every field of the plan");
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    const NanoFusedGemvDesc &d = *dp;
+    if (d.quant != NANO_QUANT_F32) { nano_hip_set_error_("not an FP32 launch"); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    static float scratch_flag[4];                   // stands for the scratch: compared with null, never followed
+    GemvArgs a{};
+    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
+    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus ? cus : 256u;
+    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    a.norm_w = d.norm_w;
+    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    Q80Route r{};
+    r.quant = d.quant; r.cus = (int)a.cus; r.f32_min_nb = 9u;
+    r.f32x = scratch_flag; r.f32x_floats = ~(size_t)0;
+    memset(out, 0, NANO_F32_GEMM_PLAN_WORDS * sizeof(uint32_t));
+    const RouteKind k = route_kind(r, a);
+    out[0] = (uint32_t)k;
+    F32GemmPlan p{};
+    if (k == ROUTE_F32_GEMM && gemm_f32_plan(a, &p)) memcpy(out + 1, &p, sizeof(p));
+    out[NANO_F32_GEMM_PLAN_WORDS - 1] = 1u;
+    return 0;
+}
+
 // The Q80 launch route_projection() issues for a descriptor: route_kind() -- assuming the step's activation scratch is present, as in
 // nano_hip_op_fused_gemv below --, then for the routes that end in the Q80 GEMV kernels gemv_q80_plan() of the first slice and
 // route_gemv_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
@@ -422,7 +452,7 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     hipDeviceProp_t prop; OP_HIP(hipGetDeviceProperties(&prop, device));
     a.cus = (uint32_t)prop.multiProcessorCount;
     // the step's own router (route.hip): use_gemm = 1 forces the fragment-order route of batched steps (quantizer launch + G6 MODE F /
-    // GC / G2); ordered = 1 is strict mode (the reference's group order in every kernel)
+    // GC / G2; FP32: lets 9..64 sequences take the MFMA GEMM); ordered = 1 is strict mode (the reference's group order in every kernel)
     a.ordered = d.ordered ? 1u : 0u;
     Q80Route r{};
     r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
@@ -436,7 +466,13 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         r.q4x = B.alloc<uint8_t>(r.q4x_bytes);
         OP_CHECK(r.q4x, "device alloc failed");
     }
-    if (d.use_gemm && (d.quant != NANO_QUANT_Q80 || !route_takes_fragments(route_kind(r, a)))) { nano_hip_set_error_("the batched GEMM route does not take this launch"); return NANO_HIP_EINVAL; }
+    if (d.quant == NANO_QUANT_F32 && d.use_gemm && d.nb > 8) {          // the operand-order activations of gemm_f32.hip; a shape it refuses keeps the slices
+        r.f32_min_nb = 9u;
+        r.f32x_floats = (size_t)((d.nb + 15) / 16) * 16 * ((d.n + 127) & ~(size_t)127);
+        r.f32x = B.alloc<float>(r.f32x_floats);
+        OP_CHECK(r.f32x, "device alloc failed");
+    }
+    if (d.use_gemm && d.quant != NANO_QUANT_F32 && (d.quant != NANO_QUANT_Q80 || !route_takes_fragments(route_kind(r, a)))) { nano_hip_set_error_("the batched GEMM route does not take this launch"); return NANO_HIP_EINVAL; }
     if (d.route_out) *d.route_out = (uint32_t)route_kind(r, a);
     const hipError_t e = route_projection(r, a, 0);
     OP_HIP(e);

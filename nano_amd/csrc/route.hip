@@ -3,6 +3,7 @@
 // exercise exactly the launches a step issues.
 //
 //   FP32 / Q4K              the GEMV kernels (gemv_f32.hip, gemv_q4k.hip), more sequences than fit a launch's LDS (at most 8) in groups
+//   FP32, 9..64 sequences   the activation prologue launch + the FP32 MFMA GEMM (gemm_f32.hip) where it takes the launch: same bits
 //   Q4K, 9..64 sequences    the staged-group quantizer launch + the int8 MFMA GEMM (gemm_q4k.hip) where it takes the launch: same bits
 //   Q80, fast path          SLAB GEMV (1..8 sequences on the small per-layer matrices; 1..2 on those of >= 8 M weights)   gemv_q80_impl.h
 //                           the batched kernels, fragment-order activations: whichever gemm_q80_plan() names      gemm_q80_host.h
@@ -51,7 +52,12 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp) {
         if (a.nb >= r.mfma_min_nb && r.q4x && (uint64_t)a.nb * a.n <= r.q4x_bytes && gemm_q4k_supports(a)) return ROUTE_Q4K_GEMM;
         return ROUTE_Q4K;
     }
-    if (r.quant != NANO_QUANT_Q80) return a.nb > 8 ? ROUTE_GEMV_SLICED : ROUTE_GEMV;
+    if (r.quant != NANO_QUANT_Q80) {
+        // FP32: from f32_min_nb sequences on every weight byte is read once per launch; what the GEMM refuses (gemm_f32_plan()) keeps the slices
+        F32GemmPlan fp;
+        if (r.f32_min_nb && a.nb >= r.f32_min_nb && r.f32x && gemm_f32_plan(a, &fp) && fp.xs_floats <= r.f32x_floats) return ROUTE_F32_GEMM;
+        return a.nb > 8 ? ROUTE_GEMV_SLICED : ROUTE_GEMV;
+    }
     const bool scratch = r.gq && r.gxs;
     const bool canon = q80_canonical(a);
     const bool wide = route_is_wide(a);
@@ -125,6 +131,10 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     a.cus = (uint32_t)r.cus;
     Q80GemmPlan gp{};
     const RouteKind k = route_kind(r, a, &gp);
+    if (k == ROUTE_F32_GEMM) {
+        a.f32_scratch = r.f32x; a.f32_scratch_floats = r.f32x_floats;
+        return launch_gemm_f32(a, st);
+    }
     if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) return launch_gemv_sliced(r.quant, a, st);      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
     switch (k) {
     case ROUTE_Q4K:
