@@ -401,7 +401,8 @@ int nano_hip_op_argmax(int device, const float *x, uint32_t n, uint32_t *idx);
  * quantization prologue, optional split-attention combine, store / residual / SwiGLU epilogue), for operator tests of those
  * kernels on caller-chosen inputs.  What it replaces in the reference: rmsnorm + quantize + matmul(_quant | _q4k) (+ the
  * residual add / SwiGLU) of one projection, infer/infer.c:758-786 (kind 0), 885-908 and 950-965 (kind 1), 914-944 (kind 2).
- * All pointers are host pointers. */
+ * With tile_max the launch is also asked for the arg-max partials exactly where a step's classifier launch is, and with argmax_out
+ * the arg-max kernel of a greedy step (sample_argmax, infer.c:1026-1037) runs behind it.  All pointers are host pointers. */
 typedef struct NanoFusedGemvDesc {
     uint32_t quant;             /* NANO_QUANT_F32 / _Q80 / _Q4K */
     uint32_t gs;                /* Q80 group size */
@@ -422,6 +423,17 @@ typedef struct NanoFusedGemvDesc {
     float *out;                 /* [nb][sum of rows] (kind 2: [nb][rows[0]]); kind 1: holds the residual stream on entry */
     uint32_t out_slots;         /* 0: nb.  Else out holds out_slots >= nb sequence slots; a launch must leave those beyond nb alone */
     uint32_t out_stride;        /* 0: sum of rows.  Else floats between the slots of out (>= sum of rows; the rest are guard elements) */
+    /* optional, for tests of the arg-max partials a step's classifier launch writes (all NULL / 0: a launch without them) */
+    float *tile_max;            /* float[tile_slots][tile_pairs][2], or NULL.  It goes to the device whole and comes back whole, and stands for
+                                 * the step's partials buffer: the launch is asked for partials exactly where the step's classifier is (one STORE
+                                 * tensor, at most 8 sequences, a route that takes no fragments, Q4K: a batch that runs as one launch) and then writes,
+                                 * as in a step, nb x ntiles (max value, bits of its first row | 0xffffffff: no row) pairs densely from the start of
+                                 * the buffer -- pair t of sequence b at float (b * ntiles + t) * 2 -- and nothing else */
+    uint32_t tile_slots;        /* capacity of tile_max: >= nb, */
+    uint32_t tile_pairs;        /* ... and >= the pairs per sequence the launch writes (else an error, before any launch) */
+    uint32_t *ntiles_out;       /* optional: pairs per sequence the launch was asked for and the arg-max kernel reads; 0: the launch was not asked */
+    uint32_t *argmax_out;       /* optional uint32_t[nb]: behind the launch, the arg-max kernel as a greedy step builds it -- over out[b][: sum of
+                                 * rows], from the partials where the launch was asked for them, scanning the result otherwise */
 } NanoFusedGemvDesc;
 int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
 /* The FP32 launch the router issues for descriptor d (quant = NANO_QUANT_F32), from the functions the launcher and the router follow:

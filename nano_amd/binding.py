@@ -34,7 +34,8 @@ class NanoFusedGemvDesc(C.Structure):
                 ("rows", C.c_uint32 * 3), ("w", C.c_void_p * 3), ("ws", C.c_void_p * 3), ("x", C.c_void_p), ("norm_w", C.c_void_p),
                 ("attn_part", C.c_void_p), ("attn_ml", C.c_void_p), ("attn_nsplit", C.c_uint32), ("attn_n_head", C.c_uint32),
                 ("attn_hd", C.c_uint32), ("use_gemm", C.c_uint32), ("ordered", C.c_uint32), ("route_out", C.c_void_p), ("out", C.c_void_p),
-                ("out_slots", C.c_uint32), ("out_stride", C.c_uint32)]
+                ("out_slots", C.c_uint32), ("out_stride", C.c_uint32), ("tile_max", C.c_void_p), ("tile_slots", C.c_uint32),
+                ("tile_pairs", C.c_uint32), ("ntiles_out", C.c_void_p), ("argmax_out", C.c_void_p)]
 
 
 class NanoAttnDecodeDesc(C.Structure):
@@ -619,7 +620,7 @@ def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
 
 
 def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, resid=None, attn=None, use_gemm=False, ordered=False,
-                  want_route=False, guard=None, device=0):
+                  want_route=False, guard=None, partials=None, want_argmax=False, device=0):
     """One fused decode GEMV launch exactly as a decode step issues it (nano_hip_op_fused_gemv).
     quant: 0x00 F32 / 0x80 Q80 / 0x42 Q4K; kind: 0 store, 1 residual add, 2 SwiGLU.
     weights: list of (w, ws_or_None, rows) -- F32 float[rows, n]; Q80 int8[rows*n] + float scales; Q4K uint8 blocks (no frame).
@@ -629,7 +630,12 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     guard: None, or a float32 array [slots >= nb, stride >= rows_total] that IS the output buffer (slot b's result in [b, :rows_total];
     kind 1: it holds the residual stream there on entry) -- it goes to the device whole and comes back whole, so the caller sees whatever
     a launch wrote beyond its rows or its sequences; the returned out is that array.
-    Returns out[nb, rows_total] (want_route: (out, route name))."""
+    partials: None, or a float32 array [slots >= nb, pairs, 2] that IS the step's arg-max partials buffer: it goes to the device whole and
+    comes back whole; the launch is asked for partials exactly where the step's classifier is (route.hip route_asks_partials()) and then
+    writes nb x ntiles (max, bits of the first row) pairs densely from the start of the buffer -- partials.reshape(-1, 2)[b * ntiles + t].
+    want_argmax: behind the launch, the arg-max kernel as a greedy step builds it (from the partials where the launch wrote them).
+    Returns out[nb, rows_total]; with any of want_route / partials / want_argmax a tuple (out, route name if want_route,
+    ntiles if partials is given -- 0: the launch was not asked --, argmax uint32[nb] if want_argmax)."""
     d = NanoFusedGemvDesc()
     d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = quant, gs, kind, n, nb, len(weights)
     keep = []
@@ -659,10 +665,23 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     route = C.c_uint32(0xffffffff)
     d.route_out = C.cast(C.pointer(route), C.c_void_p)
     d.out = out.ctypes.data
+    ntiles = C.c_uint32(0xffffffff)
+    if partials is not None:
+        assert partials.dtype == np.float32 and partials.flags.c_contiguous and partials.ndim == 3 and partials.shape[2] == 2
+        d.tile_max, d.tile_slots, d.tile_pairs = partials.ctypes.data, partials.shape[0], partials.shape[1]
+        d.ntiles_out = C.cast(C.pointer(ntiles), C.c_void_p)
+    amax = np.full(nb, 0xffffffff, np.uint32)
+    if want_argmax:
+        d.argmax_out = amax.ctypes.data
     check(lib().nano_hip_op_fused_gemv(device, C.byref(d)))
+    res = (out,)
     if want_route:
-        return out, (ROUTE_NAMES[route.value] if route.value < len(ROUTE_NAMES) else "?")
-    return out
+        res += (ROUTE_NAMES[route.value] if route.value < len(ROUTE_NAMES) else "?",)
+    if partials is not None:
+        res += (int(ntiles.value),)
+    if want_argmax:
+        res += (amax,)
+    return res if len(res) > 1 else out
 
 
 def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n_layer, layer, S, range_hint, rope_cos, rope_sin,

@@ -42,9 +42,8 @@ static GemvArgs classifier_args(const NanoHipModel *m, uint32_t nb, float *dst) 
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out, float *dst) {
     GemvArgs a = classifier_args(m, nb, dst ? dst : m->logits);
     a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes; a.cus = (uint32_t)m->cus;      // (what route_projection() will set: the partial count must match the launch)
-    uint32_t per = 0, launches = 0;
-    if (ntiles_out && nb <= 8 && !route_takes_fragments(kind_of(m, a)) &&
-        (m->d.quant_type != NANO_QUANT_Q4K || (route_gemv_slices(m->d.quant_type, a, &per, &launches) && launches == 1))) {      // per-tile arg-max partials for the sampler (Q4K: not for sliced launches)
+    a.ordered = (m->strict || m->exact) ? 1u : 0u;                     // (as gemv() sends it)
+    if (ntiles_out && route_asks_partials(route_of(m), a)) {          // per-tile arg-max partials for the sampler (route.hip: the operator's condition too)
         a.tile_max = m->tile_max;
         *ntiles_out = gemv_tiles(m->d.quant_type, a);
     }

@@ -227,6 +227,8 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp = nul
 // changes: the kernels are bit for bit per sequence whatever the capacity.  false: not even one sequence fits, or the shape is refused
 // (hipErrorInvalidValue before any launch)
 bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_t *launches);
+// whether the launch of `a` is asked for arg-max partials (a.tile_max): the one condition of the step's classifier and of the operator
+bool route_asks_partials(const Q80Route &r, GemvArgs a);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
 uint32_t route_norm_order(const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);

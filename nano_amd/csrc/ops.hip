@@ -401,6 +401,10 @@ extern "C" int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
 }
 
 // One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs.
+// With d.tile_max the launch is the step's classifier launch where route_asks_partials() (route.hip, enqueue_classifier's own condition)
+// says so: it is handed the caller's partials buffer -- uploaded whole, read back whole -- and writes nb x gemv_tiles() pairs into it as
+// into the step's buffer; *d.ntiles_out reports that count (0: not asked).  With d.argmax_out the arg-max kernel runs behind the launch
+// as a MODE_ARGMAX step builds it (backend_step.hip): over the launch's output, from the partials if the launch was asked for them.
 extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     int rc; if ((rc = begin(device))) return rc;
     if (!dp) { nano_hip_set_error_("null descriptor"); return NANO_HIP_EINVAL; }
@@ -474,10 +478,35 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     }
     if (d.use_gemm && d.quant != NANO_QUANT_F32 && (d.quant != NANO_QUANT_Q80 || !route_takes_fragments(route_kind(r, a)))) { nano_hip_set_error_("the batched GEMM route does not take this launch"); return NANO_HIP_EINVAL; }
     if (d.route_out) *d.route_out = (uint32_t)route_kind(r, a);
+    // the step's arg-max partials (enqueue_classifier): asked for where route_asks_partials() says so, into the caller's buffer
+    float *dtm = nullptr;
+    uint32_t ntiles = 0;
+    const size_t tm_floats = (size_t)d.tile_slots * d.tile_pairs * 2;
+    if (d.tile_max) {
+        if (d.tile_slots < d.nb) { nano_hip_set_error_("tile_slots smaller than the batch"); return NANO_HIP_EINVAL; }
+        dtm = tm_floats ? B.upload(d.tile_max, tm_floats) : B.alloc<float>(1);
+        OP_CHECK(dtm, "device alloc failed");
+        if (route_asks_partials(r, a)) {
+            a.tile_max = dtm;
+            GemvArgs t = a;
+            t.cus = (uint32_t)r.cus; t.q4_scratch = r.q4x; t.q4_scratch_bytes = r.q4x_bytes;      // (what route_projection() will set: the count must match the launch)
+            ntiles = gemv_tiles(d.quant, t);
+            if (d.tile_pairs < ntiles) { nano_hip_set_error_("tile_pairs smaller than the launch's partials"); return NANO_HIP_EINVAL; }
+        }
+    }
+    if (d.ntiles_out) *d.ntiles_out = ntiles;
+    uint32_t *damax = nullptr;
+    if (d.argmax_out) { damax = B.alloc<uint32_t>(d.nb); OP_CHECK(damax, "device alloc failed"); }
     const hipError_t e = route_projection(r, a, 0);
     OP_HIP(e);
+    if (damax) {                                                    // (backend_step.hip MODE_ARGMAX: no token / trace / embedding state)
+        ArgmaxArgs aa{ dout, rows_total, stride, damax, nullptr, nullptr, nullptr, nullptr, d.nb, ntiles ? dtm : nullptr, ntiles };
+        OP_HIP(launch_argmax(aa, d.nb, 0));
+    }
     OP_HIP(hipDeviceSynchronize());
     OP_HIP(hipMemcpy(d.out, dout, (size_t)slots * stride * 4, hipMemcpyDeviceToHost));
+    if (dtm && tm_floats) OP_HIP(hipMemcpy(d.tile_max, dtm, tm_floats * 4, hipMemcpyDeviceToHost));
+    if (damax) OP_HIP(hipMemcpy(d.argmax_out, damax, (size_t)d.nb * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

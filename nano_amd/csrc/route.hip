@@ -113,6 +113,19 @@ bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_
     *launches = (a.nb + fit - 1) / fit;
     return true;
 }
+// Whether the launch route_projection(r, a) issues is asked for arg-max partials (GemvArgs::tile_max): one STORE tensor of at most 8
+// sequences on a route that takes no fragments, and for Q4K a batch route_gemv_slices() leaves in one launch (gemv_slice(): a sliced
+// launch writes none).  The step's classifier (backend_step.hip enqueue_classifier) and the operator entry point (ops.hip
+// nano_hip_op_fused_gemv) both ask here, so that an operator test runs the launch a step runs.  a.ordered as the launch will carry it.
+// FINDING, left as it was: Q80 is not asked how many launches the batch takes.  A STREAM classifier on rows of more than ~18 200 values
+// at 5..8 sequences (group size 32: 18 432 values run as 4 + 1) is cut by route_gemv_slices(), its slices write no partials, and
+// gemv_tiles() still reports STREAM_WGS * 4 of them.  No model has such rows; the one-launch test of Q4K would close it.
+bool route_asks_partials(const Q80Route &r, GemvArgs a) {
+    a.cus = (uint32_t)r.cus; a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;      // (what route_projection() will set)
+    if (a.epi != GEMV_EPI_STORE || a.nseg != 1 || a.nb > 8 || route_takes_fragments(route_kind(r, a))) return false;
+    uint32_t per = 0, launches = 0;
+    return r.quant != NANO_QUANT_Q4K || (route_gemv_slices(r.quant, a, &per, &launches) && launches == 1);
+}
 // the GEMV launches of a.nb sequences, cut where route_gemv_slices() says so; a shape of which not even one sequence fits is refused
 // before any launch
 static hipError_t launch_gemv_sliced(uint32_t quant, const GemvArgs &a, hipStream_t st) {

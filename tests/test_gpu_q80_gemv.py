@@ -21,7 +21,13 @@ BARS, none of them new.
     expf against libm: test_k4_norm_swiglu_q80's bar).
 EVERY BATCHED CASE: each sequence bit-equals the same launch of that sequence alone; the launch runs in a guarded buffer -- nb + 8 slots
 of rows_total + 1 floats filled with a sentinel -- and every element outside [b < nb, : rows_total] must come back untouched (the dead
-slots of a capacity-4 / -8 kernel at 3 / 5 / 6 / 7 sequences are where a stray store would land)."""
+slots of a capacity-4 / -8 kernel at 3 / 5 / 6 / 7 sequences are where a stray store would land).
+STREAM CASES also run as the step's classifier launch runs (tests/test_gpu_q4k_gemv.py PARTIALS): with a partials buffer of nb + 2 slots x
+partials + 4 pairs prefilled with (+inf, row 0).  The launch reports STREAM_WGS * 4 pairs per sequence, one per wave; every one of the
+nb * ntiles pairs is overwritten and every pair behind them untouched; a wave owns strided 16-row tiles, so instead of a row mapping every
+written pair (v, i) has i == 0xffffffff (an idle wave) or bits(out[b, i]) == bits(v); the arg-max kernel's rule over the pairs, the arg-max
+kernel behind the launch and the arg-max kernel scanning a launch without partials all give np.argmax(out[b]).  One case duplicates the
+arg-max row's weights and scales into rows of one 16-row tile, of another tile of the same wave and of another workgroup's tile."""
 import numpy as np
 import pytest
 
@@ -30,6 +36,8 @@ from test_q80_gemv_plan import UNIVERSE, VAR, ROLE, SLAB, STREAM, canonical
 
 Q80 = 0x80
 SENTINEL = np.float32(-12345.678)
+POISON = np.array([np.inf, 0.0], np.float32)               # (+inf, row 0): wins any reduction that reads it
+NO_ROW = 0xffffffff
 
 
 def bits(a):
@@ -47,12 +55,13 @@ def silu_mul(a, b):
         return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
-def case(cid, gs, kind, n, rows, nb_, want, norm=False, comb=None, **more):
+def case(cid, gs, kind, n, rows, nb_, want, norm=False, comb=None, ties=False, **more):
     """kind 0 store / 1 residual add / 2 SwiGLU (rows: two equal counts); comb = (n_head, head_dim, split sums) for a launch whose prologue
-    combines split-attention partials; want = (kernel, B, NV, UPW, variant) of the fast path's launch, more = further plan fields"""
+    combines split-attention partials; want = (kernel, B, NV, UPW, variant) of the fast path's launch, more = further plan fields; ties:
+    the arg-max row's weights duplicated (STREAM)"""
     k, B, nv, upw, var = want
     target = dict(kernel=k, B=B, nv=nv, upw=upw, variant=VAR[var], **more)
-    return pytest.param(dict(id=cid, gs=gs, kind=kind, n=n, rows=tuple(rows), nb=nb_, norm=norm, comb=comb, target=target), id=cid)
+    return pytest.param(dict(id=cid, gs=gs, kind=kind, n=n, rows=tuple(rows), nb=nb_, norm=norm, comb=comb, ties=ties, target=target), id=cid)
 
 
 R = {k: ROLE[k] for k in ROLE}
@@ -155,6 +164,8 @@ CASES = [
     case("stream-b8-nv1-5", 32, 0, 96, (16391,), 5, (STREAM, 8, 1, 0, "plain"), norm=True),
     case("stream-b8-nv1-8-gs64", 64, 0, 256, (16400,), 8, (STREAM, 8, 1, 0, "plain"), norm=True),
     case("stream-b8-loop-5", 64, 0, 1088, (65536,), 5, (STREAM, 8, 0, 0, "plain"), norm=True),
+    # 4099 tiles on 4096 waves: waves 0..2 own two tiles; the arg-max row duplicated (TIE_ROWS)
+    case("stream-b1-ties-two-tiles-a-wave", 32, 0, 64, (65573,), 1, (STREAM, 1, 1, 0, "plain"), norm=True, ties=True, role=R["norm_store"]),
 ]
 
 
@@ -211,8 +222,9 @@ def references(oracle, c, I, b, W):
     return ref, ref
 
 
-def launch(c, I, *, kind=None, ordered=False, sl=None, guarded=True):
-    """the case's launch, or with sl = b the same launch of sequence b alone; the batched launch runs in a guarded buffer"""
+def launch(c, I, *, kind=None, ordered=False, sl=None, guarded=True, partials=None, want_argmax=False):
+    """the case's launch, or with sl = b the same launch of sequence b alone; the batched launch runs in a guarded buffer (partials: the
+    step's partials buffer, want_argmax: the arg-max kernel behind the launch -- then (out, route, ntiles or None, argmax or None))"""
     kind = c["kind"] if kind is None else kind
     rt = rows_total(c) if kind == c["kind"] else sum(c["rows"])
     if sl is not None:
@@ -223,12 +235,68 @@ def launch(c, I, *, kind=None, ordered=False, sl=None, guarded=True):
     g = np.full((c["nb"] + 8, rt + 1), SENTINEL, np.float32)
     if I["old"] is not None:
         g[:c["nb"], :rt] = I["old"]
-    _, route = nb.op_fused_gemv(Q80, kind, c["n"], I["W"], None if I["attn"] else I["x"], I["nw"], gs=c["gs"], nb=c["nb"], ordered=ordered,
-                                attn=I["attn"], guard=g, want_route=True)
+    res = nb.op_fused_gemv(Q80, kind, c["n"], I["W"], None if I["attn"] else I["x"], I["nw"], gs=c["gs"], nb=c["nb"], ordered=ordered,
+                           attn=I["attn"], guard=g, want_route=True, partials=partials, want_argmax=want_argmax)
+    route = res[1]
     assert np.all(bits(g[:, rt]) == bits(SENTINEL)), (c["id"], ordered, "a guard element behind a sequence's rows changed")
     assert np.all(bits(g[c["nb"]:]) == bits(SENTINEL)), (c["id"], ordered, "slots beyond the batch were written",
                                                          (np.flatnonzero((bits(g[c["nb"]:]) != bits(SENTINEL)).any(axis=1)) + c["nb"]).tolist())
+    if partials is not None or want_argmax:
+        return g[:c["nb"], :rt], route, res[2] if partials is not None else None, res[-1] if want_argmax else None
     return g[:c["nb"], :rt], route
+
+
+# rows the tie case copies the arg-max row's weights and scales into: two of tile 1 (wave 1), one of tile 4097 (wave 1's second tile), one of
+# tile 2000 (another workgroup) -- the arg-max row itself stays where the random weights put it
+TIE_ROWS = (16 + 3, 16 + 9, 4097 * 16 + 2, 2000 * 16 + 7)
+
+
+def plant_ties(c, I, ref):
+    (wq, ws, r), = I["W"]
+    n, ng = c["n"], c["n"] // c["gs"]
+    assert c["nb"] == 1 and r > max(TIE_ROWS) and (r + 15) // 16 > 4097
+    m = int(np.argmax(ref))
+    for t in TIE_ROWS:
+        wq[t * n:(t + 1) * n] = wq[m * n:(m + 1) * n]
+        ws[t * ng:(t + 1) * ng] = ws[m * ng:(m + 1) * ng]
+
+
+def reduce_pairs(pairs):
+    """argmax_kernel's rule over (value, row bits) pairs: no-row pairs skipped, the larger value, on equal values the lower row"""
+    best, bi = None, NO_ROW
+    for v, i in zip(pairs[:, 0].tolist(), pairs[:, 1].view(np.uint32).tolist()):
+        if i != NO_ROW and (bi == NO_ROW or v > best or (v == best and i < bi)):
+            best, bi = v, i
+    return 0 if bi == NO_ROW else bi
+
+
+def check_stream_partials(c, I, q, fused):
+    """the STREAM launch as the step's classifier launch: one (max, first row) pair per wave and sequence"""
+    nb_, rows = c["nb"], c["rows"][0]
+    want_tiles = q["grid"] * 4
+    buf = np.empty((nb_ + 2, want_tiles + 4, 2), np.float32)
+    buf[:] = POISON
+    out, _, ntiles, amax = launch(c, I, partials=buf, want_argmax=True)
+    assert np.array_equal(bits(out), bits(fused)), (c["id"], "the launch with partials differs")
+    assert ntiles == want_tiles, (c["id"], ntiles, q)
+    flat = buf.reshape(-1, 2)
+    inside, rest = flat[:nb_ * ntiles].reshape(nb_, ntiles, 2), flat[nb_ * ntiles:]
+    stale = np.argwhere((bits(inside) == bits(POISON)).all(axis=2))
+    assert stale.size == 0, (c["id"], "pairs the arg-max kernel reads were not written: (sequence, wave)", stale[:6].tolist())
+    touched = np.flatnonzero((bits(rest) != bits(POISON)).any(axis=1)) + nb_ * ntiles
+    assert touched.size == 0, (c["id"], "pairs beyond the launch's nb * ntiles were written", touched[:6].tolist())
+    first = [int(np.argmax(out[b])) for b in range(nb_)]
+    for b in range(nb_):
+        i = inside[b, :, 1].view(np.uint32)
+        live = i != NO_ROW
+        assert live.any() and np.all(i[live] < rows), (c["id"], "sequence", b, "a pair names a row beyond the matrix")
+        bad = np.flatnonzero(live)[bits(out[b][i[live]]) != bits(inside[b, live, 0])]
+        assert bad.size == 0, (c["id"], "sequence", b, "waves whose pair is not (out[row], row)", bad[:6].tolist())
+        assert reduce_pairs(inside[b]) == first[b], (c["id"], "sequence", b, "the pairs do not reduce to the first maximum")
+    assert amax.tolist() == first, (c["id"], "arg-max from the partials", amax.tolist(), first)
+    scan, _, _, amax_scan = launch(c, I, want_argmax=True)                          # no partials buffer: the arg-max kernel scans the logits
+    assert np.array_equal(bits(scan), bits(fused)), (c["id"], "the launch without partials differs")
+    assert amax_scan.tolist() == first, (c["id"], "arg-max by scanning", amax_scan.tolist(), first)
 
 
 @pytest.mark.gpu
@@ -240,6 +308,10 @@ def test_q80_gemv_plan_case(oracle, c):
     kind, nb_ = c["kind"], c["nb"]
     canon = canonical(c["gs"], c["n"], kind, c["rows"], False)
     refs = [references(oracle, c, I, b, I["W"]) for b in range(nb_)]
+    if c["ties"]:
+        plant_ties(c, I, refs[0][0])
+        refs = [references(oracle, c, I, b, I["W"]) for b in range(nb_)]
+        assert np.all(bits(refs[0][0][list(TIE_ROWS)]) == bits(refs[0][0].max())) and int(np.argmax(refs[0][0])) == min(TIE_ROWS)
     errors = []
 
     def held(out, mode, what, b, want):
@@ -284,7 +356,10 @@ def test_q80_gemv_plan_case(oracle, c):
         for b in range(nb_):
             alone, _ = launch(c, I, sl=b)
             assert np.array_equal(bits(fused[b]), bits(alone)), (c["id"], "sequence", b, "differs from its launch alone", float(np.abs(fused[b] - alone).max()))
-    # 3. the plan, last
+    # 3. the arg-max partials of the STREAM launches
+    if q["kernel"] == STREAM:
+        check_stream_partials(c, I, q, fused)
+    # 4. the plan, last
     got = {k: (nb.ROUTE_NAMES[q[k]] if k == "route" else q[k]) for k in c["target"]}
     assert got == c["target"], f"{c['id']}: the launcher's plan is {q}, the case means {c['target']}: a retune moved this case -- pick a new shape for this target"
 
@@ -300,7 +375,7 @@ def test_cases_cover_every_plan_axis():
         got = {k: (nb.ROUTE_NAMES[q[k]] if k == "route" else q[k]) for k in c["target"]}
         assert got == c["target"], (c["id"], q)
         assert (q["kernel"], q["B"], q["nv"], q["upw"], q["variant"]) in UNIVERSE, (c["id"], "a plan the sweep does not know", q)
-        T.append(dict(q, id=c["id"], kind=c["kind"], n=c["n"], rows=c["rows"], nb=c["nb"], norm=c["norm"], comb=c["comb"] is not None,
+        T.append(dict(q, id=c["id"], kind=c["kind"], n=c["n"], rows=c["rows"], nb=c["nb"], norm=c["norm"], comb=c["comb"] is not None, ties=c["ties"],
                       total=rows_total(c), route_name=nb.ROUTE_NAMES[q["route"]]))
 
     def has(f=None, **kw):
@@ -341,6 +416,7 @@ def test_cases_cover_every_plan_axis():
     for nb_ in (1, 2, 3, 5, 8):
         need(("stream sequences", nb_), has(kernel=STREAM, nb=nb_))
     need("stream, a ragged last tile", has(kernel=STREAM, rows=(16391,)))
+    need("stream, two tiles a wave with the arg-max row duplicated", has(kernel=STREAM, ties=True, f=lambda t: (t["total"] + 15) // 16 > 4 * t["grid"] + 1))
     for gs in (32, 64, 128, 256):
         need(("stream group size", gs), has(kernel=STREAM, gs=gs))
     assert not missing, missing

@@ -32,6 +32,27 @@ ROWS = [1, 3, 4, 7, 36, 333, 768, 2560, 9728, 16384, 16391, 151936]          # t
 ROWS4 = [r for r in ROWS if r % 4 == 0]
 NBS = [1, 2, 3, 4, 5, 6, 7, 8, 11, 64]
 
+SEEN = set()                # plan_tuple() of every GEMV launch the two sweeps below met
+DONE = set()                # ... the sweeps that ran
+
+
+def plan_tuple(p):
+    """the kernel instantiation a taken GEMV plan names: ("slab", role, B, nv, ipt) of gemv_q4k_slab_kernel<ROLE, B, NV, IPT> or
+    ("chunk", role, NB, nv, d, loop) of gemv_q4k_chunk_kernel<ROLE, NV, D, LOOP, NB> (tests/test_gpu_q4k_gemv.py names its cases by it)"""
+    if p["kernel"] == SLAB:
+        return ("slab", p["role"], p["B"], p["nv"], p["ipt"])
+    assert p["kernel"] == CHUNK, p
+    return ("chunk", p["role"], p["B"], p["nv"], p["d"], p["loop"])
+
+
+def sweep(grid):
+    """check() over a grid, the GEMV launches it meets noted in SEEN"""
+    for c in grid:
+        p = check(*c)
+        if p["takes"] and nb.ROUTE_NAMES[p["route"]] == "q4k":
+            SEEN.add(plan_tuple(p))
+        yield p
+
 
 def capacity(nb_):
     return 1 if nb_ <= 1 else 2 if nb_ <= 2 else 4 if nb_ <= 4 else 8
@@ -224,13 +245,56 @@ def length_grid():
 
 
 def test_named_shapes_full_cross():
-    seen = sum(1 for c in named_grid() if check(*c) is not None)
+    seen = sum(1 for p in sweep(named_grid()) if p is not None)
     assert seen > 30000
+    DONE.add("named")
 
 
 def test_every_row_length():
-    takes = sum(check(*c)["takes"] for c in length_grid())
+    takes = sum(p["takes"] for p in sweep(length_grid()))
     assert takes > 40000
+    DONE.add("lengths")
+
+
+# What the two sweeps above reach of the template space with the default 256 CUs: 55 instantiations of gemv_q4k_slab_kernel as
+# role -> (B, NV, IPT) and 90 of gemv_q4k_chunk_kernel as role -> (NB, NV, D, LOOP).  tests/test_gpu_q4k_gemv.py runs a case for every one
+# of them on the device.  The launchers instantiate more (the slab kernel every (NV, IPT) of {0, 1, 2, 4} x {1, 2, 4} with B * NV <= 8
+# per role and capacity): no descriptor of the sweeps reaches the rest, e.g. the LDS-staged activation (NV = 0) on fewer than 4 items.
+SLAB_TUPLES = {
+    "generic": [(1, 0, 4), (1, 1, 1), (1, 1, 2), (1, 1, 4), (1, 2, 1), (1, 2, 2), (1, 2, 4), (1, 4, 2), (1, 4, 4), (2, 1, 1), (2, 1, 2),
+        (2, 1, 4), (2, 2, 1), (2, 2, 2), (2, 2, 4), (2, 4, 2), (2, 4, 4), (4, 1, 1), (4, 1, 2), (4, 1, 4), (4, 2, 1), (4, 2, 2),
+        (4, 2, 4), (8, 1, 1), (8, 1, 2), (8, 1, 4)],
+    "norm_store": [(1, 0, 4), (1, 1, 1), (1, 1, 2), (1, 1, 4), (1, 2, 1), (1, 2, 4), (1, 4, 2), (1, 4, 4)],
+    "resid": [(1, 0, 4), (1, 1, 1), (1, 1, 2), (1, 1, 4), (1, 2, 1), (1, 2, 4), (1, 4, 2), (1, 4, 4)],
+    "resid_combine": [(1, 0, 4), (1, 1, 1), (1, 1, 2), (1, 1, 4), (1, 2, 1), (1, 2, 4), (1, 4, 2), (1, 4, 4)],
+    "norm_swiglu": [(1, 1, 1), (1, 1, 2), (1, 1, 4), (1, 2, 4), (1, 4, 4)],
+}
+CHUNK_TUPLES = {
+    "generic": [(1, 1, 1, 0), (1, 1, 2, 0), (1, 1, 4, 0), (1, 1, 8, 0), (1, 1, 8, 1), (1, 2, 1, 0), (1, 2, 2, 0), (1, 2, 4, 0),
+        (1, 2, 8, 0), (1, 2, 8, 1), (1, 4, 1, 0), (1, 4, 2, 0), (1, 4, 4, 0), (1, 4, 8, 0), (1, 4, 8, 1), (2, 1, 1, 0), (2, 1, 2, 0),
+        (2, 1, 4, 0), (2, 1, 8, 0), (2, 1, 8, 1), (4, 1, 1, 0), (4, 1, 2, 0), (4, 1, 4, 0), (4, 1, 8, 0), (4, 1, 8, 1), (8, 1, 1, 0),
+        (8, 1, 2, 0), (8, 1, 4, 0), (8, 1, 8, 0), (8, 1, 8, 1)],
+    "norm_store": [(1, 1, 1, 0), (1, 1, 2, 0), (1, 1, 4, 0), (1, 1, 8, 0), (1, 1, 8, 1), (1, 2, 1, 0), (1, 2, 2, 0), (1, 2, 4, 0),
+        (1, 2, 8, 0), (1, 2, 8, 1), (1, 4, 1, 0), (1, 4, 2, 0), (1, 4, 4, 0), (1, 4, 8, 0), (1, 4, 8, 1)],
+    "resid": [(1, 1, 1, 0), (1, 1, 2, 0), (1, 1, 4, 0), (1, 1, 8, 0), (1, 1, 8, 1), (1, 2, 1, 0), (1, 2, 2, 0), (1, 2, 4, 0),
+        (1, 2, 8, 0), (1, 2, 8, 1), (1, 4, 1, 0), (1, 4, 2, 0), (1, 4, 4, 0), (1, 4, 8, 0), (1, 4, 8, 1)],
+    "resid_combine": [(1, 1, 1, 0), (1, 1, 2, 0), (1, 1, 4, 0), (1, 1, 8, 0), (1, 1, 8, 1), (1, 2, 1, 0), (1, 2, 2, 0), (1, 2, 4, 0),
+        (1, 2, 8, 0), (1, 2, 8, 1), (1, 4, 1, 0), (1, 4, 2, 0), (1, 4, 4, 0), (1, 4, 8, 0), (1, 4, 8, 1)],
+    "norm_swiglu": [(1, 1, 1, 0), (1, 1, 2, 0), (1, 1, 4, 0), (1, 1, 8, 0), (1, 1, 8, 1), (1, 2, 1, 0), (1, 2, 2, 0), (1, 2, 4, 0),
+        (1, 2, 8, 0), (1, 2, 8, 1), (1, 4, 1, 0), (1, 4, 2, 0), (1, 4, 4, 0), (1, 4, 8, 0), (1, 4, 8, 1)],
+}
+UNIVERSE = {("slab", ROLE[r]) + t for r, ts in SLAB_TUPLES.items() for t in ts} | {("chunk", ROLE[r]) + t for r, ts in CHUNK_TUPLES.items() for t in ts}
+
+
+def test_universe_is_what_the_sweeps_reach():
+    """a retune that adds or drops a reachable instantiation fails here: move UNIVERSE, and the cases of tests/test_gpu_q4k_gemv.py with it"""
+    if "named" not in DONE:
+        test_named_shapes_full_cross()
+    if "lengths" not in DONE:
+        test_every_row_length()
+    print(sorted(SEEN))
+    assert len(UNIVERSE) == 145
+    assert SEEN == UNIVERSE, (sorted(SEEN - UNIVERSE), sorted(UNIVERSE - SEEN))
 
 
 def test_documented_refusals():
