@@ -250,6 +250,12 @@ int32_t nano_session_step_ids(Nano_Context *ctx, Nano_Session *session);
  * nano_mi355x.h): all twelve phases fire in the reference's order with that phase's tensors finished on the device,
  * the sampler runs in host C on the returned logits.  Slow; never on a timed path. */
 void nano_set_phase_observation(int on);
+/* Greedy decode with lookup drafts (nano_mi355x.h nano_hip_decode_lookup), opt-in: with max_draft = 1 .. 15 (or NANO_LOOKUP_DRAFT=n in the
+ * environment, read once) the greedy branch of generate_next_token (temperature 0, repetition penalty 1, no per-phase observation) runs
+ * one step of that loop per call with ngram 1 .. 3: a verify chunk's confirmed ids beyond the returned one are queued, and the following
+ * calls whose (pos, output_ids[pos]) continue them return from the queue without device work.  Any other call drops the queue.  The
+ * ids are nano_hip_decode_lookup's (see there for what that promises on wide matrices).  0 = today's path. */
+void nano_set_lookup_draft(int max_draft);
 /* Opaque device model behind an LLM (NanoHipModel*, nano_mi355x.h) for measurement tools. */
 void *nano_device_model(const LLM *llm);
 

@@ -196,6 +196,63 @@ int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *token
 int nano_hip_op_score_rows(int device, const float *logits, uint32_t rows, uint32_t V,
                            const uint32_t *targets, NanoHipTokenScore *out);
 
+/* ---- greedy decode with lookup drafts: several ids per weight read (opt-in) -----------------
+ * Greedy decode of sequence slot 0 in which a step may be a prefill chunk of K = max_draft + 1 rows: the last id plus a
+ * continuation guessed by looking the last ngram_min .. ngram_max ids up in the sequence's own history (longest suffix match, then
+ * the most recent; what followed it last time, extended periodically), verified by the chunk's own row arg-maxes.  Row i's arg-max is
+ * the id that follows row i's id; rows are accepted while the next row's fed id equals it, so a chunk emits 1 .. K ids and every
+ * emitted id is the arg-max of a row whose whole prefix is emitted ids.  Accept, append, lookup and the staging of the next step run on
+ * the device behind each step (lookup.hip); the host reads one 32-byte record per step.  A chunk never crosses a 64-position attention
+ * bucket (the rule of nano_hip_prefill's chunks): positions whose chunk would take a plain one-row step, and so does a step with
+ * no match, with fewer than 2 ids left, or whose chunk would pass max_seq_len / the RoPE table.
+ * What the ids are: wherever a prefill chunk's rows carry the bits of token-by-token feeding (the guarantee of nano_hip_prefill; every
+ * small-matrix route) they are exactly nano_hip_decode_greedy's.  On wide matrices (Qwen3-4B's shapes) launches of >= 3 rows
+ * normalise through a different reduction tree, a chunk row may differ from the one-row step in the last ulp, and the promise is the one
+ * batched prefill gives there: every emitted id is the arg-max of a fast-path chunk row, not necessarily decode_greedy's id at a near-tie.
+ * Strict and exact mode run the loop with max_draft treated as 0: plain reference-order steps, that mode's ids.  max_draft is also
+ * clipped to nano_hip_prefill_chunk_tokens() - 1 (a chunk holds no more rows than the per-token scratch).  LoRA, FP16 rows and the
+ * paged cache as in nano_hip_prefill.  is_causal = 0 is not offered. */
+typedef struct NanoHipLookupParams {
+    uint32_t max_draft;     /* 0 .. 15 drafted ids per verify chunk; 0 = plain steps only */
+    uint32_t ngram_max;     /* 1 .. 4: the longest suffix looked up */
+    uint32_t ngram_min;     /* 1 .. ngram_max: the shortest match that drafts */
+    uint32_t stop_token;    /* the loop ends after emitting it; UINT32_MAX = none */
+    uint32_t max_steps;     /* steps (plain or verify) after which the call returns; 0 = no limit */
+} NanoHipLookupParams;
+typedef struct NanoHipLookupStats {
+    uint32_t steps_plain, steps_verify;
+    uint32_t drafted;       /* steps_verify * (the clipped) max_draft */
+    uint32_t accepted;      /* draft rows confirmed, summed over the verify steps (before clipping to max_new / the stop token) */
+    uint32_t emitted;       /* = *n_out */
+} NanoHipLookupStats;
+/* Slot 0 holds positions 0 .. n_history-2 of history[0..n_history); history[n_history-1] is fed first.  Emits at most max_new ids
+ * into out_ids (host, max_new words), *n_out of them; stats may be NULL.  Afterwards slot 0 holds valid rows for positions
+ * 0 .. n_history + *n_out - 2, as after nano_hip_decode_greedy; rows beyond may hold rejected drafts' K / V and are rewritten before any
+ * causal step reads them.  The history lives on the device between calls: a history that extends the previous call's (its ids plus
+ * what that call emitted) uploads only the new ids.
+ * NANO_HIP_EINVAL before anything is queued: null m / history / p / out_ids / n_out, n_history == 0, an id >= vocab, max_draft > 15,
+ * ngram_max outside 1 .. 4, ngram_min outside 1 .. ngram_max, n_history - 1 + max_new beyond max_seq_len or the RoPE table, max_new
+ * beyond the trace capacity (max_seq_len * max_batch).  max_new == 0 returns 0 and touches nothing (*n_out = 0).
+ * A record the host cannot accept (nb_next not 1 or K, n not grown by the emitted count, n beyond the limit) ends the call with
+ * NANO_HIP_ERUNTIME.  The whole call is re-issued once after a hand-off gave up, as nano_hip_decode_greedy is. */
+int nano_hip_decode_lookup(NanoHipModel *m, const uint32_t *history, uint32_t n_history, uint32_t max_new,
+                           const NanoHipLookupParams *p, uint32_t *out_ids, uint32_t *n_out, NanoHipLookupStats *stats);
+/* For callers with a drafter of their own: nano_hip_prefill(m, slot, tokens, pos0, count) -- same chunking, same KV rows -- that also
+ * returns argmax_out[i] = the arg-max of row i's logits (the value nano_hip_prefill_score(...)[i].argmax holds) and *n_accepted = the
+ * largest a <= count-1 with tokens[i] == argmax_out[i-1] for all 1 <= i <= a (tokens[0] is the last committed id, tokens[1..] the
+ * draft).  Rows beyond pos0 + a hold the rejected ids' K / V: feed on from position pos0 + a + 1 with argmax_out[a].
+ * NANO_HIP_EINVAL as nano_hip_prefill, and for count == 0 or a null argmax_out; n_accepted may be NULL. */
+int nano_hip_verify_draft(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
+                          uint32_t *argmax_out, uint32_t *n_accepted);
+/* The between-steps kernel alone (lookup.hip; host pointers; operator tests).  history[0..n) in, room for n + 16 ids: the emitted ids are
+ * appended in place.  fed / amax [nb] describe the step it follows (nb = 0 .. 16; 0: none has run).  params as above (max_steps unused),
+ * left = ids still to emit, seq_limit = min(max_seq_len, RoPE rows).  record_out[8] = {emitted, accepted, nb_next, n, match_len,
+ * match_end, done, left}; next_tokens_out / next_pos_out [16] = the next step's rows (entries from nb_next on are UINT32_MAX).
+ * NANO_HIP_EINVAL: null pointers, n == 0 or n > 65536, nb > 16, parameters out of their ranges. */
+int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
+                            const NanoHipLookupParams *params, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
+                            uint32_t *next_tokens_out, uint32_t *next_pos_out);
+
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words
  * 6 / 7.  Attaching enables the module; nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.

@@ -110,6 +110,21 @@ TOKEN_SCORE_DTYPE = np.dtype([("logprob", "<f4"), ("target_logit", "<f4"), ("max
 assert TOKEN_SCORE_DTYPE.itemsize == C.sizeof(NanoHipTokenScore)
 
 
+class NanoHipLookupParams(C.Structure):
+    """include/nano_mi355x.h NanoHipLookupParams: greedy decode with lookup drafts (max_steps 0 = no limit; stop_token 0xffffffff = none)."""
+    _fields_ = [(n, C.c_uint32) for n in ("max_draft", "ngram_max", "ngram_min", "stop_token", "max_steps")]
+
+
+class NanoHipLookupStats(C.Structure):
+    """include/nano_mi355x.h NanoHipLookupStats (drafted = steps_verify * max_draft)."""
+    _fields_ = [(n, C.c_uint32) for n in ("steps_plain", "steps_verify", "drafted", "accepted", "emitted")]
+
+
+# the words of the record nano_hip_op_lookup_step returns (nano_amd/csrc/kernels.h LOOKUP_REC_*)
+LOOKUP_RECORD_FIELDS = ("emitted", "accepted", "nb_next", "n", "match_len", "match_end", "done", "left")
+LOOKUP_NO_STOP = 0xFFFFFFFF
+
+
 PHASE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)        # nano_hip_phase_fn(env, layer, phase)
 
 
@@ -146,6 +161,9 @@ def lib() -> C.CDLL:
     fn("nano_hip_prefill_chunk_tokens", C.c_uint32, [vp])
     fn("nano_hip_prefill_score", C.c_int, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp])
     fn("nano_hip_op_score_rows", C.c_int, [C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp])
+    fn("nano_hip_decode_lookup", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(NanoHipLookupParams), vp, C.POINTER(C.c_uint32), C.POINTER(NanoHipLookupStats)])
+    fn("nano_hip_verify_draft", C.c_int, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)])
+    fn("nano_hip_op_lookup_step", C.c_int, [C.c_int, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(NanoHipLookupParams), C.c_uint32, C.c_uint32, vp, vp, vp])
     fn("nano_hip_lora_attach", C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t])
     fn("nano_hip_lora_enable", C.c_int, [vp, C.c_int])
     fn("nano_hip_forward_sample", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
@@ -328,6 +346,26 @@ class DeviceModel:
         out = np.zeros(t.size, TOKEN_SCORE_DTYPE)
         check(lib().nano_hip_prefill_score(self.h, slot, t.ctypes.data, pos0, t.size, None if g is None else g.ctypes.data, out.ctypes.data))
         return out
+
+    def decode_lookup(self, history: Sequence[int], max_new: int, max_draft: int = 7, ngram_max: int = 3, ngram_min: int = 1,
+                      stop_token: Optional[int] = None, max_steps: int = 0):
+        """Greedy decode of slot 0 with lookup drafts (nano_hip_decode_lookup): slot 0 holds positions 0 .. len(history)-2, history[-1] is
+        fed first.  Returns (ids uint32[<= max_new], stats dict of steps_plain / steps_verify / drafted / accepted / emitted)."""
+        h = np.ascontiguousarray(history, np.uint32).reshape(-1)
+        p = NanoHipLookupParams(max_draft, ngram_max, ngram_min, LOOKUP_NO_STOP if stop_token is None else stop_token, max_steps)
+        out = np.zeros(max(max_new, 1), np.uint32)
+        n, st = C.c_uint32(0), NanoHipLookupStats()
+        check(lib().nano_hip_decode_lookup(self.h, h.ctypes.data if h.size else None, h.size, max_new, C.byref(p), out.ctypes.data, C.byref(n), C.byref(st)))
+        return out[:n.value].copy(), {k: int(getattr(st, k)) for k, _ in NanoHipLookupStats._fields_}
+
+    def verify_draft(self, tokens: Sequence[int], pos0: int = 0, slot: int = 0):
+        """prefill() that returns every fed row's arg-max (nano_hip_verify_draft): tokens[0] the last committed id, tokens[1:] a draft.
+        Returns (argmax uint32[len(tokens)], n_accepted)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        out = np.zeros(max(t.size, 1), np.uint32)
+        a = C.c_uint32(0)
+        check(lib().nano_hip_verify_draft(self.h, slot, t.ctypes.data if t.size else None, pos0, t.size, out.ctypes.data, C.byref(a)))
+        return out[:t.size], int(a.value)
 
     def prefill_chunk_tokens(self) -> int:
         """Prompt tokens prefill() feeds per weight read in the model's current mode (64 | 8; strict / exact mode: 1)."""
@@ -774,6 +812,25 @@ def op_score_rows(logits, targets=None, device=0) -> np.ndarray:
     out = np.zeros(l.shape[0], TOKEN_SCORE_DTYPE)
     check(lib().nano_hip_op_score_rows(device, l.ctypes.data, l.shape[0], l.shape[1], None if g is None else g.ctypes.data, out.ctypes.data))
     return out
+
+
+def op_lookup_step(history, fed=(), amax=(), *, left, max_draft=7, ngram_max=3, ngram_min=1, stop_token=None, seq_limit=1 << 30, device=0):
+    """lookup_step_kernel alone (nano_hip_op_lookup_step): behind a step that fed `fed` and left the row arg-maxes `amax` (both empty: no
+    step has run yet).  Returns (record dict of LOOKUP_RECORD_FIELDS, the history with the emitted ids appended, next tokens, next
+    positions -- the latter two all 16 words, 0xffffffff from nb_next on)."""
+    h = np.ascontiguousarray(history, np.uint32).reshape(-1)
+    f = np.ascontiguousarray(fed, np.uint32).reshape(-1)
+    g = np.ascontiguousarray(amax, np.uint32).reshape(-1)
+    if f.size != g.size:
+        raise ValueError(f"{f.size} fed ids but {g.size} arg-maxes")
+    buf = np.full(h.size + 16, 0xFFFFFFFF, np.uint32)
+    buf[:h.size] = h
+    p = NanoHipLookupParams(max_draft, ngram_max, ngram_min, LOOKUP_NO_STOP if stop_token is None else stop_token, 0)
+    rec, nt, npos = np.zeros(8, np.uint32), np.zeros(16, np.uint32), np.zeros(16, np.uint32)
+    check(lib().nano_hip_op_lookup_step(device, buf.ctypes.data, h.size, f.ctypes.data if f.size else None, g.ctypes.data if g.size else None, f.size,
+                                        C.byref(p), left, min(seq_limit, 0xFFFFFFFF), rec.ctypes.data, nt.ctypes.data, npos.ctypes.data))
+    r = dict(zip(LOOKUP_RECORD_FIELDS, (int(v) for v in rec)))
+    return r, buf[:r["n"]].copy() if h.size <= r["n"] <= buf.size else buf, nt, npos
 
 
 def op_argmax(x, device=0):

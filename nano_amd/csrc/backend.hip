@@ -73,6 +73,7 @@ static void destroy(NanoHipModel *m) {
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
+    lookup_free(m);
     for (hipEvent_t ev : { m->ev0, m->ev1, m->ev2 }) if (ev) (void)hipEventDestroy(ev);
     if (m->st) (void)hipStreamDestroy(m->st);
     delete m;
@@ -473,7 +474,7 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
 }
 // scratch of the scoring prefill, on its first call: the chunk's logits, the statistics kernel's partials, the chunk's targets and scores,
 // and the call's targets and scores (a call feeds at most max_seq_len tokens).  All or nothing: a failure leaves the model as it was.
-static int score_scratch(NanoHipModel *m) {
+int score_scratch(NanoHipModel *m) {
     if (m->score.logits) return 0;
     const size_t V = m->d.vocab_size, PF = m->pf_chunk, cap = m->S;
     NanoHipModel::Score s;
@@ -492,13 +493,44 @@ static int score_scratch(NanoHipModel *m) {
     m->score = s;
     return 0;
 }
+// One prefill chunk: nb rows of `slot`, their tokens and positions in m->tokens / m->pos, the last at last_pos.  replay: through a HIP graph per
+// (KV slot, range bucket, nb, key_kind) -- positions and tokens are device data, the slot's cache addresses are baked into the nodes.  The chunk
+// that meets a key first runs eagerly and is captured for the next one that reaches it; a failed capture only costs the replays (r.capture
+// is not looked at).  The cache of chunk graphs is bounded (oldest out).  Chunks of different kinds have different nodes: bits 56-57 of the
+// key = 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify, so none ever replays another's graph.
+hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind) {
+    const uint32_t range_hint = range_hint_of(m, 1, 1, last_pos);      // of the chunk's last token's own decode step
+    m->pf = true; m->pf_slot = slot;
+    hipError_t e = hipSuccess;
+    if (replay) {
+        const uint64_t key = (1ull << 62) | ((uint64_t)key_kind << 56) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
+        const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, mode, range_hint); });
+        e = r.step;
+        if (r.stored) {
+            if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
+                auto old = m->graphs.find(m->pf_graph_keys.front());
+                if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
+                m->pf_graph_keys.erase(m->pf_graph_keys.begin());
+            }
+            m->pf_graph_keys.push_back(key);
+        }
+    } else {
+        e = enqueue_step(m, nb, 1, mode, range_hint);                  // eager: one pass per chunk
+    }
+    m->pf = false;
+    m->nsplit = 1;                                                     // a prefill chunk leaves xba final (single split or the combine kernel), replayed or not
+    return e;
+}
 // Batched prefill: feeds `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot` in
 // passes of up to 64 (Q80, Q4K and FP32 through their MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
 // logits (the reference computes and discards them for prompt positions, infer.c:1146-1149).  The KV rows and every
 // later logit are the ones token-by-token feeding produces, bit for bit (same kernels and the same attention split per token).
 // score (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);
 // out[i] scores the logits of tokens[i] for targets[i] (targets == nullptr: for the row's own arg-max).  Nothing else differs.
-static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out) {
+// argmax_out (nano_hip_verify_draft): every chunk goes on into the classifier and the arg-max of all its rows (MODE_VERIFY); argmax_out[i] is row i's.
+int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
+                uint32_t *argmax_out) {
+    const bool verify = argmax_out != nullptr;
     if (!m || !tokens || (score && !out)) FAIL(NANO_HIP_EINVAL, "null argument");
     if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "slot %u out of range (max_batch %u)", slot, m->maxB);
     if ((uint64_t)pos0 + count > m->S) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed max_seq_len %u", pos0, pos0 + count, m->S);
@@ -508,6 +540,11 @@ static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, u
     if (score && !count) return 0;
     HIP_TRY(hipSetDevice(m->device));
     if (count) { const int rc = step_served(m, true); if (rc) return rc; }     // (an empty prompt queues nothing: there is nothing to refuse)
+    if (verify) {
+        int rc = score_scratch(m);
+        if (!rc) rc = lookup_scratch(m);
+        if (rc) return rc;
+    }
     if (score) {
         if (const int rc = score_scratch(m)) return rc;
         m->score.use_targets = targets != nullptr;
@@ -516,7 +553,13 @@ static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, u
     // token i's logits are in row 0 of m->logits (strict / exact mode: one reference-order step per token): their statistics
     auto score_token = [&](uint32_t i) { return enqueue_score_rows(m, m->logits, 1, targets ? m->score.stage + i : nullptr, m->score.out + i); };
     // the call's scores: one copy, behind the work queued so far and in front of the call's last wait
-    auto scores_back = [&]() { return score ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess; };
+    auto scores_back = [&]() {
+        if (verify) return hipMemcpyAsync(argmax_out, m->lk.out, (size_t)count * 4, hipMemcpyDeviceToHost, m->st);
+        return score ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess;
+    };
+    // token i's arg-max is in m->amax[0] (strict / exact mode)
+    auto amax_token = [&](uint32_t i) { return hipMemcpyAsync(m->lk.out + i, m->amax, 4, hipMemcpyDeviceToDevice, m->st); };
+    const uint32_t mode1 = verify ? MODE_ARGMAX : score ? MODE_LOGITS : MODE_NOCLS;     // of a token fed alone
     if (m->kv.paged && count) {
         const uint32_t need = pos0 + count - 1;
         int rc = kv_ensure(m, &slot, &pos0, &need, 1);
@@ -526,12 +569,13 @@ static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, u
         for (uint32_t i = 0; i < count; i++) {
             const uint32_t p = pos0 + i;
             int rc = stage_batch(m, tokens + i, &p, 1, false);
-            if (!rc) rc = run_step_ordered(m, 1, 1, score ? MODE_LOGITS : MODE_NOCLS, slot);
+            if (!rc) rc = run_step_ordered(m, 1, 1, mode1, slot);
             if (rc) return rc;
             if (score) HIP_TRY(score_token(i));
+            if (verify) HIP_TRY(amax_token(i));
             HIP_TRY(hipStreamSynchronize(m->st));
         }
-        if (score) { HIP_TRY(scores_back()); HIP_TRY(hipStreamSynchronize(m->st)); }
+        if (score || verify) { HIP_TRY(scores_back()); HIP_TRY(hipStreamSynchronize(m->st)); }
         return 0;
     }
     const uint32_t chunk_max = m->pf_chunk;
@@ -553,9 +597,10 @@ static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, u
         for (uint32_t i = 0; i < count; i++) {
             HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + i, 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + i, 4, hipMemcpyDeviceToDevice, m->st));
-            const int rc = run_step_ordered(m, 1, 1, score ? MODE_LOGITS : MODE_NOCLS, slot);
+            const int rc = run_step_ordered(m, 1, 1, mode1, slot);
             if (rc) return rc;
             if (score) HIP_TRY(score_token(i));
+            if (verify) HIP_TRY(amax_token(i));
         }
         HIP_TRY(scores_back());
         HIP_TRY(hipStreamSynchronize(m->st));
@@ -568,36 +613,14 @@ static int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, u
         HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
         HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
         if (score && targets) HIP_TRY(hipMemcpyAsync(m->score.targets, m->score.stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
-        const uint32_t range_hint = range_hint_of(m, 1, 1, pos0 + done + nb - 1);      // of the chunk's last token's own decode step
-        const uint32_t mode = score ? MODE_SCORE : MODE_NOCLS;
-        m->pf = true; m->pf_slot = slot;
-        hipError_t e = hipSuccess;
-        if (m->use_graph && nb == chunk_max && chunk_max == 64u) {
-            // a full 64-token chunk recurs in every long prompt: one HIP graph per (KV slot, range bucket) -- positions and
-            // tokens are device data, the slot's cache addresses are baked into the nodes.  Other chunk lengths run eagerly
-            // (a capture costs more than the ~300 launches it would save once).
-            // The chunk that meets a (slot, bucket) first runs eagerly and is captured for the next prompt that reaches it; a failed
-            // capture only costs the replays (r.capture is not looked at).  The cache of chunk graphs is bounded (oldest out).
-            // A scoring chunk has more nodes, and reads its targets or not: bits 56-57 of the key = 0 plain, 1 scored for targets, 2 scored
-            // for the arg-max, so neither ever replays the other's graph.
-            const uint64_t key = (1ull << 62) | ((uint64_t)(score ? (targets ? 1 : 2) : 0) << 56) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
-            const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, mode, range_hint); });
-            e = r.step;
-            if (r.stored) {
-                if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
-                    auto old = m->graphs.find(m->pf_graph_keys.front());
-                    if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
-                    m->pf_graph_keys.erase(m->pf_graph_keys.begin());
-                }
-                m->pf_graph_keys.push_back(key);
-            }
-        } else {
-            e = enqueue_step(m, nb, 1, mode, range_hint);                  // eager: one pass per chunk
-        }
-        m->pf = false;
-        m->nsplit = 1;                                                     // a prefill chunk leaves xba final (single split or the combine kernel), replayed or not
+        const uint32_t mode = verify ? MODE_VERIFY : score ? MODE_SCORE : MODE_NOCLS;
+        // a full 64-token chunk recurs in every long prompt: replayed.  Other chunk lengths run eagerly (a capture costs more than the ~300
+        // launches it would save once).
+        const bool replay = m->use_graph && nb == chunk_max && chunk_max == 64u;
+        const hipError_t e = enqueue_chunk(m, slot, nb, mode, pos0 + done + nb - 1, replay, verify ? 3u : score ? (targets ? 1u : 2u) : 0u);
         HIP_TRY(e);
         if (score) HIP_TRY(hipMemcpyAsync(m->score.out + done, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
+        if (verify) HIP_TRY(hipMemcpyAsync(m->lk.out + done, m->lk.amax, nb * 4, hipMemcpyDeviceToDevice, m->st));
         done += nb;
     }
     HIP_TRY(scores_back());

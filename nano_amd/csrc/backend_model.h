@@ -4,6 +4,7 @@
 //   backend_step.hip     the argument builders, the fast step, the reference-order step, graphs, run_step, the strict / exact switches
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
+//   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
 //   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
 #pragma once
 #include <math.h>
@@ -45,7 +46,8 @@ extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the t
 
 enum { WQ = 0, WK, WV, WO, W1, W2, W3, WCOUNT };
 enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3,
-                           MODE_SCORE = 4 };   // a prefill chunk that goes on into the classifier for all its rows (-> score.logits) and the row statistics
+                           MODE_SCORE = 4,     // a prefill chunk that goes on into the classifier for all its rows (-> score.logits) and the row statistics
+                           MODE_VERIFY = 5 };  // a prefill chunk whose rows' arg-maxes are wanted (-> lk.amax): the classifier into score.logits, no statistics
 constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs kept per model (keyed by KV slot x range bucket)
 constexpr uint32_t STAMP_MAX_LAUNCHES = 512, STAMP_WGS = 2048;
 constexpr uint32_t KV_NO_PAGE = 0xffffffffu;           // a page-table entry without a page
@@ -99,6 +101,16 @@ struct NanoHipModel {
         uint32_t *stage = nullptr;                        // [max_seq_len] the call's targets on the device
         NanoHipTokenScore *out = nullptr;                 // [max_seq_len] the call's scores, copied back once
     } score;
+    // greedy decode with lookup drafts (backend_lookup.hip), allocated on the first call that needs it
+    struct Lookup {
+        uint32_t *hist = nullptr; uint32_t cap = 0;       // slot 0's ids on the device (lookup.hip appends to them); cap = max_seq_len + 1 rounded up to 4
+        std::vector<uint32_t> shadow;                     // what hist holds, host side: a history that extends it uploads only the new ids
+        uint32_t *state = nullptr;                        // LookupArgs::state (4 words), then the step record (LOOKUP_REC_WORDS)
+        uint32_t *amax = nullptr;                         // [max(pf_chunk, 16)] row arg-maxes of a verify chunk (m->amax holds max_batch rows)
+        uint32_t *out = nullptr;                          // [max_seq_len] the row arg-maxes of a nano_hip_verify_draft call
+        uint32_t *h_rec = nullptr;                        // pinned: the record of the last step
+        bool graph = true;                                // verify chunks of the loop replay a graph per (K, range bucket); NANO_LOOKUP_GRAPH=0: eager
+    } lk;
     uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
     float *h_logits = nullptr;
     std::map<uint64_t, hipGraphExec_t> graphs;
@@ -169,6 +181,15 @@ int dev_err_check(NanoHipModel *m);
 void handoff_fallback(NanoHipModel *m);
 void drop_graphs(NanoHipModel *m);
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps);
+int score_scratch(NanoHipModel *m);
+// batched prefill of one slot, as nano_hip_prefill / _prefill_score / _verify_draft (argmax_out: every row's arg-max) call it
+int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
+                uint32_t *argmax_out = nullptr);
+// one prefill chunk of nb rows of `slot` (m->tokens / m->pos hold them; last_pos = the last row's position), eager or -- replay -- through the
+// bounded cache of chunk graphs under `key_kind` (bits 56-57 of the key: 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify)
+hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind);
+int lookup_scratch(NanoHipModel *m);                   // backend_lookup.hip
+void lookup_free(NanoHipModel *m);
 // THE re-issue policy of every entry point that hands results over (round-6 advice: correctness after a give-up depends on every one of
 // them re-issuing at the same positions).  attempt(again) queues the call's work and synchronises the stream; an error it returns is
 // the call's, without a look at the sticky word.  A hand-off that gave up gets the same work once more (again = true: same tokens,

@@ -244,6 +244,11 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
         if ((e = enqueue_classifier(m, nb, nullptr, m->score.logits)) != hipSuccess) return e;
         return enqueue_score_rows(m, m->score.logits, nb, m->score.use_targets ? m->score.targets : nullptr, m->score.rows);
     }
+    if (mode == MODE_VERIFY) {      // a verify chunk: the classifier over all nb rows, then every row's arg-max (a scan of its logits: the partials buffer holds max_batch rows)
+        if ((e = enqueue_classifier(m, nb, nullptr, m->score.logits)) != hipSuccess) return e;
+        ArgmaxArgs aa{ m->score.logits, d.vocab_size, d.vocab_size, m->lk.amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
+        return launch_argmax(aa, nb, m->st);
+    }
     const bool sample = (mode == MODE_ARGMAX || mode == MODE_LOOP);
     uint32_t ntiles = 0;
     // probe: Q80 STREAM classifier (batch <= 8) -> the kernel's own start / stop timestamps (hipExtLaunchKernelGGL);

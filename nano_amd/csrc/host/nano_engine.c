@@ -71,6 +71,9 @@ typedef struct ModelEntry {
     const float *lora_params; size_t lora_floats; uint32_t lora_rank, lora_alpha;
     const void *lora_owner;                          /* the LoRA object those parameters belong to (free_lora of another module leaves them) */
     double rep_upload_s, rep_share_s; char rep_how[48];   /* how the last nano_context_replicate moved the weights */
+    /* NANO_LOOKUP_DRAFT: ids a verify chunk confirmed beyond the one its call returned.  la_ids[la_at .. la_at + la_n) are what the
+     * greedy calls at positions la_pos, la_pos + 1, .. return, provided the id fed there is the one before them (la_prev) */
+    uint32_t la_ids[16], la_at, la_n, la_pos, la_prev; const void *la_lora;
 } ModelEntry;
 static ModelEntry g_reg[MAX_MODELS];
 
@@ -89,6 +92,20 @@ static void reg_del(const LLM *llm) {
     for (int i = 0; i < MAX_MODELS; i++) if (g_reg[i].llm == llm) memset(&g_reg[i], 0, sizeof g_reg[i]);
 }
 void *nano_device_model(const LLM *llm) { return reg_get(llm); }
+
+/* Greedy decode with lookup drafts (include/nano_mi355x.h nano_hip_decode_lookup), opt-in: NANO_LOOKUP_DRAFT=D (1 .. 15), read once.
+ * It serves the greedy branch of generate_next_token only.  Every other entry that touches the model drops the queue. */
+static int g_lookup_draft = -1;
+static uint32_t lookup_draft(void) {
+    if (g_lookup_draft < 0) {
+        const char *e = getenv("NANO_LOOKUP_DRAFT");
+        const long v = e ? strtol(e, NULL, 0) : 0;
+        g_lookup_draft = (v >= 1 && v <= 15) ? (int)v : 0;
+    }
+    return (uint32_t)g_lookup_draft;
+}
+void nano_set_lookup_draft(int max_draft) { g_lookup_draft = (max_draft >= 1 && max_draft <= 15) ? max_draft : 0; }
+static void la_clear(ModelEntry *me) { if (me) me->la_n = 0; }
 
 static void die_hip(const char *what) {
     fprintf(stderr, "%s: %s\n", what, nano_hip_last_error());
@@ -365,6 +382,7 @@ float *llm_forward(Nano_Context *ctx, uint32_t token, uint32_t pos, uint32_t max
     (void)max_seq_len;
     NanoHipModel *dev = reg_get(llm);
     if (!dev) { fprintf(stderr, "llm_forward: model is not resident on a device\n"); exit(EXIT_FAILURE); }
+    la_clear(reg_entry(llm));
     lora_select(dev, lora);
     if (phase_begin(ctx, dev)) {                       /* eager per-operator replay: the backend fires all eleven phases */
         if (nano_hip_forward(dev, &token, &pos, 1, is_causal, llm->state.logits, NULL) != NANO_HIP_OK) die_hip("llm_forward");
@@ -432,6 +450,7 @@ int nano_replicate_stats(Nano_Context *ctx, double *upload_s, double *share_s, c
 }
 
 int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, float *logits, uint32_t *argmax) {
+    la_clear(ctx ? reg_entry(ctx->llm) : NULL);
     ModelEntry *me = reg_entry(ctx->llm);
     if (!me || !me->dev) return NANO_HIP_EINVAL;
     const uint32_t G = (uint32_t)me->n_replica;
@@ -474,6 +493,7 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
 /* The log-probability of ids[1..n_ids) given what precedes each: one scoring prefill of ids[0..n_ids-1) into sequence 0 of the context's own
  * device, targets ids + 1 (nano_hip_prefill_score); the logits stay on the device. */
 int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum) {
+    la_clear(ctx ? reg_entry(ctx->llm) : NULL);
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
     if (!me || !me->dev || (!ids && n_ids)) return NANO_HIP_EINVAL;
     if (nll_sum) *nll_sum = 0.0;
@@ -500,6 +520,7 @@ int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float
 /* One prompt prefix for `batch` sequences: each replica ingests it once (batched prefill into its slot 0) and forks the rows into the
  * other slots of its share -- sequence i lives in slot i / G of replica i mod G, as in nano_forward_batch. */
 int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch) {
+    la_clear(ctx ? reg_entry(ctx->llm) : NULL);
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
     if (!me || !me->dev || (!prefix_ids && n_prefix) || batch == 0) return NANO_HIP_EINVAL;
     const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
@@ -604,6 +625,17 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
     NanoHipModel *dev = me ? me->dev : NULL;
     if (!dev) { fprintf(stderr, "generate_next_token: model is not resident on a device\n"); exit(EXIT_FAILURE); }
     uint32_t token = output_ids[pos];
+    const uint32_t draft = lookup_draft();
+    const int greedy = !phase_mode(ctx) && is_prefilling != 1 && sp->temperature == 0.0f && sp->repetition_penalty == 1.0f;
+    if (draft && greedy && me->la_n && pos == me->la_pos && token == me->la_prev && ctx->lora == me->la_lora) {
+        /* verified ahead by the chunk of an earlier call: its K / V rows are in the cache, no device work */
+        const uint32_t best = me->la_ids[me->la_at++];
+        me->la_n--; me->la_pos++; me->la_prev = best;
+        observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
+        observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
+        return best;
+    }
+    la_clear(me);
     lora_select(dev, ctx->lora);
     if (phase_mode(ctx)) {
         /* per-phase observation: the reference's own sequence -- forward (all phases from inside it), SAMPLE hook,
@@ -628,6 +660,18 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
     if (sp->temperature == 0.0f && sp->repetition_penalty == 1.0f) {
         uint32_t best = 0;                                 /* x/1.0f is exact: arg-max on the device */
         observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
+        const uint32_t lim = me->max_seq_len < llm->config.block_size ? me->max_seq_len : llm->config.block_size;
+        if (draft && pos < lim) {
+            /* one step of the lookup loop: a plain step, or a verify chunk that confirms up to `draft` ids beyond the one returned */
+            const NanoHipLookupParams lp = { draft, 3, 1, UINT32_MAX, 1 };
+            const uint32_t max_new = lim - pos < draft + 1 ? lim - pos : draft + 1;
+            uint32_t ids[16] = { 0 }, n = 0;
+            if (nano_hip_decode_lookup(dev, output_ids, pos + 1, max_new, &lp, ids, &n, NULL) != NANO_HIP_OK || n == 0) die_hip("generate_next_token (lookup)");
+            memcpy(me->la_ids, ids, sizeof ids);
+            me->la_at = 1; me->la_n = n - 1; me->la_pos = pos + 1; me->la_prev = ids[0]; me->la_lora = ctx->lora;
+            observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
+            return ids[0];
+        }
         if (nano_hip_forward(dev, &token, &pos, 1, 1, NULL, &best) != NANO_HIP_OK) die_hip("generate_next_token");
         observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
         return best;
@@ -676,6 +720,7 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
 int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                               Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history, uint32_t *out_ids) {
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    la_clear(me);
     if (!me || !me->dev || !tokens || !pos || !samplers || !out_ids || batch == 0) return NANO_HIP_EINVAL;
     const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
     if (batch > NANO_MAX_BATCH * G) return NANO_HIP_EINVAL;
@@ -781,6 +826,7 @@ static int32_t step_core(Nano_Context *ctx, Nano_Session *s, int with_text) {
     if (!me) { fprintf(stderr, "llm_session_step: model is not resident on a device\n"); return LLM_STOPPED_WITH_ERROR; }
     if (s->pos == 0) {
         me->pf_session = NULL;
+        la_clear(me);
         if (s->num_prompt_tokens > 2 && s->num_prompt_tokens - 1 <= s->max_seq_len && !phase_mode(ctx) && !getenv("NANO_NO_BATCHED_PREFILL")) {
             lora_select(me->dev, ctx->lora);
             if (nano_hip_prefill(me->dev, 0, s->output_ids, 0, s->num_prompt_tokens - 1) != NANO_HIP_OK) die_hip("llm_session_step (prefill)");

@@ -472,4 +472,25 @@ size_t sample_wide_temp_bytes(uint32_t n);                            // scratch
 hipError_t launch_sample_wide(const SampleArgs &a, void *temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_sample_wide_cut(const SampleArgs &a, hipStream_t st);   // (its last three kernels: sampler.hip)   // after the row's pick reported NANO_SAMPLE_FALLBACK
 
+// ---- greedy decode with lookup drafts (lookup.hip): what happens between two steps of the loop, one workgroup ----
+// Behind a step that fed fed[0..nb) at positions n-1 .. n-2+nb and left the row arg-maxes amax[0..nb): accept the draft rows the
+// arg-maxes confirm, clip to the ids still wanted, stop at the stop token, append to the history, look the new suffix up in the history
+// and stage the next step's rows (DESIGN.md section 10 has the definitions; tests/lookup_ref.py restates them).  nb = 0: no step has
+// run yet -- lookup, gate and staging only.
+constexpr uint32_t LOOKUP_MAX_ROWS = 16;          // rows of a verify chunk: the fed id + at most 15 drafted ones
+constexpr uint32_t LOOKUP_MAX_NGRAM = 4;
+enum { LOOKUP_REC_EMITTED = 0, LOOKUP_REC_ACCEPTED, LOOKUP_REC_NB_NEXT, LOOKUP_REC_N, LOOKUP_REC_MATCH_LEN, LOOKUP_REC_MATCH_END,
+       LOOKUP_REC_DONE, LOOKUP_REC_LEFT, LOOKUP_REC_WORDS };
+struct LookupArgs {
+    uint32_t *hist; uint32_t cap;                 // the sequence's ids, device memory, 16-byte aligned; cap a multiple of 4: nothing is written at or beyond it
+    uint32_t *state;                              // [0] n = ids in hist, [1] left = ids still to emit, [2] ids emitted so far (the cursor into trace)
+    const uint32_t *fed, *amax; uint32_t nb;      // the step this launch follows (<= LOOKUP_MAX_ROWS rows)
+    uint32_t max_draft, ngram_max, ngram_min, stop_token;
+    uint32_t seq_limit;                           // min(max_seq_len, RoPE rows): a chunk's last position stays below it
+    uint32_t *next_tokens, *next_pos;             // [LOOKUP_MAX_ROWS] the next step's rows (next_tokens may be fed: the fed ids are read first)
+    uint32_t *trace; uint32_t trace_cap;          // the call's emitted ids (nullptr: not kept)
+    uint32_t *record;                             // [LOOKUP_REC_WORDS]
+};
+hipError_t launch_lookup_step(const LookupArgs &a, hipStream_t st);
+
 }  // namespace nano

@@ -220,6 +220,37 @@ extern "C" int nano_hip_op_score_rows(int device, const float *logits, uint32_t 
     return 0;
 }
 
+// the between-steps kernel of greedy decode with lookup drafts alone (lookup.hip).  The arguments are checked before a device is asked for.
+extern "C" int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
+                                       const NanoHipLookupParams *p, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
+                                       uint32_t *next_tokens_out, uint32_t *next_pos_out) {
+    if (!history || !p || !record_out || !next_tokens_out || !next_pos_out || (nb && (!fed || !amax))) { nano_hip_set_error_("lookup_step: null argument"); return NANO_HIP_EINVAL; }
+    if (n == 0 || n > 65536u || nb > LOOKUP_MAX_ROWS) { nano_hip_set_error_("lookup_step: n outside 1 .. 65536, or more than 16 rows"); return NANO_HIP_EINVAL; }
+    if (p->max_draft > LOOKUP_MAX_ROWS - 1 || p->ngram_max < 1 || p->ngram_max > LOOKUP_MAX_NGRAM || p->ngram_min < 1 || p->ngram_min > p->ngram_max) {
+        nano_hip_set_error_("lookup_step: max_draft beyond 15, ngram_max outside 1 .. 4, or ngram_min outside 1 .. ngram_max"); return NANO_HIP_EINVAL;
+    }
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B;
+    LookupArgs a{};
+    a.cap = (n + LOOKUP_MAX_ROWS + 3u) & ~3u;
+    a.hist = B.alloc<uint32_t>(a.cap);
+    const uint32_t st[4] = { n, left, 0u, 0u };
+    a.state = B.upload(st, 4);
+    a.fed = nb ? B.upload(fed, nb) : nullptr; a.amax = nb ? B.upload(amax, nb) : nullptr; a.nb = nb;
+    a.max_draft = p->max_draft; a.ngram_max = p->ngram_max; a.ngram_min = p->ngram_min; a.stop_token = p->stop_token; a.seq_limit = seq_limit;
+    a.next_tokens = B.alloc<uint32_t>(LOOKUP_MAX_ROWS); a.next_pos = B.alloc<uint32_t>(LOOKUP_MAX_ROWS); a.record = B.alloc<uint32_t>(LOOKUP_REC_WORDS);
+    OP_CHECK(a.hist && a.state && (!nb || (a.fed && a.amax)) && a.next_tokens && a.next_pos && a.record, "device alloc failed");
+    OP_HIP(hipMemset(a.hist, 0xff, (size_t)a.cap * 4));
+    OP_HIP(hipMemcpy(a.hist, history, (size_t)n * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemset(a.next_tokens, 0xff, LOOKUP_MAX_ROWS * 4)); OP_HIP(hipMemset(a.next_pos, 0xff, LOOKUP_MAX_ROWS * 4));
+    OP_HIP(launch_lookup_step(a, 0));
+    OP_HIP(hipMemcpy(record_out, a.record, LOOKUP_REC_WORDS * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(history, a.hist, (size_t)(n + LOOKUP_MAX_ROWS) * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_tokens_out, a.next_tokens, LOOKUP_MAX_ROWS * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_pos_out, a.next_pos, LOOKUP_MAX_ROWS * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part, read as flags), or nullptr
 static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || d.n % 4) return "bad fused-gemv descriptor";
