@@ -498,7 +498,8 @@ int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
  * nw waves x grid workgroups owning rw rows each, of the first of `launches` slices of seqs_per_launch sequences.  takes = 0: the
  * shape is refused before any launch (a row of more than 16384 floats, 8192 with SwiGLU; one sequence that does not fit a CU's LDS).
  * Host arithmetic on the shape fields: works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
-int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[12]);
+#define NANO_F32_GEMV_PLAN_WORDS 12
+int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_F32_GEMV_PLAN_WORDS]);
 /* The FP32 MFMA GEMM launch (9..64 sequences per weight read) the router issues for descriptor d (quant = NANO_QUANT_F32) in a model, or
  * through nano_hip_op_fused_gemv with use_gemm = 1: out = {route, sw, threads, grid, lds_bytes, rt, nw, nt, nu, upw, tp, stage_bytes, tab_off,
  * pro_threads, pro_lds, xs_floats, takes}.  route 9: gemm_f32_kernel<sw> (sw = 1: the W1 and W3 tiles of SwiGLU in one workgroup) on
@@ -520,7 +521,8 @@ int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * seqs_per_launch = nb, zeros for the kernel fields.  takes = 0: the shape is refused before any launch (a SLAB row of more than 65536
  * values, 32768 with SwiGLU; one sequence that does not fit a CU's LDS) and every other entry is 0.  Host arithmetic on the shape fields:
  * works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
-int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[16]);
+#define NANO_Q80_GEMV_PLAN_WORDS 16
+int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_Q80_GEMV_PLAN_WORDS]);
 /* The batched Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, tt, nv, r, ms, tp, pp,
  * gs, sw, threads, grid, lds_bytes, norm_order, hh, ntiles, tc0, tc1, tpw, full, nu, nk, ttl, nw, rounds, tts, magic, nsa, pre, a_stage, a_ws,
  * b_base, b_stage, b_xs, ks, ncw, nss, tab, ring, nl, waves, lt, nhc, nwaves, ng, npass, takes}.  kernel: 1 G6 MODE S, 2 G6 MODE F, 3 G7,
@@ -541,7 +543,8 @@ int nano_hip_q80_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * the route, launches = 1, seqs_per_launch = nb, zeros for the kernel fields.  takes = 0: the shape is refused before any launch (several
  * tensors whose rows are no multiples of 4 or more than 4 items per thread on the slab kernel; one sequence that does not fit a CU's LDS)
  * and every other entry is 0.  Host arithmetic on the shape fields: works without a device, and no pointer of d is followed. */
-int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[24]);
+#define NANO_Q4K_GEMV_PLAN_WORDS 24
+int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_Q4K_GEMV_PLAN_WORDS]);
 
 /* One device-resident copy of a model's parameter bytes per GPU from ONE host upload (replicate.hip; SURVEY 8e "broadcast(weights) at
  * load"): the bytes go to `root_device` over PCIe once and from there to the other devices over xGMI -- an RCCL broadcast (librccl.so

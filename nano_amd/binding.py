@@ -58,6 +58,7 @@ ATTN_PLAN_FIELDS = ("mode", "lpr", "qv", "kvm", "npt", "w16", "paged", "kv_half"
 
 # what nano_hip_f32_gemv_plan reports (nano_amd/csrc/kernels.h F32GemvPlan + route_gemv_slices), and the kernel roles of gemv_common.h
 F32_PLAN_FIELDS = ("role", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "launches", "seqs_per_launch", "takes")
+F32_PLAN_WORDS = len(F32_PLAN_FIELDS) + 1         # NANO_F32_GEMV_PLAN_WORDS: a last word that is always 0
 F32_ROLES = ("generic", "norm_store", "resid", "resid_combine", "norm_swiglu")
 
 
@@ -565,96 +566,64 @@ def op_matmul_q4k(x_blocks, w_blocks, n, d, device=0):
 _FLAG = np.zeros(1, np.float32)         # stands for "a norm weight / attention partials are given" where only the shape is read
 
 
+def _fused_shape(quant, kind, n, rows, nb, *, gs=0, norm=False, attn=None, ordered=False, use_gemm=False) -> NanoFusedGemvDesc:
+    """The shape part of a NanoFusedGemvDesc -- all a plan query reads.  norm: False, the address of the norm weight, or True (a query:
+    null or not is all that is read, _FLAG stands for the weight); attn: None or (n_head, hd, nsplit[, address of the partials]), _FLAG likewise."""
+    d = NanoFusedGemvDesc()
+    d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = quant, gs, kind, n, nb, len(rows)
+    for i, r in enumerate(rows):
+        d.rows[i] = r
+    if norm:
+        d.norm_w = _FLAG.ctypes.data if norm is True else norm
+    if attn is not None:
+        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn[:3]
+        d.attn_part = attn[3] if len(attn) > 3 else _FLAG.ctypes.data
+    d.ordered = 1 if ordered else 0
+    d.use_gemm = 1 if use_gemm else 0
+    return d
+
+
+def _plan_query(name, fields, words, desc, cus):
+    """nano_hip_<name>_plan of a descriptor: `words` output words, the first len(fields) of them named."""
+    assert len(fields) <= words
+    out = (C.c_uint32 * words)()
+    check(getattr(lib(), f"nano_hip_{name}_plan")(C.byref(desc), cus, out))
+    return dict(zip(fields, (int(v) for v in out)))
+
+
 def f32_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
     """The FP32 launch the router issues for a fused-gemv shape (nano_hip_f32_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of F32_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.kind, d.n, d.nb, d.nseg = 0x00, kind, n, nb, len(rows)
-    for i, r in enumerate(rows):
-        d.rows[i] = r
-    if norm:
-        d.norm_w = _FLAG.ctypes.data
-    if attn is not None:
-        d.attn_part = _FLAG.ctypes.data
-        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
-    out = (C.c_uint32 * 12)()
-    check(lib().nano_hip_f32_gemv_plan(C.byref(d), cus, out))
-    return dict(zip(F32_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan_query("f32_gemv", F32_PLAN_FIELDS, F32_PLAN_WORDS, _fused_shape(0x00, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
 
 
 def f32_gemm_plan(kind, n, rows, nb=9, *, norm=False, attn=None, cus=256):
     """The FP32 MFMA GEMM launch the router issues for a fused-gemv shape of 9..64 sequences (nano_hip_f32_gemm_plan; needs no GPU);
     arguments as f32_gemv_plan.  Returns a dict of F32_GEMM_PLAN_FIELDS; a shape the GEMM refuses: the sliced route and zeros."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.kind, d.n, d.nb, d.nseg = 0x00, kind, n, nb, len(rows)
-    for i, r in enumerate(rows):
-        d.rows[i] = r
-    if norm:
-        d.norm_w = _FLAG.ctypes.data
-    if attn is not None:
-        d.attn_part = _FLAG.ctypes.data
-        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
-    out = (C.c_uint32 * len(F32_GEMM_PLAN_FIELDS))()
-    check(lib().nano_hip_f32_gemm_plan(C.byref(d), cus, out))
-    return dict(zip(F32_GEMM_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan_query("f32_gemm", F32_GEMM_PLAN_FIELDS, len(F32_GEMM_PLAN_FIELDS), _fused_shape(0x00, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
 
 
 def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):
     """The Q80 launch the router issues for a fused-gemv shape (nano_hip_q80_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of Q80_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = 0x80, gs, kind, n, nb, len(rows)
-    for i, r in enumerate(rows):
-        d.rows[i] = r
-    if norm:
-        d.norm_w = _FLAG.ctypes.data
-    if attn is not None:
-        d.attn_part = _FLAG.ctypes.data
-        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
-    d.ordered = 1 if ordered else 0
-    d.use_gemm = 1 if use_gemm else 0
-    out = (C.c_uint32 * 16)()
-    check(lib().nano_hip_q80_gemv_plan(C.byref(d), cus, out))
-    return dict(zip(Q80_PLAN_FIELDS, (int(v) for v in out)))
+    d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm)
+    return _plan_query("q80_gemv", Q80_PLAN_FIELDS, len(Q80_PLAN_FIELDS), d, cus)
 
 
 def q80_gemm_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):
     """The batched Q80 launch (G6 / G7 / G7K / GC / G2) the router issues for a fused-gemv shape (nano_hip_q80_gemm_plan; needs no GPU);
     arguments as q80_gemv_plan.  Returns a dict of Q80_GEMM_PLAN_FIELDS; a shape whose route ends in the GEMV kernels: the route and zeros."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = 0x80, gs, kind, n, nb, len(rows)
-    for i, r in enumerate(rows):
-        d.rows[i] = r
-    if norm:
-        d.norm_w = _FLAG.ctypes.data
-    if attn is not None:
-        d.attn_part = _FLAG.ctypes.data
-        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
-    d.ordered = 1 if ordered else 0
-    d.use_gemm = 1 if use_gemm else 0
-    out = (C.c_uint32 * len(Q80_GEMM_PLAN_FIELDS))()
-    check(lib().nano_hip_q80_gemm_plan(C.byref(d), cus, out))
-    return dict(zip(Q80_GEMM_PLAN_FIELDS, (int(v) for v in out)))
+    d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm)
+    return _plan_query("q80_gemm", Q80_GEMM_PLAN_FIELDS, len(Q80_GEMM_PLAN_FIELDS), d, cus)
 
 
 def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
     """The Q4K launch the router issues for a fused-gemv shape (nano_hip_q4k_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of Q4K_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.kind, d.n, d.nb, d.nseg = 0x42, kind, n, nb, len(rows)
-    for i, r in enumerate(rows):
-        d.rows[i] = r
-    if norm:
-        d.norm_w = _FLAG.ctypes.data
-    if attn is not None:
-        d.attn_part = _FLAG.ctypes.data
-        d.attn_n_head, d.attn_hd, d.attn_nsplit = attn
-    out = (C.c_uint32 * 24)()
-    check(lib().nano_hip_q4k_gemv_plan(C.byref(d), cus, out))
-    return dict(zip(Q4K_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan_query("q4k_gemv", Q4K_PLAN_FIELDS, len(Q4K_PLAN_FIELDS), _fused_shape(0x42, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
 
 
 def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, resid=None, attn=None, use_gemm=False, ordered=False,
@@ -669,37 +638,39 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     kind 1: it holds the residual stream there on entry) -- it goes to the device whole and comes back whole, so the caller sees whatever
     a launch wrote beyond its rows or its sequences; the returned out is that array.
     partials: None, or a float32 array [slots >= nb, pairs, 2] that IS the step's arg-max partials buffer: it goes to the device whole and
-    comes back whole; the launch is asked for partials exactly where the step's classifier is (route.hip route_asks_partials()) and then
+    comes back whole; the launch is asked for partials exactly where the step's classifier is (route.hip route_partials()) and then
     writes nb x ntiles (max, bits of the first row) pairs densely from the start of the buffer -- partials.reshape(-1, 2)[b * ntiles + t].
     want_argmax: behind the launch, the arg-max kernel as a greedy step builds it (from the partials where the launch wrote them).
     Returns out[nb, rows_total]; with any of want_route / partials / want_argmax a tuple (out, route name if want_route,
     ntiles if partials is given -- 0: the launch was not asked --, argmax uint32[nb] if want_argmax)."""
-    d = NanoFusedGemvDesc()
-    d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = quant, gs, kind, n, nb, len(weights)
     keep = []
-    for i, (w, ws, rows) in enumerate(weights):
-        w = np.ascontiguousarray(w); keep.append(w)
-        d.rows[i] = rows; d.w[i] = w.ctypes.data
-        if ws is not None:
-            ws = np.ascontiguousarray(ws, np.float32); keep.append(ws); d.ws[i] = ws.ctypes.data
-    rows_total = weights[0][2] if kind == 2 else sum(r for _, _, r in weights)
-    if x is not None:
-        x = np.ascontiguousarray(x, np.float32); keep.append(x); d.x = x.ctypes.data
+
+    def held(v, dtype=None):
+        v = np.ascontiguousarray(v, dtype); keep.append(v)
+        return v
+
     if norm_w is not None:
-        norm_w = np.ascontiguousarray(norm_w, np.float32); keep.append(norm_w); d.norm_w = norm_w.ctypes.data
+        norm_w = held(norm_w, np.float32)
     if attn is not None:
         part, ml, n_head, hd = attn
-        part = np.ascontiguousarray(part, np.float32); ml = np.ascontiguousarray(ml, np.float32); keep += [part, ml]
-        d.attn_part, d.attn_ml = part.ctypes.data, ml.ctypes.data
-        d.attn_nsplit, d.attn_n_head, d.attn_hd = part.shape[-2], n_head, hd
+        part, ml = held(part, np.float32), held(ml, np.float32)
+    d = _fused_shape(quant, kind, n, [rows for _, _, rows in weights], nb, gs=gs, norm=norm_w is not None and norm_w.ctypes.data,
+                     attn=None if attn is None else (n_head, hd, part.shape[-2], part.ctypes.data), ordered=ordered, use_gemm=use_gemm)
+    for i, (w, ws, _) in enumerate(weights):
+        d.w[i] = held(w).ctypes.data
+        if ws is not None:
+            d.ws[i] = held(ws, np.float32).ctypes.data
+    rows_total = weights[0][2] if kind == 2 else sum(r for _, _, r in weights)
+    if x is not None:
+        d.x = held(x, np.float32).ctypes.data
+    if attn is not None:
+        d.attn_ml = ml.ctypes.data
     if guard is not None:
         assert resid is None and guard.dtype == np.float32 and guard.flags.c_contiguous and guard.ndim == 2
         out = guard
         d.out_slots, d.out_stride = guard.shape
     else:
         out = np.zeros((nb, rows_total), np.float32) if resid is None else np.array(resid, np.float32, copy=True).reshape(nb, rows_total)
-    d.use_gemm = 1 if use_gemm else 0
-    d.ordered = 1 if ordered else 0
     route = C.c_uint32(0xffffffff)
     d.route_out = C.cast(C.pointer(route), C.c_void_p)
     d.out = out.ctypes.data

@@ -41,12 +41,9 @@ static GemvArgs classifier_args(const NanoHipModel *m, uint32_t nb, float *dst) 
 
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out, float *dst) {
     GemvArgs a = classifier_args(m, nb, dst ? dst : m->logits);
-    a.q4_scratch = m->q4x; a.q4_scratch_bytes = m->q4x_bytes; a.cus = (uint32_t)m->cus;      // (what route_projection() will set: the partial count must match the launch)
     a.ordered = (m->strict || m->exact) ? 1u : 0u;                     // (as gemv() sends it)
-    if (ntiles_out && route_asks_partials(route_of(m), a)) {          // per-tile arg-max partials for the sampler (route.hip: the operator's condition too)
-        a.tile_max = m->tile_max;
-        *ntiles_out = gemv_tiles(m->d.quant_type, a);
-    }
+    if (ntiles_out)                                                    // per-tile arg-max partials for the sampler (route.hip: the operator's condition and count too)
+        if (const uint32_t n = route_partials(route_of(m), a)) { a.tile_max = m->tile_max; *ntiles_out = n; }
     return gemv(m, a);
 }
 // the row statistics of `rows` rows of logits (row stride V) for targets[rows] (nullptr: each row's own arg-max) -> out[rows]  (score.hip)

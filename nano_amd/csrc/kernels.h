@@ -227,8 +227,11 @@ RouteKind route_kind(const Q80Route &r, const GemvArgs &a, Q80GemmPlan *gp = nul
 // changes: the kernels are bit for bit per sequence whatever the capacity.  false: not even one sequence fits, or the shape is refused
 // (hipErrorInvalidValue before any launch)
 bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_t *launches);
-// whether the launch of `a` is asked for arg-max partials (a.tile_max): the one condition of the step's classifier and of the operator
-bool route_asks_partials(const Q80Route &r, GemvArgs a);
+// the fields route_projection() itself writes into `a` before it asks route_kind() or launches (cus, the Q4K scratch): written here only
+void route_fill(const Q80Route &r, GemvArgs &a);
+// arg-max pairs per sequence the launch of `a` is asked for (a.tile_max) and writes, 0: not asked -- the one condition and the one count
+// of the step's classifier and of the operator; a.tile_max null on entry
+uint32_t route_partials(const Q80Route &r, GemvArgs a);
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st);
 uint32_t route_norm_order(const GemvArgs &a);
 bool route_is_wide(const GemvArgs &a);

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -261,179 +262,173 @@ static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     return nullptr;
 }
 
-// The FP32 launch route_projection() issues for a descriptor (its first slice when it cuts the batch): gemv_f32_plan() and
-// route_gemv_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
-// the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed.
-// out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0}; takes = 0: the router refuses the shape
-// (hipErrorInvalidValue before any launch) and the other entries are 0.
-extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[12]) {
-    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
-    const NanoFusedGemvDesc &d = *dp;
-    if (d.quant != NANO_QUANT_F32) { nano_hip_set_error_("not an FP32 launch"); return NANO_HIP_EINVAL; }
-    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    GemvArgs a{};
+// ---- ONE path from a fused-gemv descriptor to the router's inputs: nano_hip_op_fused_gemv and the five plan queries below all start here,
+// so that a query answers for the launch the operator issues.
+// FusedLaunch = the arguments (shape and flag fields only: every pointer is the descriptor's HOST pointer, read as a flag; the operator
+// replaces each with its device copy), the route with the step's switches, and the scratch the route may use -- sizes only, the pointers
+// null: the operator allocates exactly these sizes, a query points every non-empty one at a flag (flag_scratch()).
+//   Q80   the fragment-order activations of the batched routes and the quantized rows of ROUTE_GEMV_PREQ (gq bytes, gxs floats): always
+//   Q4K   the staged groups of a several-sequence chunk launch (<= 8) or of the GEMM's tokens (r.q4x_bytes): from two sequences on
+//   FP32  the operand-order activations of gemm_f32.hip (r.f32x_floats, f32_min_nb = 9): F32X_ASKED -- the caller asks for the GEMM route
+//         (use_gemm) and nb > 8; F32X_MODEL -- as in a model: present, of any size; F32X_NONE -- never (the sliced route of every batch)
+// use_gemm = 1 forces the fragment-order route of batched Q80 steps (quantizer launch + G6 MODE F / GC / G2) and lets FP32 ask for its
+// GEMM (Q4K: the operator refuses it, the query does not read it); ordered = 1 is strict mode (the reference's group order in every
+// kernel).  cus = 0: 256.
+enum F32Scratch { F32X_NONE, F32X_ASKED, F32X_MODEL };
+struct FusedLaunch {
+    GemvArgs a;
+    Q80Route r;
+    size_t gq_bytes, gxs_floats;
+};
+static FusedLaunch fused_launch(const NanoFusedGemvDesc &d, uint32_t cus, F32Scratch f32x) {
+    FusedLaunch L{};
+    GemvArgs &a = L.a;
+    Q80Route &r = L.r;
     for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
-    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus;
+    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb; a.cus = cus ? cus : 256u;
     a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
     a.norm_w = d.norm_w;
     if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
-    memset(out, 0, 12 * sizeof(uint32_t));
-    uint32_t per = 0, launches = 0;
-    F32GemvPlan p;
-    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
-    a.nb = per;
-    if (!gemv_f32_plan(a, &p)) return 0;
-    const uint32_t v[12] = { p.role, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, launches, per, 1u, 0u };
-    memcpy(out, v, sizeof(v));
+    a.ordered = d.ordered ? 1u : 0u;
+    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = (d.use_gemm && d.quant == NANO_QUANT_Q80) ? 1u : 9u;
+    if (d.quant == NANO_QUANT_Q80) {
+        const size_t n16 = (d.n + 15) & ~(size_t)15, tt = (d.nb + 15) / 16;
+        L.gq_bytes = tt * 16 * n16; L.gxs_floats = tt * 16 * (d.n / d.gs);
+    }
+    if (d.quant == NANO_QUANT_Q4K && d.nb > 1) r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);
+    if (d.quant == NANO_QUANT_F32 && (f32x == F32X_MODEL || (f32x == F32X_ASKED && d.use_gemm && d.nb > 8))) {   // a shape the GEMM refuses keeps the slices
+        r.f32_min_nb = 9u;
+        r.f32x_floats = f32x == F32X_MODEL ? ~(size_t)0 : (size_t)((d.nb + 15) / 16) * 16 * ((d.n + 127) & ~(size_t)127);
+    }
+    return L;
+}
+// a query's scratch: one flag stands for every buffer the operator would allocate -- compared with null, never followed
+static void flag_scratch(FusedLaunch &L) {
+    alignas(8) static uint8_t flag[8];
+    if (L.gq_bytes) L.r.gq = reinterpret_cast<int8_t *>(flag);
+    if (L.gxs_floats) L.r.gxs = reinterpret_cast<float *>(flag);
+    if (L.r.q4x_bytes) L.r.q4x = flag;
+    if (L.r.f32x_floats) L.r.f32x = reinterpret_cast<float *>(flag);
+}
+// The start of every plan query: the arguments checked, out zeroed, the launch as the operator builds it for `cus` compute units.
+// Host arithmetic only from here on -- no device is touched, and of the descriptor's pointers only norm_w and attn_part are looked at
+// (null or not), never followed; `ordered` and `use_gemm` as flags.
+static int query_begin(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t *out, uint32_t words, uint32_t quant, const char *not_quant,
+                       F32Scratch f32x, FusedLaunch *L) {
+    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    if (dp->quant != quant) { nano_hip_set_error_(not_quant); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(*dp)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    memset(out, 0, words * sizeof(uint32_t));
+    *L = fused_launch(*dp, cus, f32x);
+    flag_scratch(*L);
     return 0;
 }
+// The end of the three GEMV-route queries: the first of the slices route_gemv_slices() cuts the batch into, planned by the format's
+// planner -- the functions the router and the launcher themselves follow.  out = {fields(plan)..., launches, seqs_per_launch, takes = 1};
+// a shape the slicer or the planner refuses leaves out as it is (zeros: takes = 0).
+template <uint32_t WORDS, typename Plan, typename Fields>
+static int report_first_slice(FusedLaunch &L, uint32_t *out, bool (*plan)(const GemvArgs &, Plan *), Fields fields) {
+    GemvArgs &a = L.a;
+    uint32_t per = 0, launches = 0;
+    Plan p;
+    if (!route_gemv_slices(L.r.quant, a, &per, &launches)) return 0;
+    a.nb = per;
+    if (launches > 1) a.tile_max = nullptr;                          // (gemv_slice(): a sliced launch writes no partials)
+    if (!plan(a, &p)) return 0;
+    const auto v = fields(p);
+    static_assert(std::tuple_size<decltype(v)>::value + 3 <= WORDS, "the plan's fields and the three words of the slicing fit the query's output");
+    memcpy(out, v.data(), sizeof(v));
+    const uint32_t tail[3] = { launches, per, 1u };
+    memcpy(out + v.size(), tail, sizeof(tail));
+    return 0;
+}
+template <size_t N> using Words = std::array<uint32_t, N>;
 
-// The FP32 MFMA GEMM launch route_projection() issues for a descriptor of 9..64 sequences in a model (the scratch present, f32_min_nb = 9;
-// nano_hip_op_fused_gemv reaches it with use_gemm = 1): route_kind() and the F32GemmPlan (kernels.h) the launcher consumes.  Host
-// arithmetic only -- no device is touched, and of the descriptor's pointers only norm_w and attn_part are looked at (null or not).
+// The FP32 launch route_projection() issues for a descriptor on the sliced route (its first slice when it cuts the batch).
+// out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0}; takes = 0: the router refuses the shape
+// (hipErrorInvalidValue before any launch) and the other entries are 0.
+extern "C" int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_F32_GEMV_PLAN_WORDS]) {
+    FusedLaunch L;
+    if (int rc = query_begin(dp, cus, out, NANO_F32_GEMV_PLAN_WORDS, NANO_QUANT_F32, "not an FP32 launch", F32X_NONE, &L)) return rc;
+    return report_first_slice<NANO_F32_GEMV_PLAN_WORDS>(L, out, gemv_f32_plan, [](const F32GemvPlan &p) {
+        return Words<8>{{ p.role, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes }}; });
+}
+
+// The FP32 MFMA GEMM launch route_projection() issues for a descriptor of 9..64 sequences in a model (F32X_MODEL; nano_hip_op_fused_gemv
+// reaches it with use_gemm = 1): route_kind() and the F32GemmPlan (kernels.h) the launcher consumes.
 // out = {route, the plan's fields in the order of the struct, takes}; a descriptor the GEMM refuses reports the sliced route, takes = 1 and
 // zeros for the plan (nano_hip_f32_gemv_plan reports those launches, and their refusals).
 extern "C" int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_F32_GEMM_PLAN_WORDS]) {
     static_assert(sizeof(F32GemmPlan) == (NANO_F32_GEMM_PLAN_WORDS - 2) * sizeof(uint32_t), "the query reports every field of the plan");
-    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
-    const NanoFusedGemvDesc &d = *dp;
-    if (d.quant != NANO_QUANT_F32) { nano_hip_set_error_("not an FP32 launch"); return NANO_HIP_EINVAL; }
-    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    static float scratch_flag[4];                   // stands for the scratch: compared with null, never followed
-    GemvArgs a{};
-    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
-    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus ? cus : 256u;
-    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
-    a.norm_w = d.norm_w;
-    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
-    Q80Route r{};
-    r.quant = d.quant; r.cus = (int)a.cus; r.f32_min_nb = 9u;
-    r.f32x = scratch_flag; r.f32x_floats = ~(size_t)0;
-    memset(out, 0, NANO_F32_GEMM_PLAN_WORDS * sizeof(uint32_t));
-    const RouteKind k = route_kind(r, a);
+    FusedLaunch L;
+    if (int rc = query_begin(dp, cus, out, NANO_F32_GEMM_PLAN_WORDS, NANO_QUANT_F32, "not an FP32 launch", F32X_MODEL, &L)) return rc;
+    const RouteKind k = route_kind(L.r, L.a);
     out[0] = (uint32_t)k;
     F32GemmPlan p{};
-    if (k == ROUTE_F32_GEMM && gemm_f32_plan(a, &p)) memcpy(out + 1, &p, sizeof(p));
+    if (k == ROUTE_F32_GEMM && gemm_f32_plan(L.a, &p)) memcpy(out + 1, &p, sizeof(p));
     out[NANO_F32_GEMM_PLAN_WORDS - 1] = 1u;
     return 0;
 }
 
-// The Q80 launch route_projection() issues for a descriptor: route_kind() -- assuming the step's activation scratch is present, as in
-// nano_hip_op_fused_gemv below --, then for the routes that end in the Q80 GEMV kernels gemv_q80_plan() of the first slice and
-// route_gemv_slices(), the functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of
-// the descriptor's pointers only norm_w and attn_part are looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
+// The Q80 launch route_projection() issues for a descriptor: route_kind(), then for the routes that end in the Q80 GEMV kernels
+// gemv_q80_plan() of the first slice.
 // out = {route, kernel, role, gs, B, nv, upw, rw, nw, grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}; the batched routes
 // (G6 / G7 / G2 / GC) report the route, one launch of nb sequences and zeros for the kernel fields.  takes = 0: the router refuses the
 // shape (hipErrorInvalidValue before any launch) and every other entry is 0.
-extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[16]) {
-    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
-    const NanoFusedGemvDesc &d = *dp;
-    if (d.quant != NANO_QUANT_Q80) { nano_hip_set_error_("not a Q80 launch"); return NANO_HIP_EINVAL; }
-    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    static int8_t scratch_flag[4];                  // stands for the scratch and the quantized rows: compared with null, never followed
-    GemvArgs a{};
-    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
-    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb; a.cus = cus ? cus : 256u;
-    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
-    a.norm_w = d.norm_w;
-    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
-    a.ordered = d.ordered ? 1u : 0u;
-    Q80Route r{};
-    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
-    r.gq = scratch_flag; r.gxs = reinterpret_cast<float *>(scratch_flag);
-    memset(out, 0, 16 * sizeof(uint32_t));
-    const RouteKind k = route_kind(r, a);
-    if (route_takes_fragments(k)) {
-        out[0] = (uint32_t)k; out[13] = 1u; out[14] = d.nb; out[15] = 1u;
+extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_Q80_GEMV_PLAN_WORDS]) {
+    FusedLaunch L;
+    if (int rc = query_begin(dp, cus, out, NANO_Q80_GEMV_PLAN_WORDS, NANO_QUANT_Q80, "not a Q80 launch", F32X_NONE, &L)) return rc;
+    GemvArgs &a = L.a;
+    const uint32_t k = (uint32_t)route_kind(L.r, a);
+    if (route_takes_fragments((RouteKind)k)) {
+        out[0] = k; out[13] = 1u; out[14] = a.nb; out[15] = 1u;
         return 0;
     }
-    if (k == ROUTE_GEMV_PREQ) { a.xq_in = scratch_flag; a.xs_in = r.gxs; a.norm_w = nullptr; }      // (as route_projection() hands it on)
-    uint32_t per = 0, launches = 0;
-    Q80GemvPlan p;
-    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
-    a.nb = per;
-    if (!gemv_q80_plan(a, &p)) return 0;
-    const uint32_t v[16] = { (uint32_t)k, p.kernel, p.role, p.gs, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, p.variant, p.pre, launches, per, 1u };
-    memcpy(out, v, sizeof(v));
-    return 0;
+    if (k == ROUTE_GEMV_PREQ) { a.xq_in = L.r.gq; a.xs_in = L.r.gxs; a.norm_w = nullptr; }      // (as route_projection() hands it on)
+    return report_first_slice<NANO_Q80_GEMV_PLAN_WORDS>(L, out, gemv_q80_plan, [k](const Q80GemvPlan &p) {
+        return Words<13>{{ k, p.kernel, p.role, p.gs, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, p.variant, p.pre }}; });
 }
 
-// The batched Q80 launch route_projection() issues for a descriptor: route_kind() under the assumptions of nano_hip_q80_gemv_plan above
-// and the Q80GemmPlan (kernels.h) it hands to the launcher.  Host arithmetic only -- no device is touched, and of the descriptor's
-// pointers only norm_w and attn_part are looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
+// The batched Q80 launch route_projection() issues for a descriptor: route_kind() and the Q80GemmPlan (kernels.h) it hands to the launcher.
 // out = {route, the plan's fields in the order of the struct, takes}; a descriptor whose route ends in the GEMV kernels reports the route,
 // takes = 1 and zeros for the plan (nano_hip_q80_gemv_plan reports those launches, and their refusals).
 extern "C" int nano_hip_q80_gemm_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_Q80_GEMM_PLAN_WORDS]) {
     static_assert(sizeof(Q80GemmPlan) == (NANO_Q80_GEMM_PLAN_WORDS - 2) * sizeof(uint32_t), "the query reports every field of the plan");
-    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
-    const NanoFusedGemvDesc &d = *dp;
-    if (d.quant != NANO_QUANT_Q80) { nano_hip_set_error_("not a Q80 launch"); return NANO_HIP_EINVAL; }
-    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    static int8_t scratch_flag[4];                  // stands for the scratch: compared with null, never followed
-    GemvArgs a{};
-    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
-    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb; a.cus = cus ? cus : 256u;
-    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
-    a.norm_w = d.norm_w;
-    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
-    a.ordered = d.ordered ? 1u : 0u;
-    Q80Route r{};
-    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
-    r.gq = scratch_flag; r.gxs = reinterpret_cast<float *>(scratch_flag);
+    FusedLaunch L;
+    if (int rc = query_begin(dp, cus, out, NANO_Q80_GEMM_PLAN_WORDS, NANO_QUANT_Q80, "not a Q80 launch", F32X_NONE, &L)) return rc;
     Q80GemmPlan p{};
-    const RouteKind k = route_kind(r, a, &p);
-    out[0] = (uint32_t)k;
+    out[0] = (uint32_t)route_kind(L.r, L.a, &p);
     memcpy(out + 1, &p, sizeof(p));
     out[NANO_Q80_GEMM_PLAN_WORDS - 1] = 1u;
     return 0;
 }
 
-// The Q4K launch route_projection() issues for a descriptor: route_kind() -- assuming the step's scratch for the staged groups is present,
-// as in nano_hip_op_fused_gemv below --, then for the GEMV route gemv_q4k_plan() of the first slice and route_gemv_slices(), the
-// functions the launcher and the router themselves follow.  Host arithmetic only -- no device is touched, and of the descriptor's
-// pointers only norm_w and attn_part are looked at (null or not), never followed.  A launch of one STORE tensor is planned as the
-// step's classifier asks for it: with a request for arg-max partials.
+// The Q4K launch route_projection() issues for a descriptor: route_kind(), then for the GEMV route gemv_q4k_plan() of the first slice.
+// A launch of one STORE tensor is planned as the step's classifier asks for it: with a request for arg-max partials.
 // out = {route, kernel, role, B, nv, ipt, d, loop, rounds, wg[3], rw, nthr, grid, lds_bytes, pre, quant_rows, quant_nthr, quant_nv,
 // partials, launches, seqs_per_launch, takes}; the GEMM route reports the route, one launch of nb sequences and zeros for the kernel
 // fields.  takes = 0: the router refuses the shape (hipErrorInvalidValue before any launch) and every other entry is 0.
-extern "C" int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[24]) {
-    if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
-    const NanoFusedGemvDesc &d = *dp;
-    if (d.quant != NANO_QUANT_Q4K) { nano_hip_set_error_("not a Q4K launch"); return NANO_HIP_EINVAL; }
-    if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    static uint8_t scratch_flag[4];                 // stands for the scratch and the partials' buffer: compared with null, never followed
-    GemvArgs a{};
-    for (uint32_t s = 0; s < d.nseg; s++) a.seg[s].rows = d.rows[s];
-    a.nseg = d.nseg; a.n = d.n; a.nb = d.nb; a.cus = cus ? cus : 256u;
-    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
-    a.norm_w = d.norm_w;
-    if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
-    if (d.kind == 0 && d.nseg == 1) a.tile_max = reinterpret_cast<float *>(scratch_flag);
-    Q80Route r{};
-    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = 9u;
-    r.q4x = scratch_flag; r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);       // (as nano_hip_op_fused_gemv sizes it)
-    memset(out, 0, 24 * sizeof(uint32_t));
-    const RouteKind k = route_kind(r, a);
+extern "C" int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_Q4K_GEMV_PLAN_WORDS]) {
+    static float asked;                             // stands for the partials' buffer: compared with null, never followed
+    FusedLaunch L;
+    if (int rc = query_begin(dp, cus, out, NANO_Q4K_GEMV_PLAN_WORDS, NANO_QUANT_Q4K, "not a Q4K launch", F32X_NONE, &L)) return rc;
+    GemvArgs &a = L.a;
+    if (a.epi == GEMV_EPI_STORE && a.nseg == 1) a.tile_max = &asked;
+    const uint32_t k = (uint32_t)route_kind(L.r, a);
     if (k == ROUTE_Q4K_GEMM) {
-        out[0] = (uint32_t)k; out[21] = 1u; out[22] = d.nb; out[23] = 1u;
+        out[0] = k; out[21] = 1u; out[22] = a.nb; out[23] = 1u;
         return 0;
     }
-    a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;          // (as route_projection() hands it on)
-    uint32_t per = 0, launches = 0;
-    Q4kGemvPlan p;
-    if (!route_gemv_slices(d.quant, a, &per, &launches)) return 0;
-    a.nb = per;
-    if (launches > 1) a.tile_max = nullptr;                          // (gemv_slice(): a sliced launch writes no partials)
-    if (!gemv_q4k_plan(a, &p)) return 0;
-    const uint32_t v[24] = { (uint32_t)k, p.kernel, p.role, p.B, p.nv, p.ipt, p.d, p.loop, p.rounds, p.wg[0], p.wg[1], p.wg[2], p.rw, p.nthr, p.grid,
-                             p.lds_bytes, p.pre, p.quant_rows, p.quant_nthr, p.quant_nv, p.partials, launches, per, 1u };
-    memcpy(out, v, sizeof(v));
-    return 0;
+    route_fill(L.r, a);
+    return report_first_slice<NANO_Q4K_GEMV_PLAN_WORDS>(L, out, gemv_q4k_plan, [k](const Q4kGemvPlan &p) {
+        return Words<21>{{ k, p.kernel, p.role, p.B, p.nv, p.ipt, p.d, p.loop, p.rounds, p.wg[0], p.wg[1], p.wg[2], p.rw, p.nthr, p.grid,
+                           p.lds_bytes, p.pre, p.quant_rows, p.quant_nthr, p.quant_nv, p.partials }}; });
 }
 
-// One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs.
-// With d.tile_max the launch is the step's classifier launch where route_asks_partials() (route.hip, enqueue_classifier's own condition)
-// says so: it is handed the caller's partials buffer -- uploaded whole, read back whole -- and writes nb x gemv_tiles() pairs into it as
+// One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs, through the
+// step's own router (route.hip).
+// With d.tile_max the launch is the step's classifier launch where route_partials() (route.hip, enqueue_classifier's own question) says
+// so: it is handed the caller's partials buffer -- uploaded whole, read back whole -- and writes nb x route_partials() pairs into it as
 // into the step's buffer; *d.ntiles_out reports that count (0: not asked).  With d.argmax_out the arg-max kernel runs behind the launch
 // as a MODE_ARGMAX step builds it (backend_step.hip): over the launch's output, from the partials if the launch was asked for them.
 extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
@@ -444,8 +439,11 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     if (!d.x && !d.attn_part) { nano_hip_set_error_("no activation"); return NANO_HIP_EINVAL; }
     if (const char *msg = fused_desc_shape_error(d)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
     if (d.attn_part && !d.attn_ml) { nano_hip_set_error_("bad attention partials"); return NANO_HIP_EINVAL; }
+    hipDeviceProp_t prop; OP_HIP(hipGetDeviceProperties(&prop, device));
+    FusedLaunch L = fused_launch(d, (uint32_t)prop.multiProcessorCount, F32X_ASKED);
+    GemvArgs &a = L.a;
+    Q80Route &r = L.r;
     DevBufs B;
-    GemvArgs a{};
     const size_t bpl = (d.n + 255) / 256;
     uint32_t rows_total = 0;
     for (uint32_t s = 0; s < d.nseg; s++) {
@@ -458,7 +456,6 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         } else if (d.quant == NANO_QUANT_Q4K) a.seg[s].w = B.upload(reinterpret_cast<const uint8_t *>(d.w[s]), rows * bpl * 160);
         else a.seg[s].w = B.upload(reinterpret_cast<const float *>(d.w[s]), rows * d.n);
         OP_CHECK(a.seg[s].w, "device alloc failed");
-        a.seg[s].rows = d.rows[s];
         if (d.kind != 2 || s == 0) rows_total += d.rows[s];
     }
     // out_slots / out_stride (operator tests): out holds more sequence slots than nb and more floats per slot than rows -- guard
@@ -473,43 +470,22 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         a.seg[s].out_bstride = stride;
         if (d.kind != 2) off += d.rows[s];
     }
-    a.nseg = d.nseg; a.n = d.n; a.gs = d.gs; a.nb = d.nb;
-    a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
+    // every host pointer fused_launch() left in the arguments as a flag -> its device copy
     if (d.x) { a.xin = B.upload(d.x, (size_t)d.nb * d.n); OP_CHECK(a.xin, "device alloc failed"); a.xin_bstride = d.n; }
     if (d.norm_w) { a.norm_w = B.upload(d.norm_w, d.n); OP_CHECK(a.norm_w, "device alloc failed"); }
     if (d.attn_part) {
         a.attn_part = B.upload(d.attn_part, (size_t)d.nb * d.attn_nsplit * d.n);
         a.attn_ml = B.upload(d.attn_ml, (size_t)d.nb * d.attn_n_head * d.attn_nsplit * 2);
         OP_CHECK(a.attn_part && a.attn_ml, "device alloc failed");
-        a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd;
         if (!a.xin) { a.xin = a.attn_part; a.xin_bstride = d.n; }     // never read: the prologue combines the partials
     }
-    hipDeviceProp_t prop; OP_HIP(hipGetDeviceProperties(&prop, device));
-    a.cus = (uint32_t)prop.multiProcessorCount;
-    // the step's own router (route.hip): use_gemm = 1 forces the fragment-order route of batched steps (quantizer launch + G6 MODE F /
-    // GC / G2; FP32: lets 9..64 sequences take the MFMA GEMM); ordered = 1 is strict mode (the reference's group order in every kernel)
-    a.ordered = d.ordered ? 1u : 0u;
-    Q80Route r{};
-    r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = d.use_gemm ? 1u : 9u;
-    if (d.quant == NANO_QUANT_Q80) {
-        const size_t n16 = (d.n + 15) & ~(size_t)15, tt = (d.nb + 15) / 16;
-        r.gq = B.alloc<int8_t>(tt * 16 * n16); r.gxs = B.alloc<float>(tt * 16 * (d.n / d.gs));
-        OP_CHECK(r.gq && r.gxs, "device alloc failed");
-    }
-    if (d.quant == NANO_QUANT_Q4K && d.nb > 1) {                       // the staged groups of a several-sequence chunk launch (<= 8) or of the GEMM's tokens
-        r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);
-        r.q4x = B.alloc<uint8_t>(r.q4x_bytes);
-        OP_CHECK(r.q4x, "device alloc failed");
-    }
-    if (d.quant == NANO_QUANT_F32 && d.use_gemm && d.nb > 8) {          // the operand-order activations of gemm_f32.hip; a shape it refuses keeps the slices
-        r.f32_min_nb = 9u;
-        r.f32x_floats = (size_t)((d.nb + 15) / 16) * 16 * ((d.n + 127) & ~(size_t)127);
-        r.f32x = B.alloc<float>(r.f32x_floats);
-        OP_CHECK(r.f32x, "device alloc failed");
-    }
+    // the scratch, exactly as fused_launch() sizes it
+    if (L.gq_bytes) { r.gq = B.alloc<int8_t>(L.gq_bytes); r.gxs = B.alloc<float>(L.gxs_floats); OP_CHECK(r.gq && r.gxs, "device alloc failed"); }
+    if (r.q4x_bytes) { r.q4x = B.alloc<uint8_t>(r.q4x_bytes); OP_CHECK(r.q4x, "device alloc failed"); }
+    if (r.f32x_floats) { r.f32x = B.alloc<float>(r.f32x_floats); OP_CHECK(r.f32x, "device alloc failed"); }
     if (d.use_gemm && d.quant != NANO_QUANT_F32 && (d.quant != NANO_QUANT_Q80 || !route_takes_fragments(route_kind(r, a)))) { nano_hip_set_error_("the batched GEMM route does not take this launch"); return NANO_HIP_EINVAL; }
     if (d.route_out) *d.route_out = (uint32_t)route_kind(r, a);
-    // the step's arg-max partials (enqueue_classifier): asked for where route_asks_partials() says so, into the caller's buffer
+    // the step's arg-max partials (enqueue_classifier): asked for where route_partials() says so, into the caller's buffer
     float *dtm = nullptr;
     uint32_t ntiles = 0;
     const size_t tm_floats = (size_t)d.tile_slots * d.tile_pairs * 2;
@@ -517,12 +493,9 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         if (d.tile_slots < d.nb) { nano_hip_set_error_("tile_slots smaller than the batch"); return NANO_HIP_EINVAL; }
         dtm = tm_floats ? B.upload(d.tile_max, tm_floats) : B.alloc<float>(1);
         OP_CHECK(dtm, "device alloc failed");
-        if (route_asks_partials(r, a)) {
-            a.tile_max = dtm;
-            GemvArgs t = a;
-            t.cus = (uint32_t)r.cus; t.q4_scratch = r.q4x; t.q4_scratch_bytes = r.q4x_bytes;      // (what route_projection() will set: the count must match the launch)
-            ntiles = gemv_tiles(d.quant, t);
-            if (d.tile_pairs < ntiles) { nano_hip_set_error_("tile_pairs smaller than the launch's partials"); return NANO_HIP_EINVAL; }
+        if (const uint32_t n = route_partials(r, a)) {
+            if (d.tile_pairs < n) { nano_hip_set_error_("tile_pairs smaller than the launch's partials"); return NANO_HIP_EINVAL; }
+            a.tile_max = dtm; ntiles = n;
         }
     }
     if (d.ntiles_out) *d.ntiles_out = ntiles;

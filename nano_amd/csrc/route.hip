@@ -113,18 +113,33 @@ bool route_gemv_slices(uint32_t quant, const GemvArgs &a, uint32_t *per, uint32_
     *launches = (a.nb + fit - 1) / fit;
     return true;
 }
-// Whether the launch route_projection(r, a) issues is asked for arg-max partials (GemvArgs::tile_max): one STORE tensor of at most 8
-// sequences on a route that takes no fragments, and for Q4K a batch route_gemv_slices() leaves in one launch (gemv_slice(): a sliced
-// launch writes none).  The step's classifier (backend_step.hip enqueue_classifier) and the operator entry point (ops.hip
-// nano_hip_op_fused_gemv) both ask here, so that an operator test runs the launch a step runs.  a.ordered as the launch will carry it.
+// What route_projection() writes into the arguments on every path, before it asks route_kind() or launches: the device's compute units and
+// the Q4K scratch (null / 0 in the route of every other format, where the fields are null / 0 already).  The one place they are written:
+// whoever must see a launch as it will be issued (route_partials() below, the plan queries of ops.hip) calls this, and mirrors nothing.
+void route_fill(const Q80Route &r, GemvArgs &a) {
+    a.cus = (uint32_t)r.cus;
+    a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
+}
+// The (max, row) arg-max pairs per sequence the launch route_projection(r, a) issues is asked for (GemvArgs::tile_max) and writes; 0: it
+// is not asked.  Asked: one STORE tensor of at most 8 sequences on a route that takes no fragments, and for Q4K a batch
+// route_gemv_slices() leaves in one launch (gemv_slice(): a sliced launch writes none); the count is gemv_tiles() of the launch with
+// the request made (the planners read tile_max as a flag).  The step's classifier (backend_step.hip enqueue_classifier) and the
+// operator entry point (ops.hip nano_hip_op_fused_gemv) both ask here, a.tile_max still null, and hand the launch their buffer where
+// the answer is not 0, so that an operator test runs the launch a step runs.  a.ordered as the launch will carry it.
+// (A launch that is asked but writes no pairs -- FP32, the Q80 SLAB kernel, the Q4K chunk kernel's 2..8 sequences -- used to carry the
+// buffer unread; it no longer does.  Only the Q4K GEMM, which refuses a launch that carries one, can tell: with NANO_MFMA_MIN_NB = 2..8
+// such a classifier launch now takes the GEMM that switch asks for.  Same bits; nothing moves at the default 9.)
 // FINDING, left as it was: Q80 is not asked how many launches the batch takes.  A STREAM classifier on rows of more than ~18 200 values
 // at 5..8 sequences (group size 32: 18 432 values run as 4 + 1) is cut by route_gemv_slices(), its slices write no partials, and
 // gemv_tiles() still reports STREAM_WGS * 4 of them.  No model has such rows; the one-launch test of Q4K would close it.
-bool route_asks_partials(const Q80Route &r, GemvArgs a) {
-    a.cus = (uint32_t)r.cus; a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;      // (what route_projection() will set)
-    if (a.epi != GEMV_EPI_STORE || a.nseg != 1 || a.nb > 8 || route_takes_fragments(route_kind(r, a))) return false;
+uint32_t route_partials(const Q80Route &r, GemvArgs a) {
+    static float asked;                                                 // stands for the caller's buffer: compared with null, never followed
+    route_fill(r, a);
+    if (a.epi != GEMV_EPI_STORE || a.nseg != 1 || a.nb > 8 || route_takes_fragments(route_kind(r, a))) return 0;
     uint32_t per = 0, launches = 0;
-    return r.quant != NANO_QUANT_Q4K || (route_gemv_slices(r.quant, a, &per, &launches) && launches == 1);
+    if (r.quant == NANO_QUANT_Q4K && !(route_gemv_slices(r.quant, a, &per, &launches) && launches == 1)) return 0;
+    a.tile_max = &asked;
+    return gemv_tiles(r.quant, a);
 }
 // the GEMV launches of a.nb sequences, cut where route_gemv_slices() says so; a shape of which not even one sequence fits is refused
 // before any launch
@@ -141,7 +156,7 @@ static hipError_t launch_gemv_sliced(uint32_t quant, const GemvArgs &a, hipStrea
 }
 
 hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
-    a.cus = (uint32_t)r.cus;
+    route_fill(r, a);
     Q80GemmPlan gp{};
     const RouteKind k = route_kind(r, a, &gp);
     if (k == ROUTE_F32_GEMM) {
@@ -151,10 +166,8 @@ hipError_t route_projection(const Q80Route &r, GemvArgs &a, hipStream_t st) {
     if (r.quant != NANO_QUANT_Q80 && r.quant != NANO_QUANT_Q4K) return launch_gemv_sliced(r.quant, a, st);      // FP32 (ROUTE_GEMV | ROUTE_GEMV_SLICED)
     switch (k) {
     case ROUTE_Q4K:
-        a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
         return launch_gemv_sliced(r.quant, a, st);
     case ROUTE_Q4K_GEMM:
-        a.q4_scratch = r.q4x; a.q4_scratch_bytes = r.q4x_bytes;
         return launch_gemm_q4k(a, st);
     case ROUTE_FRAG_G6:
     case ROUTE_FRAG_G7:

@@ -11,12 +11,9 @@ import pytest
 from conftest import E2E_CASES, GOLD, e2e_golden, file_sha256, synth_model
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # ---- 1. tiny models, every golden case ------------------------------------------------------------------------------------------

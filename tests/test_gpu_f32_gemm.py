@@ -19,19 +19,11 @@ import numpy as np
 import pytest
 
 from nano_amd import binding as nb
+from fused_ref import bits, order_free, silu_mul, rows_total
 
 F32 = 0x00
 U = 2.0 ** -24
 SENTINEL = np.float32(-12345.678)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape):
-    """multiples of 2^-4 in [-2, 2] (test_gpu_f32_gemv.py order_free)"""
-    return (rng.integers(-32, 33, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
 
 
 def exact_weights(rng, rows, n):
@@ -53,16 +45,6 @@ def swiglu_bound(h1, S1, h3, S3, n):
     e1, e3 = row_bound(h1, S1, n), row_bound(h3, S3, n)
     silu = h1 / (1.0 + np.exp(-h1))
     return silu * h3, 1.1 * e1 * np.abs(h3) + np.abs(silu) * e3 + 1.1 * e1 * e3 + 3e-6 * np.abs(silu * h3)
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    with np.errstate(over="ignore"):
-        return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
-
-
-def rows_total(kind, rows):
-    return rows[0] if kind == 2 else sum(rows)
 
 
 def run(kind, n, W, x, nw, old, use_gemm, want_route):

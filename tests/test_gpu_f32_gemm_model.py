@@ -9,15 +9,12 @@ import pytest
 
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 S, T = 256, 150                          # 150 prompt tokens: two full chunks and a tail of 22
 PRESETS = ["tiny-nano", "tiny-nano-odd"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 class min_nb:

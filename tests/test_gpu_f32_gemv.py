@@ -38,6 +38,7 @@ import numpy as np
 import pytest
 
 from nano_amd import binding as nb
+from fused_ref import bits, order_free, silu_mul, rows_total
 
 F32 = 0x00
 U = 2.0 ** -24
@@ -45,24 +46,9 @@ SENTINEL = np.float32(-12345.678)
 ROLE = {n: i for i, n in enumerate(nb.F32_ROLES)}
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape):
-    """multiples of 2^-4 in [-2, 2] (test_gpu_fused_roles.py order_free)"""
-    return (rng.integers(-32, 33, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
-
-
 def exact_weights(rng, rows, n):
     """multiples of 2^-4 in [-1, 1]"""
     return (rng.integers(-16, 17, size=(rows, n), dtype=np.int8).astype(np.float32) / np.float32(16.0)).astype(np.float32)
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    with np.errstate(over="ignore"):            # exp(-a) beyond fp32 is +inf on the device too: silu = a * 0
-        return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
 def plan(role, B, nv, upw, rw, nw, launches=1, per=None, lds=None):
@@ -137,10 +123,6 @@ CASES = [
 ]
 
 
-def rows_total(c):
-    return c["rows"][0] if c["kind"] == 2 else sum(c["rows"])
-
-
 def query(c):
     attn = (c["comb"][0], c["comb"][1], len(c["comb"][2])) if c["comb"] else None
     return nb.f32_gemv_plan(c["kind"], c["n"], c["rows"], c["nb"], norm=c["norm"], attn=attn)
@@ -168,7 +150,7 @@ def build(c):
         x = (part.astype(np.float64).sum(axis=1) / L).astype(np.float32)            # every split's weight is exp(0) / L
         assert np.array_equal(x.astype(np.float64), part.astype(np.float64).sum(axis=1) / L)
         attn, amax, gran = (part, ml, n_head, hd), 2.0 * len(ls) / L, 2.0 ** -4 / L
-    old = (rng.integers(-1024, 1025, size=(nb_, rows_total(c))).astype(np.float32) / np.float32(256.0)) if c["kind"] == 1 else None
+    old = (rng.integers(-1024, 1025, size=(nb_, rows_total(c["kind"], c["rows"]))).astype(np.float32) / np.float32(256.0)) if c["kind"] == 1 else None
     if not c["norm"]:
         # exactness: every partial sum is a multiple of g = (2^-4 weights) x (activation granularity), the residual of 2^-8 >= g
         g, bound = 2.0 ** -4 * gran, n * 1.0 * amax + 4.0
@@ -225,7 +207,7 @@ def swiglu_bound(h1, S1, h3, S3, n):
 def launch(c, I, sl=None):
     """the case's launch, or with sl = b the same launch of sequence b alone; the batched launch runs in a guarded buffer"""
     weights = [(w, None, w.shape[0]) for w in I["W"]]
-    rt = rows_total(c)
+    rt = rows_total(c["kind"], c["rows"])
     if sl is not None:
         b = slice(sl, sl + 1)
         attn = (I["attn"][0][b], I["attn"][1][b], I["attn"][2], I["attn"][3]) if I["attn"] else None
@@ -244,7 +226,7 @@ def test_f32_gemv_plan_case(oracle, c):
     q = query(c)
     assert q["takes"] == 1, (c["id"], "the router refuses this shape: nothing is launched", q)
     I = build(c)
-    kind, n, nb_, rt = c["kind"], c["n"], c["nb"], rows_total(c)
+    kind, n, nb_, rt = c["kind"], c["n"], c["nb"], rows_total(c["kind"], c["rows"])
     g = launch(c, I)
     out = g[:nb_, :rt]
     errors = []
@@ -336,7 +318,7 @@ def test_cases_cover_every_plan_axis():
         assert q["takes"] == 1, c["id"]
         assert {k: q[k] for k in c["target"]} == c["target"], (c["id"], q)
         T.append(dict(q, id=c["id"], kind=c["kind"], n=c["n"], rows=c["rows"], nb=c["nb"], norm=c["norm"], comb=c["comb"] is not None,
-                      total=rows_total(c)))
+                      total=rows_total(c["kind"], c["rows"])))
 
     def has(f=None, **kw):
         return any(all(t[k] == v for k, v in kw.items()) and (f is None or f(t)) for t in T)

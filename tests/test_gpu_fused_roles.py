@@ -27,19 +27,11 @@ import pytest
 from canon import matmul_q80_canon
 from conftest import ROOT
 from nano_amd import binding as nb
+from fused_ref import bits, order_free, silu_mul
 
 pytestmark = pytest.mark.gpu
 
 Q80, Q4K = 0x80, 0x42
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape):
-    """multiples of 2^-4 in [-2, 2]: sums of squares of up to 2^14 of them are exact in fp32 in any order"""
-    return (rng.integers(-32, 33, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
 
 
 def q80_weights(rng, rows, n, gs):
@@ -77,11 +69,6 @@ def check_q80(oracle, kind, n, segs, x, nw, old, nb_, *, attn=None, act_of=None,
     if routes is not None:
         assert route in routes, route
     return route
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
 # (name, n, rows of the weight tensors, the fast path's route): Qwen3-0.6B and Qwen3-4B per-layer shapes (SLAB GEMV)

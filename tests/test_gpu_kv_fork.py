@@ -13,14 +13,11 @@ from conftest import e2e_golden
 from conftest import synth_model as golden_model
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 S, B, T = 256, 4, 70                 # context, slots, continuation steps (70 > 64: every continuation enters a new 64-position block)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 _models = {}

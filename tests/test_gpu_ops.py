@@ -7,12 +7,9 @@ import pytest
 from conftest import rel_err
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_device_is_gfx950():

@@ -10,12 +10,9 @@ import os
 
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 _models = {}

@@ -14,15 +14,12 @@ from conftest import synth_model
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
 from score_ref import check_scores, ref_scores
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 S = 96
 TOL_Q80 = 2e-2                       # test_gpu_e2e.py TOL["q80"]: Q80 logits, relative to the row's largest |logit|
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 _logits = {}

@@ -10,19 +10,11 @@ import pytest
 
 from conftest import synth_model
 from nano_amd import binding as nb
+from fused_ref import bits, order_free, silu_mul
 
 pytestmark = pytest.mark.gpu
 
 Q4K = 0x42
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape):
-    """multiples of 2^-4 in [-2, 2]: sums of squares of up to 2^14 of them are exact in fp32 in any order"""
-    return (rng.integers(-32, 33, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
 
 
 def q4k_weights(oracle, rng, rows, n):
@@ -33,11 +25,6 @@ def q4k_weights(oracle, rng, rows, n):
 def ref_q4k(oracle, act, WTs, n):
     XT = oracle.quantize_q4k(np.ascontiguousarray(act, np.float32), [n])
     return np.concatenate([oracle.matmul_q4k(XT, WT, 0, rows) for WT, rows in WTs])
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
 class min_nb:

@@ -5,7 +5,7 @@ arg-max partials a one-tensor STORE launch writes for the step's sampler (gemv_q
 (misc.hip) reduces instead of scanning the logits.
 
 The launches go through nb.op_fused_gemv(0x42, ...), i.e. the step's own router (route.hip), which hands a launch the partials buffer
-exactly where the step's classifier does (route_asks_partials()); nb.q4k_gemv_plan reports the plan the launchers follow.  There is ONE
+exactly where the step's classifier does (route_partials()); nb.q4k_gemv_plan reports the plan the launchers follow.  There is ONE
 case per kernel instantiation the CPU sweep finds reachable (tests/test_q4k_gemv_plan.py UNIVERSE: 55 slab and 90 chunk tuples), named by
 its tuple, at the smallest shape the search found for it, plus cases for the axes the tuples do not carry; the closing coverage test reads
 the plans (no GPU) and holds both.  Values are checked first (a plan mismatch must not hide a wrong result).
@@ -40,26 +40,12 @@ import pytest
 
 from nano_amd import binding as nb
 from test_q4k_gemv_plan import UNIVERSE, ROLE, plan_tuple
+from fused_ref import bits, order_free, silu_mul, rows_total
 
 Q4K = 0x42
 SENTINEL = np.float32(-12345.678)
 POISON = np.array([np.inf, 0.0], np.float32)               # (+inf, row 0): wins any reduction that reads it
 NO_ROW = 0xffffffff
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape, amp=32):
-    """multiples of 2^-4 in [-amp / 16, amp / 16] (test_gpu_fused_roles.py order_free)"""
-    return (rng.integers(-amp, amp + 1, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    with np.errstate(over="ignore"):
-        return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
 def case(cid, kind, n, rows, nb_, want, norm=False, comb=None, ties=False, **more):
@@ -292,10 +278,6 @@ CASES = [
 ]
 
 
-def rows_total(c):
-    return c["rows"][0] if c["kind"] == 2 else sum(c["rows"])
-
-
 def query(c, **kw):
     attn = (c["comb"][0], c["comb"][1], len(c["comb"][2])) if c["comb"] else None
     return nb.q4k_gemv_plan(c["kind"], c["n"], c["rows"], c["nb"], norm=c["norm"], attn=attn, **kw)
@@ -350,7 +332,7 @@ def build(oracle, c, q):
         x = (part.astype(np.float64).sum(axis=1) / L).astype(np.float32)            # every split's weight is exp(0) / L
         assert np.array_equal(x.astype(np.float64), part.astype(np.float64).sum(axis=1) / L)
         attn = (part, ml, n_head, hd)
-    old = rng.standard_normal((nb_, rows_total(c))).astype(np.float32) if c["kind"] == 1 else None
+    old = rng.standard_normal((nb_, rows_total(c["kind"], c["rows"]))).astype(np.float32) if c["kind"] == 1 else None
     XT = [oracle.quantize_q4k(oracle.rmsnorm(x[b], nw) if c["norm"] else x[b], [n]) for b in range(nb_)]
     pool_ref = [oracle.matmul_q4k(XT[b], T, 0, P) for b in range(nb_)]
     if c["ties"]:
@@ -423,7 +405,7 @@ def test_q4k_gemv_plan_case(oracle, c):
     q = query(c)
     assert q["takes"] == 1 and nb.ROUTE_NAMES[q["route"]] == "q4k", (c["id"], "the router sends this shape elsewhere or refuses it", q)
     I = build(oracle, c, q)
-    kind, nb_, rt = c["kind"], c["nb"], rows_total(c)
+    kind, nb_, rt = c["kind"], c["nb"], rows_total(c["kind"], c["rows"])
     errors = []
 
     def held(out, what, b, want):
@@ -500,7 +482,7 @@ def test_cases_cover_every_plan_tuple():
         assert got == c["target"], (c["id"], q)
         bpl = (c["n"] + 255) // 256
         T.append(dict(q, id=c["id"], tuple=plan_tuple(q), kern=plan_tuple(q)[0], kind=c["kind"], n=c["n"], rows=c["rows"], nb=c["nb"], norm=c["norm"],
-                      comb=c["comb"] is not None, ties=c["ties"], total=rows_total(c), GT=bpl * 8, last=c["rows"][0] % q["rw"]))
+                      comb=c["comb"] is not None, ties=c["ties"], total=rows_total(c["kind"], c["rows"]), GT=bpl * 8, last=c["rows"][0] % q["rw"]))
     reached = {t["tuple"] for t in T}
     assert reached == UNIVERSE, ("not reached", sorted(UNIVERSE - reached), "not in the sweep's universe", sorted(reached - UNIVERSE))
     assert len({t["id"] for t in T}) == len(T)

@@ -33,26 +33,12 @@ import pytest
 
 from nano_amd import binding as nb
 from test_q80_gemv_plan import UNIVERSE, VAR, ROLE, SLAB, STREAM, canonical
+from fused_ref import bits, order_free, silu_mul, rows_total
 
 Q80 = 0x80
 SENTINEL = np.float32(-12345.678)
 POISON = np.array([np.inf, 0.0], np.float32)               # (+inf, row 0): wins any reduction that reads it
 NO_ROW = 0xffffffff
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def order_free(rng, shape):
-    """multiples of 2^-4 in [-2, 2] (test_gpu_fused_roles.py order_free)"""
-    return (rng.integers(-32, 33, size=shape).astype(np.float32) / np.float32(16.0)).astype(np.float32)
-
-
-def silu_mul(a, b):
-    a = a.astype(np.float32)
-    with np.errstate(over="ignore"):
-        return (a * (np.float32(1) / (np.float32(1) + np.exp(-a.astype(np.float64)).astype(np.float32))) * b).astype(np.float32)
 
 
 def case(cid, gs, kind, n, rows, nb_, want, norm=False, comb=None, ties=False, **more):
@@ -169,10 +155,6 @@ CASES = [
 ]
 
 
-def rows_total(c):
-    return c["rows"][0] if c["kind"] == 2 else sum(c["rows"])
-
-
 def query(c, **kw):
     attn = (c["comb"][0], c["comb"][1], len(c["comb"][2])) if c["comb"] else None
     return nb.q80_gemv_plan(c["kind"], c["n"], c["rows"], c["nb"], gs=c["gs"], norm=c["norm"], attn=attn, **kw)
@@ -197,7 +179,7 @@ def build(c):
         x = (part.astype(np.float64).sum(axis=1) / L).astype(np.float32)            # every split's weight is exp(0) / L
         assert np.array_equal(x.astype(np.float64), part.astype(np.float64).sum(axis=1) / L)
         attn = (part, ml, n_head, hd)
-    old = rng.standard_normal((nb_, rows_total(c))).astype(np.float32) if c["kind"] == 1 else None
+    old = rng.standard_normal((nb_, rows_total(c["kind"], c["rows"]))).astype(np.float32) if c["kind"] == 1 else None
     return dict(W=W, nw=nw, x=x, attn=attn, old=old)
 
 
@@ -226,7 +208,7 @@ def launch(c, I, *, kind=None, ordered=False, sl=None, guarded=True, partials=No
     """the case's launch, or with sl = b the same launch of sequence b alone; the batched launch runs in a guarded buffer (partials: the
     step's partials buffer, want_argmax: the arg-max kernel behind the launch -- then (out, route, ntiles or None, argmax or None))"""
     kind = c["kind"] if kind is None else kind
-    rt = rows_total(c) if kind == c["kind"] else sum(c["rows"])
+    rt = rows_total(c["kind"], c["rows"]) if kind == c["kind"] else sum(c["rows"])
     if sl is not None:
         b = slice(sl, sl + 1)
         attn = (I["attn"][0][b], I["attn"][1][b], I["attn"][2], I["attn"][3]) if I["attn"] else None
@@ -376,7 +358,7 @@ def test_cases_cover_every_plan_axis():
         assert got == c["target"], (c["id"], q)
         assert (q["kernel"], q["B"], q["nv"], q["upw"], q["variant"]) in UNIVERSE, (c["id"], "a plan the sweep does not know", q)
         T.append(dict(q, id=c["id"], kind=c["kind"], n=c["n"], rows=c["rows"], nb=c["nb"], norm=c["norm"], comb=c["comb"] is not None, ties=c["ties"],
-                      total=rows_total(c), route_name=nb.ROUTE_NAMES[q["route"]]))
+                      total=rows_total(c["kind"], c["rows"]), route_name=nb.ROUTE_NAMES[q["route"]]))
 
     def has(f=None, **kw):
         return any(all(t[k] == v for k, v in kw.items()) and (f is None or f(t)) for t in T)

@@ -12,14 +12,11 @@ import pytest
 from conftest import E2E_CASES, GOLD, e2e_golden, rel_err, synth_model
 from nano_amd import binding as nb
 from oracle import binding as ob
+from fused_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 CASES = E2E_CASES
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("preset,quant,gs", CASES)

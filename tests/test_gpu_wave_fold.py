@@ -13,19 +13,12 @@ import pytest
 from canon import matmul_q80_canon
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits, order_free, silu_mul
 
 pytestmark = pytest.mark.gpu
 
 Q80, N, GS = 0x80, 1024, 64
 F = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def order_free(rng, shape):
-    return (rng.integers(-32, 33, size=shape).astype(F) / F(16.0)).astype(F)
 
 
 def weights(rng, rows):
@@ -37,11 +30,6 @@ def weights(rng, rows):
 def canon_of(oracle, x, nw, segs):
     xq, xs = oracle.quantize_q80(oracle.rmsnorm(x, nw), GS)
     return np.concatenate([matmul_q80_canon(xq, xs, wq, ws, N, rows, GS) for wq, ws, rows in segs])
-
-
-def silu_mul(a, b):
-    a = a.astype(F)
-    return (a * (F(1) / (F(1) + np.exp(-a.astype(np.float64)).astype(F))) * b).astype(F)
 
 
 def store_case(oracle, rng, rows, segs=None):

@@ -13,19 +13,12 @@ import pytest
 from canon import matmul_q80_canon
 from nano_amd import binding as nb
 from nano_amd import modelfile as mf
+from fused_ref import bits, order_free
 
 pytestmark = pytest.mark.gpu
 
 Q80, GS = 0x80, 64
 F = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def order_free(rng, shape):
-    return (rng.integers(-32, 33, size=shape).astype(F) / F(16.0)).astype(F)
 
 
 def weights(rng, rows, n):

@@ -10,12 +10,9 @@ import pytest
 from conftest import E2E_CASES, GOLD, e2e_golden, file_sha256, synth_model
 from nano_amd import modelfile as mf
 from oracle import binding as ob
+from fused_ref import bits
 
 E2E = E2E_CASES
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("preset,quant,gs", E2E)

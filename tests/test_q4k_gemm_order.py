@@ -14,14 +14,11 @@ That is bit for bit the oracle for every R.  A second model that lets two waves 
 lines is NOT: float addition does not associate, so lines must not be pre-added per wave."""
 import numpy as np
 import pytest
+from fused_ref import bits
 
 f32 = np.float32
 NS = (256, 768, 2560)
 ROWS, ACTS, SEED = 16, 3, 5
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def unpack6(sb):
