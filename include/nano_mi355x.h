@@ -546,6 +546,55 @@ int nano_hip_q80_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
 #define NANO_Q4K_GEMV_PLAN_WORDS 24
 int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_Q4K_GEMV_PLAN_WORDS]);
 
+/* ---- the two fused one-sequence launches of a decode step: their plans, and each launch alone on caller inputs ----
+ * nano_hip_qkv_attn_fused_plan: the q | k | v + attention launch a step issues for the projection `qkv` (kind 0, three tensors, one
+ * sequence, norm_w) and the attention `attn` (nb = 1; its nsplit, 0: the step's own choice for range_hint, and range_hint), from the function
+ * the launcher follows: out = {kernel, nv, upw, d, qv, threads, n_attn, ngemv, lds_bytes, rw, wg[3], rounds, 0, takes}.  kernel 1 =
+ * qkv_attn_fused_kernel<nv, upw> (Q80, product table), 2 = qkv_attn_fused_wf_kernel<1, upw> (Q80, rows of one chunk folded in the wave),
+ * 3 = q4k_qkv_attn_fused_kernel<nv, d>, 4 = f32_qkv_attn_fused_kernel<1, upw, qv>; `threads` threads x (ngemv projection workgroups of rw
+ * rows, wg[s] on tensor s (FP32: all in wg[0]), then n_attn attention workgroups), lds_bytes of dynamic LDS.  takes = 0: the step issues the
+ * two plain launches -- the shape is refused, or the projection's route is not the one GEMV / Q4K launch -- and every other entry is 0.
+ * nano_hip_wo_w13_fused_plan: the Wo + W1|W3 launch (Q80) for `wo` (kind 1, optional attn_part) and `w13` (kind 2, norm_w; n = wo's rows):
+ * out = {sig, threads, role, wf, wfc, nv_a, upw_a, nv_b, upw_b, wa, wb, lds_bytes, rw_a, rw_b, 0, takes} -- wo_w13_fused_kernel<role, nv_a,
+ * upw_a, nv_b, upw_b, threads, wf, wfc> on wb workgroups, the first wa of which also run Wo's rows (rw_a and rw_b rows per workgroup); role
+ * 2 = residual, 3 = residual behind the split combine.  takes = 0 likewise.
+ * Both are host arithmetic on the shape fields: they work without a device and follow no pointer (norm_w, q_norm / k_norm and attn_part
+ * are read as null or not; every other pointer of the descriptors is not looked at). */
+#define NANO_QKV_ATTN_FUSED_PLAN_WORDS 16
+#define NANO_WO_W13_FUSED_PLAN_WORDS 16
+int nano_hip_qkv_attn_fused_plan(const NanoFusedGemvDesc *qkv, const NanoAttnDecodeDesc *attn, uint32_t cus, uint32_t out[NANO_QKV_ATTN_FUSED_PLAN_WORDS]);
+int nano_hip_wo_w13_fused_plan(const NanoFusedGemvDesc *wo, const NanoFusedGemvDesc *w13, uint32_t cus, uint32_t out[NANO_WO_W13_FUSED_PLAN_WORDS]);
+/* One q | k | v + attention launch exactly as a step issues it (replaces infer/infer.c:758-786 and 810-879 of one layer).  The op stages
+ * the RoPE row of pos as the embed kernel does, takes the granule buffer and the tick words from the code a model takes them from, sets
+ * tick[0] = tick0 + 1 (the embed kernel opens a new epoch) and issues the launch with layer1 (1..127; the tag is tick * 128 + layer1).
+ * qkv: x [n], norm_w, the three tensors; its out, if not NULL, receives the raw q | raw k rows the launch stored ([q_dim + kv_dim]).  attn: nb = 1, contiguous FP32 cache; q and k are not read (the launch's own
+ * projection feeds the attention); k_cache / v_cache go in and come back whole; out = the head outputs (nsplit > 1: the partials combined
+ * as a step combines them).  A shape the plan refuses: NANO_HIP_EINVAL before any launch.  A consumer that gave up its wait
+ * (NANO_DEVERR_HANDOFF in the error word): NANO_HIP_ERUNTIME, and no result is handed back. */
+typedef struct NanoQkvAttnFusedDesc {
+    const NanoFusedGemvDesc *qkv;
+    const NanoAttnDecodeDesc *attn;
+    uint32_t layer1, tick0;
+    const unsigned long long *hand_init;   /* optional: the granule buffer's content before the launch, q_dim + 2 kv_dim entries (tag << 32 | value bits); NULL: zeros */
+    float *part_out;            /* optional, nsplit > 1: [nsplit][q_dim] raw partials */
+    float *ml_out;              /* optional, nsplit > 1: [n_head][nsplit][2] */
+    uint32_t *plan_out;         /* optional [NANO_QKV_ATTN_FUSED_PLAN_WORDS]: the plan that ran */
+    uint32_t *err_out;          /* optional: the model-style sticky error word after the launch */
+} NanoQkvAttnFusedDesc;
+int nano_hip_op_qkv_attn_fused(int device, const NanoQkvAttnFusedDesc *d);
+/* One Wo + W1|W3 launch exactly as a step issues it (replaces infer/infer.c:885-944 of one layer).  wo: kind 1, x = the attention output
+ * [n] or attn_part / attn_ml; its out holds the residual stream on entry and on return.  w13: kind 2 with norm_w; its x is not read -- the
+ * launch's input is the residual stream Wo leaves, as in a step; its out receives hb.  tick0, layer1, hand_init (w13->n entries), refusal
+ * and give-up as for nano_hip_op_qkv_attn_fused. */
+typedef struct NanoWoW13FusedDesc {
+    const NanoFusedGemvDesc *wo, *w13;
+    uint32_t layer1, tick0;
+    const unsigned long long *hand_init;
+    uint32_t *plan_out;         /* optional [NANO_WO_W13_FUSED_PLAN_WORDS] */
+    uint32_t *err_out;
+} NanoWoW13FusedDesc;
+int nano_hip_op_wo_w13_fused(int device, const NanoWoW13FusedDesc *d);
+
 /* One device-resident copy of a model's parameter bytes per GPU from ONE host upload (replicate.hip; SURVEY 8e "broadcast(weights) at
  * load"): the bytes go to `root_device` over PCIe once and from there to the other devices over xGMI -- an RCCL broadcast (librccl.so
  * is dlopen()ed on first use) or, when RCCL is unavailable / NANO_REPLICATE_VIA=peer, hipMemcpyPeer; NANO_REPLICATE_VIA=host uploads

@@ -46,6 +46,18 @@ class NanoAttnDecodeDesc(C.Structure):
                                           "out", "xf", "xsf", "plan")]
 
 
+class NanoQkvAttnFusedDesc(C.Structure):
+    """include/nano_mi355x.h NanoQkvAttnFusedDesc: one fused q | k | v + attention launch as a step issues it."""
+    _fields_ = [("qkv", C.POINTER(NanoFusedGemvDesc)), ("attn", C.POINTER(NanoAttnDecodeDesc)), ("layer1", C.c_uint32), ("tick0", C.c_uint32),
+                ("hand_init", C.c_void_p), ("part_out", C.c_void_p), ("ml_out", C.c_void_p), ("plan_out", C.c_void_p), ("err_out", C.c_void_p)]
+
+
+class NanoWoW13FusedDesc(C.Structure):
+    """include/nano_mi355x.h NanoWoW13FusedDesc: one fused Wo + W1|W3 launch as a step issues it."""
+    _fields_ = [("wo", C.POINTER(NanoFusedGemvDesc)), ("w13", C.POINTER(NanoFusedGemvDesc)), ("layer1", C.c_uint32), ("tick0", C.c_uint32),
+                ("hand_init", C.c_void_p), ("plan_out", C.c_void_p), ("err_out", C.c_void_p)]
+
+
 class NanoExactAttnDesc(C.Structure):
     """include/nano_mi355x.h NanoExactAttnDesc: exact mode's attention of one sequence and one layer."""
     _fields_ = [(n, C.c_uint32) for n in ("n_head", "n_kv_head", "hd", "S", "range", "is_causal", "long_form", "_pad")] + \
@@ -90,6 +102,16 @@ Q80_GEMM_KERNELS = ("none", "g6s", "g6f", "g7", "g7k", "gc", "g2")
 Q4K_PLAN_FIELDS = ("route", "kernel", "role", "B", "nv", "ipt", "d", "loop", "rounds", "wg0", "wg1", "wg2", "rw", "nthr", "grid", "lds_bytes",
                    "pre", "quant_rows", "quant_nthr", "quant_nv", "partials", "launches", "seqs_per_launch", "takes")
 Q4K_KERNELS = ("none", "slab", "chunk")
+
+
+# what nano_hip_qkv_attn_fused_plan / nano_hip_wo_w13_fused_plan report (nano_amd/csrc/kernels.h QkvAttnFusedPlan / WoW13FusedPlan): kernel is
+# an index into FUSED_KERNELS, role into Q80_ROLES; the word before takes is always 0
+QKV_ATTN_FUSED_PLAN_FIELDS = ("kernel", "nv", "upw", "d", "qv", "threads", "n_attn", "ngemv", "lds_bytes", "rw", "wg0", "wg1", "wg2", "rounds",
+                              "_zero", "takes")
+WO_W13_FUSED_PLAN_FIELDS = ("sig", "threads", "role", "wf", "wfc", "nv_a", "upw_a", "nv_b", "upw_b", "wa", "wb", "lds_bytes", "rw_a", "rw_b",
+                            "_zero", "takes")
+FUSED_KERNELS = ("none", "q80_table", "q80_wf", "q4k", "f32")
+NANO_DEVERR_HANDOFF = 2
 
 
 # RouteKind of nano_amd/csrc/kernels.h (what NanoFusedGemvDesc.route_out reports)
@@ -200,6 +222,10 @@ def lib() -> C.CDLL:
     fn("nano_hip_q80_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q80_gemm_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_q4k_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_qkv_attn_fused_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.POINTER(NanoAttnDecodeDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_wo_w13_fused_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
+    fn("nano_hip_op_qkv_attn_fused", C.c_int, [C.c_int, C.POINTER(NanoQkvAttnFusedDesc)])
+    fn("nano_hip_op_wo_w13_fused", C.c_int, [C.c_int, C.POINTER(NanoWoW13FusedDesc)])
     fn("nano_hip_kv_release", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_kv_pages", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_kv_fork", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32])
@@ -584,10 +610,11 @@ def _fused_shape(quant, kind, n, rows, nb, *, gs=0, norm=False, attn=None, order
 
 
 def _plan_query(name, fields, words, desc, cus):
-    """nano_hip_<name>_plan of a descriptor: `words` output words, the first len(fields) of them named."""
+    """nano_hip_<name>_plan of a descriptor (a tuple: of the query's two descriptors): `words` output words, the first len(fields) of them named."""
     assert len(fields) <= words
     out = (C.c_uint32 * words)()
-    check(getattr(lib(), f"nano_hip_{name}_plan")(C.byref(desc), cus, out))
+    descs = desc if isinstance(desc, tuple) else (desc,)
+    check(getattr(lib(), f"nano_hip_{name}_plan")(*(C.byref(d) for d in descs), cus, out))
     return dict(zip(fields, (int(v) for v in out)))
 
 
@@ -733,6 +760,132 @@ def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n
     if want_frag:
         res["xf"], res["xsf"] = xf, xsf
     return res
+
+
+def _attn_shape(n_head, n_kv_head, hd, *, range_hint, nsplit=0, rope_qwen3=True, qk_norm=True, n_layer=1, layer=0, S=None) -> NanoAttnDecodeDesc:
+    """The shape part of a one-sequence NanoAttnDecodeDesc -- all the fused plan query reads (qk_norm: _FLAG stands for the two weights)."""
+    d = NanoAttnDecodeDesc()
+    d.nb, d.n_head, d.n_kv_head, d.hd, d.n_layer, d.layer = 1, n_head, n_kv_head, hd, n_layer, layer
+    d.S = max(range_hint, 1) if S is None else S
+    d.range_hint, d.nsplit, d.rope_qwen3 = range_hint, nsplit, int(bool(rope_qwen3))
+    if qk_norm:
+        d.q_norm = d.k_norm = _FLAG.ctypes.data
+    return d
+
+
+def qkv_attn_fused_plan(quant, n, n_head, n_kv_head, hd, *, range_hint=64, nsplit=0, gs=None, rope_qwen3=None, qk_norm=None, ordered=False,
+                        use_gemm=False, cus=256):
+    """The fused q | k | v + attention launch a one-sequence step issues (nano_hip_qkv_attn_fused_plan; needs no GPU) for a projection of row
+    length n onto n_head / n_kv_head heads of hd, and decode attention with nsplit splits (0: the step's own choice) over range_hint rows.
+    rope_qwen3 / qk_norm default to what the format's models have (Q80, Q4K: Qwen3's; FP32: Nano's plain attention).
+    Returns a dict of QKV_ATTN_FUSED_PLAN_FIELDS; takes == 0: the step issues the two plain launches and every other entry is 0."""
+    qwen = quant != 0x00
+    g = _fused_shape(quant, 0, n, [n_head * hd, n_kv_head * hd, n_kv_head * hd], 1, gs=(64 if quant == 0x80 else 0) if gs is None else gs,
+                     norm=True, ordered=ordered, use_gemm=use_gemm)
+    a = _attn_shape(n_head, n_kv_head, hd, range_hint=range_hint, nsplit=nsplit, rope_qwen3=qwen if rope_qwen3 is None else rope_qwen3,
+                    qk_norm=qwen if qk_norm is None else qk_norm)
+    return _plan_query("qkv_attn_fused", QKV_ATTN_FUSED_PLAN_FIELDS, len(QKV_ATTN_FUSED_PLAN_FIELDS), (g, a), cus)
+
+
+def wo_w13_fused_plan(n_wo, n_embd, n_hidden, *, attn=None, gs=64, ordered=False, cus=256):
+    """The fused Wo + W1|W3 launch a one-sequence Q80 step issues (nano_hip_wo_w13_fused_plan; needs no GPU): Wo [n_embd, n_wo], W1 and W3
+    [n_hidden, n_embd]; attn = (n_head, hd, nsplit) when Wo combines split-attention partials.
+    Returns a dict of WO_W13_FUSED_PLAN_FIELDS; takes == 0: the step issues the two plain launches and every other entry is 0."""
+    a = _fused_shape(0x80, 1, n_wo, [n_embd], 1, gs=gs, attn=attn, ordered=ordered)
+    b = _fused_shape(0x80, 2, n_embd, [n_hidden, n_hidden], 1, gs=gs, norm=True, ordered=ordered)
+    return _plan_query("wo_w13_fused", WO_W13_FUSED_PLAN_FIELDS, len(WO_W13_FUSED_PLAN_FIELDS), (a, b), cus)
+
+
+def op_qkv_attn_fused(quant, n, weights, x, norm_w, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, S, range_hint, rope_cos, rope_sin,
+                      rope_qwen3, q_norm=None, k_norm=None, nsplit=0, gs=0, n_layer=1, layer=0, layer1=1, tick0=0, hand_init=None, device=0):
+    """One fused q | k | v + attention launch exactly as a one-sequence step issues it (nano_hip_op_qkv_attn_fused).
+    weights: [(wq, ws, rows), (wk, ..), (wv, ..)] as op_fused_gemv takes them; x [n], norm_w [n]; pos: the position; caches float32
+    [n_layer, S, kv_dim] (copied; returned whole); hand_init: None or uint64[q_dim + 2 kv_dim] granules (tag << 32 | value bits).
+    Returns dict(out [q_dim] head outputs (nsplit > 1: the combined partials), k_cache, v_cache, q [q_dim], k [kv_dim] raw rows as stored,
+    part [nsplit, q_dim] and ml [n_head, nsplit, 2] when nsplit > 1, plan (dict of QKV_ATTN_FUSED_PLAN_FIELDS), err (the error word)).
+    Raises NanoHipError for a shape the plan refuses (before any launch) and when a consumer gave up its wait."""
+    keep = []
+
+    def held(v, dtype=None):
+        v = np.ascontiguousarray(v, dtype); keep.append(v)
+        return v
+
+    QD, KD = n_head * hd, n_kv_head * hd
+    norm_w = held(norm_w, np.float32)
+    g = _fused_shape(quant, 0, n, [r for _, _, r in weights], 1, gs=gs, norm=norm_w.ctypes.data)
+    for i, (w, ws, _) in enumerate(weights):
+        g.w[i] = held(w).ctypes.data
+        if ws is not None:
+            g.ws[i] = held(ws, np.float32).ctypes.data
+    g.x = held(x, np.float32).ctypes.data
+    qk = np.zeros(QD + KD, np.float32)
+    g.out = qk.ctypes.data
+    a = _attn_shape(n_head, n_kv_head, hd, range_hint=range_hint, nsplit=nsplit, rope_qwen3=rope_qwen3, qk_norm=False, n_layer=n_layer, layer=layer, S=S)
+    if q_norm is not None:
+        a.q_norm, a.k_norm = held(q_norm, np.float32).ctypes.data, held(k_norm, np.float32).ctypes.data
+    kc = np.array(k_cache, np.float32, copy=True, order="C"); vc = np.array(v_cache, np.float32, copy=True, order="C")
+    assert kc.size == n_layer * S * KD and vc.size == kc.size
+    out = np.zeros(QD, np.float32)
+    a.pos = held(np.array([pos], np.uint32)).ctypes.data
+    a.rope_cos, a.rope_sin = held(rope_cos, np.float32).ctypes.data, held(rope_sin, np.float32).ctypes.data
+    a.k_cache, a.v_cache, a.out = kc.ctypes.data, vc.ctypes.data, out.ctypes.data
+    part = np.zeros((8, QD), np.float32); ml = np.zeros(n_head * 8 * 2, np.float32)      # room for any split count the launch takes
+    plan = np.zeros(len(QKV_ATTN_FUSED_PLAN_FIELDS), np.uint32); err = np.zeros(1, np.uint32)
+    d = NanoQkvAttnFusedDesc()
+    d.qkv, d.attn, d.layer1, d.tick0 = C.pointer(g), C.pointer(a), layer1, tick0
+    if hand_init is not None:
+        hand_init = held(hand_init, np.uint64)
+        assert hand_init.size == QD + 2 * KD
+        d.hand_init = hand_init.ctypes.data
+    d.part_out, d.ml_out, d.plan_out, d.err_out = part.ctypes.data, ml.ctypes.data, plan.ctypes.data, err.ctypes.data
+    check(lib().nano_hip_op_qkv_attn_fused(device, C.byref(d)))
+    p = dict(zip(QKV_ATTN_FUSED_PLAN_FIELDS, (int(v) for v in plan)))
+    res = {"out": out, "k_cache": kc, "v_cache": vc, "q": qk[:QD], "k": qk[QD:], "plan": p, "err": int(err[0])}
+    ran = p["n_attn"] // n_head if p["takes"] else 0
+    if ran > 1:
+        res["part"] = part.reshape(-1)[:ran * QD].reshape(ran, QD)
+        res["ml"] = ml[:n_head * ran * 2].reshape(n_head, ran, 2)
+    return res
+
+
+def op_wo_w13_fused(n_wo, wo, w1, w3, resid, norm_w, *, x=None, attn=None, gs=64, layer1=1, tick0=0, hand_init=None, device=0):
+    """One fused Wo + W1|W3 launch exactly as a one-sequence Q80 step issues it (nano_hip_op_wo_w13_fused).
+    wo = (w, ws, n_embd), w1 / w3 = (w, ws, n_hidden) as op_fused_gemv takes them; x [n_wo] the attention output, or attn = (part[nsplit, n_wo],
+    ml[n_head, nsplit, 2], n_head, hd); resid [n_embd] the residual stream on entry; norm_w [n_embd] W1|W3's rmsnorm weight;
+    hand_init: None or uint64[n_embd] granules.  Returns dict(x [n_embd] the residual stream Wo leaves, hb [n_hidden], plan, err)."""
+    keep = []
+
+    def held(v, dtype=None):
+        v = np.ascontiguousarray(v, dtype); keep.append(v)
+        return v
+
+    E, Hd = wo[2], w1[2]
+    assert w3[2] == Hd
+    norm_w = held(norm_w, np.float32)
+    if attn is not None:
+        part, ml, n_head, hd = attn
+        part, ml = held(part, np.float32), held(ml, np.float32)
+    a = _fused_shape(0x80, 1, n_wo, [E], 1, gs=gs, attn=None if attn is None else (n_head, hd, part.shape[-2], part.ctypes.data))
+    b = _fused_shape(0x80, 2, E, [Hd, Hd], 1, gs=gs, norm=norm_w.ctypes.data)
+    a.w[0], a.ws[0] = held(wo[0]).ctypes.data, held(wo[1], np.float32).ctypes.data
+    for i, t in enumerate((w1, w3)):
+        b.w[i], b.ws[i] = held(t[0]).ctypes.data, held(t[1], np.float32).ctypes.data
+    if x is not None:
+        a.x = held(x, np.float32).ctypes.data
+    if attn is not None:
+        a.attn_ml = ml.ctypes.data
+    xo = np.array(resid, np.float32, copy=True).reshape(E); hb = np.zeros(Hd, np.float32)
+    a.out, b.out = xo.ctypes.data, hb.ctypes.data
+    plan = np.zeros(len(WO_W13_FUSED_PLAN_FIELDS), np.uint32); err = np.zeros(1, np.uint32)
+    d = NanoWoW13FusedDesc()
+    d.wo, d.w13, d.layer1, d.tick0 = C.pointer(a), C.pointer(b), layer1, tick0
+    if hand_init is not None:
+        hand_init = held(hand_init, np.uint64)
+        assert hand_init.size == E
+        d.hand_init = hand_init.ctypes.data
+    d.plan_out, d.err_out = plan.ctypes.data, err.ctypes.data
+    check(lib().nano_hip_op_wo_w13_fused(device, C.byref(d)))
+    return {"x": xo, "hb": hb, "plan": dict(zip(WO_W13_FUSED_PLAN_FIELDS, (int(v) for v in plan))), "err": int(err[0])}
 
 
 def op_rope(head, fcr, fci, qwen3, device=0):

@@ -326,15 +326,11 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch (higher bits are ignored).
     // Default 3; 0 = the five launches per layer; same bits in every setting
     if (const char *fz = getenv("NANO_FUSE_LAUNCHES")) { const uint32_t v = (uint32_t)strtoul(fz, nullptr, 0); m->ho.fuse_qkv_attn = (v & 1u) != 0; m->ho.fuse_wo_w13 = (v & 2u) != 0; }
-    if (hipMalloc(reinterpret_cast<void **>(&m->ho.tick), 64) != hipSuccess || hipMemset(m->ho.tick, 0, 64) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off words failed"); }
-    if ((m->d.quant_type == NANO_QUANT_Q80 && m->d.group_size == 64) || m->d.quant_type == NANO_QUANT_Q4K || m->d.quant_type == NANO_QUANT_F32) {
-        // granule buffers of the fused one-sequence launches: tag 0 (the memset) is no epoch -- the first step's tick is 1
-        // (hand2: the Wo + W1|W3 launch, Q80 only)
-        const size_t hb = (size_t)(m->QD + 2 * m->KD) * 8, hb2 = m->d.quant_type == NANO_QUANT_Q80 ? (size_t)m->d.n_embd * 8 : 0;
-        if (hipMalloc(reinterpret_cast<void **>(&m->ho.hand), hb) != hipSuccess || hipMemset(m->ho.hand, 0, hb) != hipSuccess ||
-            (hb2 && (hipMalloc(reinterpret_cast<void **>(&m->ho.hand2), hb2) != hipSuccess || hipMemset(m->ho.hand2, 0, hb2) != hipSuccess))) {
-            destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off granules failed");
-        }
+    {
+        // granule buffers of the fused one-sequence launches (hand2: the Wo + W1|W3 launch, Q80 only)
+        const bool gran = (m->d.quant_type == NANO_QUANT_Q80 && m->d.group_size == 64) || m->d.quant_type == NANO_QUANT_Q4K || m->d.quant_type == NANO_QUANT_F32;
+        const size_t g1 = gran ? (size_t)m->QD + 2 * (size_t)m->KD : 0, g2 = (gran && m->d.quant_type == NANO_QUANT_Q80) ? (size_t)m->d.n_embd : 0;
+        if (handoff_alloc(&m->ho.tick, &m->ho.hand, g1, &m->ho.hand2, g2) != hipSuccess) { destroy(m); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the hand-off words and granules failed"); }
     }
     HIP_TRY(hipDeviceSynchronize());
     *out = m;
@@ -345,6 +341,16 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
 
 extern "C" int nano_hip_model_device(const NanoHipModel *m) { return m ? m->device : -1; }
 extern "C" uint64_t nano_hip_weight_bytes_per_step(const NanoHipModel *m) { return m ? m->weight_bytes_per_step : 0; }
+// The hand-off state of the fused one-sequence launches (device_common.h): the three tick words (64 bytes) and the granule buffers of
+// `granules` / `granules2` 8-byte {tag, value} entries (0: none, and then hand / hand2 may be null), all zeroed -- tag 0 (the memset) is no epoch: the first step's tick is 1.
+// A model's (above) and the fused-launch operators' (ops.hip) come from here.  On failure whatever was allocated stays with the caller.
+hipError_t nano::handoff_alloc(uint32_t **tick, unsigned long long **hand, size_t granules, unsigned long long **hand2, size_t granules2) {
+    hipError_t e;
+    if ((e = hipMalloc(reinterpret_cast<void **>(tick), 64)) != hipSuccess || (e = hipMemset(*tick, 0, 64)) != hipSuccess) return e;
+    if (granules && ((e = hipMalloc(reinterpret_cast<void **>(hand), granules * 8)) != hipSuccess || (e = hipMemset(*hand, 0, granules * 8)) != hipSuccess)) return e;
+    if (granules2 && ((e = hipMalloc(reinterpret_cast<void **>(hand2), granules2 * 8)) != hipSuccess || (e = hipMemset(*hand2, 0, granules2 * 8)) != hipSuccess)) return e;
+    return hipSuccess;
+}
 // A kernel gave up a bounded wait since the last check (G6's finisher, a fused launch's hand-off):
 // the results of the call are not valid.  Read after a stream synchronisation; the word lives in host-mapped memory, so the check
 // is one load.  dev_err_take() returns the code bits and clears the word (m->ho.last_dev_err keeps them); dev_err_check() turns

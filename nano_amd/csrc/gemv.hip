@@ -20,15 +20,15 @@ uint32_t gemv_tiles(uint32_t quant, const GemvArgs &a) {
 }
 
 // ---- the fused q | k | v + attention launch: each format's pair lives with its kernel ----
-#define NANO_FUSED_PAIR(F) bool qkv_attn_fused_##F##_supports(const GemvArgs &, const AttnArgs &); \
+#define NANO_FUSED_PAIR(F) bool qkv_attn_fused_##F##_plan(const GemvArgs &, const AttnArgs &, QkvAttnFusedPlan *); \
                            hipError_t launch_qkv_attn_fused_##F(const GemvArgs &, const AttnArgs &, unsigned long long *, uint32_t *, uint32_t, hipStream_t);
 NANO_FUSED_PAIR(q80) NANO_FUSED_PAIR(q4k) NANO_FUSED_PAIR(f32)
 #undef NANO_FUSED_PAIR
 
-bool qkv_attn_fused_supports(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa) {
-    if (quant == 0x80u) return qkv_attn_fused_q80_supports(ga, aa);
-    if (quant == 0x42u) return qkv_attn_fused_q4k_supports(ga, aa);
-    return qkv_attn_fused_f32_supports(ga, aa);
+bool qkv_attn_fused_plan(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan *p) {
+    if (quant == 0x80u) return qkv_attn_fused_q80_plan(ga, aa, p);
+    if (quant == 0x42u) return qkv_attn_fused_q4k_plan(ga, aa, p);
+    return qkv_attn_fused_f32_plan(ga, aa, p);
 }
 hipError_t launch_qkv_attn_fused(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
     if (quant == 0x80u) return launch_qkv_attn_fused_q80(ga, aa, hand, tick, layer1, st);

@@ -95,19 +95,23 @@ struct GemvDev {
 // `n_attn` the attention's (head_wgs per split), which nap wait16 x 16 x 64 cycles before their first poll.
 struct QkvAttnArgs { GemvDev g; AttnArgs a; SlabHand hand; uint32_t n_attn, head_wgs, wait16, ngemv; };
 // The attention side's host set-up, the same for every format: the workgroup order of fa.a (both head counts are powers of two:
-// fused_attn_side_ok()), the granule bases of q | k | v in `hand`, the attention workgroups.  Returns the LDS bytes of an attention
+// fused_attn_side_ok()), the granule bases of q | k | v in `hand`, the attention workgroups.  fused_attn_lds(): the LDS bytes of an attention
 // workgroup: q | k | maxima | sums | 4 waves' partials | the fresh v row, and -- the Qwen3 mode, attn_impl.h FAST -- | 4 give-up words |
 // 4 waves x 8 sub-groups' weighted rows.
-static size_t fused_attn_setup(QkvAttnArgs &fa, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, bool plain) {
+// (the two figures of it a plan names: the attention workgroups, one per head and split, and an attention workgroup's LDS bytes)
+static inline uint32_t fused_attn_wgs(const AttnArgs &aa) { return aa.n_head * aa.nsplit; }
+static inline size_t fused_attn_lds(uint32_t hd, bool plain) {
+    const size_t hd4 = (hd + 3) & ~3u;
+    return (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + (plain ? 0 : 4 + 4 * 8 * hd4)) * sizeof(float);
+}
+static void fused_attn_setup(QkvAttnArgs &fa, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1) {
     AttnArgs &a = fa.a;
     a = aa;
     { uint32_t l2 = 0; while ((1u << l2) < a.n_kv_head) l2++; a.kv_log2 = l2; }
     { const uint32_t kv_mul = a.n_head / a.n_kv_head; uint32_t l2 = 0; while ((1u << l2) < kv_mul) l2++; a.kvmul_log2 = l2; }
     fa.hand.buf = hand; fa.hand.tick = tick; fa.hand.layer1 = layer1;
     fa.hand.base[0] = 0; fa.hand.base[1] = a.q_dim; fa.hand.base[2] = a.q_dim + a.kv_dim;
-    fa.n_attn = a.n_head * a.nsplit; fa.head_wgs = a.n_head;
-    const size_t hd4 = (a.hd + 3) & ~3u;
-    return (hd4 + hd4 + 4 + 4 + 4 * hd4 + hd4 + (plain ? 0 : 4 + 4 * 8 * hd4)) * sizeof(float);
+    fa.n_attn = fused_attn_wgs(a); fa.head_wgs = a.n_head;
 }
 
 template <int ROLE> __device__ __forceinline__ bool has_flag(const GemvDev &a, uint32_t f) {

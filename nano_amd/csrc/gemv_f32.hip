@@ -129,25 +129,40 @@ static hipError_t launch_f32_b(const GemvArgs &a, const F32GemvPlan &p, hipStrea
 
 // the fused launch's plan: the projection's own, on 256 threads (four waves like the attention's workgroups; same bits -- the float4 items sit
 // on the same threads, the fourth wave adds +0.0 to the norm's sum)
-static bool f32_fused_shape(const GemvArgs &ga, const AttnArgs &aa, F32Plan &p) {
+static bool f32_fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan &f) {
     if (ga.nb != 1 || ga.nseg != 3 || ga.epi != GEMV_EPI_STORE || !ga.norm_w || ga.xq_in || ga.attn_part || ga.tile_max || ga.resid_add || ga.n % 4u) return false;
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
     for (uint32_t s2 = 0; s2 < 3; s2++) if (ga.seg[s2].rows % 4u) return false;
-    p = plan_f32(ga, 1);
+    const F32Plan p = plan_f32(ga, 1);
     if (p.nw > 4u || p.upw > 4u || ga.n > 1024u) return false;                   // one float4 item per thread on <= 256 threads
-    p.nw = 4u; p.nv = 1u;
-    const uint32_t units = (p.rw / 4) * ((ga.n + 255) / 256);
-    p.upw = (units + 3u) / 4u;
-    if (p.upw > 4u) return false;
-    return fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, true);
+    const uint32_t nchunk = (ga.n + 255) / 256, units = (p.rw / 4) * nchunk, upw = (units + 3u) / 4u;
+    if (upw > 4u) return false;
+    if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, true)) return false;
+    f = QkvAttnFusedPlan{};
+    f.kernel = FUSED_KERNEL_F32; f.nv = 1u; f.upw = upw <= 1 ? 1u : upw <= 2 ? 2u : 4u; f.qv = aa.hd <= 32u ? 1u : 2u;
+    f.threads = 256; f.rw = p.rw;
+    uint32_t rows = 0;
+    for (uint32_t s2 = 0; s2 < 3; s2++) rows += ga.seg[s2].rows;
+    f.ngemv = f.wg[0] = (rows + p.rw - 1) / p.rw;                                 // (a workgroup's rows may cross tensors: multiples of 4 each)
+    f.n_attn = fused_attn_wgs(aa);
+    const size_t n4 = (ga.n + 3) & ~3u, pc = (nchunk + 3) & ~3u;
+    const size_t lds_g = (n4 + 16 + (size_t)p.rw * pc) * 4, lds_a = fused_attn_lds(aa.hd, true), lds = lds_g > lds_a ? lds_g : lds_a;
+    if (lds > FUSED_LDS_MAX) return false;
+    f.lds_bytes = (uint32_t)lds;
+    return true;
 }
 
 }  // namespace
 
-bool qkv_attn_fused_f32_supports(const GemvArgs &ga, const AttnArgs &aa) { F32Plan p; return f32_fused_shape(ga, aa, p); }
+bool qkv_attn_fused_f32_plan(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan *out) {
+    QkvAttnFusedPlan f;
+    if (!f32_fused_shape(ga, aa, f)) return false;
+    if (out) *out = f;
+    return true;
+}
 
 hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
-    F32Plan p;
+    QkvAttnFusedPlan p;
     if (!hand || !tick || !layer1 || layer1 > 127u || !f32_fused_shape(ga, aa, p)) return hipErrorInvalidValue;
     GemvDev d = to_dev(ga);
     d.tile_max = nullptr;
@@ -157,23 +172,18 @@ hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, uns
     uint32_t l2 = 0; while ((1u << l2) < p.rw / 4) l2++;
     d.log2_tiles = l2;
     d.units = (p.rw / 4) * d.nchunk;
-    d.nthr = 256;
-    uint32_t rows = 0;
-    for (uint32_t s2 = 0; s2 < 3; s2++) rows += ga.seg[s2].rows;
-    const uint32_t ngemv = (rows + p.rw - 1) / p.rw;
+    d.nthr = p.threads;
     QkvAttnArgs fa{};
-    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, true);
-    const size_t n4 = (d.n + 3) & ~3u, pc = (d.nchunk + 3) & ~3u;
-    const size_t lds_g = (n4 + 16 + (size_t)p.rw * pc) * 4;
-    const size_t lds = lds_g > lds_a ? lds_g : lds_a;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    fa.g = d; fa.ngemv = ngemv;
+    fused_attn_setup(fa, aa, hand, tick, layer1);
+    const uint32_t grid = p.n_attn + p.ngemv;
+    const size_t lds = p.lds_bytes;
+    fa.g = d; fa.ngemv = p.ngemv;
     fa.wait16 = 1u;             // naps of 16 x 64 cycles before the attention's first poll: Nano-168M, one box, 0 / 1 / 2 / 3 naps: 2387 / 2384 / 2380 / 2364 and 2383 / 2381 / 2380 / 2366 tok/s
-    const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-#define F32F_GO(UPW_) do { if (aa.hd <= 32u) hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 1>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa); \
-                           else hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 2>), dim3(fa.n_attn + ngemv), dim3(256), lds, st, fa); return hipGetLastError(); } while (0)
-    if (upw == 1) F32F_GO(1);
-    if (upw == 2) F32F_GO(2);
+    // the instantiations: <1, UPW, QV> of {1, 2, 4} x {1, 2} (tests/test_fused_launch_plan.py restates the set)
+#define F32F_GO(UPW_) do { if (p.qv == 1u) hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 1>), dim3(grid), dim3(p.threads), lds, st, fa); \
+                           else hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 2>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
+    if (p.upw == 1) F32F_GO(1);
+    if (p.upw == 2) F32F_GO(2);
     F32F_GO(4);
 #undef F32F_GO
 }

@@ -285,7 +285,8 @@ hipError_t launch_q4k_chunk(const GemvArgs &a, const Q4kGemvPlan &p, hipStream_t
 }
 
 // ---- the fused q | k | v + attention launch: host side -----------------------------------------------------------------------------------
-static bool q4k_fused_shape(const GemvArgs &ga, const AttnArgs &aa, ChunkPlan &p) {
+static bool q4k_fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan &f) {
+    ChunkPlan p;
     if (ga.nb != 1 || ga.nseg != 3 || ga.epi != GEMV_EPI_STORE || !ga.norm_w || ga.xq_in || ga.x4_in || ga.attn_part || ga.tile_max || ga.resid_add) return false;
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
     // 256 threads, like the attention workgroups: the kernel needs ~200 registers (the attention body), i.e. two waves per SIMD, and a CU must
@@ -293,26 +294,41 @@ static bool q4k_fused_shape(const GemvArgs &ga, const AttnArgs &aa, ChunkPlan &p
     // the attention started when the projection had left -- 0.575 -> 0.626 ms per step).  Same bits as the 384-thread launch: one float4 item
     // per thread on threads 0 .. n / 4 - 1 either way, a Q4K block is one wave's, the waves beyond add +0.0 to the norm's sum.
     if (ga.n > 1024u || !plan_chunk(ga, p, 4u) || p.loop || p.nthr != 256u || p.nv != 1u) return false;
-    if (p.lds > 64u * 1024u) return false;
-    return fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false);
+    if (p.lds > FUSED_LDS_MAX) return false;
+    if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;
+    f = QkvAttnFusedPlan{};
+    f.kernel = FUSED_KERNEL_Q4K; f.nv = p.nv <= 1 ? 1u : p.nv <= 2 ? 2u : 4u; f.d = p.d;
+    f.threads = p.nthr; f.rw = p.rw; f.rounds = p.rounds;
+    for (uint32_t s2 = 0; s2 < 3; s2++) f.wg[s2] = p.wg[s2];
+    f.ngemv = p.grid; f.n_attn = fused_attn_wgs(aa);
+    const size_t lds_a = fused_attn_lds(aa.hd, false);
+    f.lds_bytes = (uint32_t)(p.lds > lds_a ? p.lds : lds_a);
+    return f.lds_bytes <= FUSED_LDS_MAX;
 }
-bool qkv_attn_fused_q4k_supports(const GemvArgs &ga, const AttnArgs &aa) { ChunkPlan p; return q4k_fused_shape(ga, aa, p); }
+bool qkv_attn_fused_q4k_plan(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan *out) {
+    QkvAttnFusedPlan f;
+    if (!q4k_fused_shape(ga, aa, f)) return false;
+    if (out) *out = f;
+    return true;
+}
 
 hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
-    ChunkPlan p;
+    QkvAttnFusedPlan p;
     if (!hand || !tick || !layer1 || layer1 > 127u || !q4k_fused_shape(ga, aa, p)) return hipErrorInvalidValue;
-    const GemvDev d = chunk_dev(ga, p.rw, p.nthr, p.rounds, p.wg);
+    const GemvDev d = chunk_dev(ga, p.rw, p.threads, p.rounds, p.wg);
     QkvAttnArgs fa{};
-    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, false), lds = p.lds > lds_a ? p.lds : lds_a;
-    fa.g = d; fa.ngemv = p.grid;
+    fused_attn_setup(fa, aa, hand, tick, layer1);
+    const size_t lds = p.lds_bytes;
+    fa.g = d; fa.ngemv = p.ngemv;
     // naps of 16 x 64 cycles between the K / V requests and the first poll.  Same box, driver's flags (profiles/r06_q4k_fused.txt): the five
     // launches per layer 1733 / 1755 tok/s; fused with 2 naps 1773 / 1818, 4: 1782 / 1779, 6: 1742 / 1739, 8: 1684 / 1688
     // (re-swept at the end of round 6, producers first in the grid: 0 / 1 / 2 / 3 naps 1789 / 1761 / 1782 / 1780 and 1784 / 1778 / 1779 / 1775 tok/s: flat; none)
     fa.wait16 = 0u;
-#define Q4F_GO(NV_, D_) do { hipLaunchKernelGGL((q4k_qkv_attn_fused_kernel<NV_, D_>), dim3(fa.n_attn + fa.ngemv), dim3(p.nthr), lds, st, fa); return hipGetLastError(); } while (0)
+    // the instantiations: <NV, D> of {1, 2, 4} x {1, 2, 4, 8} (tests/test_fused_launch_plan.py restates the set)
+#define Q4F_GO(NV_, D_) do { hipLaunchKernelGGL((q4k_qkv_attn_fused_kernel<NV_, D_>), dim3(p.n_attn + p.ngemv), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
 #define Q4F_NV(NV_) do { if (p.d == 1) Q4F_GO(NV_, 1); if (p.d == 2) Q4F_GO(NV_, 2); if (p.d == 4) Q4F_GO(NV_, 4); Q4F_GO(NV_, 8); } while (0)
-    if (p.nv <= 1) Q4F_NV(1);
-    if (p.nv <= 2) Q4F_NV(2);
+    if (p.nv == 1u) Q4F_NV(1);
+    if (p.nv == 2u) Q4F_NV(2);
     Q4F_NV(4);
 #undef Q4F_NV
 #undef Q4F_GO

@@ -692,13 +692,29 @@ static hipError_t launch_stream_b(GemvDev &d, const Q80GemvPlan &p, hipStream_t 
 
 #if NANO_Q80_GS == 64
 // ---- the fused q | k | v + attention launch: host side -----------------------------------------------------------------------------------
-static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, SlabPlan &p) {
+// Every choice of the launch (kernels.h QkvAttnFusedPlan): the projection's own slab plan where it runs on four waves, the table or the
+// in-wave fold, the attention workgroups, the larger of the two kinds' LDS.
+static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan &f) {
     if (ga.gs != 64 || ga.nb != 1 || ga.nseg != 3 || ga.epi != GEMV_EPI_STORE || !ga.norm_w || ga.xq_in || ga.attn_part || ga.tile_max || ga.resid_add) return false;
     if (ga.n % 64u || ga.n > 4096u || use_stream(ga) || !q80_canonical(ga)) return false;        // (the role kernels of group size 64 carry the canonical fold only)
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
-    p = q80_plan_slab(ga, 1);
+    const SlabPlan p = q80_plan_slab(ga, 1);
     if (p.nw != 4u || p.upw > 4u || !(p.nv == 1u || p.nv == 2u || p.nv == 4u)) return false;        // 256 threads, like the attention workgroups
     if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;   // (kernels.h)
+    f = QkvAttnFusedPlan{};
+    f.nv = p.nv; f.upw = p.upw <= 1 ? 1u : p.upw <= 2 ? 2u : 4u;
+    f.threads = 256; f.rw = p.rw;
+    for (uint32_t s2 = 0; s2 < 3; s2++) { f.wg[s2] = (ga.seg[s2].rows + p.rw - 1) / p.rw; f.ngemv += f.wg[s2]; }
+    f.n_attn = fused_attn_wgs(aa);
+    const GemvDev d = to_dev(ga);
+    const uint32_t tpw = (p.rw + 3) / 4;
+    const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
+    const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
+    const size_t lds_g = n16 + ng4 * 4 + 64 + (wf ? 0 : (size_t)(tpw * 4) * pitch * 4), lds_a = fused_attn_lds(aa.hd, false);
+    const size_t lds = lds_g > lds_a ? lds_g : lds_a;
+    if (lds > FUSED_LDS_MAX) return false;
+    f.lds_bytes = (uint32_t)lds;
+    f.kernel = (wf && p.nv == 1u) ? FUSED_KERNEL_Q80_WF : FUSED_KERNEL_Q80_TABLE;
     return true;
 }
 
@@ -707,7 +723,7 @@ static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, SlabPlan &p) {
 // bits).  Instantiated: Qwen3-0.6B's shapes (256 and 512 threads).  (Qwen3-4B's wide matrices had a 1024-thread form; it lost to the two
 // plain launches -- 1.531 vs 1.473 ms per step -- and was removed: those shapes are refused here and take the plain launches.)
 struct Wo13Plan { SlabPlan a, b; uint32_t nw, nv_a, upw_a, wa, wb; int sig; };
-static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
+static bool wo13_slabs(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (wo.gs != 64 || w13.gs != 64 || wo.nb != 1 || w13.nb != 1 || !q80_canonical(wo) || !q80_canonical(w13)) return false;
     if (wo.nseg != 1 || wo.epi != GEMV_EPI_RESID || wo.norm_w || wo.xq_in || wo.tile_max || wo.resid_add || wo.seg[0].out_pstride) return false;
     if (wo.attn_part && (wo.attn_nsplit > 8u || wo.attn_hd % 4u)) return false;
@@ -746,6 +762,29 @@ static size_t slab_lds(const GemvDev &d, bool table = true) {
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
     return n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + (table ? (size_t)nmat * (d.tpw * 4) * pitch * 4 : 0);
 }
+// Every choice of the launch (kernels.h WoW13FusedPlan), and the two device blocks it was made from
+static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan &f, GemvDev &da, GemvDev &db) {
+    Wo13Plan q;
+    if (!wo13_slabs(wo, w13, q)) return false;
+    da = to_dev(wo); db = to_dev(w13);
+    slab_dev_fill(da, wo, q.a, 64 * q.nw); slab_dev_fill(db, w13, q.b, 64 * q.nw);
+    // W1|W3's rows of one chunk (n == 1024): pair units (two rows of W1 and the same two of W3), folded by the wave that holds them
+    const bool wf = slab_wave_fold(db);
+    if (wf) db.units = (db.rw + 1) / 2;
+    // Wo's rows of two whole chunks (n == 2048, the widest these signatures take): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
+    const bool wfa = slab_wave_fold_chunks(da) == 2u;
+    const size_t la = slab_lds(da, !wfa) + (wfa ? slab_unit_table(da, 2u) : 0), lb = slab_lds(db, !wf), lds = la > lb ? la : lb;
+    if (lds > FUSED_LDS_MAX) return false;
+    f = WoW13FusedPlan{};
+    f.sig = (uint32_t)q.sig; f.threads = 64 * q.nw;
+    f.role = (da.flags & F_COMBINE) ? (uint32_t)R_RESID_COMBINE : (uint32_t)R_RESID;
+    f.wf = wf ? 1u : 0u; f.wfc = wfa ? 2u : 0u;
+    if (q.sig == 1) { f.nv_a = 2; f.upw_a = 1; f.nv_b = 1; f.upw_b = 2; }       // (the two signatures wo13_slabs() lets through)
+    else { f.nv_a = 1; f.upw_a = 1; f.nv_b = 1; f.upw_b = 1; }
+    f.wa = q.wa; f.wb = q.wb; f.lds_bytes = (uint32_t)lds;
+    f.rw_a = q.a.rw; f.rw_b = q.b.rw;
+    return true;
+}
 
 #endif
 
@@ -770,39 +809,37 @@ static hipError_t launch_gs(const GemvArgs &a, const Q80GemvPlan &p, hipStream_t
 hipError_t NANO_Q80_ENTRY(const GemvArgs &a, const Q80GemvPlan &p, hipStream_t st) { return launch_gs<NANO_Q80_GS>(a, p, st); }
 
 #if NANO_Q80_GS == 64
-bool qkv_attn_fused_q80_supports(const GemvArgs &ga, const AttnArgs &aa) { SlabPlan p; return fused_shape(ga, aa, p); }
+bool qkv_attn_fused_q80_plan(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan *out) {
+    QkvAttnFusedPlan f;
+    if (!fused_shape(ga, aa, f)) return false;
+    if (out) *out = f;
+    return true;
+}
 
 hipError_t launch_qkv_attn_fused_q80(const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
-    SlabPlan p;
+    QkvAttnFusedPlan p;
     if (!hand || !tick || !layer1 || layer1 > 127u || !fused_shape(ga, aa, p)) return hipErrorInvalidValue;
     GemvDev d = to_dev(ga);
     d.tile_max = nullptr;
     d.rw = p.rw; d.tpw = (p.rw + 3) / 4; d.magic_rw = 65536u / p.rw + 1u; d.log2_tiles = 0;
     d.units = d.tpw * d.nchunk;
-    uint32_t wg[3];
-    for (uint32_t s2 = 0; s2 < 3; s2++) wg[s2] = (ga.seg[s2].rows + p.rw - 1) / p.rw;
-    d.wg_c0 = wg[0]; d.wg_c1 = wg[0] + wg[1];
-    const uint32_t ngemv = wg[0] + wg[1] + wg[2];
-    d.nthr = 256;
+    d.wg_c0 = p.wg[0]; d.wg_c1 = p.wg[0] + p.wg[1];
+    d.nthr = p.threads;
     QkvAttnArgs fa{};
-    const size_t lds_a = fused_attn_setup(fa, aa, hand, tick, layer1, false);
-    const uint32_t n_attn = fa.n_attn;
-    const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
-    const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
-    const size_t lds_g = n16 + ng4 * 4 + 64 + (wf ? 0 : (size_t)(d.tpw * 4) * pitch * 4);
-    const size_t lds = lds_g > lds_a ? lds_g : lds_a;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const int upw = p.upw <= 1 ? 1 : p.upw <= 2 ? 2 : 4;
-    fa.g = d; fa.ngemv = ngemv;
+    fused_attn_setup(fa, aa, hand, tick, layer1);
+    const uint32_t grid = p.n_attn + p.ngemv;
+    const size_t lds = p.lds_bytes;
+    fa.g = d; fa.ngemv = p.ngemv;
     // The attention workgroups nap `wait16` x 16 x 64 cycles between asking for their K / V rows and the first poll.  Round 5 (consumers FIRST in
     // the grid: they started before the projection) tuned 3: 1881-1887 tok/s without, 1899-1901 with 3, 1851 with 5.  Round 6 put the PRODUCERS
     // first -- the attention workgroups start last and the nap is mostly dead time: same box, driver's flags, 0 / 1 / 2 / 3 naps: 1984 / 1983 /
     // 1961 / 1919, 1977 / 1986 / 1958 / 1920, 1982 / 1981 / 1960 / 1912 tok/s; positions 31..510: 1878 / 1880 / 1859 / 1821
     // (profiles/r06_handoff_naps.txt).
     fa.wait16 = 1u;
-#define FUSED_GO(NV_, UPW_) do { if (wf && NV_ == 1) hipLaunchKernelGGL((qkv_attn_fused_wf_kernel<1, UPW_>), dim3(n_attn + ngemv), dim3(256), lds, st, fa); \
-                                 else hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(n_attn + ngemv), dim3(256), lds, st, fa); return hipGetLastError(); } while (0)
-#define FUSED_NV(NV_) do { if (upw == 1) FUSED_GO(NV_, 1); if (upw == 2) FUSED_GO(NV_, 2); FUSED_GO(NV_, 4); } while (0)
+    // the instantiations: NV, UPW of {1, 2, 4} x {1, 2, 4} in the table form, <1, UPW> in the wave-fold form (tests/test_fused_launch_plan.py restates the set)
+#define FUSED_GO(NV_, UPW_) do { if (p.kernel == FUSED_KERNEL_Q80_WF && NV_ == 1) hipLaunchKernelGGL((qkv_attn_fused_wf_kernel<1, UPW_>), dim3(grid), dim3(p.threads), lds, st, fa); \
+                                 else hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
+#define FUSED_NV(NV_) do { if (p.upw == 1) FUSED_GO(NV_, 1); if (p.upw == 2) FUSED_GO(NV_, 2); FUSED_GO(NV_, 4); } while (0)
     if (p.nv == 1u) FUSED_NV(1);
     if (p.nv == 2u) FUSED_NV(2);
     FUSED_NV(4);
@@ -810,14 +847,17 @@ hipError_t launch_qkv_attn_fused_q80(const GemvArgs &ga, const AttnArgs &aa, uns
 #undef FUSED_GO
 }
 
-bool wo_w13_fused_supports(const GemvArgs &wo, const GemvArgs &w13) { Wo13Plan q; return wo13_shape(wo, w13, q); }
+bool wo_w13_fused_plan(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan *out) {
+    WoW13FusedPlan f; GemvDev da, db;
+    if (!wo13_shape(wo, w13, f, da, db)) return false;
+    if (out) *out = f;
+    return true;
+}
 
 hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st) {
-    Wo13Plan q;
-    if (!hand || !tick || !layer1 || layer1 > 127u || !wo13_shape(wo, w13, q)) return hipErrorInvalidValue;
+    WoW13FusedPlan q;
     Wo13Args fa{};
-    fa.wo = to_dev(wo); fa.w13 = to_dev(w13);
-    slab_dev_fill(fa.wo, wo, q.a, 64 * q.nw); slab_dev_fill(fa.w13, w13, q.b, 64 * q.nw);
+    if (!hand || !tick || !layer1 || layer1 > 127u || !wo13_shape(wo, w13, q, fa.wo, fa.w13)) return hipErrorInvalidValue;
     fa.wo_wgs = q.wa;
     // workgroups that produce nothing nap 4 x 16 x 64 cycles (~2 us) before their first poll, every workgroup 128 cycles between sweeps: same
     // box, driver's flags, Qwen3-0.6B: 1846-1852 tok/s without, 1855-1865 with 2, 1879-1889 with 3, 1882-1887 with 4, 1847-1852 with 5, 1806-1817 with 6
@@ -826,14 +866,9 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     h.buf = hand; h.tick = tick; h.layer1 = layer1;
     h.base[0] = 0; h.base[1] = 0; h.base[2] = 0;
     fa.hand = h;
-    // W1|W3's rows of one chunk (n == 1024): pair units (two rows of W1 and the same two of W3), folded by the wave that holds them
-    const bool wf = slab_wave_fold(fa.w13);
-    if (wf) fa.w13.units = (fa.w13.rw + 1) / 2;
-    // Wo's rows of two whole chunks (n == 2048, the widest these signatures take): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
-    const bool wfa = slab_wave_fold_chunks(fa.wo) == 2u;
-    const size_t la = slab_lds(fa.wo, !wfa) + (wfa ? slab_unit_table(fa.wo, 2u) : 0), lb = slab_lds(fa.w13, !wf), lds = la > lb ? la : lb;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const bool comb = (fa.wo.flags & F_COMBINE) != 0;
+    const size_t lds = q.lds_bytes;
+    const bool wf = q.wf != 0, wfa = q.wfc == 2u, comb = q.role == (uint32_t)R_RESID_COMBINE;
+    // the instantiations: sig 1 <role, 2, 1, 1, 2, 256> and sig 3 <role, 1, 1, 1, 1, 512>, each with WF 0 | 1 and WFC 0 | 2 (tests/test_fused_launch_plan.py restates the set)
 #define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { if (wf && wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \
                                                      else if (wf) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1>), dim3(q.wb), dim3(NT_), lds, st, fa); \
                                                      else if (wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 0, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \

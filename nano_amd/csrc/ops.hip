@@ -302,9 +302,10 @@ static FusedLaunch fused_launch(const NanoFusedGemvDesc &d, uint32_t cus, F32Scr
     }
     return L;
 }
-// a query's scratch: one flag stands for every buffer the operator would allocate -- compared with null, never followed
+// a query's pointers: one flag stands for every buffer the operator would allocate or upload -- compared with null, never followed
+alignas(8) static uint8_t g_flag[8];
 static void flag_scratch(FusedLaunch &L) {
-    alignas(8) static uint8_t flag[8];
+    uint8_t *const flag = g_flag;
     if (L.gq_bytes) L.r.gq = reinterpret_cast<int8_t *>(flag);
     if (L.gxs_floats) L.r.gxs = reinterpret_cast<float *>(flag);
     if (L.r.q4x_bytes) L.r.q4x = flag;
@@ -425,6 +426,23 @@ extern "C" int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
                            p.lds_bytes, p.pre, p.quant_rows, p.quant_nthr, p.quant_nv, p.partials }}; });
 }
 
+// the weight tensors of a descriptor -> device copies in the arguments' segments
+static int upload_weights(DevBufs &B, const NanoFusedGemvDesc &d, GemvArgs &a) {
+    const size_t bpl = (d.n + 255) / 256;
+    for (uint32_t s = 0; s < d.nseg; s++) {
+        const size_t rows = d.rows[s];
+        if (!d.w[s]) { nano_hip_set_error_("missing weight tensor"); return NANO_HIP_EINVAL; }
+        if (d.quant == NANO_QUANT_Q80) {
+            a.seg[s].w = B.upload(reinterpret_cast<const int8_t *>(d.w[s]), rows * d.n);
+            a.seg[s].ws = B.upload(d.ws[s], rows * d.n / d.gs);
+            OP_CHECK(a.seg[s].ws, "device alloc failed");
+        } else if (d.quant == NANO_QUANT_Q4K) a.seg[s].w = B.upload(reinterpret_cast<const uint8_t *>(d.w[s]), rows * bpl * 160);
+        else a.seg[s].w = B.upload(reinterpret_cast<const float *>(d.w[s]), rows * d.n);
+        OP_CHECK(a.seg[s].w, "device alloc failed");
+    }
+    return 0;
+}
+
 // One fused GEMV launch as enqueue_step() issues it (backend_step.hip): the role-specialised kernels on caller-chosen inputs, through the
 // step's own router (route.hip).
 // With d.tile_max the launch is the step's classifier launch where route_partials() (route.hip, enqueue_classifier's own question) says
@@ -444,20 +462,9 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     GemvArgs &a = L.a;
     Q80Route &r = L.r;
     DevBufs B;
-    const size_t bpl = (d.n + 255) / 256;
+    if (int rc2 = upload_weights(B, d, a)) return rc2;
     uint32_t rows_total = 0;
-    for (uint32_t s = 0; s < d.nseg; s++) {
-        const size_t rows = d.rows[s];
-        if (!d.w[s]) { nano_hip_set_error_("missing weight tensor"); return NANO_HIP_EINVAL; }
-        if (d.quant == NANO_QUANT_Q80) {
-            a.seg[s].w = B.upload(reinterpret_cast<const int8_t *>(d.w[s]), rows * d.n);
-            a.seg[s].ws = B.upload(d.ws[s], rows * d.n / d.gs);
-            OP_CHECK(a.seg[s].ws, "device alloc failed");
-        } else if (d.quant == NANO_QUANT_Q4K) a.seg[s].w = B.upload(reinterpret_cast<const uint8_t *>(d.w[s]), rows * bpl * 160);
-        else a.seg[s].w = B.upload(reinterpret_cast<const float *>(d.w[s]), rows * d.n);
-        OP_CHECK(a.seg[s].w, "device alloc failed");
-        if (d.kind != 2 || s == 0) rows_total += d.rows[s];
-    }
+    for (uint32_t s = 0; s < d.nseg; s++) if (d.kind != 2 || s == 0) rows_total += d.rows[s];
     // out_slots / out_stride (operator tests): out holds more sequence slots than nb and more floats per slot than rows -- guard
     // elements that go to the device and come back with the result, so the caller sees every element the launch wrote
     const uint32_t slots = d.out_slots ? d.out_slots : d.nb, stride = d.out_stride ? d.out_stride : rows_total;
@@ -514,6 +521,22 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     return 0;
 }
 
+// ---- ONE path from an attention-decode descriptor to the launch's arguments: nano_hip_op_attention_decode, the fused q | k | v + attention
+// operator and its plan query start here.  Every shape field as enqueue_step() fills it (backend_step.hip); of the pointers q_norm / k_norm
+// arrive as the descriptor's HOST pointers, read as flags -- an operator replaces them, and sets every other pointer, with device copies.
+static AttnArgs attn_launch(const NanoAttnDecodeDesc &d, uint32_t nsplit) {
+    AttnArgs a{};
+    a.q_norm = d.q_norm; a.k_norm = d.k_norm;
+    a.nsplit = nsplit; a.range_hint = d.range_hint;
+    a.layer = d.layer; a.n_layer = d.n_layer; a.S = d.S; a.hd = d.hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
+    a.q_dim = d.n_head * d.hd; a.kv_dim = d.n_kv_head * d.hd; a.rope_qwen3 = d.rope_qwen3 ? 1u : 0u; a.is_causal = 1;
+    a.cache_bstride_rows = d.chunk ? 0u : d.n_layer * d.S; a.fixed_range = 0;
+    a.kv_half = d.kv_half ? 1u : 0u;
+    if (d.pool_rows) { a.pt_stride = d.pt_stride; a.pt_bstride = d.chunk ? 0u : d.pt_stride; a.pool_rows = d.pool_rows; }
+    return a;
+}
+static uint32_t attn_desc_nsplit(const NanoAttnDecodeDesc &d) { return d.nsplit ? d.nsplit : attention_nsplit(d.range_hint, d.hd); }
+
 // One decode attention launch as enqueue_step() issues it without the fused q|k|v launch (backend_step.hip: the AttnArgs block before
 // launch_attention), or with `chunk` the two passes of a batched prefill chunk; split partials are combined by the batched / prefill
 // combine.  The plan that ran comes from attention_plan(), the function the launcher itself follows.
@@ -534,7 +557,7 @@ extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc
         OP_ARG(!d.chunk || d.pos[b] == d.pos[0] + b, "chunk: positions must be consecutive");
     }
     OP_ARG(d.range_hint >= maxpos + 1 && d.range_hint <= d.S, "range_hint must cover max(pos) + 1 and stay <= S");
-    const uint32_t nsplit = d.nsplit ? d.nsplit : attention_nsplit(d.range_hint, d.hd);
+    const uint32_t nsplit = attn_desc_nsplit(d);
     OP_ARG(nsplit >= 1 && nsplit <= ATTN_MAX_NSPLIT, "nsplit out of range");
     OP_ARG(!d.want_frag || (nsplit == 1 && d.hd % 64 == 0 && d.xf && d.xsf), "fragment output: nsplit 1 and hd % 64 == 0 only");
     const bool paged = d.pool_rows != 0;
@@ -566,7 +589,7 @@ extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc
     unsigned char *dvc = B.upload(reinterpret_cast<const unsigned char *>(d.v_cache), cache_elems * esz);
     float *dout = B.alloc<float>((size_t)nb * QD), *dpart = B.alloc<float>((size_t)nb * nsplit * QD), *dml = B.alloc<float>((size_t)nb * d.n_head * nsplit * 2);
     OP_CHECK(dq && dk && dpos && dcos && dsin && dcur && dkc && dvc && dout && dpart && dml, "device alloc failed");
-    AttnArgs a{};
+    AttnArgs a = attn_launch(d, nsplit);
     if (d.q_norm) { a.q_norm = B.upload(d.q_norm, d.hd); a.k_norm = B.upload(d.k_norm, d.hd); OP_CHECK(a.q_norm && a.k_norm, "device alloc failed"); }
     if (d.kv_half && d.vraw) { a.vraw = B.upload(d.vraw, (size_t)nb * KD); OP_CHECK(a.vraw, "device alloc failed"); }
     const size_t ntile = (nb + 15) / 16, ng = QD / 64;
@@ -578,14 +601,9 @@ extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc
     if (paged) {
         a.pt_rows = B.upload(d.pt_rows, (size_t)seqs * d.pt_stride); a.kvrow = B.upload(kvrow.data(), nb);
         OP_CHECK(a.pt_rows && a.kvrow, "device alloc failed");
-        a.pt_stride = d.pt_stride; a.pt_bstride = d.chunk ? 0u : d.pt_stride; a.pool_rows = d.pool_rows;
     }
-    a.q = dq; a.q_out = nullptr; a.kraw = dk; a.kcache = reinterpret_cast<float *>(dkc); a.vcache = reinterpret_cast<float *>(dvc); a.pos = dpos;
-    a.rope_cos = dcos; a.rope_sin = dsin; a.rope_cur = dcur; a.out = dpart; a.ml = dml; a.xba_out = dout; a.nsplit = nsplit; a.range_hint = d.range_hint;
-    a.layer = d.layer; a.n_layer = d.n_layer; a.S = d.S; a.hd = d.hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
-    a.q_dim = QD; a.kv_dim = KD; a.rope_qwen3 = d.rope_qwen3 ? 1u : 0u; a.is_causal = 1;
-    a.cache_bstride_rows = d.chunk ? 0u : d.n_layer * d.S; a.fixed_range = 0;
-    a.kv_half = d.kv_half ? 1u : 0u;
+    a.q = dq; a.kraw = dk; a.kcache = reinterpret_cast<float *>(dkc); a.vcache = reinterpret_cast<float *>(dvc); a.pos = dpos;
+    a.rope_cos = dcos; a.rope_sin = dsin; a.rope_cur = dcur; a.out = dpart; a.ml = dml; a.xba_out = dout;
     uint32_t plan[2][10] = {};
     auto record = [&](const AttnArgs &x, uint32_t *row) -> bool {
         AttnPlan p;
@@ -615,3 +633,196 @@ extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc
 #undef OP_ARG
     return 0;
 }
+
+// ---- the two fused one-sequence launches: plan queries and operators --------------------------------------------------------------------
+// ONE resolution each, shared by the query and the operator: the descriptors through fused_launch() / attn_launch() above, the conditions
+// enqueue_step() (backend_step.hip) puts in front of the launch -- the projection's route is the one GEMV (Q4K: the one Q4K) launch -- and
+// the launcher's own plan.  Pointers the launch needs and a query does not have stand as flags (compared with null, never followed); the
+// operator replaces every one with its device copy.  false: the step issues the plain launches.
+static bool qkv_attn_fused_resolve(const NanoFusedGemvDesc &g, const NanoAttnDecodeDesc &ad, uint32_t cus, FusedLaunch &L, AttnArgs &a, QkvAttnFusedPlan &p) {
+    if (fused_desc_shape_error(g) || g.kind != 0 || g.nb != 1 || ad.nb != 1 || ad.chunk || ad.want_frag) return false;
+    if (!ad.n_head || !ad.n_kv_head || ad.n_head % ad.n_kv_head || !ad.hd || !ad.range_hint) return false;
+    L = fused_launch(g, cus, F32X_MODEL);
+    flag_scratch(L);
+    route_fill(L.r, L.a);
+    a = attn_launch(ad, attn_desc_nsplit(ad));
+    const float *flag = reinterpret_cast<const float *>(g_flag);
+    a.kraw = flag; a.rope_cos = flag; a.rope_sin = flag; a.rope_cur = flag;      // (the step always has them)
+    if (ad.pool_rows) a.pt_rows = reinterpret_cast<const uint32_t *>(g_flag);
+    if (route_kind(L.r, L.a) != (g.quant == NANO_QUANT_Q4K ? ROUTE_Q4K : ROUTE_GEMV)) return false;
+    return qkv_attn_fused_plan(g.quant, L.a, a, &p);
+}
+static bool wo_w13_fused_resolve(const NanoFusedGemvDesc &wo, const NanoFusedGemvDesc &w13, uint32_t cus, FusedLaunch &La, FusedLaunch &Lb, WoW13FusedPlan &p) {
+    if (fused_desc_shape_error(wo) || fused_desc_shape_error(w13) || wo.quant != NANO_QUANT_Q80 || w13.quant != NANO_QUANT_Q80) return false;
+    if (wo.kind != 1 || w13.kind != 2 || wo.nb != 1 || w13.nb != 1 || wo.nseg != 1) return false;
+    La = fused_launch(wo, cus, F32X_NONE); Lb = fused_launch(w13, cus, F32X_NONE);
+    flag_scratch(La); flag_scratch(Lb);
+    route_fill(La.r, La.a); route_fill(Lb.r, Lb.a);
+    La.a.seg[0].out = reinterpret_cast<float *>(g_flag); Lb.a.xin = La.a.seg[0].out;       // (W1|W3 reads the stream Wo writes)
+    if (route_kind(La.r, La.a) != ROUTE_GEMV || route_kind(Lb.r, Lb.a) != ROUTE_GEMV) return false;
+    return wo_w13_fused_plan(La.a, Lb.a, &p);
+}
+static void plan_words(const QkvAttnFusedPlan &p, uint32_t *out) {
+    const uint32_t v[NANO_QKV_ATTN_FUSED_PLAN_WORDS] = { p.kernel, p.nv, p.upw, p.d, p.qv, p.threads, p.n_attn, p.ngemv, p.lds_bytes, p.rw, p.wg[0], p.wg[1], p.wg[2], p.rounds, 0u, 1u };
+    memcpy(out, v, sizeof(v));
+}
+static void plan_words(const WoW13FusedPlan &p, uint32_t *out) {
+    const uint32_t v[NANO_WO_W13_FUSED_PLAN_WORDS] = { p.sig, p.threads, p.role, p.wf, p.wfc, p.nv_a, p.upw_a, p.nv_b, p.upw_b, p.wa, p.wb, p.lds_bytes, p.rw_a, p.rw_b, 0u, 1u };
+    memcpy(out, v, sizeof(v));
+}
+
+extern "C" int nano_hip_qkv_attn_fused_plan(const NanoFusedGemvDesc *qkv, const NanoAttnDecodeDesc *attn, uint32_t cus, uint32_t out[NANO_QKV_ATTN_FUSED_PLAN_WORDS]) {
+    if (!qkv || !attn || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    memset(out, 0, NANO_QKV_ATTN_FUSED_PLAN_WORDS * sizeof(uint32_t));
+    FusedLaunch L; AttnArgs a; QkvAttnFusedPlan p;
+    if (qkv_attn_fused_resolve(*qkv, *attn, cus, L, a, p)) plan_words(p, out);
+    return 0;
+}
+extern "C" int nano_hip_wo_w13_fused_plan(const NanoFusedGemvDesc *wo, const NanoFusedGemvDesc *w13, uint32_t cus, uint32_t out[NANO_WO_W13_FUSED_PLAN_WORDS]) {
+    if (!wo || !w13 || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
+    memset(out, 0, NANO_WO_W13_FUSED_PLAN_WORDS * sizeof(uint32_t));
+    FusedLaunch La, Lb; WoW13FusedPlan p;
+    if (wo_w13_fused_resolve(*wo, *w13, cus, La, Lb, p)) plan_words(p, out);
+    return 0;
+}
+
+// what a fused-launch operator borrows from a model: the hand-off words and granules (backend.hip handoff_alloc) and the sticky error word
+struct HandoffState {
+    uint32_t *tick = nullptr; unsigned long long *hand = nullptr;
+    uint32_t *h_err = nullptr, *dev_err = nullptr;
+    ~HandoffState() { (void)hipFree(tick); (void)hipFree(hand); if (h_err) (void)hipHostFree(h_err); }
+    // granules zeroed or the caller's, tick[0] = tick0 + 1 (the embed kernel opens a new epoch), the error word 0
+    int init(size_t granules, const unsigned long long *hand_init, uint32_t tick0) {
+        OP_HIP(handoff_alloc(&tick, &hand, granules, nullptr, 0));
+        if (hand_init) OP_HIP(hipMemcpy(hand, hand_init, granules * 8, hipMemcpyHostToDevice));
+        const uint32_t t = tick0 + 1u;
+        OP_HIP(hipMemcpy(tick, &t, 4, hipMemcpyHostToDevice));
+        OP_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_err), 64, hipHostMallocMapped));
+        *h_err = 0;
+        OP_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&dev_err), h_err, 0));
+        return 0;
+    }
+    // behind the synchronisation: the error word; a give-up is the call's failure
+    int finish(uint32_t *err_out) {
+        const uint32_t c = *reinterpret_cast<volatile uint32_t *>(h_err);
+        if (err_out) *err_out = c;
+        if (c & NANO_DEVERR_HANDOFF) { nano_hip_set_error_("a consumer of the fused launch gave up waiting for its producers: no result is valid"); return NANO_HIP_ERUNTIME; }
+        return 0;
+    }
+};
+#define OP_ARG(cond, msg) do { if (!(cond)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; } } while (0)
+
+extern "C" int nano_hip_op_qkv_attn_fused(int device, const NanoQkvAttnFusedDesc *dp) {
+    int rc; if ((rc = begin(device))) return rc;
+    OP_ARG(dp && dp->qkv && dp->attn, "null descriptor");
+    const NanoFusedGemvDesc &g = *dp->qkv;
+    const NanoAttnDecodeDesc &d = *dp->attn;
+    OP_ARG(dp->layer1 >= 1 && dp->layer1 <= 127, "layer1 outside 1 .. 127");
+    if (const char *msg = fused_desc_shape_error(g)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    OP_ARG(g.x && g.norm_w, "the projection needs x and norm_w");
+    OP_ARG(d.nb == 1 && d.n_layer && d.layer < d.n_layer && d.S, "bad nb / layer / S");
+    OP_ARG(d.pos && d.rope_cos && d.rope_sin && d.k_cache && d.v_cache && d.out, "missing tensor");
+    OP_ARG(!d.q_norm == !d.k_norm, "q_norm and k_norm go together");
+    OP_ARG(d.range_hint >= d.pos[0] + 1 && d.range_hint <= d.S, "range_hint must cover pos + 1 and stay <= S");
+    hipDeviceProp_t prop; OP_HIP(hipGetDeviceProperties(&prop, device));
+    FusedLaunch L; AttnArgs a; QkvAttnFusedPlan p;
+    OP_ARG(qkv_attn_fused_resolve(g, d, (uint32_t)prop.multiProcessorCount, L, a, p), "the fused q|k|v + attention launch does not take this shape");
+    GemvArgs &ga = L.a;
+    const uint32_t QD = a.q_dim, KD = a.kv_dim, half = d.hd / 2, nsplit = a.nsplit;
+    const size_t cache_elems = (size_t)d.n_layer * d.S * KD;
+    std::vector<float> rope_cur((size_t)2 * half);                  // { cos[pos], sin[pos] } (launch_embed)
+    for (uint32_t i = 0; i < half; i++) {
+        rope_cur[i] = d.rope_cos[(size_t)d.pos[0] * half + i];
+        rope_cur[half + i] = d.rope_sin[(size_t)d.pos[0] * half + i];
+    }
+    DevBufs B;
+    if ((rc = upload_weights(B, g, ga))) return rc;
+    float *dq = B.alloc<float>(QD), *dk = B.alloc<float>(KD);
+    uint32_t *dpos = B.upload(d.pos, 1);
+    float *dcos = B.upload(d.rope_cos, (size_t)d.S * half), *dsin = B.upload(d.rope_sin, (size_t)d.S * half), *dcur = B.upload(rope_cur.data(), rope_cur.size());
+    float *dkc = B.upload(reinterpret_cast<const float *>(d.k_cache), cache_elems), *dvc = B.upload(reinterpret_cast<const float *>(d.v_cache), cache_elems);
+    float *dout = B.alloc<float>(QD), *dpart = B.alloc<float>((size_t)nsplit * QD), *dml = B.alloc<float>((size_t)d.n_head * nsplit * 2);
+    OP_CHECK(dq && dk && dpos && dcos && dsin && dcur && dkc && dvc && dout && dpart && dml, "device alloc failed");
+    OP_HIP(hipMemset(dq, 0, QD * 4)); OP_HIP(hipMemset(dk, 0, KD * 4)); OP_HIP(hipMemset(dout, 0, QD * 4));
+    OP_HIP(hipMemset(dpart, 0, (size_t)nsplit * QD * 4)); OP_HIP(hipMemset(dml, 0, (size_t)d.n_head * nsplit * 8));
+    // the projection as qkv_args() builds it: q and the raw k row to scratch, v straight to its cache row
+    ga.xin = B.upload(g.x, g.n); ga.xin_bstride = g.n;
+    ga.norm_w = B.upload(g.norm_w, g.n);
+    OP_CHECK(ga.xin && ga.norm_w, "device alloc failed");
+    ga.seg[0].out = dq; ga.seg[0].out_bstride = QD;
+    ga.seg[1].out = dk; ga.seg[1].out_bstride = KD;
+    ga.seg[2].out = dvc + (size_t)d.layer * d.S * KD; ga.seg[2].out_bstride = d.n_layer * d.S * KD; ga.seg[2].out_pstride = KD;
+    ga.pos = dpos; ga.ordered = 0;
+    if (d.q_norm) { a.q_norm = B.upload(d.q_norm, d.hd); a.k_norm = B.upload(d.k_norm, d.hd); OP_CHECK(a.q_norm && a.k_norm, "device alloc failed"); }
+    a.q = dq; a.kraw = dk; a.kcache = dkc; a.vcache = dvc; a.pos = dpos;
+    a.rope_cos = dcos; a.rope_sin = dsin; a.rope_cur = dcur; a.out = dpart; a.ml = dml; a.xba_out = dout;
+    HandoffState H;
+    if ((rc = H.init((size_t)QD + 2 * (size_t)KD, dp->hand_init, dp->tick0))) return rc;
+    ga.err = H.dev_err; a.err = H.dev_err;
+    QkvAttnFusedPlan ran;
+    OP_ARG(qkv_attn_fused_plan(g.quant, ga, a, &ran) && !memcmp(&ran, &p, sizeof(p)), "the plan moved between the query's arguments and the launch's");
+    OP_HIP(launch_qkv_attn_fused(g.quant, ga, a, H.hand, H.tick, dp->layer1, 0));
+    OP_HIP(hipDeviceSynchronize());
+    if ((rc = H.finish(dp->err_out))) return rc;
+    if (nsplit > 1) {
+        if (dp->part_out) OP_HIP(hipMemcpy(dp->part_out, dpart, (size_t)nsplit * QD * 4, hipMemcpyDeviceToHost));
+        if (dp->ml_out) OP_HIP(hipMemcpy(dp->ml_out, dml, (size_t)d.n_head * nsplit * 8, hipMemcpyDeviceToHost));
+        OP_HIP(launch_attn_combine_tokens(dpart, dml, dout, d.n_head, d.hd, nsplit, 1, nullptr, nullptr, 0));
+        OP_HIP(hipDeviceSynchronize());
+    }
+    OP_HIP(hipMemcpy(d.out, dout, (size_t)QD * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(d.k_cache, dkc, cache_elems * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(d.v_cache, dvc, cache_elems * 4, hipMemcpyDeviceToHost));
+    if (g.out) {
+        OP_HIP(hipMemcpy(g.out, dq, (size_t)QD * 4, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(g.out + QD, dk, (size_t)KD * 4, hipMemcpyDeviceToHost));
+    }
+    if (dp->plan_out) plan_words(ran, dp->plan_out);
+    return 0;
+}
+
+extern "C" int nano_hip_op_wo_w13_fused(int device, const NanoWoW13FusedDesc *dp) {
+    int rc; if ((rc = begin(device))) return rc;
+    OP_ARG(dp && dp->wo && dp->w13, "null descriptor");
+    const NanoFusedGemvDesc &wo = *dp->wo, &w13 = *dp->w13;
+    OP_ARG(dp->layer1 >= 1 && dp->layer1 <= 127, "layer1 outside 1 .. 127");
+    if (const char *msg = fused_desc_shape_error(wo)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    if (const char *msg = fused_desc_shape_error(w13)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    OP_ARG(wo.out && w13.out && w13.norm_w && (wo.x || wo.attn_part) && (!wo.attn_part || wo.attn_ml), "missing tensor");
+    hipDeviceProp_t prop; OP_HIP(hipGetDeviceProperties(&prop, device));
+    FusedLaunch La, Lb; WoW13FusedPlan p;
+    OP_ARG(wo_w13_fused_resolve(wo, w13, (uint32_t)prop.multiProcessorCount, La, Lb, p), "the fused Wo + W1|W3 launch does not take this shape");
+    GemvArgs &a = La.a, &b = Lb.a;
+    const uint32_t E = wo.rows[0], H13 = w13.rows[0];
+    DevBufs B;
+    if ((rc = upload_weights(B, wo, a))) return rc;
+    if ((rc = upload_weights(B, w13, b))) return rc;
+    float *dx = B.upload(wo.out, E), *dhb = B.alloc<float>(H13);      // the residual stream; hb
+    OP_CHECK(dx && dhb, "device alloc failed");
+    OP_HIP(hipMemset(dhb, 0, (size_t)H13 * 4));
+    a.seg[0].out = dx; a.seg[0].out_bstride = E;
+    if (wo.x) { a.xin = B.upload(wo.x, wo.n); OP_CHECK(a.xin, "device alloc failed"); a.xin_bstride = wo.n; }
+    if (wo.attn_part) {
+        a.attn_part = B.upload(wo.attn_part, (size_t)wo.attn_nsplit * wo.n);
+        a.attn_ml = B.upload(wo.attn_ml, (size_t)wo.attn_n_head * wo.attn_nsplit * 2);
+        OP_CHECK(a.attn_part && a.attn_ml, "device alloc failed");
+        if (!a.xin) { a.xin = a.attn_part; a.xin_bstride = wo.n; }   // never read: the prologue combines the partials
+    }
+    b.xin = dx; b.xin_bstride = E;                                   // as the step wires it: W1|W3 reads what Wo leaves
+    b.norm_w = B.upload(w13.norm_w, w13.n); OP_CHECK(b.norm_w, "device alloc failed");
+    b.seg[0].out = dhb; b.seg[0].out_bstride = H13; b.seg[1].out = dhb; b.seg[1].out_bstride = H13;
+    a.ordered = 0; b.ordered = 0;
+    HandoffState H;
+    if ((rc = H.init(E, dp->hand_init, dp->tick0))) return rc;
+    a.err = H.dev_err; b.err = H.dev_err;
+    WoW13FusedPlan ran;
+    OP_ARG(wo_w13_fused_plan(a, b, &ran) && !memcmp(&ran, &p, sizeof(p)), "the plan moved between the query's arguments and the launch's");
+    OP_HIP(launch_wo_w13_fused(a, b, H.hand, H.tick, dp->layer1, 0));
+    OP_HIP(hipDeviceSynchronize());
+    if ((rc = H.finish(dp->err_out))) return rc;
+    OP_HIP(hipMemcpy(wo.out, dx, (size_t)E * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(w13.out, dhb, (size_t)H13 * 4, hipMemcpyDeviceToHost));
+    if (dp->plan_out) plan_words(ran, dp->plan_out);
+    return 0;
+}
+#undef OP_ARG

@@ -1,5 +1,6 @@
 """CPU tests: the C-ABI library loads without a GPU and exports every symbol the headers declare; the
 model writer / layout helpers agree with each other; the product refuses to run without a device."""
+import ctypes as C
 import os
 import re
 
@@ -27,6 +28,22 @@ def test_library_exports_every_declared_symbol(header):
     assert not missing, missing
 
 
+def test_fused_launch_entry_points_are_declared_and_exported():
+    """the two plan queries and the two operators of the fused one-sequence launches: in the header, in the library, and the queries'
+    word counts and the descriptor layouts of the binding are the header's"""
+    syms = declared_symbols("nano_mi355x.h")
+    for name in ("nano_hip_qkv_attn_fused_plan", "nano_hip_wo_w13_fused_plan", "nano_hip_op_qkv_attn_fused", "nano_hip_op_wo_w13_fused"):
+        assert name in syms and hasattr(nb.lib(), name), name
+    src = open(os.path.join(ROOT, "include", "nano_mi355x.h")).read()
+    assert int(re.search(r"#define NANO_QKV_ATTN_FUSED_PLAN_WORDS (\d+)", src).group(1)) == len(nb.QKV_ATTN_FUSED_PLAN_FIELDS)
+    assert int(re.search(r"#define NANO_WO_W13_FUSED_PLAN_WORDS (\d+)", src).group(1)) == len(nb.WO_W13_FUSED_PLAN_FIELDS)
+    assert C.sizeof(nb.NanoQkvAttnFusedDesc) == 2 * 8 + 2 * 4 + 5 * 8 and C.sizeof(nb.NanoWoW13FusedDesc) == 2 * 8 + 2 * 4 + 3 * 8
+    # the queries answer without a device, and refuse a null descriptor
+    assert nb.qkv_attn_fused_plan(0x80, 1024, 16, 8, 128)["takes"] == 1 and nb.wo_w13_fused_plan(2048, 1024, 3072)["takes"] == 1
+    out = (C.c_uint32 * 16)()
+    assert nb.lib().nano_hip_qkv_attn_fused_plan(None, None, 256, out) == -1 and nb.lib().nano_hip_wo_w13_fused_plan(None, None, 256, out) == -1
+
+
 def test_no_cpu_fallback():
     """Without a GPU the create call must fail loudly (no silent host path)."""
     if nb.device_count() > 0:
@@ -37,6 +54,9 @@ def test_no_cpu_fallback():
         nb.DeviceModel(nb.desc_from_spec(spec), blob, blob.size)
     with pytest.raises(nb.NanoHipError):
         nb.op_quantize_q80(np.zeros(64, np.float32), 64)
+    z = np.zeros(64, np.float32)
+    with pytest.raises(nb.NanoHipError):                # the fused-launch operators too: no device, no result
+        nb.op_wo_w13_fused(64, (np.zeros(64 * 64, np.int8), z, 64), (np.zeros(64 * 64, np.int8), z, 64), (np.zeros(64 * 64, np.int8), z, 64), z, z, x=z)
 
 
 @pytest.mark.parametrize("preset,quant,gs", [("tiny-nano", "f32", 0), ("tiny-qwen3", "q80", 64), ("tiny-nano-odd", "q4k", 0),

@@ -294,15 +294,24 @@ def test_fused_launches_equal_the_five_launches_per_layer(model_dir, preset, qua
     (wo_w13_fused_kernel: W1|W3's workgroups take the residual stream from Wo's as granules -- an all-gather inside the launch).  Same
     kernel bodies, so every logit of every step -- one split and several (positions beyond 64: Wo combines the partials), eager first use
     and graph replays, the greedy loop -- must be BIT-IDENTICAL whichever of them are on (NANO_FUSE_LAUNCHES bits: 1 q|k|v + attention, 2 Wo + W1|W3;
-    values 3 | 0 | 1 | 2, read at model creation: child processes).  wide-qwen3-2l = two layers of Qwen3-4B's shapes (the q|k|v + attention launch;
-    Wo + W1|W3 stays two launches on those wide matrices); qwen3-0.6b-3l = an odd layer count (round 6: the granules carry epoch tags, no buffer
-    pair alternates by layer); Q4K and FP32 / Nano: the q|k|v + attention launch of their own kernels (bit 0)."""
+    values 3 | 0 | 1 | 2, read at model creation: child processes).  wide-qwen3-2l = two layers of Qwen3-4B's shapes: BOTH fused launches
+    refuse them (n = 2560 wants more than the four waves fused_shape() takes; Wo + W1|W3 has no form for those wide matrices), so every
+    setting issues the five plain launches there -- the parameter pins that the refusal falls back correctly, not a fused kernel;
+    qwen3-0.6b-3l = an odd layer count (round 6: the granules carry epoch tags, no buffer pair alternates by layer); Q4K and FP32 / Nano:
+    the q|k|v + attention launch of their own kernels (bit 0).  Which form each preset takes: tests/test_fused_launch_plan.py PRESETS, asked
+    of the launchers' own planners below; every form on caller inputs: tests/test_gpu_fused_launches.py."""
     import os
     import subprocess
     import sys
     import zlib
     from conftest import ROOT
     path, spec = synth_model(model_dir, preset, quant, 64 if quant == "q80" else 0)     # (Q4K, round 6: the q|k|v + attention launch, bit 0)
+    # what is claimed as fused is fused (the planners' answer for this model's shapes; no device needed), and what is not, is not
+    from test_fused_launch_plan import PRESETS, preset_forms
+    forms = preset_forms(preset, quant)
+    assert forms == PRESETS[(preset, quant)], (preset, quant, forms)
+    assert (forms[0] is not None) == (preset != "wide-qwen3-2l"), (preset, quant, "q|k|v + attention", forms)
+    assert (forms[1] is not None and forms[2] is not None) == (quant == "q80" and preset != "wide-qwen3-2l"), (preset, quant, "Wo + W1|W3", forms)
     code = ("import sys, zlib, numpy as np; sys.path.insert(0, %r)\n"
             "from nano_amd import binding as nb, modelfile as mf\n"
             "m = nb.load_model_file(%r, max_seq_len=256, max_batch=1)\n"
