@@ -39,7 +39,7 @@ namespace {
 // The first `ngemv` workgroups run the projection's SLAB body (results stored as usual AND as granules), the last n_attn the attention's
 // plain decode mode (attention_body MODE 2), 256 threads for both.  Epoch tags, give-up and re-issue: device_common.h, backend.hip.
 // Reference: infer/infer.c:637-651, 758-879.
-template <int NV, int UPW, int QV>            // QV: float4 slots per lane of the attention's 8-lane sub-groups (1: head_dim <= 32, 2: <= 64 -- launch_attention's choice)
+template <int QV>            // QV: float4 slots per lane of the attention's 8-lane sub-groups (1: head_dim <= 32, 2: <= 64 -- launch_attention's choice)
 __global__ __launch_bounds__(256) void f32_qkv_attn_fused_kernel(const QkvAttnArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint2 tk_ = hand_tick(fa.hand);
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void f32_qkv_attn_fused_kernel(const QkvAttnAr
         attention_body<8, QV, 1, 2, false, false, 2, false, true>(fa.a, smem, grp, 0u, split, fa.hand, hand_ctag(tk_, fa.hand), fa.wait16);
         return;
     }
-    constexpr int ROLE = R_NORM_STORE, B = 1;
+    constexpr int ROLE = R_NORM_STORE, B = 1, NV = 1, UPW = 1;           // one float4 item per thread, one unit per wave (f32_fused_shape)
 #define F32_A fa.g
 #define F32_BID blockIdx.x
 #define F32_HAND 1
@@ -134,12 +134,12 @@ static bool f32_fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFused
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
     for (uint32_t s2 = 0; s2 < 3; s2++) if (ga.seg[s2].rows % 4u) return false;
     const F32Plan p = plan_f32(ga, 1);
-    if (p.nw > 4u || p.upw > 4u || ga.n > 1024u) return false;                   // one float4 item per thread on <= 256 threads
-    const uint32_t nchunk = (ga.n + 255) / 256, units = (p.rw / 4) * nchunk, upw = (units + 3u) / 4u;
-    if (upw > 4u) return false;
+    if (p.nw > 4u || ga.n > 1024u) return false;                                 // one float4 item per thread on <= 256 threads
+    const uint32_t nchunk = (ga.n + 255) / 256, units = (p.rw / 4) * nchunk;
+    if (units > 4u) return false;                // one unit per wave (more than 4 make plan_f32() ask for more than 4 waves: a wave never holds a second unit)
     if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, true)) return false;
     f = QkvAttnFusedPlan{};
-    f.kernel = FUSED_KERNEL_F32; f.nv = 1u; f.upw = upw <= 1 ? 1u : upw <= 2 ? 2u : 4u; f.qv = aa.hd <= 32u ? 1u : 2u;
+    f.kernel = FUSED_KERNEL_F32; f.nv = 1u; f.upw = 1u; f.qv = aa.hd <= 32u ? 1u : 2u;
     f.threads = 256; f.rw = p.rw;
     uint32_t rows = 0;
     for (uint32_t s2 = 0; s2 < 3; s2++) rows += ga.seg[s2].rows;
@@ -179,13 +179,11 @@ hipError_t launch_qkv_attn_fused_f32(const GemvArgs &ga, const AttnArgs &aa, uns
     const size_t lds = p.lds_bytes;
     fa.g = d; fa.ngemv = p.ngemv;
     fa.wait16 = 1u;             // naps of 16 x 64 cycles before the attention's first poll: Nano-168M, one box, 0 / 1 / 2 / 3 naps: 2387 / 2384 / 2380 / 2364 and 2383 / 2381 / 2380 / 2366 tok/s
-    // the instantiations: <1, UPW, QV> of {1, 2, 4} x {1, 2} (tests/test_fused_launch_plan.py restates the set)
-#define F32F_GO(UPW_) do { if (p.qv == 1u) hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 1>), dim3(grid), dim3(p.threads), lds, st, fa); \
-                           else hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<1, UPW_, 2>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
-    if (p.upw == 1) F32F_GO(1);
-    if (p.upw == 2) F32F_GO(2);
-    F32F_GO(4);
+    // the instantiations: <QV> of 1, 2 (tests/test_fused_launch_plan.py restates the set)
+#define F32F_GO(QV_) do { if (p.qv == QV_) { hipLaunchKernelGGL((f32_qkv_attn_fused_kernel<QV_>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } } while (0)
+    F32F_GO(1); F32F_GO(2);
 #undef F32F_GO
+    return hipErrorInvalidValue;
 }
 
 // The launch of `a`: which gemv_f32_slab_kernel<ROLE, B, NV, UPW>, on how many waves and workgroups, with how much LDS.  Every choice

@@ -64,9 +64,10 @@ namespace {
 // The first `ngemv` workgroups are the projection's chunk GEMV (role: rmsnorm + block quantizer + store), whose fold threads also store every
 // result as an 8-byte {tag, value} granule; the LAST n_attn workgroups are the attention's (head x split): they ask for their K / V rows at
 // entry, nap, then poll for q, the raw k row and the fresh v row of their KV group.  256 threads for both kinds (q4k_fused_shape).  Epoch tags, give-up and re-issue: device_common.h, backend.hip.  Reference: infer/infer.c:758-879.
-template <int NV, int D>
+template <int D>
 __global__ __launch_bounds__(256) void q4k_qkv_attn_fused_kernel(const QkvAttnArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NV = 1;                                       // n <= 1024 on 256 threads: one float4 item per thread (q4k_fused_shape)
     const uint2 tk_ = hand_tick(fa.hand);                       // the step's epoch: the first load of every workgroup
     if (blockIdx.x >= fa.ngemv) {
         const uint32_t ab = blockIdx.x - fa.ngemv;
@@ -293,11 +294,13 @@ static bool q4k_fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFused
     // seat a projection workgroup AND an attention workgroup (the first build ran the projection's own 384 threads: one workgroup per CU,
     // the attention started when the projection had left -- 0.575 -> 0.626 ms per step).  Same bits as the 384-thread launch: one float4 item
     // per thread on threads 0 .. n / 4 - 1 either way, a Q4K block is one wave's, the waves beyond add +0.0 to the norm's sum.
+    // n <= 1024: one float4 item per thread (NV 1); D: the chunk plan's wave-load slots, the built 1, 2, 4, 8
     if (ga.n > 1024u || !plan_chunk(ga, p, 4u) || p.loop || p.nthr != 256u || p.nv != 1u) return false;
+    if (!(p.d == 1u || p.d == 2u || p.d == 4u || p.d == 8u)) return false;
     if (p.lds > FUSED_LDS_MAX) return false;
     if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;
     f = QkvAttnFusedPlan{};
-    f.kernel = FUSED_KERNEL_Q4K; f.nv = p.nv <= 1 ? 1u : p.nv <= 2 ? 2u : 4u; f.d = p.d;
+    f.kernel = FUSED_KERNEL_Q4K; f.nv = 1u; f.d = p.d;
     f.threads = p.nthr; f.rw = p.rw; f.rounds = p.rounds;
     for (uint32_t s2 = 0; s2 < 3; s2++) f.wg[s2] = p.wg[s2];
     f.ngemv = p.grid; f.n_attn = fused_attn_wgs(aa);
@@ -324,14 +327,11 @@ hipError_t launch_qkv_attn_fused_q4k(const GemvArgs &ga, const AttnArgs &aa, uns
     // launches per layer 1733 / 1755 tok/s; fused with 2 naps 1773 / 1818, 4: 1782 / 1779, 6: 1742 / 1739, 8: 1684 / 1688
     // (re-swept at the end of round 6, producers first in the grid: 0 / 1 / 2 / 3 naps 1789 / 1761 / 1782 / 1780 and 1784 / 1778 / 1779 / 1775 tok/s: flat; none)
     fa.wait16 = 0u;
-    // the instantiations: <NV, D> of {1, 2, 4} x {1, 2, 4, 8} (tests/test_fused_launch_plan.py restates the set)
-#define Q4F_GO(NV_, D_) do { hipLaunchKernelGGL((q4k_qkv_attn_fused_kernel<NV_, D_>), dim3(p.n_attn + p.ngemv), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
-#define Q4F_NV(NV_) do { if (p.d == 1) Q4F_GO(NV_, 1); if (p.d == 2) Q4F_GO(NV_, 2); if (p.d == 4) Q4F_GO(NV_, 4); Q4F_GO(NV_, 8); } while (0)
-    if (p.nv == 1u) Q4F_NV(1);
-    if (p.nv == 2u) Q4F_NV(2);
-    Q4F_NV(4);
-#undef Q4F_NV
+    // the instantiations: <D> of 1, 2, 4, 8 (tests/test_fused_launch_plan.py restates the set)
+#define Q4F_GO(D_) do { if (p.d == D_) { hipLaunchKernelGGL((q4k_qkv_attn_fused_kernel<D_>), dim3(p.n_attn + p.ngemv), dim3(p.threads), lds, st, fa); return hipGetLastError(); } } while (0)
+    Q4F_GO(1); Q4F_GO(2); Q4F_GO(4); Q4F_GO(8);
 #undef Q4F_GO
+    return hipErrorInvalidValue;
 }
 
 }  // namespace nano

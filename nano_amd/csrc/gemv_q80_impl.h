@@ -373,9 +373,10 @@ __global__ __launch_bounds__(256) void qkv_attn_fused_kernel(const QkvAttnArgs f
 #include "qkv_attn_fused_body.inc"
 #undef SLAB_WF
 }
-// ... its form for n == 1024 (rows of one chunk): no product table, no barrier between the dots and the granules the attention workgroups wait for
-template <int NV, int UPW>
+// ... its form for n == 1024 (rows of one chunk): no product table, no barrier between the dots and the granules the attention workgroups wait
+// for.  One float4 item per thread, one unit per wave: the only form a shape reaches (fused_shape)
 __global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const QkvAttnArgs fa) {
+    constexpr int NV = 1, UPW = 1;
 #define SLAB_WF 1
 #include "qkv_attn_fused_body.inc"
 #undef SLAB_WF
@@ -391,16 +392,17 @@ __global__ __launch_bounds__(256) void qkv_attn_fused_wf_kernel(const QkvAttnArg
 // workgroups of the grid and never wait for consumers; a grid of <= one workgroup per CU is resident as a whole.  Same bodies, same bits
 // (test_fused_wo_w13_launch_equals_the_two_launches).  Reference: infer/infer.c:885-944.
 struct Wo13Args { GemvDev wo; GemvDev w13; SlabHand hand; uint32_t wo_wgs, wait16; };   // wait16: naps of 16 x 64 cycles before a non-producer workgroup starts polling
-template <int ROLE_A, int NV_A, int UPW_A, int NV_B, int UPW_B, int NT, int WF = 0, int WFA = 0>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF; WFA: Wo's rows are that many whole chunks: SLAB_WFC
-__global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
+// Eight waves, one float4 item per thread and one unit per wave in both bodies: the one form wo13_slabs() takes
+template <int ROLE_A, int WF, int WFA>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF; WFA: Wo's rows are that many whole chunks: SLAB_WFC
+__global__ __launch_bounds__(512) void wo_w13_fused_kernel(const Wo13Args fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int GS = 64, B = 1;
+    constexpr int GS = 64, B = 1, NV = 1, UPW = 1;
     const uint2 tk_ = hand_tick(fa.hand);
     // Order of issue: Wo's loads, W1|W3's loads, Wo's arithmetic, W1|W3's.  (vmcnt counts in order: loads issued BEFORE Wo's would have to
     // land before Wo may use its own -- the first build had W1|W3's in front and Wo waited for the whole 64 MB of Qwen3-4B's two matrices.)
     // Workgroups beyond Wo's grid run Wo's part 1 on rows past the matrix (out-of-range buffer loads: no traffic) and skip its part 2.
     {
-        constexpr int ROLE = ROLE_A, NV = NV_A, UPW = UPW_A;
+        constexpr int ROLE = ROLE_A;
 #define SLAB_BID blockIdx.x
 #define SLAB_A fa.wo
 #define SLAB_HAND 1
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(NT) void wo_w13_fused_kernel(const Wo13Args fa) {
 #undef SLAB_XHANDV
 #undef SLAB_CTAG
         {
-            constexpr int ROLE = R_NORM_SWIGLU, NV = NV_B, UPW = UPW_B;
+            constexpr int ROLE = R_NORM_SWIGLU;
 #define SLAB_A fa.w13
 #define SLAB_HAND 0
 #define SLAB_HANDV (SlabHand{})
@@ -699,30 +701,35 @@ static bool fused_shape(const GemvArgs &ga, const AttnArgs &aa, QkvAttnFusedPlan
     if (ga.n % 64u || ga.n > 4096u || use_stream(ga) || !q80_canonical(ga)) return false;        // (the role kernels of group size 64 carry the canonical fold only)
     if (ga.seg[0].out_pstride || ga.seg[1].out_pstride) return false;            // (only v is position indexed: its cache row)
     const SlabPlan p = q80_plan_slab(ga, 1);
-    if (p.nw != 4u || p.upw > 4u || !(p.nv == 1u || p.nv == 2u || p.nv == 4u)) return false;        // 256 threads, like the attention workgroups
+    if (p.nw != 4u || p.upw > 4u) return false;                                  // 256 threads, like the attention workgroups
+    const GemvDev d = to_dev(ga);
+    const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
+    const uint32_t upw = p.upw <= 1 ? 1u : p.upw <= 2 ? 2u : 4u;
+    // The built forms and no other.  Four waves = ceil(n / 384) mean n <= 1536: two float4 items per thread at most, no NV 4.  More than 8
+    // units of two chunks -- in the wave fold, more than 4 of one chunk -- need slabs of >= 20 rows, which q80_plan_slab grows only from
+    // 16384 rows on: >= 8 Mi weights, and those matrices get >= 8 waves: no <2, 4>, and the wave fold holds one unit per wave.
+    if (wf ? p.nv != 1u || upw != 1u : !(p.nv == 1u || (p.nv == 2u && upw <= 2u))) return false;
     if (!fused_attn_side_ok(aa, ga.seg[0].rows, ga.seg[1].rows, ga.seg[2].rows, false)) return false;   // (kernels.h)
     f = QkvAttnFusedPlan{};
-    f.nv = p.nv; f.upw = p.upw <= 1 ? 1u : p.upw <= 2 ? 2u : 4u;
+    f.kernel = wf ? FUSED_KERNEL_Q80_WF : FUSED_KERNEL_Q80_TABLE;
+    f.nv = p.nv; f.upw = upw;
     f.threads = 256; f.rw = p.rw;
     for (uint32_t s2 = 0; s2 < 3; s2++) { f.wg[s2] = (ga.seg[s2].rows + p.rw - 1) / p.rw; f.ngemv += f.wg[s2]; }
     f.n_attn = fused_attn_wgs(aa);
-    const GemvDev d = to_dev(ga);
     const uint32_t tpw = (p.rw + 3) / 4;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
-    const bool wf = slab_wave_fold(d);                    // n == 1024: the projection's waves fold their own rows, no product table
     const size_t lds_g = n16 + ng4 * 4 + 64 + (wf ? 0 : (size_t)(tpw * 4) * pitch * 4), lds_a = fused_attn_lds(aa.hd, false);
     const size_t lds = lds_g > lds_a ? lds_g : lds_a;
     if (lds > FUSED_LDS_MAX) return false;
     f.lds_bytes = (uint32_t)lds;
-    f.kernel = (wf && p.nv == 1u) ? FUSED_KERNEL_Q80_WF : FUSED_KERNEL_Q80_TABLE;
     return true;
 }
 
 // ---- the fused Wo + W1|W3 launch: host side ----------------------------------------------------------------------------------------------
-// Both bodies run on the launch's threads = W1|W3's own plan (its rmsnorm tree follows the thread count; Wo has no tree: any count gives its
-// bits).  Instantiated: Qwen3-0.6B's shapes (256 and 512 threads).  (Qwen3-4B's wide matrices had a 1024-thread form; it lost to the two
-// plain launches -- 1.531 vs 1.473 ms per step -- and was removed: those shapes are refused here and take the plain launches.)
-struct Wo13Plan { SlabPlan a, b; uint32_t nw, nv_a, upw_a, wa, wb; int sig; };
+// Both bodies run on the launch's 512 threads (W1|W3's rmsnorm tree follows the thread count; Wo has no tree: any count gives its bits).
+// One form: Qwen3-0.6B's shapes.  (Qwen3-4B's wide matrices had a 1024-thread form; it lost to the two plain launches -- 1.531 vs 1.473 ms
+// per step -- and was removed: those shapes are refused here and take the plain launches.)
+struct Wo13Plan { SlabPlan a, b; uint32_t wa, wb; };
 static bool wo13_slabs(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (wo.gs != 64 || w13.gs != 64 || wo.nb != 1 || w13.nb != 1 || !q80_canonical(wo) || !q80_canonical(w13)) return false;
     if (wo.nseg != 1 || wo.epi != GEMV_EPI_RESID || wo.norm_w || wo.xq_in || wo.tile_max || wo.resid_add || wo.seg[0].out_pstride) return false;
@@ -730,25 +737,19 @@ static bool wo13_slabs(const GemvArgs &wo, const GemvArgs &w13, Wo13Plan &q) {
     if (w13.nseg != 2 || w13.epi != GEMV_EPI_SWIGLU || !w13.norm_w || w13.xq_in || w13.attn_part || w13.tile_max || w13.resid_add) return false;
     if (use_stream(wo) || use_stream(w13) || w13.n != wo.seg[0].rows || w13.xin != wo.seg[0].out || w13.n % 4u) return false;
     q.a = q80_plan_slab(wo, 1); q.b = q80_plan_slab(w13, 1);
-    q.nw = q.b.nw;
-    const uint32_t units_a = ((q.a.rw + 3) / 4) * ((wo.n + 1023) / 1024);
-    q.upw_a = (units_a + q.nw - 1) / q.nw;
-    q.nv_a = (wo.n / 4 + 64 * q.nw - 1) / (64 * q.nw);
     q.wa = (wo.seg[0].rows + q.a.rw - 1) / q.a.rw; q.wb = (w13.seg[0].rows + q.b.rw - 1) / q.b.rw;
     const uint32_t cus = w13.cus ? w13.cus : 256u;
     if (q.wa > q.wb || q.wb > cus) return false;                                                // one workgroup per CU: the whole grid is resident
-    if (q.a.rw > 64 * q.nw || q.b.rw > 64 * q.nw) return false;                                 // one fold thread per row
-    q.sig = 0;
-    if (q.nw == 4u && q.nv_a == 2u && q.upw_a == 1u && q.b.nv == 1u && q.b.upw == 2u) q.sig = 1;       // Qwen3-0.6B
-    if (q.sig == 1) {
-        // Round 6, last day: the same two bodies on EIGHT waves where that leaves one float4 item per thread and one unit per wave in both (Qwen3-0.6B:
-        // Wo's 512 items, 4 units; W1|W3's 256 items, 6 units) -- the four-wave form dates from the first fused build and had Wo's threads quantize
-        // two items each.  Same bits (Wo has no tree; W1|W3's items sit on the same threads).  Same box, driver's flags | full window:
-        // 1991.2 | 1894.2, 1992.5 | 1893.4, 1990.7 | 1895.2 with four waves, 2033.3 | 1919.6, 2039.2 | 1937.1, 2030.2 | 1919.2 with eight.
-        const uint32_t units_b = ((q.b.rw + 3) / 4) * ((w13.n + 1023) / 1024) * 2u;
-        if ((units_a + 7u) / 8u == 1u && (wo.n / 4 + 511u) / 512u == 1u && (units_b + 7u) / 8u == 1u && (w13.n / 4 + 511u) / 512u == 1u) { q.sig = 3; q.nw = 8u; }
-    }
-    return q.sig != 0;
+    // One form: EIGHT waves, one float4 item per thread and one unit per wave in both bodies.  Its shapes are the small matrices the first fused
+    // build ran on W1|W3's own four waves (one item per thread and two units per wave there; Wo's threads quantized two items each and held at
+    // most 4 units): every one of them has at most 512 items and 8 units a side -- 32 rows, a fold thread each (Qwen3-0.6B: Wo's 512 items, 4
+    // units; W1|W3's 256 items, 6 units).  Why eight waves (round 6, last day): same bits (Wo has no tree; W1|W3's items sit on the same
+    // threads), and on the same box, driver's flags | full window:
+    // 1991.2 | 1894.2, 1992.5 | 1893.4, 1990.7 | 1895.2 with four waves, 2033.3 | 1919.6, 2039.2 | 1937.1, 2030.2 | 1919.2 with eight.
+    const uint32_t units_a = ((q.a.rw + 3) / 4) * ((wo.n + 1023) / 1024), items_a = wo.n / 4;
+    const uint32_t units_b = ((q.b.rw + 3) / 4) * ((w13.n + 1023) / 1024) * 2u, items_b = w13.n / 4;
+    return q.b.nw == 4u && q.b.nv == 1u && q.b.upw == 2u && units_b <= 8u && items_b >= 1u && items_b <= 512u &&      // W1|W3
+           items_a > 256u && items_a <= 512u && units_a >= 1u && units_a <= 4u;                                          // Wo
 }
 static void slab_dev_fill(GemvDev &d, const GemvArgs &a, const SlabPlan &p, uint32_t nthr) {
     d.tile_max = nullptr;
@@ -767,20 +768,19 @@ static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan &
     Wo13Plan q;
     if (!wo13_slabs(wo, w13, q)) return false;
     da = to_dev(wo); db = to_dev(w13);
-    slab_dev_fill(da, wo, q.a, 64 * q.nw); slab_dev_fill(db, w13, q.b, 64 * q.nw);
+    slab_dev_fill(da, wo, q.a, 512); slab_dev_fill(db, w13, q.b, 512);
     // W1|W3's rows of one chunk (n == 1024): pair units (two rows of W1 and the same two of W3), folded by the wave that holds them
     const bool wf = slab_wave_fold(db);
     if (wf) db.units = (db.rw + 1) / 2;
-    // Wo's rows of two whole chunks (n == 2048, the widest these signatures take): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
+    // Wo's rows of two whole chunks (n == 2048, the widest this form takes): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
     const bool wfa = slab_wave_fold_chunks(da) == 2u;
     const size_t la = slab_lds(da, !wfa) + (wfa ? slab_unit_table(da, 2u) : 0), lb = slab_lds(db, !wf), lds = la > lb ? la : lb;
     if (lds > FUSED_LDS_MAX) return false;
     f = WoW13FusedPlan{};
-    f.sig = (uint32_t)q.sig; f.threads = 64 * q.nw;
+    f.sig = 3; f.threads = 512;                                                 // (sig: the queries' word for this form; 1 was the four-wave one)
     f.role = (da.flags & F_COMBINE) ? (uint32_t)R_RESID_COMBINE : (uint32_t)R_RESID;
     f.wf = wf ? 1u : 0u; f.wfc = wfa ? 2u : 0u;
-    if (q.sig == 1) { f.nv_a = 2; f.upw_a = 1; f.nv_b = 1; f.upw_b = 2; }       // (the two signatures wo13_slabs() lets through)
-    else { f.nv_a = 1; f.upw_a = 1; f.nv_b = 1; f.upw_b = 1; }
+    f.nv_a = 1; f.upw_a = 1; f.nv_b = 1; f.upw_b = 1;
     f.wa = q.wa; f.wb = q.wb; f.lds_bytes = (uint32_t)lds;
     f.rw_a = q.a.rw; f.rw_b = q.b.rw;
     return true;
@@ -836,15 +836,14 @@ hipError_t launch_qkv_attn_fused_q80(const GemvArgs &ga, const AttnArgs &aa, uns
     // 1961 / 1919, 1977 / 1986 / 1958 / 1920, 1982 / 1981 / 1960 / 1912 tok/s; positions 31..510: 1878 / 1880 / 1859 / 1821
     // (profiles/r06_handoff_naps.txt).
     fa.wait16 = 1u;
-    // the instantiations: NV, UPW of {1, 2, 4} x {1, 2, 4} in the table form, <1, UPW> in the wave-fold form (tests/test_fused_launch_plan.py restates the set)
-#define FUSED_GO(NV_, UPW_) do { if (p.kernel == FUSED_KERNEL_Q80_WF && NV_ == 1) hipLaunchKernelGGL((qkv_attn_fused_wf_kernel<1, UPW_>), dim3(grid), dim3(p.threads), lds, st, fa); \
-                                 else hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } while (0)
-#define FUSED_NV(NV_) do { if (p.upw == 1) FUSED_GO(NV_, 1); if (p.upw == 2) FUSED_GO(NV_, 2); FUSED_GO(NV_, 4); } while (0)
-    if (p.nv == 1u) FUSED_NV(1);
-    if (p.nv == 2u) FUSED_NV(2);
-    FUSED_NV(4);
-#undef FUSED_NV
+    // the instantiations: the table form's <NV, UPW> of <1, 1> <1, 2> <1, 4> <2, 1> <2, 2> and the wave-fold kernel -- what fused_shape() lets through
+    // (tests/test_fused_launch_plan.py restates the set)
+    if (p.kernel == FUSED_KERNEL_Q80_WF) { hipLaunchKernelGGL(qkv_attn_fused_wf_kernel, dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); }
+#define FUSED_GO(NV_, UPW_) do { if (p.nv == NV_ && p.upw == UPW_) { hipLaunchKernelGGL((qkv_attn_fused_kernel<NV_, UPW_>), dim3(grid), dim3(p.threads), lds, st, fa); return hipGetLastError(); } } while (0)
+    FUSED_GO(1, 1); FUSED_GO(1, 2); FUSED_GO(1, 4);
+    FUSED_GO(2, 1); FUSED_GO(2, 2);
 #undef FUSED_GO
+    return hipErrorInvalidValue;
 }
 
 bool wo_w13_fused_plan(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan *out) {
@@ -867,16 +866,13 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     h.base[0] = 0; h.base[1] = 0; h.base[2] = 0;
     fa.hand = h;
     const size_t lds = q.lds_bytes;
-    const bool wf = q.wf != 0, wfa = q.wfc == 2u, comb = q.role == (uint32_t)R_RESID_COMBINE;
-    // the instantiations: sig 1 <role, 2, 1, 1, 2, 256> and sig 3 <role, 1, 1, 1, 1, 512>, each with WF 0 | 1 and WFC 0 | 2 (tests/test_fused_launch_plan.py restates the set)
-#define WO13_GO(RA_, NVA_, UA_, NVB_, UB_, NT_) do { if (wf && wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \
-                                                     else if (wf) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 1>), dim3(q.wb), dim3(NT_), lds, st, fa); \
-                                                     else if (wfa) hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_, 0, 2>), dim3(q.wb), dim3(NT_), lds, st, fa); \
-                                                     else hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, NVA_, UA_, NVB_, UB_, NT_>), dim3(q.wb), dim3(NT_), lds, st, fa); return hipGetLastError(); } while (0)
-    if (q.sig == 1) { if (comb) WO13_GO(R_RESID_COMBINE, 2, 1, 1, 2, 256); WO13_GO(R_RESID, 2, 1, 1, 2, 256); }
-    if (comb) WO13_GO(R_RESID_COMBINE, 1, 1, 1, 1, 512);           // (sig 3)
-    WO13_GO(R_RESID, 1, 1, 1, 1, 512);
+    // the instantiations: <role, WF, WFC> of {R_RESID, R_RESID_COMBINE} x {0, 1} x {0, 2} (tests/test_fused_launch_plan.py restates the set)
+#define WO13_GO(RA_, WF_, WFC_) do { if (q.role == (uint32_t)RA_ && q.wf == WF_ && q.wfc == WFC_) { \
+        hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, WF_, WFC_>), dim3(q.wb), dim3(q.threads), lds, st, fa); return hipGetLastError(); } } while (0)
+    WO13_GO(R_RESID, 0, 0); WO13_GO(R_RESID, 0, 2); WO13_GO(R_RESID, 1, 0); WO13_GO(R_RESID, 1, 2);
+    WO13_GO(R_RESID_COMBINE, 0, 0); WO13_GO(R_RESID_COMBINE, 0, 2); WO13_GO(R_RESID_COMBINE, 1, 0); WO13_GO(R_RESID_COMBINE, 1, 2);
 #undef WO13_GO
+    return hipErrorInvalidValue;
 }
 #endif
 

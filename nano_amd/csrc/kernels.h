@@ -291,16 +291,16 @@ bool attention_plan(const AttnArgs &a, uint32_t nb, AttnPlan *p);
 // q | k | v projection of one sequence + decode attention as ONE launch (gemv.hip dispatches on the weight format -- Q80 group size 64:
 // gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip, round 6, both with Qwen3 attention; FP32: gemv_f32.hip, the plain mode): the attention workgroups
 // wait for q / k / v as 8-byte {tag, value} granules in `hand` (q_dim + 2 kv_dim entries); tag = the step's tick * 128 + layer1 (device_common.h)
-// The launch launch_qkv_attn_fused() issues: qkv_attn_fused_kernel<nv, upw> (Q80, the product-table body) | qkv_attn_fused_wf_kernel<1, upw>
-// (Q80, rows of one chunk: the in-wave fold) | q4k_qkv_attn_fused_kernel<nv, d> | f32_qkv_attn_fused_kernel<1, upw, qv>, on `threads` threads
+// The launch launch_qkv_attn_fused() issues: qkv_attn_fused_kernel<nv, upw> (Q80, the product-table body) | qkv_attn_fused_wf_kernel
+// (Q80, rows of one chunk: the in-wave fold; nv = upw = 1) | q4k_qkv_attn_fused_kernel<d> (nv = 1) | f32_qkv_attn_fused_kernel<qv> (nv = upw = 1), on `threads` threads
 // x (ngemv projection workgroups of rw rows -- wg[s] on tensor s -- followed by n_attn attention workgroups) with lds_bytes of dynamic LDS.
 // qkv_attn_fused_plan() makes every choice, the launchers take them from it; false: the launch is refused (the step issues the two plain
-// launches).  Host arithmetic on shape fields; of the pointers only null-or-not is read.
+// launches) -- a plan names a built instantiation or does not exist.  Host arithmetic on shape fields; of the pointers only null-or-not is read.
 enum : uint32_t { FUSED_KERNEL_NONE = 0, FUSED_KERNEL_Q80_TABLE = 1, FUSED_KERNEL_Q80_WF = 2, FUSED_KERNEL_Q4K = 3, FUSED_KERNEL_F32 = 4 };
 constexpr uint32_t FUSED_LDS_MAX = 64 * 1024;
 struct QkvAttnFusedPlan {
     uint32_t kernel, nv;
-    uint32_t upw, d, qv;                        // Q80, FP32: UPW; Q4K: D; FP32: QV (1: head_dim <= 32, 2: above); the others 0
+    uint32_t upw, d, qv;                        // Q80: UPW, FP32: 1; Q4K: D; FP32: QV (1: head_dim <= 32, 2: above); the others 0
     uint32_t threads, n_attn, ngemv, lds_bytes;
     uint32_t rw, wg[3], rounds;                 // rows of a projection workgroup, its workgroups per tensor (FP32: all in wg[0]); Q4K: the chunk plan's rounds
 };
@@ -308,9 +308,10 @@ bool qkv_attn_fused_plan(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa,
 inline bool qkv_attn_fused_supports(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa) { return qkv_attn_fused_plan(quant, ga, aa, nullptr); }
 hipError_t launch_qkv_attn_fused(uint32_t quant, const GemvArgs &ga, const AttnArgs &aa, unsigned long long *hand, uint32_t *tick, uint32_t layer1, hipStream_t st);
 // Wo + W1|W3 of one sequence in ONE launch (gemv_q80_impl.h wo_w13_fused_kernel): x reaches W1|W3 as granules of the same launch.
-// The launch: wo_w13_fused_kernel<role, nv_a, upw_a, nv_b, upw_b, threads, wf, wfc> on wb workgroups (the first wa also run Wo's rows: rw_a
-// and rw_b rows each) -- sig 1: 256 threads, sig 3: 512; role R_RESID | R_RESID_COMBINE (gemv_common.h: 2 | 3); wf 1: W1|W3's rows of one
-// chunk folded in the wave; wfc 2: Wo's rows of two chunks likewise, else 0.  wo_w13_fused_plan() makes every choice; false: refused.
+// The launch: wo_w13_fused_kernel<role, wf, wfc> on wb workgroups (the first wa also run Wo's rows: rw_a and rw_b rows each) of 512 threads,
+// one float4 item per thread and one unit per wave in both bodies; role R_RESID | R_RESID_COMBINE (gemv_common.h: 2 | 3); wf 1: W1|W3's rows
+// of one chunk folded in the wave; wfc 2: Wo's rows of two chunks likewise, else 0.  wo_w13_fused_plan() makes every choice; false: refused.
+// sig, threads, nv_a .. upw_b are the constants 3, 512, 1, 1, 1, 1 of that one form: words of the plan queries (nano_mi355x.h).
 struct WoW13FusedPlan {
     uint32_t sig, threads, role, wf, wfc;
     uint32_t nv_a, upw_a, nv_b, upw_b;

@@ -1,6 +1,6 @@
 // qkv_attn_fused_body.inc -- the statements of the fused q | k | v + attention kernel (gemv_q80_impl.h), included textually into its two
-// forms: qkv_attn_fused_kernel (the projection's rows fold through the LDS product table) and qkv_attn_fused_wf_kernel (rows of one chunk,
-// n == 1024: every wave folds its own rows, gemv_q80_slab_body.inc SLAB_WF).  The includer defines SLAB_WF; fa, NV, UPW are in scope.
+// forms: qkv_attn_fused_kernel<NV, UPW> (the projection's rows fold through the LDS product table) and qkv_attn_fused_wf_kernel (rows of one chunk,
+// n == 1024: every wave folds its own rows, gemv_q80_slab_body.inc SLAB_WF; NV = UPW = 1).  The includer defines SLAB_WF; fa, NV, UPW are in scope.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint2 tk_ = hand_tick(fa.hand);                       // the step's epoch: the first load of every workgroup
     if (blockIdx.x >= fa.ngemv) {

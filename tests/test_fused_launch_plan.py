@@ -4,16 +4,16 @@ the conditions backend_step.hip puts in front of them).  No GPU: the queries are
 
 A FORM is the kernel and the template values of a launch:
     ("q80_table", NV, UPW)   qkv_attn_fused_kernel<NV, UPW>          Q80 group size 64, the product table and the barrier behind the dots
-    ("q80_wf", 1, UPW)       qkv_attn_fused_wf_kernel<1, UPW>        Q80, rows of one chunk (n == 1024): every wave folds its own rows
-    ("q4k", NV, D)           q4k_qkv_attn_fused_kernel<NV, D>
-    ("f32", UPW, QV)         f32_qkv_attn_fused_kernel<1, UPW, QV>   QV 1: head_dim <= 32, 2: above
-    ("wo_w13", sig, role, WF, WFC)   wo_w13_fused_kernel<role, .., threads, WF, WFC>: sig 1 = <2, 1, 1, 2, 256>, sig 3 = <1, 1, 1, 1, 512>
+    ("q80_wf", 1, 1)         qkv_attn_fused_wf_kernel                Q80, rows of one chunk (n == 1024): every wave folds its own rows
+    ("q4k", 1, D)            q4k_qkv_attn_fused_kernel<D>
+    ("f32", 1, QV)           f32_qkv_attn_fused_kernel<QV>           QV 1: head_dim <= 32, 2: above
+    ("wo_w13", 3, role, WF, WFC)     wo_w13_fused_kernel<role, WF, WFC>: 512 threads, one item per thread and one unit per wave (the queries' sig 3)
 The sweeps below run the shape space the models can bring -- row lengths in multiples of 64 up to 4096; 1 .. 64 heads, the KV head count
 and the head ratio powers of two; head_dim 128 (Q80, Q4K: Qwen3's attention) or 4 .. 64 in steps of 4 (FP32: Nano's); 1 .. 8 splits;
 range_hint up to nsplit * 64; 256 compute units; Wo rows of up to 4096, W1|W3 rows of up to 2048 values, hidden sizes in steps of 256 (the
 planner's slabs move with rows / 256) up to 16384 -- and check that
   * the forms met are exactly UNIVERSE, and SMALLEST names the smallest shape of each (weight bytes, then range_hint, then the shape);
-  * every instantiation the launcher macros FUSED_GO, Q4F_GO, F32F_GO and WO13_GO can name is in UNIVERSE or in DEAD, with the planner's reason;
+  * the instantiations the launchers (the wave-fold kernel and the macros FUSED_GO, Q4F_GO, F32F_GO, WO13_GO) name are exactly UNIVERSE;
   * no plan asks for more than 64 KiB of LDS, runs other than 256 threads next to the attention workgroups, or -- Wo + W1|W3, whose waits
     rely on the whole grid being resident -- more workgroups than compute units;
   * the attention side (kernels.h fused_attn_side_ok()) decides independently of the projection: nsplit 1 .. 8, a power-of-two KV head
@@ -59,30 +59,12 @@ SMALLEST = {
 }
 UNIVERSE = frozenset(SMALLEST)
 
-# ---- every instantiation the launcher macros can name (gemv_q80_impl.h FUSED_GO / WO13_GO, gemv_q4k_chunk.hip Q4F_GO, gemv_f32.hip F32F_GO) ----
+# ---- every instantiation the launchers name (gemv_q80_impl.h FUSED_GO / the wave-fold kernel / WO13_GO, gemv_q4k_chunk.hip Q4F_GO, gemv_f32.hip F32F_GO) ----
 NAMED = frozenset(
-    [("q80_table", nv, upw) for nv in (1, 2, 4) for upw in (1, 2, 4)] + [("q80_wf", 1, upw) for upw in (1, 2, 4)] +
-    [("q4k", nv, d) for nv in (1, 2, 4) for d in (1, 2, 4, 8)] +
-    [("f32", upw, qv) for upw in (1, 2, 4) for qv in (1, 2)] +
-    [("wo_w13", sig, role, wf, wfc) for sig in (1, 3) for role in (R_RESID, R_COMBINE) for wf in (0, 1) for wfc in (0, 2)])
-
-# ... and those no shape reaches, each with the planner's reason (DESIGN.md section 3 lists them too)
-_Q80_NV4 = "fused_shape() wants q80_plan_slab's nw == 4 = ceil(n / 384) waves: n <= 1536, two float4 items per thread at most"
-_Q80_UPW4 = ("NV 2 is two chunks; more than 8 units on four waves needs slabs of >= 20 rows, which q80_plan_slab grows only from 16384 rows "
-             "on: >= 8 Mi weights, and those matrices get >= 8 waves")
-_WF_UPW = ("n == 1024 is one chunk; more than 4 units on four waves needs slabs of >= 20 rows, which q80_plan_slab grows only from 16384 rows "
-           "on: >= 8 Mi weights, and those matrices get >= 8 waves")
-_Q4K_NV = "q4k_fused_shape() takes n <= 1024 on 256 threads: one float4 item per thread (p.nv != 1 is refused)"
-_F32_UPW = "more than 4 units make plan_f32() ask for more than 4 waves, which f32_fused_shape() refuses: a wave never holds a second unit"
-_SIG1 = "every shape with wo13_slabs()'s signature 1 also passes its eight-wave test (<= 8 units and <= 512 float4 items on both sides): sig 3"
-DEAD = {
-    **{("q80_table", 4, upw): _Q80_NV4 for upw in (1, 2, 4)},
-    ("q80_table", 2, 4): _Q80_UPW4,
-    ("q80_wf", 1, 2): _WF_UPW, ("q80_wf", 1, 4): _WF_UPW,
-    **{("q4k", nv, d): _Q4K_NV for nv in (2, 4) for d in (1, 2, 4, 8)},
-    **{("f32", upw, qv): _F32_UPW for upw in (2, 4) for qv in (1, 2)},
-    **{("wo_w13", 1, role, wf, wfc): _SIG1 for role in (R_RESID, R_COMBINE) for wf in (0, 1) for wfc in (0, 2)},
-}
+    [("q80_table", nv, upw) for nv, upw in ((1, 1), (1, 2), (1, 4), (2, 1), (2, 2))] + [("q80_wf", 1, 1)] +
+    [("q4k", 1, d) for d in (1, 2, 4, 8)] +
+    [("f32", 1, qv) for qv in (1, 2)] +
+    [("wo_w13", 3, role, wf, wfc) for role in (R_RESID, R_COMBINE) for wf in (0, 1) for wfc in (0, 2)])
 
 # ---- the presets: which form each takes (None: the step issues the plain launches) -------------------------------------------------------
 # (preset, quant) -> (q | k | v + attention, Wo + W1|W3 at one split, ... at two)
@@ -267,8 +249,8 @@ def test_wo_w13_sweep_meets_exactly_the_universe():
                     assert p["lds_bytes"] <= LDS_MAX and p["_zero"] == 0, ctx
                     assert p["wb"] <= CUS and p["wa"] <= p["wb"], ("the whole grid must be resident, Wo's workgroups among W1|W3's", ctx)
                     assert p["wa"] == (E + p["rw_a"] - 1) // p["rw_a"] and p["wb"] == (hidden + p["rw_b"] - 1) // p["rw_b"], ctx
-                    assert p["threads"] == {1: 256, 3: 512}[p["sig"]] and max(p["rw_a"], p["rw_b"]) <= p["threads"], ctx
-                    assert (p["nv_a"], p["upw_a"], p["nv_b"], p["upw_b"]) == {1: (2, 1, 1, 2), 3: (1, 1, 1, 1)}[p["sig"]], ctx
+                    assert p["sig"] == 3 and p["threads"] == 512 and max(p["rw_a"], p["rw_b"]) <= p["threads"], ctx
+                    assert (p["nv_a"], p["upw_a"], p["nv_b"], p["upw_b"]) == (1, 1, 1, 1), ctx
                     assert p["nv_a"] * p["threads"] * 4 >= n_wo and p["nv_b"] * p["threads"] * 4 >= E, ("an activation float4 without a register", ctx)
                     waves = p["threads"] // 64
                     assert (p["rw_a"] + 3) // 4 * ((n_wo + 1023) // 1024) <= waves * p["upw_a"], ("a Wo unit without a wave slot", ctx)
@@ -285,10 +267,8 @@ def test_wo_w13_sweep_meets_exactly_the_universe():
 
 
 def test_universe_and_dead_account_for_every_named_instantiation():
-    assert UNIVERSE <= NAMED, sorted(UNIVERSE - NAMED)
-    assert set(DEAD) == NAMED - UNIVERSE, ("named by a launcher macro, neither reachable nor listed as dead -- or listed as both", sorted(set(DEAD) ^ (NAMED - UNIVERSE)))
-    assert all(isinstance(r, str) and r for r in DEAD.values())
-    assert len(NAMED) == 12 + 12 + 6 + 16
+    assert NAMED == UNIVERSE, ("named by a launcher and reached by no shape, or reachable and not built", sorted(NAMED ^ UNIVERSE))
+    assert len(NAMED) == 5 + 1 + 4 + 2 + 8 == 20
 
 
 def test_a_smaller_chip_changes_no_form_but_may_refuse():

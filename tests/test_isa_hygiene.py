@@ -68,9 +68,8 @@ def test_q80_batch1_roles_fetch_their_arguments_up_front():
         for k in hot(recs, ["gemv_q80_slab_kernel" + sig]):
             check(k)
             assert not k["late_scalar_loads"], (k["name"], "kernel arguments fetched after the first batch", k["late_scalar_loads"])
-    expected = (["qkv_attn_fused_kernelILi%dELi%dEE" % (nv, upw) for nv in (1, 2, 4) for upw in (1, 2, 4)] +
-                ["wo_w13_fused_kernelILi%dELi2ELi1ELi1ELi2ELi256E" % role for role in (2, 3)] +         # Wo + W1|W3: 256 and 512 threads, with and
-                ["wo_w13_fused_kernelILi%dELi1ELi1ELi1ELi1ELi512E" % role for role in (2, 3)] +         # without the split combine
+    expected = (["qkv_attn_fused_kernelILi%dELi%dEE" % f for f in ((1, 1), (1, 2), (1, 4), (2, 1), (2, 2))] +       # every built form (tests/test_fused_launch_plan.py)
+                ["wo_w13_fused_kernelILi%dELi%dELi%dEE" % (role, wf, wfc) for role in (2, 3) for wf in (0, 1) for wfc in (0, 2)] +   # Wo + W1|W3, with and without the split combine
                 ["gemv_q80_slab_kernel" + sig for sig in ("ILi1ELi64ELi1ELi1ELi1E", "ILi2ELi64ELi1ELi2ELi1E", "ILi3ELi64ELi1ELi2ELi1E", "ILi4ELi64ELi1ELi1ELi2E")])
     seen = set()
     for blk in re.findall(r"- \.agpr_count:.*?\.wavefront_size: *\d+", asm, re.S):
