@@ -225,6 +225,13 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
  * its slot 0 and forks it into the other slots of its share (nano_hip_kv_fork, nano_mi355x.h: a copy, or shared pages on a paged
  * cache).  Applies the context's LoRA selection as nano_forward_batch does.  Returns 0 or a NANO_HIP_E* code. */
 int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch);
+/* Ingest `batch` prompts at once: sequence i (the sequences nano_forward_batch addresses) takes prompts[i][0..n_tokens[i]) from position
+ * 0, and first_ids[i] (optional, batch words) is the arg-max behind its last token -- the first id of a greedy continuation (an empty
+ * prompt leaves first_ids[i] untouched).  One ragged step per device (nano_hip_step_rows, nano_mi355x.h): the prompts share the weight
+ * reads, and each sequence's rows are those of its own batched prefill.  With replicas (sequence i -> replica i mod G, slot i / G) each
+ * replica's share is one call, one replica after another.  The ragged step has no LoRA branches: with a module selected the call
+ * returns NANO_HIP_EINVAL.  Returns 0 or a NANO_HIP_E* code; a refused call feeds nothing on the device that refused. */
+int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const uint32_t *n_tokens, uint32_t batch, uint32_t *first_ids);
 /* Feed ids[0..n_ids-1) into sequence 0 from position 0 and score ids[1..n_ids): logprobs / argmax hold n_ids-1 entries (either may be NULL),
  * *nll_sum = -(sum of the logprobs), added in double in index order.  Applies the context's LoRA selection as nano_forward_batch does.
  * logprobs[i] = log p(ids[i + 1] | ids[0..i]) and argmax[i] = the model's own choice there, both taken on the device from a batched

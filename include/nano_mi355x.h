@@ -253,6 +253,42 @@ int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uin
                             const NanoHipLookupParams *params, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
                             uint32_t *next_tokens_out, uint32_t *next_pos_out);
 
+/* ---- ragged steps: rows of several KV slots share one weight read --------------------------------------------------
+ * A step whose rows each carry their own (slot, position): several prompts in one chunk, a new prompt joining running sequences, one
+ * greedy step for sequences in ANY slots, drafts of several sequences verified at once.  A segment names positions
+ * pos0 .. pos0 + count - 1 of `slot`; tokens holds sum(count) ids, segment after segment.
+ * Contract: the K / V rows and every later output of every slot are those of nano_hip_prefill(m, slot, ...) called per segment, bit for
+ * bit (with the wide-matrix caveat stated at nano_hip_decode_lookup above), and argmax_out (optional, sum(count) words, caller order)
+ * holds what nano_hip_verify_draft returns for the same rows.  A segment of count 1 is a decode row: with argmax_out one call is a
+ * greedy step of the running sequences plus a piece of a newcomer's prompt.  Sampled rows follow with nano_hip_forward_sample_batch,
+ * as after nano_hip_prefill.
+ * How: the rows are cut into passes of up to nano_hip_prefill_chunk_tokens() rows in caller order (nano_hip_rows_plan below); a pass
+ * is one embed launch and per layer one q|k|v launch, one Wo, W1|W3 and W2 launch over ALL its rows.  Each row's attention is split
+ * exactly as that token's own one-sequence decode step (64 positions per split at head_dim <= 128), which is what makes the bits
+ * hold: inside a pass the rows are ordered by range bucket and every bucket gets its own attention (and combine) launch.  Passes run
+ * eagerly (no graphs); the call's tokens, positions and slots are staged once and the host waits once.  Paged cache: the pages of all
+ * segments are ensured before anything is queued, all or nothing, shared pages copied on write as for nano_hip_prefill.  Contiguous
+ * FP32 cache: the fresh v rows travel through scratch and are stored by the attention kernel's row-preparation pass, as on the FP16
+ * cache (a copy: the same bits).  Strict and exact mode feed token by token, each a reference-order step in the row's slot.
+ * NANO_HIP_EINVAL before anything is queued (a refused call feeds nothing): null m / segs / tokens, a slot >= max_batch, two segments
+ * with the same slot, positions beyond max_seq_len or the RoPE table, a token >= vocab, reserved != 0, LoRA switched on (its v branch
+ * addresses the cache by a flat stride), a cache the row map cannot address (nano_hip_rows_addressable), and whatever
+ * nano_hip_prefill refuses for the model's switches.  n_segs == 0, or all counts 0, returns 0 and touches nothing.  is_causal = 0 is
+ * not offered. */
+typedef struct NanoHipRowSeg { uint32_t slot, pos0, count, reserved; } NanoHipRowSeg;   /* positions pos0 .. pos0+count-1 of `slot` */
+int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out);
+/* Device-free: how nano_hip_step_rows cuts its rows into passes of at most `cap` rows (cap = nano_hip_prefill_chunk_tokens()).  For
+ * row r in caller order (all outputs optional, sum(count) words): row_pass[r] = its pass, row_index[r] = its row inside the pass,
+ * row_hint[r] = min((pos / 64 + 1) * 64, max_seq_len), the range hint of its own decode step.  Passes fill in caller order, so a slot's
+ * rows ascend over (pass, position) and there are ceil(rows / cap) passes; inside a pass rows are ordered by hint, stably.
+ * NANO_HIP_EINVAL: null segs with n_segs > 0, cap or max_seq_len of 0, reserved != 0, two segments with the same slot, positions beyond
+ * max_seq_len. */
+int nano_hip_rows_plan(const NanoHipRowSeg *segs, uint32_t n_segs, uint32_t cap, uint32_t max_seq_len,
+                       uint32_t *row_pass, uint32_t *row_index, uint32_t *row_hint, uint32_t *n_passes);
+/* Device-free: 1 when a contiguous cache of these dimensions can be indexed by a row map (a slot's n_layer x max_seq_len rows counted in
+ * 32 bits, a layer of one slot within a 32-bit byte offset), else 0.  The paged pool is checked when the model is created. */
+int nano_hip_rows_addressable(uint32_t n_layer, uint32_t max_seq_len, uint32_t kv_dim, uint32_t elem_bytes);
+
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words
  * 6 / 7.  Attaching enables the module; nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.

@@ -231,6 +231,13 @@ def lib() -> C.CDLL:
     fn("nano_hip_kv_fork", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32])
     fn("nano_hip_kv_sharing", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)])
     fn("nano_prefill_shared", C.c_int, [vp, u32p, C.c_uint32, C.c_uint32])
+    # ragged steps.  (Declared where present: NANO_LIB may name an older build, loaded to be measured against this one.)
+    for name, args in (("nano_hip_step_rows", [vp, vp, C.c_uint32, vp, vp]),
+                       ("nano_hip_rows_plan", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]),
+                       ("nano_hip_rows_addressable", [C.c_uint32] * 4),
+                       ("nano_prefill_batch", [vp, vp, u32p, C.c_uint32, vp])):
+        if hasattr(L, name) or not os.environ.get("NANO_LIB"):
+            fn(name, C.c_int, args)
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_set_fusion", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_debug_fault", C.c_int, [vp, C.c_uint32])
@@ -244,6 +251,26 @@ def lib() -> C.CDLL:
 def check(rc: int):
     if rc != 0:
         raise NanoHipError(f"nano_hip error {rc}: {lib().nano_hip_last_error().decode(errors='replace')}")
+
+
+def row_segs(segs) -> np.ndarray:
+    """(slot, pos0, count[, reserved]) rows as the NanoHipRowSeg array the library reads: uint32 [n][4]"""
+    s = np.zeros((len(segs), 4), np.uint32)
+    for i, g in enumerate(segs):
+        s[i, :len(g)] = g
+    return s
+
+
+def rows_plan(segs, cap: int, max_seq_len: int):
+    """nano_hip_rows_plan (device-free): how a ragged step cuts its rows into passes of at most cap rows.  Returns
+    (row_pass, row_index, row_hint, n_passes), the arrays per row in caller order."""
+    s = row_segs(segs)
+    rows = int(s[:, 2].astype(np.uint64).sum()) if s.size else 0
+    rows = min(rows, len(segs) * max_seq_len)          # (no plan has more; a refused list may claim any number)
+    rp, ri, rh = (np.zeros(max(rows, 1), np.uint32) for _ in range(3))
+    n = C.c_uint32(0)
+    check(lib().nano_hip_rows_plan(s.ctypes.data if s.size else None, s.shape[0], cap, max_seq_len, rp.ctypes.data, ri.ctypes.data, rh.ctypes.data, C.byref(n)))
+    return rp[:rows], ri[:rows], rh[:rows], int(n.value)
 
 
 def last_error() -> str:
@@ -397,6 +424,23 @@ class DeviceModel:
     def prefill_chunk_tokens(self) -> int:
         """Prompt tokens prefill() feeds per weight read in the model's current mode (64 | 8; strict / exact mode: 1)."""
         return int(lib().nano_hip_prefill_chunk_tokens(self.h))
+
+    def step_rows(self, segs: Sequence[Sequence[int]], tokens: Sequence[int], want_argmax: bool = False) -> Optional[np.ndarray]:
+        """A ragged step (nano_hip_step_rows): segs = (slot, pos0, count) triples, tokens = their ids, segment after segment.  Each
+        slot's K / V rows are those of prefill() per segment; want_argmax: returns every row's arg-max, caller order (verify_draft's)."""
+        s = row_segs(segs)
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        rows = int(s[:, 2].sum()) if s.size else 0
+        if t.size != rows:
+            raise ValueError(f"{rows} rows but {t.size} tokens")
+        out = np.zeros(max(rows, 1), np.uint32) if want_argmax else None
+        check(lib().nano_hip_step_rows(self.h, s.ctypes.data if s.size else None, s.shape[0], t.ctypes.data if t.size else None,
+                                       out.ctypes.data if want_argmax else None))
+        return out[:rows] if want_argmax else None
+
+    def rows_plan(self, segs: Sequence[Sequence[int]], max_seq_len: int):
+        """How step_rows() cuts these segments in the model's current mode: rows_plan(segs, prefill_chunk_tokens(), max_seq_len)."""
+        return rows_plan(segs, self.prefill_chunk_tokens(), max_seq_len)
 
     def forward_sample(self, token: int, pos: int, history: Sequence[int], repetition_penalty: float, temperature: float,
                        top_p: float, coin: float) -> NanoHipSample:
@@ -1047,6 +1091,16 @@ class Engine:
         """nano_prefill_shared: ingest the prefix once per device and make it positions 0..len(prefix)-1 of sequences 0..batch-1."""
         t = np.ascontiguousarray(prefix, np.uint32).reshape(-1)
         check(self.L.nano_prefill_shared(self.ctx, t, t.size, batch))
+
+    def prefill_batch(self, prompts: Sequence[Sequence[int]], want_first_ids: bool = True) -> Optional[np.ndarray]:
+        """nano_prefill_batch: sequence i ingests prompts[i] from position 0, all in one ragged step per device; returns first_ids
+        (the arg-max behind each prompt's last token), or None."""
+        ps = [np.ascontiguousarray(p, np.uint32).reshape(-1) for p in prompts]
+        ptrs = (C.c_void_p * len(ps))(*[p.ctypes.data if p.size else None for p in ps])
+        n = np.array([p.size for p in ps], np.uint32)
+        first = np.zeros(max(len(ps), 1), np.uint32) if want_first_ids else None
+        check(self.L.nano_prefill_batch(self.ctx, ptrs, n, len(ps), first.ctypes.data if want_first_ids else None))
+        return first[:len(ps)] if want_first_ids else None
 
     def forward_batch_sample(self, tokens: Sequence[int], pos: Sequence[int], samplers, histories) -> np.ndarray:
         """nano_forward_batch_sample: one decode step of B sequences, sequence i sampled with samplers[i] (from build_sampler)

@@ -34,8 +34,10 @@ static hipError_t launch_mode_kv(const AttnArgs &a_in, const AttnPlan &p, uint32
     constexpr bool CAN16 = KVH && QV % 4 == 0;
     const bool w16 = CAN16 && p.w16;
     const bool np4 = p.npt == 4u;
-#define ATTN_GO3(KVM_, NP_, PG_) do { if constexpr (CAN16) { if (w16) { hipLaunchKernelGGL((attention_kernel<LPR, QV, KVM_, MODE, KVH, PG_, NP_, CAN16>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); break; } } \
-                         hipLaunchKernelGGL((attention_kernel<LPR, QV, KVM_, MODE, KVH, PG_, NP_, false>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); } while (0)
+    // (a ragged step's launches -- a.row_slot -- run the attention_rows_kernel instantiation of the same plan)
+#define ATTN_GO4(K_, KVM_, NP_, PG_) do { if constexpr (CAN16) { if (w16) { hipLaunchKernelGGL((K_<LPR, QV, KVM_, MODE, KVH, PG_, NP_, CAN16>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); break; } } \
+                         hipLaunchKernelGGL((K_<LPR, QV, KVM_, MODE, KVH, PG_, NP_, false>), dim3(a.n_head / KVM_, nb, a.nsplit), dim3(256), lds_for(KVM_), st, a); } while (0)
+#define ATTN_GO3(KVM_, NP_, PG_) do { if (a.row_slot) ATTN_GO4(attention_rows_kernel, KVM_, NP_, PG_); else ATTN_GO4(attention_kernel, KVM_, NP_, PG_); } while (0)
 #define ATTN_GO2(KVM_, NP_) do { if (p.paged) ATTN_GO3(KVM_, NP_, true); else ATTN_GO3(KVM_, NP_, false); } while (0)
 #define ATTN_GO(KVM_) do { if (np4) ATTN_GO2(KVM_, 4); else ATTN_GO2(KVM_, NP); } while (0)
     if (p.kvm == 4) {
@@ -45,6 +47,7 @@ static hipError_t launch_mode_kv(const AttnArgs &a_in, const AttnPlan &p, uint32
 #undef ATTN_GO
 #undef ATTN_GO2
 #undef ATTN_GO3
+#undef ATTN_GO4
     return hipGetLastError();
 }
 template <int LPR, int QV, int MODE>

@@ -160,10 +160,15 @@ constexpr int NP = 2;            // timestep blocks a workgroup keeps in flight 
 // workgroups store write-through (hh.buf: q at 0, k at hh.base[1], v at hh.base[2]; tag = hand_tag, the epoch of this step and layer --
 // device_common.h): one sweep per wave until every tag matches, the values go through LDS into the registers the loads used to fill.
 // A workgroup that gives up (bounded wait) reports it and stores NOTHING: no k row, no output (round-5 advice).
-template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16, bool FUSE>
+// RAGGED (attention_rows_kernel; nano_hip_step_rows): row b's cache base and page-table row are those of KV slot a.row_slot[b]
+// (kernels.h AttnArgs::row_slot), and an FP32 cache takes its fresh v row from a.vraw as the FP16 cache does (stored next to k; the
+// timestep loop still reads it from the cache: the prep_only pass of the step stored it).  false: nothing of this is compiled in.
+template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16, bool FUSE, bool RAGGED = false>
 __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char *smem, const uint32_t grp, const uint32_t b, const uint32_t split,
                                                const SlabHand &hh, const uint32_t hand_tag = 0u, const uint32_t hand_wait16 = 0u) {
     static_assert(!W16 || (KVH && QV % 4 == 0), "16-byte FP16 loads: two float4 slots per load");
+    static_assert(!RAGGED || !FUSE, "the fused one-sequence launches have no row map");
+    constexpr bool VRAW = KVH || RAGGED;                       // the fresh v row may arrive in a.vraw and be stored by this kernel
     static_assert(!FUSE || (((MODE == 1 && LPR * QV * 4 == 128) || MODE == 2) && KVM == 1 && !KVH && !PG && LPR * QV * 4 <= 128),
                   "the fused launch: Qwen3 decode at head_dim 128, or the plain decode mode (no q/k norm, adjacent-pair RoPE: Nano) at head_dim <= 128; FP32 contiguous cache");
     constexpr int R = 256 / LPR;                 // timesteps per block
@@ -227,9 +232,11 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     constexpr bool paged = PG;                                 // paged KV cache: rows are reached through the sequence's page table
     uint32_t prow_ld = 0u;                                     // pool row of position pos
     if constexpr (PG) prow_ld = a.kvrow[b];
+    uint32_t slot_b = b;                                       // the KV slot of row b
+    if constexpr (RAGGED) slot_b = a.row_slot[b];
     // ---- 1. issue every load --------------------------------------------------------------------------------
     constexpr uint32_t ESZ = KVH ? 2u : 4u;                    // bytes per cache element
-    const size_t slot_rows = paged ? (size_t)a.layer * a.pool_rows : (size_t)b * a.cache_bstride_rows + (size_t)a.layer * a.S;
+    const size_t slot_rows = paged ? (size_t)a.layer * a.pool_rows : (size_t)slot_b * a.cache_bstride_rows + (size_t)a.layer * a.S;
     // start of this KV head's rows, in the cache's own element size (typed float* for the FP32 path's arithmetic)
     const float *kc = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.kcache) + (slot_rows * a.kv_dim + (size_t)g * hd) * ESZ);
     const float *vc = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.vcache) + (slot_rows * a.kv_dim + (size_t)g * hd) * ESZ);
@@ -260,7 +267,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     const __amdgpu_buffer_rsrc_t rq = mkrsrc(a.q + (size_t)b * a.q_dim, a.q_dim * 4u);
     const __amdgpu_buffer_rsrc_t rkr = mkrsrc(fresh_k ? a.kraw + (size_t)b * a.kv_dim : nullptr, fresh_k ? a.kv_dim * 4u : 0u);
     // FP16 cache: the QKV GEMV leaves the fresh v row in scratch (FP32) and this kernel rounds and stores it next to k
-    const bool fresh_v = KVH && a.vraw != nullptr;
+    const bool fresh_v = VRAW && a.vraw != nullptr;
     const __amdgpu_buffer_rsrc_t rvr = mkrsrc(fresh_v ? a.vraw + (size_t)b * a.kv_dim : nullptr, fresh_v ? a.kv_dim * 4u : 0u);
     const __amdgpu_buffer_rsrc_t rqn = mkrsrc(a.q_norm, has_norm ? hd * 4u : 0u);
     const __amdgpu_buffer_rsrc_t rkn = mkrsrc(a.k_norm, has_norm ? hd * 4u : 0u);
@@ -290,7 +297,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
                 }
             }
         }
-        if constexpr (KVH) {                                    // FP16 cache: every lane keeps the fresh v row (it is not in the cache yet)
+        if constexpr (VRAW) {                                   // FP16 cache: every lane keeps the fresh v row (it is not in the cache yet)
 #pragma unroll
             for (int q = 0; q < QV; q++) { const uint32_t f = fidx(q); vfresh[q] = bload_f4(rvr, (f * 4u < hd) ? g * hd * 4u + f * 16u : OOB); }
         }
@@ -304,7 +311,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
 #pragma unroll
                 for (int m = 0; m < KVM; m++) qv[m][q] = bload_f4(rq, fo == OOB ? OOB : (h0 + m) * hd * 4u + fo);
                 kfresh[q] = bload_f4(rkr, fo == OOB ? OOB : g * hd * 4u + fo);
-                if (KVH) vfresh[q] = bload_f4(rvr, fo == OOB ? OOB : g * hd * 4u + fo);
+                if (VRAW) vfresh[q] = bload_f4(rvr, fo == OOB ? OOB : g * hd * 4u + fo);
             }
             if (MODE == 1) {
                 qnw[q] = bload_f4(rqn, fo); knw[q] = bload_f4(rkn, fo);
@@ -358,7 +365,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
                 const uint32_t blk = tb >> 6;
                 uint32_t rb = 0xffffffffu;
                 if (blk < a.pt_stride && tb < range_hint) {                // wave-uniform: a SCALAR load (a vector load here would have to wait for
-                    const uint64_t pa = reinterpret_cast<uint64_t>(a.pt_rows + (size_t)b * a.pt_bstride + blk);   // every K / V load issued before it -- vmcnt counts in order)
+                    const uint64_t pa = reinterpret_cast<uint64_t>(a.pt_rows + (RAGGED ? (size_t)slot_b * a.pt_stride : (size_t)b * a.pt_bstride) + blk);   // every K / V load issued before it -- vmcnt counts in order)
                     const uint64_t pu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa);   // (readfirstlane returns int: no sign extension into the high word)
                     asm volatile("s_nop 4\n\ts_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rb) : "s"(pu) : "memory");
                 }
@@ -489,7 +496,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
 #pragma unroll
                 for (int q = 0; q < QV; q++) {
                     const uint32_t f = fidx(q);
-                    if (f * 4u < hd) { kv_store4<KVH>(krow, 4u * f, sv[q]); if (KVH && fresh_v) kv_store4<KVH>(vrow, 4u * f, kv_round<KVH>(vfresh[q])); }
+                    if (f * 4u < hd) { kv_store4<KVH>(krow, 4u * f, sv[q]); if (VRAW && fresh_v) kv_store4<KVH>(vrow, 4u * f, kv_round<KVH>(vfresh[q])); }
                 }
             }
         }
@@ -563,7 +570,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
 #pragma unroll
             for (int q = 0; q < QV; q++) {
                 const uint32_t f = fidx(q);
-                if (f * 4u < hd) { kv_store4<KVH>(krow, 4u * f, kfresh[q]); if (KVH && fresh_v) kv_store4<KVH>(vrow, 4u * f, vfresh[q]); }
+                if (f * 4u < hd) { kv_store4<KVH>(krow, 4u * f, kfresh[q]); if (VRAW && fresh_v) kv_store4<KVH>(vrow, 4u * f, vfresh[q]); }
             }
         }
         if (a.prep_only) return;                                  // batched prefill, pass 1: the k row is all that was wanted
@@ -617,7 +624,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
             }
         }
     }
-    if constexpr (KVH) {                                          // generic path: the fresh v row straight from scratch, rounded, stored by split 0
+    if constexpr (VRAW) {                                         // generic path: the fresh v row straight from scratch, rounded, stored by split 0
 #pragma unroll
         for (int q = 0; q < QV; q++) {
             const uint32_t f = fidx(q);
@@ -806,6 +813,12 @@ template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     attention_body<LPR, QV, KVM, MODE, KVH, PG, NPT, W16, false>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z, SlabHand{});
+}
+// the same body with the row -> slot map of a ragged step (AttnArgs::row_slot != nullptr)
+template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16>
+__global__ __launch_bounds__(256) void attention_rows_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    attention_body<LPR, QV, KVM, MODE, KVH, PG, NPT, W16, false, true>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z, SlabHand{});
 }
 
 

@@ -68,7 +68,7 @@ static void destroy(NanoHipModel *m) {
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
                     m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->pf_stage,
-                    m->score.logits, m->score.part, m->score.targets, m->score.rows, m->score.stage, m->score.out };
+                    m->score.logits, m->score.part, m->score.targets, m->score.rows, m->score.stage, m->score.out, m->rows.stage, m->rows.vraw };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
     for (void *p : host) if (p) (void)hipHostFree(p);

@@ -5,6 +5,7 @@
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
 //   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
+//   backend_rows.hip     ragged steps: rows of several KV slots in one pass (the planner, the entry point)
 //   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
 #pragma once
 #include <math.h>
@@ -111,6 +112,15 @@ struct NanoHipModel {
         uint32_t *h_rec = nullptr;                        // pinned: the record of the last step
         bool graph = true;                                // verify chunks of the loop replay a graph per (K, range bucket); NANO_LOOKUP_GRAPH=0: eager
     } lk;
+    // ragged steps (nano_hip_step_rows, backend_rows.hip): rows that each carry their own (slot, position)
+    struct Rows {
+        bool on = false;                                  // the pass being queued is ragged (with m->pf: every row splits as its own decode step)
+        const uint32_t *row_slot = nullptr;               // device [nb]: the KV slot of each row of the pass
+        struct Group { uint32_t row0, n, hint; };         // a contiguous run of the pass's rows that share a range hint: one attention launch
+        std::vector<Group> groups;
+        uint32_t *stage = nullptr; uint32_t cap = 0;      // the call's tokens | positions | slots | row arg-maxes on the device, pass after pass (4 x cap words)
+        float *vraw = nullptr;                            // [Bs][KD] fresh v rows of a pass on the contiguous FP32 cache (the FP16 cache has m->vraw)
+    } rows;
     uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
     float *h_logits = nullptr;
     std::map<uint64_t, hipGraphExec_t> graphs;

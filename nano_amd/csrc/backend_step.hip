@@ -119,6 +119,38 @@ static uint32_t xba_nsplit(const NanoHipModel *m, uint32_t nb, uint32_t range_hi
     const uint32_t ns = step_nsplit(m, nb, range_hint);
     return (ns > 1 && !wo_takes_parts(m, nb, ns)) ? 1u : ns;
 }
+// The attention launches of one layer of a ragged pass (m->rows; `a` = the layer's arguments as enqueue_step built them for all nb rows).
+// Pass 1 over ALL rows finishes every k row -- and the v row, from scratch, on the FP16 and the contiguous FP32 cache -- so that every
+// row of the pass finds the rows of the earlier positions of its slot in the cache, whichever group they belong to.  Then one launch per
+// group of rows that share a range hint, with that bucket's split count and hint -- the launch a prefill chunk of the bucket gets -- on
+// the group's rows of every row-indexed array, and the combine launch where the range is split.  The groups run one after the other on
+// the stream, so their partials may lie anywhere in the partial buffers.
+static hipError_t enqueue_rows_attention(NanoHipModel *m, AttnArgs a, uint32_t nb, bool wo_frag) {
+    const NanoModelDesc &d = m->d;
+    const uint32_t QD = m->QD, KD = m->KD;
+    hipError_t e;
+    a.row_slot = m->rows.row_slot;
+    a.xf_out = nullptr; a.xsf_out = nullptr; a.stamps = nullptr;
+    if (!m->kv_half && !m->kv.paged) a.vraw = m->rows.vraw;
+    AttnArgs p = a;
+    p.prep_only = 1; p.nsplit = 1; p.range_hint = m->rows.groups.front().hint;    // (nothing attended: the fewest workgroups, the smallest range)
+    if ((e = launch_attention(p, nb, m->st)) != hipSuccess) return e;
+    for (const NanoHipModel::Rows::Group &g : m->rows.groups) {
+        AttnArgs b = a;
+        const uint32_t ns = step_nsplit(m, 1, g.hint);
+        const size_t r0 = g.row0;
+        b.nsplit = ns; b.range_hint = g.hint;
+        b.q += r0 * QD; b.kraw += r0 * KD; b.pos += r0; b.row_slot += r0;
+        if (b.rope_cur) b.rope_cur += r0 * 2 * (m->hd / 2);
+        if (b.kvrow) b.kvrow += r0;
+        b.vraw = m->kv_half ? m->vraw + r0 * KD : nullptr;                          // (FP32: pass 1 stored the row, the cache has it)
+        b.out += r0 * ns * QD; b.ml += r0 * d.n_head * ns * 2; b.xba_out += r0 * QD;
+        if (wo_frag && ns == 1) { b.xf_out = m->gq; b.xsf_out = m->gxs; }           // (one group: row0 = 0)
+        if ((e = launch_attention(b, g.n, m->st)) != hipSuccess) return e;
+        if (ns > 1 && (e = launch_attn_combine_tokens(b.out, b.ml, b.xba_out, d.n_head, m->hd, ns, g.n, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 // range_hint: host-side upper bound of the attended range of every sequence (a multiple of 64, <= S)
 hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint) {
     const NanoModelDesc &d = m->d;
@@ -127,6 +159,11 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
     // Batched prefill splits every token's attention exactly as that token's own decode step would (chunks start on
     // multiples of the 64-position bucket, so one range_hint covers them) and combines with a kernel of its own: the KV
     // rows and the following logits then carry the bits of token-by-token ingestion.
+    // A ragged pass (m->rows.on, with m->pf; backend_rows.hip): rows of several slots and range buckets.  Its rows come sorted into groups
+    // that share a range hint; each group gets the attention launch (and combine launch) of a prefill chunk of that bucket, so every row
+    // still splits as its own decode step.  range_hint is the last group's (the largest), nsplit below the largest split count.
+    const bool ragged = m->rows.on;
+    const size_t ngroups = ragged ? m->rows.groups.size() : 1u;
     const uint32_t nsplit = m->pf ? step_nsplit(m, 1, range_hint) : step_nsplit(m, nb, range_hint);
     // Does this step's Wo launch go to the batched GEMM (plain activations only), or is the range split wider than the Wo
     // GEMV's prologue combines?  Then a split attention is combined by a kernel of its own (as in batched prefill) -- for
@@ -137,15 +174,19 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
     m->nsplit = pf_combine ? 1 : nsplit;
     // Single-split attention (or the combine kernel) of a step whose Wo launch goes to the batched GEMM: that kernel writes
     // Wo's quantized input itself (Q80 groups of 64 inside a head, fragment order) -- one quantizer launch less per layer.
-    const bool wo_frag = wo_gemm && d.group_size == 64 && m->hd % 64 == 0;
+    // (a ragged pass of several groups: fragment rows are 16-token tiles of the WHOLE pass, a group starts at any row -- its launches
+    // write plain xba and the Wo launch runs its quantizer, which by definition makes the same fragments)
+    const bool wo_frag = wo_gemm && d.group_size == 64 && m->hd % 64 == 0 && ngroups == 1;
     EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
                   m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0, nullptr, nullptr, 0, 0 };
     // paged KV cache: the step's sequences are slots 0..nb-1 (batched prefill: every token is a position of slot pf_slot); the
     // embed kernel stages each one's pool row next to its RoPE row, the QKV launch and the attention kernel write there
-    const uint32_t *pt_base = m->kv.paged ? m->kv.pt + (m->pf ? (size_t)m->pf_slot * m->kv.pt_stride : 0) : nullptr;
+    // (a ragged pass: row b is a position of slot row_slot[b] -- the kernels index the whole table / cache by it)
+    const uint32_t *pt_base = m->kv.paged ? m->kv.pt + ((m->pf && !ragged) ? (size_t)m->pf_slot * m->kv.pt_stride : 0) : nullptr;
     const uint32_t pt_bstride = (m->kv.paged && !m->pf) ? m->kv.pt_stride : 0u;
-    const KvRows kv{ m, m->pf ? m->pf_slot : 0u, m->pf };
+    const KvRows kv{ m, (m->pf && !ragged) ? m->pf_slot : 0u, m->pf && !ragged };
     if (m->kv.paged) { ea.pt_rows = pt_base; ea.kvrow = m->kv.kvrow; ea.pt_bstride = pt_bstride; ea.pt_entries = m->kv.pt_stride; }
+    if (ragged) ea.row_slot = m->rows.row_slot;
     ea.tick = m->ho.tick;                                                       // the step's first kernel opens a new hand-off epoch
     if (!(m->skip_embed && mode == MODE_LOOP) && (e = launch_embed(ea, nb, m->st)) != hipSuccess) return e;
 
@@ -187,18 +228,22 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
                 la_.pos = m->pos; la_.E = E; la_.KD = KD; la_.rank = m->lora_rank; la_.alpha = m->lora_alpha;
                 if ((e = launch_lora_qkv(la_, nb, m->st)) != hipSuccess) return e;
             }
-            if (m->pf) {
-                // batched prefill: the nb tokens are consecutive positions of ONE sequence.  Pass 1 finishes every k row
-                // (norm + RoPE + cache write -- paged: into its page -- nothing else) so that pass 2 finds the rows of the earlier
-                // tokens of the chunk in the cache; pass 2 is the ordinary decode attention per token (it recomputes its own k row).
-                a.prep_only = 1;
+            if (ragged) {           // pass 1 over all rows, then a launch (and a combine launch) per range bucket
+                if ((e = enqueue_rows_attention(m, a, nb, wo_frag)) != hipSuccess) return e;
+            } else {
+                if (m->pf) {
+                    // batched prefill: the nb tokens are consecutive positions of ONE sequence.  Pass 1 finishes every k row
+                    // (norm + RoPE + cache write -- paged: into its page -- nothing else) so that pass 2 finds the rows of the earlier
+                    // tokens of the chunk in the cache; pass 2 is the ordinary decode attention per token (it recomputes its own k row).
+                    a.prep_only = 1;
+                    if ((e = launch_attention(a, nb, m->st)) != hipSuccess) return e;
+                    a.prep_only = 0;
+                }
+                a.stamps = next_stamps(m, 2);
                 if ((e = launch_attention(a, nb, m->st)) != hipSuccess) return e;
-                a.prep_only = 0;
             }
-            a.stamps = next_stamps(m, 2);
-            if ((e = launch_attention(a, nb, m->st)) != hipSuccess) return e;
         }
-        if (pf_combine && (e = launch_attn_combine_tokens(m->attn_part, m->attn_ml, m->xba, d.n_head, m->hd, nsplit, nb, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
+        if (pf_combine && !ragged && (e = launch_attn_combine_tokens(m->attn_part, m->attn_ml, m->xba, d.n_head, m->hd, nsplit, nb, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
         {   // x += Wo . xba   reference infer.c:885-908
             if (m->lora_on) {       // o1 = (alpha/rank) B_o (A_o xba), added by the Wo epilogue: x += (Wo xba + o1)   infer.c:898-908
                 LoraArgs la_{};

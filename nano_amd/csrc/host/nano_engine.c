@@ -538,6 +538,36 @@ int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t 
     return NANO_HIP_OK;
 }
 
+/* `batch` prompts at once: each replica gets the prompts of its share (sequence i in slot i / G of replica i mod G, as in
+ * nano_forward_batch) as the segments of ONE ragged step, and the arg-max behind each prompt's last row becomes first_ids[i]. */
+int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const uint32_t *n_tokens, uint32_t batch, uint32_t *first_ids) {
+    la_clear(ctx ? reg_entry(ctx->llm) : NULL);
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || !prompts || !n_tokens || batch == 0) return NANO_HIP_EINVAL;
+    const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
+    if (batch > NANO_MAX_BATCH * G) return NANO_HIP_EINVAL;
+    for (uint32_t i = 0; i < batch; i++) if (n_tokens[i] && !prompts[i]) return NANO_HIP_EINVAL;
+    int rc = NANO_HIP_OK;
+    for (uint32_t r = 0; r < G && r < batch && rc == NANO_HIP_OK; r++) {
+        NanoHipModel *dev = me->n_replica > 0 ? me->replica[r] : me->dev;
+        NanoHipRowSeg segs[NANO_MAX_BATCH];
+        uint32_t n_segs = 0;
+        size_t rows = 0;
+        for (uint32_t i = r; i < batch; i += G) { segs[n_segs++] = (NanoHipRowSeg){ i / G, 0, n_tokens[i], 0 }; rows += n_tokens[i]; }
+        lora_select(dev, ctx->lora);
+        if (!rows) continue;
+        uint32_t *tok = (uint32_t *)malloc(rows * sizeof *tok), *amax = first_ids ? (uint32_t *)malloc(rows * sizeof *amax) : NULL;
+        if (!tok || (first_ids && !amax)) { free(tok); free(amax); return NANO_HIP_ENOMEM; }
+        size_t o = 0;
+        for (uint32_t i = r; i < batch; i += G) { if (n_tokens[i]) memcpy(tok + o, prompts[i], (size_t)n_tokens[i] * sizeof *tok); o += n_tokens[i]; }
+        rc = nano_hip_step_rows(dev, segs, n_segs, tok, amax);
+        o = 0;
+        for (uint32_t i = r; i < batch; i += G) { o += n_tokens[i]; if (rc == NANO_HIP_OK && first_ids && n_tokens[i]) first_ids[i] = amax[o - 1]; }
+        free(tok); free(amax);
+    }
+    return rc;
+}
+
 /* =====================================================================================================
  * sampling (reference infer/infer.c:1026-1127; RNG infer/utils.c:959-970)
  * =================================================================================================== */

@@ -282,6 +282,13 @@ struct AttnArgs {
     uint32_t pool_rows, _pad6;      // rows of one layer plane = pages * 64
     uint32_t *err;          // sticky error word (as GemvArgs::err)
     unsigned long long *stamps;   // measurement builds only (NANO_STAMPS): per-workgroup phase stamps, or nullptr
+    // RAGGED steps (nano_hip_step_rows): row b is position pos[b] of KV slot row_slot[b] -- its cache base is row_slot[b] *
+    // cache_bstride_rows rows into kcache / vcache (paged: its table row pt_rows + row_slot[b] * pt_stride; pt_bstride is not read);
+    // q / kraw / vraw / out / ml / xba_out / pos / kvrow / rope_cur stay indexed by the row.  On an FP32 cache vraw, where set, is stored
+    // to the row's v row like the FP16 cache's.  nullptr: the two fixed maps above.  Set: launch_attention() runs the attention_rows_kernel
+    // instantiations (the same body with the map compiled in); the attention_kernel ones never read the field.  Last in the block: no
+    // other field's kernarg offset moved.
+    const uint32_t *row_slot;
 };
 hipError_t launch_attention(const AttnArgs &a, uint32_t nb, hipStream_t st);
 // the attention_kernel<LPR, QV, KVM, MODE, KVH, PG, NPT, W16> launch_attention() runs for `a` and nb sequences, and the workgroup order
@@ -397,6 +404,9 @@ struct EmbedArgs {
     const uint32_t *pt_rows; uint32_t *kvrow; uint32_t pt_bstride, pt_entries;   // pt_entries: table entries per slot (a position beyond them stages nothing)
     // the step's first kernel also advances the model's hand-off epoch (device_common.h: tick[0] += 1, workgroup 0), or nullptr
     uint32_t *tick;
+    // ragged steps: row b belongs to KV slot row_slot[b] -- kvrow[b] = pt_rows[row_slot[b] * pt_entries + pos[b] / 64] + pos[b] % 64
+    // (pt_bstride is not read); nullptr: row b is slot b (x pt_bstride)
+    const uint32_t *row_slot;
 };
 hipError_t launch_embed(const EmbedArgs &a, uint32_t nb, hipStream_t st);
 

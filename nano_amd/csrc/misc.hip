@@ -19,7 +19,7 @@ __device__ __forceinline__ void embed_row(const EmbedArgs &a, uint32_t b, uint32
     // the position AFTER the last step too -- with max_seq_len a multiple of 64 that position's block lies one entry past the slot's row
     // of the table (round-3 advice: a device read out of bounds; the value was never used)
     if (stage_pos && a.kvrow && threadIdx.x == 0 && (p >> 6) < a.pt_entries)
-        a.kvrow[b] = a.pt_rows[(size_t)b * a.pt_bstride + (p >> 6)] + (p & 63u);
+        a.kvrow[b] = a.pt_rows[(a.row_slot ? (size_t)a.row_slot[b] * a.pt_entries : (size_t)b * a.pt_bstride) + (p >> 6)] + (p & 63u);   // (ragged steps: the row's own slot)
     if (stage_pos && a.rope_cur) {
         for (uint32_t i = threadIdx.x; i < a.half; i += blockDim.x) {
             a.rope_cur[(size_t)b * 2 * a.half + i] = a.rope_cos[(size_t)p * a.half + i];
