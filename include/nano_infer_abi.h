@@ -238,6 +238,18 @@ int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const 
  * prefill whose logits never reach the host (nano_hip_prefill_score, nano_mi355x.h); perplexity = exp(nll_sum / (n_ids - 1)).
  * Uses the context's own device, not its replicas; n_ids < 2 scores nothing and returns 0.  Returns 0 or a NANO_HIP_E* code. */
 int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum);
+/* nano_score_ids plus the alternatives the model weighed at every scored position: top_ids / top_logprobs hold (n_ids - 1) * k entries
+ * (either may be NULL, not both), position after position, most probable first -- the `top_logprobs` of a serving front end, selected on the
+ * device (nano_hip_prefill_score_topk, nano_mi355x.h: order, ties and bits are stated there).  1 <= k <= min(32, vocab), else
+ * NANO_HIP_EINVAL.  logprobs, argmax and *nll_sum are nano_score_ids's, bit for bit. */
+int nano_score_ids_topk(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, uint32_t k, float *logprobs, uint32_t *argmax,
+                        uint32_t *top_ids, float *top_logprobs, double *nll_sum);
+/* One decode step for `batch` sequences as nano_forward_batch (same sequence -> (replica, slot) map), handing back per sequence its k
+ * most probable next ids and their log-probs (batch * k entries each; either may be NULL, not both) and its arg-max (may be NULL) instead
+ * of batch * vocab logits (nano_hip_forward_topk).  With replicas, each replica's share is served by its own call, one replica after
+ * another (not concurrently, unlike nano_forward_batch).  1 <= k <= min(32, vocab).  Returns 0 or a negative NANO_HIP_E* code. */
+int nano_forward_batch_topk(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t k,
+                            uint32_t *top_ids, float *top_logprobs, uint32_t *argmax);
 /* Replicas of the context's model on the listed further GPUs of the node, in this process: nano_forward_batch then serves
  * sequence i from replica i mod (1 + n_devices) (replica 0 = the context's own device) and the replicas decode their
  * shares concurrently -- independent sequences shard trivially, no collective.  The one-process-per-GPU

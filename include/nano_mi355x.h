@@ -196,6 +196,42 @@ int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *token
 int nano_hip_op_score_rows(int device, const float *logits, uint32_t rows, uint32_t V,
                            const uint32_t *targets, NanoHipTokenScore *out);
 
+/* ---- top-k alternatives: the k most probable tokens of a row, with their log-probs (topk.hip) ---------------------
+ * For a row of V float32 logits and 1 <= k <= min(NANO_TOPK_MAX, V) the row's k entries, selected on the device behind the
+ * statistics above (the logits never leave the device):
+ *   order    float comparison, descending; equal floats: the smaller index first.  -0.0f == +0.0f is such a tie.  Denormals
+ *            compare by value (nothing is flushed).  -inf is a float like any other: a row with fewer than k finite logits goes
+ *            on with its -inf entries in index order, logprob -inf.
+ *   so       entry j is the token whose NanoHipTokenScore.rank would be j; top[0].token is the record's argmax.
+ *   logit    the stored float, bit for bit (a -0.0f stays -0.0f);  logprob = logit - lse, that one float32 subtraction with the
+ *            lse of the row's score record: a target among the k entries has the record's logprob, bit for bit.
+ * Rows with NaN or +inf, and rows of -inf only, are unspecified, as above.  The selection is exact, so the entries do not depend
+ * on how a prompt is cut into calls, chunks or passes, on the row's index or alignment, or on the launch that produced the logits. */
+#define NANO_TOPK_MAX 32u
+typedef struct NanoHipTopEntry { uint32_t token; float logit; float logprob; } NanoHipTopEntry;   /* 12 bytes */
+/* In the three model entry points below k == 0 means scores only (top_out may be NULL); k >= 1 requires top_out with rows * k
+ * entries in caller order, and scores_out may then be NULL.  k > NANO_TOPK_MAX, k > vocab, a null top_out with k >= 1, a null
+ * scores_out with k == 0 and a target >= vocab are NANO_HIP_EINVAL before anything is queued.  The selection's scratch is allocated on the
+ * first such call (all or nothing: NANO_HIP_ENOMEM leaves the model usable); callers of the other entry points allocate nothing.
+ *
+ * nano_hip_prefill_score_topk: everything nano_hip_prefill_score does -- same chunks and chunk graphs, same KV rows, same later
+ * outputs, the same score records bit for bit -- plus the k entries of every fed position (top_out[i * k + j]).  The two selection
+ * launches are queued eagerly behind each chunk (strict / exact mode: behind each token's reference-order step). */
+int nano_hip_prefill_score_topk(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
+                                const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out);
+/* One causal decode step of the sequences in slots 0 .. batch-1, queued exactly as nano_hip_forward queues it with logits wanted
+ * (same graphs, same re-issue after a hand-off gave up, strict / exact mode alike) -- but no logits are copied to the host: the
+ * statistics and the selection run on the step's rows on the device and the records come back in one copy behind the call's
+ * wait.  targets (may be NULL: each row's own arg-max) as in nano_hip_prefill_score.  The logits stay where nano_hip_forward
+ * leaves them: nano_hip_read_state(m, i, 4, ...) returns the row the entries of sequence i were taken from. */
+int nano_hip_forward_topk(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                          const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out);
+/* The statistics and the selection alone on caller logits [rows][V] (host pointers; targets and scores_out may be NULL; top_out
+ * [rows][k]).  NANO_HIP_EINVAL before a device is asked for: null logits / top_out, rows, V or k of 0, k > NANO_TOPK_MAX, k > V,
+ * a target >= V. */
+int nano_hip_op_topk_rows(int device, const float *logits, uint32_t rows, uint32_t V, uint32_t k,
+                          const uint32_t *targets, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out);
+
 /* ---- greedy decode with lookup drafts: several ids per weight read (opt-in) -----------------
  * Greedy decode of sequence slot 0 in which a step may be a prefill chunk of K = max_draft + 1 rows: the last id plus a
  * continuation guessed by looking the last ngram_min .. ngram_max ids up in the sequence's own history (longest suffix match, then
@@ -277,6 +313,14 @@ int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uin
  * not offered. */
 typedef struct NanoHipRowSeg { uint32_t slot, pos0, count, reserved; } NanoHipRowSeg;   /* positions pos0 .. pos0+count-1 of `slot` */
 int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out);
+/* The scoring form of a ragged step: everything nano_hip_step_rows promises for the cache, and for every row (caller order, sum(count)
+ * rows) the score record and the k entries that nano_hip_prefill_score_topk returns for the same rows called per segment, bit for
+ * bit.  targets (may be NULL: each row's own arg-max), k, scores_out and top_out as described at nano_hip_prefill_score_topk.  A pass
+ * goes on into the classifier for all its rows and the statistics; the selection's two launches follow it.  Strict and exact mode:
+ * per row a reference-order step with logits, then the statistics and the selection on that row.
+ * NANO_HIP_EINVAL as nano_hip_step_rows, plus the k and target checks. */
+int nano_hip_step_rows_score(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens,
+                             const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out);
 /* Device-free: how nano_hip_step_rows cuts its rows into passes of at most `cap` rows (cap = nano_hip_prefill_chunk_tokens()).  For
  * row r in caller order (all outputs optional, sum(count) words): row_pass[r] = its pass, row_index[r] = its row inside the pass,
  * row_hint[r] = min((pos / 64 + 1) * 64, max_seq_len), the range hint of its own decode step.  Passes fill in caller order, so a slot's

@@ -133,6 +133,17 @@ TOKEN_SCORE_DTYPE = np.dtype([("logprob", "<f4"), ("target_logit", "<f4"), ("max
 assert TOKEN_SCORE_DTYPE.itemsize == C.sizeof(NanoHipTokenScore)
 
 
+class NanoHipTopEntry(C.Structure):
+    """include/nano_mi355x.h NanoHipTopEntry: one of the k most probable tokens of a row (12 bytes)."""
+    _fields_ = [("token", C.c_uint32), ("logit", C.c_float), ("logprob", C.c_float)]
+
+
+# the same record as a numpy structured dtype: the top-k methods return [rows, k] arrays of it, most probable first
+TOP_ENTRY_DTYPE = np.dtype([("token", "<u4"), ("logit", "<f4"), ("logprob", "<f4")])
+assert TOP_ENTRY_DTYPE.itemsize == C.sizeof(NanoHipTopEntry) == 12
+TOPK_MAX = 32                                                          # NANO_TOPK_MAX
+
+
 class NanoHipLookupParams(C.Structure):
     """include/nano_mi355x.h NanoHipLookupParams: greedy decode with lookup drafts (max_steps 0 = no limit; stop_token 0xffffffff = none)."""
     _fields_ = [(n, C.c_uint32) for n in ("max_draft", "ngram_max", "ngram_min", "stop_token", "max_steps")]
@@ -235,7 +246,14 @@ def lib() -> C.CDLL:
     for name, args in (("nano_hip_step_rows", [vp, vp, C.c_uint32, vp, vp]),
                        ("nano_hip_rows_plan", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]),
                        ("nano_hip_rows_addressable", [C.c_uint32] * 4),
-                       ("nano_prefill_batch", [vp, vp, u32p, C.c_uint32, vp])):
+                       ("nano_prefill_batch", [vp, vp, u32p, C.c_uint32, vp]),
+                       # top-k alternatives
+                       ("nano_hip_op_topk_rows", [C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
+                       ("nano_hip_prefill_score_topk", [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]),
+                       ("nano_hip_forward_topk", [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
+                       ("nano_hip_step_rows_score", [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]),
+                       ("nano_score_ids_topk", [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_double)]),
+                       ("nano_forward_batch_topk", [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp])):
         if hasattr(L, name) or not os.environ.get("NANO_LIB"):
             fn(name, C.c_int, args)
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
@@ -400,6 +418,48 @@ class DeviceModel:
         out = np.zeros(t.size, TOKEN_SCORE_DTYPE)
         check(lib().nano_hip_prefill_score(self.h, slot, t.ctypes.data, pos0, t.size, None if g is None else g.ctypes.data, out.ctypes.data))
         return out
+
+    def prefill_score_topk(self, tokens: Sequence[int], k: int, targets: Optional[Sequence[int]] = None, pos0: int = 0, slot: int = 0):
+        """prefill_score() plus the k most probable tokens of every fed position (nano_hip_prefill_score_topk).  Returns (scores
+        TOKEN_SCORE_DTYPE[len(tokens)], top TOP_ENTRY_DTYPE[len(tokens), k], most probable first); k = 0: (scores, None)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        if g is not None and g.size != t.size:
+            raise ValueError(f"{t.size} tokens but {g.size} targets")
+        out = np.zeros(t.size, TOKEN_SCORE_DTYPE)
+        top = np.zeros((t.size, k), TOP_ENTRY_DTYPE) if k else None
+        check(lib().nano_hip_prefill_score_topk(self.h, slot, t.ctypes.data, pos0, t.size, None if g is None else g.ctypes.data, k,
+                                                out.ctypes.data, top.ctypes.data if k else None))
+        return out, top
+
+    def forward_topk(self, tokens: Sequence[int], pos: Sequence[int], k: int, targets: Optional[Sequence[int]] = None):
+        """One causal decode step of slots 0 .. B-1 whose logits stay on the device (nano_hip_forward_topk).  Returns (scores
+        TOKEN_SCORE_DTYPE[B] for targets -- None: each row's own arg-max --, top TOP_ENTRY_DTYPE[B, k]); k = 0: (scores, None)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        if p.size != t.size or (g is not None and g.size != t.size):
+            raise ValueError(f"{t.size} tokens but {p.size} positions / {0 if g is None else g.size} targets")
+        out = np.zeros(t.size, TOKEN_SCORE_DTYPE)
+        top = np.zeros((t.size, k), TOP_ENTRY_DTYPE) if k else None
+        check(lib().nano_hip_forward_topk(self.h, t.ctypes.data, p.ctypes.data, t.size, None if g is None else g.ctypes.data, k,
+                                          out.ctypes.data, top.ctypes.data if k else None))
+        return out, top
+
+    def step_rows_score(self, segs: Sequence[Sequence[int]], tokens: Sequence[int], k: int, targets: Optional[Sequence[int]] = None):
+        """The scoring form of a ragged step (nano_hip_step_rows_score): step_rows() that returns, per row in caller order, what
+        prefill_score_topk() per segment returns: (scores TOKEN_SCORE_DTYPE[rows], top TOP_ENTRY_DTYPE[rows, k]); k = 0: (scores, None)."""
+        s = row_segs(segs)
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        rows = int(s[:, 2].sum()) if s.size else 0
+        if t.size != rows or (g is not None and g.size != rows):
+            raise ValueError(f"{rows} rows but {t.size} tokens / {0 if g is None else g.size} targets")
+        out = np.zeros(max(rows, 1), TOKEN_SCORE_DTYPE)
+        top = np.zeros((max(rows, 1), k), TOP_ENTRY_DTYPE) if k else None
+        check(lib().nano_hip_step_rows_score(self.h, s.ctypes.data if s.size else None, s.shape[0], t.ctypes.data if t.size else None,
+                                             None if g is None else g.ctypes.data, k, out.ctypes.data, top.ctypes.data if k else None))
+        return out[:rows], (top[:rows] if k else None)
 
     def decode_lookup(self, history: Sequence[int], max_new: int, max_draft: int = 7, ngram_max: int = 3, ngram_min: int = 1,
                       stop_token: Optional[int] = None, max_steps: int = 0):
@@ -982,6 +1042,22 @@ def op_score_rows(logits, targets=None, device=0) -> np.ndarray:
     return out
 
 
+def op_topk_rows(logits, k, targets=None, device=0):
+    """The row statistics and the top-k selection alone (nano_hip_op_topk_rows): logits [rows, V] float32, targets [rows] or None.
+    Returns (scores TOKEN_SCORE_DTYPE[rows], top TOP_ENTRY_DTYPE[rows, k], most probable first).  Device only: no host path."""
+    l = np.ascontiguousarray(logits, np.float32)
+    if l.ndim != 2:
+        raise ValueError("logits must be [rows, V]")
+    g = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+    if g is not None and g.size != l.shape[0]:
+        raise ValueError(f"{l.shape[0]} rows but {g.size} targets")
+    out = np.zeros(l.shape[0], TOKEN_SCORE_DTYPE)
+    top = np.zeros((l.shape[0], max(k, 1)), TOP_ENTRY_DTYPE)
+    check(lib().nano_hip_op_topk_rows(device, l.ctypes.data, l.shape[0], l.shape[1], k, None if g is None else g.ctypes.data,
+                                      out.ctypes.data, top.ctypes.data))
+    return out, top
+
+
 def op_lookup_step(history, fed=(), amax=(), *, left, max_draft=7, ngram_max=3, ngram_min=1, stop_token=None, seq_limit=1 << 30, device=0):
     """lookup_step_kernel alone (nano_hip_op_lookup_step): behind a step that fed `fed` and left the row arg-maxes `amax` (both empty: no
     step has run yet).  Returns (record dict of LOOKUP_RECORD_FIELDS, the history with the emitted ids appended, next tokens, next
@@ -1086,6 +1162,23 @@ class Engine:
         lp, am, nll = np.zeros(n, np.float32), np.zeros(n, np.uint32), C.c_double(0.0)
         check(self.L.nano_score_ids(self.ctx, t, t.size, lp.ctypes.data, am.ctypes.data, C.byref(nll)))
         return lp, am, float(nll.value)
+
+    def score_ids_topk(self, ids: Sequence[int], k: int):
+        """nano_score_ids_topk: score_ids() plus (top_ids uint32[n - 1, k], top_logprobs float32[n - 1, k]), most probable first."""
+        t = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        n = max(t.size - 1, 0)
+        lp, am, nll = np.zeros(n, np.float32), np.zeros(n, np.uint32), C.c_double(0.0)
+        ti, tl = np.zeros((n, k), np.uint32), np.zeros((n, k), np.float32)
+        check(self.L.nano_score_ids_topk(self.ctx, t.ctypes.data, t.size, k, lp.ctypes.data, am.ctypes.data, ti.ctypes.data, tl.ctypes.data, C.byref(nll)))
+        return lp, am, float(nll.value), ti, tl
+
+    def forward_batch_topk(self, tokens: Sequence[int], pos: Sequence[int], k: int):
+        """nano_forward_batch_topk: one decode step of B sequences -> (top_ids uint32[B, k], top_logprobs float32[B, k], argmax uint32[B])."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        ti, tl, am = np.zeros((t.size, k), np.uint32), np.zeros((t.size, k), np.float32), np.zeros(t.size, np.uint32)
+        check(self.L.nano_forward_batch_topk(self.ctx, t.ctypes.data, p.ctypes.data, t.size, k, ti.ctypes.data, tl.ctypes.data, am.ctypes.data))
+        return ti, tl, am
 
     def prefill_shared(self, prefix: Sequence[int], batch: int):
         """nano_prefill_shared: ingest the prefix once per device and make it positions 0..len(prefix)-1 of sequences 0..batch-1."""

@@ -74,6 +74,7 @@ static void destroy(NanoHipModel *m) {
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
     lookup_free(m);
+    topk_free(m);
     for (hipEvent_t ev : { m->ev0, m->ev1, m->ev2 }) if (ev) (void)hipEventDestroy(ev);
     if (m->st) (void)hipStreamDestroy(m->st);
     delete m;
@@ -534,10 +535,13 @@ hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t m
 // score (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);
 // out[i] scores the logits of tokens[i] for targets[i] (targets == nullptr: for the row's own arg-max).  Nothing else differs.
 // argmax_out (nano_hip_verify_draft): every chunk goes on into the classifier and the arg-max of all its rows (MODE_VERIFY); argmax_out[i] is row i's.
+// k >= 1 (nano_hip_prefill_score_topk): the selection's two launches (topk.hip) are queued eagerly behind every scored chunk, on score.logits and
+// the chunk's records, before the next chunk overwrites them: the chunk graphs and their keys are nano_hip_prefill_score's.
 int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
-                uint32_t *argmax_out) {
+                uint32_t *argmax_out, uint32_t k, NanoHipTopEntry *top_out) {
     const bool verify = argmax_out != nullptr;
-    if (!m || !tokens || (score && !out)) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (!m || !tokens || (score && !out && !k)) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (k) { if (const int rc = topk_check(m, k, out, top_out)) return rc; }
     if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "slot %u out of range (max_batch %u)", slot, m->maxB);
     if ((uint64_t)pos0 + count > m->S) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed max_seq_len %u", pos0, pos0 + count, m->S);
     if ((uint64_t)pos0 + count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed the model's RoPE table (%u rows = block_size)", pos0, pos0 + count, m->rope_rows);
@@ -554,14 +558,19 @@ int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t
     if (score) {
         if (const int rc = score_scratch(m)) return rc;
         m->score.use_targets = targets != nullptr;
+        if (k) { if (const int rc = topk_scratch(m, count)) return rc; }
         if (targets) HIP_TRY(hipMemcpyAsync(m->score.stage, targets, (size_t)count * 4, hipMemcpyHostToDevice, m->st));      // (a pageable source, like the tokens below)
     }
     // token i's logits are in row 0 of m->logits (strict / exact mode: one reference-order step per token): their statistics
-    auto score_token = [&](uint32_t i) { return enqueue_score_rows(m, m->logits, 1, targets ? m->score.stage + i : nullptr, m->score.out + i); };
+    auto score_token = [&](uint32_t i) {
+        const hipError_t e = enqueue_score_rows(m, m->logits, 1, targets ? m->score.stage + i : nullptr, m->score.out + i);
+        return (e != hipSuccess || !k) ? e : enqueue_topk_rows(m, m->logits, 1, k, m->score.out + i, m->tk.out + (size_t)i * k);
+    };
     // the call's scores: one copy, behind the work queued so far and in front of the call's last wait
     auto scores_back = [&]() {
         if (verify) return hipMemcpyAsync(argmax_out, m->lk.out, (size_t)count * 4, hipMemcpyDeviceToHost, m->st);
-        return score ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess;
+        if (k) { const hipError_t e = hipMemcpyAsync(top_out, m->tk.out, (size_t)count * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost, m->st); if (e != hipSuccess) return e; }
+        return (score && out) ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess;
     };
     // token i's arg-max is in m->amax[0] (strict / exact mode)
     auto amax_token = [&](uint32_t i) { return hipMemcpyAsync(m->lk.out + i, m->amax, 4, hipMemcpyDeviceToDevice, m->st); };
@@ -626,6 +635,7 @@ int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t
         const hipError_t e = enqueue_chunk(m, slot, nb, mode, pos0 + done + nb - 1, replay, verify ? 3u : score ? (targets ? 1u : 2u) : 0u);
         HIP_TRY(e);
         if (score) HIP_TRY(hipMemcpyAsync(m->score.out + done, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
+        if (k) HIP_TRY(enqueue_topk_rows(m, m->score.logits, nb, k, m->score.rows, m->tk.out + (size_t)done * k));
         if (verify) HIP_TRY(hipMemcpyAsync(m->lk.out + done, m->lk.amax, nb * 4, hipMemcpyDeviceToDevice, m->st));
         done += nb;
     }
@@ -639,6 +649,12 @@ extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *
 extern "C" int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
                                       const uint32_t *targets, NanoHipTokenScore *out) {
     return prefill_run(m, slot, tokens, pos0, count, true, targets, out);
+}
+extern "C" int nano_hip_prefill_score_topk(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
+                                           const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (const int rc = topk_check(m, k, scores_out, top_out)) return rc;
+    return prefill_run(m, slot, tokens, pos0, count, true, targets, scores_out, nullptr, k, top_out);
 }
 extern "C" uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m) {
     if (!m) return 0u;

@@ -5,7 +5,8 @@
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
 //   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
-//   backend_rows.hip     ragged steps: rows of several KV slots in one pass (the planner, the entry point)
+//   backend_rows.hip     ragged steps: rows of several KV slots in one pass (the planner, the entry points)
+//   backend_topk.hip     top-k alternatives behind the statistics: the scratch, the enqueue, the decode-step entry
 //   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
 #pragma once
 #include <math.h>
@@ -102,6 +103,18 @@ struct NanoHipModel {
         uint32_t *stage = nullptr;                        // [max_seq_len] the call's targets on the device
         NanoHipTokenScore *out = nullptr;                 // [max_seq_len] the call's scores, copied back once
     } score;
+    // top-k alternatives (backend_topk.hip, topk.hip), allocated on the first call that asks for them -- apart from `score`, so that callers
+    // of the existing entry points allocate nothing new.  rows_cap = max(pf_chunk, max_batch): a decode step scores max_batch rows
+    struct Topk {
+        unsigned long long *part = nullptr;               // [rows_cap][score_tiles(V)][NANO_TOPK_MAX] the tiles' best keys
+        ScorePartial *spart = nullptr;                    // [rows_cap][score_tiles(V)] statistics partials of a decode step's rows (score.part holds pf_chunk rows)
+        uint32_t *targets = nullptr;                      // [rows_cap] a decode step's targets
+        NanoHipTokenScore *rows = nullptr;                // [rows_cap] a decode step's records
+        NanoHipTopEntry *out = nullptr;                   // [cap][NANO_TOPK_MAX] the call's entries (row i's k entries at i * k), copied back once
+        NanoHipTokenScore *sc = nullptr;                  // [cap] the records of a scored ragged step, pass order
+        uint32_t *tg = nullptr;                           // [cap] its targets, pass order
+        uint32_t rows_cap = 0, cap = 0;                   // cap >= max_seq_len: rows of one call
+    } tk;
     // greedy decode with lookup drafts (backend_lookup.hip), allocated on the first call that needs it
     struct Lookup {
         uint32_t *hist = nullptr; uint32_t cap = 0;       // slot 0's ids on the device (lookup.hip appends to them); cap = max_seq_len + 1 rounded up to 4
@@ -192,9 +205,16 @@ void handoff_fallback(NanoHipModel *m);
 void drop_graphs(NanoHipModel *m);
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps);
 int score_scratch(NanoHipModel *m);
+int topk_scratch(NanoHipModel *m, size_t call_rows);   // backend_topk.hip: room for a call of call_rows rows
+void topk_free(NanoHipModel *m);
+// the selection behind the statistics: `rows` rows of logits (row stride V), their records in scores (queued before) -> out[rows][k]
+hipError_t enqueue_topk_rows(NanoHipModel *m, const float *logits, uint32_t rows, uint32_t k, const NanoHipTokenScore *scores, NanoHipTopEntry *out);
+// what every top-k entry point refuses before anything is queued (m is not null)
+int topk_check(const NanoHipModel *m, uint32_t k, const NanoHipTokenScore *scores_out, const NanoHipTopEntry *top_out);
 // batched prefill of one slot, as nano_hip_prefill / _prefill_score / _verify_draft (argmax_out: every row's arg-max) call it
+// k >= 1 (with score): the k entries of every fed position too -> top_out[count][k]; out may then be null
 int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
-                uint32_t *argmax_out = nullptr);
+                uint32_t *argmax_out = nullptr, uint32_t k = 0, NanoHipTopEntry *top_out = nullptr);
 // one prefill chunk of nb rows of `slot` (m->tokens / m->pos hold them; last_pos = the last row's position), eager or -- replay -- through the
 // bounded cache of chunk graphs under `key_kind` (bits 56-57 of the key: 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify)
 hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind);
@@ -244,7 +264,8 @@ void sampler_free(Sampler *sp);                        // backend_sampler.hip
 
 // ---- backend_step.hip ----
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr, float *dst = nullptr);    // dst: nullptr = m->logits
-hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out);
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out,
+                              ScorePartial *part = nullptr);      // part: nullptr = m->score.part (pf_chunk rows)
 hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint);
 bool strict_serves(const NanoHipModel *m);
 bool exact_serves(const NanoHipModel *m);

@@ -83,8 +83,14 @@ static hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, uint32_t mode,
     return e;
 }
 
-extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out) {
+// A ragged step, as nano_hip_step_rows (argmax_out: every row's arg-max, may be null) and nano_hip_step_rows_score (score: every row's
+// record for targets -- null: its own arg-max -- and, k >= 1, its k entries) call it.  A scoring pass is a MODE_SCORE pass: the classifier
+// over all its rows into score.logits and the statistics for the pass's targets, staged in pass order; the selection's two launches
+// follow eagerly on the same buffers.  Records and entries are gathered to caller order through where[].
+static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out,
+                         bool score, const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
+    if (score) { if (const int rc = topk_check(m, k, scores_out, top_out)) return rc; }
     if (n_segs == 0) return 0;
     if (!segs) FAIL(NANO_HIP_EINVAL, "null argument");
     const uint32_t cap = nano_hip_prefill_chunk_tokens(m);
@@ -97,6 +103,7 @@ extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, ui
         if ((uint64_t)segs[i].pos0 + segs[i].count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "segment %u: positions %u..%u exceed the model's RoPE table (%u rows = block_size)", i, segs[i].pos0, segs[i].pos0 + segs[i].count, m->rope_rows);
     }
     for (size_t r = 0; r < total; r++) if (tokens[r] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[r]);
+    if (score && targets) for (size_t r = 0; r < total; r++) if (targets[r] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", targets[r]);
     if (m->lora_on) FAIL(NANO_HIP_EINVAL, "ragged steps are not available with the LoRA side branches (their v branch addresses the cache by a flat stride)");
     if (!m->kv.paged && !nano_hip_rows_addressable(m->d.n_layer, m->S, m->KD, (uint32_t)kv_esz(m)))
         FAIL(NANO_HIP_EINVAL, "the row map cannot address a cache of %u layers x %u positions x %u elements", m->d.n_layer, m->S, m->KD);
@@ -107,6 +114,11 @@ extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, ui
     if (verify) {
         int rc = score_scratch(m);
         if (!rc) rc = lookup_scratch(m);
+        if (rc) return rc;
+    }
+    if (score) {
+        int rc = score_scratch(m);
+        if (!rc) rc = topk_scratch(m, total);
         if (rc) return rc;
     }
     if (!ordered && !m->kv_half && !m->kv.paged && !m->rows.vraw && hipMalloc(reinterpret_cast<void **>(&m->rows.vraw), (size_t)m->Bs * m->KD * 4) != hipSuccess) {
@@ -126,29 +138,37 @@ extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, ui
         if (const int rc = kv_ensure(m, slots.data(), first.data(), need.data(), (uint32_t)slots.size())) return rc;
     }
     // the call's rows in pass order: where caller row r went, and its token, position and slot there -- on the device ONCE
-    std::vector<uint32_t> pass_start(plan.n_passes + 1, 0u), where(total), stage(3 * total);
+    std::vector<uint32_t> pass_start(plan.n_passes + 1, 0u), where(total), stage(3 * total), tstage(score && targets ? total : 0);
     for (size_t r = 0; r < total; r++) pass_start[plan.pass[r] + 1]++;
     for (uint32_t p = 0; p < plan.n_passes; p++) pass_start[p + 1] += pass_start[p];
     {
         size_t r = 0;
         for (uint32_t i = 0; i < n_segs; i++)
-            for (uint32_t k = 0; k < segs[i].count; k++, r++) {
+            for (uint32_t j = 0; j < segs[i].count; j++, r++) {
                 const size_t w = where[r] = pass_start[plan.pass[r]] + plan.index[r];
-                stage[w] = tokens[r]; stage[total + w] = segs[i].pos0 + k; stage[2 * total + w] = segs[i].slot;
+                stage[w] = tokens[r]; stage[total + w] = segs[i].pos0 + j; stage[2 * total + w] = segs[i].slot;
+                if (!tstage.empty()) tstage[w] = targets[r];
             }
     }
     uint32_t *const d_tok = m->rows.stage, *const d_pos = d_tok + m->rows.cap, *const d_slot = d_pos + m->rows.cap, *const d_amax = d_slot + m->rows.cap;
     HIP_TRY(hipMemcpyAsync(d_tok, stage.data(), total * 4, hipMemcpyHostToDevice, m->st));
     HIP_TRY(hipMemcpyAsync(d_pos, stage.data() + total, total * 4, hipMemcpyHostToDevice, m->st));
     HIP_TRY(hipMemcpyAsync(d_slot, stage.data() + 2 * total, total * 4, hipMemcpyHostToDevice, m->st));
+    const uint32_t *const d_tgt = tstage.empty() ? nullptr : m->tk.tg;       // the call's targets, pass order
+    if (d_tgt) HIP_TRY(hipMemcpyAsync(m->tk.tg, tstage.data(), total * 4, hipMemcpyHostToDevice, m->st));
+    if (score) m->score.use_targets = d_tgt != nullptr;
     if (ordered) {
         // strict / exact mode: one pass = one row (cap 1, so pass order is caller order): a reference-order step in the row's slot
-        const uint32_t mode1 = verify ? MODE_ARGMAX : MODE_NOCLS;
+        const uint32_t mode1 = verify ? MODE_ARGMAX : score ? MODE_LOGITS : MODE_NOCLS;
         for (size_t w = 0; w < total; w++) {
             HIP_TRY(hipMemcpyAsync(m->tokens, d_tok + w, 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, d_pos + w, 4, hipMemcpyDeviceToDevice, m->st));
             if (const int rc = run_step_ordered(m, 1, 1, mode1, stage[2 * total + w])) return rc;
             if (verify) HIP_TRY(hipMemcpyAsync(d_amax + w, m->amax, 4, hipMemcpyDeviceToDevice, m->st));
+            if (score) {                                                   // the row's logits are row 0 of m->logits, as in prefill_run
+                HIP_TRY(enqueue_score_rows(m, m->logits, 1, d_tgt ? d_tgt + w : nullptr, m->tk.sc + w));
+                if (k) HIP_TRY(enqueue_topk_rows(m, m->logits, 1, k, m->tk.sc + w, m->tk.out + w * k));
+            }
         }
     } else {
         for (uint32_t p = 0; p < plan.n_passes; p++) {
@@ -157,19 +177,38 @@ extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, ui
             HIP_TRY(hipMemcpyAsync(m->tokens, d_tok + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, d_pos + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
             m->rows.groups.clear();
-            for (uint32_t k = 0; k < nb; k++) {                            // (sorted by hint: a group is a run of equal hints)
-                const uint32_t pos = stage[total + w0 + k], h = range_hint_of(m, 1, 1, pos);
-                if (m->rows.groups.empty() || m->rows.groups.back().hint != h) m->rows.groups.push_back({k, 1u, h});
+            for (uint32_t j = 0; j < nb; j++) {                            // (sorted by hint: a group is a run of equal hints)
+                const uint32_t pos = stage[total + w0 + j], h = range_hint_of(m, 1, 1, pos);
+                if (m->rows.groups.empty() || m->rows.groups.back().hint != h) m->rows.groups.push_back({j, 1u, h});
                 else m->rows.groups.back().n++;
             }
-            HIP_TRY(enqueue_rows_pass(m, nb, verify ? MODE_VERIFY : MODE_NOCLS, d_slot + w0));
+            if (d_tgt) HIP_TRY(hipMemcpyAsync(m->score.targets, d_tgt + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
+            HIP_TRY(enqueue_rows_pass(m, nb, verify ? MODE_VERIFY : score ? MODE_SCORE : MODE_NOCLS, d_slot + w0));
             if (verify) HIP_TRY(hipMemcpyAsync(d_amax + w0, m->lk.amax, nb * 4, hipMemcpyDeviceToDevice, m->st));
+            if (score) {
+                HIP_TRY(hipMemcpyAsync(m->tk.sc + w0, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
+                if (k) HIP_TRY(enqueue_topk_rows(m, m->score.logits, nb, k, m->score.rows, m->tk.out + w0 * k));
+            }
         }
     }
     std::vector<uint32_t> amax(verify ? total : 0);
+    std::vector<NanoHipTokenScore> sc(score && scores_out ? total : 0);
+    std::vector<NanoHipTopEntry> top(score ? total * k : 0);
     if (verify) HIP_TRY(hipMemcpyAsync(amax.data(), d_amax, total * 4, hipMemcpyDeviceToHost, m->st));
+    if (!sc.empty()) HIP_TRY(hipMemcpyAsync(sc.data(), m->tk.sc, total * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st));
+    if (!top.empty()) HIP_TRY(hipMemcpyAsync(top.data(), m->tk.out, total * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipStreamSynchronize(m->st));                                   // the call's one wait
     if (const int rc = dev_err_check(m)) return rc;
     for (size_t r = 0; r < (verify ? total : 0); r++) argmax_out[r] = amax[where[r]];
+    for (size_t r = 0; r < (sc.empty() ? 0 : total); r++) scores_out[r] = sc[where[r]];
+    for (size_t r = 0; r < (top.empty() ? 0 : total); r++) std::copy(top.begin() + where[r] * k, top.begin() + (where[r] + 1) * k, top_out + r * k);
     return 0;
+}
+
+extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out) {
+    return step_rows_run(m, segs, n_segs, tokens, argmax_out, false, nullptr, 0, nullptr, nullptr);
+}
+extern "C" int nano_hip_step_rows_score(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens,
+                                        const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+    return step_rows_run(m, segs, n_segs, tokens, nullptr, true, targets, k, scores_out, top_out);
 }

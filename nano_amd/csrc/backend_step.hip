@@ -47,9 +47,9 @@ hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out
     return gemv(m, a);
 }
 // the row statistics of `rows` rows of logits (row stride V) for targets[rows] (nullptr: each row's own arg-max) -> out[rows]  (score.hip)
-hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out) {
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out, ScorePartial *part) {
     ScoreArgs a{};
-    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.targets = targets; a.part = m->score.part; a.out = out;
+    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.targets = targets; a.part = part ? part : m->score.part; a.out = out;
     return launch_score_rows(a, rows, m->st);
 }
 // attention splits of a step: batches bring their own parallelism (nb x KV groups workgroups per split) and every

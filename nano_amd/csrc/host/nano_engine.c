@@ -491,8 +491,11 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
 }
 
 /* The log-probability of ids[1..n_ids) given what precedes each: one scoring prefill of ids[0..n_ids-1) into sequence 0 of the context's own
- * device, targets ids + 1 (nano_hip_prefill_score); the logits stay on the device. */
-int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum) {
+ * device, targets ids + 1 (nano_hip_prefill_score); the logits stay on the device.  k >= 1 (nano_score_ids_topk): for every scored
+ * position also the k most probable ids and their log-probs (nano_hip_prefill_score_topk; with k == 0 that call is nano_hip_prefill_score):
+ * top_ids / top_logprobs hold (n_ids - 1) * k entries, position after position, most probable first. */
+static int score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, uint32_t k, float *logprobs, uint32_t *argmax,
+                     uint32_t *top_ids, float *top_logprobs, double *nll_sum) {
     la_clear(ctx ? reg_entry(ctx->llm) : NULL);
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
     if (!me || !me->dev || (!ids && n_ids)) return NANO_HIP_EINVAL;
@@ -500,10 +503,11 @@ int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float
     if (n_ids < 2) return NANO_HIP_OK;
     const uint32_t n = n_ids - 1;
     NanoHipTokenScore *sc = (NanoHipTokenScore *)malloc((size_t)n * sizeof *sc);
-    if (!sc) return NANO_HIP_ENOMEM;
+    NanoHipTopEntry *top = k ? (NanoHipTopEntry *)malloc((size_t)n * k * sizeof *top) : NULL;
+    if (!sc || (k && !top)) { free(sc); free(top); return NANO_HIP_ENOMEM; }
     lora_select(me->dev, ctx->lora);
     me->pf_session = NULL;                                    /* sequence 0's rows are this text's now */
-    const int rc = nano_hip_prefill_score(me->dev, 0, ids, 0, n, ids + 1, sc);
+    const int rc = nano_hip_prefill_score_topk(me->dev, 0, ids, 0, n, ids + 1, k, sc, top);
     if (rc == NANO_HIP_OK) {
         double nll = 0.0;
         for (uint32_t i = 0; i < n; i++) {
@@ -511,9 +515,59 @@ int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float
             if (argmax) argmax[i] = sc[i].argmax;
             nll -= (double)sc[i].logprob;
         }
+        for (size_t e = 0; e < (size_t)n * k; e++) {
+            if (top_ids) top_ids[e] = top[e].token;
+            if (top_logprobs) top_logprobs[e] = top[e].logprob;
+        }
         if (nll_sum) *nll_sum = nll;
     }
-    free(sc);
+    free(sc); free(top);
+    return rc;
+}
+int nano_score_ids(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, float *logprobs, uint32_t *argmax, double *nll_sum) {
+    return score_ids(ctx, ids, n_ids, 0, logprobs, argmax, NULL, NULL, nll_sum);
+}
+int nano_score_ids_topk(Nano_Context *ctx, const uint32_t *ids, uint32_t n_ids, uint32_t k, float *logprobs, uint32_t *argmax,
+                        uint32_t *top_ids, float *top_logprobs, double *nll_sum) {
+    if (k == 0 || k > NANO_TOPK_MAX || (!top_ids && !top_logprobs)) return NANO_HIP_EINVAL;   /* (k > vocab: the device entry refuses it) */
+    return score_ids(ctx, ids, n_ids, k, logprobs, argmax, top_ids, top_logprobs, nll_sum);
+}
+
+/* One decode step of `batch` sequences (sequence i -> replica i mod G, slot i / G, as nano_forward_batch) that hands back, per sequence,
+ * the k most probable next ids and their log-probs instead of the logits (nano_hip_forward_topk).  With replicas each replica's share is
+ * served by its own call, one replica after another. */
+int nano_forward_batch_topk(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t k,
+                            uint32_t *top_ids, float *top_logprobs, uint32_t *argmax) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    la_clear(me);
+    if (!me || !me->dev || !tokens || !pos || batch == 0) return NANO_HIP_EINVAL;
+    if (k == 0 || k > NANO_TOPK_MAX || k > (uint32_t)ctx->llm->config.vocab_size || (!top_ids && !top_logprobs)) return NANO_HIP_EINVAL;
+    const uint32_t G = me->n_replica > 0 ? (uint32_t)me->n_replica : 1;
+    if (batch > NANO_MAX_BATCH * G) return NANO_HIP_EINVAL;
+    NanoHipTokenScore sc[NANO_MAX_BATCH];
+    NanoHipTopEntry *top = (NanoHipTopEntry *)malloc((size_t)NANO_MAX_BATCH * k * sizeof *top);
+    if (!top) return NANO_HIP_ENOMEM;
+    int rc = NANO_HIP_OK;
+    for (uint32_t r = 0; r < G && rc == NANO_HIP_OK; r++) {
+        NanoHipModel *dev = G > 1 ? me->replica[r] : me->dev;
+        uint32_t tk[NANO_MAX_BATCH], ps[NANO_MAX_BATCH], n = 0;
+        for (uint32_t i = r; i < batch; i += G) {
+            if (n >= NANO_MAX_BATCH) { rc = NANO_HIP_EINVAL; break; }
+            tk[n] = tokens[i]; ps[n++] = pos[i];
+        }
+        if (rc != NANO_HIP_OK || n == 0) continue;
+        lora_select(dev, ctx->lora);
+        if ((rc = nano_hip_forward_topk(dev, tk, ps, n, NULL, k, sc, top)) != NANO_HIP_OK) break;
+        for (uint32_t j = 0; j < n; j++) {
+            const size_t i = (size_t)j * G + r;
+            if (argmax) argmax[i] = sc[j].argmax;
+            for (uint32_t e = 0; e < k; e++) {
+                if (top_ids) top_ids[i * k + e] = top[(size_t)j * k + e].token;
+                if (top_logprobs) top_logprobs[i * k + e] = top[(size_t)j * k + e].logprob;
+            }
+        }
+    }
+    free(top);
     return rc;
 }
 

@@ -437,6 +437,16 @@ uint32_t score_tiles(uint32_t V);
 // two launches: the tiles, then one wave per row
 hipError_t launch_score_rows(const ScoreArgs &a, uint32_t rows, hipStream_t st);
 
+// ---- the k most probable tokens of every row, with their log-probs (topk.hip): k NanoHipTopEntry per row ----
+struct TopkArgs {
+    const float *logits; uint32_t V, ntiles, k;            // [rows][V], row stride V; ntiles = score_tiles(V); 1 <= k <= min(NANO_TOPK_MAX, V)
+    unsigned long long *part;                              // scratch [rows][ntiles][k]: every tile's best keys, in order (0: none)
+    const NanoHipTokenScore *scores;                       // [rows]: launch_score_rows' records of the same rows (queued first on the same stream): lse
+    NanoHipTopEntry *out;                                  // [rows][k]
+};
+// two launches: the tiles (score.hip's tiles), then one workgroup per row; rows <= 65535
+hipError_t launch_topk_rows(const TopkArgs &a, uint32_t rows, hipStream_t st);
+
 hipError_t launch_rmsnorm(float *out, const float *x, const float *w, uint32_t n, hipStream_t st);
 hipError_t launch_quantize_q80(const float *x, uint32_t n, uint32_t gs, int8_t *q, float *s, hipStream_t st);
 hipError_t launch_quantize_q4k(const float *x, uint32_t n, uint8_t *blocks, hipStream_t st);

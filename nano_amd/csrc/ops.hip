@@ -221,6 +221,31 @@ extern "C" int nano_hip_op_score_rows(int device, const float *logits, uint32_t 
     return 0;
 }
 
+// the row statistics and, behind them, the top-k selection (topk.hip) alone.  The arguments are checked before a device is asked for.
+extern "C" int nano_hip_op_topk_rows(int device, const float *logits, uint32_t rows, uint32_t V, uint32_t k, const uint32_t *targets,
+                                     NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+    if (!logits || !top_out || !rows || !V || !k) { nano_hip_set_error_("topk_rows: null logits / top_out, or no rows / no vocabulary / k of 0"); return NANO_HIP_EINVAL; }
+    if (k > NANO_TOPK_MAX || k > V) { nano_hip_set_error_("topk_rows: k exceeds NANO_TOPK_MAX or the vocabulary"); return NANO_HIP_EINVAL; }
+    if (rows > 65535u) { nano_hip_set_error_("topk_rows: more than 65535 rows"); return NANO_HIP_EINVAL; }
+    if (targets) for (uint32_t r = 0; r < rows; r++) if (targets[r] >= V) { nano_hip_set_error_("topk_rows: target out of vocabulary"); return NANO_HIP_EINVAL; }
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B;
+    ScoreArgs a{};
+    a.V = V; a.ntiles = score_tiles(V);
+    a.logits = B.upload(logits, (size_t)rows * V);
+    a.targets = targets ? B.upload(targets, rows) : nullptr;
+    a.part = B.alloc<ScorePartial>((size_t)rows * a.ntiles); a.out = B.alloc<NanoHipTokenScore>(rows);
+    TopkArgs t{};
+    t.logits = a.logits; t.V = V; t.ntiles = a.ntiles; t.k = k; t.scores = a.out;
+    t.part = B.alloc<unsigned long long>((size_t)rows * a.ntiles * k); t.out = B.alloc<NanoHipTopEntry>((size_t)rows * k);
+    OP_CHECK(a.logits && (a.targets || !targets) && a.part && a.out && t.part && t.out, "device alloc failed");
+    OP_HIP(launch_score_rows(a, rows, 0));
+    OP_HIP(launch_topk_rows(t, rows, 0));
+    OP_HIP(hipMemcpy(top_out, t.out, (size_t)rows * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost));
+    if (scores_out) OP_HIP(hipMemcpy(scores_out, a.out, (size_t)rows * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // the between-steps kernel of greedy decode with lookup drafts alone (lookup.hip).  The arguments are checked before a device is asked for.
 extern "C" int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
                                        const NanoHipLookupParams *p, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
