@@ -212,7 +212,7 @@ typedef struct NanoHipTopEntry { uint32_t token; float logit; float logprob; } N
 /* In the three model entry points below k == 0 means scores only (top_out may be NULL); k >= 1 requires top_out with rows * k
  * entries in caller order, and scores_out may then be NULL.  k > NANO_TOPK_MAX, k > vocab, a null top_out with k >= 1, a null
  * scores_out with k == 0 and a target >= vocab are NANO_HIP_EINVAL before anything is queued.  The selection's scratch is allocated on the
- * first such call (all or nothing: NANO_HIP_ENOMEM leaves the model usable); callers of the other entry points allocate nothing.
+ * first such call with k >= 1 (NANO_HIP_ENOMEM leaves the model usable); k == 0 and callers of the other entry points allocate none of it.
  *
  * nano_hip_prefill_score_topk: everything nano_hip_prefill_score does -- same chunks and chunk graphs, same KV rows, same later
  * outputs, the same score records bit for bit -- plus the k entries of every fed position (top_out[i * k + j]).  The two selection

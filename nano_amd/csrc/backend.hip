@@ -67,14 +67,13 @@ static void destroy(NanoHipModel *m) {
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
-                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->pf_stage,
-                    m->score.logits, m->score.part, m->score.targets, m->score.rows, m->score.stage, m->score.out, m->rows.stage, m->rows.vraw };
+                    m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->rows.vraw };
     for (void *p : dev) if (p) (void)hipFree(p);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
     lookup_free(m);
-    topk_free(m);
+    rows_free(m);
     for (hipEvent_t ev : { m->ev0, m->ev1, m->ev2 }) if (ev) (void)hipEventDestroy(ev);
     if (m->st) (void)hipStreamDestroy(m->st);
     delete m;
@@ -479,32 +478,11 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     m->lora_on = on != 0;
     return 0;
 }
-// scratch of the scoring prefill, on its first call: the chunk's logits, the statistics kernel's partials, the chunk's targets and scores,
-// and the call's targets and scores (a call feeds at most max_seq_len tokens).  All or nothing: a failure leaves the model as it was.
-int score_scratch(NanoHipModel *m) {
-    if (m->score.logits) return 0;
-    const size_t V = m->d.vocab_size, PF = m->pf_chunk, cap = m->S;
-    NanoHipModel::Score s;
-    const bool ok = hipMalloc(reinterpret_cast<void **>(&s.logits), PF * V * 4) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.part), PF * score_tiles((uint32_t)V) * sizeof(ScorePartial)) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.targets), PF * 4) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.rows), PF * sizeof(NanoHipTokenScore)) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.stage), cap * 4) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.out), cap * sizeof(NanoHipTokenScore)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        void *got[] = { s.logits, s.part, s.targets, s.rows, s.stage, s.out };
-        for (void *p : got) if (p) (void)hipFree(p);
-        FAIL(NANO_HIP_ENOMEM, "hipMalloc of the scoring prefill's buffers failed (%zu x %zu logits)", PF, V);
-    }
-    m->score = s;
-    return 0;
-}
 // One prefill chunk: nb rows of `slot`, their tokens and positions in m->tokens / m->pos, the last at last_pos.  replay: through a HIP graph per
 // (KV slot, range bucket, nb, key_kind) -- positions and tokens are device data, the slot's cache addresses are baked into the nodes.  The chunk
 // that meets a key first runs eagerly and is captured for the next one that reaches it; a failed capture only costs the replays (r.capture
 // is not looked at).  The cache of chunk graphs is bounded (oldest out).  Chunks of different kinds have different nodes: bits 56-57 of the
-// key = 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify, so none ever replays another's graph.
+// key are RowWant::key_kind, so none ever replays another's graph.
 hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind) {
     const uint32_t range_hint = range_hint_of(m, 1, 1, last_pos);      // of the chunk's last token's own decode step
     m->pf = true; m->pf_slot = slot;
@@ -532,129 +510,70 @@ hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t m
 // passes of up to 64 (Q80, Q4K and FP32 through their MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
 // logits (the reference computes and discards them for prompt positions, infer.c:1146-1149).  The KV rows and every
 // later logit are the ones token-by-token feeding produces, bit for bit (same kernels and the same attention split per token).
-// score (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);
-// out[i] scores the logits of tokens[i] for targets[i] (targets == nullptr: for the row's own arg-max).  Nothing else differs.
-// argmax_out (nano_hip_verify_draft): every chunk goes on into the classifier and the arg-max of all its rows (MODE_VERIFY); argmax_out[i] is row i's.
-// k >= 1 (nano_hip_prefill_score_topk): the selection's two launches (topk.hip) are queued eagerly behind every scored chunk, on score.logits and
-// the chunk's records, before the next chunk overwrites them: the chunk graphs and their keys are nano_hip_prefill_score's.
-int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
-                uint32_t *argmax_out, uint32_t k, NanoHipTopEntry *top_out) {
-    const bool verify = argmax_out != nullptr;
-    if (!m || !tokens || (score && !out && !k)) FAIL(NANO_HIP_EINVAL, "null argument");
-    if (k) { if (const int rc = topk_check(m, k, out, top_out)) return rc; }
+// want (RowWant, backend_model.h) says what comes back per fed row; nothing else differs.
+//   scores (nano_hip_prefill_score): every chunk goes on into the classifier for all its rows and the row statistics (enqueue_step MODE_SCORE);
+//     scores_out[i] scores the logits of tokens[i] for targets[i] (no targets: for the row's own arg-max).  k >= 1 (nano_hip_prefill_score_topk):
+//     the selection's two launches (topk.hip) are queued eagerly behind every scored chunk, so the chunk graphs and their keys are nano_hip_prefill_score's.
+//   arg-maxes (nano_hip_verify_draft): every chunk goes on into the classifier and the arg-max of all its rows (MODE_VERIFY); argmax_out[i] is row i's.
+// Strict and exact mode feed token by token through rows_run_ordered: the prompt is staged once and the host waits once per prompt in both
+// (no wait per token: a token comes from the staged prompt by a device-to-device copy, not through stage_batch's pinned row; the phase hook waits itself).
+int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, const RowWant &want) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (const int rc = rows_check(m, want)) return rc;
+    if (!tokens) FAIL(NANO_HIP_EINVAL, "null argument");
     if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "slot %u out of range (max_batch %u)", slot, m->maxB);
     if ((uint64_t)pos0 + count > m->S) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed max_seq_len %u", pos0, pos0 + count, m->S);
     if ((uint64_t)pos0 + count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "positions %u..%u exceed the model's RoPE table (%u rows = block_size)", pos0, pos0 + count, m->rope_rows);
     for (uint32_t i = 0; i < count; i++) if (tokens[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[i]);
-    if (score && targets) for (uint32_t i = 0; i < count; i++) if (targets[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", targets[i]);
-    if (score && !count) return 0;
+    if (want.use_targets()) for (uint32_t i = 0; i < count; i++) if (want.targets[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", want.targets[i]);
+    if (want.kind == RowWant::SCORE && !count) return 0;
     HIP_TRY(hipSetDevice(m->device));
     if (count) { const int rc = step_served(m, true); if (rc) return rc; }     // (an empty prompt queues nothing: there is nothing to refuse)
-    if (verify) {
-        int rc = score_scratch(m);
-        if (!rc) rc = lookup_scratch(m);
-        if (rc) return rc;
-    }
-    if (score) {
-        if (const int rc = score_scratch(m)) return rc;
-        m->score.use_targets = targets != nullptr;
-        if (k) { if (const int rc = topk_scratch(m, count)) return rc; }
-        if (targets) HIP_TRY(hipMemcpyAsync(m->score.stage, targets, (size_t)count * 4, hipMemcpyHostToDevice, m->st));      // (a pageable source, like the tokens below)
-    }
-    // token i's logits are in row 0 of m->logits (strict / exact mode: one reference-order step per token): their statistics
-    auto score_token = [&](uint32_t i) {
-        const hipError_t e = enqueue_score_rows(m, m->logits, 1, targets ? m->score.stage + i : nullptr, m->score.out + i);
-        return (e != hipSuccess || !k) ? e : enqueue_topk_rows(m, m->logits, 1, k, m->score.out + i, m->tk.out + (size_t)i * k);
-    };
-    // the call's scores: one copy, behind the work queued so far and in front of the call's last wait
-    auto scores_back = [&]() {
-        if (verify) return hipMemcpyAsync(argmax_out, m->lk.out, (size_t)count * 4, hipMemcpyDeviceToHost, m->st);
-        if (k) { const hipError_t e = hipMemcpyAsync(top_out, m->tk.out, (size_t)count * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost, m->st); if (e != hipSuccess) return e; }
-        return (score && out) ? hipMemcpyAsync(out, m->score.out, (size_t)count * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st) : hipSuccess;
-    };
-    // token i's arg-max is in m->amax[0] (strict / exact mode)
-    auto amax_token = [&](uint32_t i) { return hipMemcpyAsync(m->lk.out + i, m->amax, 4, hipMemcpyDeviceToDevice, m->st); };
-    const uint32_t mode1 = verify ? MODE_ARGMAX : score ? MODE_LOGITS : MODE_NOCLS;     // of a token fed alone
+    const bool ordered = strict_serves(m) || exact_serves(m);                 // one reference-order step per prompt token (exact mode: each a replay)
+    if (const int rc = rows_begin(m, want, !ordered, C_FEED, count, want.targets)) return rc;
     if (m->kv.paged && count) {
         const uint32_t need = pos0 + count - 1;
         int rc = kv_ensure(m, &slot, &pos0, &need, 1);
         if (rc) return rc;
     }
-    if (strict_serves(m)) {                                                 // strict mode: one reference-order forward per prompt token
-        for (uint32_t i = 0; i < count; i++) {
-            const uint32_t p = pos0 + i;
-            int rc = stage_batch(m, tokens + i, &p, 1, false);
-            if (!rc) rc = run_step_ordered(m, 1, 1, mode1, slot);
-            if (rc) return rc;
-            if (score) HIP_TRY(score_token(i));
-            if (verify) HIP_TRY(amax_token(i));
-            HIP_TRY(hipStreamSynchronize(m->st));
-        }
-        if (score || verify) { HIP_TRY(scores_back()); HIP_TRY(hipStreamSynchronize(m->st)); }
-        return 0;
-    }
-    const uint32_t chunk_max = m->pf_chunk;
     // the whole prompt's tokens and positions go to the device ONCE; a chunk takes its share by device-to-device copies on the stream, the host waits only at the end
-    if (count > m->pf_cap) {
-        if (m->pf_stage) { HIP_TRY(hipStreamSynchronize(m->st)); (void)hipFree(m->pf_stage); m->pf_stage = nullptr; m->pf_cap = 0; }
-        const uint32_t cap = count > m->S ? count : m->S;
-        if (hipMalloc(reinterpret_cast<void **>(&m->pf_stage), (size_t)cap * 8) != hipSuccess) FAIL(NANO_HIP_ENOMEM, "hipMalloc of the prompt staging buffer failed");
-        m->pf_cap = cap;
-    }
     if (count) {
         std::vector<uint32_t> hp(count);
         for (uint32_t i = 0; i < count; i++) hp[i] = pos0 + i;
-        HIP_TRY(hipMemcpyAsync(m->pf_stage, tokens, (size_t)count * 4, hipMemcpyHostToDevice, m->st));          // (pageable sources: staged by the runtime before the call returns)
-        HIP_TRY(hipMemcpyAsync(m->pf_stage + m->pf_cap, hp.data(), (size_t)count * 4, hipMemcpyHostToDevice, m->st));
+        if (const int rc = rows_feed(m, count, tokens, hp.data(), nullptr)) return rc;
         HIP_TRY(hipStreamSynchronize(m->st));                              // hp leaves scope; one wait per prompt
     }
-    if (exact_serves(m)) {                                                  // exact mode: token by token too, each a MODE_NOCLS replay; one wait per prompt
-        for (uint32_t i = 0; i < count; i++) {
-            HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + i, 4, hipMemcpyDeviceToDevice, m->st));
-            HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + i, 4, hipMemcpyDeviceToDevice, m->st));
-            const int rc = run_step_ordered(m, 1, 1, mode1, slot);
-            if (rc) return rc;
-            if (score) HIP_TRY(score_token(i));
-            if (verify) HIP_TRY(amax_token(i));
-        }
-        HIP_TRY(scores_back());
-        HIP_TRY(hipStreamSynchronize(m->st));
-        return dev_err_check(m);
+    if (ordered) {
+        if (const int rc = rows_run_ordered(m, want, count, slot, nullptr)) return rc;
+        return rows_back(m, want, count, nullptr, true);
     }
+    const uint32_t chunk_max = m->pf_chunk;
     for (uint32_t done = 0; done < count;) {
         uint32_t nb = (count - done < chunk_max) ? count - done : chunk_max;
         const uint32_t to_bucket_end = 64u - (pos0 + done) % 64u;          // one attention range bucket per chunk (see enqueue_step)
         if (nb > to_bucket_end) nb = to_bucket_end;
-        HIP_TRY(hipMemcpyAsync(m->tokens, m->pf_stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(m->pos, m->pf_stage + m->pf_cap + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
-        if (score && targets) HIP_TRY(hipMemcpyAsync(m->score.targets, m->score.stage + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
-        const uint32_t mode = verify ? MODE_VERIFY : score ? MODE_SCORE : MODE_NOCLS;
+        HIP_TRY(hipMemcpyAsync(m->tokens, m->rb.tok + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
+        HIP_TRY(hipMemcpyAsync(m->pos, m->rb.pos + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
+        HIP_TRY(rows_pass_targets(m, done, nb));
         // a full 64-token chunk recurs in every long prompt: replayed.  Other chunk lengths run eagerly (a capture costs more than the ~300
         // launches it would save once).
         const bool replay = m->use_graph && nb == chunk_max && chunk_max == 64u;
-        const hipError_t e = enqueue_chunk(m, slot, nb, mode, pos0 + done + nb - 1, replay, verify ? 3u : score ? (targets ? 1u : 2u) : 0u);
-        HIP_TRY(e);
-        if (score) HIP_TRY(hipMemcpyAsync(m->score.out + done, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
-        if (k) HIP_TRY(enqueue_topk_rows(m, m->score.logits, nb, k, m->score.rows, m->tk.out + (size_t)done * k));
-        if (verify) HIP_TRY(hipMemcpyAsync(m->lk.out + done, m->lk.amax, nb * 4, hipMemcpyDeviceToDevice, m->st));
+        HIP_TRY(enqueue_chunk(m, slot, nb, want.mode_pass(), pos0 + done + nb - 1, replay, want.key_kind()));
+        HIP_TRY(rows_after_pass(m, want, done, nb));
         done += nb;
     }
-    HIP_TRY(scores_back());
-    HIP_TRY(hipStreamSynchronize(m->st));
-    return dev_err_check(m);
+    return rows_back(m, want, count, nullptr, true);
 }
 extern "C" int nano_hip_prefill(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count) {
-    return prefill_run(m, slot, tokens, pos0, count, false, nullptr, nullptr);
+    return prefill_run(m, slot, tokens, pos0, count, RowWant());
 }
 extern "C" int nano_hip_prefill_score(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
                                       const uint32_t *targets, NanoHipTokenScore *out) {
-    return prefill_run(m, slot, tokens, pos0, count, true, targets, out);
+    return prefill_run(m, slot, tokens, pos0, count, RowWant::scores(targets, 0, out, nullptr));
 }
 extern "C" int nano_hip_prefill_score_topk(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
                                            const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
-    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
-    if (const int rc = topk_check(m, k, scores_out, top_out)) return rc;
-    return prefill_run(m, slot, tokens, pos0, count, true, targets, scores_out, nullptr, k, top_out);
+    return prefill_run(m, slot, tokens, pos0, count, RowWant::scores(targets, k, scores_out, top_out));
 }
 extern "C" uint32_t nano_hip_prefill_chunk_tokens(const NanoHipModel *m) {
     if (!m) return 0u;

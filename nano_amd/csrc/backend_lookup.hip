@@ -3,21 +3,18 @@
 // that goes on into the classifier and the arg-max of all its rows (backend_step.hip MODE_VERIFY, backend.hip enqueue_chunk).
 #include "backend_model.h"
 
-// the device history (max_seq_len + 1 ids: the call's last emitted id has no position yet), the loop's state and record, the arg-maxes of a
-// verify chunk and of a verify call.  All or nothing: a failure leaves the model as it was.
+// the device history (max_seq_len + 1 ids: the call's last emitted id has no position yet), the loop's state and record (a verify chunk's
+// logits and arg-maxes are rows_scratch's pass buffers).  All or nothing: a failure leaves the model as it was.
 int lookup_scratch(NanoHipModel *m) {
     if (m->lk.hist) return 0;
     NanoHipModel::Lookup s;
     s.cap = (m->S + 1u + 3u) & ~3u;
-    const size_t rows = m->pf_chunk > LOOKUP_MAX_ROWS ? m->pf_chunk : LOOKUP_MAX_ROWS;
     const bool ok = hipMalloc(reinterpret_cast<void **>(&s.hist), (size_t)s.cap * 4) == hipSuccess &&
                     hipMalloc(reinterpret_cast<void **>(&s.state), (4 + LOOKUP_REC_WORDS) * 4) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.amax), rows * 4) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&s.out), (size_t)m->S * 4) == hipSuccess &&
                     hipHostMalloc(reinterpret_cast<void **>(&s.h_rec), LOOKUP_REC_WORDS * 4) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        void *got[] = { s.hist, s.state, s.amax, s.out };
+        void *got[] = { s.hist, s.state };
         for (void *p : got) if (p) (void)hipFree(p);
         if (s.h_rec) (void)hipHostFree(s.h_rec);
         FAIL(NANO_HIP_ENOMEM, "hipMalloc of the lookup decode buffers failed");
@@ -27,7 +24,7 @@ int lookup_scratch(NanoHipModel *m) {
     return 0;
 }
 void lookup_free(NanoHipModel *m) {
-    void *dev[] = { m->lk.hist, m->lk.state, m->lk.amax, m->lk.out };
+    void *dev[] = { m->lk.hist, m->lk.state };
     for (void *p : dev) if (p) (void)hipFree(p);
     if (m->lk.h_rec) (void)hipHostFree(m->lk.h_rec);
     m->lk = NanoHipModel::Lookup();
@@ -36,7 +33,7 @@ void lookup_free(NanoHipModel *m) {
 extern "C" int nano_hip_verify_draft(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count,
                                      uint32_t *argmax_out, uint32_t *n_accepted) {
     if (!m || !tokens || !argmax_out || !count) FAIL(NANO_HIP_EINVAL, "null argument or no tokens");
-    const int rc = prefill_run(m, slot, tokens, pos0, count, false, nullptr, nullptr, argmax_out);
+    const int rc = prefill_run(m, slot, tokens, pos0, count, RowWant::argmaxes(argmax_out));
     if (rc) return rc;
     uint32_t a = 0;
     while (a + 1 < count && tokens[a + 1] == argmax_out[a]) a++;
@@ -52,7 +49,7 @@ static int decode_lookup_once(NanoHipModel *m, const uint32_t *history, uint32_t
     HIP_TRY(hipSetDevice(m->device));
     if ((rc = step_served(m, false))) return rc;
     if ((rc = lookup_scratch(m))) return rc;
-    if (D >= 1 && (rc = score_scratch(m))) return rc;
+    if (D >= 1 && (rc = rows_scratch(m, P_LOGITS | P_AMAX, 0))) return rc;
     const uint32_t K = D + 1, slot = 0;
     if (m->kv.paged) {                                                      // every page the loop will enter, up front (a chunk stays inside its first row's block)
         const uint32_t first = n_history - 1, need = n_history - 2 + max_new;
@@ -77,7 +74,7 @@ static int decode_lookup_once(NanoHipModel *m, const uint32_t *history, uint32_t
     uint32_t n = n_history, nb = 0, steps = 0;
     bool lost = false;                                                      // a hand-off gave up: the records are not to be trusted, with_reissue() takes over
     for (;;) {
-        la.nb = nb; la.amax = nb > 1 ? m->lk.amax : m->amax;
+        la.nb = nb; la.amax = nb > 1 ? m->rb.amax : m->amax;
         HIP_TRY(launch_lookup_step(la, m->st));
         HIP_TRY(hipMemcpyAsync(m->lk.h_rec, la.record, LOOKUP_REC_WORDS * 4, hipMemcpyDeviceToHost, m->st));
         HIP_TRY(hipStreamSynchronize(m->st));

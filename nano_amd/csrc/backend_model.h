@@ -5,8 +5,7 @@
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
 //   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
-//   backend_rows.hip     ragged steps: rows of several KV slots in one pass (the planner, the entry points)
-//   backend_topk.hip     top-k alternatives behind the statistics: the scratch, the enqueue, the decode-step entry
+//   backend_rows.hip     what calls get back per fed row (RowWant: the scratch, the sink, the decode-step entry) and ragged steps
 //   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
 #pragma once
 #include <math.h>
@@ -48,8 +47,8 @@ extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the t
 
 enum { WQ = 0, WK, WV, WO, W1, W2, W3, WCOUNT };
 enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3,
-                           MODE_SCORE = 4,     // a prefill chunk that goes on into the classifier for all its rows (-> score.logits) and the row statistics
-                           MODE_VERIFY = 5 };  // a prefill chunk whose rows' arg-maxes are wanted (-> lk.amax): the classifier into score.logits, no statistics
+                           MODE_SCORE = 4,     // a pass that goes on into the classifier for all its rows (-> rb.logits) and the row statistics (-> rb.rows)
+                           MODE_VERIFY = 5 };  // a pass whose rows' arg-maxes are wanted (-> rb.amax): the classifier into rb.logits, no statistics
 constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs kept per model (keyed by KV slot x range bucket)
 constexpr uint32_t STAMP_MAX_LAUNCHES = 512, STAMP_WGS = 2048;
 constexpr uint32_t KV_NO_PAGE = 0xffffffffu;           // a page-table entry without a page
@@ -92,36 +91,32 @@ struct NanoHipModel {
     uint32_t nsplit_cap = 8;                             // the partial buffers are sized for it (32 beyond 2048 positions)
     // pinned host staging
     uint32_t *h_tokens = nullptr, *h_pos = nullptr, *h_amax = nullptr;
-    uint32_t *pf_stage = nullptr; uint32_t pf_cap = 0;    // batched prefill: the prompt's tokens | positions on the device (the chunks copy from here: no host round trip per chunk)
-    // scoring prefill (nano_hip_prefill_score), allocated on its first call: the chunk's logits never leave the device
-    struct Score {
-        float *logits = nullptr;                          // [pf_chunk][V]: m->logits holds max_batch rows, not chunk rows
-        ScorePartial *part = nullptr;                     // [pf_chunk][score_tiles(V)] tile partials of the statistics kernel
-        uint32_t *targets = nullptr;                      // [pf_chunk] the chunk's targets (a chunk graph reads them here, like m->tokens)
-        NanoHipTokenScore *rows = nullptr;                // [pf_chunk] the chunk's scores
-        bool use_targets = false;                         // of the call in progress: false = each row's own arg-max
-        uint32_t *stage = nullptr;                        // [max_seq_len] the call's targets on the device
-        NanoHipTokenScore *out = nullptr;                 // [max_seq_len] the call's scores, copied back once
-    } score;
-    // top-k alternatives (backend_topk.hip, topk.hip), allocated on the first call that asks for them -- apart from `score`, so that callers
-    // of the existing entry points allocate nothing new.  rows_cap = max(pf_chunk, max_batch): a decode step scores max_batch rows
-    struct Topk {
-        unsigned long long *part = nullptr;               // [rows_cap][score_tiles(V)][NANO_TOPK_MAX] the tiles' best keys
-        ScorePartial *spart = nullptr;                    // [rows_cap][score_tiles(V)] statistics partials of a decode step's rows (score.part holds pf_chunk rows)
-        uint32_t *targets = nullptr;                      // [rows_cap] a decode step's targets
-        NanoHipTokenScore *rows = nullptr;                // [rows_cap] a decode step's records
-        NanoHipTopEntry *out = nullptr;                   // [cap][NANO_TOPK_MAX] the call's entries (row i's k entries at i * k), copied back once
-        NanoHipTokenScore *sc = nullptr;                  // [cap] the records of a scored ragged step, pass order
-        uint32_t *tg = nullptr;                           // [cap] its targets, pass order
-        uint32_t rows_cap = 0, cap = 0;                   // cap >= max_seq_len: rows of one call
-    } tk;
+    // what calls get back per fed row (backend_rows.hip: rows_scratch is the one allocator, the rows_* functions the one sink).  Everything
+    // here is allocated on the first call whose RowWant needs it: nano_hip_forward / _decode_greedy allocate none of it, nano_hip_prefill the fed
+    // tokens and positions only, a model that never asks for k >= 1 neither keys nor entries.
+    struct RowScratch {
+        // pass buffers: enqueue_step's MODE_SCORE / MODE_VERIFY branches read and write them and chunk graphs hold their addresses, so each is
+        // allocated once and never moved.  R = max(pf_chunk, max_batch): a decode step scores max_batch rows
+        float *logits = nullptr;                          // [pf_chunk][V] a pass's logits: m->logits holds max_batch rows, not chunk rows
+        ScorePartial *part = nullptr;                     // [R][score_tiles(V)] tile partials of the statistics kernel
+        uint32_t *targets = nullptr;                      // [R] a pass's targets (a chunk graph reads them here, like m->tokens)
+        NanoHipTokenScore *rows = nullptr;                // [R] a pass's records
+        uint32_t *amax = nullptr;                         // [max(pf_chunk, LOOKUP_MAX_ROWS)] a pass's row arg-maxes (m->amax holds max_batch rows)
+        unsigned long long *keys = nullptr;               // [R][score_tiles(V)][NANO_TOPK_MAX] the tiles' best keys of the selection
+        bool use_targets = false;                         // of the call in progress (rows_begin): false = each row's own arg-max
+        // call buffers: one block of `cap` = max(max_seq_len, rows of the largest call so far) rows of what the calls so far needed (`have`).
+        // Only copies and eager launches outside any captured region touch them, so a larger or needier call replaces the block.
+        uint8_t *call = nullptr; uint32_t cap = 0, have = 0;
+        uint32_t *tok = nullptr, *pos = nullptr, *slot = nullptr;   // the call's fed tokens | positions | KV slots, in the order it feeds them
+        uint32_t *tgt = nullptr, *out_amax = nullptr;     // its targets; its row arg-maxes
+        NanoHipTokenScore *sc = nullptr;                  // its records
+        NanoHipTopEntry *top = nullptr;                   // [cap][NANO_TOPK_MAX] its entries (row i's k entries at i * k)
+    } rb;
     // greedy decode with lookup drafts (backend_lookup.hip), allocated on the first call that needs it
     struct Lookup {
         uint32_t *hist = nullptr; uint32_t cap = 0;       // slot 0's ids on the device (lookup.hip appends to them); cap = max_seq_len + 1 rounded up to 4
         std::vector<uint32_t> shadow;                     // what hist holds, host side: a history that extends it uploads only the new ids
         uint32_t *state = nullptr;                        // LookupArgs::state (4 words), then the step record (LOOKUP_REC_WORDS)
-        uint32_t *amax = nullptr;                         // [max(pf_chunk, 16)] row arg-maxes of a verify chunk (m->amax holds max_batch rows)
-        uint32_t *out = nullptr;                          // [max_seq_len] the row arg-maxes of a nano_hip_verify_draft call
         uint32_t *h_rec = nullptr;                        // pinned: the record of the last step
         bool graph = true;                                // verify chunks of the loop replay a graph per (K, range bucket); NANO_LOOKUP_GRAPH=0: eager
     } lk;
@@ -131,7 +126,6 @@ struct NanoHipModel {
         const uint32_t *row_slot = nullptr;               // device [nb]: the KV slot of each row of the pass
         struct Group { uint32_t row0, n, hint; };         // a contiguous run of the pass's rows that share a range hint: one attention launch
         std::vector<Group> groups;
-        uint32_t *stage = nullptr; uint32_t cap = 0;      // the call's tokens | positions | slots | row arg-maxes on the device, pass after pass (4 x cap words)
         float *vraw = nullptr;                            // [Bs][KD] fresh v rows of a pass on the contiguous FP32 cache (the FP16 cache has m->vraw)
     } rows;
     uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
@@ -204,19 +198,61 @@ int dev_err_check(NanoHipModel *m);
 void handoff_fallback(NanoHipModel *m);
 void drop_graphs(NanoHipModel *m);
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps);
-int score_scratch(NanoHipModel *m);
-int topk_scratch(NanoHipModel *m, size_t call_rows);   // backend_topk.hip: room for a call of call_rows rows
-void topk_free(NanoHipModel *m);
+// What a call wants of the rows it feeds, built by the extern "C" entry points: nothing, every row's arg-max (verify), or every row's score
+// record for targets (null: for its own arg-max) and -- k >= 1 -- its k best entries.  Every switch derived from that is answered here.
+struct RowWant {
+    enum Kind : uint32_t { NONE, ARGMAX, SCORE } kind = NONE;
+    const uint32_t *targets = nullptr; uint32_t k = 0;                      // SCORE: the caller's targets (host), entries per row
+    uint32_t *argmax_out = nullptr; NanoHipTokenScore *scores_out = nullptr; NanoHipTopEntry *top_out = nullptr;    // the caller's arrays, caller order
+    static RowWant argmaxes(uint32_t *out) { RowWant w; if (out) { w.kind = ARGMAX; w.argmax_out = out; } return w; }
+    static RowWant scores(const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+        RowWant w; w.kind = SCORE; w.targets = targets; w.k = k; w.scores_out = scores_out; w.top_out = top_out; return w;
+    }
+    bool use_targets() const { return kind == SCORE && targets; }
+    uint32_t mode_row() const { return kind == ARGMAX ? MODE_ARGMAX : kind == SCORE ? MODE_LOGITS : MODE_NOCLS; }     // step mode of a row fed alone
+    uint32_t mode_pass() const { return kind == ARGMAX ? MODE_VERIFY : kind == SCORE ? MODE_SCORE : MODE_NOCLS; }     // ... of a pass of several rows
+    // bits 56-57 of a chunk graph's key: 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify (different nodes: none replays another's graph)
+    uint32_t key_kind() const { return kind == ARGMAX ? 3u : kind == SCORE ? (targets ? 1u : 2u) : 0u; }
+    uint32_t need(bool passes) const;                                       // the result buffers of rows_scratch it uses; passes: MODE_SCORE / MODE_VERIFY passes run
+                                                                            // (false: every row is left in m->logits / m->amax -- reference-order steps, a decode step)
+};
+// rows_scratch's buffers: P_* pass buffers (P_STATS: partials, targets, records), C_* parts of the call block (C_FEED: tokens and positions)
+enum : uint32_t { P_LOGITS = 1, P_STATS = 2, P_AMAX = 4, P_KEYS = 8, C_FEED = 0x10, C_SLOT = 0x20, C_TGT = 0x40, C_SC = 0x80, C_AMAX = 0x100, C_TOP = 0x200, C_ALL = 0x3f0 };
+inline uint32_t RowWant::need(bool passes) const {
+    if (kind == ARGMAX) return (passes ? P_LOGITS | P_AMAX : 0u) | C_AMAX;
+    if (kind != SCORE) return 0u;
+    return (passes ? P_LOGITS : 0u) | P_STATS | C_SC | (targets ? C_TGT : 0u) | (k ? P_KEYS | C_TOP : 0u);
+}
+// ---- backend_rows.hip: the scratch and the sink of the row outputs ----
+// what every entry point with a RowWant refuses before anything is queued (m is not null)
+int rows_check(const NanoHipModel *m, const RowWant &w);
+// THE allocator of RowScratch: the pass buffers of `need` that are not there yet, and a call block that holds need's parts (and those of
+// earlier calls) for call_rows rows.  NANO_HIP_ENOMEM leaves the model usable: pass buffers as they were, and -- where the call block had
+// to be replaced (wait, free, allocate) -- no call block, so the next call allocates one.
+int rows_scratch(NanoHipModel *m, uint32_t need, size_t call_rows);
+void rows_free(NanoHipModel *m);
 // the selection behind the statistics: `rows` rows of logits (row stride V), their records in scores (queued before) -> out[rows][k]
 hipError_t enqueue_topk_rows(NanoHipModel *m, const float *logits, uint32_t rows, uint32_t k, const NanoHipTokenScore *scores, NanoHipTopEntry *out);
-// what every top-k entry point refuses before anything is queued (m is not null)
-int topk_check(const NanoHipModel *m, uint32_t k, const NanoHipTokenScore *scores_out, const NanoHipTopEntry *top_out);
-// batched prefill of one slot, as nano_hip_prefill / _prefill_score / _verify_draft (argmax_out: every row's arg-max) call it
-// k >= 1 (with score): the k entries of every fed position too -> top_out[count][k]; out may then be null
-int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, bool score, const uint32_t *targets, NanoHipTokenScore *out,
-                uint32_t *argmax_out = nullptr, uint32_t k = 0, NanoHipTopEntry *top_out = nullptr);
+// a call of `total` rows begins: room for w.need(passes) | more, rb.use_targets, and the targets (host, in the order the call feeds its rows) on the device
+int rows_begin(NanoHipModel *m, const RowWant &w, bool passes, uint32_t more, size_t total, const uint32_t *targets);
+// the call's tokens, positions and (null: none) KV slots, in feeding order, on the device once (pageable sources: the caller keeps them until it has waited)
+int rows_feed(NanoHipModel *m, size_t total, const uint32_t *tokens, const uint32_t *pos, const uint32_t *slots);
+// a step left rows 0 .. nb - 1 in m->logits / m->amax (a reference-order step of one row, a decode step): their statistics and selection,
+// or their arg-maxes, into the call's slots at ..
+hipError_t rows_after_step(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
+// a MODE_SCORE / MODE_VERIFY pass of nb rows is to run: its targets from the call's; it has run: its records or arg-maxes into the call's
+// slots at .., and the selection on its logits before the next pass overwrites them
+hipError_t rows_pass_targets(NanoHipModel *m, size_t at, uint32_t nb);
+hipError_t rows_after_pass(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
+// strict / exact mode: the call's rows one by one, each a reference-order step on its staged token and position in KV slot row_slot[i] (null: slot)
+int rows_run_ordered(NanoHipModel *m, const RowWant &w, size_t total, uint32_t slot, const uint32_t *row_slot);
+// the call's results to the caller's arrays and the call's one wait (check: then dev_err_check).  where (null: feeding order is caller
+// order, straight into the caller's arrays): caller row r was fed as row where[r]
+int rows_back(NanoHipModel *m, const RowWant &w, size_t total, const uint32_t *where, bool check);
+// batched prefill of one slot, as nano_hip_prefill / _prefill_score / _prefill_score_topk / _verify_draft call it
+int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, const RowWant &want);
 // one prefill chunk of nb rows of `slot` (m->tokens / m->pos hold them; last_pos = the last row's position), eager or -- replay -- through the
-// bounded cache of chunk graphs under `key_kind` (bits 56-57 of the key: 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify)
+// bounded cache of chunk graphs under `key_kind` (RowWant::key_kind)
 hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind);
 int lookup_scratch(NanoHipModel *m);                   // backend_lookup.hip
 void lookup_free(NanoHipModel *m);
@@ -264,8 +300,7 @@ void sampler_free(Sampler *sp);                        // backend_sampler.hip
 
 // ---- backend_step.hip ----
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr, float *dst = nullptr);    // dst: nullptr = m->logits
-hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out,
-                              ScorePartial *part = nullptr);      // part: nullptr = m->score.part (pf_chunk rows)
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out);
 hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint);
 bool strict_serves(const NanoHipModel *m);
 bool exact_serves(const NanoHipModel *m);

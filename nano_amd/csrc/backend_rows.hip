@@ -1,9 +1,132 @@
-// backend_rows.hip -- ragged steps (nano_hip_step_rows): rows that each carry their own (KV slot, position).  The planner that cuts a
-// call's rows into passes (device-free, queryable), the host predicate of what the row map can address, and the entry point that stages
-// the call once and queues its passes through enqueue_step (backend_step.hip: m->rows).
+// backend_rows.hip -- what calls get back per fed row, and ragged steps.
+// Row outputs (RowWant, backend_model.h): the one allocator of their scratch (rows_scratch), the sink that batched prefill (backend.hip),
+// ragged steps and the decode step with scores (nano_hip_forward_topk, below) share, and the one loop of strict / exact mode.
+// Ragged steps (nano_hip_step_rows): rows that each carry their own (KV slot, position).  The planner that cuts a call's rows into passes
+// (device-free, queryable), the host predicate of what the row map can address, and the entry point that stages the call once and queues
+// its passes through enqueue_step (backend_step.hip: m->rows).
 #include <algorithm>
 
 #include "backend_model.h"
+
+int rows_check(const NanoHipModel *m, const RowWant &w) {
+    if (w.kind != RowWant::SCORE) return 0;
+    if (w.k > NANO_TOPK_MAX) FAIL(NANO_HIP_EINVAL, "k = %u exceeds NANO_TOPK_MAX (%u)", w.k, NANO_TOPK_MAX);
+    if (w.k > m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "k = %u exceeds the vocabulary (%u)", w.k, m->d.vocab_size);
+    if (w.k ? !w.top_out : !w.scores_out) FAIL(NANO_HIP_EINVAL, "null argument");
+    return 0;
+}
+
+static size_t pass_rows(const NanoHipModel *m) { return std::max<size_t>(m->pf_chunk, m->maxB); }
+void rows_free(NanoHipModel *m) {
+    NanoHipModel::RowScratch &s = m->rb;
+    void *dev[] = { s.logits, s.part, s.targets, s.rows, s.amax, s.keys, s.call };
+    for (void *p : dev) if (p) (void)hipFree(p);
+    s = NanoHipModel::RowScratch();
+}
+int rows_scratch(NanoHipModel *m, uint32_t need, size_t call_rows) {
+    NanoHipModel::RowScratch &s = m->rb;
+    const size_t V = m->d.vocab_size, nt = score_tiles((uint32_t)V), R = pass_rows(m);
+    struct Buf { uint32_t bit; void **p; size_t bytes; };                   // (of the call block: bytes per row)
+    auto P = [](auto **p) { return reinterpret_cast<void **>(p); };
+    // pass buffers: allocated once each; a failure frees what this call added
+    const Buf pass[] = { { P_LOGITS, P(&s.logits), m->pf_chunk * V * 4 }, { P_STATS, P(&s.part), R * nt * sizeof(ScorePartial) }, { P_STATS, P(&s.targets), R * 4 },
+                         { P_STATS, P(&s.rows), R * sizeof(NanoHipTokenScore) }, { P_AMAX, P(&s.amax), std::max<size_t>(m->pf_chunk, LOOKUP_MAX_ROWS) * 4 },
+                         { P_KEYS, P(&s.keys), R * nt * NANO_TOPK_MAX * sizeof(unsigned long long) } };
+    void **fresh[sizeof pass / sizeof *pass]; size_t n_fresh = 0;
+    for (const Buf &b : pass) {
+        if (!(need & b.bit) || *b.p) continue;
+        if (hipMalloc(b.p, b.bytes) == hipSuccess) { fresh[n_fresh++] = b.p; continue; }
+        (void)hipGetLastError();
+        *b.p = nullptr;
+        while (n_fresh) { void **f = fresh[--n_fresh]; (void)hipFree(*f); *f = nullptr; }
+        FAIL(NANO_HIP_ENOMEM, "hipMalloc of the row outputs' pass buffers failed (%zu rows, %zu logits each)", R, V);
+    }
+    // the call block: one capacity, one grow path (wait for the stream, free, allocate), one allocation to unwind
+    const uint32_t parts = s.have | (need & C_ALL);
+    if (!call_rows || (parts == s.have && call_rows <= s.cap)) return 0;
+    const size_t cap = std::max<size_t>({ (size_t)m->S, call_rows, (size_t)s.cap });
+    const Buf call[] = { { C_FEED, P(&s.tok), 4 }, { C_FEED, P(&s.pos), 4 }, { C_SLOT, P(&s.slot), 4 }, { C_TGT, P(&s.tgt), 4 }, { C_AMAX, P(&s.out_amax), 4 },
+                         { C_SC, P(&s.sc), sizeof(NanoHipTokenScore) }, { C_TOP, P(&s.top), NANO_TOPK_MAX * sizeof(NanoHipTopEntry) } };
+    if (s.call) { HIP_TRY(hipStreamSynchronize(m->st)); (void)hipFree(s.call); }
+    s.call = nullptr; s.cap = s.have = 0;
+    size_t bytes = 0;
+    for (const Buf &b : call) { *b.p = nullptr; if (parts & b.bit) bytes += align_up(cap * b.bytes, 256); }
+    if (hipMalloc(reinterpret_cast<void **>(&s.call), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s.call = nullptr;
+        FAIL(NANO_HIP_ENOMEM, "hipMalloc of the row outputs' buffers of a call of %zu rows failed", cap);
+    }
+    size_t off = 0;
+    for (const Buf &b : call) { *b.p = (parts & b.bit) ? s.call + off : nullptr; if (parts & b.bit) off += align_up(cap * b.bytes, 256); }
+    s.cap = (uint32_t)cap; s.have = parts;
+    return 0;
+}
+
+hipError_t enqueue_topk_rows(NanoHipModel *m, const float *logits, uint32_t rows, uint32_t k, const NanoHipTokenScore *scores, NanoHipTopEntry *out) {
+    if (rows > pass_rows(m)) return hipErrorInvalidValue;
+    TopkArgs a{};
+    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.k = k; a.part = m->rb.keys; a.scores = scores; a.out = out;
+    return launch_topk_rows(a, rows, m->st);
+}
+
+// ---- the sink (backend_model.h says what each does) ----
+int rows_begin(NanoHipModel *m, const RowWant &w, bool passes, uint32_t more, size_t total, const uint32_t *targets) {
+    if (const int rc = rows_scratch(m, w.need(passes) | more, total)) return rc;
+    m->rb.use_targets = w.use_targets();
+    if (w.use_targets() && total) HIP_TRY(hipMemcpyAsync(m->rb.tgt, targets, total * 4, hipMemcpyHostToDevice, m->st));     // (a pageable source)
+    return 0;
+}
+int rows_feed(NanoHipModel *m, size_t total, const uint32_t *tokens, const uint32_t *pos, const uint32_t *slots) {
+    HIP_TRY(hipMemcpyAsync(m->rb.tok, tokens, total * 4, hipMemcpyHostToDevice, m->st));          // (pageable sources: staged by the runtime before the call returns)
+    HIP_TRY(hipMemcpyAsync(m->rb.pos, pos, total * 4, hipMemcpyHostToDevice, m->st));
+    if (slots) HIP_TRY(hipMemcpyAsync(m->rb.slot, slots, total * 4, hipMemcpyHostToDevice, m->st));
+    return 0;
+}
+hipError_t rows_after_step(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb) {
+    const NanoHipModel::RowScratch &s = m->rb;
+    if (w.kind == RowWant::ARGMAX) return hipMemcpyAsync(s.out_amax + at, m->amax, nb * 4, hipMemcpyDeviceToDevice, m->st);
+    if (w.kind != RowWant::SCORE) return hipSuccess;
+    const hipError_t e = enqueue_score_rows(m, m->logits, nb, s.use_targets ? s.tgt + at : nullptr, s.sc + at);
+    return (e != hipSuccess || !w.k) ? e : enqueue_topk_rows(m, m->logits, nb, w.k, s.sc + at, s.top + at * w.k);
+}
+hipError_t rows_pass_targets(NanoHipModel *m, size_t at, uint32_t nb) {
+    const NanoHipModel::RowScratch &s = m->rb;
+    return s.use_targets ? hipMemcpyAsync(s.targets, s.tgt + at, nb * 4, hipMemcpyDeviceToDevice, m->st) : hipSuccess;
+}
+hipError_t rows_after_pass(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb) {
+    const NanoHipModel::RowScratch &s = m->rb;
+    if (w.kind == RowWant::ARGMAX) return hipMemcpyAsync(s.out_amax + at, s.amax, nb * 4, hipMemcpyDeviceToDevice, m->st);
+    if (w.kind != RowWant::SCORE) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(s.sc + at, s.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st);
+    return (e != hipSuccess || !w.k) ? e : enqueue_topk_rows(m, s.logits, nb, w.k, s.rows, s.top + at * w.k);
+}
+int rows_run_ordered(NanoHipModel *m, const RowWant &w, size_t total, uint32_t slot, const uint32_t *row_slot) {
+    for (size_t i = 0; i < total; i++) {
+        HIP_TRY(hipMemcpyAsync(m->tokens, m->rb.tok + i, 4, hipMemcpyDeviceToDevice, m->st));
+        HIP_TRY(hipMemcpyAsync(m->pos, m->rb.pos + i, 4, hipMemcpyDeviceToDevice, m->st));
+        if (const int rc = run_step_ordered(m, 1, 1, w.mode_row(), row_slot ? row_slot[i] : slot)) return rc;
+        HIP_TRY(rows_after_step(m, w, i, 1));
+    }
+    return 0;
+}
+int rows_back(NanoHipModel *m, const RowWant &w, size_t total, const uint32_t *where, bool check) {
+    const NanoHipModel::RowScratch &s = m->rb;
+    const bool score = w.kind == RowWant::SCORE;
+    const size_t k = score ? w.k : 0;
+    // (where: through host copies in feeding order, gathered after the wait)
+    std::vector<uint32_t> amax(where && w.kind == RowWant::ARGMAX ? total : 0);
+    std::vector<NanoHipTokenScore> sc(where && score && w.scores_out ? total : 0);
+    std::vector<NanoHipTopEntry> top(where ? total * k : 0);
+    if (w.kind == RowWant::ARGMAX) HIP_TRY(hipMemcpyAsync(where ? amax.data() : w.argmax_out, s.out_amax, total * 4, hipMemcpyDeviceToHost, m->st));
+    if (k) HIP_TRY(hipMemcpyAsync(where ? top.data() : w.top_out, s.top, total * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost, m->st));
+    if (score && w.scores_out) HIP_TRY(hipMemcpyAsync(where ? sc.data() : w.scores_out, s.sc, total * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipStreamSynchronize(m->st));                                   // the call's one wait
+    if (check) { if (const int rc = dev_err_check(m)) return rc; }
+    for (size_t r = 0; r < amax.size(); r++) w.argmax_out[r] = amax[where[r]];
+    for (size_t r = 0; r < sc.size(); r++) w.scores_out[r] = sc[where[r]];
+    for (size_t r = 0; r < (top.empty() ? 0 : total); r++) std::copy(top.begin() + where[r] * k, top.begin() + (where[r] + 1) * k, w.top_out + r * k);
+    return 0;
+}
 
 namespace {
 // how a call's rows are cut: per row in caller order its pass, its row inside the pass and its range hint
@@ -83,14 +206,13 @@ static hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, uint32_t mode,
     return e;
 }
 
-// A ragged step, as nano_hip_step_rows (argmax_out: every row's arg-max, may be null) and nano_hip_step_rows_score (score: every row's
-// record for targets -- null: its own arg-max -- and, k >= 1, its k entries) call it.  A scoring pass is a MODE_SCORE pass: the classifier
-// over all its rows into score.logits and the statistics for the pass's targets, staged in pass order; the selection's two launches
-// follow eagerly on the same buffers.  Records and entries are gathered to caller order through where[].
-static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out,
-                         bool score, const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+// A ragged step, as nano_hip_step_rows (every row's arg-max, or nothing) and nano_hip_step_rows_score (every row's record and, k >= 1, its
+// k entries) call it.  A scoring pass is a MODE_SCORE pass: the classifier over all its rows and the statistics for the pass's targets,
+// staged in pass order; the selection's two launches follow eagerly on the same buffers (rows_after_pass).  Results are gathered to caller
+// order through where[].
+static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, const RowWant &want) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
-    if (score) { if (const int rc = topk_check(m, k, scores_out, top_out)) return rc; }
+    if (const int rc = rows_check(m, want)) return rc;
     if (n_segs == 0) return 0;
     if (!segs) FAIL(NANO_HIP_EINVAL, "null argument");
     const uint32_t cap = nano_hip_prefill_chunk_tokens(m);
@@ -103,42 +225,20 @@ static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_
         if ((uint64_t)segs[i].pos0 + segs[i].count > m->rope_rows) FAIL(NANO_HIP_EINVAL, "segment %u: positions %u..%u exceed the model's RoPE table (%u rows = block_size)", i, segs[i].pos0, segs[i].pos0 + segs[i].count, m->rope_rows);
     }
     for (size_t r = 0; r < total; r++) if (tokens[r] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "token %u out of vocabulary", tokens[r]);
-    if (score && targets) for (size_t r = 0; r < total; r++) if (targets[r] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", targets[r]);
+    if (want.use_targets()) for (size_t r = 0; r < total; r++) if (want.targets[r] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", want.targets[r]);
     if (m->lora_on) FAIL(NANO_HIP_EINVAL, "ragged steps are not available with the LoRA side branches (their v branch addresses the cache by a flat stride)");
     if (!m->kv.paged && !nano_hip_rows_addressable(m->d.n_layer, m->S, m->KD, (uint32_t)kv_esz(m)))
         FAIL(NANO_HIP_EINVAL, "the row map cannot address a cache of %u layers x %u positions x %u elements", m->d.n_layer, m->S, m->KD);
     if (total == 0) return 0;
     HIP_TRY(hipSetDevice(m->device));
     if (const int rc = step_served(m, true)) return rc;
-    const bool verify = argmax_out != nullptr, ordered = strict_serves(m) || exact_serves(m);
-    if (verify) {
-        int rc = score_scratch(m);
-        if (!rc) rc = lookup_scratch(m);
-        if (rc) return rc;
-    }
-    if (score) {
-        int rc = score_scratch(m);
-        if (!rc) rc = topk_scratch(m, total);
-        if (rc) return rc;
-    }
+    const bool ordered = strict_serves(m) || exact_serves(m);
     if (!ordered && !m->kv_half && !m->kv.paged && !m->rows.vraw && hipMalloc(reinterpret_cast<void **>(&m->rows.vraw), (size_t)m->Bs * m->KD * 4) != hipSuccess) {
         (void)hipGetLastError();
         FAIL(NANO_HIP_ENOMEM, "hipMalloc of the ragged steps' v scratch failed");
     }
-    if (total > m->rows.cap) {
-        if (m->rows.stage) { HIP_TRY(hipStreamSynchronize(m->st)); (void)hipFree(m->rows.stage); m->rows.stage = nullptr; m->rows.cap = 0; }
-        const size_t want = std::max<size_t>(total, (size_t)m->S);
-        if (hipMalloc(reinterpret_cast<void **>(&m->rows.stage), want * 16) != hipSuccess) { (void)hipGetLastError(); FAIL(NANO_HIP_ENOMEM, "hipMalloc of the ragged steps' staging buffer failed"); }
-        m->rows.cap = (uint32_t)want;
-    }
-    if (m->kv.paged) {                                                      // every page of every segment, all or nothing, before anything is queued
-        std::vector<uint32_t> slots, first, need;
-        for (uint32_t i = 0; i < n_segs; i++)
-            if (segs[i].count) { slots.push_back(segs[i].slot); first.push_back(segs[i].pos0); need.push_back(segs[i].pos0 + segs[i].count - 1); }
-        if (const int rc = kv_ensure(m, slots.data(), first.data(), need.data(), (uint32_t)slots.size())) return rc;
-    }
-    // the call's rows in pass order: where caller row r went, and its token, position and slot there -- on the device ONCE
-    std::vector<uint32_t> pass_start(plan.n_passes + 1, 0u), where(total), stage(3 * total), tstage(score && targets ? total : 0);
+    // the call's rows in pass order: where caller row r went, and its token, position, slot and target there -- on the device ONCE
+    std::vector<uint32_t> pass_start(plan.n_passes + 1, 0u), where(total), stage(3 * total), tstage(want.use_targets() ? total : 0);
     for (size_t r = 0; r < total; r++) pass_start[plan.pass[r] + 1]++;
     for (uint32_t p = 0; p < plan.n_passes; p++) pass_start[p + 1] += pass_start[p];
     {
@@ -147,68 +247,69 @@ static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_
             for (uint32_t j = 0; j < segs[i].count; j++, r++) {
                 const size_t w = where[r] = pass_start[plan.pass[r]] + plan.index[r];
                 stage[w] = tokens[r]; stage[total + w] = segs[i].pos0 + j; stage[2 * total + w] = segs[i].slot;
-                if (!tstage.empty()) tstage[w] = targets[r];
+                if (!tstage.empty()) tstage[w] = want.targets[r];
             }
     }
-    uint32_t *const d_tok = m->rows.stage, *const d_pos = d_tok + m->rows.cap, *const d_slot = d_pos + m->rows.cap, *const d_amax = d_slot + m->rows.cap;
-    HIP_TRY(hipMemcpyAsync(d_tok, stage.data(), total * 4, hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(d_pos, stage.data() + total, total * 4, hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(d_slot, stage.data() + 2 * total, total * 4, hipMemcpyHostToDevice, m->st));
-    const uint32_t *const d_tgt = tstage.empty() ? nullptr : m->tk.tg;       // the call's targets, pass order
-    if (d_tgt) HIP_TRY(hipMemcpyAsync(m->tk.tg, tstage.data(), total * 4, hipMemcpyHostToDevice, m->st));
-    if (score) m->score.use_targets = d_tgt != nullptr;
+    if (m->kv.paged) {                                                      // every page of every segment, all or nothing, before anything is queued
+        std::vector<uint32_t> slots, first, need;
+        for (uint32_t i = 0; i < n_segs; i++)
+            if (segs[i].count) { slots.push_back(segs[i].slot); first.push_back(segs[i].pos0); need.push_back(segs[i].pos0 + segs[i].count - 1); }
+        if (const int rc = kv_ensure(m, slots.data(), first.data(), need.data(), (uint32_t)slots.size())) return rc;
+    }
+    if (const int rc = rows_begin(m, want, !ordered, C_FEED | C_SLOT, total, tstage.data())) return rc;
+    if (const int rc = rows_feed(m, total, stage.data(), stage.data() + total, stage.data() + 2 * total)) return rc;
     if (ordered) {
         // strict / exact mode: one pass = one row (cap 1, so pass order is caller order): a reference-order step in the row's slot
-        const uint32_t mode1 = verify ? MODE_ARGMAX : score ? MODE_LOGITS : MODE_NOCLS;
-        for (size_t w = 0; w < total; w++) {
-            HIP_TRY(hipMemcpyAsync(m->tokens, d_tok + w, 4, hipMemcpyDeviceToDevice, m->st));
-            HIP_TRY(hipMemcpyAsync(m->pos, d_pos + w, 4, hipMemcpyDeviceToDevice, m->st));
-            if (const int rc = run_step_ordered(m, 1, 1, mode1, stage[2 * total + w])) return rc;
-            if (verify) HIP_TRY(hipMemcpyAsync(d_amax + w, m->amax, 4, hipMemcpyDeviceToDevice, m->st));
-            if (score) {                                                   // the row's logits are row 0 of m->logits, as in prefill_run
-                HIP_TRY(enqueue_score_rows(m, m->logits, 1, d_tgt ? d_tgt + w : nullptr, m->tk.sc + w));
-                if (k) HIP_TRY(enqueue_topk_rows(m, m->logits, 1, k, m->tk.sc + w, m->tk.out + w * k));
-            }
-        }
+        if (const int rc = rows_run_ordered(m, want, total, 0, stage.data() + 2 * total)) return rc;
     } else {
         for (uint32_t p = 0; p < plan.n_passes; p++) {
             const size_t w0 = pass_start[p];
             const uint32_t nb = pass_start[p + 1] - pass_start[p];
-            HIP_TRY(hipMemcpyAsync(m->tokens, d_tok + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
-            HIP_TRY(hipMemcpyAsync(m->pos, d_pos + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
+            HIP_TRY(hipMemcpyAsync(m->tokens, m->rb.tok + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
+            HIP_TRY(hipMemcpyAsync(m->pos, m->rb.pos + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
             m->rows.groups.clear();
             for (uint32_t j = 0; j < nb; j++) {                            // (sorted by hint: a group is a run of equal hints)
                 const uint32_t pos = stage[total + w0 + j], h = range_hint_of(m, 1, 1, pos);
                 if (m->rows.groups.empty() || m->rows.groups.back().hint != h) m->rows.groups.push_back({j, 1u, h});
                 else m->rows.groups.back().n++;
             }
-            if (d_tgt) HIP_TRY(hipMemcpyAsync(m->score.targets, d_tgt + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
-            HIP_TRY(enqueue_rows_pass(m, nb, verify ? MODE_VERIFY : score ? MODE_SCORE : MODE_NOCLS, d_slot + w0));
-            if (verify) HIP_TRY(hipMemcpyAsync(d_amax + w0, m->lk.amax, nb * 4, hipMemcpyDeviceToDevice, m->st));
-            if (score) {
-                HIP_TRY(hipMemcpyAsync(m->tk.sc + w0, m->score.rows, nb * sizeof(NanoHipTokenScore), hipMemcpyDeviceToDevice, m->st));
-                if (k) HIP_TRY(enqueue_topk_rows(m, m->score.logits, nb, k, m->score.rows, m->tk.out + w0 * k));
-            }
+            HIP_TRY(rows_pass_targets(m, w0, nb));
+            HIP_TRY(enqueue_rows_pass(m, nb, want.mode_pass(), m->rb.slot + w0));
+            HIP_TRY(rows_after_pass(m, want, w0, nb));
         }
     }
-    std::vector<uint32_t> amax(verify ? total : 0);
-    std::vector<NanoHipTokenScore> sc(score && scores_out ? total : 0);
-    std::vector<NanoHipTopEntry> top(score ? total * k : 0);
-    if (verify) HIP_TRY(hipMemcpyAsync(amax.data(), d_amax, total * 4, hipMemcpyDeviceToHost, m->st));
-    if (!sc.empty()) HIP_TRY(hipMemcpyAsync(sc.data(), m->tk.sc, total * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost, m->st));
-    if (!top.empty()) HIP_TRY(hipMemcpyAsync(top.data(), m->tk.out, total * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipStreamSynchronize(m->st));                                   // the call's one wait
-    if (const int rc = dev_err_check(m)) return rc;
-    for (size_t r = 0; r < (verify ? total : 0); r++) argmax_out[r] = amax[where[r]];
-    for (size_t r = 0; r < (sc.empty() ? 0 : total); r++) scores_out[r] = sc[where[r]];
-    for (size_t r = 0; r < (top.empty() ? 0 : total); r++) std::copy(top.begin() + where[r] * k, top.begin() + (where[r] + 1) * k, top_out + r * k);
-    return 0;
+    return rows_back(m, want, total, where.data(), true);
 }
 
 extern "C" int nano_hip_step_rows(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens, uint32_t *argmax_out) {
-    return step_rows_run(m, segs, n_segs, tokens, argmax_out, false, nullptr, 0, nullptr, nullptr);
+    return step_rows_run(m, segs, n_segs, tokens, RowWant::argmaxes(argmax_out));
 }
 extern "C" int nano_hip_step_rows_score(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens,
                                         const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
-    return step_rows_run(m, segs, n_segs, tokens, nullptr, true, targets, k, scores_out, top_out);
+    return step_rows_run(m, segs, n_segs, tokens, RowWant::scores(targets, k, scores_out, top_out));
+}
+
+// The decode step with scores: the step as nano_hip_forward_begin queues it with logits wanted (without the copy of the logits), the
+// statistics and the selection on its rows of m->logits, the results back, the wait.  A hand-off that gave up: the same step once more
+// through the plain launches, as nano_hip_forward_end does (with_reissue takes the sticky word: no check in rows_back).
+extern "C" int nano_hip_forward_topk(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                     const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
+    const RowWant want = RowWant::scores(targets, k, scores_out, top_out);
+    int rc;
+    if ((rc = rows_check(m, want))) return rc;
+    if ((rc = check_batch(m, tokens, pos, batch, 0))) return rc;
+    if (targets) for (uint32_t i = 0; i < batch; i++) if (targets[i] >= m->d.vocab_size) FAIL(NANO_HIP_EINVAL, "target %u out of vocabulary", targets[i]);
+    HIP_TRY(hipSetDevice(m->device));
+    if ((rc = step_served(m, false))) return rc;
+    if ((rc = rows_begin(m, want, false, 0, batch, targets))) return rc;     // (the step's rows are in m->logits: no pass buffer for logits)
+    return with_reissue(m, [&](bool) {
+        int rc;
+        if ((rc = kv_ensure_batch(m, pos, batch, 0, false))) return rc;
+        uint32_t max_pos = 0;
+        if ((rc = stage_batch(m, tokens, pos, batch, false, &max_pos))) return rc;
+        if ((rc = run_step(m, batch, 1u, MODE_LOGITS, max_pos))) return rc;
+        HIP_TRY(rows_after_step(m, want, 0, batch));
+        return rows_back(m, want, batch, nullptr, false);
+    });
 }

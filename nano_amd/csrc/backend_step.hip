@@ -47,9 +47,9 @@ hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out
     return gemv(m, a);
 }
 // the row statistics of `rows` rows of logits (row stride V) for targets[rows] (nullptr: each row's own arg-max) -> out[rows]  (score.hip)
-hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out, ScorePartial *part) {
+hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out) {
     ScoreArgs a{};
-    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.targets = targets; a.part = part ? part : m->score.part; a.out = out;
+    a.logits = logits; a.V = m->d.vocab_size; a.ntiles = score_tiles(a.V); a.targets = targets; a.part = m->rb.part; a.out = out;
     return launch_score_rows(a, rows, m->st);
 }
 // attention splits of a step: batches bring their own parallelism (nb x KV groups workgroups per split) and every
@@ -283,12 +283,12 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
     }
     if (mode == MODE_NOCLS) return hipSuccess;
     if (mode == MODE_SCORE) {       // a scoring prefill chunk: the classifier over all nb rows (final rmsnorm in its prologue), then their statistics
-        if ((e = enqueue_classifier(m, nb, nullptr, m->score.logits)) != hipSuccess) return e;
-        return enqueue_score_rows(m, m->score.logits, nb, m->score.use_targets ? m->score.targets : nullptr, m->score.rows);
+        if ((e = enqueue_classifier(m, nb, nullptr, m->rb.logits)) != hipSuccess) return e;
+        return enqueue_score_rows(m, m->rb.logits, nb, m->rb.use_targets ? m->rb.targets : nullptr, m->rb.rows);
     }
     if (mode == MODE_VERIFY) {      // a verify chunk: the classifier over all nb rows, then every row's arg-max (a scan of its logits: the partials buffer holds max_batch rows)
-        if ((e = enqueue_classifier(m, nb, nullptr, m->score.logits)) != hipSuccess) return e;
-        ArgmaxArgs aa{ m->score.logits, d.vocab_size, d.vocab_size, m->lk.amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
+        if ((e = enqueue_classifier(m, nb, nullptr, m->rb.logits)) != hipSuccess) return e;
+        ArgmaxArgs aa{ m->rb.logits, d.vocab_size, d.vocab_size, m->rb.amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
         return launch_argmax(aa, nb, m->st);
     }
     const bool sample = (mode == MODE_ARGMAX || mode == MODE_LOOP);
