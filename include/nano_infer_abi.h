@@ -215,7 +215,10 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
  * n_history[i] ids the repetition penalty marks (histories / n_history may be NULL: no history).  Each sampler's coin comes from its
  * own rng_state, drawn only when its temperature is not 0.  The rows are sampled on the device; rows it declines, and every row under
  * NANO_HOST_SAMPLER=1, go through the host loops.  With replicas, each replica's share is served by its own batched call, one replica
- * after another (not concurrently).  Returns 0 or a negative NANO_HIP_E* code. */
+ * after another (not concurrently).  Returns 0 or a negative NANO_HIP_E* code.
+ * Sampler.top_k is stored and ignored here and in generate_next_token, as in the reference.  With NANO_SAMPLE_TOP_K=1 in the
+ * environment (read once) both pass it to the device sampler and the host loops apply the same truncation: the sorted candidates are
+ * cut to the first top_k in front of the top-p cut (nano_mi355x.h, "top-k truncation"); top_k == 0 stays off. */
 int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                               Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
                               uint32_t *out_ids);

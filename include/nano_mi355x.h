@@ -394,6 +394,35 @@ int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *tokens, const
 int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, uint32_t batch,
                              const NanoHipSampleParams *params, NanoHipSample *out);
 
+/* ---- top-k truncation in front of the top-p cut -----------------------------------------------------------
+ * The calls above with one more row parameter; they are these calls with top_k = 0, and top_k == 0 is that sampler field for field.
+ * For top_k >= 1 the result is that of sample_top_p (reference infer/infer.c:1062-1109) with one statement added behind its qsort:
+ *     if (top_k > 0 && (uint32_t)n0 > top_k) n0 = top_k;
+ * The softmax denominator runs over all V tokens and the candidates are p >= cutoff as before; the stable descending sort (equal
+ * probabilities in index order) is cut to its first min(n0, top_k) entries, and the cut loop and the draw run on that list: `last` is
+ * the first running sum above top_p, else the list's last entry; r = coin * cdf[last]; the pick is the first running sum above r, else
+ * `last`.  So:
+ *   - n_candidates stays the count of p >= cutoff;
+ *   - nucleus = last + 1 <= top_k;
+ *   - top[i] is 0 for i >= min(n0, top_k);
+ *   - sum_bits and walked_chunks do not depend on top_k;
+ *   - temperature 0 ignores top_k;
+ *   - n_sorted is a diagnostic (>= nucleus) and otherwise unspecified for top_k >= 1;
+ *   - any top_k >= 1 is accepted, and a top_k of V or more changes nothing.
+ * With more candidates than the LDS sorter holds, only the histogram bins down to the one in which the count reaches top_k are sorted
+ * (or down to the bin of the top-p cut, whichever comes first), so a flat distribution with a small top_k stays out of the wide phase;
+ * a row whose leading bin alone exceeds the sorter (all logits equal) still goes there and is truncated in the same way.
+ * NANO_HIP_EINVAL before anything is queued for a non-zero reserved word, and for everything the calls above refuse. */
+typedef struct NanoHipSampleParamsEx {
+    NanoHipSampleParams p;
+    uint32_t top_k;
+    uint32_t reserved[3];
+} NanoHipSampleParamsEx;   /* top_k 0 = off; reserved must be 0 */
+int nano_hip_forward_sample_batch_ex(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                     const NanoHipSampleParamsEx *params, NanoHipSample *out);
+int nano_hip_op_sample_batch_ex(NanoHipModel *m, const float *logits, uint32_t batch,
+                                const NanoHipSampleParamsEx *params, NanoHipSample *out);
+
 /* ---- strict-parity / per-phase mode -------------------------------------------------------------------------
  * nano_hip_set_strict(m, 1): every later forward / prefill runs eagerly, one kernel per reference operator, with
  * every float reduction (rmsnorm, q.k, softmax sum, weighted V, FP32 matmul) in the reference's sequential order

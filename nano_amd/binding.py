@@ -204,6 +204,8 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_sample", C.c_int, [vp, f32p, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
     fn("nano_hip_forward_sample_batch", C.c_int, [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParams), C.POINTER(NanoHipSample)])
     fn("nano_hip_op_sample_batch", C.c_int, [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParams), C.POINTER(NanoHipSample)])
+    fn("nano_hip_forward_sample_batch_ex", C.c_int, [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEx), C.POINTER(NanoHipSample)])
+    fn("nano_hip_op_sample_batch_ex", C.c_int, [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEx), C.POINTER(NanoHipSample)])
     fn("nano_hip_sync", C.c_int, [vp])
     fn("nano_hip_set_strict", C.c_int, [vp, C.c_int])
     fn("nano_hip_set_phase_hook", C.c_int, [vp, PHASE_FN, vp])
@@ -343,6 +345,23 @@ def sample_params(rows):
         h = np.ascontiguousarray(hist if hist is not None else [], np.uint32).reshape(-1)
         keep.append(h)
         arr[i] = NanoHipSampleParams(rp, temp, top_p, coin, h.ctypes.data_as(C.POINTER(C.c_uint32)) if h.size else None, h.size)
+    return arr, keep
+
+
+class NanoHipSampleParamsEx(C.Structure):
+    """A row with top-k truncation in front of the top-p cut (include/nano_mi355x.h NanoHipSampleParamsEx): top_k 0 = off."""
+    _fields_ = [("p", NanoHipSampleParams), ("top_k", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def sample_params_ex(rows, top_k):
+    """sample_params() with row i's top_k: one int for all rows, or one per row"""
+    base, keep = sample_params(rows)
+    ks = [int(top_k)] * len(rows) if np.isscalar(top_k) else [int(k) for k in top_k]
+    assert len(ks) == len(rows)
+    arr = (NanoHipSampleParamsEx * len(rows))()
+    for i, k in enumerate(ks):
+        arr[i].p = base[i]
+        arr[i].top_k = k
     return arr, keep
 
 
@@ -502,41 +521,55 @@ class DeviceModel:
         """How step_rows() cuts these segments in the model's current mode: rows_plan(segs, prefill_chunk_tokens(), max_seq_len)."""
         return rows_plan(segs, self.prefill_chunk_tokens(), max_seq_len)
 
+    # top_k= on the four helpers below: the default, the int 0, is the entry point without top_k; anything else -- an int >= 1, or one
+    # value per row (zeros included) -- goes through the _ex entry point (nano_mi355x.h, "top-k truncation").
     def forward_sample(self, token: int, pos: int, history: Sequence[int], repetition_penalty: float, temperature: float,
-                       top_p: float, coin: float) -> NanoHipSample:
+                       top_p: float, coin: float, top_k: int = 0) -> NanoHipSample:
         """One decode step of slot 0 + the reference's sampler on the device (infer.c:1156-1189)."""
+        if top_k != 0:
+            return self.forward_sample_batch([token], [pos], [(repetition_penalty, temperature, top_p, coin, history)], top_k=[top_k])[0]
         h = np.ascontiguousarray(history, np.uint32).reshape(-1)
         r = NanoHipSample()
         check(lib().nano_hip_forward_sample(self.h, token, pos, h, h.size, repetition_penalty, temperature, top_p, coin, C.byref(r)))
         return r
 
     def op_sample(self, logits: np.ndarray, history: Sequence[int], repetition_penalty: float, temperature: float,
-                  top_p: float, coin: float) -> NanoHipSample:
+                  top_p: float, coin: float, top_k: int = 0) -> NanoHipSample:
         """The device sampler alone, on host-provided logits (V floats)."""
         l = np.ascontiguousarray(logits, np.float32).reshape(-1)
         assert l.size == self.vocab
+        if top_k != 0:
+            return self.op_sample_batch(l.reshape(1, -1), [(repetition_penalty, temperature, top_p, coin, history)], top_k=[top_k])[0]
         h = np.ascontiguousarray(history, np.uint32).reshape(-1)
         r = NanoHipSample()
         check(lib().nano_hip_op_sample(self.h, l, h, h.size, repetition_penalty, temperature, top_p, coin, C.byref(r)))
         return r
 
-    def forward_sample_batch(self, tokens: Sequence[int], pos: Sequence[int], params) -> list:
+    def forward_sample_batch(self, tokens: Sequence[int], pos: Sequence[int], params, top_k=0) -> list:
         """One decode step of slots 0..B-1, then row i sampled on the device with params[i] =
-        (repetition_penalty, temperature, top_p, coin, history); one NanoHipSample per row."""
+        (repetition_penalty, temperature, top_p, coin, history); one NanoHipSample per row.  top_k: one int, or one per row."""
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
-        arr, _keep = sample_params(params)
         out = (NanoHipSample * max(t.size, 1))()
-        check(lib().nano_hip_forward_sample_batch(self.h, t, p, t.size, arr, out))
+        if np.isscalar(top_k) and top_k == 0:
+            arr, _keep = sample_params(params)
+            check(lib().nano_hip_forward_sample_batch(self.h, t, p, t.size, arr, out))
+        else:
+            arr, _keep = sample_params_ex(params, top_k)
+            check(lib().nano_hip_forward_sample_batch_ex(self.h, t, p, t.size, arr, out))
         return list(out)[:t.size]
 
-    def op_sample_batch(self, logits: np.ndarray, params) -> list:
-        """The batched device sampler alone, on host logits [B][V]; params as forward_sample_batch."""
+    def op_sample_batch(self, logits: np.ndarray, params, top_k=0) -> list:
+        """The batched device sampler alone, on host logits [B][V]; params and top_k as forward_sample_batch."""
         l = np.ascontiguousarray(logits, np.float32)
         assert l.ndim == 2 and l.shape[1] == self.vocab
-        arr, _keep = sample_params(params)
         out = (NanoHipSample * max(l.shape[0], 1))()
-        check(lib().nano_hip_op_sample_batch(self.h, l.reshape(-1), l.shape[0], arr, out))
+        if np.isscalar(top_k) and top_k == 0:
+            arr, _keep = sample_params(params)
+            check(lib().nano_hip_op_sample_batch(self.h, l.reshape(-1), l.shape[0], arr, out))
+        else:
+            arr, _keep = sample_params_ex(params, top_k)
+            check(lib().nano_hip_op_sample_batch_ex(self.h, l.reshape(-1), l.shape[0], arr, out))
         return list(out)[:l.shape[0]]
 
     def lora_attach_file(self, path: str):

@@ -75,12 +75,14 @@ static int sampler_init(NanoHipModel *m) {
     return 0;
 }
 // the checks of every row (before anything is queued)
-static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampleParams *params, const NanoHipSample *out) {
-    if (!m || !params || !out) FAIL(NANO_HIP_EINVAL, "null argument");
+static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampleParamsEx *params, const NanoHipSample *out) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
     if (batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH) FAIL(NANO_HIP_EINVAL, "batch %u out of range (max_batch %u)", batch, m->maxB);
+    if (!params || !out) FAIL(NANO_HIP_EINVAL, "null argument");
     const uint32_t V = m->d.vocab_size;
     for (uint32_t i = 0; i < batch; i++) {
-        const NanoHipSampleParams &p = params[i];
+        const NanoHipSampleParams &p = params[i].p;
+        if (params[i].reserved[0] | params[i].reserved[1] | params[i].reserved[2]) FAIL(NANO_HIP_EINVAL, "reserved words of row %u are not 0", i);
         if (p.n_history && !p.history) FAIL(NANO_HIP_EINVAL, "null history of row %u", i);
         if (p.repetition_penalty == 1.0f) continue;                        // (the history is not read)
         if (p.n_history > m->S + 1) FAIL(NANO_HIP_EINVAL, "history of %u ids of row %u exceeds max_seq_len + 1", p.n_history, i);
@@ -90,7 +92,7 @@ static int check_sample_rows(NanoHipModel *m, uint32_t batch, const NanoHipSampl
 }
 // queue the sampler behind whatever produced logits[batch][V] (device) on the model's stream, wait, fill out[batch].  Returns 0 with
 // the stream synchronised: the caller then looks at the sticky error word (and may re-issue the forward).
-static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParamsEx *params, NanoHipSample *out) {
     Sampler *sp = m->smp;
     SampleRows b = sp->b;
     b.a.logits = logits;
@@ -102,9 +104,9 @@ static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, con
     uint32_t *h_ids = reinterpret_cast<uint32_t *>(sp->h_params + batch);
     size_t n_ids = 0;
     for (uint32_t i = 0; i < batch; i++) {
-        const NanoHipSampleParams &p = params[i];
+        const NanoHipSampleParams &p = params[i].p;
         SampleRowParams &q = sp->h_params[i];
-        q.penalty = p.repetition_penalty; q.temperature = p.temperature; q.top_p = p.top_p; q.coin = p.coin;
+        q.penalty = p.repetition_penalty; q.temperature = p.temperature; q.top_p = p.top_p; q.coin = p.coin; q.top_k = params[i].top_k;
         q.cutoff = (1.0f - p.top_p) / (float)((int)V - 1);                  // (1.0f - top_p) / (n - 1), infer.c:1064
         (p.temperature == 0.0f ? any_argmax : any_softmax) = true;
         if (p.repetition_penalty == 1.0f) continue;                        // x / 1.0f is exact: no set needed
@@ -130,7 +132,7 @@ static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, con
     // denominator -- every candidate sorted by a device radix sort, the same cut and draw -- one row after another
     bool wide_ran = false;
     for (uint32_t i = 0; i < batch && any_softmax; i++) {
-        if (params[i].temperature == 0.0f || sp->h_res[i].status != NANO_SAMPLE_FALLBACK || sp->h_res[i].n_candidates == 0) continue;
+        if (params[i].p.temperature == 0.0f || sp->h_res[i].status != NANO_SAMPLE_FALLBACK || sp->h_res[i].n_candidates == 0) continue;
         if (!sp->wide) {
             sp->wide_temp_bytes = sample_wide_temp_bytes((uint32_t)npad);
             const size_t tb = (sp->wide_temp_bytes + 255) & ~(size_t)255;
@@ -149,14 +151,14 @@ static int sampler_run(NanoHipModel *m, const float *logits, uint32_t batch, con
         HIP_TRY(hipStreamSynchronize(m->st));
     }
     for (uint32_t i = 0; i < batch; i++) {
-        if (params[i].temperature == 0.0f) { memset(&out[i], 0, sizeof out[i]); out[i].token = m->h_amax[i]; out[i].status = NANO_SAMPLE_OK; }
+        if (params[i].p.temperature == 0.0f) { memset(&out[i], 0, sizeof out[i]); out[i].token = m->h_amax[i]; out[i].status = NANO_SAMPLE_OK; }
         else out[i] = sp->h_res[i];
     }
     return 0;
 }
 
-extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
-                                             const NanoHipSampleParams *params, NanoHipSample *out) {
+extern "C" int nano_hip_forward_sample_batch_ex(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                                const NanoHipSampleParamsEx *params, NanoHipSample *out) {
     int rc;
     if ((rc = check_sample_rows(m, batch, params, out))) return rc;
     if ((rc = check_batch(m, tokens, pos, batch, 0))) return rc;
@@ -171,7 +173,7 @@ extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *to
     });
 }
 
-extern "C" int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+extern "C" int nano_hip_op_sample_batch_ex(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParamsEx *params, NanoHipSample *out) {
     int rc;
     if ((rc = check_sample_rows(m, batch, params, out))) return rc;
     if (!logits) FAIL(NANO_HIP_EINVAL, "null argument");
@@ -182,6 +184,21 @@ extern "C" int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, ui
     HIP_TRY(hipMemcpyAsync(m->logits, m->h_logits, batch * V * 4, hipMemcpyHostToDevice, m->st));
     if ((rc = sampler_run(m, m->logits, batch, params, out))) return rc;
     return dev_err_check(m);
+}
+// The entry points without top_k: the same rows with top_k = 0.  A null `params` or a batch beyond NANO_MAX_BATCH is passed on unread:
+// the _ex call refuses it (a null model first, then the batch, then null pointers) before it reads a row.
+template <class Call> static int with_top_k_off(uint32_t batch, const NanoHipSampleParams *params, Call call) {
+    NanoHipSampleParamsEx ex[NANO_MAX_BATCH];
+    if (!params || batch > NANO_MAX_BATCH) return call(static_cast<const NanoHipSampleParamsEx *>(nullptr));
+    for (uint32_t i = 0; i < batch; i++) ex[i] = NanoHipSampleParamsEx{ params[i], 0u, { 0u, 0u, 0u } };
+    return call(static_cast<const NanoHipSampleParamsEx *>(ex));
+}
+extern "C" int nano_hip_forward_sample_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                             const NanoHipSampleParams *params, NanoHipSample *out) {
+    return with_top_k_off(batch, params, [&](const NanoHipSampleParamsEx *ex) { return nano_hip_forward_sample_batch_ex(m, tokens, pos, batch, ex, out); });
+}
+extern "C" int nano_hip_op_sample_batch(NanoHipModel *m, const float *logits, uint32_t batch, const NanoHipSampleParams *params, NanoHipSample *out) {
+    return with_top_k_off(batch, params, [&](const NanoHipSampleParamsEx *ex) { return nano_hip_op_sample_batch_ex(m, logits, batch, ex, out); });
 }
 // one row: slot 0, a batch of one
 extern "C" int nano_hip_forward_sample(NanoHipModel *m, uint32_t token, uint32_t pos, const uint32_t *history, uint32_t n_history,

@@ -6,7 +6,8 @@
  * samplers (repetition penalty, temperature, softmax, top-p, xorshift64* coin).  Everything the
  * reference does inside llm_forward() runs on the GPU.
  *
- * Mirrored reference behaviour: top_k is stored and ignored; the top-p branch is always
+ * Mirrored reference behaviour: top_k is stored and ignored (NANO_SAMPLE_TOP_K=1 makes it cut
+ * the sorted candidates in front of the top-p cut, an extension); the top-p branch is always
  * taken; the repetition penalty divides regardless of sign.  Greedy decoding with penalty 1.0 uses
  * the device arg-max (4 bytes back instead of vocab*4).
  */
@@ -653,11 +654,12 @@ static int by_prob_desc(const void *a, const void *b) {
     return 0;
 }
 
-static int nucleus(Nano_Context *ctx, const float *p, int n, float top_p, ProbIndex *pi, float coin) {
+static int nucleus(Nano_Context *ctx, const float *p, int n, float top_p, uint32_t top_k, ProbIndex *pi, float coin) {
     int n0 = 0;
     const float cutoff = (1.0f - top_p) / (n - 1);
     for (int i = 0; i < n; i++) if (p[i] >= cutoff) { pi[n0].index = i; pi[n0].prob = p[i]; n0++; }
     qsort(pi, (size_t)n0, sizeof(ProbIndex), by_prob_desc);
+    if (top_k > 0 && (uint32_t)n0 > top_k) n0 = (int)top_k;             /* NANO_SAMPLE_TOP_K=1 only (nano_mi355x.h): the caller passes 0 otherwise */
     float cum = 0.0f;
     int last = n0 - 1;
     for (int i = 0; i < n0; i++) { cum += pi[i].prob; if (cum > top_p) { last = i; break; } }
@@ -685,6 +687,13 @@ void free_sampler(Sampler *s) { if (s) { free(s->probindex); free(s); } }
 
 /* NANO_HOST_SAMPLER=1: copy the logits back and run the sampler loops on the host (A/B checks) */
 static int g_host_sampler = -1;
+/* NANO_SAMPLE_TOP_K=1: Sampler.top_k truncates the sorted candidates in front of the top-p cut, on the device and in the host loops
+ * alike (include/nano_mi355x.h, "top-k truncation").  Without it top_k stays stored and ignored, as in the reference. */
+static int g_sample_top_k = -1;
+static uint32_t sampler_top_k(const Sampler *sp) {
+    if (g_sample_top_k < 0) { const char *e = getenv("NANO_SAMPLE_TOP_K"); g_sample_top_k = (e && *e && *e != '0') ? 1 : 0; }
+    return g_sample_top_k ? sp->top_k : 0u;
+}
 
 /* the sampler loops of generate_next_token on a host copy of the logits (reference infer.c:1156-1189) */
 static uint32_t host_sample(Nano_Context *ctx, Sampler *sp, float *logits, const uint32_t *output_ids, uint32_t pos, float coin) {
@@ -698,7 +707,7 @@ static uint32_t host_sample(Nano_Context *ctx, Sampler *sp, float *logits, const
     if (sp->temperature == 0.0f) return (uint32_t)argmax_first(logits, V);
     for (int i = 0; i < V; i++) logits[i] /= sp->temperature;
     softmax_inplace(logits, V);
-    return (uint32_t)nucleus(ctx, logits, V, sp->top_p, sp->probindex, coin);   /* top-p always (infer.c:1183) */
+    return (uint32_t)nucleus(ctx, logits, V, sp->top_p, sampler_top_k(sp), sp->probindex, coin);   /* top-p always (infer.c:1183) */
 }
 
 /* reference infer/infer.c:1135-1193 */
@@ -771,7 +780,8 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         /* the sampler runs on the device behind the forward: one 52-byte result comes back */
         NanoHipSample r;
         observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
-        if (nano_hip_forward_sample(dev, token, pos, output_ids, pos, sp->repetition_penalty, sp->temperature, sp->top_p, coin, &r) != NANO_HIP_OK)
+        const NanoHipSampleParamsEx px = { { sp->repetition_penalty, sp->temperature, sp->top_p, coin, output_ids, pos }, sampler_top_k(sp), { 0, 0, 0 } };
+        if (nano_hip_forward_sample_batch_ex(dev, &token, &pos, 1, &px, &r) != NANO_HIP_OK)
             die_hip("generate_next_token");
         observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
         if (r.status == NANO_SAMPLE_OK) {
@@ -834,21 +844,23 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
             }
             continue;
         }
-        NanoHipSampleParams prm[NANO_MAX_BATCH];
+        NanoHipSampleParamsEx prm[NANO_MAX_BATCH];
         NanoHipSample res[NANO_MAX_BATCH];
+        memset(prm, 0, sizeof prm);
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t i = idx[k];
             const Sampler *sp = samplers[i];
-            prm[k].repetition_penalty = sp->repetition_penalty; prm[k].temperature = sp->temperature; prm[k].top_p = sp->top_p; prm[k].coin = coin[i];
-            prm[k].history = histories ? histories[i] : NULL; prm[k].n_history = n_history ? n_history[i] : 0;
+            prm[k].p.repetition_penalty = sp->repetition_penalty; prm[k].p.temperature = sp->temperature; prm[k].p.top_p = sp->top_p; prm[k].p.coin = coin[i];
+            prm[k].p.history = histories ? histories[i] : NULL; prm[k].p.n_history = n_history ? n_history[i] : 0;
+            prm[k].top_k = sampler_top_k(sp);
         }
-        if ((rc = nano_hip_forward_sample_batch(dev, tk, ps, n, prm, res)) != NANO_HIP_OK) break;
+        if ((rc = nano_hip_forward_sample_batch_ex(dev, tk, ps, n, prm, res)) != NANO_HIP_OK) break;
         for (uint32_t k = 0; k < n && rc == NANO_HIP_OK; k++) {
             const uint32_t i = idx[k];
             if (res[k].status == NANO_SAMPLE_OK) { out_ids[i] = res[k].token; continue; }
             /* the device declined this row (no candidate, or no memory for the wide phase): host loops on the slot's logits */
             if ((rc = nano_hip_read_state(dev, k, 4, 0, 0, lbuf, (size_t)V)) != NANO_HIP_OK) break;
-            out_ids[i] = host_sample(NULL, samplers[i], lbuf, prm[k].history, prm[k].n_history, coin[i]);
+            out_ids[i] = host_sample(NULL, samplers[i], lbuf, prm[k].p.history, prm[k].p.n_history, coin[i]);
         }
     }
     free(lbuf);

@@ -480,6 +480,7 @@ struct SampleArgs {
     float *y, *e;                                 // penalised+tempered logits, softmax numerators
     const uint8_t *seen;                          // null when the penalty is 1
     float penalty, temperature, top_p, cutoff, coin;
+    uint32_t top_k;                               // 0 = off; else the sorted list is cut to its first top_k entries (nano_mi355x.h)
     float *pmax;                                  // [nch/4] workgroup maxima of the prep kernel
     uint32_t *ncand, *ndrop, *dropmax, *bstar;    // accumulators, left at 0 by the last kernel (bstar: set by propagate)
     uint32_t *bin_cnt; unsigned long long *bin_mass;      // [SAMPLE_BINS], likewise
@@ -493,7 +494,7 @@ struct SampleArgs {
 // The sampler's rows (a one-row call is a batch of one): `a` is row 0's view -- its scratch pointers (y, e, seen, pmax, cells, bins,
 // approx, spec, fn, cand) are row 0's, and row r's lie `rstride` bytes further per row; row r's logits are `lstride` floats further,
 // its result is res[r], its parameters rp[r].  The wide-phase pointers of `a` are not used.
-struct SampleRowParams { float penalty, temperature, top_p, cutoff, coin; };
+struct SampleRowParams { float penalty, temperature, top_p, cutoff, coin; uint32_t top_k; };
 struct SampleRows {
     SampleArgs a;
     const SampleRowParams *rp;
@@ -513,7 +514,7 @@ __host__ __device__ inline SampleArgs sample_row(const SampleRows &b, uint32_t r
     a.approx = mv(a.approx); a.spec = mv(a.spec); a.fn = mv(a.fn); a.cand = mv(a.cand);
     a.seen = p.penalty != 1.0f ? mv(b.a.seen) : nullptr;
     a.res = b.a.res + r;
-    a.penalty = p.penalty; a.temperature = p.temperature; a.top_p = p.top_p; a.cutoff = p.cutoff; a.coin = p.coin;
+    a.penalty = p.penalty; a.temperature = p.temperature; a.top_p = p.top_p; a.cutoff = p.cutoff; a.coin = p.coin; a.top_k = p.top_k;
     return a;
 }
 hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st);

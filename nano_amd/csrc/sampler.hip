@@ -16,6 +16,10 @@
 //                 (counts + fixed-point masses) tells at which bin the mass passes top_p, tokens in later bins are
 //                 dropped, and the cut is accepted only if it fell strictly above every dropped token;
 //   * the cut and the draw   one thread, sequential, over the sorted nucleus.
+// top_k (a row parameter, 0 = off; semantics in nano_mi355x.h): the sorted list is cut to its first top_k entries in front of the cut and
+// the draw.  The list is then needed only down to entry top_k - 1, so the bins kept also stop at the first one at which the count reaches
+// top_k, and a list whose entry top_k - 1 lies strictly above every dropped token is accepted whether or not the top-p cut fell in it.
+// Every such step is a branch on the row's top_k: a row without it executes what it executed before.
 // Six dependent kernels over all rows of a call, ~V*4 B per row each way through L2; across PCIe only the rows' parameters and new
 // history ids go up and a 52-byte result per row comes back.
 #include "kernels.h"
@@ -212,6 +216,16 @@ __device__ __forceinline__ void samp_propagate(const SampleArgs &a) {
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { bm = min(bm, (uint32_t)__shfl_xor(bm, o, 64)); b6 = min(b6, (uint32_t)__shfl_xor(b6, o, 64)); }
+    // top_k: the list is read only down to entry top_k - 1, which lies in the first bin at which the count reaches top_k (the bins
+    // count every non-zero numerator, candidate or not: bk can only be later than needed).  Row-uniform: a top_k == 0 row skips it.
+    if (a.top_k) {
+        uint32_t bk = SAMPLE_BINS - 1;
+#pragma unroll
+        for (int k = 3; k >= 0; k--) if (cbase + c[k] >= a.top_k) bk = lane * 4 + k;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bk = min(bk, (uint32_t)__shfl_xor(bk, o, 64));
+        bm = min(bm, bk);
+    }
     const uint32_t bc = exp_bin(a.cutoff * sum * 0.999f);            // every candidate (p >= cutoff) lies in bins <= bc
     uint32_t cc = bc % 4 == 0 ? c[0] : bc % 4 == 1 ? c[1] : bc % 4 == 2 ? c[2] : c[3];
     cc = __shfl(cbase + cc, bc / 4, 64);
@@ -290,12 +304,16 @@ __device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long lon
     uint32_t *kw = reinterpret_cast<uint32_t *>(key);                  // probability bits = high word of key i
     if (tid == 0) {
         auto prob = [&](uint32_t i) { return __uint_as_float(kw[2 * i + 1]); };
-        float probe5 = n0 > 5 ? prob(5) : 0.0f;                       // (index 5 may be overwritten below)
+        // top_k (nano_mi355x.h): the two loops run over the first nk = min(n0, top_k) entries of the sorted list
+        const uint32_t nk = a.top_k && a.top_k < n0 ? a.top_k : n0;
+        const uint32_t i5 = nk > 5 ? 5 : nk - 1;                       // the last entry reported in top[]
+        float probe5 = n0 > 5 ? prob(i5) : 0.0f;                      // (that index may be overwritten below)
+        const float probek = a.top_k && a.top_k <= n0 ? prob(a.top_k - 1) : 0.0f;      // (likewise)
         float cum = 0.0f, plast = 0.0f;
-        uint32_t last = n0 - 1;
+        uint32_t last = nk - 1;
         bool cut = false;
         uint32_t i = 0;
-        for (; i + 16 <= n0 && !cut; i += 16) {
+        for (; i + 16 <= nk && !cut; i += 16) {
             float pv[16], cs[16];
 #pragma unroll
             for (int k = 0; k < 16; k++) pv[k] = prob(i + k);
@@ -310,16 +328,17 @@ __device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long lon
 #pragma unroll
             for (int k = 0; k < 16; k++) kw[2 * (i + k) + 1] = __float_as_uint(cs[k]);      // (sums past `last` are never read)
         }
-        for (; i < n0 && !cut; i++) {
+        for (; i < nk && !cut; i++) {
             const float pv = prob(i);
             cum += pv; kw[2 * i + 1] = __float_as_uint(cum);
             if (cum > a.top_p) { last = i; plast = pv; cut = true; }
         }
         if (!cut) plast = 0.0f;                                        // (only read when cut)
         // tokens were dropped: the sorted list is the reference's only down to the largest dropped probability
-        // (and so are the six most probable tokens reported to the observation hook)
-        const float pdeep = last > 5 ? plast : probe5;                 // probability of entry max(last, 5); n0 >= 6 whenever ndrop != 0
-        const bool ok = !(ndrop && !(cut && pdeep > dropmax));
+        // (and so are the most probable tokens reported to the observation hook).  Valid: the cut fell strictly above it, or entry
+        // top_k - 1 lies strictly above it -- the whole truncated list is then the reference's, cut or no cut.
+        const float pdeep = last > i5 ? plast : probe5;                // probability of entry max(last, min(5, top_k - 1)); n0 >= 6 whenever ndrop != 0
+        const bool ok = !(ndrop && !(cut && pdeep > dropmax) && !(probek > dropmax));
         s_ok = ok ? 1u : 0u; s_last = last; s_pick = last;             // r >= every running sum: probindex[last_idx] (infer.c:1108)
         s_r = a.coin * cum;
         if (!ok) { a.res->status = NANO_SAMPLE_FALLBACK; a.res->token = 0; }
@@ -340,7 +359,8 @@ __device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long lon
     a.res->token = 0xffffffffu - (uint32_t)key[s_pick];
     a.res->status = NANO_SAMPLE_OK;
     a.res->nucleus = s_last + 1;
-    for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < n0 ? 0xffffffffu - (uint32_t)key[i] : 0u;
+    const uint32_t ntop = a.top_k && a.top_k < n0 ? a.top_k : n0;
+    for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < ntop ? 0xffffffffu - (uint32_t)key[i] : 0u;
 }
 
 // The six kernels over rows 0 .. rows-1 (a one-row call is a batch of one): each body runs on row `r`'s view (kernels.h sample_row).
@@ -386,6 +406,13 @@ __global__ __launch_bounds__(256) void samp_wide_unpack_kernel(const SampleArgs 
     float4 p;
     p.x = __uint_as_float((uint32_t)(k0.x >> 32)); p.y = __uint_as_float((uint32_t)(k0.y >> 32));
     p.z = __uint_as_float((uint32_t)(k1.x >> 32)); p.w = __uint_as_float((uint32_t)(k1.y >> 32));
+    if (a.top_k) {                                                   // the list ends behind entry top_k - 1: zeros from there, as behind the last candidate
+        const uint32_t i0 = c * CH + lane * 4;
+        if (i0 + 0 >= a.top_k) p.x = 0.0f;
+        if (i0 + 1 >= a.top_k) p.y = 0.0f;
+        if (i0 + 2 >= a.top_k) p.z = 0.0f;
+        if (i0 + 3 >= a.top_k) p.w = 0.0f;
+    }
     reinterpret_cast<float4 *>(a.wide_p)[c * 64 + lane] = p;
     float s = (p.x + p.y) + (p.z + p.w);
 #pragma unroll
@@ -436,7 +463,8 @@ __global__ __launch_bounds__(64) void samp_wide_cut_kernel(const SampleArgs a) {
     if (lane == 0) { *a.ncand = 0; a.res->n_candidates = n0; a.res->n_sorted = n0; }
     if (n0 == 0 || n0 > a.wide_cap) { if (lane == 0) { a.res->status = NANO_SAMPLE_FALLBACK; a.res->token = 0; } return; }
     __syncthreads();
-    const uint32_t nchw = (n0 + CH - 1) / CH;                        // chunks that hold candidates (the rest are zeros)
+    const uint32_t nk = a.top_k && a.top_k < n0 ? a.top_k : n0;      // entries of the list (top_k: the unpack kernel left zeros behind them)
+    const uint32_t nchw = (nk + CH - 1) / CH;                        // chunks that hold them (the rest are zeros)
     const float *p = a.wide_p;
     uint32_t sb = 0, cur = 0;
     while (cur < nchw && !(__uint_as_float(sb) > a.top_p)) {
@@ -466,7 +494,7 @@ __global__ __launch_bounds__(64) void samp_wide_cut_kernel(const SampleArgs a) {
             a.res->token = 0xffffffffu - (uint32_t)a.wide_out[0];
             a.res->status = NANO_SAMPLE_OK;
             a.res->nucleus = 1u;
-            for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < n0 ? 0xffffffffu - (uint32_t)a.wide_out[i] : 0u;
+            for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < nk ? 0xffffffffu - (uint32_t)a.wide_out[i] : 0u;
         }
         return;
     }
@@ -479,7 +507,7 @@ __global__ __launch_bounds__(64) void samp_wide_cut_kernel(const SampleArgs a) {
         return upto;
     };
     // the cut (infer.c:1078-1084): the first running sum above top_p; without one the whole list and its total
-    uint32_t last = n0 - 1u;
+    uint32_t last = nk - 1u;
     float cum = __uint_as_float(s_bound[ncov - 1u]);
     float r0, r1, r2, r3;
     const uint32_t cstar = first_chunk_above(a.top_p, ncov);
@@ -504,7 +532,7 @@ __global__ __launch_bounds__(64) void samp_wide_cut_kernel(const SampleArgs a) {
     a.res->token = 0xffffffffu - (uint32_t)a.wide_out[pick];
     a.res->status = NANO_SAMPLE_OK;
     a.res->nucleus = last + 1u;
-    for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < n0 ? 0xffffffffu - (uint32_t)a.wide_out[i] : 0u;
+    for (uint32_t i = 0; i < 6; i++) a.res->top[i] = i < nk ? 0xffffffffu - (uint32_t)a.wide_out[i] : 0u;
 }
 
 hipError_t launch_sample_wide_cut(const SampleArgs &a, hipStream_t st) {

@@ -21,7 +21,9 @@
 //   W3-W5 (sampler.hip) the reference's sequential float sum over the sorted list (infer.c:1078-1084: the cut is the first running sum
 //       above top_p; infer.c:1096-1108: the draw is the first running sum above r = coin * cumulative) through the chunk functions of
 //       exact_math.h: exact sums at every 256-entry boundary by one wave, only the two chunks that hold the cut and the draw added
-//       element by element.
+//       element by element.  With the row's top_k set, W3 leaves zeros behind entry top_k - 1 of the sorted list (as behind the last candidate)
+//       and W5 walks min(n, top_k) entries: the truncated list of nano_mi355x.h.  The sort of every candidate is still paid -- this is
+//       where a row goes whose leading histogram bin alone exceeds the LDS sorter (all-equal logits); it is right, not fast.
 // Results (token, nucleus size, the six most probable tokens) are the reference's bit for bit: tests/test_gpu_sampler.py holds them to
 // the compiled reference's goldens at V = 151 936 and to the oracle on ties (all-equal logits: 136 743 equal probabilities).
 #include <cstring>
