@@ -98,6 +98,17 @@ int  nano_hip_model_create(NanoHipModel **out, const NanoModelDesc *desc, const 
  * first gives the writing slot a copy of its own (copy-on-write: one free page per such block, NANO_HIP_ENOMEM and nothing changed when
  * the pool has none), and nano_hip_kv_release() returns a page to the pool only when its last owner leaves. */
 #define NANO_HIP_KV_PAGED 2u
+/* NANO_HIP_KV_FP8 (opt-in because it changes results): the KV cache holds one-byte OCP e4m3fn elements (bias 7, largest
+ * finite +-448, smallest subnormal 2^-9, no infinities; not the MI300 fnuz encoding) with scale 1 -- a stored byte decodes to the value
+ * itself.  A quarter of the FP32 cache's memory and of the bytes attention reads per position.  Every row is rounded once when it is
+ * written, byte = e4m3_rne(clamp(x, -448, 448)): to nearest even, subnormals included, the sign of zero kept; out-of-range values and
+ * +-Inf saturate and never become a NaN code (NaN inputs are outside the contract).  The current token attends to its own rounded k
+ * and v row, all arithmetic stays FP32, and a zero byte is +0, so a fresh cache or page reads as the reference's calloc'd rows -- the
+ * FP16 cache's rules.  e4m3 keeps 3 mantissa bits: the logits move further from the FP32-cache path than with FP16 rows (measured in
+ * tests/test_gpu_kv8.py, stated in DESIGN.md).  Combinable with NANO_HIP_KV_PAGED; together with NANO_HIP_KV_F16 creation fails with
+ * NANO_HIP_EINVAL (also when the two arrive through the environment); not with strict mode, exact mode or LoRA.
+ * nano_hip_model_create() applies it when NANO_KV_FP8=1 is set in the environment. */
+#define NANO_HIP_KV_FP8 4u
 int  nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc *desc, const void *params, size_t params_bytes,
                               int params_on_device, int device, uint32_t max_seq_len, uint32_t max_batch, uint32_t flags);
 void nano_hip_model_destroy(NanoHipModel *m);
@@ -525,14 +536,14 @@ typedef struct NanoAttnDecodeDesc {
     uint32_t range_hint;        /* max(pos) + 1 <= range_hint <= S */
     uint32_t nsplit;            /* 0: attention_nsplit(range_hint, hd); else forced (<= 64) */
     uint32_t rope_qwen3;        /* 1: (i, i + hd/2) pairs, 0: adjacent pairs */
-    uint32_t kv_half;           /* 1: FP16 cache elements (k_cache / v_cache hold uint16 bit patterns) */
+    uint32_t kv_half;           /* the cache's element format: 0 FP32, 1 FP16 (k_cache / v_cache hold uint16 bit patterns), 2 FP8 e4m3fn (bytes) */
     uint32_t chunk;             /* 1: the nb rows are consecutive positions of ONE sequence: pass 1 (prep_only), then pass 2 */
     uint32_t want_frag;         /* 1: also the Q80 groups of 64 in fragment order (nsplit == 1, hd % 64 == 0 only) */
     uint32_t pool_rows;         /* paged cache: rows of one layer plane (a multiple of 64); 0: contiguous cache */
     uint32_t pt_stride;         /* paged: page-table entries per sequence */
     const float *q;             /* [nb][n_head * hd] raw q */
     const float *k;             /* [nb][n_kv_head * hd] raw k of pos */
-    const float *vraw;          /* FP16 cache: [nb][kv_dim] v of pos (FP32), or NULL; FP32 cache: the v rows of pos are in v_cache already */
+    const float *vraw;          /* FP16 / FP8 cache: [nb][kv_dim] v of pos (FP32), or NULL; FP32 cache: the v rows of pos are in v_cache already */
     const uint32_t *pos;        /* [nb] */
     const float *q_norm, *k_norm;          /* [hd] (Qwen3) or NULL */
     const float *rope_cos, *rope_sin;      /* [S][hd / 2] */

@@ -366,19 +366,25 @@ def sample_params_ex(rows, top_k):
 
 
 class DeviceModel:
-    """A model resident on one GPU: mirrors what the reference keeps in ``LLM`` (weights + FwdBuffer)."""
+    """A model resident on one GPU: mirrors what the reference keeps in ``LLM`` (weights + FwdBuffer).
+    kv_f16 / kv_paged / kv_fp8: with all three None the library reads NANO_KV_F16 / NANO_KV_FP8 / NANO_KV_PAGED from the environment;
+    as soon as one of them is given (False included) the flags are exactly the keywords and the environment is not consulted."""
 
     def __init__(self, desc: NanoModelDesc, params, params_bytes: int, *, on_device: bool = False,
                  device: int = 0, max_seq_len: int = 512, max_batch: int = 1, kv_f16: Optional[bool] = None,
-                 kv_paged: Optional[bool] = None):
+                 kv_paged: Optional[bool] = None, kv_fp8: Optional[bool] = None):
         self.desc = desc
         self.h = C.c_void_p(None)
         ptr = params if isinstance(params, int) else params.ctypes.data
-        if kv_paged is not None:     # explicit flags: NANO_HIP_KV_F16 = 1, NANO_HIP_KV_PAGED = 2
+        if kv_fp8 is not None:       # explicit flags, NANO_HIP_KV_FP8 = 4 among them (with kv_f16: refused by the library)
+            check(lib().nano_hip_model_create_ex(C.byref(self.h), C.byref(desc), C.c_void_p(ptr), params_bytes,
+                                                 1 if on_device else 0, device, max_seq_len, max_batch,
+                                                 (1 if kv_f16 else 0) | (2 if kv_paged else 0) | (4 if kv_fp8 else 0)))
+        elif kv_paged is not None:   # explicit flags: NANO_HIP_KV_F16 = 1, NANO_HIP_KV_PAGED = 2
             check(lib().nano_hip_model_create_ex(C.byref(self.h), C.byref(desc), C.c_void_p(ptr), params_bytes,
                                                  1 if on_device else 0, device, max_seq_len, max_batch,
                                                  (1 if kv_f16 else 0) | (2 if kv_paged else 0)))
-        elif kv_f16 is None:         # environment default (NANO_KV_F16 / NANO_KV_PAGED)
+        elif kv_f16 is None:         # environment default (NANO_KV_F16 / NANO_KV_FP8 / NANO_KV_PAGED)
             check(lib().nano_hip_model_create(C.byref(self.h), C.byref(desc), C.c_void_p(ptr), params_bytes,
                                               1 if on_device else 0, device, max_seq_len, max_batch))
         else:
@@ -678,7 +684,7 @@ def desc_from_spec(spec) -> NanoModelDesc:
 
 
 def load_model_file(path: str, *, device: int = 0, max_seq_len: int = 512, max_batch: int = 1, kv_f16: Optional[bool] = None,
-                    kv_paged: Optional[bool] = None) -> DeviceModel:
+                    kv_paged: Optional[bool] = None, kv_fp8: Optional[bool] = None) -> DeviceModel:
     """Open a Nano ``.bin`` (header + tokenizer section + parameter blob) and upload it.
     The tokenizer section is skipped: this entry works on token ids."""
     from . import modelfile as mf
@@ -687,7 +693,7 @@ def load_model_file(path: str, *, device: int = 0, max_seq_len: int = 512, max_b
     tok_bytes = int(np.frombuffer(bytes(raw[256:260]), "<u4")[0])
     off = 256 + tok_bytes
     params = np.ascontiguousarray(raw[off:])         # private, aligned copy of the blob
-    m = DeviceModel(desc_from_spec(spec), params, params.size, device=device, max_seq_len=max_seq_len, max_batch=max_batch, kv_f16=kv_f16, kv_paged=kv_paged)
+    m = DeviceModel(desc_from_spec(spec), params, params.size, device=device, max_seq_len=max_seq_len, max_batch=max_batch, kv_f16=kv_f16, kv_paged=kv_paged, kv_fp8=kv_fp8)
     m.spec = spec
     return m
 
@@ -861,14 +867,17 @@ def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n
                         rope_qwen3, q_norm=None, k_norm=None, vraw=None, kv_half=False, chunk=False, nsplit=0, want_frag=False,
                         pt_rows=None, pool_rows=0, device=0):
     """One decode attention launch as a step issues it (nano_hip_op_attention_decode); chunk: the two passes of a prefill chunk.
-    q [nb, n_head*hd], k [nb, kv_dim] raw rows; pos [nb]; caches float32 (kv_half: float16) contiguous [seqs, n_layer, S, kv_dim]
+    q [nb, n_head*hd], k [nb, kv_dim] raw rows; pos [nb]; caches float32 (kv_half 1 / True: float16 bit patterns; kv_half 2: uint8 e4m3fn
+    bytes, taken and returned as uint8) contiguous [seqs, n_layer, S, kv_dim]
     or paged (pt_rows [seqs, pt_stride], pool_rows) [n_layer, pool_rows, kv_dim]; rope tables [S, hd/2].
     Returns dict(out [nb, n_head*hd], k_cache, v_cache (new arrays, same shape / dtype), plan (one dict; chunk: [pass 1, pass 2]),
     xf / xsf when want_frag)."""
     d = NanoAttnDecodeDesc()
     q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); pos = np.ascontiguousarray(pos, np.uint32)
     nb_ = q.shape[0]
-    cdt = np.float16 if kv_half else np.float32
+    if int(kv_half) == 2 and (np.asarray(k_cache).dtype != np.uint8 or np.asarray(v_cache).dtype != np.uint8):
+        raise TypeError("kv_half=2: the caches are uint8 arrays of e4m3fn bytes")
+    cdt = np.uint8 if int(kv_half) == 2 else np.float16 if kv_half else np.float32
     kc = np.array(k_cache, cdt, copy=True, order="C"); vc = np.array(v_cache, cdt, copy=True, order="C")
     rope_cos = np.ascontiguousarray(rope_cos, np.float32); rope_sin = np.ascontiguousarray(rope_sin, np.float32)
     out = np.zeros((nb_, n_head * hd), np.float32)

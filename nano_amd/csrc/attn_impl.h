@@ -46,40 +46,65 @@ __device__ __forceinline__ float bload_f(__amdgpu_buffer_rsrc_t r, uint32_t off)
 }
 #endif
 
-// ---- KV element format: FP32 rows (the reference's, infer/infer.c:46-51) or, opt-in, FP16 rows ------------
-// A lane's four consecutive elements of a row travel as one 16-byte (FP32) or 8-byte (FP16) load and stay in that raw
+// ---- KV element format: FP32 rows (the reference's, infer/infer.c:46-51) or, opt-in, FP16 or FP8 (OCP e4m3fn) rows -----
+// KVH is the format: 0 FP32, 1 FP16, 2 FP8 (kernels.h KV_FMT_*; `false` / `true` of the callers that predate FP8 still mean 0 / 1).
+// A lane's four consecutive elements of a row travel as one 16-byte (FP32), 8-byte (FP16) or 4-byte (FP8) load and stay in that raw
 // form until they are used, so that the loads remain in flight.
-template <bool KVH> struct KVRaw { float4 v; };
-template <> struct KVRaw<true> { uint2 v; };
-__device__ __forceinline__ float4 kv_cvt(const KVRaw<false> &r) { return r.v; }
-__device__ __forceinline__ float4 kv_cvt(const KVRaw<true> &r) {
+// FP8: e4m3fn, scale 1 (a byte decodes to the value itself; bias 7, largest finite +-448 = 0x7E / 0xFE, smallest subnormal 2^-9, 0x7F /
+// 0xFF = NaN, no infinities).  A row is written as e4m3_rne(clamp(x, -448, 448)): v_med3_f32 in front of v_cvt_pk_fp8_f32 (round to
+// nearest even, subnormals included, the sign of zero kept), so nothing finite -- and no infinity -- becomes a NaN code; read with
+// v_cvt_pk_f32_fp8.  tests/test_gpu_attention_decode_fp8.py holds the stored bytes to tests/kv8_ref.py at every tie and edge.
+template <int KVH> struct KVRaw { float4 v; };
+template <> struct KVRaw<1> { uint2 v; };
+template <> struct KVRaw<2> { uint32_t v; };
+typedef float kv_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 kv_cvt(const KVRaw<0> &r) { return r.v; }
+__device__ __forceinline__ float4 kv_cvt(const KVRaw<1> &r) {
     const __half2 a = *reinterpret_cast<const __half2 *>(&r.v.x), b = *reinterpret_cast<const __half2 *>(&r.v.y);
     const float2 fa = __half22float2(a), fb = __half22float2(b);
     return make_float4(fa.x, fa.y, fb.x, fb.y);
+}
+__device__ __forceinline__ float4 kv_cvt(const KVRaw<2> &r) {
+    const kv_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r.v, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r.v, true);
+    return make_float4(lo[0], lo[1], hi[0], hi[1]);
 }
 __device__ __forceinline__ uint2 kv_pack_half(const float4 &v) {       // round to nearest even, like every later reader will see the row
     const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
     uint2 r; r.x = *reinterpret_cast<const uint32_t *>(&a); r.y = *reinterpret_cast<const uint32_t *>(&b);
     return r;
 }
-template <bool KVH> __device__ __forceinline__ float4 kv_round(const float4 &v) {      // what the cache will hold for v
-    if constexpr (!KVH) return v;
-    else { KVRaw<true> r; r.v = kv_pack_half(v); return kv_cvt(r); }
+__device__ __forceinline__ float kv_clamp_fp8(float x) { return __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f); }
+__device__ __forceinline__ uint32_t kv_pack_fp8(const float4 &v) {     // four bytes, element i in byte i
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv_clamp_fp8(v.x), kv_clamp_fp8(v.y), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv_clamp_fp8(v.z), kv_clamp_fp8(v.w), w, true);
+    return (uint32_t)w;
 }
-template <bool KVH> __device__ __forceinline__ float kv_round1(float v) {
-    if constexpr (!KVH) return v; else return __half2float(__float2half_rn(v));
+__device__ __forceinline__ uint32_t kv_pack_fp8_1(float v) { return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(kv_clamp_fp8(v), 0.0f, 0, false) & 0xffu; }
+template <int KVH> __device__ __forceinline__ float4 kv_round(const float4 &v) {      // what the cache will hold for v
+    if constexpr (KVH == 0) return v;
+    else if constexpr (KVH == 1) { KVRaw<1> r; r.v = kv_pack_half(v); return kv_cvt(r); }
+    else { KVRaw<2> r; r.v = kv_pack_fp8(v); return kv_cvt(r); }
 }
-template <bool KVH> __device__ __forceinline__ void kv_store4(float *row_base, uint32_t elem, const float4 &v) {   // row_base: start of the row (in the cache's own format)
-    if constexpr (!KVH) *reinterpret_cast<float4 *>(row_base + elem) = v;
-    else *reinterpret_cast<uint2 *>(reinterpret_cast<__half *>(row_base) + elem) = kv_pack_half(v);
+template <int KVH> __device__ __forceinline__ float kv_round1(float v) {
+    if constexpr (KVH == 0) return v;
+    else if constexpr (KVH == 1) return __half2float(__float2half_rn(v));
+    else { const kv_f32x2 f = __builtin_amdgcn_cvt_pk_f32_fp8((int)kv_pack_fp8_1(v), false); return f[0]; }
 }
-template <bool KVH> __device__ __forceinline__ void kv_store1(float *row_base, uint32_t elem, float v) {
-    if constexpr (!KVH) row_base[elem] = v; else reinterpret_cast<__half *>(row_base)[elem] = __float2half_rn(v);
+template <int KVH> __device__ __forceinline__ void kv_store4(float *row_base, uint32_t elem, const float4 &v) {   // row_base: start of the row (in the cache's own format)
+    if constexpr (KVH == 0) *reinterpret_cast<float4 *>(row_base + elem) = v;
+    else if constexpr (KVH == 1) *reinterpret_cast<uint2 *>(reinterpret_cast<__half *>(row_base) + elem) = kv_pack_half(v);
+    else *reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(row_base) + elem) = kv_pack_fp8(v);
 }
-template <bool KVH> __device__ __forceinline__ KVRaw<KVH> kv_load4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+template <int KVH> __device__ __forceinline__ void kv_store1(float *row_base, uint32_t elem, float v) {
+    if constexpr (KVH == 0) row_base[elem] = v;
+    else if constexpr (KVH == 1) reinterpret_cast<__half *>(row_base)[elem] = __float2half_rn(v);
+    else reinterpret_cast<unsigned char *>(row_base)[elem] = (unsigned char)kv_pack_fp8_1(v);
+}
+template <int KVH> __device__ __forceinline__ KVRaw<KVH> kv_load4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
     KVRaw<KVH> o;
-    if constexpr (!KVH) o.v = bload_f4(r, off);
-    else { typedef int i32x2 __attribute__((ext_vector_type(2))); const i32x2 t = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0); o.v = make_uint2((uint32_t)t.x, (uint32_t)t.y); }
+    if constexpr (KVH == 0) o.v = bload_f4(r, off);
+    else if constexpr (KVH == 1) { typedef int i32x2 __attribute__((ext_vector_type(2))); const i32x2 t = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0); o.v = make_uint2((uint32_t)t.x, (uint32_t)t.y); }
+    else o.v = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
     return o;
 }
 
@@ -155,18 +180,20 @@ constexpr int NP = 2;            // timestep blocks a workgroup keeps in flight 
 // 2c and 2c + 1 of chunk c = j + LPR * (q / 2) -- so a row costs half the load instructions and every instruction still asks for
 // whole 128-byte lines (round 3's 8-byte loads: as many requests as FP32 rows for half the bytes, and not a microsecond saved).
 // The RoPE partner of slot q stays slot q + QV / 2 of the same lane (f + 2 LPR = half a head further for QV = 4).
+// FP8 rows have no wide form: one 4-byte load per float4 slot with the FP32 rows' lane -> slot map (8-byte loads with W16's map were
+// measured and not shown to pay, profiles/kv_fp8.txt; 16-byte loads would put a slot's RoPE partner into another lane).
 // FUSE (qkv_attn_fused_kernel, gemv_q80_impl.h): the workgroup runs INSIDE the launch that computes q | k | v -- its K / V rows are
 // asked for at entry as always, q, the raw k row and the fresh v row then arrive as 8-byte {value, tag} granules that the projection's
 // workgroups store write-through (hh.buf: q at 0, k at hh.base[1], v at hh.base[2]; tag = hand_tag, the epoch of this step and layer --
 // device_common.h): one sweep per wave until every tag matches, the values go through LDS into the registers the loads used to fill.
 // A workgroup that gives up (bounded wait) reports it and stores NOTHING: no k row, no output (round-5 advice).
 // RAGGED (attention_rows_kernel; nano_hip_step_rows): row b's cache base and page-table row are those of KV slot a.row_slot[b]
-// (kernels.h AttnArgs::row_slot), and an FP32 cache takes its fresh v row from a.vraw as the FP16 cache does (stored next to k; the
+// (kernels.h AttnArgs::row_slot), and an FP32 cache takes its fresh v row from a.vraw as the FP16 / FP8 cache does (stored next to k; the
 // timestep loop still reads it from the cache: the prep_only pass of the step stored it).  false: nothing of this is compiled in.
-template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16, bool FUSE, bool RAGGED = false>
+template <int LPR, int QV, int KVM, int MODE, int KVH, bool PG, int NPT, bool W16, bool FUSE, bool RAGGED = false>
 __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char *smem, const uint32_t grp, const uint32_t b, const uint32_t split,
                                                const SlabHand &hh, const uint32_t hand_tag = 0u, const uint32_t hand_wait16 = 0u) {
-    static_assert(!W16 || (KVH && QV % 4 == 0), "16-byte FP16 loads: two float4 slots per load");
+    static_assert(!W16 || (KVH == 1 && QV % 4 == 0), "16-byte FP16 loads: two float4 slots per load");
     static_assert(!RAGGED || !FUSE, "the fused one-sequence launches have no row map");
     constexpr bool VRAW = KVH || RAGGED;                       // the fresh v row may arrive in a.vraw and be stored by this kernel
     static_assert(!FUSE || (((MODE == 1 && LPR * QV * 4 == 128) || MODE == 2) && KVM == 1 && !KVH && !PG && LPR * QV * 4 <= 128),
@@ -235,7 +262,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     uint32_t slot_b = b;                                       // the KV slot of row b
     if constexpr (RAGGED) slot_b = a.row_slot[b];
     // ---- 1. issue every load --------------------------------------------------------------------------------
-    constexpr uint32_t ESZ = KVH ? 2u : 4u;                    // bytes per cache element
+    constexpr uint32_t ESZ = KVH == 2 ? 1u : KVH == 1 ? 2u : 4u; // bytes per cache element
     const size_t slot_rows = paged ? (size_t)a.layer * a.pool_rows : (size_t)slot_b * a.cache_bstride_rows + (size_t)a.layer * a.S;
     // start of this KV head's rows, in the cache's own element size (typed float* for the FP32 path's arithmetic)
     const float *kc = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.kcache) + (slot_rows * a.kv_dim + (size_t)g * hd) * ESZ);
@@ -266,7 +293,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     float4 qnw[QV], knw[QV], rcs[QV], rsn[QV];
     const __amdgpu_buffer_rsrc_t rq = mkrsrc(a.q + (size_t)b * a.q_dim, a.q_dim * 4u);
     const __amdgpu_buffer_rsrc_t rkr = mkrsrc(fresh_k ? a.kraw + (size_t)b * a.kv_dim : nullptr, fresh_k ? a.kv_dim * 4u : 0u);
-    // FP16 cache: the QKV GEMV leaves the fresh v row in scratch (FP32) and this kernel rounds and stores it next to k
+    // FP16 / FP8 cache: the QKV GEMV leaves the fresh v row in scratch (FP32) and this kernel rounds and stores it next to k
     const bool fresh_v = VRAW && a.vraw != nullptr;
     const __amdgpu_buffer_rsrc_t rvr = mkrsrc(fresh_v ? a.vraw + (size_t)b * a.kv_dim : nullptr, fresh_v ? a.kv_dim * 4u : 0u);
     const __amdgpu_buffer_rsrc_t rqn = mkrsrc(a.q_norm, has_norm ? hd * 4u : 0u);
@@ -297,7 +324,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
                 }
             }
         }
-        if constexpr (VRAW) {                                   // FP16 cache: every lane keeps the fresh v row (it is not in the cache yet)
+        if constexpr (VRAW) {                                   // FP16 / FP8 cache: every lane keeps the fresh v row (it is not in the cache yet)
 #pragma unroll
             for (int q = 0; q < QV; q++) { const uint32_t f = fidx(q); vfresh[q] = bload_f4(rvr, (f * 4u < hd) ? g * hd * 4u + f * 16u : OOB); }
         }
@@ -490,7 +517,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
 #pragma unroll
                 for (int q = 0; q < QV; q++) { const uint32_t f = fidx(q); if (f * 4u < hd) *reinterpret_cast<float4 *>(dst + 4u * f) = sv[q]; }
             }
-            if (isk && split == 0 && first_of_group) {            // the finished k row (FP16 cache: and the v row) -> cache row pos
+            if (isk && split == 0 && first_of_group) {            // the finished k row (FP16 / FP8 cache: and the v row) -> cache row pos
                 float *krow = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(const_cast<float *>(kc)) + (size_t)prow * a.kv_dim * ESZ);
                 float *vrow = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(const_cast<float *>(vc)) + (size_t)prow * a.kv_dim * ESZ);
 #pragma unroll
@@ -564,7 +591,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
         }
 #pragma unroll
         for (int q = 0; q < QV; q++) { kfresh[q] = kv_round<KVH>(kfresh[q]); if (KVH) vfresh[q] = kv_round<KVH>(vfresh[q]); }   // what the cache holds
-        if (split == 0 && sub == 0 && first_of_group) {          // the finished k row (FP16 cache: and the v row) -> cache row pos
+        if (split == 0 && sub == 0 && first_of_group) {          // the finished k row (FP16 / FP8 cache: and the v row) -> cache row pos
             float *krow = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(const_cast<float *>(kc)) + (size_t)prow * a.kv_dim * ESZ);
             float *vrow = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(const_cast<float *>(vc)) + (size_t)prow * a.kv_dim * ESZ);
 #pragma unroll
@@ -703,7 +730,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
                 const float e = (sc[m][p] == -INFINITY) ? 0.0f : expf(sc[m][p] - mx);
                 l += e;
                 const uint32_t tv = ((round * NPT + p) * nsplit + split) * R + sub;
-                const bool vf = !FAST && (FUSE || (KVH && fresh_v)) && tv == pos;   // FP16 cache / fused launch: the fresh v row is not in the cache yet
+                const bool vf = !FAST && (FUSE || (KVH && fresh_v)) && tv == pos;   // FP16 / FP8 cache / fused launch: the fresh v row is not in the cache yet
 #pragma unroll
                 for (int q = 0; q < QV; q++) {
                     const float4 vv = vf ? vfresh[q] : kv_cvt(vreg[p][q]);
@@ -809,13 +836,13 @@ __device__ __forceinline__ void attention_body(const AttnArgs &a, unsigned char 
     NANO_STAMP_END(a.stamps, 5);                               // combined and stored: the workgroup's last wave ends
 }
 
-template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16>
+template <int LPR, int QV, int KVM, int MODE, int KVH, bool PG, int NPT, bool W16>
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     attention_body<LPR, QV, KVM, MODE, KVH, PG, NPT, W16, false>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z, SlabHand{});
 }
 // the same body with the row -> slot map of a ragged step (AttnArgs::row_slot != nullptr)
-template <int LPR, int QV, int KVM, int MODE, bool KVH, bool PG, int NPT, bool W16>
+template <int LPR, int QV, int KVM, int MODE, int KVH, bool PG, int NPT, bool W16>
 __global__ __launch_bounds__(256) void attention_rows_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     attention_body<LPR, QV, KVM, MODE, KVH, PG, NPT, W16, false, true>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z, SlabHand{});

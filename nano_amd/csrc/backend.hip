@@ -85,6 +85,7 @@ extern "C" int nano_hip_model_create(NanoHipModel **out, const NanoModelDesc *de
                                      int params_on_device, int device, uint32_t max_seq_len, uint32_t max_batch) {
     uint32_t flags = 0;
     if (const char *kv = getenv("NANO_KV_F16")) if (*kv && *kv != '0') flags |= NANO_HIP_KV_F16;
+    if (const char *k8 = getenv("NANO_KV_FP8")) if (*k8 && *k8 != '0') flags |= NANO_HIP_KV_FP8;      // (with NANO_KV_F16: refused below)
     if (const char *kp = getenv("NANO_KV_PAGED")) if (*kp && *kp != '0') flags |= NANO_HIP_KV_PAGED;
     return nano_hip_model_create_ex(out, desc, params, params_bytes, params_on_device, device, max_seq_len, max_batch, flags);
 }
@@ -92,7 +93,8 @@ extern "C" int nano_hip_model_create(NanoHipModel **out, const NanoModelDesc *de
 extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc *desc, const void *params, size_t params_bytes,
                                         int params_on_device, int device, uint32_t max_seq_len, uint32_t max_batch, uint32_t flags) {
     if (!out || !desc || !params) FAIL(NANO_HIP_EINVAL, "null argument");
-    if (flags & ~(NANO_HIP_KV_F16 | NANO_HIP_KV_PAGED)) FAIL(NANO_HIP_EINVAL, "unknown flags 0x%x", flags);
+    if (flags & ~(NANO_HIP_KV_F16 | NANO_HIP_KV_PAGED | NANO_HIP_KV_FP8)) FAIL(NANO_HIP_EINVAL, "unknown flags 0x%x", flags);
+    if ((flags & NANO_HIP_KV_F16) && (flags & NANO_HIP_KV_FP8)) FAIL(NANO_HIP_EINVAL, "NANO_HIP_KV_F16 and NANO_HIP_KV_FP8 (NANO_KV_F16 / NANO_KV_FP8) both set: the KV cache has one element format");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FAIL(NANO_HIP_ENODEV, "no HIP device visible (this backend has no CPU fallback)");
@@ -121,7 +123,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     NanoHipModel *m = new NanoHipModel();
     m->d = d; m->device = device; m->cus = prop.multiProcessorCount;
     m->S = max_seq_len; m->maxB = max_batch; m->hd = hd; m->QD = QD; m->KD = KD;
-    m->kv_half = (flags & NANO_HIP_KV_F16) != 0;
+    m->kv_half = (flags & NANO_HIP_KV_FP8) ? KV_FMT_FP8 : (flags & NANO_HIP_KV_F16) ? KV_FMT_F16 : KV_FMT_F32;
     m->kv.paged = (flags & NANO_HIP_KV_PAGED) != 0;
     const uint8_t *src = reinterpret_cast<const uint8_t *>(params);
     const size_t L = d.n_layer, E = d.n_embd, H = d.n_hidden, V = d.vocab_size;

@@ -4,7 +4,7 @@
 
 // ---- where the KV cache's rows are (KvRows, backend_model.h) ----------------------------------------------------------------------------
 KvRows::VTarget KvRows::v_target(uint32_t l) const {
-    if (m->kv_half) return { m->vraw, m->KD, 0u, m->pos };                                     // FP16 cache: the attention kernel rounds and stores the row
+    if (m->kv_half) return { m->vraw, m->KD, 0u, m->pos };                                     // FP16 / FP8 cache: the attention kernel rounds and stores the row
     if (m->kv.paged) return { m->vcache + l * plane_elems(), 0u, m->KD, m->kv.kvrow };            // paged: row kvrow[b] of this layer's plane (the one position-indexed output)
     // a ragged pass on the contiguous FP32 cache goes the FP16 cache's way: 64 slots of a 4B model are more v plane than a 32-bit offset
     // reaches, and not every projection epilogue multiplies in 64 bits; the attention kernel's prep pass copies the row (same bits)

@@ -150,8 +150,8 @@ struct NanoHipModel {
     Sampler *smp = nullptr;                               // device-side sampler scratch (max_batch rows), created on first use
     uint32_t rope_rows = 0;       // rows of the RoPE tables on the device: positions >= rope_rows are rejected
     uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
-    bool kv_half = false;         // opt-in FP16 KV cache: rows hold __half, v passes through vraw like k through kraw
-    float *vraw = nullptr;        // [Bs][KD] fresh v rows (FP16 cache only)
+    uint32_t kv_half = 0;         // the cache's element format (kernels.h KV_FMT_*).  Opt-in FP16 / FP8 KV cache: rows hold __half / e4m3 bytes, v passes through vraw like k through kraw
+    float *vraw = nullptr;        // [Bs][KD] fresh v rows (FP16 / FP8 cache only)
     // greedy loop (nano_hip_decode_greedy): from the second step on the previous step's arg-max kernel has already embedded this
     // step's token (misc.hip argmax_kernel) -- the step then starts at layer 0's QKV launch
     bool skip_embed = false;
@@ -185,7 +185,7 @@ struct NanoHipModel {
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline size_t kv_esz(const NanoHipModel *m) { return m->kv_half ? 2 : 4; }      // bytes of a KV cache element
+inline size_t kv_esz(const NanoHipModel *m) { return kv_fmt_bytes(m->kv_half); }      // bytes of a KV cache element: 4, 2 (FP16) or 1 (FP8)
 // bytes of n_weights weights in a format: FP32 | Q80 int8 + one FP32 scale per group | Q4K 160-byte blocks of 256
 inline uint64_t weight_bytes(uint32_t quant, uint32_t gs, uint64_t n_weights) {
     return quant == NANO_QUANT_F32 ? 4 * n_weights : quant == NANO_QUANT_Q80 ? n_weights + 4 * (n_weights / gs) : n_weights * 160 / 256;

@@ -1,4 +1,5 @@
 // backend_probe.hip -- measurement, state read-back, the hand-off switches and fault injection (tests; tools).
+#include <array>
 #include "backend_model.h"
 
 // ---- the in-launch hand-offs: state, switches, fault injection (tests; tools) ----------------------------------------------------------
@@ -137,13 +138,28 @@ extern "C" int nano_hip_read_state(NanoHipModel *m, uint32_t slot, int which, ui
     HIP_TRY(hipStreamSynchronize(m->st));
     const float *src = nullptr; size_t cap = 0;
     const KvRows kv{ m, slot, true };
-    if (which == 5 || which == 6) {                              // a cache row, FP32 or (widened on the way back) FP16
+    if (which == 5 || which == 6) {                              // a cache row, FP32 or (widened on the way back) FP16 / FP8
         if (layer >= m->d.n_layer || pos >= m->S) FAIL(NANO_HIP_EINVAL, "bad layer/pos");
         if (n > m->KD) FAIL(NANO_HIP_EINVAL, "n too large");
         size_t row = 0;
         if (!kv.row(layer, pos, &row)) { memset(out, 0, n * 4); return 0; }     // paged, no page yet: a never-written (zero) row
         const float *rp = kv.at(which == 5 ? m->kcache : m->vcache, row);
         if (!m->kv_half) { HIP_TRY(hipMemcpy(out, rp, n * 4, hipMemcpyDeviceToHost)); return 0; }
+        if (m->kv_half == KV_FMT_FP8) {                          // e4m3fn bytes (scale 1): widened through the 256 values of the format
+            static const std::array<float, 256> e4m3 = [] {
+                std::array<float, 256> t{};
+                for (uint32_t c = 0; c < 256; c++) {
+                    const uint32_t ex = (c >> 3) & 15u, mt = c & 7u;
+                    const float mag = (ex == 15u && mt == 7u) ? NAN : ex ? ldexpf((float)(8u + mt), (int)ex - 10) : ldexpf((float)mt, -9);
+                    t[c] = (c & 0x80u) ? -mag : mag;
+                }
+                return t;
+            }();
+            std::vector<uint8_t> b8(n);
+            HIP_TRY(hipMemcpy(b8.data(), rp, n, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; i++) out[i] = e4m3[b8[i]];
+            return 0;
+        }
         std::vector<__half> tmp(n);
         HIP_TRY(hipMemcpy(tmp.data(), rp, n * 2, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) out[i] = __half2float(tmp[i]);

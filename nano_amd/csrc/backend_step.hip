@@ -203,7 +203,7 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
         a.layer = l; a.n_layer = L; a.S = S; a.hd = m->hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
         a.q_dim = QD; a.kv_dim = KD; a.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); a.is_causal = is_causal;
         a.fixed_range = 0;
-        a.kv_half = m->kv_half ? 1u : 0u; a.vraw = m->kv_half ? m->vraw : nullptr;
+        a.kv_half = m->kv_half; a.vraw = m->kv_half ? m->vraw : nullptr;
         if (wo_frag && nsplit == 1) { a.xf_out = m->gq; a.xsf_out = m->gxs; }
         if (m->kv.paged) { a.pt_rows = pt_base; a.kvrow = m->kv.kvrow; a.pt_stride = m->kv.pt_stride; a.pt_bstride = pt_bstride; a.pool_rows = m->kv.pages * 64u; }
         qa.ordered = 0; qa.cus = (uint32_t)m->cus; qa.err = m->dev_err;
@@ -455,8 +455,9 @@ bool strict_serves(const NanoHipModel *m) { return m->strict || (m->exact && m->
 bool exact_serves(const NanoHipModel *m) { return m->exact && !strict_serves(m); }
 // THE place that says which combinations of (strict, exact, phase hook, LoRA, FP16 KV, paged KV) are served: asked by run_step and
 // nano_hip_prefill before they queue anything.  The reference-order step has neither the LoRA side branches nor the FP16 or paged
-// cache; the fast step has no LoRA side branches on a paged or FP16 cache (they write FP32 v rows of the contiguous cache).
-// prefill: batched prefill has never refused LoRA on the FP16 cache; kept as it is.
+// cache; the fast step has no LoRA side branches on a paged, FP16 or FP8 cache (they write FP32 v rows of the contiguous cache).
+// prefill: batched prefill has never refused LoRA on the FP16 cache; kept as it is.  The FP8 cache refuses it there too: the v branch's
+// FP32 read-modify-write would land on byte rows, from a quarter of the layers on beyond the allocation.
 int step_served(const NanoHipModel *m, bool prefill) {
     if (strict_serves(m) || exact_serves(m)) {
         const char *mode = m->strict ? "strict mode" : exact_serves(m) ? "exact mode" : "exact mode with a phase hook";
@@ -466,6 +467,7 @@ int step_served(const NanoHipModel *m, bool prefill) {
     }
     if (m->kv.paged && m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with the LoRA side branches");
     if (m->kv_half && m->lora_on && !prefill) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");
+    if (m->kv_half == KV_FMT_FP8 && m->lora_on) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");   // (batched prefill: the same message)
     return 0;
 }
 // the policy of the decode steps: either failure fails the call

@@ -240,6 +240,10 @@ bool route_is_wide(const GemvArgs &a);
 // up to attention_split_cap() (default 32, capacity 64) splits of a range beyond attention_wide_from() positions (default 2048; <= 8
 // below, which the Wo GEMV's prologue combines: attention_nsplit())
 constexpr uint32_t ATTN_MAX_NSPLIT = 64;
+// the KV cache's element format (AttnArgs::kv_half, AttnPlan::kv_half, NanoAttnDecodeDesc::kv_half, NanoHipModel::kv_half): FP32 rows, or
+// opt-in FP16 / FP8 (OCP e4m3fn, scale 1) rows -- 4, 2, 1 bytes per element
+enum : uint32_t { KV_FMT_F32 = 0, KV_FMT_F16 = 1, KV_FMT_FP8 = 2 };
+inline uint32_t kv_fmt_bytes(uint32_t fmt) { return fmt == KV_FMT_FP8 ? 1u : fmt == KV_FMT_F16 ? 2u : 4u; }
 uint32_t attention_wide_from();
 uint32_t attention_split_cap();
 struct AttnArgs {
@@ -265,8 +269,8 @@ struct AttnArgs {
     uint32_t cache_bstride_rows;   // = L*S rows between slots (in units of kv_dim floats)
     uint32_t fixed_range;          // op-test mode: attend over rows [0, fixed_range) of an externally filled cache
     uint32_t prep_only;            // 1: finish and store the k row of pos[b] (norm + RoPE), then return (batched prefill, pass 1)
-    uint32_t kv_half;              // 1: kcache / vcache hold FP16 elements (opt-in); the fresh v row comes from vraw
-    const float *vraw;             // FP16 cache: [nb][kv_dim] v of the current position from the QKV GEMV (FP32 scratch), else nullptr
+    uint32_t kv_half;              // KV_FMT_*: 1 / 2 = kcache / vcache hold FP16 / FP8 elements (opt-in); the fresh v row then comes from vraw
+    const float *vraw;             // FP16 / FP8 cache: [nb][kv_dim] v of the current position from the QKV GEMV (FP32 scratch), else nullptr
     // single-split launches only, optional: the finished output also leaves as Q80 groups of 64 in MFMA B-fragment order (what
     // quant_rows_frag_kernel would make of xba_out), so the batched Wo GEMM needs no quantizer launch.  head_dim % 64 == 0.
     int8_t *xf_out; float *xsf_out;
@@ -293,8 +297,10 @@ struct AttnArgs {
 hipError_t launch_attention(const AttnArgs &a, uint32_t nb, hipStream_t st);
 // the attention_kernel<LPR, QV, KVM, MODE, KVH, PG, NPT, W16> launch_attention() runs for `a` and nb sequences, and the workgroup order
 // it fills in (kv_log2 / kvmul_log2 of AttnArgs); the launcher takes every choice from here.  false: the arguments are refused.
+// kv_half: the element format (KV_FMT_*); w16: the wide load form ran (FP16 rows only: 16-byte loads, two float4 slots each).
 struct AttnPlan { uint32_t mode, lpr, qv, kvm, npt, w16, paged, kv_half, nsplit, kv_log2, kvmul_log2; };
 bool attention_plan(const AttnArgs &a, uint32_t nb, AttnPlan *p);
+hipError_t launch_attention_fp8(const AttnArgs &a, const AttnPlan &p, uint32_t nb, hipStream_t st);   // launch_attention()'s FP8 half (attn_fp8.hip)
 // q | k | v projection of one sequence + decode attention as ONE launch (gemv.hip dispatches on the weight format -- Q80 group size 64:
 // gemv_q80_impl.h, Q4K: gemv_q4k_chunk.hip, round 6, both with Qwen3 attention; FP32: gemv_f32.hip, the plain mode): the attention workgroups
 // wait for q / k / v as 8-byte {tag, value} granules in `hand` (q_dim + 2 kv_dim entries); tag = the step's tick * 128 + layer1 (device_common.h)

@@ -7,8 +7,9 @@
 // K | V): a workgroup loads its vectors of the source run ONCE and stores them to every destination of the group from registers, so a fork
 // into 63 slots reads the source once per plane and is one launch.  The trailing rows - keep_rows rows of a destination are written as
 // zero (a forked page must not carry the source's later rows: a fresh page is zero, and non-causal attention reads unwritten rows).
-// Inside a plane a run of rows is contiguous memory: it moves as 16-byte vectors (FP32 rows, and FP16 rows of kv_dim % 8 == 0) or 8-byte
-// vectors (FP16 rows of kv_dim % 8 == 4); the host picks, there is no per-element path.  Plain vector loads and stores only.
+// Inside a plane a run of rows is contiguous memory: it moves as 16-byte vectors (FP32 rows, FP16 rows of kv_dim % 8 == 0, FP8 rows of
+// kv_dim % 16 == 0), 8-byte vectors (FP16 rows of kv_dim % 8 == 4, FP8 rows of kv_dim % 16 == 8) or 4-byte words (FP8 rows of
+// kv_dim % 8 == 4: kv_dim is a multiple of 4 always); the host picks, there is no per-element path.  Plain vector loads and stores only.
 #include "device_common.h"
 #include "kernels.h"
 
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(KVC_THREADS) void kv_copy_kernel(KvCopyArgs a) {
 // whole grid, never more chunks than a run has KVC_UNROLL x 256 vectors for.
 hipError_t launch_kv_copy(KvCopyArgs a, uint32_t n_layer, uint32_t max_rows, uint32_t cus, bool nt_stores, hipStream_t st) {
     if (!a.n_groups || !max_rows || !n_layer) return hipSuccess;
-    const uint32_t vb = a.row_bytes % 16 == 0 ? 16u : 8u;
+    const uint32_t vb = a.row_bytes % 16 == 0 ? 16u : a.row_bytes % 8 == 0 ? 8u : 4u;
     if (a.row_bytes % vb || a.plane_bytes % vb) return hipErrorInvalidValue;
     const size_t nvec = (size_t)max_rows * a.row_bytes / vb;
     const size_t per_wg = (size_t)KVC_THREADS * KVC_UNROLL;
@@ -70,9 +71,12 @@ hipError_t launch_kv_copy(KvCopyArgs a, uint32_t n_layer, uint32_t max_rows, uin
     if (vb == 16) {
         if (nt_stores) hipLaunchKernelGGL((kv_copy_kernel<kvc_u32x4, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((kv_copy_kernel<kvc_u32x4, false>), grid, block, 0, st, a);
-    } else {
+    } else if (vb == 8) {
         if (nt_stores) hipLaunchKernelGGL((kv_copy_kernel<kvc_u32x2, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((kv_copy_kernel<kvc_u32x2, false>), grid, block, 0, st, a);
+    } else {
+        if (nt_stores) hipLaunchKernelGGL((kv_copy_kernel<uint32_t, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((kv_copy_kernel<uint32_t, false>), grid, block, 0, st, a);
     }
     return hipGetLastError();
 }

@@ -317,7 +317,10 @@ static FusedLaunch fused_launch(const NanoFusedGemvDesc &d, uint32_t cus, F32Scr
     a.ordered = d.ordered ? 1u : 0u;
     r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = (d.use_gemm && d.quant == NANO_QUANT_Q80) ? 1u : 9u;
     if (d.quant == NANO_QUANT_Q80) {
-        const size_t n16 = (d.n + 15) & ~(size_t)15, tt = (d.nb + 15) / 16;
+        // token tiles of 16 as the batched kernels walk them: 1, 2 or 4 (G2's TT, gemm_q80.hip) -- 33..48 tokens run the four-tile
+        // kernel, which loads the fragments of all four tiles (a model's buffers always hold 64 tokens); three tiles here left the
+        // fourth tile's loads beyond the allocation
+        const size_t n16 = (d.n + 15) & ~(size_t)15, tiles = (d.nb + 15) / 16, tt = tiles > 2 ? 4 : tiles;
         L.gq_bytes = tt * 16 * n16; L.gxs_floats = tt * 16 * (d.n / d.gs);
     }
     if (d.quant == NANO_QUANT_Q4K && d.nb > 1) r.q4x_bytes = (size_t)(d.nb > 8 ? d.nb : 8u) * ((d.n + 255) & ~(size_t)255);
@@ -556,7 +559,7 @@ static AttnArgs attn_launch(const NanoAttnDecodeDesc &d, uint32_t nsplit) {
     a.layer = d.layer; a.n_layer = d.n_layer; a.S = d.S; a.hd = d.hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
     a.q_dim = d.n_head * d.hd; a.kv_dim = d.n_kv_head * d.hd; a.rope_qwen3 = d.rope_qwen3 ? 1u : 0u; a.is_causal = 1;
     a.cache_bstride_rows = d.chunk ? 0u : d.n_layer * d.S; a.fixed_range = 0;
-    a.kv_half = d.kv_half ? 1u : 0u;
+    a.kv_half = d.kv_half;                                          // the element format: 0 FP32, 1 FP16, 2 FP8 (kernels.h KV_FMT_*)
     if (d.pool_rows) { a.pt_stride = d.pt_stride; a.pt_bstride = d.chunk ? 0u : d.pt_stride; a.pool_rows = d.pool_rows; }
     return a;
 }
@@ -587,7 +590,8 @@ extern "C" int nano_hip_op_attention_decode(int device, const NanoAttnDecodeDesc
     OP_ARG(!d.want_frag || (nsplit == 1 && d.hd % 64 == 0 && d.xf && d.xsf), "fragment output: nsplit 1 and hd % 64 == 0 only");
     const bool paged = d.pool_rows != 0;
     const uint32_t seqs = d.chunk ? 1u : nb;                       // cache slots / page-table rows
-    const size_t esz = d.kv_half ? 2 : 4;
+    OP_ARG(d.kv_half <= KV_FMT_FP8, "kv_half: 0 (FP32), 1 (FP16) or 2 (FP8 e4m3) cache elements");
+    const size_t esz = kv_fmt_bytes(d.kv_half);
     const size_t cache_elems = paged ? (size_t)d.n_layer * d.pool_rows * KD : (size_t)seqs * d.n_layer * d.S * KD;
     std::vector<uint32_t> kvrow(nb, 0u);
     if (paged) {
