@@ -483,30 +483,24 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
 // One prefill chunk: nb rows of `slot`, their tokens and positions in m->tokens / m->pos, the last at last_pos.  replay: through a HIP graph per
 // (KV slot, range bucket, nb, key_kind) -- positions and tokens are device data, the slot's cache addresses are baked into the nodes.  The chunk
 // that meets a key first runs eagerly and is captured for the next one that reaches it; a failed capture only costs the replays (r.capture
-// is not looked at).  The cache of chunk graphs is bounded (oldest out).  Chunks of different kinds have different nodes: bits 56-57 of the
-// key are RowWant::key_kind, so none ever replays another's graph.
-hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind) {
-    const uint32_t range_hint = range_hint_of(m, 1, 1, last_pos);      // of the chunk's last token's own decode step
-    m->pf = true; m->pf_slot = slot;
-    hipError_t e = hipSuccess;
-    if (replay) {
-        const uint64_t key = (1ull << 62) | ((uint64_t)key_kind << 56) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) | ((uint64_t)slot << 32) | ((uint64_t)range_hint << 8) | nb;
-        const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, 1, mode, range_hint); });
-        e = r.step;
-        if (r.stored) {
-            if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
-                auto old = m->graphs.find(m->pf_graph_keys.front());
-                if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
-                m->pf_graph_keys.erase(m->pf_graph_keys.begin());
-            }
-            m->pf_graph_keys.push_back(key);
+// is not looked at).  The cache of chunk graphs is bounded (oldest out).  Chunks of different kinds have different nodes: the key carries
+// RowWant::key_kind (step_key), so none ever replays another's graph.
+hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, const RowWant &want, uint32_t last_pos, bool replay) {
+    // (the range hint of the chunk's last token's own decode step)
+    const StepSpec s = StepSpec::chunk(slot, nb, want.mode_pass(), range_hint_of(m, 1, 1, last_pos), want.use_targets());
+    const uint64_t key = replay ? step_key(m, s, want.key_kind()) : STEP_NO_KEY;
+    m->nsplit = xba_nsplit(m, s);                                      // 1: a prefill chunk leaves xba final (single split or the combine kernel), replayed or not
+    if (key == STEP_NO_KEY) return enqueue_step(m, s);                 // eager: one pass per chunk
+    const GraphRun r = graph_step(m, key, [&, s] { return enqueue_step(m, s); });
+    if (r.stored) {
+        if (m->pf_graph_keys.size() >= PF_GRAPH_CAP) {
+            auto old = m->graphs.find(m->pf_graph_keys.front());
+            if (old != m->graphs.end()) { (void)hipGraphExecDestroy(old->second); m->graphs.erase(old); }
+            m->pf_graph_keys.erase(m->pf_graph_keys.begin());
         }
-    } else {
-        e = enqueue_step(m, nb, 1, mode, range_hint);                  // eager: one pass per chunk
+        m->pf_graph_keys.push_back(key);
     }
-    m->pf = false;
-    m->nsplit = 1;                                                     // a prefill chunk leaves xba final (single split or the combine kernel), replayed or not
-    return e;
+    return r.step;
 }
 // Batched prefill: feeds `count` prompt tokens at positions pos0 .. pos0+count-1 of sequence `slot` in
 // passes of up to 64 (Q80, Q4K and FP32 through their MFMA GEMMs: m->pf_chunk) / 8 tokens per weight read instead of one decode step per token; no
@@ -556,11 +550,11 @@ int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t
         if (nb > to_bucket_end) nb = to_bucket_end;
         HIP_TRY(hipMemcpyAsync(m->tokens, m->rb.tok + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
         HIP_TRY(hipMemcpyAsync(m->pos, m->rb.pos + done, nb * 4, hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(rows_pass_targets(m, done, nb));
+        HIP_TRY(rows_pass_targets(m, want, done, nb));
         // a full 64-token chunk recurs in every long prompt: replayed.  Other chunk lengths run eagerly (a capture costs more than the ~300
         // launches it would save once).
         const bool replay = m->use_graph && nb == chunk_max && chunk_max == 64u;
-        HIP_TRY(enqueue_chunk(m, slot, nb, want.mode_pass(), pos0 + done + nb - 1, replay, want.key_kind()));
+        HIP_TRY(enqueue_chunk(m, slot, nb, want, pos0 + done + nb - 1, replay));
         HIP_TRY(rows_after_pass(m, want, done, nb));
         done += nb;
     }
@@ -591,10 +585,9 @@ static int decode_greedy_once(NanoHipModel *m, const uint32_t *tokens, const uin
     uint32_t max_pos = 0;
     if ((rc = stage_batch(m, tokens, pos, batch, true, &max_pos))) return rc;
     for (uint32_t s = 0; s < steps; s++) {
-        m->skip_embed = s > 0 && !m->strict && !m->exact;   // the fused path's arg-max kernel of step s - 1 embedded this step's token
-        rc = run_step(m, batch, 1, MODE_LOOP, max_pos + s);
-        m->skip_embed = false;
-        if (rc) return rc;
+        // from the second step on the fast path's arg-max kernel of step s - 1 has embedded this step's token (misc.hip argmax_kernel): the
+        // step then starts at layer 0's QKV launch (the reference-order step always embeds)
+        if ((rc = run_step(m, batch, 1, MODE_LOOP, max_pos + s, s > 0))) return rc;
     }
     if (out_ids) HIP_TRY(hipMemcpyAsync(m->h_amax, m->trace, (size_t)steps * batch * 4, hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipStreamSynchronize(m->st));

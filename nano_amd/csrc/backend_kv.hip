@@ -8,7 +8,7 @@ KvRows::VTarget KvRows::v_target(uint32_t l) const {
     if (m->kv.paged) return { m->vcache + l * plane_elems(), 0u, m->KD, m->kv.kvrow };            // paged: row kvrow[b] of this layer's plane (the one position-indexed output)
     // a ragged pass on the contiguous FP32 cache goes the FP16 cache's way: 64 slots of a 4B model are more v plane than a 32-bit offset
     // reaches, and not every projection epilogue multiplies in 64 bits; the attention kernel's prep pass copies the row (same bits)
-    if (m->rows.on) return { m->rows.vraw, m->KD, 0u, m->pos };
+    if (ragged) return { m->rows.vraw, m->KD, 0u, m->pos };
     return { v_flat(l), v_flat_bstride(), m->KD, m->pos };
 }
 // (batched prefill on the contiguous cache: the slot's own rows, no stride; on the paged cache the table row is the slot's and these stay)

@@ -51,7 +51,8 @@ static int decode_lookup_once(NanoHipModel *m, const uint32_t *history, uint32_t
     if ((rc = lookup_scratch(m))) return rc;
     if (D >= 1 && (rc = rows_scratch(m, P_LOGITS | P_AMAX, 0))) return rc;
     const uint32_t K = D + 1, slot = 0;
-    if (m->kv.paged) {                                                      // every page the loop will enter, up front (a chunk stays inside its first row's block)
+    RowWant verify; verify.kind = RowWant::ARGMAX;                         // what a verify chunk wants of its rows (no caller array: lookup.hip reads rb.amax, where the pass leaves them)
+    if (m->kv.paged) {                                                     // every page the loop will enter, up front (a chunk stays inside its first row's block)
         const uint32_t first = n_history - 1, need = n_history - 2 + max_new;
         if ((rc = kv_ensure(m, &slot, &first, &need, 1))) return rc;
     }
@@ -94,7 +95,7 @@ static int decode_lookup_once(NanoHipModel *m, const uint32_t *history, uint32_t
             if ((rc = run_step(m, 1, 1, MODE_ARGMAX, n - 1))) return rc;   // the fused launches and graphs of a one-row step, as nano_hip_forward's
         } else {
             // verify chunks recur with the same (K, range bucket): replayed (profiles/lookup_decode.txt has the eager form beside it)
-            HIP_TRY(enqueue_chunk(m, slot, nb, MODE_VERIFY, n - 2 + nb, m->use_graph && m->lk.graph, 3u));
+            HIP_TRY(enqueue_chunk(m, slot, nb, verify, n - 2 + nb, m->use_graph && m->lk.graph));
         }
     }
     if (lost) { HIP_TRY(hipStreamSynchronize(m->st)); return 0; }

@@ -1,5 +1,6 @@
 // backend_model.h -- the model struct of the C-ABI device backend and what its translation units share.  Internal: nothing here is part
-// of the C ABI (include/nano_mi355x.h), and nothing declared here is exported by the library.
+// of the C ABI (include/nano_mi355x.h), and nothing declared here is exported by the library.  The model holds what lasts from call to
+// call; what one step is travels as a StepSpec value (step_spec.h, with the graph key built from it), never as fields set around a call.
 //   backend.hip          create / destroy / layout, the forward / prefill / greedy entry points, the sticky error word and the re-issue policy
 //   backend_step.hip     the argument builders, the fast step, the reference-order step, graphs, run_step, the strict / exact switches
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
@@ -21,6 +22,7 @@
 #include <hip/hip_fp16.h>
 #include "../../include/nano_mi355x.h"
 #include "kernels.h"
+#include "step_spec.h"
 
 using namespace nano;
 extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the thread's nano_hip_last_error() text
@@ -46,9 +48,6 @@ extern "C" void nano_hip_set_error_(const char *msg);      // backend.hip: the t
 #pragma GCC visibility push(hidden)
 
 enum { WQ = 0, WK, WV, WO, W1, W2, W3, WCOUNT };
-enum StepMode : uint32_t { MODE_NOCLS = 0, MODE_LOGITS = 1, MODE_ARGMAX = 2, MODE_LOOP = 3,
-                           MODE_SCORE = 4,     // a pass that goes on into the classifier for all its rows (-> rb.logits) and the row statistics (-> rb.rows)
-                           MODE_VERIFY = 5 };  // a pass whose rows' arg-maxes are wanted (-> rb.amax): the classifier into rb.logits, no statistics
 constexpr size_t PF_GRAPH_CAP = 64;                    // prefill-chunk graphs kept per model (keyed by KV slot x range bucket)
 constexpr uint32_t STAMP_MAX_LAUNCHES = 512, STAMP_WGS = 2048;
 constexpr uint32_t KV_NO_PAGE = 0xffffffffu;           // a page-table entry without a page
@@ -61,10 +60,9 @@ struct NanoHipModel {
     int device = 0, cus = 0;
     uint32_t S = 0, maxB = 0, hd = 0, QD = 0, KD = 0;
     uint32_t Bs = 0;                                      // rows of the per-token scratch (>= maxB: a prefill chunk processes Bs prompt tokens of ONE sequence)
-    uint32_t pf_slot = 0; bool pf = false;                // prefill in progress: every token of the step lives in KV slot pf_slot
     hipStream_t st = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    bool probe_cls = false, probe_ext = false;                               // record ev0 / ev1 / ev2 around the classifier launch of the next eager step
+    bool probe_ext = false;                               // the last step with StepSpec::probe_cls took the classifier kernel's own timestamps (ev0 / ev1), not events around it
     uint8_t *arena = nullptr;
     size_t arena_bytes = 0;
     const float *rms_attn = nullptr, *rms_ffn = nullptr, *rms_final = nullptr;
@@ -103,7 +101,6 @@ struct NanoHipModel {
         NanoHipTokenScore *rows = nullptr;                // [R] a pass's records
         uint32_t *amax = nullptr;                         // [max(pf_chunk, LOOKUP_MAX_ROWS)] a pass's row arg-maxes (m->amax holds max_batch rows)
         unsigned long long *keys = nullptr;               // [R][score_tiles(V)][NANO_TOPK_MAX] the tiles' best keys of the selection
-        bool use_targets = false;                         // of the call in progress (rows_begin): false = each row's own arg-max
         // call buffers: one block of `cap` = max(max_seq_len, rows of the largest call so far) rows of what the calls so far needed (`have`).
         // Only copies and eager launches outside any captured region touch them, so a larger or needier call replaces the block.
         uint8_t *call = nullptr; uint32_t cap = 0, have = 0;
@@ -122,10 +119,7 @@ struct NanoHipModel {
     } lk;
     // ragged steps (nano_hip_step_rows, backend_rows.hip): rows that each carry their own (slot, position)
     struct Rows {
-        bool on = false;                                  // the pass being queued is ragged (with m->pf: every row splits as its own decode step)
-        const uint32_t *row_slot = nullptr;               // device [nb]: the KV slot of each row of the pass
-        struct Group { uint32_t row0, n, hint; };         // a contiguous run of the pass's rows that share a range hint: one attention launch
-        std::vector<Group> groups;
+        using Group = RowGroup;                           // (step_spec.h; a call keeps its passes' groups itself: StepSpec::groups)
         float *vraw = nullptr;                            // [Bs][KD] fresh v rows of a pass on the contiguous FP32 cache (the FP16 cache has m->vraw)
     } rows;
     uint32_t *h_err = nullptr, *dev_err = nullptr;        // sticky error word: host-mapped, written by kernels that give up a bounded wait (kernels.h NANO_DEVERR_*)
@@ -152,9 +146,6 @@ struct NanoHipModel {
     uint32_t pending_batch = 0;   // sequences of the step queued by nano_hip_forward_begin
     uint32_t kv_half = 0;         // the cache's element format (kernels.h KV_FMT_*).  Opt-in FP16 / FP8 KV cache: rows hold __half / e4m3 bytes, v passes through vraw like k through kraw
     float *vraw = nullptr;        // [Bs][KD] fresh v rows (FP16 / FP8 cache only)
-    // greedy loop (nano_hip_decode_greedy): from the second step on the previous step's arg-max kernel has already embedded this
-    // step's token (misc.hip argmax_kernel) -- the step then starts at layer 0's QKV launch
-    bool skip_embed = false;
     // paged KV cache (opt-in): kcache / vcache are pools [L][pages][64][KD]; pt = first pool row of every 64-position block
     struct PagedKv {
         bool paged = false;
@@ -211,7 +202,7 @@ struct RowWant {
     bool use_targets() const { return kind == SCORE && targets; }
     uint32_t mode_row() const { return kind == ARGMAX ? MODE_ARGMAX : kind == SCORE ? MODE_LOGITS : MODE_NOCLS; }     // step mode of a row fed alone
     uint32_t mode_pass() const { return kind == ARGMAX ? MODE_VERIFY : kind == SCORE ? MODE_SCORE : MODE_NOCLS; }     // ... of a pass of several rows
-    // bits 56-57 of a chunk graph's key: 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify (different nodes: none replays another's graph)
+    // KEY_KIND of a chunk graph's key (step_spec.h): 0 plain, 1 scored for targets, 2 scored for the arg-max, 3 verify (different nodes: none replays another's graph)
     uint32_t key_kind() const { return kind == ARGMAX ? 3u : kind == SCORE ? (targets ? 1u : 2u) : 0u; }
     uint32_t need(bool passes) const;                                       // the result buffers of rows_scratch it uses; passes: MODE_SCORE / MODE_VERIFY passes run
                                                                             // (false: every row is left in m->logits / m->amax -- reference-order steps, a decode step)
@@ -233,7 +224,7 @@ int rows_scratch(NanoHipModel *m, uint32_t need, size_t call_rows);
 void rows_free(NanoHipModel *m);
 // the selection behind the statistics: `rows` rows of logits (row stride V), their records in scores (queued before) -> out[rows][k]
 hipError_t enqueue_topk_rows(NanoHipModel *m, const float *logits, uint32_t rows, uint32_t k, const NanoHipTokenScore *scores, NanoHipTopEntry *out);
-// a call of `total` rows begins: room for w.need(passes) | more, rb.use_targets, and the targets (host, in the order the call feeds its rows) on the device
+// a call of `total` rows begins: room for w.need(passes) | more, and the targets (host, in the order the call feeds its rows) on the device
 int rows_begin(NanoHipModel *m, const RowWant &w, bool passes, uint32_t more, size_t total, const uint32_t *targets);
 // the call's tokens, positions and (null: none) KV slots, in feeding order, on the device once (pageable sources: the caller keeps them until it has waited)
 int rows_feed(NanoHipModel *m, size_t total, const uint32_t *tokens, const uint32_t *pos, const uint32_t *slots);
@@ -242,7 +233,7 @@ int rows_feed(NanoHipModel *m, size_t total, const uint32_t *tokens, const uint3
 hipError_t rows_after_step(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 // a MODE_SCORE / MODE_VERIFY pass of nb rows is to run: its targets from the call's; it has run: its records or arg-maxes into the call's
 // slots at .., and the selection on its logits before the next pass overwrites them
-hipError_t rows_pass_targets(NanoHipModel *m, size_t at, uint32_t nb);
+hipError_t rows_pass_targets(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 hipError_t rows_after_pass(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 // strict / exact mode: the call's rows one by one, each a reference-order step on its staged token and position in KV slot row_slot[i] (null: slot)
 int rows_run_ordered(NanoHipModel *m, const RowWant &w, size_t total, uint32_t slot, const uint32_t *row_slot);
@@ -251,9 +242,9 @@ int rows_run_ordered(NanoHipModel *m, const RowWant &w, size_t total, uint32_t s
 int rows_back(NanoHipModel *m, const RowWant &w, size_t total, const uint32_t *where, bool check);
 // batched prefill of one slot, as nano_hip_prefill / _prefill_score / _prefill_score_topk / _verify_draft call it
 int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t pos0, uint32_t count, const RowWant &want);
-// one prefill chunk of nb rows of `slot` (m->tokens / m->pos hold them; last_pos = the last row's position), eager or -- replay -- through the
-// bounded cache of chunk graphs under `key_kind` (RowWant::key_kind)
-hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, uint32_t mode, uint32_t last_pos, bool replay, uint32_t key_kind);
+// one prefill chunk of nb rows of `slot` (m->tokens / m->pos hold them; last_pos = the last row's position) of a call that wants `want` of
+// its rows, eager or -- replay -- through the bounded cache of chunk graphs
+hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, const RowWant &want, uint32_t last_pos, bool replay);
 int lookup_scratch(NanoHipModel *m);                   // backend_lookup.hip
 void lookup_free(NanoHipModel *m);
 // THE re-issue policy of every entry point that hands results over (round-6 advice: correctness after a give-up depends on every one of
@@ -273,12 +264,14 @@ static int with_reissue(NanoHipModel *m, Attempt attempt) {
 }
 
 // ---- backend_kv.hip ----
-// The KV rows of one step, built once per enqueue_step / enqueue_step_ordered: sequence b lives in KV slot `slot` + b, or -- one_slot,
-// batched prefill -- every token is a position of `slot`.  Contiguous cache: [slot][layer][S][kv_dim].  Paged cache: pools
+// The KV rows of one step, built once per enqueue_step / enqueue_step_ordered from the step's spec (of): sequence b lives in KV slot
+// `slot` + b, or -- one_slot, batched prefill -- every token is a position of `slot`, or -- ragged -- row b is a position of the slot the
+// pass's row map names (slot 0 as the base).  Contiguous cache: [slot][layer][S][kv_dim].  Paged cache: pools
 // [layer][page][64][kv_dim], a slot's table names the first pool row of each of its 64-position blocks.  Elements are FP32, or FP16
 // (kv_half); the caches are held as float *, so an offset into an FP16 cache goes through at() -- float * arithmetic counts 4-byte units.
 struct KvRows {
-    const NanoHipModel *m; uint32_t slot; bool one_slot;
+    const NanoHipModel *m; uint32_t slot; bool one_slot; bool ragged = false;
+    static KvRows of(const NanoHipModel *m, const StepSpec &s) { return KvRows{ m, s.ragged() ? 0u : s.slot, s.one_slot(), s.ragged() }; }
     size_t layer_elems() const { return (size_t)m->S * m->KD; }                                   // contiguous: one layer of one slot
     size_t slot_elems() const { return (size_t)m->d.n_layer * layer_elems(); }
     size_t plane_elems() const { return (size_t)m->kv.pages * 64 * m->KD; }                       // paged: one layer plane of the pool
@@ -301,14 +294,25 @@ void sampler_free(Sampler *sp);                        // backend_sampler.hip
 // ---- backend_step.hip ----
 hipError_t enqueue_classifier(NanoHipModel *m, uint32_t nb, uint32_t *ntiles_out = nullptr, float *dst = nullptr);    // dst: nullptr = m->logits
 hipError_t enqueue_score_rows(NanoHipModel *m, const float *logits, uint32_t rows, const uint32_t *targets, NanoHipTokenScore *out);
-hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint);
+// the fast step `s` describes, queued eagerly.  It writes nothing into the model but stamp bookkeeping and probe_ext: its caller records
+// m->nsplit = xba_nsplit(m, s), whether the step ran here or in a replay
+hipError_t enqueue_step(NanoHipModel *m, const StepSpec &s);
 bool strict_serves(const NanoHipModel *m);
 bool exact_serves(const NanoHipModel *m);
 int step_served(const NanoHipModel *m, bool prefill);
+// splits nano_hip_read_state still has to combine xba from after step `s` (1: the step leaves it final -- every chunk, ragged pass and
+// reference-order step (ordered), and a decode step whose range is not split or whose splits a kernel of its own combines)
+uint32_t xba_nsplit(const NanoHipModel *m, const StepSpec &s, bool ordered = false);
+// THE graph key of step `s` on this model (step_spec.h); key_kind: RowWant::key_kind of a chunk's call; ordered: the reference-order
+// step runs it.  STEP_NO_KEY: run it eagerly
+inline uint64_t step_key(const NanoHipModel *m, const StepSpec &s, uint32_t key_kind = 0, bool ordered = false) {
+    return step_key(s, ordered, key_kind, m->lora_on, m->stamp.on);
+}
 int run_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0);
 int stage_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, bool also_pos0, uint32_t *max_pos = nullptr);
 uint32_t range_hint_of(const NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t max_pos);
-int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos);
+// skip_embed: the greedy loop's steps after the first (StepSpec::skip_embed)
+int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos, bool skip_embed = false);
 // HIP graphs of a step: replay the graph stored under `key`, or -- first use -- run enqueue() eagerly (the launchers set their kernel
 // attributes and validate their arguments outside any capture), capture the same enqueue() for the replays to come, instantiate and
 // store it.  Reports and leaves the policy to the caller: `step` is the error of the work this call had to queue (the replay or the

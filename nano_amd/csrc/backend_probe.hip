@@ -60,13 +60,12 @@ extern "C" int nano_hip_time_classifier_in_step(NanoHipModel *m, uint32_t batch,
     if (!m || !iters || batch == 0 || batch > m->maxB || batch > NANO_MAX_BATCH || pos >= m->S) FAIL(NANO_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(m->device));
     { const int rc = stage_probe_batch(m, batch, pos); if (rc) return rc; }
-    const uint32_t range_hint = range_hint_of(m, 1, 1, pos);               // (this probe has always timed the step of the 64-position hint, whatever the batch)
+    StepSpec s = StepSpec::seqs(batch, 1, MODE_ARGMAX, range_hint_of(m, 1, 1, pos));      // (this probe has always timed the step of the 64-position hint, whatever the batch)
+    s.probe_cls = true;
+    m->nsplit = xba_nsplit(m, s);
     double cls = 0.0, empty = 0.0;
     for (uint32_t i = 0; i < iters + 1; i++) {
-        m->probe_cls = true;
-        hipError_t e = enqueue_step(m, batch, 1, MODE_ARGMAX, range_hint);
-        m->probe_cls = false;
-        HIP_TRY(e);
+        HIP_TRY(enqueue_step(m, s));
         HIP_TRY(hipEventSynchronize(m->ev2));
         float a = 0, b = 0;
         HIP_TRY(hipEventElapsedTime(&a, m->ev0, m->ev1));

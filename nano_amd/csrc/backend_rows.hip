@@ -3,7 +3,7 @@
 // ragged steps and the decode step with scores (nano_hip_forward_topk, below) share, and the one loop of strict / exact mode.
 // Ragged steps (nano_hip_step_rows): rows that each carry their own (KV slot, position).  The planner that cuts a call's rows into passes
 // (device-free, queryable), the host predicate of what the row map can address, and the entry point that stages the call once and queues
-// its passes through enqueue_step (backend_step.hip: m->rows).
+// its passes through enqueue_step as RAGGED specs (step_spec.h) over row groups the call itself keeps.
 #include <algorithm>
 
 #include "backend_model.h"
@@ -72,7 +72,6 @@ hipError_t enqueue_topk_rows(NanoHipModel *m, const float *logits, uint32_t rows
 // ---- the sink (backend_model.h says what each does) ----
 int rows_begin(NanoHipModel *m, const RowWant &w, bool passes, uint32_t more, size_t total, const uint32_t *targets) {
     if (const int rc = rows_scratch(m, w.need(passes) | more, total)) return rc;
-    m->rb.use_targets = w.use_targets();
     if (w.use_targets() && total) HIP_TRY(hipMemcpyAsync(m->rb.tgt, targets, total * 4, hipMemcpyHostToDevice, m->st));     // (a pageable source)
     return 0;
 }
@@ -86,12 +85,12 @@ hipError_t rows_after_step(NanoHipModel *m, const RowWant &w, size_t at, uint32_
     const NanoHipModel::RowScratch &s = m->rb;
     if (w.kind == RowWant::ARGMAX) return hipMemcpyAsync(s.out_amax + at, m->amax, nb * 4, hipMemcpyDeviceToDevice, m->st);
     if (w.kind != RowWant::SCORE) return hipSuccess;
-    const hipError_t e = enqueue_score_rows(m, m->logits, nb, s.use_targets ? s.tgt + at : nullptr, s.sc + at);
+    const hipError_t e = enqueue_score_rows(m, m->logits, nb, w.use_targets() ? s.tgt + at : nullptr, s.sc + at);
     return (e != hipSuccess || !w.k) ? e : enqueue_topk_rows(m, m->logits, nb, w.k, s.sc + at, s.top + at * w.k);
 }
-hipError_t rows_pass_targets(NanoHipModel *m, size_t at, uint32_t nb) {
+hipError_t rows_pass_targets(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb) {
     const NanoHipModel::RowScratch &s = m->rb;
-    return s.use_targets ? hipMemcpyAsync(s.targets, s.tgt + at, nb * 4, hipMemcpyDeviceToDevice, m->st) : hipSuccess;
+    return w.use_targets() ? hipMemcpyAsync(s.targets, s.tgt + at, nb * 4, hipMemcpyDeviceToDevice, m->st) : hipSuccess;
 }
 hipError_t rows_after_pass(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb) {
     const NanoHipModel::RowScratch &s = m->rb;
@@ -196,14 +195,12 @@ extern "C" int nano_hip_rows_addressable(uint32_t n_layer, uint32_t max_seq_len,
     return (uint64_t)max_seq_len * kv_dim * elem_bytes < (1ull << 32) ? 1 : 0;
 }
 
-// one ragged pass of nb rows (m->tokens / m->pos hold them, row_slot their slots, groups their buckets): eager, with m->pf for the
-// per-row split rule and the combine kernel
-static hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, uint32_t mode, const uint32_t *row_slot) {
-    m->pf = true; m->pf_slot = 0; m->rows.on = true; m->rows.row_slot = row_slot;
-    const hipError_t e = enqueue_step(m, nb, 1, mode, m->rows.groups.back().hint);
-    m->pf = false; m->rows.on = false; m->rows.row_slot = nullptr;
-    m->nsplit = 1;                                                     // (as a prefill chunk: xba is left final)
-    return e;
+// one ragged pass of nb rows (m->tokens / m->pos hold them, row_slot their slots, groups their buckets): eager; every row splits as
+// its own decode step and a kernel of its own combines, as in a prefill chunk
+static hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, const RowWant &want, const uint32_t *row_slot, const std::vector<RowGroup> &groups) {
+    const StepSpec s = StepSpec::ragged(nb, want.mode_pass(), row_slot, groups.data(), (uint32_t)groups.size(), want.use_targets());
+    m->nsplit = xba_nsplit(m, s);                                      // 1 (as a prefill chunk: xba is left final)
+    return enqueue_step(m, s);
 }
 
 // A ragged step, as nano_hip_step_rows (every row's arg-max, or nothing) and nano_hip_step_rows_score (every row's record and, k >= 1, its
@@ -262,19 +259,20 @@ static int step_rows_run(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_
         // strict / exact mode: one pass = one row (cap 1, so pass order is caller order): a reference-order step in the row's slot
         if (const int rc = rows_run_ordered(m, want, total, 0, stage.data() + 2 * total)) return rc;
     } else {
+        std::vector<RowGroup> groups;
         for (uint32_t p = 0; p < plan.n_passes; p++) {
             const size_t w0 = pass_start[p];
             const uint32_t nb = pass_start[p + 1] - pass_start[p];
             HIP_TRY(hipMemcpyAsync(m->tokens, m->rb.tok + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
             HIP_TRY(hipMemcpyAsync(m->pos, m->rb.pos + w0, nb * 4, hipMemcpyDeviceToDevice, m->st));
-            m->rows.groups.clear();
+            groups.clear();
             for (uint32_t j = 0; j < nb; j++) {                            // (sorted by hint: a group is a run of equal hints)
                 const uint32_t pos = stage[total + w0 + j], h = range_hint_of(m, 1, 1, pos);
-                if (m->rows.groups.empty() || m->rows.groups.back().hint != h) m->rows.groups.push_back({j, 1u, h});
-                else m->rows.groups.back().n++;
+                if (groups.empty() || groups.back().hint != h) groups.push_back({j, 1u, h});
+                else groups.back().n++;
             }
-            HIP_TRY(rows_pass_targets(m, w0, nb));
-            HIP_TRY(enqueue_rows_pass(m, nb, want.mode_pass(), m->rb.slot + w0));
+            HIP_TRY(rows_pass_targets(m, want, w0, nb));
+            HIP_TRY(enqueue_rows_pass(m, nb, want, m->rb.slot + w0, groups));
             HIP_TRY(rows_after_pass(m, want, w0, nb));
         }
     }

@@ -1,5 +1,8 @@
-// backend_step.hip -- one decode step, enqueued on m->st: the argument builders, the fast step, the reference-order step of strict and
-// exact mode, the graphs of a step, run_step, and which step serves the model's switches.
+// backend_step.hip -- one step, enqueued on m->st: the argument builders, the fast step, the reference-order step of strict and
+// exact mode, the graphs of a step, run_step, and which step serves the model's switches.  Both steps take a StepSpec (step_spec.h) and
+// read nothing about the step from the model: the same spec queues the same launches, eagerly or under capture, and step_key() of it is
+// the graph's key.  The runners (run_step, run_step_ordered; enqueue_chunk in backend.hip, the ragged pass in backend_rows.hip) record
+// m->nsplit = xba_nsplit(m, spec) themselves: a replay never runs the enqueue.
 #include "backend_model.h"
 
 namespace nano { extern hipEvent_t g_q80_probe_start, g_q80_probe_stop; }     // gemv_q80.hip: exact start / stop of the next STREAM launch
@@ -106,36 +109,77 @@ static GemvArgs w2_args(const NanoHipModel *m, uint32_t l, uint32_t nb) {
     return a;
 }
 // does the Wo launch combine the `nsplit` partials itself?  (else: a combine kernel of its own in front of it)
-static bool wo_takes_parts(const NanoHipModel *m, uint32_t nb, uint32_t nsplit) {
-    if (nsplit <= 1 || nsplit > 8 || m->pf) return false;
+static bool wo_takes_parts(const NanoHipModel *m, const StepSpec &s, uint32_t nsplit) {
+    const uint32_t nb = s.nb;
+    if (nsplit <= 1 || nsplit > 8 || s.rows_split_alone()) return false;
     // the plain-activation route first: a Wo launch the batched GEMM would take (Qwen3-4B at 2..8 sequences) keeps it -- the splits are
     // then combined by a kernel of its own.  (Asking only about the launch WITH the partials attached always answered "GEMV": the
     // batched routes refuse partials, and 4 sequences beyond 64 positions ran the 8-sequence SLAB GEMV: 2.6 ms against 2.0.)
     if (route_takes_fragments(kind_of(m, wo_args(m, 0, nb, 1)))) return false;
     return route_takes_attn_parts(kind_of(m, wo_args(m, 0, nb, nsplit)));
 }
-// splits nano_hip_read_state still has to combine xba from after a decode step (1: the step left it final)
-static uint32_t xba_nsplit(const NanoHipModel *m, uint32_t nb, uint32_t range_hint) {
-    const uint32_t ns = step_nsplit(m, nb, range_hint);
-    return (ns > 1 && !wo_takes_parts(m, nb, ns)) ? 1u : ns;
+// the attention splits of step s: a chunk's or ragged pass's rows split as the one-sequence decode step of the step's range hint does
+static uint32_t spec_nsplit(const NanoHipModel *m, const StepSpec &s) { return step_nsplit(m, s.rows_split_alone() ? 1u : s.nb, s.range_hint); }
+uint32_t xba_nsplit(const NanoHipModel *m, const StepSpec &s, bool ordered) {
+    if (s.rows != StepSpec::SEQS || ordered) return 1u;
+    const uint32_t ns = spec_nsplit(m, s);
+    return (ns > 1 && !wo_takes_parts(m, s, ns)) ? 1u : ns;
 }
-// The attention launches of one layer of a ragged pass (m->rows; `a` = the layer's arguments as enqueue_step built them for all nb rows).
+// paged KV cache: the table rows of the step's rows and the entries between them.  SEQS rows are slots 0 .. nb - 1 of the table, a chunk's
+// rows positions of its slot's table row, a ragged pass's rows index the whole table by row_slot.  The embed kernel stages each row's pool
+// row next to its RoPE row; the q | k | v launch and the attention kernel write there.
+static const uint32_t *paged_rows(const NanoHipModel *m, const StepSpec &s) { return m->kv.pt + (s.one_slot() ? (size_t)s.slot * m->kv.pt_stride : 0); }
+static uint32_t paged_bstride(const NanoHipModel *m, const StepSpec &s) { return s.rows_split_alone() ? 0u : m->kv.pt_stride; }
+// the step's first kernel: tokens -> x, and each row's RoPE row and -- paged cache -- pool row staged at fixed addresses
+static EmbedArgs embed_args(const NanoHipModel *m, const StepSpec &s) {
+    EmbedArgs ea{};
+    ea.tok = m->tok.w; ea.tok_s = m->tok.s; ea.tokens = m->tokens; ea.x = m->x;
+    ea.E = m->d.n_embd; ea.gs = m->d.group_size; ea.quant = m->d.quant_type; ea.x_bstride = m->d.n_embd;
+    ea.rope_cos = m->rope_cos; ea.rope_sin = m->rope_sin; ea.pos = m->pos; ea.rope_cur = m->rope_cos ? m->rope_cur : nullptr; ea.half = m->hd / 2;
+    if (m->kv.paged) { ea.pt_rows = paged_rows(m, s); ea.kvrow = m->kv.kvrow; ea.pt_bstride = paged_bstride(m, s); ea.pt_entries = m->kv.pt_stride; }
+    ea.row_slot = s.row_slot;
+    return ea;
+}
+// every row's arg-max of logits[nb][V] -> amax (the caller adds the classifier's partials and the loop's feedback)
+static ArgmaxArgs argmax_args(const NanoHipModel *m, uint32_t nb, const float *logits, uint32_t *amax) {
+    ArgmaxArgs aa{};
+    aa.logits = logits; aa.V = m->d.vocab_size; aa.bstride = m->d.vocab_size; aa.out = amax; aa.pos = m->pos; aa.pos0 = m->pos0; aa.nb = nb;
+    return aa;
+}
+// layer l's attention launch over all the step's rows: qk-norm, rope, k-cache write, attention   reference infer.c:810-879
+static AttnArgs attn_args(const NanoHipModel *m, const StepSpec &s, const KvRows &kv, uint32_t l, uint32_t nsplit) {
+    const NanoModelDesc &d = m->d;
+    AttnArgs a{};
+    a.err = m->dev_err;
+    a.q = m->q; a.kraw = m->kraw; kv.attention(a); a.pos = m->pos;
+    a.q_norm = m->q_norm ? m->q_norm + (size_t)l * m->hd : nullptr;
+    a.k_norm = m->k_norm ? m->k_norm + (size_t)l * m->hd : nullptr;
+    a.rope_cos = m->rope_cos; a.rope_sin = m->rope_sin; a.rope_cur = m->rope_cos ? m->rope_cur : nullptr;
+    a.out = m->attn_part; a.ml = m->attn_ml; a.xba_out = m->xba; a.nsplit = nsplit; a.range_hint = s.range_hint;
+    a.layer = l; a.n_layer = d.n_layer; a.S = m->S; a.hd = m->hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
+    a.q_dim = m->QD; a.kv_dim = m->KD; a.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); a.is_causal = s.is_causal;
+    a.kv_half = m->kv_half; a.vraw = m->kv_half ? m->vraw : nullptr;
+    if (m->kv.paged) { a.pt_rows = paged_rows(m, s); a.kvrow = m->kv.kvrow; a.pt_stride = m->kv.pt_stride; a.pt_bstride = paged_bstride(m, s); a.pool_rows = m->kv.pages * 64u; }
+    return a;
+}
+// The attention launches of one layer of a ragged pass (s.groups; `a` = the layer's arguments as attn_args built them for all nb rows).
 // Pass 1 over ALL rows finishes every k row -- and the v row, from scratch, on the FP16 and the contiguous FP32 cache -- so that every
 // row of the pass finds the rows of the earlier positions of its slot in the cache, whichever group they belong to.  Then one launch per
 // group of rows that share a range hint, with that bucket's split count and hint -- the launch a prefill chunk of the bucket gets -- on
 // the group's rows of every row-indexed array, and the combine launch where the range is split.  The groups run one after the other on
 // the stream, so their partials may lie anywhere in the partial buffers.
-static hipError_t enqueue_rows_attention(NanoHipModel *m, AttnArgs a, uint32_t nb, bool wo_frag) {
+static hipError_t enqueue_rows_attention(NanoHipModel *m, const StepSpec &s, AttnArgs a, bool wo_frag) {
     const NanoModelDesc &d = m->d;
     const uint32_t QD = m->QD, KD = m->KD;
     hipError_t e;
-    a.row_slot = m->rows.row_slot;
+    a.row_slot = s.row_slot;
     a.xf_out = nullptr; a.xsf_out = nullptr; a.stamps = nullptr;
     if (!m->kv_half && !m->kv.paged) a.vraw = m->rows.vraw;
     AttnArgs p = a;
-    p.prep_only = 1; p.nsplit = 1; p.range_hint = m->rows.groups.front().hint;    // (nothing attended: the fewest workgroups, the smallest range)
-    if ((e = launch_attention(p, nb, m->st)) != hipSuccess) return e;
-    for (const NanoHipModel::Rows::Group &g : m->rows.groups) {
+    p.prep_only = 1; p.nsplit = 1; p.range_hint = s.groups[0].hint;               // (nothing attended: the fewest workgroups, the smallest range)
+    if ((e = launch_attention(p, s.nb, m->st)) != hipSuccess) return e;
+    for (uint32_t gi = 0; gi < s.n_groups; gi++) {
+        const RowGroup &g = s.groups[gi];
         AttnArgs b = a;
         const uint32_t ns = step_nsplit(m, 1, g.hint);
         const size_t r0 = g.row0;
@@ -151,66 +195,46 @@ static hipError_t enqueue_rows_attention(NanoHipModel *m, AttnArgs a, uint32_t n
     }
     return hipSuccess;
 }
-// range_hint: host-side upper bound of the attended range of every sequence (a multiple of 64, <= S)
-hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t range_hint) {
+// s.range_hint: host-side upper bound of the attended range of every sequence (a multiple of 64, <= S)
+hipError_t enqueue_step(NanoHipModel *m, const StepSpec &s) {
     const NanoModelDesc &d = m->d;
-    const uint32_t E = d.n_embd, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
+    const uint32_t E = d.n_embd, KD = m->KD, L = d.n_layer, nb = s.nb, mode = s.mode;
     hipError_t e;
-    // Batched prefill splits every token's attention exactly as that token's own decode step would (chunks start on
+    // Batched prefill (CHUNK) splits every token's attention exactly as that token's own decode step would (chunks start on
     // multiples of the 64-position bucket, so one range_hint covers them) and combines with a kernel of its own: the KV
     // rows and the following logits then carry the bits of token-by-token ingestion.
-    // A ragged pass (m->rows.on, with m->pf; backend_rows.hip): rows of several slots and range buckets.  Its rows come sorted into groups
+    // A ragged pass (RAGGED; backend_rows.hip): rows of several slots and range buckets.  Its rows come sorted into groups
     // that share a range hint; each group gets the attention launch (and combine launch) of a prefill chunk of that bucket, so every row
     // still splits as its own decode step.  range_hint is the last group's (the largest), nsplit below the largest split count.
-    const bool ragged = m->rows.on;
-    const size_t ngroups = ragged ? m->rows.groups.size() : 1u;
-    const uint32_t nsplit = m->pf ? step_nsplit(m, 1, range_hint) : step_nsplit(m, nb, range_hint);
+    const bool ragged = s.ragged(), pf = s.rows_split_alone();
+    const size_t ngroups = ragged ? s.n_groups : 1u;
+    const uint32_t nsplit = spec_nsplit(m, s);
     // Does this step's Wo launch go to the batched GEMM (plain activations only), or is the range split wider than the Wo
     // GEMV's prologue combines?  Then a split attention is combined by a kernel of its own (as in batched prefill) -- for
     // <= 8 splits the same arithmetic, same bits.
-    const bool pf_combine = nsplit > 1 && !wo_takes_parts(m, nb, nsplit);
-    const uint32_t wo_nsplit = pf_combine ? 1u : nsplit;                     // splits the Wo launch combines in its prologue
+    const bool pf_combine = nsplit > 1 && !wo_takes_parts(m, s, nsplit);
+    const uint32_t wo_nsplit = pf_combine ? 1u : nsplit;                     // splits the Wo launch combines in its prologue (SEQS: xba_nsplit(m, s))
     const bool wo_gemm = route_takes_fragments(kind_of(m, wo_args(m, 0, nb, wo_nsplit)));
-    m->nsplit = pf_combine ? 1 : nsplit;
     // Single-split attention (or the combine kernel) of a step whose Wo launch goes to the batched GEMM: that kernel writes
     // Wo's quantized input itself (Q80 groups of 64 inside a head, fragment order) -- one quantizer launch less per layer.
     // (a ragged pass of several groups: fragment rows are 16-token tiles of the WHOLE pass, a group starts at any row -- its launches
     // write plain xba and the Wo launch runs its quantizer, which by definition makes the same fragments)
     const bool wo_frag = wo_gemm && d.group_size == 64 && m->hd % 64 == 0 && ngroups == 1;
-    EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
-                  m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0, nullptr, nullptr, 0, 0 };
-    // paged KV cache: the step's sequences are slots 0..nb-1 (batched prefill: every token is a position of slot pf_slot); the
-    // embed kernel stages each one's pool row next to its RoPE row, the QKV launch and the attention kernel write there
-    // (a ragged pass: row b is a position of slot row_slot[b] -- the kernels index the whole table / cache by it)
-    const uint32_t *pt_base = m->kv.paged ? m->kv.pt + ((m->pf && !ragged) ? (size_t)m->pf_slot * m->kv.pt_stride : 0) : nullptr;
-    const uint32_t pt_bstride = (m->kv.paged && !m->pf) ? m->kv.pt_stride : 0u;
-    const KvRows kv{ m, (m->pf && !ragged) ? m->pf_slot : 0u, m->pf && !ragged };
-    if (m->kv.paged) { ea.pt_rows = pt_base; ea.kvrow = m->kv.kvrow; ea.pt_bstride = pt_bstride; ea.pt_entries = m->kv.pt_stride; }
-    if (ragged) ea.row_slot = m->rows.row_slot;
+    EmbedArgs ea = embed_args(m, s);
+    const KvRows kv = KvRows::of(m, s);
     ea.tick = m->ho.tick;                                                       // the step's first kernel opens a new hand-off epoch
-    if (!(m->skip_embed && mode == MODE_LOOP) && (e = launch_embed(ea, nb, m->st)) != hipSuccess) return e;
+    if (s.embeds() && (e = launch_embed(ea, nb, m->st)) != hipSuccess) return e;
 
     for (uint32_t l = 0; l < L; l++) {
-        AttnArgs a{};
-        // q | raw k | v; v goes straight to its cache row; prefill: every token of the step is a position of KV slot pf_slot
+        // q | raw k | v; v goes straight to its cache row; a chunk: every token of the step is a position of KV slot s.slot
         GemvArgs qa = qkv_args(m, l, nb, m->x, m->rms_attn + (size_t)l * E, kv.v_target(l));
-        // qk-norm, rope, k-cache write, attention   reference infer.c:810-879
-        a.err = m->dev_err;
-        a.q = m->q; a.q_out = nullptr; a.kraw = m->kraw; kv.attention(a); a.pos = m->pos;
-        a.q_norm = m->q_norm ? m->q_norm + (size_t)l * m->hd : nullptr;
-        a.k_norm = m->k_norm ? m->k_norm + (size_t)l * m->hd : nullptr;
-        a.rope_cos = m->rope_cos; a.rope_sin = m->rope_sin; a.rope_cur = m->rope_cos ? m->rope_cur : nullptr; a.out = m->attn_part; a.ml = m->attn_ml; a.xba_out = m->xba; a.nsplit = nsplit; a.range_hint = range_hint;
-        a.layer = l; a.n_layer = L; a.S = S; a.hd = m->hd; a.n_head = d.n_head; a.n_kv_head = d.n_kv_head;
-        a.q_dim = QD; a.kv_dim = KD; a.rope_qwen3 = (d.arch == NANO_ARCH_QWEN3); a.is_causal = is_causal;
-        a.fixed_range = 0;
-        a.kv_half = m->kv_half; a.vraw = m->kv_half ? m->vraw : nullptr;
+        AttnArgs a = attn_args(m, s, kv, l, nsplit);
         if (wo_frag && nsplit == 1) { a.xf_out = m->gq; a.xsf_out = m->gxs; }
-        if (m->kv.paged) { a.pt_rows = pt_base; a.kvrow = m->kv.kvrow; a.pt_stride = m->kv.pt_stride; a.pt_bstride = pt_bstride; a.pool_rows = m->kv.pages * 64u; }
         qa.ordered = 0; qa.cus = (uint32_t)m->cus; qa.err = m->dev_err;
         // ONE launch for both (one sequence, Q80 group size 64, Qwen3 attention at head_dim 128: gemv_q80_impl.h qkv_attn_fused_kernel): the
         // attention workgroups start with the projection's, ask for their K / V rows and take q / k / v from it as write-through granules
         // tagged with the epoch of this step and layer (tick * 128 + l + 1: at most 126 layers).
-        const bool fused = m->ho.fuse_qkv_attn && m->ho.hand && nb == 1 && !m->pf && !m->lora_on && !m->stamp.on && L <= 126u &&
+        const bool fused = m->ho.fuse_qkv_attn && m->ho.hand && nb == 1 && !pf && !m->lora_on && !m->stamp.on && L <= 126u &&
                            kind_of(m, qa) == (d.quant_type == NANO_QUANT_Q4K ? ROUTE_Q4K : ROUTE_GEMV) && qkv_attn_fused_supports(d.quant_type, qa, a);
         if (fused) {
             if ((e = launch_qkv_attn_fused(d.quant_type, qa, a, m->ho.hand, m->ho.tick, l + 1u, m->st)) != hipSuccess) return e;
@@ -229,9 +253,9 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
                 if ((e = launch_lora_qkv(la_, nb, m->st)) != hipSuccess) return e;
             }
             if (ragged) {           // pass 1 over all rows, then a launch (and a combine launch) per range bucket
-                if ((e = enqueue_rows_attention(m, a, nb, wo_frag)) != hipSuccess) return e;
+                if ((e = enqueue_rows_attention(m, s, a, wo_frag)) != hipSuccess) return e;
             } else {
-                if (m->pf) {
+                if (pf) {
                     // batched prefill: the nb tokens are consecutive positions of ONE sequence.  Pass 1 finishes every k row
                     // (norm + RoPE + cache write -- paged: into its page -- nothing else) so that pass 2 finds the rows of the earlier
                     // tokens of the chunk in the cache; pass 2 is the ordinary decode attention per token (it recomputes its own k row).
@@ -264,7 +288,7 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
             // wide matrices a 1024-thread form LOST (1.531 vs 1.473 ms per step: workgroups that spill, polls queued behind their own 207 KB of weight
             // loads) -- wo13_shape refuses those shapes; Q4K's lost 1 % over positions 31..510 (profiles/r06_q4k_fused.txt), FP32's 1.5 % at
             // positions 20..39 and 2.9 % over 31..510.
-            const bool fuse13 = m->ho.fuse_wo_w13 && m->ho.hand2 && nb == 1 && !m->pf && !m->lora_on && !m->stamp.on && L <= 126u && d.quant_type == NANO_QUANT_Q80 &&
+            const bool fuse13 = m->ho.fuse_wo_w13 && m->ho.hand2 && nb == 1 && !pf && !m->lora_on && !m->stamp.on && L <= 126u && d.quant_type == NANO_QUANT_Q80 &&
                                 kind_of(m, a) == ROUTE_GEMV && kind_of(m, b) == ROUTE_GEMV && wo_w13_fused_supports(a, b);
             if (fuse13) {
                 if ((e = launch_wo_w13_fused(a, b, m->ho.hand2, m->ho.tick, l + 1u, m->st)) != hipSuccess) return e;
@@ -284,38 +308,37 @@ hipError_t enqueue_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32
     if (mode == MODE_NOCLS) return hipSuccess;
     if (mode == MODE_SCORE) {       // a scoring prefill chunk: the classifier over all nb rows (final rmsnorm in its prologue), then their statistics
         if ((e = enqueue_classifier(m, nb, nullptr, m->rb.logits)) != hipSuccess) return e;
-        return enqueue_score_rows(m, m->rb.logits, nb, m->rb.use_targets ? m->rb.targets : nullptr, m->rb.rows);
+        return enqueue_score_rows(m, m->rb.logits, nb, s.use_targets ? m->rb.targets : nullptr, m->rb.rows);
     }
     if (mode == MODE_VERIFY) {      // a verify chunk: the classifier over all nb rows, then every row's arg-max (a scan of its logits: the partials buffer holds max_batch rows)
         if ((e = enqueue_classifier(m, nb, nullptr, m->rb.logits)) != hipSuccess) return e;
-        ArgmaxArgs aa{ m->rb.logits, d.vocab_size, d.vocab_size, m->rb.amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
-        return launch_argmax(aa, nb, m->st);
+        return launch_argmax(argmax_args(m, nb, m->rb.logits, m->rb.amax), nb, m->st);
     }
     const bool sample = (mode == MODE_ARGMAX || mode == MODE_LOOP);
     uint32_t ntiles = 0;
     // probe: Q80 STREAM classifier (batch <= 8) -> the kernel's own start / stop timestamps (hipExtLaunchKernelGGL);
     // other classifiers -> events recorded around the launch (ev1..ev2 = an empty pair, the event overhead)
-    bool probe_ext = m->probe_cls && d.quant_type == NANO_QUANT_Q80 && nb <= 8 && d.vocab_size >= 16384 && !route_takes_fragments(kind_of(m, classifier_args(m, nb, m->logits)));
-    if (m->probe_cls && d.quant_type == NANO_QUANT_Q4K && nb == 1 && d.vocab_size >= 65536) {      // gemv_q4k_chunk.hip's looping launch
+    bool probe_ext = s.probe_cls && d.quant_type == NANO_QUANT_Q80 && nb <= 8 && d.vocab_size >= 16384 && !route_takes_fragments(kind_of(m, classifier_args(m, nb, m->logits)));
+    if (s.probe_cls && d.quant_type == NANO_QUANT_Q4K && nb == 1 && d.vocab_size >= 65536) {      // gemv_q4k_chunk.hip's looping launch
         GemvArgs ca = classifier_args(m, nb, m->logits);
         Q4kGemvPlan cp;
         probe_ext = gemv_q4k_plan(ca, &cp) && cp.kernel == Q4K_KERNEL_CHUNK && cp.loop;
     }
     if (probe_ext) { g_q80_probe_start = m->ev0; g_q80_probe_stop = m->ev1; }
-    else if (m->probe_cls && (e = hipEventRecord(m->ev0, m->st)) != hipSuccess) return e;
+    else if (s.probe_cls && (e = hipEventRecord(m->ev0, m->st)) != hipSuccess) return e;
     if ((e = enqueue_classifier(m, nb, sample ? &ntiles : nullptr)) != hipSuccess) return e;
     g_q80_probe_start = g_q80_probe_stop = nullptr;
-    if (m->probe_cls) {
+    if (s.probe_cls) {
         if (!probe_ext && (e = hipEventRecord(m->ev1, m->st)) != hipSuccess) return e;
         if ((e = hipEventRecord(m->ev2, m->st)) != hipSuccess) return e;
     }
     m->probe_ext = probe_ext;   // final rmsnorm fused in the prologue (infer.c:999-1015)
     if (sample) {
-        ArgmaxArgs aa{ m->logits, d.vocab_size, d.vocab_size, m->amax, nullptr, m->pos, nullptr, m->pos0, nb,
-                       ntiles ? m->tile_max : nullptr, ntiles };
+        ArgmaxArgs aa = argmax_args(m, nb, m->logits, m->amax);
+        if (ntiles) { aa.tile_max = m->tile_max; aa.ntiles = ntiles; }
         if (mode == MODE_LOOP) {
             aa.tokens = m->tokens; aa.trace = m->trace;
-            if (!m->pf) { aa.emb = ea; aa.rope_rows = m->rope_rows; }      // ... and embeds the token it picked for the next step
+            if (!pf) { aa.emb = ea; aa.rope_rows = m->rope_rows; }      // ... and embeds the token it picked for the next step
         }
         if ((e = launch_argmax(aa, nb, m->st)) != hipSuccess) return e;
     }
@@ -352,9 +375,10 @@ static hipError_t strict_project(NanoHipModel *m, GemvArgs a) {
     return hipSuccess;
 }
 // (the caller has asked step_served(): neither the LoRA side branches nor the FP16 / paged KV cache are on)
-static hipError_t enqueue_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0, bool exact_kernels) {
+static hipError_t enqueue_step_ordered(NanoHipModel *m, const StepSpec &s, bool exact_kernels) {
     const NanoModelDesc &d = m->d;
     const uint32_t E = d.n_embd, H = d.n_hidden, QD = m->QD, KD = m->KD, L = d.n_layer, S = m->S;
+    const uint32_t nb = s.nb, is_causal = s.is_causal, mode = s.mode, slot0 = s.slot;
     const bool one_launch = exact_kernels && exact_attention_fits(m->hd, S) && KD % 4u == 0;
     hipError_t e;
 #define ST(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
@@ -362,12 +386,9 @@ static hipError_t enqueue_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is
     // early-out one: nothing that could synchronise may sit in a capture.
     auto phase = [&](int32_t layer, int32_t ph) { return exact_kernels ? hipSuccess : strict_phase(m, layer, ph); };
     auto rmsnorm = [&](const float *w) { return exact_kernels ? launch_exact_rmsnorm(m->xn, m->x, w, E, nb, E, E, m->st) : launch_strict_rmsnorm(m->xn, m->x, w, E, nb, E, E, m->st); };
-    m->nsplit = 1;                                                      // xba holds final head outputs (nano_hip_read_state, also from inside the hook)
     ST(phase(-1, 1));                                                   // NANO_LLM_PHASE_EMBEDDING
-    EmbedArgs ea{ m->tok.w, m->tok.s, m->tokens, m->x, E, d.group_size, d.quant_type, E,
-                  m->rope_cos, m->rope_sin, m->pos, m->rope_cos ? m->rope_cur : nullptr, m->hd / 2, 0 };
-    ST(launch_embed(ea, nb, m->st));
-    const KvRows kv{ m, slot0, false };
+    ST(launch_embed(embed_args(m, s), nb, m->st));
+    const KvRows kv = KvRows::of(m, s);
     for (uint32_t l = 0; l < L; l++) {
         ST(phase(l, 2));                                                // ATTN_NORM   infer.c:755-758
         ST(rmsnorm(m->rms_attn + (size_t)l * E));
@@ -409,7 +430,7 @@ static hipError_t enqueue_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is
         ST(strict_project(m, a));
     }
     if (mode == MODE_ARGMAX || mode == MODE_LOOP) {
-        ArgmaxArgs aa{ m->logits, d.vocab_size, d.vocab_size, m->amax, nullptr, m->pos, nullptr, m->pos0, nb, nullptr, 0 };
+        ArgmaxArgs aa = argmax_args(m, nb, m->logits, m->amax);
         if (mode == MODE_LOOP) { aa.tokens = m->tokens; aa.trace = m->trace; }
         ST(launch_argmax(aa, nb, m->st));
     }
@@ -480,14 +501,15 @@ static int graph_step_check(const GraphRun &r) {
 // runs eagerly; exact mode replays one graph per (batch, mode, is_causal, slot0).
 int run_step_ordered(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t slot0) {
     const bool exact = exact_serves(m);
-    m->nsplit = 1;
-    if (!exact || !m->use_graph) {
-        HIP_TRY(enqueue_step_ordered(m, nb, is_causal, mode, slot0, exact));
+    const StepSpec s = StepSpec::seqs(nb, is_causal, mode, 0, slot0);
+    const uint64_t key = (exact && m->use_graph) ? step_key(m, s, 0, true) : STEP_NO_KEY;
+    m->nsplit = xba_nsplit(m, s, true);                                    // 1: xba holds final head outputs (nano_hip_read_state, also from inside the hook)
+    if (key == STEP_NO_KEY) {
+        HIP_TRY(enqueue_step_ordered(m, s, exact));
         if (exact) m->exact_launches = 0;
         return 0;
     }
-    const uint64_t key = (1ull << 61) | ((uint64_t)slot0 << 32) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
-    const GraphRun r = graph_step(m, key, [&] { return enqueue_step_ordered(m, nb, is_causal, mode, slot0, true); });
+    const GraphRun r = graph_step(m, key, [&, s] { return enqueue_step_ordered(m, s, true); });
     if (const int rc = graph_step_check(r)) return rc;
     if (r.stored) m->exact_nodes[key] = r.nodes;
     m->exact_launches = m->exact_nodes[key];
@@ -526,20 +548,19 @@ uint32_t range_hint_of(const NanoHipModel *m, uint32_t nb, uint32_t is_causal, u
     return hint > m->S ? m->S : hint;
 }
 // max_pos: largest position among the sequences of this step (host knowledge; the device reads the exact pos[b])
-int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos) {
+int run_step(NanoHipModel *m, uint32_t nb, uint32_t is_causal, uint32_t mode, uint32_t max_pos, bool skip_embed) {
     if (const int rc = step_served(m, false)) return rc;
     if (strict_serves(m) || exact_serves(m)) return run_step_ordered(m, nb, is_causal, mode, 0);
-    const uint32_t range_hint = range_hint_of(m, nb, is_causal, max_pos);
+    StepSpec s = StepSpec::seqs(nb, is_causal, mode, range_hint_of(m, nb, is_causal, max_pos));
+    s.skip_embed = skip_embed;
     // (measurement builds: NANO_STAMPS_GRAPH=1 captures the stamped step too -- the stamp slots are baked into a graph of its own key)
 #if NANO_STAMPS
     static const bool stamps_graph = getenv("NANO_STAMPS_GRAPH") && *getenv("NANO_STAMPS_GRAPH") == '1';
 #else
     constexpr bool stamps_graph = false;
 #endif
-    if (!m->use_graph || (m->stamp.on && !stamps_graph)) { HIP_TRY(enqueue_step(m, nb, is_causal, mode, range_hint)); m->nsplit = xba_nsplit(m, nb, range_hint); return 0; }
-    const uint64_t key = ((uint64_t)(m->stamp.on ? 1 : 0) << 50) | ((uint64_t)((m->skip_embed && mode == MODE_LOOP) ? 1 : 0) << 49) | ((uint64_t)(m->lora_on ? 1 : 0) << 48) |
-                         ((uint64_t)range_hint << 16) | ((uint64_t)nb << 8) | ((uint64_t)is_causal << 4) | mode;
-    const GraphRun r = graph_step(m, key, [&] { return enqueue_step(m, nb, is_causal, mode, range_hint); });
-    m->nsplit = xba_nsplit(m, nb, range_hint);
-    return graph_step_check(r);
+    const uint64_t key = (m->use_graph && (!m->stamp.on || stamps_graph)) ? step_key(m, s) : STEP_NO_KEY;
+    m->nsplit = xba_nsplit(m, s);
+    if (key == STEP_NO_KEY) { HIP_TRY(enqueue_step(m, s)); return 0; }
+    return graph_step_check(graph_step(m, key, [&, s] { return enqueue_step(m, s); }));
 }
