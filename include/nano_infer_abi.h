@@ -222,6 +222,22 @@ int nano_forward_batch(Nano_Context *ctx, const uint32_t *tokens, const uint32_t
 int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                               Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
                               uint32_t *out_ids);
+/* Logit edits (nano_mi355x.h, "logit edits"): an allowed-token mask (ceil(V / 32) words, bit (j & 31) of word (j >> 5) allows token j,
+ * NULL = every token) and a bias list (n_bias <= NANO_BIAS_MAX distinct tokens with their biases), applied in front of the pick:
+ * l' = allowed ? l + bias : -inf, and a disallowed token is never a candidate, so the returned id is always an allowed one.
+ * nano_set_logit_edit copies `edit` into the context (NULL clears it); it then applies to the decode branch of generate_next_token,
+ * and therefore to sessions and generate_sync; prompt positions are unaffected.  With an edit set the greedy branch (temperature 0,
+ * penalty 1) goes through the device sampler as a temperature-0 row, not through the arg-max of the forward or the lookup-draft loop.
+ * The host loops (per-phase observation, NANO_HOST_SAMPLER=1, rows the device declines) apply the same edit and the same candidate
+ * filter: device and host agree id for id.  Without an edit every path is what it was.  Returns 0, or NANO_HIP_EINVAL for an edit the
+ * device sampler would refuse (no allowed token, too many / duplicate / out-of-vocabulary bias tokens, a NaN or +inf bias).
+ * nano_forward_batch_sample_edit is nano_forward_batch_sample with edits[i] for sequence i (`edits` NULL: no edits; an entry with a
+ * NULL mask and n_bias 0: none for that sequence); nano_forward_batch_sample is this call with edits = NULL. */
+typedef struct NanoLogitEdit { const uint32_t *allow; const uint32_t *bias_tokens; const float *bias_values; uint32_t n_bias; } NanoLogitEdit;
+int nano_set_logit_edit(Nano_Context *ctx, const NanoLogitEdit *edit);
+int nano_forward_batch_sample_edit(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                   Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
+                                   const NanoLogitEdit *edits, uint32_t *out_ids);
 /* Ingest prefix_ids[0..n_prefix) once per device and make it the first n_prefix positions of sequences 0..batch-1 of the
  * context (the sequences nano_forward_batch addresses): N continuations of one prompt, or N questions behind one instruction
  * prefix, pay the prompt once.  With replicas (sequence i -> replica i mod G, slot i / G) each replica ingests the prefix into

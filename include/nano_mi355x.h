@@ -434,6 +434,54 @@ int nano_hip_forward_sample_batch_ex(NanoHipModel *m, const uint32_t *tokens, co
 int nano_hip_op_sample_batch_ex(NanoHipModel *m, const float *logits, uint32_t batch,
                                 const NanoHipSampleParamsEx *params, NanoHipSample *out);
 
+/* ---- logit edits: allowed-token masks and logit bias in front of the pick ---------------------------------
+ * The _ex calls above with a per-row edit; they are these calls with no edit, and a row without an edit is the _ex row field for field.
+ * Let V be the vocabulary and W = ceil(V / 32).  A row may carry
+ *   - a mask: W words; token j is allowed when bit (j & 31) of word (j >> 5) is set.  Bits of tokens >= V in the last word are ignored,
+ *     whatever they hold.  Given per call (`allow`, host memory, uploaded with the call) or by id from the model's mask table
+ *     (`mask_id`, 1-based; nano_hip_mask_table_set uploads the table once: ban lists, fixed answer sets, a grammar's per-state masks);
+ *   - a bias list: n_bias <= NANO_BIAS_MAX entries {token, bias}; the tokens are distinct and may come in any order.
+ * The edited row is
+ *     x_j  = l_j + b_j                      one float32 add, only for a token that has an entry; a token without one keeps its stored bits
+ *     l'_j = allowed(j) ? x_j : -INFINITY
+ * and the result is the sampler's result on l' as the _ex call defines it: penalty, temperature, softmax over all V, candidates, stable
+ * sort, top-k cut, top-p cut, draw; temperature 0 gives the first maximum of the penalised l'.  So y = ((l + b) / penalty) / temperature.
+ * ONE difference from the reference sampler run on l': a disallowed token is never a candidate -- the candidate test is
+ *     allowed(j) && p_j >= cutoff.
+ * For top_p < 1 that changes nothing (p = 0 < cutoff).  For top_p >= 1 the cutoff is <= 0 and the reference on l' counts the p = 0
+ * tokens as candidates, lists them in top[] and returns the sorted list's last entry when coin * sum is not below the sum; with the filter
+ * n_candidates and top[] hold allowed tokens only.
+ * GUARANTEE: a result with NANO_SAMPLE_OK names an allowed token, for every top_p, top_k, coin and temperature.
+ *   - sum_bits and walked_chunks are those of the _ex call on l';
+ *   - a -inf bias is allowed and bans that one token;
+ *   - an edited row whose allowed tokens are all -inf after the bias is unspecified, as rows of -inf only are elsewhere;
+ *   - the step's logits are NOT modified: nano_hip_read_state(m, i, 4, ...) still returns what nano_hip_forward leaves; the edit enters
+ *     only the sampler's y.
+ * NANO_HIP_EINVAL before anything is queued (a failed table call leaves the old table in place) for: `allow` and `mask_id` both given;
+ * a mask_id beyond the table; a mask (per call or in the table) with no allowed token among its first V bits; n_bias > NANO_BIAS_MAX;
+ * n_bias > 0 with a null list; a bias token >= V; a token listed twice; a NaN or +inf bias; and everything the _ex calls refuse.
+ * The staging of per-call masks and bias lists -- pinned plus device memory of max_batch x (W x 4 + NANO_BIAS_MAX x 8) bytes -- is
+ * allocated on the first call that carries an edit (NANO_HIP_ENOMEM leaves the model usable); callers that never edit allocate nothing
+ * new.  Masks and lists go up in the same single copy as the rows' parameters and new history ids; a table mask costs no upload.
+ * NOT offered here: edits for nano_hip_decode_greedy's device loop, nano_hip_decode_lookup and nano_hip_verify_draft; for the scoring
+ * and top-k entry points (log-probs renormalised over an allowed set are another reduction); inside nano_hip_step_rows; and deriving
+ * masks from a grammar -- that is the caller's library, this is the hook it needs. */
+#define NANO_BIAS_MAX 1024u
+typedef struct NanoHipLogitBias { uint32_t token; float bias; } NanoHipLogitBias;
+typedef struct NanoHipSampleParamsEdit {
+    NanoHipSampleParamsEx ex;            /* reserved words still 0 */
+    const uint32_t *allow;               /* host, W words, or NULL */
+    const NanoHipLogitBias *bias;        /* host, n_bias entries, or NULL */
+    uint32_t mask_id;                    /* 0 = none, else 1-based index into the model's mask table */
+    uint32_t n_bias;
+} NanoHipSampleParamsEdit;
+/* n_masks x W words (host); replaces the table; n_masks = 0 frees it */
+int nano_hip_mask_table_set(NanoHipModel *m, const uint32_t *words, uint32_t n_masks);
+int nano_hip_forward_sample_batch_edit(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                       const NanoHipSampleParamsEdit *params, NanoHipSample *out);
+int nano_hip_op_sample_batch_edit(NanoHipModel *m, const float *logits, uint32_t batch,
+                                  const NanoHipSampleParamsEdit *params, NanoHipSample *out);
+
 /* ---- strict-parity / per-phase mode -------------------------------------------------------------------------
  * nano_hip_set_strict(m, 1): every later forward / prefill runs eagerly, one kernel per reference operator, with
  * every float reduction (rmsnorm, q.k, softmax sum, weighted V, FP32 matmul) in the reference's sequential order

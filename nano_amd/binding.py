@@ -255,7 +255,13 @@ def lib() -> C.CDLL:
                        ("nano_hip_forward_topk", [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
                        ("nano_hip_step_rows_score", [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]),
                        ("nano_score_ids_topk", [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_double)]),
-                       ("nano_forward_batch_topk", [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp])):
+                       ("nano_forward_batch_topk", [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]),
+                       # logit edits
+                       ("nano_hip_forward_sample_batch_edit", [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
+                       ("nano_hip_op_sample_batch_edit", [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
+                       ("nano_hip_mask_table_set", [vp, C.c_void_p, C.c_uint32]),
+                       ("nano_set_logit_edit", [vp, vp]),
+                       ("nano_forward_batch_sample_edit", [vp, u32p, u32p, C.c_uint32, vp, vp, vp, vp, vp])):
         if hasattr(L, name) or not os.environ.get("NANO_LIB"):
             fn(name, C.c_int, args)
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
@@ -362,6 +368,57 @@ def sample_params_ex(rows, top_k):
     for i, k in enumerate(ks):
         arr[i].p = base[i]
         arr[i].top_k = k
+    return arr, keep
+
+
+NANO_BIAS_MAX = 1024
+
+
+class NanoHipLogitBias(C.Structure):
+    """One entry of a row's bias list (include/nano_mi355x.h NanoHipLogitBias)."""
+    _fields_ = [("token", C.c_uint32), ("bias", C.c_float)]
+
+
+class NanoHipSampleParamsEdit(C.Structure):
+    """A row with a logit edit (include/nano_mi355x.h NanoHipSampleParamsEdit): a mask per call (allow) or by table id, and a bias list."""
+    _fields_ = [("ex", NanoHipSampleParamsEx), ("allow", C.POINTER(C.c_uint32)), ("bias", C.POINTER(NanoHipLogitBias)),
+                ("mask_id", C.c_uint32), ("n_bias", C.c_uint32)]
+
+
+def mask_words(allowed, vocab):
+    """ceil(vocab / 32) mask words from a boolean array [vocab] or a list of allowed ids"""
+    a = np.asarray(allowed)
+    on = np.zeros(-(-vocab // 32) * 32, bool)
+    if a.dtype == bool:
+        on[:vocab] = a.reshape(-1)
+    else:
+        on[a.astype(np.int64).reshape(-1)] = True
+    return np.packbits(on.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+
+
+def sample_params_edit(rows, top_k, edits):
+    """sample_params_ex() with row i's edit: None, or a dict with any of allow (uint32 mask words), mask_id (int, 1-based),
+    bias (a (tokens, values) pair of arrays)"""
+    base, keep = sample_params_ex(rows, top_k)
+    edits = [None] * len(rows) if edits is None else list(edits)
+    assert len(edits) == len(rows)
+    arr = (NanoHipSampleParamsEdit * len(rows))()
+    for i, e in enumerate(edits):
+        arr[i].ex = base[i]
+        if not e:
+            continue
+        if e.get("allow") is not None:
+            w = np.ascontiguousarray(e["allow"], np.uint32).reshape(-1)
+            keep.append(w)
+            arr[i].allow = w.ctypes.data_as(C.POINTER(C.c_uint32))
+        arr[i].mask_id = int(e.get("mask_id", 0))
+        b = e.get("bias")
+        if b is not None and len(b[0]):
+            ent = np.zeros(np.size(b[0]), np.dtype([("token", "<u4"), ("bias", "<f4")]))      # NanoHipLogitBias[n]
+            ent["token"], ent["bias"] = np.asarray(b[0]).reshape(-1), np.asarray(b[1]).reshape(-1)
+            keep.append(ent)
+            arr[i].bias = ent.ctypes.data_as(C.POINTER(NanoHipLogitBias))
+            arr[i].n_bias = ent.size
     return arr, keep
 
 
@@ -551,13 +608,24 @@ class DeviceModel:
         check(lib().nano_hip_op_sample(self.h, l, h, h.size, repetition_penalty, temperature, top_p, coin, C.byref(r)))
         return r
 
-    def forward_sample_batch(self, tokens: Sequence[int], pos: Sequence[int], params, top_k=0) -> list:
+    def set_mask_table(self, masks) -> None:
+        """nano_hip_mask_table_set: masks [n][ceil(V / 32)] uint32 words replace the model's mask table (rows refer to it by
+        mask_id = index + 1); None or an empty array frees it."""
+        w = np.zeros((0, 0), np.uint32) if masks is None else np.ascontiguousarray(masks, np.uint32)
+        n = 0 if w.size == 0 else (1 if w.ndim == 1 else w.shape[0])
+        check(lib().nano_hip_mask_table_set(self.h, w.ctypes.data if n else None, n))
+
+    def forward_sample_batch(self, tokens: Sequence[int], pos: Sequence[int], params, top_k=0, edits=None) -> list:
         """One decode step of slots 0..B-1, then row i sampled on the device with params[i] =
-        (repetition_penalty, temperature, top_p, coin, history); one NanoHipSample per row.  top_k: one int, or one per row."""
+        (repetition_penalty, temperature, top_p, coin, history); one NanoHipSample per row.  top_k: one int, or one per row.
+        edits: None (the entry points without edits), or one entry per row as sample_params_edit takes them."""
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
         out = (NanoHipSample * max(t.size, 1))()
-        if np.isscalar(top_k) and top_k == 0:
+        if edits is not None:
+            arr, _keep = sample_params_edit(params, top_k, edits)
+            check(lib().nano_hip_forward_sample_batch_edit(self.h, t, p, t.size, arr, out))
+        elif np.isscalar(top_k) and top_k == 0:
             arr, _keep = sample_params(params)
             check(lib().nano_hip_forward_sample_batch(self.h, t, p, t.size, arr, out))
         else:
@@ -565,12 +633,15 @@ class DeviceModel:
             check(lib().nano_hip_forward_sample_batch_ex(self.h, t, p, t.size, arr, out))
         return list(out)[:t.size]
 
-    def op_sample_batch(self, logits: np.ndarray, params, top_k=0) -> list:
-        """The batched device sampler alone, on host logits [B][V]; params and top_k as forward_sample_batch."""
+    def op_sample_batch(self, logits: np.ndarray, params, top_k=0, edits=None) -> list:
+        """The batched device sampler alone, on host logits [B][V]; params, top_k and edits as forward_sample_batch."""
         l = np.ascontiguousarray(logits, np.float32)
         assert l.ndim == 2 and l.shape[1] == self.vocab
         out = (NanoHipSample * max(l.shape[0], 1))()
-        if np.isscalar(top_k) and top_k == 0:
+        if edits is not None:
+            arr, _keep = sample_params_edit(params, top_k, edits)
+            check(lib().nano_hip_op_sample_batch_edit(self.h, l.reshape(-1), l.shape[0], arr, out))
+        elif np.isscalar(top_k) and top_k == 0:
             arr, _keep = sample_params(params)
             check(lib().nano_hip_op_sample_batch(self.h, l.reshape(-1), l.shape[0], arr, out))
         else:
@@ -1237,9 +1308,17 @@ class Engine:
         check(self.L.nano_prefill_batch(self.ctx, ptrs, n, len(ps), first.ctypes.data if want_first_ids else None))
         return first[:len(ps)] if want_first_ids else None
 
-    def forward_batch_sample(self, tokens: Sequence[int], pos: Sequence[int], samplers, histories) -> np.ndarray:
+    def set_logit_edit(self, allow=None, bias=None) -> None:
+        """nano_set_logit_edit: allow = mask words (or None), bias = (tokens, values) (or None); both None clears the context's edit."""
+        if allow is None and bias is None:
+            check(self.L.nano_set_logit_edit(self.ctx, None)); return
+        e, _keep = logit_edit(allow, bias)
+        check(self.L.nano_set_logit_edit(self.ctx, C.cast(C.pointer(e), C.c_void_p)))
+
+    def forward_batch_sample(self, tokens: Sequence[int], pos: Sequence[int], samplers, histories, edits=None) -> np.ndarray:
         """nano_forward_batch_sample: one decode step of B sequences, sequence i sampled with samplers[i] (from build_sampler)
-        over histories[i] (the ids its repetition penalty marks); returns the B sampled ids."""
+        over histories[i] (the ids its repetition penalty marks); returns the B sampled ids.  edits: None, or per sequence None or
+        (allow words or None, (bias tokens, bias values) or None): nano_forward_batch_sample_edit."""
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         p = np.ascontiguousarray(pos, np.uint32).reshape(-1)
         B = t.size
@@ -1248,6 +1327,14 @@ class Engine:
         hp = (C.POINTER(C.c_uint32) * B)(*[h.ctypes.data_as(C.POINTER(C.c_uint32)) if h.size else None for h in hs])
         nh = np.array([h.size for h in hs], np.uint32)
         out = np.empty(B, np.uint32)
+        if edits is not None:
+            arr, keep = (NanoLogitEdit * B)(), []
+            for i, e in enumerate(edits):
+                if e is not None:
+                    arr[i], k = logit_edit(*e); keep.append(k)
+            check(self.L.nano_forward_batch_sample_edit(self.ctx, t, p, B, C.cast(sp, C.c_void_p), C.cast(hp, C.c_void_p),
+                                                        nh.ctypes.data, C.cast(arr, C.c_void_p), out.ctypes.data))
+            return out
         check(self.L.nano_forward_batch_sample(self.ctx, t, p, B, C.cast(sp, C.c_void_p), C.cast(hp, C.c_void_p),
                                                nh.ctypes.data, out.ctypes.data))
         return out
@@ -1267,6 +1354,23 @@ class Engine:
                 break
         self.L.llm_session_free(s)
         return out, status
+
+
+class NanoLogitEdit(C.Structure):
+    """NanoLogitEdit (include/nano_infer_abi.h)."""
+    _fields_ = [("allow", C.POINTER(C.c_uint32)), ("bias_tokens", C.POINTER(C.c_uint32)), ("bias_values", C.POINTER(C.c_float)), ("n_bias", C.c_uint32)]
+
+
+def logit_edit(allow=None, bias=None):
+    """(NanoLogitEdit, the arrays it points into) from mask words and a (tokens, values) pair"""
+    e, keep = NanoLogitEdit(), []
+    if allow is not None:
+        w = np.ascontiguousarray(allow, np.uint32).reshape(-1); keep.append(w)
+        e.allow = w.ctypes.data_as(C.POINTER(C.c_uint32))
+    if bias is not None and len(bias[0]):
+        t = np.ascontiguousarray(bias[0], np.uint32).reshape(-1); v = np.ascontiguousarray(bias[1], np.float32).reshape(-1); keep += [t, v]
+        e.bias_tokens, e.bias_values, e.n_bias = t.ctypes.data_as(C.POINTER(C.c_uint32)), v.ctypes.data_as(C.POINTER(C.c_float)), t.size
+    return e, keep
 
 
 class SamplerC(C.Structure):

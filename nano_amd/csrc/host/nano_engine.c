@@ -330,7 +330,67 @@ Nano_Context *llm_context_init(char *model_path, char *lora_path, uint32_t max_s
     return ctx;
 }
 
+/* A context's logit edit (nano_set_logit_edit): kept beside the context, whose layout is the ABI and cannot grow.  The copy is in the
+ * device sampler's form: mask words and {token, bias} entries. */
+typedef struct HostEdit { const uint32_t *allow; const NanoHipLogitBias *bias; uint32_t n_bias; } HostEdit;
+typedef struct CtxEdit { const Nano_Context *ctx; uint32_t *allow; NanoHipLogitBias *bias; HostEdit e; } CtxEdit;
+static CtxEdit g_edit[MAX_MODELS];
+static const HostEdit *ctx_edit(const Nano_Context *ctx) {
+    for (int i = 0; i < MAX_MODELS; i++) if (g_edit[i].ctx == ctx) return &g_edit[i].e;
+    return NULL;
+}
+static void ctx_edit_clear(const Nano_Context *ctx) {
+    for (int i = 0; i < MAX_MODELS; i++)
+        if (g_edit[i].ctx == ctx) { free(g_edit[i].allow); free(g_edit[i].bias); memset(&g_edit[i], 0, sizeof g_edit[i]); }
+}
+static int cmp_u32(const void *a, const void *b) { const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b; return x < y ? -1 : x > y; }
+/* the refusals of the device sampler (nano_mi355x.h "logit edits"), for the paths that do not reach it */
+static int edit_check(uint32_t V, const NanoLogitEdit *ed) {
+    if (ed->allow) {
+        const uint32_t W = (V + 31u) / 32u;
+        uint32_t any = 0;
+        for (uint32_t j = 0; j + 1 < W; j++) any |= ed->allow[j];
+        any |= ed->allow[W - 1] & (V % 32u ? (1u << (V % 32u)) - 1u : 0xffffffffu);
+        if (!any) return NANO_HIP_EINVAL;
+    }
+    if (ed->n_bias > NANO_BIAS_MAX || (ed->n_bias && (!ed->bias_tokens || !ed->bias_values))) return NANO_HIP_EINVAL;
+    uint32_t tok[NANO_BIAS_MAX];
+    for (uint32_t k = 0; k < ed->n_bias; k++) {
+        const float b = ed->bias_values[k];
+        if (ed->bias_tokens[k] >= V || isnan(b) || (isinf(b) && b > 0.0f)) return NANO_HIP_EINVAL;
+        tok[k] = ed->bias_tokens[k];
+    }
+    qsort(tok, ed->n_bias, sizeof tok[0], cmp_u32);
+    for (uint32_t k = 1; k < ed->n_bias; k++) if (tok[k] == tok[k - 1]) return NANO_HIP_EINVAL;
+    return NANO_HIP_OK;
+}
+static void edit_entries(const NanoLogitEdit *ed, NanoHipLogitBias *out) {
+    for (uint32_t k = 0; k < ed->n_bias; k++) { out[k].token = ed->bias_tokens[k]; out[k].bias = ed->bias_values[k]; }
+}
+int nano_set_logit_edit(Nano_Context *ctx, const NanoLogitEdit *edit) {
+    if (!ctx || !ctx->llm) return NANO_HIP_EINVAL;
+    const uint32_t V = ctx->llm->config.vocab_size, W = (V + 31u) / 32u;
+    if (edit && (edit->allow || edit->n_bias)) {
+        if (edit_check(V, edit) != NANO_HIP_OK) return NANO_HIP_EINVAL;
+        uint32_t *allow = edit->allow ? (uint32_t *)malloc((size_t)W * 4) : NULL;
+        NanoHipLogitBias *bias = edit->n_bias ? (NanoHipLogitBias *)malloc((size_t)edit->n_bias * sizeof *bias) : NULL;
+        int slot = -1;
+        for (int i = 0; i < MAX_MODELS && slot < 0; i++) if (g_edit[i].ctx == ctx) slot = i;
+        for (int i = 0; i < MAX_MODELS && slot < 0; i++) if (!g_edit[i].ctx) slot = i;
+        if (slot < 0 || (edit->allow && !allow) || (edit->n_bias && !bias)) { free(allow); free(bias); return NANO_HIP_ENOMEM; }
+        if (allow) memcpy(allow, edit->allow, (size_t)W * 4);
+        edit_entries(edit, bias);
+        free(g_edit[slot].allow); free(g_edit[slot].bias);
+        g_edit[slot].ctx = ctx; g_edit[slot].allow = allow; g_edit[slot].bias = bias;
+        g_edit[slot].e.allow = allow; g_edit[slot].e.bias = bias; g_edit[slot].e.n_bias = edit->n_bias;
+    } else ctx_edit_clear(ctx);
+    ModelEntry *me = reg_entry(ctx->llm);
+    if (me) la_clear(me);                                 /* ids a lookup chunk confirmed ahead were picked without the edit */
+    return NANO_HIP_OK;
+}
+
 void llm_context_free(Nano_Context *ctx) {
+    ctx_edit_clear(ctx);
     free_llm(ctx->llm, ctx->tokenizer);
     free(ctx->tokenizer);
     free_sampler(ctx->sampler);
@@ -654,10 +714,11 @@ static int by_prob_desc(const void *a, const void *b) {
     return 0;
 }
 
-static int nucleus(Nano_Context *ctx, const float *p, int n, float top_p, uint32_t top_k, ProbIndex *pi, float coin) {
+/* `allow` (an edited row's mask, or NULL): a disallowed token is never a candidate (nano_mi355x.h "logit edits") */
+static int nucleus(Nano_Context *ctx, const float *p, int n, float top_p, uint32_t top_k, ProbIndex *pi, float coin, const uint32_t *allow) {
     int n0 = 0;
     const float cutoff = (1.0f - top_p) / (n - 1);
-    for (int i = 0; i < n; i++) if (p[i] >= cutoff) { pi[n0].index = i; pi[n0].prob = p[i]; n0++; }
+    for (int i = 0; i < n; i++) if ((!allow || ((allow[i >> 5] >> (i & 31)) & 1u)) && p[i] >= cutoff) { pi[n0].index = i; pi[n0].prob = p[i]; n0++; }
     qsort(pi, (size_t)n0, sizeof(ProbIndex), by_prob_desc);
     if (top_k > 0 && (uint32_t)n0 > top_k) n0 = (int)top_k;             /* NANO_SAMPLE_TOP_K=1 only (nano_mi355x.h): the caller passes 0 otherwise */
     float cum = 0.0f;
@@ -695,9 +756,14 @@ static uint32_t sampler_top_k(const Sampler *sp) {
     return g_sample_top_k ? sp->top_k : 0u;
 }
 
-/* the sampler loops of generate_next_token on a host copy of the logits (reference infer.c:1156-1189) */
-static uint32_t host_sample(Nano_Context *ctx, Sampler *sp, float *logits, const uint32_t *output_ids, uint32_t pos, float coin) {
+/* the sampler loops of generate_next_token on a host copy of the logits (reference infer.c:1156-1189); `ed` (or NULL): the row's logit
+ * edit, applied first -- l' = allowed ? l + bias : -inf */
+static uint32_t host_sample(Nano_Context *ctx, Sampler *sp, float *logits, const uint32_t *output_ids, uint32_t pos, float coin, const HostEdit *ed) {
     const int V = sp->vocab_size;
+    if (ed) {
+        for (uint32_t k = 0; k < ed->n_bias; k++) logits[ed->bias[k].token] += ed->bias[k].bias;
+        if (ed->allow) for (int i = 0; i < V; i++) if (!((ed->allow[i >> 5] >> (i & 31)) & 1u)) logits[i] = -INFINITY;
+    }
     uint32_t *seen = (uint32_t *)calloc((size_t)V, sizeof(uint32_t));
     if (seen) {
         for (uint32_t i = 0; i < pos; i++) seen[output_ids[i]] = 1;
@@ -707,7 +773,7 @@ static uint32_t host_sample(Nano_Context *ctx, Sampler *sp, float *logits, const
     if (sp->temperature == 0.0f) return (uint32_t)argmax_first(logits, V);
     for (int i = 0; i < V; i++) logits[i] /= sp->temperature;
     softmax_inplace(logits, V);
-    return (uint32_t)nucleus(ctx, logits, V, sp->top_p, sampler_top_k(sp), sp->probindex, coin);   /* top-p always (infer.c:1183) */
+    return (uint32_t)nucleus(ctx, logits, V, sp->top_p, sampler_top_k(sp), sp->probindex, coin, ed ? ed->allow : NULL);   /* top-p always (infer.c:1183) */
 }
 
 /* reference infer/infer.c:1135-1193 */
@@ -719,7 +785,8 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
     if (!dev) { fprintf(stderr, "generate_next_token: model is not resident on a device\n"); exit(EXIT_FAILURE); }
     uint32_t token = output_ids[pos];
     const uint32_t draft = lookup_draft();
-    const int greedy = !phase_mode(ctx) && is_prefilling != 1 && sp->temperature == 0.0f && sp->repetition_penalty == 1.0f;
+    const HostEdit *ed = ctx_edit(ctx);                  /* the context's logit edit (decode positions only), or NULL */
+    const int greedy = !phase_mode(ctx) && is_prefilling != 1 && sp->temperature == 0.0f && sp->repetition_penalty == 1.0f && !ed;
     if (draft && greedy && me->la_n && pos == me->la_pos && token == me->la_prev && ctx->lora == me->la_lora) {
         /* verified ahead by the chunk of an earlier call: its K / V rows are in the cache, no device work */
         const uint32_t best = me->la_ids[me->la_at++];
@@ -737,7 +804,7 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         if (is_prefilling == 1) return output_ids[pos + 1];
         observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
         /* the coin is drawn exactly when the reference draws it: only on the softmax branch (infer.c:1181) */
-        return host_sample(ctx, sp, lg, output_ids, pos, sp->temperature != 0.0f ? xorshift_f32(&sp->rng_state) : 0.0f);
+        return host_sample(ctx, sp, lg, output_ids, pos, sp->temperature != 0.0f ? xorshift_f32(&sp->rng_state) : 0.0f, ed);
     }
     if (g_host_sampler < 0) { const char *e = getenv("NANO_HOST_SAMPLER"); g_host_sampler = (e && *e && *e != '0') ? 1 : 0; }
 
@@ -750,7 +817,7 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         return output_ids[pos + 1];
     }
 
-    if (sp->temperature == 0.0f && sp->repetition_penalty == 1.0f) {
+    if (greedy) {                                          /* (with an edit: a temperature-0 row of the sampler, below) */
         uint32_t best = 0;                                 /* x/1.0f is exact: arg-max on the device */
         observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
         const uint32_t lim = me->max_seq_len < llm->config.block_size ? me->max_seq_len : llm->config.block_size;
@@ -781,7 +848,10 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         NanoHipSample r;
         observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
         const NanoHipSampleParamsEx px = { { sp->repetition_penalty, sp->temperature, sp->top_p, coin, output_ids, pos }, sampler_top_k(sp), { 0, 0, 0 } };
-        if (nano_hip_forward_sample_batch_ex(dev, &token, &pos, 1, &px, &r) != NANO_HIP_OK)
+        if (ed) {
+            const NanoHipSampleParamsEdit pe = { px, ed->allow, ed->bias, 0, ed->n_bias };
+            if (nano_hip_forward_sample_batch_edit(dev, &token, &pos, 1, &pe, &r) != NANO_HIP_OK) die_hip("generate_next_token");
+        } else if (nano_hip_forward_sample_batch_ex(dev, &token, &pos, 1, &px, &r) != NANO_HIP_OK)
             die_hip("generate_next_token");
         observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
         if (r.status == NANO_SAMPLE_OK) {
@@ -804,7 +874,7 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         logits = llm_forward(ctx, token, pos, ctx->max_seq_len, 1, llm, ctx->lora);
         observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
     }
-    return host_sample(ctx, sp, logits, output_ids, pos, coin);
+    return host_sample(ctx, sp, logits, output_ids, pos, coin, ed);
 }
 
 /* One decode step of `batch` sequences sampled with each sequence's own Sampler (include/nano_infer_abi.h).  The rows are sampled on
@@ -813,6 +883,12 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
  * nano_forward_batch) is served by its own batched call, one replica after another. */
 int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
                               Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history, uint32_t *out_ids) {
+    return nano_forward_batch_sample_edit(ctx, tokens, pos, batch, samplers, histories, n_history, NULL, out_ids);
+}
+/* ... with edits[i] for sequence i (include/nano_infer_abi.h): the device rows carry them, the host loops apply the same edit */
+int nano_forward_batch_sample_edit(Nano_Context *ctx, const uint32_t *tokens, const uint32_t *pos, uint32_t batch,
+                                   Sampler *const *samplers, const uint32_t *const *histories, const uint32_t *n_history,
+                                   const NanoLogitEdit *edits, uint32_t *out_ids) {
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
     la_clear(me);
     if (!me || !me->dev || !tokens || !pos || !samplers || !out_ids || batch == 0) return NANO_HIP_EINVAL;
@@ -824,8 +900,23 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
     /* the coin of each sequence, drawn exactly when generate_next_token draws it (only on the softmax branch, infer.c:1181) */
     float coin[NANO_MAX_BATCH * NANO_MAX_REPLICAS];
     for (uint32_t i = 0; i < batch; i++) coin[i] = samplers[i]->temperature != 0.0f ? xorshift_f32(&samplers[i]->rng_state) : 0.0f;
+    /* the edits in the device sampler's form, one HostEdit per sequence (NULL where it has none) */
+    HostEdit *he = NULL; NanoHipLogitBias *hb = NULL;
+    if (edits) {
+        size_t nb = 0;
+        for (uint32_t i = 0; i < batch; i++) { if (edit_check((uint32_t)V, &edits[i]) != NANO_HIP_OK) return NANO_HIP_EINVAL; nb += edits[i].n_bias; }
+        he = (HostEdit *)calloc(batch, sizeof *he); hb = (NanoHipLogitBias *)malloc((nb ? nb : 1) * sizeof *hb);
+        if (!he || !hb) { free(he); free(hb); return NANO_HIP_ENOMEM; }
+        nb = 0;
+        for (uint32_t i = 0; i < batch; i++) {
+            edit_entries(&edits[i], hb + nb);
+            he[i].allow = edits[i].allow; he[i].bias = edits[i].n_bias ? hb + nb : NULL; he[i].n_bias = edits[i].n_bias;
+            nb += edits[i].n_bias;
+        }
+    }
+#define ROW_EDIT(i) (he && (he[i].allow || he[i].n_bias) ? &he[i] : NULL)
     float *lbuf = (float *)malloc((size_t)NANO_MAX_BATCH * V * sizeof(float));
-    if (!lbuf) return NANO_HIP_ENOMEM;
+    if (!lbuf) { free(he); free(hb); return NANO_HIP_ENOMEM; }
     int rc = NANO_HIP_OK;
     for (uint32_t r = 0; r < G && rc == NANO_HIP_OK; r++) {
         NanoHipModel *dev = G > 1 ? me->replica[r] : me->dev;
@@ -840,7 +931,7 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
             if ((rc = nano_hip_forward(dev, tk, ps, n, 1, lbuf, NULL)) != NANO_HIP_OK) break;
             for (uint32_t k = 0; k < n; k++) {
                 const uint32_t i = idx[k];
-                out_ids[i] = host_sample(NULL, samplers[i], lbuf + (size_t)k * V, histories ? histories[i] : NULL, n_history ? n_history[i] : 0, coin[i]);
+                out_ids[i] = host_sample(NULL, samplers[i], lbuf + (size_t)k * V, histories ? histories[i] : NULL, n_history ? n_history[i] : 0, coin[i], ROW_EDIT(i));
             }
             continue;
         }
@@ -854,16 +945,26 @@ int nano_forward_batch_sample(Nano_Context *ctx, const uint32_t *tokens, const u
             prm[k].p.history = histories ? histories[i] : NULL; prm[k].p.n_history = n_history ? n_history[i] : 0;
             prm[k].top_k = sampler_top_k(sp);
         }
-        if ((rc = nano_hip_forward_sample_batch_ex(dev, tk, ps, n, prm, res)) != NANO_HIP_OK) break;
+        if (he) {
+            NanoHipSampleParamsEdit pe[NANO_MAX_BATCH];
+            for (uint32_t k = 0; k < n; k++) {
+                const HostEdit *e = ROW_EDIT(idx[k]);
+                const NanoHipSampleParamsEdit one = { prm[k], e ? e->allow : NULL, e ? e->bias : NULL, 0, e ? e->n_bias : 0 };
+                pe[k] = one;
+            }
+            rc = nano_hip_forward_sample_batch_edit(dev, tk, ps, n, pe, res);
+        } else rc = nano_hip_forward_sample_batch_ex(dev, tk, ps, n, prm, res);
+        if (rc != NANO_HIP_OK) break;
         for (uint32_t k = 0; k < n && rc == NANO_HIP_OK; k++) {
             const uint32_t i = idx[k];
             if (res[k].status == NANO_SAMPLE_OK) { out_ids[i] = res[k].token; continue; }
             /* the device declined this row (no candidate, or no memory for the wide phase): host loops on the slot's logits */
             if ((rc = nano_hip_read_state(dev, k, 4, 0, 0, lbuf, (size_t)V)) != NANO_HIP_OK) break;
-            out_ids[i] = host_sample(NULL, samplers[i], lbuf, prm[k].p.history, prm[k].p.n_history, coin[i]);
+            out_ids[i] = host_sample(NULL, samplers[i], lbuf, prm[k].p.history, prm[k].p.n_history, coin[i], ROW_EDIT(i));
         }
     }
-    free(lbuf);
+#undef ROW_EDIT
+    free(lbuf); free(he); free(hb);
     return rc;
 }
 

@@ -487,6 +487,9 @@ struct SampleArgs {
     const uint8_t *seen;                          // null when the penalty is 1
     float penalty, temperature, top_p, cutoff, coin;
     uint32_t top_k;                               // 0 = off; else the sorted list is cut to its first top_k entries (nano_mi355x.h)
+    // the row's logit edit (nano_mi355x.h "logit edits"), device memory: allow = ceil(V / 32) mask words, null = every token allowed;
+    // bias = n_bias entries of distinct tokens, any order.  Both enter the prep kernel's y only; the logits stay as they are.
+    const uint32_t *allow; const NanoHipLogitBias *bias; uint32_t n_bias;
     float *pmax;                                  // [nch/4] workgroup maxima of the prep kernel
     uint32_t *ncand, *ndrop, *dropmax, *bstar;    // accumulators, left at 0 by the last kernel (bstar: set by propagate)
     uint32_t *bin_cnt; unsigned long long *bin_mass;      // [SAMPLE_BINS], likewise
@@ -500,7 +503,10 @@ struct SampleArgs {
 // The sampler's rows (a one-row call is a batch of one): `a` is row 0's view -- its scratch pointers (y, e, seen, pmax, cells, bins,
 // approx, spec, fn, cand) are row 0's, and row r's lie `rstride` bytes further per row; row r's logits are `lstride` floats further,
 // its result is res[r], its parameters rp[r].  The wide-phase pointers of `a` are not used.
-struct SampleRowParams { float penalty, temperature, top_p, cutoff, coin; uint32_t top_k; };
+struct SampleRowParams {
+    float penalty, temperature, top_p, cutoff, coin; uint32_t top_k;
+    const uint32_t *allow; const NanoHipLogitBias *bias; uint32_t n_bias, _pad;      // the row's edit (device pointers; null / 0 = none)
+};
 struct SampleRows {
     SampleArgs a;
     const SampleRowParams *rp;
@@ -521,9 +527,17 @@ __host__ __device__ inline SampleArgs sample_row(const SampleRows &b, uint32_t r
     a.seen = p.penalty != 1.0f ? mv(b.a.seen) : nullptr;
     a.res = b.a.res + r;
     a.penalty = p.penalty; a.temperature = p.temperature; a.top_p = p.top_p; a.cutoff = p.cutoff; a.coin = p.coin; a.top_k = p.top_k;
+    a.allow = p.allow; a.bias = p.bias; a.n_bias = p.n_bias;
     return a;
 }
-hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st);
+// The mask bits of tokens i0 .. i0 + 3 (i0 a multiple of 4: one nibble of one word), 0xF for a row without a mask.  Nothing is read for
+// i0 >= V, so the last word read is word ceil(V / 32) - 1; bits of tokens >= V inside the nibble are the caller's to ignore (i < V).
+// The prep kernel, the candidate filter and the wide phase's candidate test all ask this one function: the branch is row-uniform.
+__device__ __forceinline__ uint32_t sample_allow_nibble(const SampleArgs &a, uint32_t i0) {
+    if (!a.allow) return 0xFu;
+    return i0 < a.V ? (a.allow[i0 >> 5] >> (i0 & 31u)) & 0xFu : 0u;
+}
+hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, bool edited, hipStream_t st);      // edited: some row has an edit
 hipError_t launch_seen_set(const uint32_t *ids, uint32_t n, uint8_t *seen, hipStream_t st);
 size_t sample_wide_temp_bytes(uint32_t n);                            // scratch of the device sort of n keys
 hipError_t launch_sample_wide(const SampleArgs &a, void *temp, size_t temp_bytes, hipStream_t st);

@@ -48,16 +48,44 @@ __global__ __launch_bounds__(256) void seen_set_kernel(const uint32_t *ids, uint
 }
 
 // K1: y = (seen ? l / penalty : l) / temperature over the padded range (padding = -inf -> numerator 0), one max per workgroup
-__device__ __forceinline__ void samp_prep(const SampleArgs &a) {
+// A row's logit edit (nano_mi355x.h "logit edits") is applied here, in front of the two divides: l' = allowed ? l + bias : -inf.  Both hooks
+// are branches on the row's pointers, so workgroup-uniform; a row without an edit takes neither.  The logits themselves are not written.
+// EDIT is a compile-time flag: a call in which no row carries an edit launches the EDIT = false kernels, which hold no hook at all (the
+// first measurement put one of four 64-row medians 0.02 ms outside the parent build's range: profiles/logit_edit.txt).
+//   mask  a thread's four tokens are one nibble of one mask word (sample_allow_nibble);
+//   bias  the workgroup owns tokens base .. base + 1023: every thread strides over the row's entries, an entry whose token falls in the
+//         window leaves its value and a presence bit at token - base in LDS, and behind the barrier each thread adds where its bit is set
+//         (tokens are distinct: no two entries meet in one cell; a token without an entry keeps its bits, -0.0 included).
+template <bool EDIT> __device__ __forceinline__ void samp_prep(const SampleArgs &a) {
     const uint32_t i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     float v[4];
     float mx = -INFINITY;
+    __shared__ float s_bias[EDIT ? 1024 : 1];
+    __shared__ uint32_t s_has[EDIT ? 32 : 1];
+    uint32_t has = 0;
+    if (EDIT && a.n_bias) {
+        const uint32_t base = blockIdx.x * 1024;
+        if (threadIdx.x < 32) s_has[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < a.n_bias; j += 256) {
+            const NanoHipLogitBias en = a.bias[j];
+            const uint32_t t = en.token - base;
+            if (t < 1024u) { s_bias[t] = en.bias; atomicOr(&s_has[t >> 5], 1u << (t & 31u)); }
+        }
+        __syncthreads();
+        has = (s_has[threadIdx.x >> 3] >> ((threadIdx.x & 7u) * 4u)) & 0xFu;
+    }
+    const uint32_t nib = EDIT ? sample_allow_nibble(a, i0) : 0xFu;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const uint32_t i = i0 + k;
         float l = -INFINITY;
         if (i < a.V) {
             l = a.logits[i];
+            if constexpr (EDIT) {
+                if ((has >> k) & 1u) l += s_bias[threadIdx.x * 4 + k];
+                if (!((nib >> k) & 1u)) l = -INFINITY;
+            }
             if (a.seen && a.seen[i]) l /= a.penalty;
             if (a.temperature != 0.0f) l /= a.temperature;
         }
@@ -91,7 +119,8 @@ __device__ __forceinline__ void samp_exp(const SampleArgs &a) {
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (lane == 0) a.approx[c] = s;
     // per-bin count and mass of the numerators; the mass in 2^-40 fixed point so that the totals do not depend on the
-    // order of the atomics (truncation < 2^-40 per token: 1.4e-7 over the whole vocabulary)
+    // order of the atomics (truncation < 2^-40 per token: 1.4e-7 over the whole vocabulary).  Numerators of 0 are skipped, and a
+    // disallowed token of an edited row has y = -inf, numerator 0: bins, bstar and the superset logic see allowed tokens only.
     __shared__ uint32_t hcnt[SAMPLE_BINS];
     __shared__ unsigned long long hmass[SAMPLE_BINS];
     hcnt[threadIdx.x] = 0; hmass[threadIdx.x] = 0;
@@ -239,17 +268,18 @@ __device__ __forceinline__ void samp_propagate(const SampleArgs &a) {
 // reference's order (probability descending, then index ascending — glibc's qsort is a stable merge sort).
 // Candidates in bins after `bstar` (chosen by the propagate kernel) are only counted, and their largest probability
 // recorded for the check in the pick kernel.
-__device__ __forceinline__ void samp_filter(const SampleArgs &a) {
+template <bool EDIT> __device__ __forceinline__ void samp_filter(const SampleArgs &a) {
     const uint32_t i0 = (blockIdx.x * 256 + threadIdx.x) * 4, lane = threadIdx.x & 63;
     const float sum = a.sum[0];
     const uint32_t bstar = *a.bstar;
     const float4 e = reinterpret_cast<const float4 *>(a.e)[i0 / 4];
     const float ev[4] = {e.x, e.y, e.z, e.w};
+    const uint32_t nib = EDIT ? sample_allow_nibble(a, i0) : 0xFu;   // a disallowed token is never a candidate (top_p >= 1: cutoff <= 0 <= its p = 0)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const uint32_t i = i0 + k;
         const float p = ev[k] / sum;
-        const bool cand = i < a.V && p >= a.cutoff;
+        const bool cand = i < a.V && (!EDIT || ((nib >> k) & 1u)) && p >= a.cutoff;
         const bool keep = cand && exp_bin(ev[k]) <= bstar;
         const bool drop = cand && !keep;
         const unsigned long long mask = __ballot(keep), dmask = __ballot(drop);
@@ -366,7 +396,7 @@ __device__ __forceinline__ void samp_pick(const SampleArgs &a, unsigned long lon
 // The six kernels over rows 0 .. rows-1 (a one-row call is a batch of one): each body runs on row `r`'s view (kernels.h sample_row).
 // The chunk-parallel kernels take the row from blockIdx.y, the one-workgroup kernels from blockIdx.x; a workgroup never spans two rows,
 // so every early exit (temperature 0: no softmax for that row) stays workgroup-uniform.
-__global__ __launch_bounds__(256) void samp_prep_rows_kernel(const SampleRows b) { samp_prep(sample_row(b, blockIdx.y, b.rp[blockIdx.y])); }
+template <bool EDIT> __global__ __launch_bounds__(256) void samp_prep_rows_kernel(const SampleRows b) { samp_prep<EDIT>(sample_row(b, blockIdx.y, b.rp[blockIdx.y])); }
 __global__ __launch_bounds__(256) void samp_exp_rows_kernel(const SampleRows b) {
     const SampleRowParams p = b.rp[blockIdx.y];
     if (p.temperature != 0.0f) samp_exp(sample_row(b, blockIdx.y, p));
@@ -379,9 +409,9 @@ __global__ __launch_bounds__(64) void samp_propagate_rows_kernel(const SampleRow
     const SampleRowParams p = b.rp[blockIdx.x];
     if (p.temperature != 0.0f) samp_propagate(sample_row(b, blockIdx.x, p));
 }
-__global__ __launch_bounds__(256) void samp_filter_rows_kernel(const SampleRows b) {
+template <bool EDIT> __global__ __launch_bounds__(256) void samp_filter_rows_kernel(const SampleRows b) {
     const SampleRowParams p = b.rp[blockIdx.y];
-    if (p.temperature != 0.0f) samp_filter(sample_row(b, blockIdx.y, p));
+    if (p.temperature != 0.0f) samp_filter<EDIT>(sample_row(b, blockIdx.y, p));
 }
 __global__ __launch_bounds__(1024) void samp_pick_rows_kernel(const SampleRows b) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long pick_lds[];
@@ -553,16 +583,19 @@ hipError_t launch_seen_set(const uint32_t *ids, uint32_t n, uint8_t *seen, hipSt
 // Rows 0 .. rows-1 of `b`.  prep runs for every row (a temperature-0 row's arg-max reads its `y`); the softmax kernels only when some row
 // samples (`softmax`), and skip the temperature-0 rows themselves.  Pick holds 64 KB + 64 B of LDS: two of its workgroups per CU
 // (160 KB), so 64 rows are one wave of workgroups on the 256 CUs; the chunk-parallel kernels are rows x (nch / 4) workgroups of 256.
-hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, hipStream_t st) {
+// `edited`: some row of the call carries a mask or a bias list -- the prep and filter kernels with the hooks; otherwise the ones without.
+hipError_t launch_sample_rows(const SampleRows &b, uint32_t rows, bool softmax, bool edited, hipStream_t st) {
     const SampleArgs &a = b.a;
     if (rows == 0) return hipSuccess;
     const uint32_t wgs = a.nch * CH / 1024;
-    hipLaunchKernelGGL(samp_prep_rows_kernel, dim3(wgs, rows), dim3(256), 0, st, b);
+    if (edited) hipLaunchKernelGGL(samp_prep_rows_kernel<true>, dim3(wgs, rows), dim3(256), 0, st, b);
+    else hipLaunchKernelGGL(samp_prep_rows_kernel<false>, dim3(wgs, rows), dim3(256), 0, st, b);
     if (!softmax) return hipGetLastError();
     hipLaunchKernelGGL(samp_exp_rows_kernel, dim3(a.nch / 4, rows), dim3(256), 0, st, b);
     hipLaunchKernelGGL(samp_chunkfn_rows_kernel, dim3(a.nch / 4, rows), dim3(256), 0, st, b);
     hipLaunchKernelGGL(samp_propagate_rows_kernel, dim3(rows), dim3(64), 0, st, b);
-    hipLaunchKernelGGL(samp_filter_rows_kernel, dim3(wgs, rows), dim3(256), 0, st, b);
+    if (edited) hipLaunchKernelGGL(samp_filter_rows_kernel<true>, dim3(wgs, rows), dim3(256), 0, st, b);
+    else hipLaunchKernelGGL(samp_filter_rows_kernel<false>, dim3(wgs, rows), dim3(256), 0, st, b);
     constexpr size_t pick_lds_bytes = (size_t)SAMPLE_MAX_CANDIDATES * 8 + 64;
     static std::atomic<unsigned long long> armed{0};                  // bit per device: the attribute call is a host round trip
     int dev = 0; (void)hipGetDevice(&dev);

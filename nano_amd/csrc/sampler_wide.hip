@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t wdigit(unsigned long long w, uint32_t sh) { 
 // pass's INPUT arrangement: pass 0's by the filter kernel, pass p + 1's by pass p's scatter (one global atomic per entry it moves).
 struct WideSort { uint32_t *tot, *hist; uint32_t ntile; };
 
-__global__ __launch_bounds__(256) void samp_wide_filter_kernel(const SampleArgs a, const WideSort ws) {
+template <bool EDIT> __global__ __launch_bounds__(256) void samp_wide_filter_kernel(const SampleArgs a, const WideSort ws) {      // EDIT: the row has a mask
     __shared__ uint32_t h[4][256];
     const uint32_t tid = threadIdx.x, i0 = (blockIdx.x * 256 + tid) * 4, lane = tid & 63;
     for (int p = 0; p < 4; p++) h[p][tid] = 0;
@@ -54,11 +54,12 @@ __global__ __launch_bounds__(256) void samp_wide_filter_kernel(const SampleArgs 
     const float ev[4] = {e.x, e.y, e.z, e.w};
     unsigned long long w[4];
     uint32_t n = 0;
+    const uint32_t nib = EDIT ? sample_allow_nibble(a, i0) : 0xFu;    // an edited row's disallowed tokens are never candidates (as in samp_filter)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const uint32_t i = i0 + k;
         const float p = ev[k] / sum;                                   // the reference's division (infer.c:631)
-        const bool cand = i < a.V && p >= a.cutoff;
+        const bool cand = i < a.V && (!EDIT || ((nib >> k) & 1u)) && p >= a.cutoff;
         w[k] = cand ? ((unsigned long long)__float_as_uint(p) << 32) | (unsigned long long)(0xffffffffu - i) : 0ull;
         n += (uint32_t)__popcll(__ballot(cand));
 #pragma unroll
@@ -157,7 +158,8 @@ hipError_t launch_sample_wide(const SampleArgs &a, void *temp, size_t temp_bytes
     ws.tot = reinterpret_cast<uint32_t *>(temp); ws.hist = ws.tot + 4 * 256; ws.ntile = a.wide_cap / WT;
     hipError_t e = hipMemsetAsync(ws.tot, 0, 4 * 256 * 4, st);        // (the totals are accumulated with atomics)
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(samp_wide_filter_kernel, dim3(ws.ntile), dim3(256), 0, st, a, ws);
+    if (a.allow) hipLaunchKernelGGL(samp_wide_filter_kernel<true>, dim3(ws.ntile), dim3(256), 0, st, a, ws);
+    else hipLaunchKernelGGL(samp_wide_filter_kernel<false>, dim3(ws.ntile), dim3(256), 0, st, a, ws);
     unsigned long long *src = a.wide_in, *dst = a.wide_out;
     for (uint32_t pass = 0; pass < 4; pass++) {                        // the buffers swap roles: an even number of passes ends in wide_in
         hipLaunchKernelGGL(samp_wide_scatter_kernel, dim3(ws.ntile), dim3(256), 0, st, src, dst, ws, pass);
