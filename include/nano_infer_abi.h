@@ -251,6 +251,17 @@ int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t 
  * replica's share is one call, one replica after another.  The ragged step has no LoRA branches: with a module selected the call
  * returns NANO_HIP_EINVAL.  Returns 0 or a NANO_HIP_E* code; a refused call feeds nothing on the device that refused. */
 int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const uint32_t *n_tokens, uint32_t batch, uint32_t *first_ids);
+/* Text embeddings of `batch` texts in one ragged step (nano_hip_step_rows_pool, nano_mi355x.h: the float chains, the order of every sum
+ * and what strict / exact mode return are stated there): sequence i takes texts[i][0..n_tokens[i]) from position 0, as in
+ * nano_prefill_batch, and out[i * d .. (i + 1) * d) with d = dim ? dim : n_embd is its vector: the final-norm hidden state of its last
+ * token (pooling = NANO_POOL_LAST, what an embedding checkpoint of the Qwen3 family is trained for) or the mean over its tokens
+ * (NANO_POOL_MEAN), cut to its leading dim components, then -- normalize = 1 -- scaled to unit length.  An empty text gets zeros.  No
+ * classifier runs and no logit exists.  The sequences are left ingested: a caller may go on decoding from them with nano_forward_batch.
+ * Runs on the context's own device: with replicas attached the call returns NANO_HIP_EINVAL, as it does with a LoRA module selected
+ * (the ragged step has no LoRA branches), for batch == 0 or beyond the device's slots, and for whatever the backend call refuses.
+ * Not offered: bidirectional attention (is_causal = 0), CLS pooling, texts longer than max_seq_len.  Returns 0 or a NANO_HIP_E* code. */
+int nano_embed_batch(Nano_Context *ctx, const uint32_t *const *texts, const uint32_t *n_tokens, uint32_t batch, uint32_t pooling,
+                     uint32_t normalize, uint32_t dim, float *out);
 /* Feed ids[0..n_ids-1) into sequence 0 from position 0 and score ids[1..n_ids): logprobs / argmax hold n_ids-1 entries (either may be NULL),
  * *nll_sum = -(sum of the logprobs), added in double in index order.  Applies the context's LoRA selection as nano_forward_batch does.
  * logprobs[i] = log p(ids[i + 1] | ids[0..i]) and argmax[i] = the model's own choice there, both taken on the device from a batched

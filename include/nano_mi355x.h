@@ -344,6 +344,47 @@ int nano_hip_rows_plan(const NanoHipRowSeg *segs, uint32_t n_segs, uint32_t cap,
  * 32 bits, a layer of one slot within a 32-bit byte offset), else 0.  The paged pool is checked when the model is created. */
 int nano_hip_rows_addressable(uint32_t n_layer, uint32_t max_seq_len, uint32_t kv_dim, uint32_t elem_bytes);
 
+/* ---- text embeddings: pooled final-norm hidden states from a ragged step ---------------------
+ * nano_hip_step_rows_pool feeds the rows of its segments exactly as nano_hip_step_rows does -- same passes, the same K / V rows left
+ * behind bit for bit, so a caller may go on decoding from the slots -- stops every pass in front of the classifier and returns ONE
+ * vector of dim floats per segment (out[n_segs][dim ? dim : n_embd], caller order).  The quantity, as float chains:
+ *   per-row vector  y_r[i] = w_final[i] * (x_r[i] * (1 / sqrtf(mean(x_r^2) + 1e-5f))), x_r the row's residual after the last layer: what
+ *                   the reference holds in s->x after llm_forward (its final rmsnorm).  Fast path: the sum of x^2 in ONE fixed order of the
+ *                   pool kernel's own (pool.hip states it), which does not depend on the pass the row landed in, its row inside the
+ *                   pass, or the other rows of the call.  Strict and exact mode: that mode's ordered rmsnorm, the reference's bits.
+ *   pooling         NANO_POOL_LAST: v = y of the segment's last fed row.  NANO_POOL_MEAN: v = (((y_0 + y_1) + y_2) + ...) / (float)count,
+ *                   plain FP32 adds in ascending position and one division; count == 1 gives y_0 / 1.0f, LAST's bits.  v does not depend
+ *                   on how the call's rows were cut into passes.
+ *   truncation      components 0 .. dim-1 are kept (dim == 0: n_embd), BEFORE normalisation.
+ *   normalisation   normalize = 1: out = v * (1 / sqrtf(sum_{i<dim} v[i]^2)); fast path: a fixed order of the kernel's own; strict / exact
+ *                   mode: ascending FP32.  A sum of 0 returns zeros, never NaN.  normalize = 0: out = v.
+ * A segment of count 0 gets a row of zeros and touches nothing.  How: one launch behind each pass (strict / exact mode: behind each
+ * pooled row's reference-order step, which LAST needs for one row per segment only), one workgroup per segment present in the pass; a
+ * call whose texts fit one pass costs one extra launch, the vectors come back in one copy behind the call's one wait.
+ * NANO_HIP_EINVAL before anything is queued: whatever nano_hip_step_rows refuses (LoRA included), a null p or out, pooling > 1,
+ * normalize > 1, dim > n_embd, reserved != 0.  n_segs == 0 returns 0 and touches nothing.
+ * Not offered: is_causal = 0 (bidirectional encoders), CLS pooling, a text longer than one call's positions (max_seq_len / the RoPE
+ * table), LoRA. */
+#define NANO_POOL_LAST 0u
+#define NANO_POOL_MEAN 1u
+typedef struct NanoHipPoolParams { uint32_t pooling, normalize, dim, reserved; } NanoHipPoolParams;   /* 16 bytes; reserved must be 0 */
+int nano_hip_step_rows_pool(NanoHipModel *m, const NanoHipRowSeg *segs, uint32_t n_segs, const uint32_t *tokens,
+                            const NanoHipPoolParams *p, float *out /* [n_segs][dim ? dim : n_embd] */);
+/* Device-free: the row map nano_hip_step_rows_pool builds for its kernel, from the function it builds it with.  Per FED row, in the order
+ * the call feeds them (pass after pass, a pass's rows by row_index of nano_hip_rows_plan; all outputs optional, sum(count) words):
+ * row_seg = its segment, row_ordinal = its ordinal among the segment's pooled rows, 0xffffffff where the row is not pooled (LAST: every
+ * row but the segment's last, which is ordinal 0; MEAN: row j of a segment is ordinal j).  NANO_HIP_EINVAL as nano_hip_rows_plan, and
+ * for pooling > 1. */
+int nano_hip_rows_pool_plan(const NanoHipRowSeg *segs, uint32_t n_segs, uint32_t cap, uint32_t max_seq_len, uint32_t pooling,
+                            uint32_t *row_seg, uint32_t *row_ordinal);
+/* The pool kernel alone on caller rows (host pointers; the fast form: it norms the rows itself).  x[rows][n_embd] holds the residual
+ * rows segment after segment, seg_count[n_segs] their counts (sum = rows); the rows are cut into passes of at most pass_cap rows
+ * exactly as a model with that chunk size would cut them (positions from 0) and one launch runs per pass.  out[n_segs][dim ? dim :
+ * n_embd].  NANO_HIP_EINVAL before a device is asked for: null x / w_final / seg_count / p / out, n_segs or n_embd of 0, rows not the
+ * sum of the counts, pass_cap of 0 or above 256, and the parameter checks above. */
+int nano_hip_op_pool_rows(int device, const float *x, uint32_t rows, uint32_t n_embd, const float *w_final, const uint32_t *seg_count,
+                          uint32_t n_segs, const NanoHipPoolParams *p, uint32_t pass_cap, float *out);
+
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words
  * 6 / 7.  Attaching enables the module; nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.

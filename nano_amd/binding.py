@@ -149,6 +149,18 @@ class NanoHipLookupParams(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("max_draft", "ngram_max", "ngram_min", "stop_token", "max_steps")]
 
 
+class NanoHipPoolParams(C.Structure):
+    """include/nano_mi355x.h NanoHipPoolParams: text embeddings (pooling POOL_LAST | POOL_MEAN, normalize 0 | 1, dim 0 = n_embd, reserved 0)."""
+    _fields_ = [(n, C.c_uint32) for n in ("pooling", "normalize", "dim", "reserved")]
+
+
+POOL_LAST, POOL_MEAN = 0, 1
+
+
+def _pooling(pooling) -> int:
+    return {"last": POOL_LAST, "mean": POOL_MEAN}[pooling] if isinstance(pooling, str) else int(pooling)
+
+
 class NanoHipLookupStats(C.Structure):
     """include/nano_mi355x.h NanoHipLookupStats (drafted = steps_verify * max_draft)."""
     _fields_ = [(n, C.c_uint32) for n in ("steps_plain", "steps_verify", "drafted", "accepted", "emitted")]
@@ -256,6 +268,11 @@ def lib() -> C.CDLL:
                        ("nano_hip_step_rows_score", [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]),
                        ("nano_score_ids_topk", [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_double)]),
                        ("nano_forward_batch_topk", [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]),
+                       # text embeddings
+                       ("nano_hip_step_rows_pool", [vp, vp, C.c_uint32, vp, C.POINTER(NanoHipPoolParams), vp]),
+                       ("nano_hip_rows_pool_plan", [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+                       ("nano_hip_op_pool_rows", [C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(NanoHipPoolParams), C.c_uint32, vp]),
+                       ("nano_embed_batch", [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
                        # logit edits
                        ("nano_hip_forward_sample_batch_edit", [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
                        ("nano_hip_op_sample_batch_edit", [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
@@ -297,6 +314,17 @@ def rows_plan(segs, cap: int, max_seq_len: int):
     n = C.c_uint32(0)
     check(lib().nano_hip_rows_plan(s.ctypes.data if s.size else None, s.shape[0], cap, max_seq_len, rp.ctypes.data, ri.ctypes.data, rh.ctypes.data, C.byref(n)))
     return rp[:rows], ri[:rows], rh[:rows], int(n.value)
+
+
+def rows_pool_plan(segs, cap: int, max_seq_len: int, pooling="last"):
+    """nano_hip_rows_pool_plan (device-free): the row map step_rows_pool() builds for its kernel.  Returns (row_seg, row_ordinal), per fed
+    row in feeding order (pass after pass, a pass's rows by rows_plan()'s row_index); row_ordinal is 0xffffffff where a row is not pooled."""
+    s = row_segs(segs)
+    rows = int(s[:, 2].astype(np.uint64).sum()) if s.size else 0
+    rows = min(rows, len(segs) * max_seq_len)          # (no plan has more; a refused list may claim any number)
+    rs, ro = (np.zeros(max(rows, 1), np.uint32) for _ in range(2))
+    check(lib().nano_hip_rows_pool_plan(s.ctypes.data if s.size else None, s.shape[0], cap, max_seq_len, _pooling(pooling), rs.ctypes.data, ro.ctypes.data))
+    return rs[:rows], ro[:rows]
 
 
 def last_error() -> str:
@@ -579,6 +607,21 @@ class DeviceModel:
         check(lib().nano_hip_step_rows(self.h, s.ctypes.data if s.size else None, s.shape[0], t.ctypes.data if t.size else None,
                                        out.ctypes.data if want_argmax else None))
         return out[:rows] if want_argmax else None
+
+    def step_rows_pool(self, segs: Sequence[Sequence[int]], tokens: Sequence[int], pooling="last", normalize: bool = True, dim: int = 0) -> np.ndarray:
+        """Text embeddings from a ragged step (nano_hip_step_rows_pool): step_rows() that stops in front of the classifier and returns
+        one vector per segment, float32 [len(segs), dim or n_embd]: the final-norm hidden state of the segment's last row (pooling "last")
+        or the mean over its rows ("mean"), cut to `dim` leading components, then scaled to unit length (normalize)."""
+        s = row_segs(segs)
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        rows = int(s[:, 2].sum()) if s.size else 0
+        if t.size != rows:
+            raise ValueError(f"{rows} rows but {t.size} tokens")
+        p = NanoHipPoolParams(_pooling(pooling), int(normalize), dim, 0)
+        out = np.zeros((max(s.shape[0], 1), dim or int(self.desc.n_embd)), np.float32)
+        check(lib().nano_hip_step_rows_pool(self.h, s.ctypes.data if s.size else None, s.shape[0], t.ctypes.data if t.size else None,
+                                            C.byref(p), out.ctypes.data))
+        return out[:s.shape[0]]
 
     def rows_plan(self, segs: Sequence[Sequence[int]], max_seq_len: int):
         """How step_rows() cuts these segments in the model's current mode: rows_plan(segs, prefill_chunk_tokens(), max_seq_len)."""
@@ -1171,6 +1214,26 @@ def op_topk_rows(logits, k, targets=None, device=0):
     return out, top
 
 
+def op_pool_rows(x, w_final, seg_count, pooling="last", normalize=True, dim=0, pass_cap=64, device=0, guard=0):
+    """The pool kernel alone (nano_hip_op_pool_rows): x [rows, n_embd] float32 residual rows, segment after segment; w_final [n_embd];
+    seg_count the segments' row counts.  Returns float32 [n_segs, dim or n_embd].  guard > 0: (out, tail) where tail is `guard` words of
+    the output buffer behind the result, filled with 0xa5a5a5a5 before the call.  Device only: no host path."""
+    xv = np.ascontiguousarray(x, np.float32)
+    if xv.ndim != 2:
+        raise ValueError("x must be [rows, n_embd]")
+    w = np.ascontiguousarray(w_final, np.float32).reshape(-1)
+    c = np.ascontiguousarray(seg_count, np.uint32).reshape(-1)
+    if w.size != xv.shape[1]:
+        raise ValueError(f"n_embd {xv.shape[1]} but {w.size} weights")
+    d = dim or xv.shape[1]
+    buf = np.full(c.size * d + guard, 0xA5A5A5A5, np.uint32)
+    p = NanoHipPoolParams(_pooling(pooling), int(normalize), dim, 0)
+    xp = xv if xv.size else np.zeros((1, xv.shape[1]), np.float32)
+    check(lib().nano_hip_op_pool_rows(device, xp.ctypes.data, xv.shape[0], xv.shape[1], w.ctypes.data, c.ctypes.data, c.size, C.byref(p), pass_cap, buf.ctypes.data))
+    out = buf[:c.size * d].view(np.float32).reshape(c.size, d)
+    return (out, buf[c.size * d:]) if guard else out
+
+
 def op_lookup_step(history, fed=(), amax=(), *, left, max_draft=7, ngram_max=3, ngram_min=1, stop_token=None, seq_limit=1 << 30, device=0):
     """lookup_step_kernel alone (nano_hip_op_lookup_step): behind a step that fed `fed` and left the row arg-maxes `amax` (both empty: no
     step has run yet).  Returns (record dict of LOOKUP_RECORD_FIELDS, the history with the emitted ids appended, next tokens, next
@@ -1307,6 +1370,16 @@ class Engine:
         first = np.zeros(max(len(ps), 1), np.uint32) if want_first_ids else None
         check(self.L.nano_prefill_batch(self.ctx, ptrs, n, len(ps), first.ctypes.data if want_first_ids else None))
         return first[:len(ps)] if want_first_ids else None
+
+    def embed_batch(self, texts: Sequence[Sequence[int]], n_embd: int, pooling="last", normalize: bool = True, dim: int = 0) -> np.ndarray:
+        """nano_embed_batch: sequence i ingests texts[i] from position 0, all in one pooled ragged step; returns float32
+        [len(texts), dim or n_embd], one vector per text (DeviceModel.step_rows_pool says which)."""
+        ts = [np.ascontiguousarray(t, np.uint32).reshape(-1) for t in texts]
+        ptrs = (C.c_void_p * len(ts))(*[t.ctypes.data if t.size else None for t in ts])
+        n = np.array([t.size for t in ts], np.uint32)
+        out = np.zeros((max(len(ts), 1), dim or n_embd), np.float32)
+        check(self.L.nano_embed_batch(self.ctx, ptrs, n.ctypes.data, len(ts), _pooling(pooling), int(normalize), dim, out.ctypes.data))
+        return out[:len(ts)]
 
     def set_logit_edit(self, allow=None, bias=None) -> None:
         """nano_set_logit_edit: allow = mask words (or None), bias = (tokens, values) (or None); both None clears the context's edit."""

@@ -22,6 +22,7 @@
 #include <hip/hip_fp16.h>
 #include "../../include/nano_mi355x.h"
 #include "kernels.h"
+#include "pool_plan.h"
 #include "step_spec.h"
 
 using namespace nano;
@@ -108,6 +109,8 @@ struct NanoHipModel {
         uint32_t *tgt = nullptr, *out_amax = nullptr;     // its targets; its row arg-maxes
         NanoHipTokenScore *sc = nullptr;                  // its records
         NanoHipTopEntry *top = nullptr;                   // [cap][NANO_TOPK_MAX] its entries (row i's k entries at i * k)
+        uint32_t *pool_map = nullptr;                     // C_POOL: PoolPlan::map of the call (at most 5 words per row)
+        float *pool_acc = nullptr, *pool_out = nullptr;   // C_POOL: [max_batch][n_embd] running sums of segments that straddle passes | the call's vectors [n_segs][dim]
     } rb;
     // greedy decode with lookup drafts (backend_lookup.hip), allocated on the first call that needs it
     struct Lookup {
@@ -190,15 +193,19 @@ void handoff_fallback(NanoHipModel *m);
 void drop_graphs(NanoHipModel *m);
 int check_batch(NanoHipModel *m, const uint32_t *tokens, const uint32_t *pos, uint32_t batch, uint32_t extra_steps);
 // What a call wants of the rows it feeds, built by the extern "C" entry points: nothing, every row's arg-max (verify), or every row's score
-// record for targets (null: for its own arg-max) and -- k >= 1 -- its k best entries.  Every switch derived from that is answered here.
+// record for targets (null: for its own arg-max) and -- k >= 1 -- its k best entries, or -- POOL, ragged steps only -- one pooled
+// final-norm vector per segment (pool.hip; no classifier runs).  Every switch derived from that is answered here.
 struct RowWant {
-    enum Kind : uint32_t { NONE, ARGMAX, SCORE } kind = NONE;
+    enum Kind : uint32_t { NONE, ARGMAX, SCORE, POOL } kind = NONE;
     const uint32_t *targets = nullptr; uint32_t k = 0;                      // SCORE: the caller's targets (host), entries per row
     uint32_t *argmax_out = nullptr; NanoHipTokenScore *scores_out = nullptr; NanoHipTopEntry *top_out = nullptr;    // the caller's arrays, caller order
+    const NanoHipPoolParams *pool = nullptr; float *pool_out = nullptr;     // POOL: the caller's parameters; its vectors [n_segs][pool_dim]
+    uint32_t pool_segs = 0, pool_dim = 0; const PoolPlan *pool_plan = nullptr;   // ... the call's segments, dim resolved (0 -> n_embd), its plan (set by the ragged step)
     static RowWant argmaxes(uint32_t *out) { RowWant w; if (out) { w.kind = ARGMAX; w.argmax_out = out; } return w; }
     static RowWant scores(const uint32_t *targets, uint32_t k, NanoHipTokenScore *scores_out, NanoHipTopEntry *top_out) {
         RowWant w; w.kind = SCORE; w.targets = targets; w.k = k; w.scores_out = scores_out; w.top_out = top_out; return w;
     }
+    static RowWant pooled(const NanoHipPoolParams *p, float *out) { RowWant w; w.kind = POOL; w.pool = p; w.pool_out = out; return w; }
     bool use_targets() const { return kind == SCORE && targets; }
     uint32_t mode_row() const { return kind == ARGMAX ? MODE_ARGMAX : kind == SCORE ? MODE_LOGITS : MODE_NOCLS; }     // step mode of a row fed alone
     uint32_t mode_pass() const { return kind == ARGMAX ? MODE_VERIFY : kind == SCORE ? MODE_SCORE : MODE_NOCLS; }     // ... of a pass of several rows
@@ -208,9 +215,10 @@ struct RowWant {
                                                                             // (false: every row is left in m->logits / m->amax -- reference-order steps, a decode step)
 };
 // rows_scratch's buffers: P_* pass buffers (P_STATS: partials, targets, records), C_* parts of the call block (C_FEED: tokens and positions)
-enum : uint32_t { P_LOGITS = 1, P_STATS = 2, P_AMAX = 4, P_KEYS = 8, C_FEED = 0x10, C_SLOT = 0x20, C_TGT = 0x40, C_SC = 0x80, C_AMAX = 0x100, C_TOP = 0x200, C_ALL = 0x3f0 };
+enum : uint32_t { P_LOGITS = 1, P_STATS = 2, P_AMAX = 4, P_KEYS = 8, C_FEED = 0x10, C_SLOT = 0x20, C_TGT = 0x40, C_SC = 0x80, C_AMAX = 0x100, C_TOP = 0x200, C_POOL = 0x400, C_ALL = 0x7f0 };
 inline uint32_t RowWant::need(bool passes) const {
     if (kind == ARGMAX) return (passes ? P_LOGITS | P_AMAX : 0u) | C_AMAX;
+    if (kind == POOL) return C_POOL;
     if (kind != SCORE) return 0u;
     return (passes ? P_LOGITS : 0u) | P_STATS | C_SC | (targets ? C_TGT : 0u) | (k ? P_KEYS | C_TOP : 0u);
 }
@@ -232,7 +240,8 @@ int rows_feed(NanoHipModel *m, size_t total, const uint32_t *tokens, const uint3
 // or their arg-maxes, into the call's slots at ..
 hipError_t rows_after_step(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 // a MODE_SCORE / MODE_VERIFY pass of nb rows is to run: its targets from the call's; it has run: its records or arg-maxes into the call's
-// slots at .., and the selection on its logits before the next pass overwrites them
+// slots at .., and the selection on its logits before the next pass overwrites them.  POOL (a MODE_NOCLS pass; a reference-order step
+// in rows_after_step): the pool launch on the pass's rows in m->x, before the next pass overwrites them
 hipError_t rows_pass_targets(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 hipError_t rows_after_pass(NanoHipModel *m, const RowWant &w, size_t at, uint32_t nb);
 // strict / exact mode: the call's rows one by one, each a reference-order step on its staged token and position in KV slot row_slot[i] (null: slot)

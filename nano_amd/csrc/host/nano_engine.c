@@ -683,6 +683,28 @@ int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const 
     return rc;
 }
 
+/* Text embeddings of `batch` texts: sequence i in slot i of the context's own device, all texts the segments of ONE pooled ragged step. */
+int nano_embed_batch(Nano_Context *ctx, const uint32_t *const *texts, const uint32_t *n_tokens, uint32_t batch, uint32_t pooling,
+                     uint32_t normalize, uint32_t dim, float *out) {
+    la_clear(ctx ? reg_entry(ctx->llm) : NULL);
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || !texts || !n_tokens || !out || batch == 0 || batch > NANO_MAX_BATCH || me->n_replica > 1) return NANO_HIP_EINVAL;      /* (replica[0] is the own device) */
+    for (uint32_t i = 0; i < batch; i++) if (n_tokens[i] && !texts[i]) return NANO_HIP_EINVAL;
+    NanoHipRowSeg segs[NANO_MAX_BATCH];
+    size_t rows = 0;
+    for (uint32_t i = 0; i < batch; i++) { segs[i] = (NanoHipRowSeg){ i, 0, n_tokens[i], 0 }; rows += n_tokens[i]; }
+    uint32_t *tok = (uint32_t *)malloc((rows ? rows : 1) * sizeof *tok);
+    if (!tok) return NANO_HIP_ENOMEM;
+    size_t o = 0;
+    for (uint32_t i = 0; i < batch; i++) { if (n_tokens[i]) memcpy(tok + o, texts[i], (size_t)n_tokens[i] * sizeof *tok); o += n_tokens[i]; }
+    const NanoHipPoolParams p = { pooling, normalize, dim, 0 };
+    lora_select(me->dev, ctx->lora);
+    me->pf_session = NULL;                                    /* the sequences' rows are these texts' now */
+    const int rc = nano_hip_step_rows_pool(me->dev, segs, batch, tok, &p, out);
+    free(tok);
+    return rc;
+}
+
 /* =====================================================================================================
  * sampling (reference infer/infer.c:1026-1127; RNG infer/utils.c:959-970)
  * =================================================================================================== */

@@ -453,6 +453,21 @@ struct TopkArgs {
 // two launches: the tiles (score.hip's tiles), then one workgroup per row; rows <= 65535
 hipError_t launch_topk_rows(const TopkArgs &a, uint32_t rows, hipStream_t st);
 
+// ---- text embeddings: a pass's final-norm rows pooled per segment (pool.hip) ----
+constexpr uint32_t POOL_THREADS = 256, POOL_MAX_ROWS = 256;  // threads of a workgroup; the most rows a pass may hold (the inverse RMS of each in LDS)
+// a workgroup's 4 words: { segment, first entry of its row list in `lists`, rows in the list | POOL_BEGUN | POOL_ENDS, the segment's row count }
+constexpr uint32_t POOL_GROUP_WORDS = 4, POOL_N_MASK = 0x3fffffffu, POOL_BEGUN = 0x40000000u, POOL_ENDS = 0x80000000u;
+struct PoolArgs {
+    const float *x; uint32_t x_stride, rows_max;           // the pass's rows (residual rows; w == nullptr: rows already normed); rows_max: rows of the pass
+    const float *w;                                        // [n_embd] the final norm's weights, or nullptr: the ordered form (pool.hip)
+    const uint32_t *groups, *lists;                        // [workgroups][POOL_GROUP_WORDS]; pass rows, each list ascending (= ascending position)
+    float *acc;                                            // [n_segs][dim rounded up to 4] running sums of segments that straddle passes
+    float *out;                                            // [n_segs][dim]
+    uint32_t n_embd, dim, mean, normalize;                 // dim: 1 .. n_embd; mean: 0 the (one) listed row itself, 1 sum / count
+};
+// one launch: one workgroup per entry of groups
+hipError_t launch_pool_rows(const PoolArgs &a, uint32_t n_groups, hipStream_t st);
+
 hipError_t launch_rmsnorm(float *out, const float *x, const float *w, uint32_t n, hipStream_t st);
 hipError_t launch_quantize_q80(const float *x, uint32_t n, uint32_t gs, int8_t *q, float *s, hipStream_t st);
 hipError_t launch_quantize_q4k(const float *x, uint32_t n, uint8_t *blocks, hipStream_t st);

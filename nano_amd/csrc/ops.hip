@@ -4,12 +4,14 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <string>
 #include <vector>
 
 #include "../../include/nano_mi355x.h"
 #include "kernels.h"
+#include "pool_plan.h"
 
 using namespace nano;
 
@@ -243,6 +245,45 @@ extern "C" int nano_hip_op_topk_rows(int device, const float *logits, uint32_t r
     OP_HIP(launch_topk_rows(t, rows, 0));
     OP_HIP(hipMemcpy(top_out, t.out, (size_t)rows * k * sizeof(NanoHipTopEntry), hipMemcpyDeviceToHost));
     if (scores_out) OP_HIP(hipMemcpy(scores_out, a.out, (size_t)rows * sizeof(NanoHipTokenScore), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the pool kernel alone (pool.hip), driven as a model drives it: the plan of nano_hip_step_rows_pool (pool_plan(), segments in slots
+// 0 .. n_segs-1 from position 0), the rows uploaded in the order a call feeds them, one launch per pass on that pass's rows.  The
+// arguments are checked before a device is asked for.
+extern "C" int nano_hip_op_pool_rows(int device, const float *x, uint32_t rows, uint32_t n_embd, const float *w_final, const uint32_t *seg_count,
+                                     uint32_t n_segs, const NanoHipPoolParams *p, uint32_t pass_cap, float *out) {
+    if (!x || !w_final || !seg_count || !p || !out || !n_segs || !n_embd) { nano_hip_set_error_("pool_rows: null argument, or no segments / n_embd of 0"); return NANO_HIP_EINVAL; }
+    if (p->pooling > NANO_POOL_MEAN || p->normalize > 1u || p->dim > n_embd || p->reserved) { nano_hip_set_error_("pool_rows: pooling / normalize / dim out of range, or reserved != 0"); return NANO_HIP_EINVAL; }
+    if (!pass_cap || pass_cap > POOL_MAX_ROWS) { nano_hip_set_error_("pool_rows: pass_cap of 0 or above 256"); return NANO_HIP_EINVAL; }
+    uint64_t sum = 0;
+    uint32_t longest = 1;
+    std::vector<NanoHipRowSeg> segs(n_segs);
+    for (uint32_t i = 0; i < n_segs; i++) { segs[i] = NanoHipRowSeg{ i, 0u, seg_count[i], 0u }; sum += seg_count[i]; longest = seg_count[i] > longest ? seg_count[i] : longest; }
+    if (sum != rows) { nano_hip_set_error_("pool_rows: rows is not the sum of the segments' counts"); return NANO_HIP_EINVAL; }
+    PoolPlan pl;
+    int rc; if ((rc = pool_plan(segs.data(), n_segs, pass_cap, longest, p->pooling, &pl))) return rc;
+    if ((rc = begin(device))) return rc;
+    const uint32_t dim = p->dim ? p->dim : n_embd, dpad = (dim + 3u) & ~3u;
+    std::fill(out, out + (size_t)n_segs * dim, 0.0f);
+    if (!rows) return 0;
+    std::vector<float> fed((size_t)rows * n_embd);                          // caller row r is fed as row where[r]
+    for (uint32_t r = 0; r < rows; r++) memcpy(fed.data() + (size_t)pl.where[r] * n_embd, x + (size_t)r * n_embd, (size_t)n_embd * 4);
+    DevBufs B;
+    PoolArgs a{};
+    const float *dx = B.upload(fed.data(), fed.size());
+    const uint32_t *dmap = B.upload(pl.map.data(), pl.map.size());
+    a.w = B.upload(w_final, n_embd); a.acc = B.alloc<float>((size_t)n_segs * dpad); a.out = B.alloc<float>((size_t)n_segs * dim);
+    OP_CHECK(dx && dmap && a.w && a.acc && a.out, "device alloc failed");
+    OP_HIP(hipMemset(a.out, 0, (size_t)n_segs * dim * 4));
+    a.x_stride = n_embd; a.lists = dmap + (size_t)pl.n_groups() * POOL_GROUP_WORDS;
+    a.n_embd = n_embd; a.dim = dim; a.mean = p->pooling == NANO_POOL_MEAN; a.normalize = p->normalize;
+    for (uint32_t ps = 0; ps < pl.n_passes(); ps++) {
+        a.x = dx + (size_t)pl.pass_start[ps] * n_embd; a.rows_max = pl.pass_start[ps + 1] - pl.pass_start[ps];
+        a.groups = dmap + (size_t)pl.group_start[ps] * POOL_GROUP_WORDS;
+        OP_HIP(launch_pool_rows(a, pl.group_start[ps + 1] - pl.group_start[ps], 0));
+    }
+    OP_HIP(hipMemcpy(out, a.out, (size_t)n_segs * dim * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
