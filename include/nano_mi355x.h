@@ -700,8 +700,34 @@ typedef struct NanoFusedGemvDesc {
     uint32_t *ntiles_out;       /* optional: pairs per sequence the launch was asked for and the arg-max kernel reads; 0: the launch was not asked */
     uint32_t *argmax_out;       /* optional uint32_t[nb]: behind the launch, the arg-max kernel as a greedy step builds it -- over out[b][: sum of
                                  * rows], from the partials where the launch was asked for them, scanning the result otherwise */
+    const float *resid_add;     /* optional, kind 1 only: [nb][resid_add_stride] -- the addend of the residual epilogue, out += (W act + resid_add)
+                                 * (the LoRA o-branch's o1, infer.c:898-908); NULL: out += W act.  The plan queries read it as a flag */
+    uint32_t resid_add_stride;  /* floats between the sequences of resid_add (>= rows[0]) */
 } NanoFusedGemvDesc;
 int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *d);
+
+/* The two LoRA side-branch launches of a layer (nano_amd/csrc/lora.hip) exactly as a decode step issues them, on caller-chosen inputs:
+ *   nano_hip_op_lora_qkv   q[b] += s B_q (A_q xb),  kraw[b] += s B_k (A_k xb),  v[b * v_bstride + pos[b] * KD ...] += s B_v (A_v xb)
+ *                          with xb = rmsnorm(x[b], norm_w) and s = (float)alpha / (float)rank     (reference infer/infer.c:792-808)
+ *   nano_hip_op_lora_o     q[b] = s B (A x[b]) -- x = the attention output, q = o1, a[0] / b[0] = the o pair    (infer.c:898-903)
+ * q, kraw and v go to the device whole (q_floats / k_floats / v_floats floats) and come back whole, so the caller sees every element a
+ * launch wrote: q holds nb rows of E floats from its start, kraw nb rows of KD; v is a whole cache plane [slots][S][KD] and v_bstride the
+ * floats between the sequences' slots -- S * KD for a decode step, 0 for a prefill chunk (every sequence is a position of one slot).
+ * Refused before any launch (NANO_HIP_EINVAL): a null pointer, nb of 0 or above NANO_MAX_BATCH, E % 4 != 0, rank of 0, E + 3 rank + 32
+ * floats beyond the 64 KiB of LDS a launch may ask for, a buffer smaller than its rows, pos[b] >= S, a v row beyond v_floats.
+ * All pointers are host pointers. */
+typedef struct NanoLoraOpDesc {
+    uint32_t E, KD, rank, alpha, nb, S;
+    uint32_t v_bstride, _pad;
+    const float *x;             /* [nb][E] */
+    const float *norm_w;        /* qkv: [E] */
+    const float *a[3], *b[3];   /* qkv: the q, k, v pairs -- a[i] [rank][E], b[i] [E | KD | KD][rank]; o: a[0] / b[0] [E][rank] */
+    const uint32_t *pos;        /* qkv: [nb] */
+    float *q, *kraw, *v;        /* in-place targets (o: q alone, overwritten) */
+    uint64_t q_floats, k_floats, v_floats;
+} NanoLoraOpDesc;
+int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d);
+int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d);
 /* The FP32 launch the router issues for descriptor d (quant = NANO_QUANT_F32), from the functions the launcher and the router follow:
  * out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0} -- gemv_f32_slab_kernel<role, B, nv, upw> on
  * nw waves x grid workgroups owning rw rows each, of the first of `launches` slices of seqs_per_launch sequences.  takes = 0: the

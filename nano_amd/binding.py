@@ -35,7 +35,15 @@ class NanoFusedGemvDesc(C.Structure):
                 ("attn_part", C.c_void_p), ("attn_ml", C.c_void_p), ("attn_nsplit", C.c_uint32), ("attn_n_head", C.c_uint32),
                 ("attn_hd", C.c_uint32), ("use_gemm", C.c_uint32), ("ordered", C.c_uint32), ("route_out", C.c_void_p), ("out", C.c_void_p),
                 ("out_slots", C.c_uint32), ("out_stride", C.c_uint32), ("tile_max", C.c_void_p), ("tile_slots", C.c_uint32),
-                ("tile_pairs", C.c_uint32), ("ntiles_out", C.c_void_p), ("argmax_out", C.c_void_p)]
+                ("tile_pairs", C.c_uint32), ("ntiles_out", C.c_void_p), ("argmax_out", C.c_void_p), ("resid_add", C.c_void_p),
+                ("resid_add_stride", C.c_uint32)]
+
+
+class NanoLoraOpDesc(C.Structure):
+    """include/nano_mi355x.h NanoLoraOpDesc: one LoRA side-branch launch (q | k | v, or o) as a step issues it."""
+    _fields_ = [(n, C.c_uint32) for n in ("E", "KD", "rank", "alpha", "nb", "S", "v_bstride", "_pad")] + \
+               [("x", C.c_void_p), ("norm_w", C.c_void_p), ("a", C.c_void_p * 3), ("b", C.c_void_p * 3), ("pos", C.c_void_p),
+                ("q", C.c_void_p), ("kraw", C.c_void_p), ("v", C.c_void_p), ("q_floats", C.c_uint64), ("k_floats", C.c_uint64), ("v_floats", C.c_uint64)]
 
 
 class NanoAttnDecodeDesc(C.Structure):
@@ -241,6 +249,8 @@ def lib() -> C.CDLL:
     fn("nano_hip_op_swiglu", C.c_int, [C.c_int, f32p, f32p, C.c_uint32])
     fn("nano_hip_op_argmax", C.c_int, [C.c_int, f32p, C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_op_fused_gemv", C.c_int, [C.c_int, C.POINTER(NanoFusedGemvDesc)])
+    fn("nano_hip_op_lora_qkv", C.c_int, [C.c_int, C.POINTER(NanoLoraOpDesc)])
+    fn("nano_hip_op_lora_o", C.c_int, [C.c_int, C.POINTER(NanoLoraOpDesc)])
     fn("nano_hip_op_attention_decode", C.c_int, [C.c_int, C.POINTER(NanoAttnDecodeDesc)])
     fn("nano_hip_f32_gemv_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
     fn("nano_hip_f32_gemm_plan", C.c_int, [C.POINTER(NanoFusedGemvDesc), C.c_uint32, C.POINTER(C.c_uint32)])
@@ -849,9 +859,10 @@ def op_matmul_q4k(x_blocks, w_blocks, n, d, device=0):
 _FLAG = np.zeros(1, np.float32)         # stands for "a norm weight / attention partials are given" where only the shape is read
 
 
-def _fused_shape(quant, kind, n, rows, nb, *, gs=0, norm=False, attn=None, ordered=False, use_gemm=False) -> NanoFusedGemvDesc:
+def _fused_shape(quant, kind, n, rows, nb, *, gs=0, norm=False, attn=None, ordered=False, use_gemm=False, resid_add=False) -> NanoFusedGemvDesc:
     """The shape part of a NanoFusedGemvDesc -- all a plan query reads.  norm: False, the address of the norm weight, or True (a query:
-    null or not is all that is read, _FLAG stands for the weight); attn: None or (n_head, hd, nsplit[, address of the partials]), _FLAG likewise."""
+    null or not is all that is read, _FLAG stands for the weight); attn: None or (n_head, hd, nsplit[, address of the partials]), _FLAG likewise;
+    resid_add: False, True (a query: _FLAG) or (address, stride) of the residual epilogue's addend (kind 1)."""
     d = NanoFusedGemvDesc()
     d.quant, d.gs, d.kind, d.n, d.nb, d.nseg = quant, gs, kind, n, nb, len(rows)
     for i, r in enumerate(rows):
@@ -861,6 +872,8 @@ def _fused_shape(quant, kind, n, rows, nb, *, gs=0, norm=False, attn=None, order
     if attn is not None:
         d.attn_n_head, d.attn_hd, d.attn_nsplit = attn[:3]
         d.attn_part = attn[3] if len(attn) > 3 else _FLAG.ctypes.data
+    if resid_add:
+        d.resid_add, d.resid_add_stride = (_FLAG.ctypes.data, rows[0]) if resid_add is True else resid_add
     d.ordered = 1 if ordered else 0
     d.use_gemm = 1 if use_gemm else 0
     return d
@@ -875,11 +888,11 @@ def _plan_query(name, fields, words, desc, cus):
     return dict(zip(fields, (int(v) for v in out)))
 
 
-def f32_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
+def f32_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, resid_add=False, cus=256):
     """The FP32 launch the router issues for a fused-gemv shape (nano_hip_f32_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of F32_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    return _plan_query("f32_gemv", F32_PLAN_FIELDS, F32_PLAN_WORDS, _fused_shape(0x00, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
+    return _plan_query("f32_gemv", F32_PLAN_FIELDS, F32_PLAN_WORDS, _fused_shape(0x00, kind, n, rows, nb, norm=bool(norm), attn=attn, resid_add=bool(resid_add)), cus)
 
 
 def f32_gemm_plan(kind, n, rows, nb=9, *, norm=False, attn=None, cus=256):
@@ -888,11 +901,11 @@ def f32_gemm_plan(kind, n, rows, nb=9, *, norm=False, attn=None, cus=256):
     return _plan_query("f32_gemm", F32_GEMM_PLAN_FIELDS, len(F32_GEMM_PLAN_FIELDS), _fused_shape(0x00, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
 
 
-def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):
+def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, resid_add=False, cus=256):
     """The Q80 launch the router issues for a fused-gemv shape (nano_hip_q80_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of Q80_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm)
+    d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm, resid_add=bool(resid_add))
     return _plan_query("q80_gemv", Q80_PLAN_FIELDS, len(Q80_PLAN_FIELDS), d, cus)
 
 
@@ -903,15 +916,15 @@ def q80_gemm_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=
     return _plan_query("q80_gemm", Q80_GEMM_PLAN_FIELDS, len(Q80_GEMM_PLAN_FIELDS), d, cus)
 
 
-def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, cus=256):
+def q4k_gemv_plan(kind, n, rows, nb=1, *, norm=False, attn=None, resid_add=False, cus=256):
     """The Q4K launch the router issues for a fused-gemv shape (nano_hip_q4k_gemv_plan; needs no GPU).  rows: the row count of each
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of Q4K_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
-    return _plan_query("q4k_gemv", Q4K_PLAN_FIELDS, len(Q4K_PLAN_FIELDS), _fused_shape(0x42, kind, n, rows, nb, norm=bool(norm), attn=attn), cus)
+    return _plan_query("q4k_gemv", Q4K_PLAN_FIELDS, len(Q4K_PLAN_FIELDS), _fused_shape(0x42, kind, n, rows, nb, norm=bool(norm), attn=attn, resid_add=bool(resid_add)), cus)
 
 
 def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, resid=None, attn=None, use_gemm=False, ordered=False,
-                  want_route=False, guard=None, partials=None, want_argmax=False, device=0):
+                  want_route=False, guard=None, partials=None, want_argmax=False, resid_add=None, device=0):
     """One fused decode GEMV launch exactly as a decode step issues it (nano_hip_op_fused_gemv).
     quant: 0x00 F32 / 0x80 Q80 / 0x42 Q4K; kind: 0 store, 1 residual add, 2 SwiGLU.
     weights: list of (w, ws_or_None, rows) -- F32 float[rows, n]; Q80 int8[rows*n] + float scales; Q4K uint8 blocks (no frame).
@@ -925,6 +938,7 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     comes back whole; the launch is asked for partials exactly where the step's classifier is (route.hip route_partials()) and then
     writes nb x ntiles (max, bits of the first row) pairs densely from the start of the buffer -- partials.reshape(-1, 2)[b * ntiles + t].
     want_argmax: behind the launch, the arg-max kernel as a greedy step builds it (from the partials where the launch wrote them).
+    resid_add: None, or a float32 array [nb, stride >= rows] (kind 1): the residual epilogue's addend, out += (W act + resid_add[b, :rows]).
     Returns out[nb, rows_total]; with any of want_route / partials / want_argmax a tuple (out, route name if want_route,
     ntiles if partials is given -- 0: the launch was not asked --, argmax uint32[nb] if want_argmax)."""
     keep = []
@@ -938,8 +952,12 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     if attn is not None:
         part, ml, n_head, hd = attn
         part, ml = held(part, np.float32), held(ml, np.float32)
+    if resid_add is not None:
+        resid_add = held(resid_add, np.float32)
+        assert resid_add.ndim == 2 and resid_add.shape[0] == nb
     d = _fused_shape(quant, kind, n, [rows for _, _, rows in weights], nb, gs=gs, norm=norm_w is not None and norm_w.ctypes.data,
-                     attn=None if attn is None else (n_head, hd, part.shape[-2], part.ctypes.data), ordered=ordered, use_gemm=use_gemm)
+                     attn=None if attn is None else (n_head, hd, part.shape[-2], part.ctypes.data), ordered=ordered, use_gemm=use_gemm,
+                     resid_add=resid_add is not None and (resid_add.ctypes.data, resid_add.shape[1]))
     for i, (w, ws, _) in enumerate(weights):
         d.w[i] = held(w).ctypes.data
         if ws is not None:
@@ -975,6 +993,49 @@ def op_fused_gemv(quant, kind, n, weights, x=None, norm_w=None, *, gs=0, nb=1, r
     if want_argmax:
         res += (amax,)
     return res if len(res) > 1 else out
+
+
+def _lora_desc(E, KD, rank, alpha, x, pairs, keep):
+    def held(v, dtype=np.float32):
+        v = np.ascontiguousarray(v, dtype); keep.append(v)
+        return v
+    x = held(x)
+    d = NanoLoraOpDesc()
+    d.E, d.KD, d.rank, d.alpha, d.nb = E, KD, rank, alpha, x.reshape(-1, E).shape[0]
+    d.x = x.ctypes.data
+    for i, (A, Bm) in enumerate(pairs):
+        d.a[i], d.b[i] = held(A).ctypes.data, held(Bm).ctypes.data
+    return d, held
+
+
+def _inplace(a):
+    assert a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
+    return a.ctypes.data, a.size
+
+
+def op_lora_qkv(x, norm_w, pairs, q, kraw, v, pos, *, KD, rank, alpha, S, v_bstride, device=0):
+    """One lora_qkv launch as a step issues it (nano_hip_op_lora_qkv).  x [nb, E]; pairs = ((A_q, B_q), (A_k, B_k), (A_v, B_v)), A [rank, E],
+    B [E | KD, rank]; q, kraw, v: float32 arrays changed IN PLACE, each going to the device whole and coming back whole -- q holds the nb
+    rows of E floats from its start, kraw those of KD, v is a whole cache plane [slots, S, KD] with sequence b's row at flat offset
+    b * v_bstride + pos[b] * KD (v_bstride = S * KD: a decode step; 0: a prefill chunk)."""
+    keep = []
+    x = np.ascontiguousarray(x, np.float32)
+    d, held = _lora_desc(x.shape[-1], KD, rank, alpha, x, pairs, keep)
+    d.S, d.v_bstride = S, v_bstride
+    d.norm_w = held(norm_w).ctypes.data
+    d.pos = held(pos, np.uint32).ctypes.data
+    (d.q, d.q_floats), (d.kraw, d.k_floats), (d.v, d.v_floats) = _inplace(q), _inplace(kraw), _inplace(v)
+    check(lib().nano_hip_op_lora_qkv(device, C.byref(d)))
+
+
+def op_lora_o(xba, pair, o1, *, rank, alpha, device=0):
+    """One lora_o launch as a step issues it (nano_hip_op_lora_o): o1[b] = (alpha / rank) B (A xba[b]).  o1: a float32 array changed IN
+    PLACE (the nb rows of E floats from its start are written; it goes to the device whole and comes back whole)."""
+    keep = []
+    xba = np.ascontiguousarray(xba, np.float32)
+    d, _ = _lora_desc(xba.shape[-1], 0, rank, alpha, xba, (pair,), keep)
+    d.q, d.q_floats = _inplace(o1)
+    check(lib().nano_hip_op_lora_o(device, C.byref(d)))
 
 
 def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n_layer, layer, S, range_hint, rope_cos, rope_sin,

@@ -457,6 +457,8 @@ extern "C" int nano_hip_forward(NanoHipModel *m, const uint32_t *tokens, const u
 extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats) {
     if (!m || !params || !rank) FAIL(NANO_HIP_EINVAL, "bad argument");
     if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
+    // (n_embd % 16 == 0 is the model's own check; rank is the caller's: a module whose t vectors do not fit the launches' LDS is refused here)
+    if (const char *msg = lora_shape_error(m->d.n_embd, rank)) FAIL(NANO_HIP_EINVAL, "%s (n_embd %u, rank %u)", msg, m->d.n_embd, rank);
     HIP_TRY(hipSetDevice(m->device));
     const size_t L = m->d.n_layer, E = m->d.n_embd, KD = m->KD, r = rank;
     const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };

@@ -477,8 +477,9 @@ bool exact_serves(const NanoHipModel *m) { return m->exact && !strict_serves(m);
 // THE place that says which combinations of (strict, exact, phase hook, LoRA, FP16 KV, paged KV) are served: asked by run_step and
 // nano_hip_prefill before they queue anything.  The reference-order step has neither the LoRA side branches nor the FP16 or paged
 // cache; the fast step has no LoRA side branches on a paged, FP16 or FP8 cache (they write FP32 v rows of the contiguous cache).
-// prefill: batched prefill has never refused LoRA on the FP16 cache; kept as it is.  The FP8 cache refuses it there too: the v branch's
-// FP32 read-modify-write would land on byte rows, from a quarter of the layers on beyond the allocation.
+// That holds for decode and batched prefill alike: on the FP16 cache the fresh v row goes to vraw (KvRows::v_target) while the v branch
+// would read-modify-write FP32 at a float offset into a cache of halfs -- twice the byte offset, from half of the layers on beyond the
+// slot; on the FP8 cache, byte rows, from a quarter of the layers on beyond the allocation.
 int step_served(const NanoHipModel *m, bool prefill) {
     if (strict_serves(m) || exact_serves(m)) {
         const char *mode = m->strict ? "strict mode" : exact_serves(m) ? "exact mode" : "exact mode with a phase hook";
@@ -487,8 +488,8 @@ int step_served(const NanoHipModel *m, bool prefill) {
         return 0;
     }
     if (m->kv.paged && m->lora_on) FAIL(NANO_HIP_EINVAL, "the paged KV cache is served by the fused path only: not with the LoRA side branches");
-    if (m->kv_half && m->lora_on && !prefill) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");
-    if (m->kv_half == KV_FMT_FP8 && m->lora_on) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");   // (batched prefill: the same message)
+    if (m->kv_half && m->lora_on) FAIL(NANO_HIP_EINVAL, "the LoRA side branches write FP32 v rows: not available with the FP16 KV cache");   // (FP8 too: the same message)
+    (void)prefill;                      // (no combination is served for one and refused for the other any more)
     return 0;
 }
 // the policy of the decode steps: either failure fails the call

@@ -393,6 +393,9 @@ struct LoraArgs {
     const uint32_t *pos;
     uint32_t E, KD, rank, alpha, v_bstride, _pad;
 };
+// what the two launches cannot run, or nullptr: E % 4 (float4 loads of the A rows and of the LDS copy), rank 0, and dynamic LDS beyond the
+// 64 KiB a launch may ask for (qkv: E + 3 rank + 32 floats).  Asked by nano_hip_lora_attach and by the operators; the launches refuse too.
+const char *lora_shape_error(uint32_t E, uint32_t rank);
 hipError_t launch_lora_qkv(const LoraArgs &a, uint32_t nb, hipStream_t st);
 hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st);
 

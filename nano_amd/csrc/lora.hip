@@ -74,13 +74,23 @@ __global__ __launch_bounds__(256) void lora_o_kernel(const LoraArgs a) {
 
 }  // namespace
 
+static size_t lora_qkv_lds(uint32_t E, uint32_t rank) { return (((size_t)E + 3) & ~(size_t)3) * 4 + 3 * (size_t)rank * 4 + 32 * 4; }
+const char *lora_shape_error(uint32_t E, uint32_t rank) {
+    if (E == 0 || E % 4) return "LoRA side branches need n_embd % 4 == 0";
+    if (rank == 0) return "LoRA rank 0";
+    if (lora_qkv_lds(E, rank) > (size_t)64 * 1024) return "LoRA side branches: n_embd + 3 rank + 32 floats exceed the 64 KiB of LDS a launch may ask for";
+    return nullptr;
+}
+
 hipError_t launch_lora_qkv(const LoraArgs &a, uint32_t nb, hipStream_t st) {
-    const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + 3 * (size_t)a.rank * 4 + 32 * 4;
+    if (lora_shape_error(a.E, a.rank)) return hipErrorInvalidValue;
+    const size_t lds = lora_qkv_lds(a.E, a.rank);
     hipLaunchKernelGGL(lora_qkv_kernel, dim3(nb), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 // x = xba [nb][E] in, q = o1 [nb][E] out, qa / qb = the o pair
 hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st) {
+    if (lora_shape_error(a.E, a.rank)) return hipErrorInvalidValue;
     const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + (size_t)a.rank * 4;
     hipLaunchKernelGGL(lora_o_kernel, dim3(nb), dim3(256), lds, st, a);
     return hipGetLastError();

@@ -318,12 +318,13 @@ extern "C" int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n
     return 0;
 }
 
-// what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part, read as flags), or nullptr
+// what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part / resid_add, read as flags), or nullptr
 static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || d.n % 4) return "bad fused-gemv descriptor";
     if (d.quant == NANO_QUANT_Q80 && (!(d.gs == 32 || d.gs == 64 || d.gs == 128 || d.gs == 256) || d.n % d.gs || d.n % 16)) return "bad n / group size";
     for (uint32_t s = 0; s < d.nseg; s++) if (!d.rows[s]) return "missing weight tensor";
     if (d.kind == 2 && d.rows[0] != d.rows[1]) return "W1 / W3 row counts differ";
+    if (d.resid_add && (d.kind != 1 || d.resid_add_stride < d.rows[0])) return "bad residual addend";
     if (d.attn_part && (!d.attn_nsplit || d.attn_nsplit > 8 || !d.attn_n_head || d.attn_n_head * d.attn_hd != d.n || d.kind != 1 || (d.nb > 8 && d.quant != NANO_QUANT_Q4K))) return "bad attention partials";
     return nullptr;
 }
@@ -355,6 +356,7 @@ static FusedLaunch fused_launch(const NanoFusedGemvDesc &d, uint32_t cus, F32Scr
     a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
     a.norm_w = d.norm_w;
     if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    if (d.resid_add) { a.resid_add = d.resid_add; a.resid_add_bstride = d.resid_add_stride; }
     a.ordered = d.ordered ? 1u : 0u;
     r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = (d.use_gemm && d.quant == NANO_QUANT_Q80) ? 1u : 9u;
     if (d.quant == NANO_QUANT_Q80) {
@@ -381,8 +383,8 @@ static void flag_scratch(FusedLaunch &L) {
     if (L.r.f32x_floats) L.r.f32x = reinterpret_cast<float *>(flag);
 }
 // The start of every plan query: the arguments checked, out zeroed, the launch as the operator builds it for `cus` compute units.
-// Host arithmetic only from here on -- no device is touched, and of the descriptor's pointers only norm_w and attn_part are looked at
-// (null or not), never followed; `ordered` and `use_gemm` as flags.
+// Host arithmetic only from here on -- no device is touched, and of the descriptor's pointers only norm_w, attn_part and resid_add are
+// looked at (null or not), never followed; `ordered` and `use_gemm` as flags.
 static int query_begin(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t *out, uint32_t words, uint32_t quant, const char *not_quant,
                        F32Scratch f32x, FusedLaunch *L) {
     if (!dp || !out) { nano_hip_set_error_("null argument"); return NANO_HIP_EINVAL; }
@@ -555,6 +557,7 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
         OP_CHECK(a.attn_part && a.attn_ml, "device alloc failed");
         if (!a.xin) { a.xin = a.attn_part; a.xin_bstride = d.n; }     // never read: the prologue combines the partials
     }
+    if (d.resid_add) { a.resid_add = B.upload(d.resid_add, (size_t)d.nb * d.resid_add_stride); OP_CHECK(a.resid_add, "device alloc failed"); }
     // the scratch, exactly as fused_launch() sizes it
     if (L.gq_bytes) { r.gq = B.alloc<int8_t>(L.gq_bytes); r.gxs = B.alloc<float>(L.gxs_floats); OP_CHECK(r.gq && r.gxs, "device alloc failed"); }
     if (r.q4x_bytes) { r.q4x = B.alloc<uint8_t>(r.q4x_bytes); OP_CHECK(r.q4x, "device alloc failed"); }
@@ -589,6 +592,52 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     if (damax) OP_HIP(hipMemcpy(d.argmax_out, damax, (size_t)d.nb * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- the LoRA side-branch launches (lora.hip), LoraArgs filled as enqueue_step() fills them (backend_step.hip).  The arguments are checked
+// before a device is asked for.
+static const char *lora_desc_error(const NanoLoraOpDesc *d, bool qkv) {
+    if (!d || !d->x || !d->a[0] || !d->b[0] || !d->q) return "lora: null argument";
+    if (qkv && (!d->norm_w || !d->a[1] || !d->b[1] || !d->a[2] || !d->b[2] || !d->pos || !d->kraw || !d->v)) return "lora: null argument";
+    if (d->nb == 0 || d->nb > NANO_MAX_BATCH) return "lora: nb outside 1 .. NANO_MAX_BATCH";
+    if (const char *msg = lora_shape_error(d->E, d->rank)) return msg;
+    if (d->q_floats < (uint64_t)d->nb * d->E) return "lora: q smaller than nb rows of E";
+    if (!qkv) return nullptr;
+    if (d->KD == 0 || d->k_floats < (uint64_t)d->nb * d->KD) return "lora: KD of 0, or kraw smaller than nb rows of KD";
+    for (uint32_t b = 0; b < d->nb; b++) {
+        if (d->pos[b] >= d->S) return "lora: position beyond S";
+        if ((uint64_t)b * d->v_bstride + ((uint64_t)d->pos[b] + 1) * d->KD > d->v_floats) return "lora: a v row beyond v_floats";
+    }
+    return nullptr;
+}
+static int lora_op(int device, const NanoLoraOpDesc *d, bool qkv) {
+    if (const char *msg = lora_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    int rc; if ((rc = begin(device))) return rc;
+    const size_t E = d->E, KD = d->KD, r = d->rank;
+    DevBufs B;
+    LoraArgs la{};
+    la.x = B.upload(d->x, d->nb * E);
+    la.qa = B.upload(d->a[0], r * E); la.qb = B.upload(d->b[0], E * r);
+    la.q = B.upload(d->q, (size_t)d->q_floats);
+    OP_CHECK(la.x && la.qa && la.qb && la.q, "device alloc failed");
+    la.E = d->E; la.KD = d->KD; la.rank = d->rank; la.alpha = d->alpha;
+    if (qkv) {
+        la.norm_w = B.upload(d->norm_w, E);
+        la.ka = B.upload(d->a[1], r * E); la.kb = B.upload(d->b[1], KD * r); la.va = B.upload(d->a[2], r * E); la.vb = B.upload(d->b[2], KD * r);
+        la.kraw = B.upload(d->kraw, (size_t)d->k_floats); la.v = B.upload(d->v, (size_t)d->v_floats);
+        la.pos = B.upload(d->pos, d->nb); la.v_bstride = d->v_bstride;
+        OP_CHECK(la.norm_w && la.ka && la.kb && la.va && la.vb && la.kraw && la.v && la.pos, "device alloc failed");
+    }
+    OP_HIP(qkv ? launch_lora_qkv(la, d->nb, 0) : launch_lora_o(la, d->nb, 0));
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(d->q, la.q, (size_t)d->q_floats * 4, hipMemcpyDeviceToHost));
+    if (qkv) {
+        OP_HIP(hipMemcpy(d->kraw, la.kraw, (size_t)d->k_floats * 4, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(d->v, la.v, (size_t)d->v_floats * 4, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, true); }
+extern "C" int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, false); }
 
 // ---- ONE path from an attention-decode descriptor to the launch's arguments: nano_hip_op_attention_decode, the fused q | k | v + attention
 // operator and its plan query start here.  Every shape field as enqueue_step() fills it (backend_step.hip); of the pointers q_norm / k_norm

@@ -256,13 +256,16 @@ def make_fullsize64(tmpdir):
     np.savez_compressed(os.path.join(GOLD, f"fullsize64_{name}_{quant}.npz"), **out)
 
 
-LORA_CASES = [("tiny-nano", "f32", 0), ("tiny-nano", "q80", 32), ("tiny-nano-odd", "f32", 0)]
+LORA_CASES = [("tiny-nano", "f32", 0), ("tiny-nano", "q80", 32), ("tiny-nano-odd", "f32", 0), ("tiny-nano", "q4k", 0), ("tiny-nano-odd", "q4k", 0)]
 
 
-def make_lora(tmpdir):
-    """Teacher-forced logits of the compiled reference with a synthetic LoRA module attached (rank 8, alpha 16)."""
+def make_lora(tmpdir, only=None):
+    """Teacher-forced logits of the compiled reference with a synthetic LoRA module attached (rank 8, alpha 16).  only: the cases asked
+    for as name_quant (the others' files are left as they are)."""
     ref = ob.load_ref()
     for (name, quant, gs) in LORA_CASES:
+        if only and f"{name}_{quant}" not in only:
+            continue
         spec = mf.preset(name, quant, group_size=gs)
         path = os.path.join(tmpdir, f"{name}-{quant}.bin")
         lpath = os.path.join(tmpdir, f"{name}-lora.bin")
@@ -364,6 +367,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 2 and sys.argv[1] == "e2e":               # python tools/make_golden.py e2e name_quant[_gs128] ...
         make_e2e(tmp, set(sys.argv[2:]))
+        sys.exit(0)
+    if len(sys.argv) > 2 and sys.argv[1] == "lora":              # python tools/make_golden.py lora name_quant ...
+        make_lora(tmp, set(sys.argv[2:]))
         sys.exit(0)
     extract_sort_model()
     make_e2e(tmp)
