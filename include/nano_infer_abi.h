@@ -244,6 +244,17 @@ int nano_forward_batch_sample_edit(Nano_Context *ctx, const uint32_t *tokens, co
  * its slot 0 and forks it into the other slots of its share (nano_hip_kv_fork, nano_mi355x.h: a copy, or shared pages on a paged
  * cache).  Applies the context's LoRA selection as nano_forward_batch does.  Returns 0 or a NANO_HIP_E* code. */
 int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t n_prefix, uint32_t batch);
+/* Park a sequence's KV rows in host memory and bring them back (KV images, nano_mi355x.h: the format, and what save and restore
+ * promise, are stated there).  `slot` is a slot of the context's device model -- sequence i of nano_forward_batch lives in slot i, a
+ * session in slot 0.  nano_kv_image_bytes = the size of the image of n_pos positions (0 for a context without a device model);
+ * nano_kv_save writes it into buf[0..cap) and its size into *bytes; nano_kv_restore makes positions 0 .. n_pos-1 of `slot` those of
+ * the image (n_pos = UINT32_MAX: all of it), in this process or in another that opened the same model file: the continuation is bit
+ * for bit the uninterrupted one.  Contexts with replicas are not offered: both return NANO_HIP_EINVAL there (a sequence's slot is on
+ * one of several devices).  Not offered either: format conversion, ranges that do not start at position 0, an asynchronous call, file
+ * I/O or compression, several slots at once (restore, then nano_hip_kv_fork).  Returns 0 or a NANO_HIP_E* code. */
+size_t nano_kv_image_bytes(Nano_Context *ctx, uint32_t n_pos);
+int nano_kv_save(Nano_Context *ctx, uint32_t slot, uint32_t n_pos, void *buf, size_t cap, size_t *bytes);
+int nano_kv_restore(Nano_Context *ctx, uint32_t slot, const void *buf, size_t bytes, uint32_t n_pos);
 /* Ingest `batch` prompts at once: sequence i (the sequences nano_forward_batch addresses) takes prompts[i][0..n_tokens[i]) from position
  * 0, and first_ids[i] (optional, batch words) is the arg-max behind its last token -- the first id of a greedy continuation (an empty
  * prompt leaves first_ids[i] untouched).  One ragged step per device (nano_hip_step_rows, nano_mi355x.h): the prompts share the weight

@@ -131,6 +131,67 @@ int  nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_pos, const 
 /* paged models: pages that currently have more than one owner; page copies made so far because a slot wrote into a page it
  * shared (copy-on-write), since the model was created.  NANO_HIP_EINVAL on a model without NANO_HIP_KV_PAGED. */
 int  nano_hip_kv_sharing(const NanoHipModel *m, uint32_t *shared_pages, uint64_t *cow_copies);
+
+/* ---- KV images: a slot's rows in host memory and back ---------------------------------------------
+ * A KV image is a self-describing byte string holding positions 0 .. n_pos-1 of one sequence slot, bit for bit as the cache holds
+ * them; the caller keeps it in RAM, a file or another process.  The rows of a position do not depend on the slot, so an image
+ * comes back into any slot, and into any model -- of this process or another -- opened from the same model file with the same
+ * element format; decoding then continues with exactly the bits it would have had.  The reference has no counterpart (one cache per
+ * context, infer/infer.c:46-51).
+ * Header (64 bytes, little-endian): NanoKvImageHeader below.  model_tag is an FNV-1a (64 bit) of the twelve NanoModelDesc words and
+ * params_bytes: a guard against mixing up shapes, NOT a proof of equal weights (two files of one shape and size share a tag).
+ * Payload, block-major: block b covers positions 64 b .. min(64 b + 63, n_pos - 1) and starts at byte 64 + 64 b n_layer 2 row_bytes;
+ * inside a block the layers ascend, and each layer holds the block's K rows (one contiguous run) and then its V rows, every row the
+ * cache's own bytes (FP32, FP16 or e4m3).  The payload is n_pos n_layer 2 row_bytes bytes.  A block is a page of the paged cache, the
+ * image streams in whole blocks, and the image of the first n' <= n_pos positions is a prefix of the bytes plus a row cut inside one
+ * block.  The bytes are the same whether the slot was contiguous or paged: an image of one layout restores into the other.
+ * Not offered: conversion between element formats (an FP32 image does not restore into an FP16 or FP8 cache), ranges that do not
+ * start at position 0, an asynchronous call, file I/O or compression, replicas (the engine entries refuse a replicated context), and
+ * restoring into several slots at once (restore into one, then nano_hip_kv_fork). */
+typedef struct NanoKvImageHeader {
+    uint32_t magic;            /* "NKV1" */
+    uint32_t version;          /* 1 */
+    uint32_t header_bytes;     /* 64 */
+    uint32_t format;           /* element format: 0 FP32, 1 FP16, 2 FP8 e4m3 */
+    uint32_t n_layer, kv_dim, n_pos;
+    uint32_t block_rows;       /* 64 */
+    uint32_t row_bytes;        /* kv_dim x element bytes */
+    uint32_t reserved0;        /* 0 */
+    uint64_t payload_bytes;    /* n_pos * n_layer * 2 * row_bytes */
+    uint64_t model_tag;
+    uint32_t reserved1[2];     /* 0 */
+} NanoKvImageHeader;
+/* Host-only (no device is touched, they answer on a machine without a GPU).
+ * _plan: out[0..8) = header bytes, payload bytes, total bytes, blocks, rows per run of the last block (0 when n_pos is 0), bytes of a
+ * full block (the block stride), the byte width of the vectors the pack kernel moves the rows in (16, 8 or 4, from row_bytes), 0.
+ * NANO_HIP_EINVAL: null out, elem_bytes not 4 / 2 / 1, n_layer 0, kv_dim 0 or no multiple of 4.
+ * _bytes: the size of the image of n_pos positions of model m (0 for a null model).
+ * _check: 0 and *out_header (may be NULL) for a well-formed image; NANO_HIP_EINVAL with a message for a null or short buffer (shorter
+ * than the header, or than header + payload), bad magic or version, block_rows != 64, a format / n_layer / kv_dim that describe no
+ * cache, row_bytes != kv_dim x element bytes, payload_bytes that are not the plan's, non-zero reserved words. */
+#define NANO_KV_IMAGE_PLAN_WORDS 8
+int    nano_hip_kv_image_plan(uint32_t n_layer, uint32_t kv_dim, uint32_t elem_bytes, uint32_t n_pos, uint64_t *out);
+size_t nano_hip_kv_image_bytes(const NanoHipModel *m, uint32_t n_pos);
+int    nano_hip_kv_image_check(const void *image, size_t bytes, NanoKvImageHeader *out_header);
+/* Save: the image of positions 0 .. n_pos-1 of `slot` into image[0..cap), any host memory; *bytes = its size.  Runs behind everything
+ * queued on the model's stream and returns when `image` holds the header and all rows.  The slot, its pages and the owner counts are
+ * unchanged (a shared page is read, not copied); a block the slot has not mapped (paged cache) is written as zeros, which is what
+ * attention reads there.  n_pos == 0 is valid: the image is the header alone.  Every mode, layout and element format.
+ * NANO_HIP_EINVAL: null model / image / bytes, slot >= max_batch, n_pos > max_seq_len, cap below the image's size (*bytes still gets
+ * the size needed).  NANO_HIP_ENOMEM: the staging buffers (allocated on first use, freed with the model) could not be had; the model
+ * stays usable.
+ * Restore: positions 0 .. n_pos-1 of the image into `slot`; n_pos <= the header's n_pos, UINT32_MAX = all of it.  Fewer positions
+ * read the byte prefix plus the row cut: a rollback to an earlier turn.  `image` is reusable at return; the device work is queued on
+ * the model's stream behind what is already there.  Contiguous cache: rows 0 .. n_pos-1 of the slot are overwritten, rows >= n_pos
+ * stay as they are (as with a fork).  Paged cache, the fork's contract for a destination: the slot first gives back what it holds and
+ * takes ceil(n_pos / 64) pages of its own, drawn from the free pages plus those only this slot owns; rows n_pos % 64 .. 63 of a partial
+ * last page are zero; other owners of pages the slot shared keep their rows.  Everything is planned first and committed after it was
+ * queued: NANO_HIP_ENOMEM (pool, or staging buffers) leaves tables, owner counts and contents as they were.
+ * NANO_HIP_EINVAL, before anything is queued: whatever nano_hip_kv_image_check refuses, slot >= max_batch, n_pos beyond the image or
+ * max_seq_len, an element format, n_layer, kv_dim or model tag that is not the model's.
+ * Neither touches the sampler's per-slot records or the lookup loop's history: those are keyed by the caller's history. */
+int  nano_hip_kv_save(NanoHipModel *m, uint32_t slot, uint32_t n_pos, void *image, size_t cap, size_t *bytes);
+int  nano_hip_kv_restore(NanoHipModel *m, uint32_t slot, const void *image, size_t bytes, uint32_t n_pos);
 /* number of parameter-blob bytes the backend expects for `desc` (0 if it cannot be derived
  * without reading the blob, i.e. Q4K whose tensor frames carry their own sizes) */
 size_t nano_hip_params_bytes(const NanoModelDesc *desc);

@@ -288,9 +288,19 @@ def lib() -> C.CDLL:
                        ("nano_hip_op_sample_batch_edit", [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
                        ("nano_hip_mask_table_set", [vp, C.c_void_p, C.c_uint32]),
                        ("nano_set_logit_edit", [vp, vp]),
-                       ("nano_forward_batch_sample_edit", [vp, u32p, u32p, C.c_uint32, vp, vp, vp, vp, vp])):
+                       ("nano_forward_batch_sample_edit", [vp, u32p, u32p, C.c_uint32, vp, vp, vp, vp, vp]),
+                       # KV images
+                       ("nano_hip_kv_image_plan", [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+                       ("nano_hip_kv_image_check", [vp, C.c_size_t, vp]),
+                       ("nano_hip_kv_save", [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+                       ("nano_hip_kv_restore", [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32]),
+                       ("nano_kv_save", [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+                       ("nano_kv_restore", [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32])):
         if hasattr(L, name) or not os.environ.get("NANO_LIB"):
             fn(name, C.c_int, args)
+    for name, args in (("nano_hip_kv_image_bytes", [vp, C.c_uint32]), ("nano_kv_image_bytes", [vp, C.c_uint32])):
+        if hasattr(L, name) or not os.environ.get("NANO_LIB"):
+            fn(name, C.c_size_t, args)
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     fn("nano_hip_set_fusion", C.c_int, [vp, C.c_uint32])
     fn("nano_hip_debug_fault", C.c_int, [vp, C.c_uint32])
@@ -335,6 +345,34 @@ def rows_pool_plan(segs, cap: int, max_seq_len: int, pooling="last"):
     rs, ro = (np.zeros(max(rows, 1), np.uint32) for _ in range(2))
     check(lib().nano_hip_rows_pool_plan(s.ctypes.data if s.size else None, s.shape[0], cap, max_seq_len, _pooling(pooling), rs.ctypes.data, ro.ctypes.data))
     return rs[:rows], ro[:rows]
+
+
+class NanoKvImageHeader(C.Structure):
+    """include/nano_mi355x.h NanoKvImageHeader: the 64-byte header of a KV image."""
+    _fields_ = [(n, C.c_uint32) for n in ("magic", "version", "header_bytes", "format", "n_layer", "kv_dim", "n_pos", "block_rows", "row_bytes",
+                                          "reserved0")] + [("payload_bytes", C.c_uint64), ("model_tag", C.c_uint64), ("reserved1", C.c_uint32 * 2)]
+
+
+assert C.sizeof(NanoKvImageHeader) == 64
+KV_IMAGE_PLAN_FIELDS = ("header_bytes", "payload_bytes", "total_bytes", "blocks", "last_rows", "block_stride", "vec_bytes", "_zero")
+KV_ALL = 0xFFFFFFFF                                                   # nano_hip_kv_restore's n_pos for "all of the image"
+
+
+def kv_image_plan(n_layer: int, kv_dim: int, elem_bytes: int, n_pos: int) -> dict:
+    """nano_hip_kv_image_plan (device-free): the sizes of the image of n_pos positions of a cache of n_layer layers, kv_dim elements per
+    row and elem_bytes (4 FP32, 2 FP16, 1 FP8) per element."""
+    out = np.zeros(len(KV_IMAGE_PLAN_FIELDS), np.uint64)
+    check(lib().nano_hip_kv_image_plan(n_layer, kv_dim, elem_bytes, n_pos, out.ctypes.data))
+    return {k: int(v) for k, v in zip(KV_IMAGE_PLAN_FIELDS, out)}
+
+
+def kv_image_check(image) -> dict:
+    """nano_hip_kv_image_check (device-free): the header's fields of a well-formed image (bytes-like or uint8 array); raises NanoHipError
+    with the library's message for anything else."""
+    a = np.ascontiguousarray(np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else image, np.uint8).reshape(-1)
+    h = NanoKvImageHeader()
+    check(lib().nano_hip_kv_image_check(a.ctypes.data if a.size else None, a.size, C.byref(h)))
+    return {n: (list(getattr(h, n)) if n == "reserved1" else int(getattr(h, n))) for n, _ in NanoKvImageHeader._fields_}
 
 
 def last_error() -> str:
@@ -772,6 +810,25 @@ class DeviceModel:
         a, b = C.c_uint32(0), C.c_uint64(0)
         check(lib().nano_hip_kv_sharing(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def kv_image_bytes(self, n_pos: int) -> int:
+        """the size of the KV image of n_pos positions of this model (nano_hip_kv_image_bytes)"""
+        return int(lib().nano_hip_kv_image_bytes(self.h, n_pos))
+
+    def kv_save(self, slot: int, n_pos: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """nano_hip_kv_save: the KV image of positions 0..n_pos-1 of `slot` as a uint8 array (64-byte header + the rows, block-major);
+        the slot is unchanged.  out: a contiguous uint8 array to write into (a view of its front is returned) instead of a new one."""
+        img = np.empty(max(self.kv_image_bytes(n_pos), 64), np.uint8) if out is None else out
+        assert img.dtype == np.uint8 and img.flags.c_contiguous
+        n = C.c_size_t(0)
+        check(lib().nano_hip_kv_save(self.h, slot, n_pos, img.ctypes.data, img.size, C.byref(n)))
+        return img[:n.value]
+
+    def kv_restore(self, slot: int, image, n_pos: Optional[int] = None):
+        """nano_hip_kv_restore: positions 0..n_pos-1 (None: all) of the image into `slot` of this model, which may be another model opened
+        from the same file than the one that saved it."""
+        a = np.ascontiguousarray(np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else image, np.uint8).reshape(-1)
+        check(lib().nano_hip_kv_restore(self.h, slot, a.ctypes.data if a.size else None, a.size, KV_ALL if n_pos is None else n_pos))
 
     def handoff_state(self):
         """(fusion bits in force, re-issues after a hand-off gave up, code bits of the last give-up)"""
@@ -1421,6 +1478,21 @@ class Engine:
         """nano_prefill_shared: ingest the prefix once per device and make it positions 0..len(prefix)-1 of sequences 0..batch-1."""
         t = np.ascontiguousarray(prefix, np.uint32).reshape(-1)
         check(self.L.nano_prefill_shared(self.ctx, t, t.size, batch))
+
+    def kv_image_bytes(self, n_pos: int) -> int:
+        return int(self.L.nano_kv_image_bytes(self.ctx, n_pos))
+
+    def kv_save(self, slot: int, n_pos: int) -> np.ndarray:
+        """nano_kv_save: the KV image of positions 0..n_pos-1 of `slot` of the context's device model (uint8 array)"""
+        img = np.empty(max(self.kv_image_bytes(n_pos), 64), np.uint8)
+        n = C.c_size_t(0)
+        check(self.L.nano_kv_save(self.ctx, slot, n_pos, img.ctypes.data, img.size, C.byref(n)))
+        return img[:n.value]
+
+    def kv_restore(self, slot: int, image, n_pos: Optional[int] = None):
+        """nano_kv_restore: positions 0..n_pos-1 (None: all) of the image into `slot` of the context's device model"""
+        a = np.ascontiguousarray(np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else image, np.uint8).reshape(-1)
+        check(self.L.nano_kv_restore(self.ctx, slot, a.ctypes.data if a.size else None, a.size, KV_ALL if n_pos is None else n_pos))
 
     def prefill_batch(self, prompts: Sequence[Sequence[int]], want_first_ids: bool = True) -> Optional[np.ndarray]:
         """nano_prefill_batch: sequence i ingests prompts[i] from position 0, all in one ragged step per device; returns first_ids

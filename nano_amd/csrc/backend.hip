@@ -74,6 +74,7 @@ static void destroy(NanoHipModel *m) {
     sampler_free(m->smp);
     lookup_free(m);
     rows_free(m);
+    kv_image_free(m);
     for (hipEvent_t ev : { m->ev0, m->ev1, m->ev2 }) if (ev) (void)hipEventDestroy(ev);
     if (m->st) (void)hipStreamDestroy(m->st);
     delete m;
@@ -125,6 +126,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     m->S = max_seq_len; m->maxB = max_batch; m->hd = hd; m->QD = QD; m->KD = KD;
     m->kv_half = (flags & NANO_HIP_KV_FP8) ? KV_FMT_FP8 : (flags & NANO_HIP_KV_F16) ? KV_FMT_F16 : KV_FMT_F32;
     m->kv.paged = (flags & NANO_HIP_KV_PAGED) != 0;
+    m->params_bytes = params_bytes;
     const uint8_t *src = reinterpret_cast<const uint8_t *>(params);
     const size_t L = d.n_layer, E = d.n_embd, H = d.n_hidden, V = d.vocab_size;
     const size_t each[WCOUNT] = { (size_t)QD * E, (size_t)KD * E, (size_t)KD * E, E * QD, H * E, E * H, H * E };

@@ -1,5 +1,5 @@
 // backend_kv.hip -- the KV cache as the host sees it: where its rows are, the paged cache (pages on demand, copy-on-write, release),
-// a prefix shared between slots (fork).
+// a prefix shared between slots (fork), a slot's rows in host memory and back (KV images: save / restore).
 #include "backend_model.h"
 
 // ---- where the KV cache's rows are (KvRows, backend_model.h) ----------------------------------------------------------------------------
@@ -242,4 +242,249 @@ extern "C" int nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_p
         p.rows.emplace_back(dst_slots[i], std::move(row));
     }
     return kv_apply(m, p, "the fork");
+}
+
+// ---- KV images: a slot's rows in host memory and back (kv_image.h the layout, kv_image.hip the kernel) ---------------------------
+// Host-only queries: no device call, no model state.
+extern "C" int nano_hip_kv_image_plan(uint32_t n_layer, uint32_t kv_dim, uint32_t elem_bytes, uint32_t n_pos, uint64_t *out) {
+    KvImagePlan p;
+    if (!out) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (!kvi_plan(n_layer, kv_dim, elem_bytes, n_pos, &p)) FAIL(NANO_HIP_EINVAL, "KV image plan: %u layers, kv_dim %u, %u-byte elements describe no cache (elements of 4, 2 or 1 bytes; kv_dim a multiple of 4)", n_layer, kv_dim, elem_bytes);
+    const uint64_t w[NANO_KV_IMAGE_PLAN_WORDS] = { KVI_HEADER_BYTES, p.payload_bytes, p.total_bytes, p.blocks, p.last_rows, p.block_stride, p.vec_bytes, 0 };
+    memcpy(out, w, sizeof w);
+    return 0;
+}
+extern "C" size_t nano_hip_kv_image_bytes(const NanoHipModel *m, uint32_t n_pos) {
+    KvImagePlan p;
+    return m && kvi_plan(m->d.n_layer, m->KD, (uint32_t)kv_esz(m), n_pos, &p) ? (size_t)p.total_bytes : 0;
+}
+extern "C" int nano_hip_kv_image_check(const void *image, size_t bytes, NanoKvImageHeader *out_header) {
+    char msg[320];
+    if (kvi_check(image, bytes, out_header, msg, sizeof msg)) FAIL(NANO_HIP_EINVAL, "%s", msg);
+    return 0;
+}
+
+// The transport.  A chunk is a whole number of 64-position blocks in image order; the device staging buffer and the pinned host buffer
+// each hold two, so the pack of one chunk (the model's stream) runs beside the copy of the previous one (kvi.cp) and the host's memcpy
+// of the one before, and unpack the same way round.  Chunk size, measured with tools/kv_park_probe.py on Qwen3-0.6B at 4095 positions
+// (profiles/kv_park.txt; NANO_KV_IMAGE_CHUNK_MB overrides the constant for such a run), save | restore, medians of 5:
+//   FP32 rows (939 MB; a block is 14.7 MB):  4 MiB 46.3 | 30.0 ms   16 MiB 46.0 | 30.5   64 MiB 46.5 | 33.9   256 MiB 49.7 | 33.5
+//   FP8 rows  (235 MB; a block is 3.7 MB):   4 MiB 12.5 |  9.1 ms   16 MiB 12.5 |  8.8   64 MiB 13.2 |  8.7   256 MiB 15.9 | 12.2
+// 4 .. 64 MiB are inside each other's spread, 256 MiB is slower (fewer chunks, less overlap): 16 MiB, the smallest staging memory among
+// the sizes that were not slower.  A chunk is never less than one block.
+constexpr size_t KVI_CHUNK_BYTES = (size_t)16 << 20;
+void kv_image_free(NanoHipModel *m) {
+    NanoHipModel::KvImageIo &io = m->kvi;
+    if (io.cp) (void)hipStreamSynchronize(io.cp);
+    if (io.dev) (void)hipFree(io.dev);
+    if (io.host) (void)hipHostFree(io.host);
+    if (io.jobs) (void)hipFree(io.jobs);
+    for (int h = 0; h < 2; h++) { if (io.staged[h]) (void)hipEventDestroy(io.staged[h]); if (io.freed[h]) (void)hipEventDestroy(io.freed[h]); }
+    if (io.cp) (void)hipStreamDestroy(io.cp);
+    io = NanoHipModel::KvImageIo{};
+}
+// the buffers, on first use; NANO_HIP_ENOMEM leaves none of them and the model as it was
+static int kv_image_io(NanoHipModel *m, const KvImagePlan &p) {
+    NanoHipModel::KvImageIo &io = m->kvi;
+    if (io.dev) return 0;
+    size_t target = KVI_CHUNK_BYTES;
+    if (const char *mb = getenv("NANO_KV_IMAGE_CHUNK_MB")) { const unsigned long v = strtoul(mb, nullptr, 0); if (v >= 1 && v <= 1024) target = (size_t)v << 20; }
+    const uint32_t all = (m->S + 63) / 64;                                  // blocks of a whole slot
+    uint64_t nb = target / p.block_stride;
+    if (nb < 1) nb = 1;
+    if (nb > all) nb = all;
+    const uint64_t half = nb * p.block_stride;
+    if (half > 0x7fffffffull) FAIL(NANO_HIP_EINVAL, "KV image: a block of %llu bytes is beyond the staging buffer's 32-bit offsets", (unsigned long long)p.block_stride);
+    bool ok = hipMalloc(reinterpret_cast<void **>(&io.dev), 2 * half) == hipSuccess && hipHostMalloc(reinterpret_cast<void **>(&io.host), 2 * half) == hipSuccess &&
+              hipStreamCreateWithFlags(&io.cp, hipStreamNonBlocking) == hipSuccess;
+    for (int h = 0; h < 2 && ok; h++)
+        ok = hipEventCreateWithFlags(&io.staged[h], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&io.freed[h], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        kv_image_free(m);
+        FAIL(NANO_HIP_ENOMEM, "KV image: staging buffers of 2 x %llu bytes on the device and in pinned host memory could not be allocated", (unsigned long long)half);
+    }
+    io.half = (size_t)half; io.chunk_blocks = (uint32_t)nb;
+    return 0;
+}
+// The jobs of every chunk of a call, chunk after chunk (chunk c's are jobs cstart[c] .. cstart[c + 1] - 1): row[b] = the cache row of
+// block b's first position (paged: the page-table entry, KV_NO_PAGE = none), or -- contiguous -- one job per chunk from base_row on.
+namespace {
+struct KvImageCall {
+    std::vector<KvImageJob> jobs; std::vector<uint32_t> cstart{0u};
+    uint32_t n_pos = 0, blocks = 0, chunk_blocks = 0;
+    uint32_t chunks() const { return (uint32_t)cstart.size() - 1u; }
+    uint32_t first_block(uint32_t c) const { return c * chunk_blocks; }
+    uint32_t rows_of(uint32_t c) const { const uint32_t r0 = first_block(c) * 64u, r1 = r0 + chunk_blocks * 64u; return (r1 < n_pos ? r1 : n_pos) - r0; }
+};
+}  // namespace
+static KvImageCall kv_image_jobs(const NanoHipModel *m, uint32_t n_pos, bool pack, uint64_t block_stride, uint32_t base_row, const uint32_t *row) {
+    KvImageCall c;
+    c.n_pos = n_pos; c.blocks = (n_pos + 63) / 64; c.chunk_blocks = m->kvi.chunk_blocks;
+    for (uint32_t b0 = 0; b0 < c.blocks; b0 += c.chunk_blocks) {
+        const uint32_t b1 = b0 + c.chunk_blocks < c.blocks ? b0 + c.chunk_blocks : c.blocks;
+        const uint32_t rows = (b1 * 64u < n_pos ? b1 * 64u : n_pos) - b0 * 64u;
+        if (!row) c.jobs.push_back(KvImageJob{ base_row + b0 * 64u, 0u, rows, 0u });
+        else
+            for (uint32_t b = b0; b < b1; b++) {
+                const uint32_t r = (b * 64u + 64u < n_pos ? b * 64u + 64u : n_pos) - b * 64u;
+                const bool none = row[b] == KV_NO_PAGE;
+                c.jobs.push_back(KvImageJob{ none ? 0u : row[b], (uint32_t)((b - b0) * block_stride), r, pack ? (none ? r : 0u) : 64u - r });
+            }
+        c.cstart.push_back((uint32_t)c.jobs.size());
+    }
+    return c;
+}
+// the call's job list to the device, on the model's stream (from a staging copy of its own, like the copy jobs of a fork)
+static int kv_image_upload(NanoHipModel *m, const KvImageCall &c) {
+    NanoHipModel::KvImageIo &io = m->kvi;
+    const size_t words = c.jobs.size() * 4;
+    if (words > io.jobs_cap) {
+        HIP_TRY(hipStreamSynchronize(m->st));                              // (a queued launch may still read the old list)
+        if (io.jobs) { (void)hipFree(io.jobs); io.jobs = nullptr; io.jobs_cap = 0; }
+        const size_t cap = words < 1024 ? 1024 : 2 * words;
+        if (hipMalloc(reinterpret_cast<void **>(&io.jobs), cap * 4) != hipSuccess) { (void)hipGetLastError(); FAIL(NANO_HIP_ENOMEM, "KV image: a job list of %zu bytes could not be allocated", cap * 4); }
+        io.jobs_cap = cap;
+    }
+    if (!words) return 0;
+    m->kv.pt_stage.emplace_back(words, 0u);
+    memcpy(m->kv.pt_stage.back().data(), c.jobs.data(), words * 4);
+    HIP_TRY(hipMemcpyAsync(io.jobs, m->kv.pt_stage.back().data(), words * 4, hipMemcpyHostToDevice, m->st));
+    return 0;
+}
+static hipError_t kv_image_launch(NanoHipModel *m, const KvImageCall &c, uint32_t chunk, int h, bool pack) {
+    KvImageArgs a{};
+    a.k = m->kcache; a.v = m->vcache; a.staging = m->kvi.dev + (size_t)h * m->kvi.half;
+    a.row_bytes = (uint32_t)(m->KD * kv_esz(m)); a.n_layer = m->d.n_layer;
+    a.plane_bytes = (uint64_t)(m->kv.paged ? (size_t)m->kv.pages * 64 : m->S) * a.row_bytes;
+    a.n_jobs = c.cstart[chunk + 1] - c.cstart[chunk];
+    a.job_blocks = m->kv.paged ? 1u : (c.rows_of(chunk) + 63u) / 64u;
+    a.jobs = reinterpret_cast<const KvImageJob *>(m->kvi.jobs) + c.cstart[chunk];
+    return launch_kv_image(a, pack, (uint32_t)m->cus, m->st);
+}
+static int kv_image_slot_check(const NanoHipModel *m, uint32_t slot) {
+    if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "slot %u out of range (max_batch %u)", slot, m->maxB);
+    if (!m->kv.paged && (uint64_t)m->maxB * m->d.n_layer * m->S > 0xffffffffull)
+        FAIL(NANO_HIP_EINVAL, "cache of %u slots x %u rows is beyond the image kernel's 32-bit row index", m->maxB, m->d.n_layer * m->S);
+    return 0;
+}
+
+extern "C" int nano_hip_kv_save(NanoHipModel *m, uint32_t slot, uint32_t n_pos, void *image, size_t cap, size_t *bytes) {
+    if (!m || !image || !bytes) FAIL(NANO_HIP_EINVAL, "null argument");
+    if (const int rc = kv_image_slot_check(m, slot)) return rc;
+    if (n_pos > m->S) FAIL(NANO_HIP_EINVAL, "%u positions exceed max_seq_len %u", n_pos, m->S);
+    KvImagePlan p;
+    if (!kvi_plan(m->d.n_layer, m->KD, (uint32_t)kv_esz(m), n_pos, &p)) FAIL(NANO_HIP_EINVAL, "the model's cache has no image (kv_dim %u)", m->KD);
+    *bytes = (size_t)p.total_bytes;
+    if (cap < p.total_bytes) FAIL(NANO_HIP_EINVAL, "KV image of %u positions needs %llu bytes, the buffer has %zu", n_pos, (unsigned long long)p.total_bytes, cap);
+    HIP_TRY(hipSetDevice(m->device));
+    NanoKvImageHeader hd;
+    kvi_header(&hd, m->kv_half, m->d.n_layer, m->KD, n_pos, kvi_model_tag(m->d, m->params_bytes), p);
+    uint8_t *out = static_cast<uint8_t *>(image);
+    if (n_pos) {
+        if (const int rc = kv_image_io(m, p)) return rc;
+        NanoHipModel::KvImageIo &io = m->kvi;
+        const KvImageCall c = kv_image_jobs(m, n_pos, true, p.block_stride, slot * m->d.n_layer * m->S, m->kv.paged ? m->kv.h_pt + (size_t)slot * m->kv.pt_stride : nullptr);
+        if (const int rc = kv_image_upload(m, c)) return rc;
+        auto chunk_bytes = [&](uint32_t ch) { return (size_t)c.rows_of(ch) * m->d.n_layer * 2 * p.row_bytes; };
+        // a failure past this point waits for what was queued (the caller's buffer and the pinned halves must not be written behind its back)
+        hipError_t e = hipSuccess;
+        auto drain = [&](uint32_t ch) {
+            const int h = (int)(ch & 1u);
+            if ((e = hipEventSynchronize(io.freed[h])) != hipSuccess) return;
+            memcpy(out + KVI_HEADER_BYTES + (size_t)c.first_block(ch) * p.block_stride, io.host + (size_t)h * io.half, chunk_bytes(ch));
+        };
+        for (uint32_t ch = 0; ch < c.chunks() && e == hipSuccess; ch++) {
+            const int h = (int)(ch & 1u);
+            if ((e = hipStreamWaitEvent(m->st, io.freed[h], 0)) != hipSuccess) break;          // the half's earlier chunk has been copied out
+            if ((e = kv_image_launch(m, c, ch, h, true)) != hipSuccess) break;
+            if ((e = hipEventRecord(io.staged[h], m->st)) != hipSuccess) break;
+            if ((e = hipStreamWaitEvent(io.cp, io.staged[h], 0)) != hipSuccess) break;
+            if ((e = hipMemcpyAsync(io.host + (size_t)h * io.half, io.dev + (size_t)h * io.half, chunk_bytes(ch), hipMemcpyDeviceToHost, io.cp)) != hipSuccess) break;
+            if ((e = hipEventRecord(io.freed[h], io.cp)) != hipSuccess) break;
+            if (ch) drain(ch - 1);                                         // ... while this chunk is packed and copied
+        }
+        if (e == hipSuccess) drain(c.chunks() - 1);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(m->st); (void)hipStreamSynchronize(io.cp);
+            FAIL(NANO_HIP_ERUNTIME, "KV image: saving slot %u failed: %s", slot, hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(m->st));                                 // (n_pos == 0 too: the call runs behind everything queued)
+    memcpy(out, &hd, sizeof hd);
+    return kv_stage_trim(m);
+}
+
+extern "C" int nano_hip_kv_restore(NanoHipModel *m, uint32_t slot, const void *image, size_t bytes, uint32_t n_pos) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "null argument");
+    NanoKvImageHeader hd;
+    if (const int rc = nano_hip_kv_image_check(image, bytes, &hd)) return rc;
+    if (const int rc = kv_image_slot_check(m, slot)) return rc;
+    if (n_pos == 0xffffffffu) n_pos = hd.n_pos;
+    if (n_pos > hd.n_pos) FAIL(NANO_HIP_EINVAL, "%u positions asked of a KV image of %u", n_pos, hd.n_pos);
+    if (n_pos > m->S) FAIL(NANO_HIP_EINVAL, "%u positions exceed max_seq_len %u", n_pos, m->S);
+    if (hd.format != m->kv_half) FAIL(NANO_HIP_EINVAL, "KV image of element format %u, the model's cache has format %u (0 FP32, 1 FP16, 2 FP8; formats are not converted)", hd.format, m->kv_half);
+    if (hd.n_layer != m->d.n_layer || hd.kv_dim != m->KD) FAIL(NANO_HIP_EINVAL, "KV image of %u layers x kv_dim %u, the model has %u x %u", hd.n_layer, hd.kv_dim, m->d.n_layer, m->KD);
+    if (hd.model_tag != kvi_model_tag(m->d, m->params_bytes)) FAIL(NANO_HIP_EINVAL, "KV image with model tag %016llx, this model's is %016llx (another model file)", (unsigned long long)hd.model_tag, (unsigned long long)kvi_model_tag(m->d, m->params_bytes));
+    HIP_TRY(hipSetDevice(m->device));
+    KvImagePlan p, pi;                                                     // of the n_pos positions restored | of the image
+    kvi_plan(hd.n_layer, hd.kv_dim, (uint32_t)kv_esz(m), n_pos, &p);
+    kvi_plan(hd.n_layer, hd.kv_dim, (uint32_t)kv_esz(m), hd.n_pos, &pi);
+    // paged: the slot's new table row, planned before anything is queued (the fork's rule for a destination)
+    KvPlan plan;
+    std::vector<uint32_t> row;
+    if (m->kv.paged) {
+        const uint32_t P = m->kv.pt_stride;
+        std::map<uint32_t, uint32_t> leaving;
+        plan.free_pages = m->kv.free_pages;
+        for (uint32_t blk = 0; blk < P; blk++) {
+            const uint32_t e = m->kv.h_pt[(size_t)slot * P + blk];
+            if (e != KV_NO_PAGE && ++leaving[e / 64u] == m->kv.page_owners[e / 64u]) plan.free_pages.push_back(e / 64u);
+        }
+        if (p.blocks > plan.free_pages.size())
+            FAIL(NANO_HIP_ENOMEM, "paged KV cache: restoring %u positions needs %u pages, %zu available (%zu free + the slot's own) of %u (nano_hip_kv_release() returns a finished sequence's pages)",
+                 n_pos, p.blocks, plan.free_pages.size(), m->kv.free_pages.size(), m->kv.pages);
+        for (const auto &lv : leaving) plan.owners.emplace_back(lv.first, -(int32_t)lv.second);
+        row.assign(P, KV_NO_PAGE);
+        for (uint32_t blk = 0; blk < p.blocks; blk++) {
+            const uint32_t page = plan.free_pages.back(); plan.free_pages.pop_back();
+            row[blk] = page * 64u;
+            plan.owners.emplace_back(page, 1);
+        }
+        plan.rows.emplace_back(slot, row);
+    }
+    if (n_pos) {
+        if (const int rc = kv_image_io(m, p)) return rc;
+        NanoHipModel::KvImageIo &io = m->kvi;
+        const KvImageCall c = kv_image_jobs(m, n_pos, false, p.block_stride, slot * m->d.n_layer * m->S, m->kv.paged ? row.data() : nullptr);
+        if (const int rc = kv_image_upload(m, c)) return rc;
+        const uint8_t *in = static_cast<const uint8_t *>(image);
+        const uint32_t img_rows_cut = p.blocks == pi.blocks ? pi.last_rows : 64u;      // rows per run, in the image, of the block the restore ends in
+        hipError_t e = hipSuccess;
+        for (uint32_t ch = 0; ch < c.chunks() && e == hipSuccess; ch++) {
+            const int h = (int)(ch & 1u);
+            if ((e = hipEventSynchronize(io.staged[h])) != hipSuccess) break;                   // the pinned half's earlier chunk is on the device
+            uint8_t *pin = io.host + (size_t)h * io.half;
+            const uint32_t b0 = c.first_block(ch), rows = c.rows_of(ch), nfull = rows / 64u, part = rows % 64u;
+            const size_t chunk_bytes = (size_t)rows * m->d.n_layer * 2 * p.row_bytes;
+            // whole blocks are a byte range of the image; a partial last block is one too unless the image's block holds more rows (the row cut)
+            const bool cut = part && img_rows_cut != part;
+            memcpy(pin, in + KVI_HEADER_BYTES + (size_t)b0 * p.block_stride, cut ? (size_t)nfull * p.block_stride : chunk_bytes);
+            if (cut)
+                for (uint32_t run = 0; run < m->d.n_layer * 2u; run++)
+                    memcpy(pin + (size_t)nfull * p.block_stride + (size_t)run * part * p.row_bytes,
+                           in + kvi_offset(pi, b0 + nfull, img_rows_cut, run / 2u, run % 2u, 0), (size_t)part * p.row_bytes);
+            if ((e = hipStreamWaitEvent(io.cp, io.freed[h], 0)) != hipSuccess) break;           // the device half's earlier chunk has been unpacked
+            if ((e = hipMemcpyAsync(io.dev + (size_t)h * io.half, pin, chunk_bytes, hipMemcpyHostToDevice, io.cp)) != hipSuccess) break;
+            if ((e = hipEventRecord(io.staged[h], io.cp)) != hipSuccess) break;
+            if ((e = hipStreamWaitEvent(m->st, io.staged[h], 0)) != hipSuccess) break;
+            if ((e = kv_image_launch(m, c, ch, h, false)) != hipSuccess) break;
+            e = hipEventRecord(io.freed[h], m->st);
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(io.cp); (void)hipStreamSynchronize(m->st);
+            FAIL(NANO_HIP_ERUNTIME, "KV image: queueing the restore into slot %u failed: %s (nothing committed)", slot, hipGetErrorString(e));
+        }
+    }
+    return kv_apply(m, plan, "the restore");
 }

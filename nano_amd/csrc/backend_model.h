@@ -3,7 +3,7 @@
 // call; what one step is travels as a StepSpec value (step_spec.h, with the graph key built from it), never as fields set around a call.
 //   backend.hip          create / destroy / layout, the forward / prefill / greedy entry points, the sticky error word and the re-issue policy
 //   backend_step.hip     the argument builders, the fast step, the reference-order step, graphs, run_step, the strict / exact switches
-//   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release
+//   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release, KV images (save / restore)
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
 //   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
 //   backend_rows.hip     what calls get back per fed row (RowWant: the scratch, the sink, the decode-step entry) and ragged steps
@@ -22,6 +22,7 @@
 #include <hip/hip_fp16.h>
 #include "../../include/nano_mi355x.h"
 #include "kernels.h"
+#include "kv_image.h"
 #include "pool_plan.h"
 #include "step_spec.h"
 
@@ -176,6 +177,16 @@ struct NanoHipModel {
         unsigned long long *buf = nullptr; uint32_t launches = 0; bool on = false;
         std::vector<uint32_t> kinds;
     } stamp;
+    // KV images (nano_hip_kv_save / _restore, backend_kv.hip): the transport between the cache and host memory, allocated on the first call
+    struct KvImageIo {
+        uint8_t *dev = nullptr, *host = nullptr;          // device staging | pinned host memory: two halves of `half` bytes each, a half holds one chunk in image order
+        size_t half = 0; uint32_t chunk_blocks = 0;       // bytes of a half = chunk_blocks whole 64-position blocks
+        hipStream_t cp = nullptr;                         // the copies between dev and host run here, beside the pack / unpack launches on the model's stream
+        hipEvent_t staged[2] = {nullptr, nullptr};        // device half h holds its chunk (save: packed, on the model's stream; restore: copied in, on cp)
+        hipEvent_t freed[2] = {nullptr, nullptr};         // ... has been consumed (save: copied out, on cp; restore: unpacked, on the model's stream)
+        uint32_t *jobs = nullptr; size_t jobs_cap = 0;    // the device job list of the call being queued (capacity in 32-bit words)
+    } kvi;
+    uint64_t params_bytes = 0;                            // what create was given: a word of the KV image's model tag (kv_image.h)
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -298,6 +309,7 @@ struct KvRows {
 };
 int kv_ensure(NanoHipModel *m, const uint32_t *slots, const uint32_t *first, const uint32_t *need, uint32_t n);
 int kv_ensure_batch(NanoHipModel *m, const uint32_t *pos, uint32_t batch, uint32_t extra, bool whole_context);
+void kv_image_free(NanoHipModel *m);                   // the transport of nano_hip_kv_save / _restore
 void sampler_free(Sampler *sp);                        // backend_sampler.hip
 
 // ---- backend_step.hip ----

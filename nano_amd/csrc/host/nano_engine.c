@@ -653,6 +653,23 @@ int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t 
     return NANO_HIP_OK;
 }
 
+/* KV images on the context's device model (nano_mi355x.h).  A replicated context is refused: sequence i lives on replica i mod G. */
+size_t nano_kv_image_bytes(Nano_Context *ctx, uint32_t n_pos) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    return me && me->dev ? nano_hip_kv_image_bytes(me->dev, n_pos) : 0;
+}
+int nano_kv_save(Nano_Context *ctx, uint32_t slot, uint32_t n_pos, void *buf, size_t cap, size_t *bytes) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev || me->n_replica > 1) return NANO_HIP_EINVAL;      /* (replica[0] is the own device) */
+    return nano_hip_kv_save(me->dev, slot, n_pos, buf, cap, bytes);
+}
+int nano_kv_restore(Nano_Context *ctx, uint32_t slot, const void *buf, size_t bytes, uint32_t n_pos) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    la_clear(me);                                          /* ids a lookup chunk confirmed ahead belong to the rows that leave */
+    if (!me || !me->dev || me->n_replica > 1) return NANO_HIP_EINVAL;      /* (replica[0] is the own device) */
+    return nano_hip_kv_restore(me->dev, slot, buf, bytes, n_pos);
+}
+
 /* `batch` prompts at once: each replica gets the prompts of its share (sequence i in slot i / G of replica i mod G, as in
  * nano_forward_batch) as the segments of ONE ragged step, and the arg-max behind each prompt's last row becomes first_ids[i]. */
 int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const uint32_t *n_tokens, uint32_t batch, uint32_t *first_ids) {

@@ -493,6 +493,23 @@ struct KvCopyArgs {
 };
 hipError_t launch_kv_copy(KvCopyArgs a, uint32_t n_layer, uint32_t max_rows, uint32_t cus, bool nt_stores, hipStream_t st);
 
+// ---- KV images (kv_image.hip): a slot's rows to / from a staging buffer in image order (kv_image.h) ----
+// A job starts at a 64-position block boundary and covers `rows` positions: cache rows cache_row .. (counted inside a layer plane, the
+// slot's base folded in) on one side, the blocks at staging_off .. on the other -- block i of the job at staging_off + i * 64 * n_layer
+// * 2 * row_bytes, its runs holding min(64, rows - 64 i) rows each.  Pack (cache -> staging): the job's trailing zero_rows rows are not
+// read but staged as zero (a block the slot has not mapped: zero_rows == rows, cache_row is not used).  Unpack (staging -> cache): the
+// zero_rows cache rows behind the job's `rows` are written as zero (the rest of a partial last page).  job_blocks: blocks of the
+// longest job (contiguous cache: one job per staging chunk; paged: one job per block).
+struct KvImageJob { uint32_t cache_row, staging_off, rows, zero_rows; };
+struct KvImageArgs {
+    void *k, *v, *staging;
+    uint64_t plane_bytes;
+    uint32_t row_bytes, n_layer;
+    uint32_t n_jobs, job_blocks, cx, _pad;       // cx: workgroups per block and plane (set by the launcher)
+    const KvImageJob *jobs;                      // device memory
+};
+hipError_t launch_kv_image(KvImageArgs a, bool pack, uint32_t cus, hipStream_t st);
+
 // ---- device-side sampler (sampler.hip) ----
 constexpr uint32_t SAMPLE_CHUNK = 256;            // softmax numerators per chunk function (one wave x float4)
 constexpr uint32_t SAMPLE_MAX_CHUNKS = 1024;      // vocabularies up to 262144
