@@ -255,6 +255,23 @@ int nano_prefill_shared(Nano_Context *ctx, const uint32_t *prefix_ids, uint32_t 
 size_t nano_kv_image_bytes(Nano_Context *ctx, uint32_t n_pos);
 int nano_kv_save(Nano_Context *ctx, uint32_t slot, uint32_t n_pos, void *buf, size_t cap, size_t *bytes);
 int nano_kv_restore(Nano_Context *ctx, uint32_t slot, const void *buf, size_t bytes, uint32_t n_pos);
+/* LoRA table (nano_mi355x.h, "LoRA table"): several modules of one base model resident at once and a binding sequence -> module, so that
+ * one nano_forward_batch* step (or nano_prefill_shared, nano_forward_batch_sample*, nano_forward_batch_topk) serves sequences with
+ * different adapters from ONE read of the base weights.  nano_lora_table_load reads a module file of load_lora's format into entry id (<
+ * 64) and applies load_lora's check that the module fits the base model; _from_buffer takes the file's bytes (copied: the buffer may go).
+ * nano_lora_table_free empties an entry (refused while a slot is bound to it).  nano_lora_bind: slots[i] -- sequence i of
+ * nano_forward_batch lives in slot i, a session in slot 0 -- takes entry ids[i], or none (0xffffffff, NANO_LORA_NONE).  Bind a slot
+ * before its sequence's first token and keep the binding while the sequence lives: its K / V rows carry that module's deltas.
+ * The reference's load_lora / free_lora / llm_forward(..., lora) keep their single-module meaning and do not mix with a table: on a
+ * model with a loaded module the table calls return NANO_HIP_EINVAL, and load_lora on a model with a table fails as every load_lora
+ * failure does.  llm_forward with lora = NULL on a model with a table applies slot 0's binding.  Not offered: replicas (with replicas
+ * attached the table calls return NANO_HIP_EINVAL, and nano_context_replicate refuses a context with a table), the ragged calls
+ * (nano_prefill_batch, nano_embed_batch: NANO_HIP_EINVAL as with a module), Qwen architectures.  Returns 0 or a NANO_HIP_E* code: an
+ * unreadable file and a module that does not fit are NANO_HIP_EINVAL. */
+int nano_lora_table_load(Nano_Context *ctx, uint32_t id, const char *path);
+int nano_lora_table_load_from_buffer(Nano_Context *ctx, uint32_t id, const uint8_t *buffer, size_t bytes);
+int nano_lora_table_free(Nano_Context *ctx, uint32_t id);
+int nano_lora_bind(Nano_Context *ctx, const uint32_t *slots, const uint32_t *ids, uint32_t n);
 /* Ingest `batch` prompts at once: sequence i (the sequences nano_forward_batch addresses) takes prompts[i][0..n_tokens[i]) from position
  * 0, and first_ids[i] (optional, batch words) is the arg-max behind its last token -- the first id of a greedy continuation (an empty
  * prompt leaves first_ids[i] untouched).  One ragged step per device (nano_hip_step_rows, nano_mi355x.h): the prompts share the weight

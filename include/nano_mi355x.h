@@ -126,7 +126,9 @@ int  nano_hip_kv_pages(const NanoHipModel *m, uint32_t *in_use, uint32_t *total)
  * NANO_HIP_EINVAL: null model / list, a slot >= max_batch, n_pos > max_seq_len, the source or a duplicate in dst_slots.
  * n_pos == 0 is valid (paged: the destinations end up empty).  NANO_HIP_ENOMEM: the pool cannot supply the partial-block pages
  * from its free pages plus the pages only the destinations own; nothing has changed then.  The work is queued on the model's
- * stream behind what is already there.  The reference has no counterpart (one cache per context, infer/infer.c:46-51). */
+ * stream behind what is already there.  The reference has no counterpart (one cache per context, infer/infer.c:46-51).
+ * With a LoRA table (below) a fork that copies rows also binds every destination to the source slot's entry: the rows carry that
+ * module's deltas. */
 int  nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_pos, const uint32_t *dst_slots, uint32_t n_dst);
 /* paged models: pages that currently have more than one owner; page copies made so far because a slot wrote into a page it
  * shared (copy-on-write), since the model was created.  NANO_HIP_EINVAL on a model without NANO_HIP_KV_PAGED. */
@@ -189,7 +191,9 @@ int    nano_hip_kv_image_check(const void *image, size_t bytes, NanoKvImageHeade
  * queued: NANO_HIP_ENOMEM (pool, or staging buffers) leaves tables, owner counts and contents as they were.
  * NANO_HIP_EINVAL, before anything is queued: whatever nano_hip_kv_image_check refuses, slot >= max_batch, n_pos beyond the image or
  * max_seq_len, an element format, n_layer, kv_dim or model tag that is not the model's.
- * Neither touches the sampler's per-slot records or the lookup loop's history: those are keyed by the caller's history. */
+ * Neither touches the sampler's per-slot records or the lookup loop's history: those are keyed by the caller's history.
+ * Neither touches the slot's LoRA table binding (nano_hip_lora_bind): an image does not know the adapter its rows were written
+ * under, so the caller binds the slot as it was when the image was saved before stepping it. */
 int  nano_hip_kv_save(NanoHipModel *m, uint32_t slot, uint32_t n_pos, void *image, size_t cap, size_t *bytes);
 int  nano_hip_kv_restore(NanoHipModel *m, uint32_t slot, const void *image, size_t bytes, uint32_t n_pos);
 /* number of parameter-blob bytes the backend expects for `desc` (0 if it cannot be derived
@@ -452,6 +456,38 @@ int nano_hip_op_pool_rows(int device, const float *x, uint32_t rows, uint32_t n_
  * Replaces: load_lora / parse_lora_file's device side and the use_lora branches of transformer_block_forward. */
 int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats);
 int nano_hip_lora_enable(NanoHipModel *m, int on);
+
+/* LoRA table: up to NANO_LORA_TABLE_MAX modules resident on the device and a binding KV slot -> entry.  Every step that runs the LoRA
+ * launches then applies to each row the module of that row's slot (slot0 + b in a decode step, the chunk's slot for every row of a prefill /
+ * scoring / verify chunk), or none: one base model, one weight read per step, each running sequence with its own adapter.  The binding
+ * belongs to the slot, not to a call: the slot's K / V rows carry that module's deltas for as long as the sequence lives.
+ *   nano_hip_lora_param_floats  floats of a module's parameter block (what follows a module file's 256-byte header): device-free.
+ *   nano_hip_lora_table_set     stores `params` (layout and meaning as nano_hip_lora_attach) as entry id and switches the table on.
+ *                               Overwriting an entry is allowed while no slot is bound to it.
+ *   nano_hip_lora_table_clear   empties an entry; NANO_HIP_EINVAL while a slot is bound to it.  An empty table is no table.
+ *   nano_hip_lora_bind          slots[i] takes entry ids[i], or none (NANO_LORA_NONE).  A small upload: captured graphs read the
+ *                               bindings when they replay and are kept.  (Storing or clearing an entry and switching the table on or
+ *                               off drop the graphs.)
+ *   nano_hip_lora_binding       *id_out = the entry of `slot`, or NANO_LORA_NONE.
+ * A row with module i is bit for bit what a model with module i attached (nano_hip_lora_attach) gives that row; a row without a module
+ * keeps q, k and v as the projections left them and adds -0.0f in Wo's epilogue, which changes no bit.  A model with a stored, enabled
+ * table is a model "with LoRA on" wherever this header says so: one attention split, the gates of nano_hip_lora_attach.
+ * nano_hip_lora_enable switches whichever is present.  nano_hip_kv_fork copies the source slot's binding to its destinations;
+ * nano_hip_kv_restore leaves bindings alone (an image does not know its adapter: bind the slot before stepping it).
+ * NANO_HIP_EINVAL before anything is allocated or queued, the model unchanged: a null pointer, an id >= NANO_LORA_TABLE_MAX, a slot >=
+ * max_batch, a bind to an empty entry, a slot named twice in one call, an architecture other than Nano, a rank the launches cannot run
+ * (as nano_hip_lora_attach), a parameter block shorter than nano_hip_lora_param_floats, a set or clear of a bound entry, and a table
+ * call on a model with an attached module (nano_hip_lora_attach on a model with a stored entry likewise).
+ * Not offered: LoRA for the Qwen architectures (the reference has none); a table on the FP16, FP8 or paged cache, in strict or exact
+ * mode, in ragged steps or pooling; more than one attention split with a module on; adapters in quantized form; bindings inside KV
+ * images. */
+#define NANO_LORA_TABLE_MAX 64u
+#define NANO_LORA_NONE      0xffffffffu
+size_t nano_hip_lora_param_floats(uint32_t n_layer, uint32_t n_embd, uint32_t kv_dim, uint32_t rank);
+int nano_hip_lora_table_set(NanoHipModel *m, uint32_t id, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats);
+int nano_hip_lora_table_clear(NanoHipModel *m, uint32_t id);
+int nano_hip_lora_bind(NanoHipModel *m, const uint32_t *slots, const uint32_t *ids, uint32_t n);
+int nano_hip_lora_binding(const NanoHipModel *m, uint32_t slot, uint32_t *id_out);
 
 /* ---- device-side sampling ------------------------------------------------------------------
  * One decode step of sequence slot 0 followed by the reference's sampler, run on the device: repetition penalty over
@@ -789,6 +825,30 @@ typedef struct NanoLoraOpDesc {
 } NanoLoraOpDesc;
 int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d);
 int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d);
+/* The per-row forms of the two launches (a LoRA table: each row takes the module of its KV slot, or none), one launch on caller arrays:
+ * the fields of NanoLoraOpDesc that do not depend on the module, n_adapters adapters {rank, alpha, a[3], b[3]} (o: a[0] / b[0] = the o
+ * pair), and row_adapter[nb] = each row's adapter or NANO_LORA_NONE.  A row without an adapter: nano_hip_op_lora_qkv_rows leaves its q,
+ * kraw and v rows untouched, nano_hip_op_lora_o_rows stores -0.0f into its row of q.  The launch's LDS is sized by the largest rank.
+ * Refused before any launch, before a device is asked for (NANO_HIP_EINVAL): what the operators above refuse (each adapter's rank), n_adapters
+ * of 0 or above NANO_LORA_TABLE_MAX, a null adapters / row_adapter, a row_adapter entry that is neither an adapter nor
+ * NANO_LORA_NONE.  No host path: without a device NANO_HIP_ENODEV. */
+typedef struct NanoLoraAdapter {
+    uint32_t rank, alpha;
+    const float *a[3], *b[3];
+} NanoLoraAdapter;
+typedef struct NanoLoraRowsOpDesc {
+    uint32_t E, KD, nb, S;
+    uint32_t v_bstride, n_adapters;
+    const float *x;             /* [nb][E] */
+    const float *norm_w;        /* qkv: [E] */
+    const NanoLoraAdapter *adapters;    /* [n_adapters] */
+    const uint32_t *row_adapter;        /* [nb] */
+    const uint32_t *pos;        /* qkv: [nb] */
+    float *q, *kraw, *v;        /* in-place targets (o: q alone, overwritten) */
+    uint64_t q_floats, k_floats, v_floats;
+} NanoLoraRowsOpDesc;
+int nano_hip_op_lora_qkv_rows(int device, const NanoLoraRowsOpDesc *d);
+int nano_hip_op_lora_o_rows(int device, const NanoLoraRowsOpDesc *d);
 /* The FP32 launch the router issues for descriptor d (quant = NANO_QUANT_F32), from the functions the launcher and the router follow:
  * out = {role, B, nv, upw, rw, nw, grid, lds_bytes, launches, seqs_per_launch, takes, 0} -- gemv_f32_slab_kernel<role, B, nv, upw> on
  * nw waves x grid workgroups owning rw rows each, of the first of `launches` slices of seqs_per_launch sequences.  takes = 0: the

@@ -46,6 +46,22 @@ class NanoLoraOpDesc(C.Structure):
                 ("q", C.c_void_p), ("kraw", C.c_void_p), ("v", C.c_void_p), ("q_floats", C.c_uint64), ("k_floats", C.c_uint64), ("v_floats", C.c_uint64)]
 
 
+NANO_LORA_TABLE_MAX = 64
+NANO_LORA_NONE = 0xffffffff
+
+
+class NanoLoraAdapter(C.Structure):
+    """include/nano_mi355x.h NanoLoraAdapter: one adapter of a per-row LoRA launch."""
+    _fields_ = [("rank", C.c_uint32), ("alpha", C.c_uint32), ("a", C.c_void_p * 3), ("b", C.c_void_p * 3)]
+
+
+class NanoLoraRowsOpDesc(C.Structure):
+    """include/nano_mi355x.h NanoLoraRowsOpDesc: one per-row LoRA side-branch launch (q | k | v, or o) as a step with a LoRA table issues it."""
+    _fields_ = [(n, C.c_uint32) for n in ("E", "KD", "nb", "S", "v_bstride", "n_adapters")] + \
+               [("x", C.c_void_p), ("norm_w", C.c_void_p), ("adapters", C.POINTER(NanoLoraAdapter)), ("row_adapter", C.c_void_p), ("pos", C.c_void_p),
+                ("q", C.c_void_p), ("kraw", C.c_void_p), ("v", C.c_void_p), ("q_floats", C.c_uint64), ("k_floats", C.c_uint64), ("v_floats", C.c_uint64)]
+
+
 class NanoAttnDecodeDesc(C.Structure):
     """include/nano_mi355x.h NanoAttnDecodeDesc: one decode attention launch (or a prefill chunk's two passes) as a step issues it."""
     _fields_ = [(n, C.c_uint32) for n in ("nb", "n_head", "n_kv_head", "hd", "n_layer", "layer", "S", "range_hint", "nsplit", "rope_qwen3",
@@ -295,10 +311,22 @@ def lib() -> C.CDLL:
                        ("nano_hip_kv_save", [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
                        ("nano_hip_kv_restore", [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32]),
                        ("nano_kv_save", [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-                       ("nano_kv_restore", [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32])):
+                       ("nano_kv_restore", [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32]),
+                       # LoRA table
+                       ("nano_hip_lora_table_set", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t]),
+                       ("nano_hip_lora_table_clear", [vp, C.c_uint32]),
+                       ("nano_hip_lora_bind", [vp, vp, vp, C.c_uint32]),
+                       ("nano_hip_lora_binding", [vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+                       ("nano_hip_op_lora_qkv_rows", [C.c_int, C.POINTER(NanoLoraRowsOpDesc)]),
+                       ("nano_hip_op_lora_o_rows", [C.c_int, C.POINTER(NanoLoraRowsOpDesc)]),
+                       ("nano_lora_table_load", [vp, C.c_uint32, C.c_char_p]),
+                       ("nano_lora_table_load_from_buffer", [vp, C.c_uint32, vp, C.c_size_t]),
+                       ("nano_lora_table_free", [vp, C.c_uint32]),
+                       ("nano_lora_bind", [vp, vp, vp, C.c_uint32])):
         if hasattr(L, name) or not os.environ.get("NANO_LIB"):
             fn(name, C.c_int, args)
-    for name, args in (("nano_hip_kv_image_bytes", [vp, C.c_uint32]), ("nano_kv_image_bytes", [vp, C.c_uint32])):
+    for name, args in (("nano_hip_kv_image_bytes", [vp, C.c_uint32]), ("nano_kv_image_bytes", [vp, C.c_uint32]),
+                       ("nano_hip_lora_param_floats", [C.c_uint32] * 4)):
         if hasattr(L, name) or not os.environ.get("NANO_LIB"):
             fn(name, C.c_size_t, args)
     fn("nano_hip_handoff_state", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
@@ -750,6 +778,29 @@ class DeviceModel:
     def lora_enable(self, on: bool):
         check(lib().nano_hip_lora_enable(self.h, 1 if on else 0))
 
+    def lora_table_set_file(self, id: int, path: str):
+        """Store a LoRA module file (format as lora_attach_file) as entry `id` of the model's LoRA table (nano_hip_lora_table_set)."""
+        raw = np.fromfile(path, dtype=np.uint8)
+        hdr = raw[:256].view(np.uint32)
+        params = np.ascontiguousarray(raw[256:].view(np.float32))
+        check(lib().nano_hip_lora_table_set(self.h, id, int(hdr[6]), int(hdr[7]), params.ctypes.data, params.size))
+
+    def lora_table_clear(self, id: int):
+        check(lib().nano_hip_lora_table_clear(self.h, id))
+
+    def lora_bind(self, slots, ids):
+        """KV slot slots[i] takes table entry ids[i]; None (or NANO_LORA_NONE) = no module (nano_hip_lora_bind)."""
+        s = np.ascontiguousarray(slots, np.uint32)
+        i = np.ascontiguousarray([NANO_LORA_NONE if v is None else v for v in ids], np.uint32)
+        assert s.ndim == 1 and s.shape == i.shape
+        check(lib().nano_hip_lora_bind(self.h, s.ctypes.data, i.ctypes.data, s.size))
+
+    def lora_binding(self, slot: int):
+        """the table entry `slot` is bound to, or None"""
+        out = C.c_uint32(0)
+        check(lib().nano_hip_lora_binding(self.h, slot, C.byref(out)))
+        return None if out.value == NANO_LORA_NONE else int(out.value)
+
     def sync(self):
         check(lib().nano_hip_sync(self.h))
 
@@ -1093,6 +1144,55 @@ def op_lora_o(xba, pair, o1, *, rank, alpha, device=0):
     d, _ = _lora_desc(xba.shape[-1], 0, rank, alpha, xba, (pair,), keep)
     d.q, d.q_floats = _inplace(o1)
     check(lib().nano_hip_op_lora_o(device, C.byref(d)))
+
+
+def lora_param_floats(n_layer, n_embd, kv_dim, rank) -> int:
+    """floats of a LoRA module's parameter block (nano_hip_lora_param_floats; no device)"""
+    return int(lib().nano_hip_lora_param_floats(n_layer, n_embd, kv_dim, rank))
+
+
+def _lora_rows_desc(E, KD, x, adapters, row_adapter, keep, n_pairs):
+    def held(v, dtype=np.float32):
+        v = np.ascontiguousarray(v, dtype); keep.append(v)
+        return v
+    x = held(x)
+    d = NanoLoraRowsOpDesc()
+    d.E, d.KD, d.nb, d.n_adapters = E, KD, x.reshape(-1, E).shape[0], len(adapters)
+    d.x = x.ctypes.data
+    arr = (NanoLoraAdapter * max(len(adapters), 1))()
+    for i, (rank, alpha, pairs) in enumerate(adapters):
+        arr[i].rank, arr[i].alpha = rank, alpha
+        assert len(pairs) == n_pairs
+        for j, (A, Bm) in enumerate(pairs):
+            arr[i].a[j], arr[i].b[j] = held(A).ctypes.data, held(Bm).ctypes.data
+    keep.append(arr)
+    d.adapters = arr
+    d.row_adapter = held([NANO_LORA_NONE if v is None else v for v in row_adapter], np.uint32).ctypes.data
+    return d, held
+
+
+def op_lora_qkv_rows(x, norm_w, adapters, row_adapter, q, kraw, v, pos, *, KD, S, v_bstride, device=0):
+    """One per-row lora_qkv launch as a step with a LoRA table issues it (nano_hip_op_lora_qkv_rows).  adapters = [(rank, alpha, ((A_q, B_q),
+    (A_k, B_k), (A_v, B_v)))]; row_adapter[b] = the adapter of row b, or None: that row's q, kraw and v row are left untouched.  The rest as
+    op_lora_qkv: q, kraw, v changed IN PLACE, going to the device whole and coming back whole."""
+    keep = []
+    x = np.ascontiguousarray(x, np.float32)
+    d, held = _lora_rows_desc(x.shape[-1], KD, x, adapters, row_adapter, keep, 3)
+    d.S, d.v_bstride = S, v_bstride
+    d.norm_w = held(norm_w).ctypes.data
+    d.pos = held(pos, np.uint32).ctypes.data
+    (d.q, d.q_floats), (d.kraw, d.k_floats), (d.v, d.v_floats) = _inplace(q), _inplace(kraw), _inplace(v)
+    check(lib().nano_hip_op_lora_qkv_rows(device, C.byref(d)))
+
+
+def op_lora_o_rows(xba, adapters, row_adapter, o1, *, device=0):
+    """One per-row lora_o launch (nano_hip_op_lora_o_rows): adapters = [(rank, alpha, ((A_o, B_o),))]; a row without an adapter gets -0.0 in
+    every element of its o1 row.  o1: a float32 array changed IN PLACE."""
+    keep = []
+    xba = np.ascontiguousarray(xba, np.float32)
+    d, _ = _lora_rows_desc(xba.shape[-1], 0, xba, adapters, row_adapter, keep, 1)
+    d.q, d.q_floats = _inplace(o1)
+    check(lib().nano_hip_op_lora_o_rows(device, C.byref(d)))
 
 
 def op_attention_decode(q, k, pos, k_cache, v_cache, *, n_head, n_kv_head, hd, n_layer, layer, S, range_hint, rope_cos, rope_sin,
@@ -1493,6 +1593,24 @@ class Engine:
         """nano_kv_restore: positions 0..n_pos-1 (None: all) of the image into `slot` of the context's device model"""
         a = np.ascontiguousarray(np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else image, np.uint8).reshape(-1)
         check(self.L.nano_kv_restore(self.ctx, slot, a.ctypes.data if a.size else None, a.size, KV_ALL if n_pos is None else n_pos))
+
+    def lora_table_load(self, id: int, path: str):
+        """nano_lora_table_load: a LoRA module file into entry `id` of the context's LoRA table"""
+        check(self.L.nano_lora_table_load(self.ctx, id, path.encode()))
+
+    def lora_table_load_bytes(self, id: int, data: bytes):
+        """nano_lora_table_load_from_buffer: the bytes of a LoRA module file into entry `id`"""
+        a = np.frombuffer(data, np.uint8)
+        check(self.L.nano_lora_table_load_from_buffer(self.ctx, id, a.ctypes.data if a.size else None, a.size))
+
+    def lora_table_free(self, id: int):
+        check(self.L.nano_lora_table_free(self.ctx, id))
+
+    def lora_bind(self, slots, ids):
+        """nano_lora_bind: sequence slots[i] takes table entry ids[i]; None = no module"""
+        s = np.ascontiguousarray(slots, np.uint32)
+        i = np.ascontiguousarray([NANO_LORA_NONE if v is None else v for v in ids], np.uint32)
+        check(self.L.nano_lora_bind(self.ctx, s.ctypes.data, i.ctypes.data, s.size))
 
     def prefill_batch(self, prompts: Sequence[Sequence[int]], want_first_ids: bool = True) -> Optional[np.ndarray]:
         """nano_prefill_batch: sequence i ingests prompts[i] from position 0, all in one ragged step per device; returns first_ids

@@ -69,6 +69,8 @@ static void destroy(NanoHipModel *m) {
                     m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
                     m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->rows.vraw };
     for (void *p : dev) if (p) (void)hipFree(p);
+    for (auto &en : m->lt.e) if (en.buf) (void)hipFree(en.buf);
+    if (m->lt.desc) (void)hipFree(m->lt.desc);
     void *host[] = { m->h_tokens, m->h_pos, m->h_amax, m->h_logits, m->kv.h_pt, m->h_err };
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
@@ -461,6 +463,7 @@ extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alp
     if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
     // (n_embd % 16 == 0 is the model's own check; rank is the caller's: a module whose t vectors do not fit the launches' LDS is refused here)
     if (const char *msg = lora_shape_error(m->d.n_embd, rank)) FAIL(NANO_HIP_EINVAL, "%s (n_embd %u, rank %u)", msg, m->d.n_embd, rank);
+    if (m->lt.n) FAIL(NANO_HIP_EINVAL, "a LoRA table is stored (nano_hip_lora_table_set); the table and an attached module exclude each other");
     HIP_TRY(hipSetDevice(m->device));
     const size_t L = m->d.n_layer, E = m->d.n_embd, KD = m->KD, r = rank;
     const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };
@@ -480,8 +483,116 @@ extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alp
 // use_lora of the reference's forward (lora != NULL): switch the attached module on / off per call
 extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
-    if (on && !m->lora_buf) FAIL(NANO_HIP_EINVAL, "no LoRA module attached");
+    if (on && !m->lora_buf && !m->lt.n) FAIL(NANO_HIP_EINVAL, "no LoRA module attached and no LoRA table entry stored");
+    if (m->lt.n && m->lora_on != (on != 0)) {              // the table switched: drop the graphs, as every change of the table does
+        HIP_TRY(hipSetDevice(m->device));
+        HIP_TRY(hipStreamSynchronize(m->st));
+        drop_graphs(m);
+    }
     m->lora_on = on != 0;
+    return 0;
+}
+
+// ---- LoRA table: many modules on the device, one bound to each KV slot (lora.hip's per-row launches) -----------------------------------
+extern "C" size_t nano_hip_lora_param_floats(uint32_t n_layer, uint32_t n_embd, uint32_t kv_dim, uint32_t rank) {
+    return (size_t)n_layer * rank * (6 * (size_t)n_embd + 2 * (size_t)kv_dim);      // four A [r][E], two B [E][r], two B [KD][r] per layer
+}
+static LoraSlotDesc lora_slot_desc(const NanoHipModel *m, uint32_t id) {
+    LoraSlotDesc d{};
+    if (id == NANO_LORA_NONE) return d;
+    const NanoHipModel::LoraTable::Entry &en = m->lt.e[id];
+    for (int i = 0; i < 8; i++) d.t[i] = en.t[i];
+    d.rank = en.rank; d.alpha = en.alpha;
+    return d;
+}
+static bool lora_entry_bound(const NanoHipModel *m, uint32_t id) {
+    for (const uint32_t b : m->lt.bound) if (b == id) return true;
+    return false;
+}
+static void lora_table_summary(NanoHipModel *m) {
+    m->lt.n = 0; m->lt.max_rank = 0;
+    for (const auto &en : m->lt.e) if (en.buf) { m->lt.n++; if (en.rank > m->lt.max_rank) m->lt.max_rank = en.rank; }
+}
+extern "C" int nano_hip_lora_table_set(NanoHipModel *m, uint32_t id, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats) {
+    if (!m || !params) FAIL(NANO_HIP_EINVAL, "LoRA table: null argument");
+    if (id >= NANO_LORA_TABLE_MAX) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u beyond the %u entries of the table", id, NANO_LORA_TABLE_MAX);
+    if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
+    if (m->lora_buf) FAIL(NANO_HIP_EINVAL, "LoRA table: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
+    if (const char *msg = lora_shape_error(m->d.n_embd, rank)) FAIL(NANO_HIP_EINVAL, "%s (n_embd %u, rank %u)", msg, m->d.n_embd, rank);
+    const size_t L = m->d.n_layer, E = m->d.n_embd, KD = m->KD, r = rank;
+    const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };
+    const size_t total = nano_hip_lora_param_floats(m->d.n_layer, m->d.n_embd, m->KD, rank);
+    if (n_floats < total) FAIL(NANO_HIP_EINVAL, "LoRA parameter block too small: %zu floats, need %zu", n_floats, total);
+    if (!m->lt.e.empty() && m->lt.e[id].buf && lora_entry_bound(m, id)) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u is bound to a slot (bind the slot elsewhere first)", id);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->st));
+    // everything the entry needs is allocated before the model changes: a failure below leaves it as it was
+    float *buf = nullptr, *o1 = m->lora_o1; LoraSlotDesc *desc = m->lt.desc;
+    HIP_TRY(hipMalloc(&buf, total * 4));
+    hipError_t e = hipMemcpy(buf, params, total * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !o1) e = hipMalloc(&o1, (size_t)m->Bs * E * 4);
+    if (e == hipSuccess && !desc) {
+        e = hipMalloc(&desc, (size_t)m->maxB * sizeof(LoraSlotDesc));
+        if (e == hipSuccess) e = hipMemset(desc, 0, (size_t)m->maxB * sizeof(LoraSlotDesc));      // rank 0: no slot has a module
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(buf); if (o1 != m->lora_o1) (void)hipFree(o1); if (desc != m->lt.desc) (void)hipFree(desc);
+        HIP_TRY(e);
+    }
+    m->lora_o1 = o1; m->lt.desc = desc;
+    if (m->lt.e.empty()) { m->lt.e.resize(NANO_LORA_TABLE_MAX); m->lt.bound.assign(m->maxB, NANO_LORA_NONE); }
+    drop_graphs(m);                                          // their LDS size (the largest rank) and their launch choice may have changed
+    NanoHipModel::LoraTable::Entry &en = m->lt.e[id];
+    if (en.buf) (void)hipFree(en.buf);
+    en.buf = buf; en.rank = rank; en.alpha = alpha;
+    size_t off = 0; for (int i = 0; i < 8; i++) { en.t[i] = buf + off; off += len[i]; }
+    lora_table_summary(m);
+    m->lora_on = true;
+    return 0;
+}
+extern "C" int nano_hip_lora_table_clear(NanoHipModel *m, uint32_t id) {
+    if (!m) FAIL(NANO_HIP_EINVAL, "LoRA table: null model");
+    if (id >= NANO_LORA_TABLE_MAX) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u beyond the %u entries of the table", id, NANO_LORA_TABLE_MAX);
+    if (m->lt.e.empty() || !m->lt.e[id].buf) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u is empty", id);
+    if (lora_entry_bound(m, id)) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u is bound to a slot (bind the slot elsewhere first)", id);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->st));
+    drop_graphs(m);
+    (void)hipFree(m->lt.e[id].buf);
+    m->lt.e[id] = NanoHipModel::LoraTable::Entry{};
+    lora_table_summary(m);
+    if (!m->lt.n) m->lora_on = false;                        // an empty table is no table: the model steps as one that never had a module
+    return 0;
+}
+// Rebinding is a small upload into the descriptor array; captured launches read it when they replay, so no graph is dropped.
+extern "C" int nano_hip_lora_bind(NanoHipModel *m, const uint32_t *slots, const uint32_t *ids, uint32_t n) {
+    if (!m || !slots || !ids) FAIL(NANO_HIP_EINVAL, "LoRA bind: null argument");
+    if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
+    if (m->lora_buf) FAIL(NANO_HIP_EINVAL, "LoRA bind: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
+    std::vector<bool> listed(m->maxB, false);
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= m->maxB) FAIL(NANO_HIP_EINVAL, "LoRA bind: slot %u out of range (max_batch %u)", slots[i], m->maxB);
+        if (listed[slots[i]]) FAIL(NANO_HIP_EINVAL, "LoRA bind: slot %u listed twice", slots[i]);
+        listed[slots[i]] = true;
+        if (ids[i] == NANO_LORA_NONE) continue;
+        if (ids[i] >= NANO_LORA_TABLE_MAX) FAIL(NANO_HIP_EINVAL, "LoRA bind: entry %u beyond the %u entries of the table", ids[i], NANO_LORA_TABLE_MAX);
+        if (m->lt.e.empty() || !m->lt.e[ids[i]].buf) FAIL(NANO_HIP_EINVAL, "LoRA bind: entry %u is empty", ids[i]);
+    }
+    if (m->lt.e.empty() || n == 0) return 0;                 // (no table yet: only NANO_LORA_NONE passed the checks, which every slot already is)
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->st));                    // queued steps read the descriptors
+    std::vector<LoraSlotDesc> all(m->maxB);
+    std::vector<uint32_t> bound = m->lt.bound;
+    for (uint32_t i = 0; i < n; i++) bound[slots[i]] = ids[i];
+    for (uint32_t s = 0; s < m->maxB; s++) all[s] = lora_slot_desc(m, bound[s]);
+    HIP_TRY(hipMemcpy(m->lt.desc, all.data(), all.size() * sizeof(LoraSlotDesc), hipMemcpyHostToDevice));      // at most 64 x 72 bytes
+    m->lt.bound = std::move(bound);
+    return 0;
+}
+extern "C" int nano_hip_lora_binding(const NanoHipModel *m, uint32_t slot, uint32_t *id_out) {
+    if (!m || !id_out) FAIL(NANO_HIP_EINVAL, "LoRA binding: null argument");
+    if (slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "LoRA binding: slot %u out of range (max_batch %u)", slot, m->maxB);
+    *id_out = m->lt.bound.empty() ? NANO_LORA_NONE : m->lt.bound[slot];
     return 0;
 }
 // One prefill chunk: nb rows of `slot`, their tokens and positions in m->tokens / m->pos, the last at last_pos.  replay: through a HIP graph per

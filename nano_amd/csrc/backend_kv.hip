@@ -190,6 +190,12 @@ extern "C" int nano_hip_kv_sharing(const NanoHipModel *m, uint32_t *shared_pages
 // non-causal attention reads unwritten rows).  Everything is planned first and committed after the queueing succeeded: a call that
 // fails (arguments, pool) leaves tables, owner counts and the destinations' contents as they were.  The pages a fork can draw on are
 // the free ones plus those only its destinations own.
+// The rows a fork copies carry the deltas of the source slot's LoRA module: with a table, the destinations take its binding too.
+static int fork_bindings(NanoHipModel *m, int rc, uint32_t src_slot, const uint32_t *dst_slots, uint32_t n_dst) {
+    if (rc || m->lt.bound.empty()) return rc;
+    const std::vector<uint32_t> ids(n_dst, m->lt.bound[src_slot]);
+    return nano_hip_lora_bind(m, dst_slots, ids.data(), n_dst);
+}
 extern "C" int nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_pos, const uint32_t *dst_slots, uint32_t n_dst) {
     if (!m || !dst_slots) FAIL(NANO_HIP_EINVAL, "null argument");
     if (src_slot >= m->maxB) FAIL(NANO_HIP_EINVAL, "source slot %u out of range (max_batch %u)", src_slot, m->maxB);
@@ -212,7 +218,7 @@ extern "C" int nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_p
         const uint32_t slot_rows = m->d.n_layer * m->S;                    // rows of one slot: [slot][layer][S][kv_dim]
         if ((uint64_t)m->maxB * slot_rows > 0xffffffffull) FAIL(NANO_HIP_EINVAL, "cache of %u slots x %u rows is beyond the copy kernel's 32-bit row index", m->maxB, slot_rows);
         for (uint32_t i = 0; i < n_dst; i++) p.jobs.push_back(KvCopyJob{src_slot * slot_rows, dst_slots[i] * slot_rows, n_pos, n_pos});
-        return kv_apply(m, p, "the fork");
+        return fork_bindings(m, kv_apply(m, p, "the fork"), src_slot, dst_slots, n_dst);
     }
     const uint32_t P = m->kv.pt_stride, nfull = n_pos >> 6, part = n_pos & 63u;
     const uint32_t *srow = m->kv.h_pt + (size_t)src_slot * P;
@@ -241,7 +247,7 @@ extern "C" int nano_hip_kv_fork(NanoHipModel *m, uint32_t src_slot, uint32_t n_p
         for (const uint32_t e : row) if (e != KV_NO_PAGE) p.owners.emplace_back(e / 64u, 1);
         p.rows.emplace_back(dst_slots[i], std::move(row));
     }
-    return kv_apply(m, p, "the fork");
+    return fork_bindings(m, kv_apply(m, p, "the fork"), src_slot, dst_slots, n_dst);
 }
 
 // ---- KV images: a slot's rows in host memory and back (kv_image.h the layout, kv_image.hip the kernel) ---------------------------

@@ -79,6 +79,16 @@ struct NanoHipModel {
     float *lora_buf = nullptr, *lora_o1 = nullptr;
     const float *lora_t[8] = {nullptr};                   // qa qb ka kb va vb oa ob, each [L][...]
     uint32_t lora_rank = 0, lora_alpha = 0; bool lora_on = false;
+    // LoRA table (nano_hip_lora_table_set / nano_hip_lora_bind): up to NANO_LORA_TABLE_MAX modules, each one device buffer laid out as
+    // lora_buf, and the module of every KV slot.  Excludes lora_buf.  lora_on is then "the table is not empty and switched on": every
+    // gate and every step decision that reads the flag treats a table as it treats a module.
+    struct LoraTable {
+        struct Entry { float *buf = nullptr; const float *t[8] = {nullptr}; uint32_t rank = 0, alpha = 0; };
+        std::vector<Entry> e;                             // NANO_LORA_TABLE_MAX entries once the first is stored (buf == nullptr: empty)
+        std::vector<uint32_t> bound;                      // [maxB] the entry of each slot, or NANO_LORA_NONE
+        LoraSlotDesc *desc = nullptr;                     // device [maxB]: what `bound` says, at an address fixed for the model's life
+        uint32_t n = 0, max_rank = 0;                     // entries stored; the largest rank among them (the launches' LDS)
+    } lt;
     int8_t *gq = nullptr; float *gxs = nullptr;           // MFMA GEMM path (batch > 8, Q80): quantized activations of all sequences
     uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 64 sequences: the staged activation groups (gemv_q4k_chunk.hip, gemm_q4k.hip)
     float *f32x = nullptr; size_t f32x_floats = 0;        // FP32, 9 .. 64 sequences: the operand-order activations of a GEMM launch (gemm_f32.hip)

@@ -71,6 +71,7 @@ typedef struct ModelEntry {
     /* the LoRA module attached to the model (load_lora*): later replicas get it too */
     const float *lora_params; size_t lora_floats; uint32_t lora_rank, lora_alpha;
     const void *lora_owner;                          /* the LoRA object those parameters belong to (free_lora of another module leaves them) */
+    uint64_t lt_mask;                                /* entries of the device's LoRA table stored through nano_lora_table_load* (bit id) */
     double rep_upload_s, rep_share_s; char rep_how[48];   /* how the last nano_context_replicate moved the weights */
     /* NANO_LOOKUP_DRAFT: ids a verify chunk confirmed beyond the one its call returned.  la_ids[la_at .. la_at + la_n) are what the
      * greedy calls at positions la_pos, la_pos + 1, .. return, provided the id fed there is the one before them (la_prev) */
@@ -411,8 +412,63 @@ static inline void observe(Nano_Context *ctx, int32_t layer, int32_t phase) {
 
 /* the reference's use_lora = (lora != NULL) of each forward call (infer.c:721): a flag store on the device model */
 static void lora_select(NanoHipModel *dev, const LoRA *lora) {
-    const int on = lora != NULL;
+    int on = lora != NULL;
+    /* a LoRA table (nano_lora_table_load*) stays on: it excludes a loaded module, and each row takes its slot's binding or none */
+    for (int i = 0; i < MAX_MODELS && !on; i++) on = g_reg[i].llm && g_reg[i].dev == dev && g_reg[i].lt_mask;
     if (nano_hip_lora_enable(dev, on) != NANO_HIP_OK && on) die_hip("lora");
+}
+
+/* LoRA table (include/nano_mi355x.h nano_hip_lora_table_set / _bind): several module files of the reference's format on the device and a
+ * binding KV slot -> entry, which nano_forward_batch*, nano_prefill_shared and the other batched calls then apply row by row.  The same
+ * header check as load_lora ("does not fit the base model"), reported as NANO_HIP_EINVAL.  The reference's own entry points keep
+ * their single-module meaning: load_lora on a model with a table fails as every load_lora failure does, a table call on a model with
+ * a loaded module returns NANO_HIP_EINVAL.  Not with replicas (NANO_HIP_EINVAL, as nano_embed_batch). */
+static ModelEntry *table_entry(Nano_Context *ctx) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    la_clear(me);
+    return (!me || !me->dev || me->n_replica > 1) ? NULL : me;      /* (replica[0] is the own device) */
+}
+int nano_lora_table_load_from_buffer(Nano_Context *ctx, uint32_t id, const uint8_t *buffer, size_t bytes) {
+    ModelEntry *me = table_entry(ctx);
+    if (!me || !buffer || bytes < 256 || id >= NANO_LORA_TABLE_MAX || ctx->llm->arch != LLM_ARCH_NANO) return NANO_HIP_EINVAL;
+    uint32_t h[14];
+    memcpy(h, buffer, sizeof h);
+    const LLM_Config *m = &ctx->llm->config;
+    if (m->n_layer != h[8] || m->n_embd != h[9] || m->n_head != h[10] || m->n_kv_head != h[11] || m->n_hidden != h[12]) return NANO_HIP_EINVAL;   /* does not fit the base model */
+    const size_t n_floats = (bytes - 256) / sizeof(float);
+    float *params = (float *)malloc(n_floats ? n_floats * sizeof(float) : sizeof(float));      /* (the caller's buffer need not be aligned) */
+    if (!params) return NANO_HIP_ENOMEM;
+    memcpy(params, buffer + 256, n_floats * sizeof(float));
+    const int rc = nano_hip_lora_table_set(me->dev, id, h[6], h[7], params, n_floats);
+    free(params);
+    if (rc == NANO_HIP_OK) me->lt_mask |= 1ull << id;
+    return rc;
+}
+int nano_lora_table_load(Nano_Context *ctx, uint32_t id, const char *path) {
+    if (!ctx || !path) return NANO_HIP_EINVAL;
+    FILE *file = fopen(path, "rb");
+    if (!file) return NANO_HIP_EINVAL;
+    fseek(file, 0, SEEK_END);
+    const long file_size = ftell(file);
+    rewind(file);
+    uint8_t *buf = file_size >= 256 ? (uint8_t *)malloc((size_t)file_size) : NULL;
+    const int got = buf && fread(buf, 1, (size_t)file_size, file) == (size_t)file_size;
+    fclose(file);
+    const int rc = got ? nano_lora_table_load_from_buffer(ctx, id, buf, (size_t)file_size) : (file_size >= 256 && !buf) ? NANO_HIP_ENOMEM : NANO_HIP_EINVAL;
+    free(buf);
+    return rc;
+}
+int nano_lora_table_free(Nano_Context *ctx, uint32_t id) {
+    ModelEntry *me = table_entry(ctx);
+    if (!me || id >= NANO_LORA_TABLE_MAX) return NANO_HIP_EINVAL;
+    const int rc = nano_hip_lora_table_clear(me->dev, id);
+    if (rc == NANO_HIP_OK) me->lt_mask &= ~(1ull << id);
+    return rc;
+}
+int nano_lora_bind(Nano_Context *ctx, const uint32_t *slots, const uint32_t *ids, uint32_t n) {
+    ModelEntry *me = table_entry(ctx);
+    if (!me) return NANO_HIP_EINVAL;
+    return nano_hip_lora_bind(me->dev, slots, ids, n);
 }
 
 /* Per-phase observation (reference infer.c:755-949, 985-1003: eight callbacks per layer plus three per token from
@@ -467,6 +523,7 @@ int nano_context_replicate(Nano_Context *ctx, const int *devices, int n_devices)
     ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
     if (!me || !devices || n_devices < 0 || me->n_replica + n_devices > NANO_MAX_REPLICAS) return NANO_HIP_EINVAL;
     if (n_devices == 0) return NANO_HIP_OK;
+    if (me->lt_mask) return NANO_HIP_EINVAL;                /* a LoRA table and its bindings live on the context's own device only */
     /* ONE upload of the parameter bytes to the context's own device, then device to device (RCCL broadcast over xGMI, or peer copies):
      * replicate.hip.  Each replica is built from the copy on its own device. */
     size_t bytes = nano_hip_params_bytes(&me->desc);

@@ -398,6 +398,24 @@ struct LoraArgs {
 const char *lora_shape_error(uint32_t E, uint32_t rank);
 hipError_t launch_lora_qkv(const LoraArgs &a, uint32_t nb, hipStream_t st);
 hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st);
+// The per-row forms (a table of modules, one bound to each KV slot): row b belongs to slot slot0 + b * slot_stride (1: a decode step,
+// 0: a prefill chunk) and takes its pointers, rank and alpha from that slot's descriptor in device memory -- read when the kernel runs,
+// so a captured launch follows a rebinding.  rank 0 = no module: the qkv form returns before its first barrier and writes nothing, the
+// o form stores -0.0f into its o1 row (r + (-0.0f) has r's bits for every float r: the Wo epilogue then leaves x += Wo xba).  A row with
+// a module runs lora_qkv_kernel's / lora_o_kernel's arithmetic in their order: the same bits.
+struct LoraSlotDesc {
+    const float *t[8];      // qa qb ka kb va vb oa ob of the bound entry, each [L][...] (the layout of nano_hip_lora_attach's buffer)
+    uint32_t rank, alpha;   // rank 0: no module
+};
+struct LoraRowsArgs {
+    const LoraSlotDesc *desc;                      // [slots]
+    const float *x, *norm_w;                       // as LoraArgs
+    float *q, *kraw, *v;
+    const uint32_t *pos;
+    uint32_t E, KD, layer, slot0, slot_stride, v_bstride, max_rank, _pad;   // max_rank sizes the launch's LDS: the largest rank a descriptor may name
+};
+hipError_t launch_lora_qkv_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st);
+hipError_t launch_lora_o_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st);
 
 // ---- small kernels ----------------------------------------------------------------------------------
 struct EmbedArgs {

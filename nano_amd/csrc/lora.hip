@@ -72,6 +72,57 @@ __global__ __launch_bounds__(256) void lora_o_kernel(const LoraArgs a) {
     for (uint32_t i = tid; i < E; i += 256u) a.q[(size_t)b * E + i] = lowrank_up(a.qb, i, rank, t, s);
 }
 
+// ---- the per-row forms: each row takes the module its KV slot is bound to (LoraSlotDesc, device memory) or none.  The arithmetic of a
+// row with a module is the two kernels' above, operation for operation (same helpers, same LDS roles; t and red sit behind xb at
+// offsets of the row's OWN rank): the same bits.  The descriptor is one load per workgroup of an address that depends on blockIdx
+// alone, so `rank == 0` is uniform and the early return comes before the first barrier.
+__global__ __launch_bounds__(256) void lora_qkv_rows_kernel(const LoraRowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, E = a.E, KD = a.KD;
+    const LoraSlotDesc d = a.desc[a.slot0 + b * a.slot_stride];
+    const uint32_t rank = d.rank;
+    if (rank == 0) return;                              // no module: q, raw k and the v row keep their bytes
+    const size_t la = (size_t)a.layer * rank * E, lbq = (size_t)a.layer * E * rank, lbk = (size_t)a.layer * KD * rank;
+    float *xb = sm, *t = sm + ((E + 3) & ~3u), *red = t + 3 * rank;
+    const float *x = a.x + (size_t)b * E;
+    float acc = 0.0f;                                   // rmsnorm (infer.c:601-614), tree order
+    for (uint32_t i = tid; i < E; i += 256u) acc += x[i] * x[i];
+    float ss = block_sum(acc, red);
+    ss /= (float)E; ss += 1e-5f; ss = 1.0f / sqrtf(ss);
+    for (uint32_t i = tid; i < E; i += 256u) xb[i] = a.norm_w[i] * (ss * x[i]);
+    __syncthreads();
+    lowrank_down(d.t[0] + la, rank, E, xb, t);
+    lowrank_down(d.t[2] + la, rank, E, xb, t + rank);
+    lowrank_down(d.t[4] + la, rank, E, xb, t + 2 * rank);
+    __syncthreads();
+    const float s = (float)d.alpha / (float)rank;
+    const float *qb = d.t[1] + lbq, *kb = d.t[3] + lbk, *vb = d.t[5] + lbk;
+    float *q = a.q + (size_t)b * E, *k = a.kraw + (size_t)b * KD;
+    float *v = a.v + (size_t)b * a.v_bstride + (size_t)a.pos[b] * KD;
+    for (uint32_t i = tid; i < E; i += 256u) q[i] += lowrank_up(qb, i, rank, t, s);
+    for (uint32_t i = tid; i < KD; i += 256u) { k[i] += lowrank_up(kb, i, rank, t + rank, s); v[i] += lowrank_up(vb, i, rank, t + 2 * rank, s); }
+}
+
+// x = xba [nb][E] in, q = o1 [nb][E] out
+__global__ __launch_bounds__(256) void lora_o_rows_kernel(const LoraRowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, E = a.E;
+    const LoraSlotDesc d = a.desc[a.slot0 + b * a.slot_stride];
+    const uint32_t rank = d.rank;
+    if (rank == 0) {                                    // no module: the addend that changes no bit of (Wo xba)[i], either zero included
+        for (uint32_t i = tid; i < E; i += 256u) a.q[(size_t)b * E + i] = -0.0f;
+        return;
+    }
+    float *xba = sm, *t = sm + ((E + 3) & ~3u);
+    for (uint32_t i = tid; i < E; i += 256u) xba[i] = a.x[(size_t)b * E + i];
+    __syncthreads();
+    lowrank_down(d.t[6] + (size_t)a.layer * rank * E, rank, E, xba, t);
+    __syncthreads();
+    const float s = (float)d.alpha / (float)rank;
+    const float *ob = d.t[7] + (size_t)a.layer * E * rank;
+    for (uint32_t i = tid; i < E; i += 256u) a.q[(size_t)b * E + i] = lowrank_up(ob, i, rank, t, s);
+}
+
 }  // namespace
 
 static size_t lora_qkv_lds(uint32_t E, uint32_t rank) { return (((size_t)E + 3) & ~(size_t)3) * 4 + 3 * (size_t)rank * 4 + 32 * 4; }
@@ -93,6 +144,18 @@ hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st) {
     if (lora_shape_error(a.E, a.rank)) return hipErrorInvalidValue;
     const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + (size_t)a.rank * 4;
     hipLaunchKernelGGL(lora_o_kernel, dim3(nb), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+// LDS for the largest rank a descriptor may name (every stored rank passed lora_shape_error, so max_rank does)
+hipError_t launch_lora_qkv_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st) {
+    if (!a.desc || lora_shape_error(a.E, a.max_rank)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lora_qkv_rows_kernel, dim3(nb), dim3(256), lora_qkv_lds(a.E, a.max_rank), st, a);
+    return hipGetLastError();
+}
+hipError_t launch_lora_o_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st) {
+    if (!a.desc || lora_shape_error(a.E, a.max_rank)) return hipErrorInvalidValue;
+    const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + (size_t)a.max_rank * 4;
+    hipLaunchKernelGGL(lora_o_rows_kernel, dim3(nb), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -639,6 +639,78 @@ static int lora_op(int device, const NanoLoraOpDesc *d, bool qkv) {
 extern "C" int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, true); }
 extern "C" int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, false); }
 
+// ---- the per-row forms: LoraRowsArgs as enqueue_step() fills them for a table, with row b in "slot" b of a descriptor array built from
+// row_adapter (layer 0 of one-layer adapters).  Checked before a device is asked for.
+static const char *lora_rows_desc_error(const NanoLoraRowsOpDesc *d, bool qkv) {
+    if (!d || !d->x || !d->q || !d->adapters || !d->row_adapter) return "lora rows: null argument";
+    if (qkv && (!d->norm_w || !d->pos || !d->kraw || !d->v)) return "lora rows: null argument";
+    if (d->nb == 0 || d->nb > NANO_MAX_BATCH) return "lora rows: nb outside 1 .. NANO_MAX_BATCH";
+    if (d->n_adapters == 0 || d->n_adapters > NANO_LORA_TABLE_MAX) return "lora rows: n_adapters outside 1 .. NANO_LORA_TABLE_MAX";
+    for (uint32_t i = 0; i < d->n_adapters; i++) {
+        const NanoLoraAdapter &ad = d->adapters[i];
+        if (!ad.a[0] || !ad.b[0] || (qkv && (!ad.a[1] || !ad.b[1] || !ad.a[2] || !ad.b[2]))) return "lora rows: null argument";
+        if (const char *msg = lora_shape_error(d->E, ad.rank)) return msg;
+    }
+    for (uint32_t b = 0; b < d->nb; b++)
+        if (d->row_adapter[b] != NANO_LORA_NONE && d->row_adapter[b] >= d->n_adapters) return "lora rows: row_adapter names no adapter";
+    if (d->q_floats < (uint64_t)d->nb * d->E) return "lora rows: q smaller than nb rows of E";
+    if (!qkv) return nullptr;
+    if (d->KD == 0 || d->k_floats < (uint64_t)d->nb * d->KD) return "lora rows: KD of 0, or kraw smaller than nb rows of KD";
+    for (uint32_t b = 0; b < d->nb; b++) {
+        if (d->pos[b] >= d->S) return "lora rows: position beyond S";
+        if ((uint64_t)b * d->v_bstride + ((uint64_t)d->pos[b] + 1) * d->KD > d->v_floats) return "lora rows: a v row beyond v_floats";
+    }
+    return nullptr;
+}
+static int lora_rows_op(int device, const NanoLoraRowsOpDesc *d, bool qkv) {
+    if (const char *msg = lora_rows_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    int rc; if ((rc = begin(device))) return rc;
+    const size_t E = d->E, KD = d->KD;
+    DevBufs B;
+    std::vector<LoraSlotDesc> ent(d->n_adapters);
+    uint32_t max_rank = 0;
+    for (uint32_t i = 0; i < d->n_adapters; i++) {
+        const NanoLoraAdapter &ad = d->adapters[i];
+        const size_t r = ad.rank;
+        LoraSlotDesc &t = ent[i];
+        t = LoraSlotDesc{};
+        t.rank = ad.rank; t.alpha = ad.alpha;
+        if (ad.rank > max_rank) max_rank = ad.rank;
+        if (qkv) {
+            t.t[0] = B.upload(ad.a[0], r * E); t.t[1] = B.upload(ad.b[0], E * r); t.t[2] = B.upload(ad.a[1], r * E); t.t[3] = B.upload(ad.b[1], KD * r);
+            t.t[4] = B.upload(ad.a[2], r * E); t.t[5] = B.upload(ad.b[2], KD * r);
+            OP_CHECK(t.t[0] && t.t[1] && t.t[2] && t.t[3] && t.t[4] && t.t[5], "device alloc failed");
+        } else {
+            t.t[6] = B.upload(ad.a[0], r * E); t.t[7] = B.upload(ad.b[0], E * r);
+            OP_CHECK(t.t[6] && t.t[7], "device alloc failed");
+        }
+    }
+    std::vector<LoraSlotDesc> rows(d->nb);
+    for (uint32_t b = 0; b < d->nb; b++) rows[b] = d->row_adapter[b] == NANO_LORA_NONE ? LoraSlotDesc{} : ent[d->row_adapter[b]];
+    LoraRowsArgs la{};
+    la.desc = B.upload(rows.data(), rows.size());
+    la.x = B.upload(d->x, d->nb * E);
+    la.q = B.upload(d->q, (size_t)d->q_floats);
+    OP_CHECK(la.desc && la.x && la.q, "device alloc failed");
+    la.E = d->E; la.KD = d->KD; la.layer = 0; la.slot0 = 0; la.slot_stride = 1; la.max_rank = max_rank;
+    if (qkv) {
+        la.norm_w = B.upload(d->norm_w, E);
+        la.kraw = B.upload(d->kraw, (size_t)d->k_floats); la.v = B.upload(d->v, (size_t)d->v_floats);
+        la.pos = B.upload(d->pos, d->nb); la.v_bstride = d->v_bstride;
+        OP_CHECK(la.norm_w && la.kraw && la.v && la.pos, "device alloc failed");
+    }
+    OP_HIP(qkv ? launch_lora_qkv_rows(la, d->nb, 0) : launch_lora_o_rows(la, d->nb, 0));
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(d->q, la.q, (size_t)d->q_floats * 4, hipMemcpyDeviceToHost));
+    if (qkv) {
+        OP_HIP(hipMemcpy(d->kraw, la.kraw, (size_t)d->k_floats * 4, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(d->v, la.v, (size_t)d->v_floats * 4, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int nano_hip_op_lora_qkv_rows(int device, const NanoLoraRowsOpDesc *d) { return lora_rows_op(device, d, true); }
+extern "C" int nano_hip_op_lora_o_rows(int device, const NanoLoraRowsOpDesc *d) { return lora_rows_op(device, d, false); }
+
 // ---- ONE path from an attention-decode descriptor to the launch's arguments: nano_hip_op_attention_decode, the fused q | k | v + attention
 // operator and its plan query start here.  Every shape field as enqueue_step() fills it (backend_step.hip); of the pointers q_norm / k_norm
 // arrive as the descriptor's HOST pointers, read as flags -- an operator replaces them, and sets every other pointer, with device copies.
