@@ -452,7 +452,8 @@ int nano_hip_op_pool_rows(int device, const float *x, uint32_t rows, uint32_t n_
 
 /* LoRA side branches of the Nano architecture (reference infer.c:434-498 loader, 792-808 / 898-903 forward).
  * `params` = the floats that follow the 256-byte header of a LoRA module file, in file order; rank / alpha = header words
- * 6 / 7.  Attaching enables the module; nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.
+ * 6 / 7.  Attaching enables the module (every KV slot's rows take it; a call that fails leaves the model as it was);
+ * nano_hip_lora_enable(m, 0/1) is the reference's per-call `lora != NULL`.
  * Replaces: load_lora / parse_lora_file's device side and the use_lora branches of transformer_block_forward. */
 int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats);
 int nano_hip_lora_enable(NanoHipModel *m, int on);
@@ -825,7 +826,8 @@ typedef struct NanoLoraOpDesc {
 } NanoLoraOpDesc;
 int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d);
 int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d);
-/* The per-row forms of the two launches (a LoRA table: each row takes the module of its KV slot, or none), one launch on caller arrays:
+/* The same two launches with a module per row (a LoRA table: each row takes the module of its KV slot, or none; the operators above are
+ * one adapter with every row bound to it), one launch on caller arrays:
  * the fields of NanoLoraOpDesc that do not depend on the module, n_adapters adapters {rank, alpha, a[3], b[3]} (o: a[0] / b[0] = the o
  * pair), and row_adapter[nb] = each row's adapter or NANO_LORA_NONE.  A row without an adapter: nano_hip_op_lora_qkv_rows leaves its q,
  * kraw and v rows untouched, nano_hip_op_lora_o_rows stores -0.0f into its row of q.  The launch's LDS is sized by the largest rank.

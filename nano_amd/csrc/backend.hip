@@ -66,7 +66,7 @@ static void destroy(NanoHipModel *m) {
     if (m->st) (void)hipStreamSynchronize(m->st);
     for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     void *dev[] = { m->arena, m->x, m->q, m->kraw, m->xba, m->hb, m->logits, m->kcache, m->vcache,
-                    m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lora_buf, m->lora_o1,
+                    m->tokens, m->pos, m->amax, m->trace, m->pos0, m->attn_part, m->attn_ml, m->tile_max, m->rope_cur, m->gq, m->gxs, m->lt.at.buf, m->lora_o1,
                     m->xn, m->hb2, m->att, m->vraw, m->stamp.buf, m->kv.pt, m->kv.kvrow, m->ho.hand, m->ho.hand2, m->ho.tick, m->kv.jobs, m->q4x, m->f32x, m->rows.vraw };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &en : m->lt.e) if (en.buf) (void)hipFree(en.buf);
@@ -455,9 +455,48 @@ extern "C" int nano_hip_forward(NanoHipModel *m, const uint32_t *tokens, const u
     return nano_hip_forward_end(m, logits_out, argmax_out);
 }
 
-// ---- LoRA ---------------------------------------------------------------------------------------------
+// ---- LoRA: one attached module, or a table of modules with one bound to each KV slot (lora.hip) ------------------------
 // `params` = the floats of a LoRA module file after its 256-byte header, in file order (reference infer.c:476-497):
 // wq_a[L][r][E] wq_b[L][E][r] wk_a[L][r][E] wk_b[L][KD][r] wv_a[L][r][E] wv_b[L][KD][r] wo_a[L][r][E] wo_b[L][E][r].
+static size_t lora_layout(size_t L, size_t E, size_t KD, size_t r, size_t off[8]) {
+    const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };
+    size_t total = 0;
+    for (int i = 0; i < 8; i++) { off[i] = total; total += len[i]; }
+    return total;
+}
+extern "C" size_t nano_hip_lora_param_floats(uint32_t n_layer, uint32_t n_embd, uint32_t kv_dim, uint32_t rank) {
+    size_t off[8];
+    return lora_layout(n_layer, n_embd, kv_dim, rank, off);
+}
+// A module on the device: its buffer, and the o1 scratch and the descriptor array (rank 0 in every slot) where the model has none yet.
+// every_slot: the module goes into every slot's descriptor (an attached module).  Everything is allocated and uploaded before the model
+// changes: a failure leaves it as it was.  The stream is idle (queued steps read the descriptors).
+static int lora_entry_make(NanoHipModel *m, uint32_t rank, uint32_t alpha, const float *params, bool every_slot, NanoHipModel::LoraTable::Entry *out) {
+    size_t off[8];
+    const size_t total = lora_layout(m->d.n_layer, m->d.n_embd, m->KD, rank, off);
+    NanoHipModel::LoraTable::Entry en;
+    float *o1 = m->lora_o1; LoraSlotDesc *desc = m->lt.desc;
+    HIP_TRY(hipMalloc(&en.buf, total * 4));
+    for (int i = 0; i < 8; i++) en.d.t[i] = en.buf + off[i];
+    en.d.rank = rank; en.d.alpha = alpha;
+    hipError_t e = hipMemcpy(en.buf, params, total * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !o1) e = hipMalloc(&o1, (size_t)m->Bs * m->d.n_embd * 4);
+    if (e == hipSuccess && !desc) {
+        e = hipMalloc(&desc, (size_t)m->maxB * sizeof(LoraSlotDesc));
+        if (e == hipSuccess) e = hipMemset(desc, 0, (size_t)m->maxB * sizeof(LoraSlotDesc));      // rank 0: no slot has a module
+    }
+    if (e == hipSuccess && every_slot) {
+        const std::vector<LoraSlotDesc> all(m->maxB, en.d);
+        e = hipMemcpy(desc, all.data(), all.size() * sizeof(LoraSlotDesc), hipMemcpyHostToDevice);     // at most 64 x 72 bytes
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(en.buf); if (o1 != m->lora_o1) (void)hipFree(o1); if (desc != m->lt.desc) (void)hipFree(desc);
+        HIP_TRY(e);
+    }
+    m->lora_o1 = o1; m->lt.desc = desc;
+    *out = en;
+    return 0;
+}
 extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats) {
     if (!m || !params || !rank) FAIL(NANO_HIP_EINVAL, "bad argument");
     if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
@@ -465,25 +504,20 @@ extern "C" int nano_hip_lora_attach(NanoHipModel *m, uint32_t rank, uint32_t alp
     if (const char *msg = lora_shape_error(m->d.n_embd, rank)) FAIL(NANO_HIP_EINVAL, "%s (n_embd %u, rank %u)", msg, m->d.n_embd, rank);
     if (m->lt.n) FAIL(NANO_HIP_EINVAL, "a LoRA table is stored (nano_hip_lora_table_set); the table and an attached module exclude each other");
     HIP_TRY(hipSetDevice(m->device));
-    const size_t L = m->d.n_layer, E = m->d.n_embd, KD = m->KD, r = rank;
-    const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };
-    size_t total = 0; for (size_t v : len) total += v;
+    const size_t total = nano_hip_lora_param_floats(m->d.n_layer, m->d.n_embd, m->KD, rank);
     if (n_floats < total) FAIL(NANO_HIP_EINVAL, "LoRA parameter block too small: %zu floats, need %zu", n_floats, total);
     HIP_TRY(hipStreamSynchronize(m->st));
-    // graphs captured with the previous module carry its device pointers and rank in their kernel arguments
-    drop_graphs(m);
-    if (m->lora_buf) { (void)hipFree(m->lora_buf); m->lora_buf = nullptr; }
-    if (!m->lora_o1) HIP_TRY(hipMalloc(&m->lora_o1, (size_t)m->Bs * E * 4));
-    HIP_TRY(hipMalloc(&m->lora_buf, total * 4));
-    HIP_TRY(hipMemcpy(m->lora_buf, params, total * 4, hipMemcpyHostToDevice));
-    size_t off = 0; for (int i = 0; i < 8; i++) { m->lora_t[i] = m->lora_buf + off; off += len[i]; }
-    m->lora_rank = rank; m->lora_alpha = alpha; m->lora_on = true;
+    NanoHipModel::LoraTable::Entry en;
+    int rc; if ((rc = lora_entry_make(m, rank, alpha, params, true, &en))) return rc;
+    drop_graphs(m);                                          // graphs captured with the previous module carry its rank as their LDS size
+    if (m->lt.at.buf) (void)hipFree(m->lt.at.buf);
+    m->lt.at = en; m->lt.max_rank = rank; m->lora_on = true;
     return 0;
 }
 // use_lora of the reference's forward (lora != NULL): switch the attached module on / off per call
 extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     if (!m) FAIL(NANO_HIP_EINVAL, "null model");
-    if (on && !m->lora_buf && !m->lt.n) FAIL(NANO_HIP_EINVAL, "no LoRA module attached and no LoRA table entry stored");
+    if (on && !m->lt.at.buf && !m->lt.n) FAIL(NANO_HIP_EINVAL, "no LoRA module attached and no LoRA table entry stored");
     if (m->lt.n && m->lora_on != (on != 0)) {              // the table switched: drop the graphs, as every change of the table does
         HIP_TRY(hipSetDevice(m->device));
         HIP_TRY(hipStreamSynchronize(m->st));
@@ -493,59 +527,32 @@ extern "C" int nano_hip_lora_enable(NanoHipModel *m, int on) {
     return 0;
 }
 
-// ---- LoRA table: many modules on the device, one bound to each KV slot (lora.hip's per-row launches) -----------------------------------
-extern "C" size_t nano_hip_lora_param_floats(uint32_t n_layer, uint32_t n_embd, uint32_t kv_dim, uint32_t rank) {
-    return (size_t)n_layer * rank * (6 * (size_t)n_embd + 2 * (size_t)kv_dim);      // four A [r][E], two B [E][r], two B [KD][r] per layer
-}
-static LoraSlotDesc lora_slot_desc(const NanoHipModel *m, uint32_t id) {
-    LoraSlotDesc d{};
-    if (id == NANO_LORA_NONE) return d;
-    const NanoHipModel::LoraTable::Entry &en = m->lt.e[id];
-    for (int i = 0; i < 8; i++) d.t[i] = en.t[i];
-    d.rank = en.rank; d.alpha = en.alpha;
-    return d;
-}
+static LoraSlotDesc lora_slot_desc(const NanoHipModel *m, uint32_t id) { return id == NANO_LORA_NONE ? LoraSlotDesc{} : m->lt.e[id].d; }
 static bool lora_entry_bound(const NanoHipModel *m, uint32_t id) {
     for (const uint32_t b : m->lt.bound) if (b == id) return true;
     return false;
 }
 static void lora_table_summary(NanoHipModel *m) {
     m->lt.n = 0; m->lt.max_rank = 0;
-    for (const auto &en : m->lt.e) if (en.buf) { m->lt.n++; if (en.rank > m->lt.max_rank) m->lt.max_rank = en.rank; }
+    for (const auto &en : m->lt.e) if (en.buf) { m->lt.n++; if (en.d.rank > m->lt.max_rank) m->lt.max_rank = en.d.rank; }
 }
 extern "C" int nano_hip_lora_table_set(NanoHipModel *m, uint32_t id, uint32_t rank, uint32_t alpha, const float *params, size_t n_floats) {
     if (!m || !params) FAIL(NANO_HIP_EINVAL, "LoRA table: null argument");
     if (id >= NANO_LORA_TABLE_MAX) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u beyond the %u entries of the table", id, NANO_LORA_TABLE_MAX);
     if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
-    if (m->lora_buf) FAIL(NANO_HIP_EINVAL, "LoRA table: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
+    if (m->lt.at.buf) FAIL(NANO_HIP_EINVAL, "LoRA table: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
     if (const char *msg = lora_shape_error(m->d.n_embd, rank)) FAIL(NANO_HIP_EINVAL, "%s (n_embd %u, rank %u)", msg, m->d.n_embd, rank);
-    const size_t L = m->d.n_layer, E = m->d.n_embd, KD = m->KD, r = rank;
-    const size_t len[8] = { L * r * E, L * E * r, L * r * E, L * KD * r, L * r * E, L * KD * r, L * r * E, L * E * r };
     const size_t total = nano_hip_lora_param_floats(m->d.n_layer, m->d.n_embd, m->KD, rank);
     if (n_floats < total) FAIL(NANO_HIP_EINVAL, "LoRA parameter block too small: %zu floats, need %zu", n_floats, total);
     if (!m->lt.e.empty() && m->lt.e[id].buf && lora_entry_bound(m, id)) FAIL(NANO_HIP_EINVAL, "LoRA table: entry %u is bound to a slot (bind the slot elsewhere first)", id);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->st));
-    // everything the entry needs is allocated before the model changes: a failure below leaves it as it was
-    float *buf = nullptr, *o1 = m->lora_o1; LoraSlotDesc *desc = m->lt.desc;
-    HIP_TRY(hipMalloc(&buf, total * 4));
-    hipError_t e = hipMemcpy(buf, params, total * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !o1) e = hipMalloc(&o1, (size_t)m->Bs * E * 4);
-    if (e == hipSuccess && !desc) {
-        e = hipMalloc(&desc, (size_t)m->maxB * sizeof(LoraSlotDesc));
-        if (e == hipSuccess) e = hipMemset(desc, 0, (size_t)m->maxB * sizeof(LoraSlotDesc));      // rank 0: no slot has a module
-    }
-    if (e != hipSuccess) {
-        (void)hipFree(buf); if (o1 != m->lora_o1) (void)hipFree(o1); if (desc != m->lt.desc) (void)hipFree(desc);
-        HIP_TRY(e);
-    }
-    m->lora_o1 = o1; m->lt.desc = desc;
+    NanoHipModel::LoraTable::Entry en;
+    int rc; if ((rc = lora_entry_make(m, rank, alpha, params, false, &en))) return rc;
     if (m->lt.e.empty()) { m->lt.e.resize(NANO_LORA_TABLE_MAX); m->lt.bound.assign(m->maxB, NANO_LORA_NONE); }
     drop_graphs(m);                                          // their LDS size (the largest rank) and their launch choice may have changed
-    NanoHipModel::LoraTable::Entry &en = m->lt.e[id];
-    if (en.buf) (void)hipFree(en.buf);
-    en.buf = buf; en.rank = rank; en.alpha = alpha;
-    size_t off = 0; for (int i = 0; i < 8; i++) { en.t[i] = buf + off; off += len[i]; }
+    if (m->lt.e[id].buf) (void)hipFree(m->lt.e[id].buf);
+    m->lt.e[id] = en;
     lora_table_summary(m);
     m->lora_on = true;
     return 0;
@@ -568,7 +575,7 @@ extern "C" int nano_hip_lora_table_clear(NanoHipModel *m, uint32_t id) {
 extern "C" int nano_hip_lora_bind(NanoHipModel *m, const uint32_t *slots, const uint32_t *ids, uint32_t n) {
     if (!m || !slots || !ids) FAIL(NANO_HIP_EINVAL, "LoRA bind: null argument");
     if (m->d.arch != NANO_ARCH_NANO) FAIL(NANO_HIP_EINVAL, "LoRA side branches exist for the Nano architecture only (reference infer.c:792)");
-    if (m->lora_buf) FAIL(NANO_HIP_EINVAL, "LoRA bind: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
+    if (m->lt.at.buf) FAIL(NANO_HIP_EINVAL, "LoRA bind: a module is attached (nano_hip_lora_attach); the table and an attached module exclude each other");
     std::vector<bool> listed(m->maxB, false);
     for (uint32_t i = 0; i < n; i++) {
         if (slots[i] >= m->maxB) FAIL(NANO_HIP_EINVAL, "LoRA bind: slot %u out of range (max_batch %u)", slots[i], m->maxB);

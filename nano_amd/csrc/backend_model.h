@@ -75,19 +75,18 @@ struct NanoHipModel {
     float *x = nullptr, *q = nullptr, *kraw = nullptr, *xba = nullptr, *hb = nullptr, *logits = nullptr;
     float *attn_part = nullptr, *attn_ml = nullptr;       // split-attention partials [B][nsplit][QD], [B][n_head][nsplit][2]
     float *tile_max = nullptr;                            // classifier arg-max partials [B][<=V][2]
-    // LoRA module (Nano architecture, reference infer.c:434-498): 8 FP32 tensors in one device buffer + o1 scratch
-    float *lora_buf = nullptr, *lora_o1 = nullptr;
-    const float *lora_t[8] = {nullptr};                   // qa qb ka kb va vb oa ob, each [L][...]
-    uint32_t lora_rank = 0, lora_alpha = 0; bool lora_on = false;
-    // LoRA table (nano_hip_lora_table_set / nano_hip_lora_bind): up to NANO_LORA_TABLE_MAX modules, each one device buffer laid out as
-    // lora_buf, and the module of every KV slot.  Excludes lora_buf.  lora_on is then "the table is not empty and switched on": every
-    // gate and every step decision that reads the flag treats a table as it treats a module.
+    // LoRA (Nano architecture, reference infer.c:434-498).  A module is 8 FP32 tensors in one device buffer; the steps read the module of
+    // every KV slot from `desc`.  Either ONE attached module (nano_hip_lora_attach: `at`, in every slot's descriptor) or a table of up to
+    // NANO_LORA_TABLE_MAX (nano_hip_lora_table_set / nano_hip_lora_bind: `e`, each slot's descriptor from `bound`); they exclude each
+    // other.  lora_on: a module is attached, or the table is not empty, and switched on -- all that the gates and step decisions read.
+    float *lora_o1 = nullptr; bool lora_on = false;       // the o branch's addend [Bs][E]
     struct LoraTable {
-        struct Entry { float *buf = nullptr; const float *t[8] = {nullptr}; uint32_t rank = 0, alpha = 0; };
+        struct Entry { float *buf = nullptr; LoraSlotDesc d{}; };   // d.t[]: qa qb ka kb va vb oa ob inside buf, each [L][...]
+        Entry at;                                         // the attached module (buf == nullptr: none)
         std::vector<Entry> e;                             // NANO_LORA_TABLE_MAX entries once the first is stored (buf == nullptr: empty)
-        std::vector<uint32_t> bound;                      // [maxB] the entry of each slot, or NANO_LORA_NONE
-        LoraSlotDesc *desc = nullptr;                     // device [maxB]: what `bound` says, at an address fixed for the model's life
-        uint32_t n = 0, max_rank = 0;                     // entries stored; the largest rank among them (the launches' LDS)
+        std::vector<uint32_t> bound;                      // [maxB] the entry of each slot, or NANO_LORA_NONE (empty without a table)
+        LoraSlotDesc *desc = nullptr;                     // device [maxB]: `at` in every slot, or what `bound` says; at an address fixed for the model's life
+        uint32_t n = 0, max_rank = 0;                     // table entries stored; the largest rank a descriptor may name (the launches' LDS)
     } lt;
     int8_t *gq = nullptr; float *gxs = nullptr;           // MFMA GEMM path (batch > 8, Q80): quantized activations of all sequences
     uint8_t *q4x = nullptr; size_t q4x_bytes = 0;         // Q4K, 2 .. 64 sequences: the staged activation groups (gemv_q4k_chunk.hip, gemm_q4k.hip)

@@ -102,7 +102,7 @@ static GemvArgs w13_args(const NanoHipModel *m, uint32_t l, uint32_t nb, const f
     a.norm_w = norm_w;
     return a;
 }
-// what the two per-row LoRA launches of layer l share: row b belongs to KV slot s.slot + b (a decode step) or s.slot (a chunk)
+// what the two LoRA launches of layer l share: row b belongs to KV slot s.slot + b (a decode step) or s.slot (a chunk)
 static LoraRowsArgs lora_rows_args(const NanoHipModel *m, const StepSpec &s, uint32_t l) {
     LoraRowsArgs a{};
     a.desc = m->lt.desc; a.E = m->d.n_embd; a.KD = m->KD; a.layer = l; a.slot0 = s.slot; a.slot_stride = s.one_slot() ? 0u : 1u; a.max_rank = m->lt.max_rank;
@@ -204,7 +204,7 @@ static hipError_t enqueue_rows_attention(NanoHipModel *m, const StepSpec &s, Att
 // s.range_hint: host-side upper bound of the attended range of every sequence (a multiple of 64, <= S)
 hipError_t enqueue_step(NanoHipModel *m, const StepSpec &s) {
     const NanoModelDesc &d = m->d;
-    const uint32_t E = d.n_embd, KD = m->KD, L = d.n_layer, nb = s.nb, mode = s.mode;
+    const uint32_t E = d.n_embd, L = d.n_layer, nb = s.nb, mode = s.mode;
     hipError_t e;
     // Batched prefill (CHUNK) splits every token's attention exactly as that token's own decode step would (chunks start on
     // multiples of the 64-position bucket, so one range_hint covers them) and combines with a kernel of its own: the KV
@@ -247,21 +247,11 @@ hipError_t enqueue_step(NanoHipModel *m, const StepSpec &s) {
         } else {
             qa.stamps = next_stamps(m, 1);
             if ((e = gemv(m, qa)) != hipSuccess) return e;
-            if (m->lora_on && m->lt.n) {       // ... each row with the module of its slot (the table), or none
+            if (m->lora_on) {       // q / k / v += (alpha/rank) B (A xb), each row with the module of its slot or none   reference infer.c:792-808
                 LoraRowsArgs lr = lora_rows_args(m, s, l);
                 lr.x = m->x; lr.norm_w = m->rms_attn + (size_t)l * E;
                 lr.q = m->q; lr.kraw = m->kraw; lr.v = kv.v_flat(l); lr.v_bstride = kv.v_flat_bstride(); lr.pos = m->pos;
                 if ((e = launch_lora_qkv_rows(lr, nb, m->st)) != hipSuccess) return e;
-            } else if (m->lora_on) {       // q / k / v += (alpha/rank) B (A xb)   reference infer.c:792-808
-                const size_t la = (size_t)l * m->lora_rank * E, lbq = (size_t)l * E * m->lora_rank, lbk = (size_t)l * KD * m->lora_rank;
-                LoraArgs la_{};
-                la_.x = m->x; la_.norm_w = m->rms_attn + (size_t)l * E;
-                la_.qa = m->lora_t[0] + la; la_.qb = m->lora_t[1] + lbq; la_.ka = m->lora_t[2] + la; la_.kb = m->lora_t[3] + lbk;
-                la_.va = m->lora_t[4] + la; la_.vb = m->lora_t[5] + lbk;
-                la_.q = m->q; la_.kraw = m->kraw;
-                la_.v = kv.v_flat(l); la_.v_bstride = kv.v_flat_bstride();
-                la_.pos = m->pos; la_.E = E; la_.KD = KD; la_.rank = m->lora_rank; la_.alpha = m->lora_alpha;
-                if ((e = launch_lora_qkv(la_, nb, m->st)) != hipSuccess) return e;
             }
             if (ragged) {           // pass 1 over all rows, then a launch (and a combine launch) per range bucket
                 if ((e = enqueue_rows_attention(m, s, a, wo_frag)) != hipSuccess) return e;
@@ -280,15 +270,10 @@ hipError_t enqueue_step(NanoHipModel *m, const StepSpec &s) {
         }
         if (pf_combine && !ragged && (e = launch_attn_combine_tokens(m->attn_part, m->attn_ml, m->xba, d.n_head, m->hd, nsplit, nb, wo_frag ? m->gq : nullptr, wo_frag ? m->gxs : nullptr, m->st)) != hipSuccess) return e;
         {   // x += Wo . xba   reference infer.c:885-908
-            if (m->lora_on && m->lt.n) {       // ... per row; a row without a module gets o1 = -0.0f, which changes no bit of the sum
+            if (m->lora_on) {       // o1 = (alpha/rank) B_o (A_o xba), added by the Wo epilogue: x += (Wo xba + o1); a row without a module gets -0.0f   infer.c:898-908
                 LoraRowsArgs lr = lora_rows_args(m, s, l);
                 lr.x = m->xba; lr.q = m->lora_o1;
                 if ((e = launch_lora_o_rows(lr, nb, m->st)) != hipSuccess) return e;
-            } else if (m->lora_on) {       // o1 = (alpha/rank) B_o (A_o xba), added by the Wo epilogue: x += (Wo xba + o1)   infer.c:898-908
-                LoraArgs la_{};
-                la_.x = m->xba; la_.qa = m->lora_t[6] + (size_t)l * m->lora_rank * E; la_.qb = m->lora_t[7] + (size_t)l * E * m->lora_rank;
-                la_.q = m->lora_o1; la_.E = E; la_.KD = KD; la_.rank = m->lora_rank; la_.alpha = m->lora_alpha;
-                if ((e = launch_lora_o(la_, nb, m->st)) != hipSuccess) return e;
             }
             GemvArgs a = wo_args(m, l, nb, wo_nsplit);
             a.frag_ready = wo_frag ? 1u : 0u;

@@ -385,32 +385,23 @@ bool exact_attention_fits(uint32_t hd, uint32_t max_range);
 hipError_t launch_exact_attention(const StrictAttnArgs &a, uint32_t nb, hipStream_t st);
 
 // ---- LoRA side branches (lora.hip) -------------------------------------------------------------------
-struct LoraArgs {
-    const float *x;         // qkv: residual stream x [nb][E]; o: attention output xba [nb][E]
-    const float *norm_w;    // qkv: rms_attn weight of the layer
-    const float *qa, *qb, *ka, *kb, *va, *vb;      // this layer's pairs; o: qa / qb = the o pair
-    float *q, *kraw, *v;    // qkv: in-place targets (v = cache base of slot 0 / of the prefill slot); o: q = o1 out
-    const uint32_t *pos;
-    uint32_t E, KD, rank, alpha, v_bstride, _pad;
-};
 // what the two launches cannot run, or nullptr: E % 4 (float4 loads of the A rows and of the LDS copy), rank 0, and dynamic LDS beyond the
-// 64 KiB a launch may ask for (qkv: E + 3 rank + 32 floats).  Asked by nano_hip_lora_attach and by the operators; the launches refuse too.
+// 64 KiB a launch may ask for (qkv: E + 3 rank + 32 floats).  Asked by nano_hip_lora_attach / _table_set and by the operators; the launches refuse too.
 const char *lora_shape_error(uint32_t E, uint32_t rank);
-hipError_t launch_lora_qkv(const LoraArgs &a, uint32_t nb, hipStream_t st);
-hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st);
-// The per-row forms (a table of modules, one bound to each KV slot): row b belongs to slot slot0 + b * slot_stride (1: a decode step,
+// One kernel pair.  A row's "module" is the descriptor of its KV slot: row b belongs to slot slot0 + b * slot_stride (1: a decode step,
 // 0: a prefill chunk) and takes its pointers, rank and alpha from that slot's descriptor in device memory -- read when the kernel runs,
-// so a captured launch follows a rebinding.  rank 0 = no module: the qkv form returns before its first barrier and writes nothing, the
-// o form stores -0.0f into its o1 row (r + (-0.0f) has r's bits for every float r: the Wo epilogue then leaves x += Wo xba).  A row with
-// a module runs lora_qkv_kernel's / lora_o_kernel's arithmetic in their order: the same bits.
+// so a captured launch follows a rebinding.  An attached module (nano_hip_lora_attach) is the same descriptor in every slot; a table binds
+// one per slot.  rank 0 = no module: the qkv launch returns before its first barrier and writes nothing, the o launch stores -0.0f into
+// its o1 row (r + (-0.0f) has r's bits for every float r: the Wo epilogue then leaves x += Wo xba).
 struct LoraSlotDesc {
-    const float *t[8];      // qa qb ka kb va vb oa ob of the bound entry, each [L][...] (the layout of nano_hip_lora_attach's buffer)
+    const float *t[8];      // qa qb ka kb va vb oa ob of the module, each [L][...] (the layout of nano_hip_lora_attach's parameter block)
     uint32_t rank, alpha;   // rank 0: no module
 };
 struct LoraRowsArgs {
     const LoraSlotDesc *desc;                      // [slots]
-    const float *x, *norm_w;                       // as LoraArgs
-    float *q, *kraw, *v;
+    const float *x;         // qkv: residual stream x [nb][E]; o: attention output xba [nb][E]
+    const float *norm_w;    // qkv: rms_attn weight of the layer
+    float *q, *kraw, *v;    // qkv: in-place targets (v = cache base of slot 0 / of the prefill slot); o: q = o1 out
     const uint32_t *pos;
     uint32_t E, KD, layer, slot0, slot_stride, v_bstride, max_rank, _pad;   // max_rank sizes the launch's LDS: the largest rank a descriptor may name
 };

@@ -2,10 +2,12 @@
 // file format / loader infer.c:434-498).  FP32 low-rank pairs (A [rank][E], B [out][rank]) on q, k, v and o:
 //     q += (alpha/rank) * B_q (A_q xb),  same for k and v,  xb2 += (alpha/rank) * B_o (A_o xba)
 // where xb = rmsnorm(x, rms_attn) and xba = the attention output.  The matrices are tiny (rank x E floats): one
-// workgroup per sequence, everything through LDS; two extra launches per layer, only when a module is attached.
-//   lora_qkv_kernel : after the QKV GEMV, before attention (q / raw k live in scratch, v in its cache row);
-//   lora_o_kernel   : after attention, before the Wo GEMV; writes o1 = (alpha/rank) * B_o (A_o xba) which the Wo
-//                     GEMV's residual epilogue adds in the reference's order  x += (Wo xba + o1).
+// workgroup per row, everything through LDS; two extra launches per layer, only while LoRA is on.  ONE kernel pair: a row's
+// "module" is the descriptor of its KV slot (LoraSlotDesc, device memory) -- the same descriptor in every slot for an attached
+// module, the table's binding otherwise, rank 0 for none.
+//   lora_qkv_rows_kernel : after the QKV GEMV, before attention (q / raw k live in scratch, v in its cache row);
+//   lora_o_rows_kernel   : after attention, before the Wo GEMV; writes o1 = (alpha/rank) * B_o (A_o xba) which the Wo
+//                          GEMV's residual epilogue adds in the reference's order  x += (Wo xba + o1).
 // A-side dot products (length E) are wave tree sums (the reference's matmul adds sequentially: tolerance 1e-5);
 // the B-side (length rank), the scaling and the accumulation follow the reference's operation order exactly.
 #include "device_common.h"
@@ -38,44 +40,8 @@ __device__ __forceinline__ float lowrank_up(const float *B, uint32_t i, uint32_t
     return val * s;
 }
 
-__global__ __launch_bounds__(256) void lora_qkv_kernel(const LoraArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, E = a.E, KD = a.KD, rank = a.rank;
-    float *xb = sm, *t = sm + ((E + 3) & ~3u), *red = t + 3 * rank;
-    const float *x = a.x + (size_t)b * E;
-    float acc = 0.0f;                                   // rmsnorm (infer.c:601-614), tree order
-    for (uint32_t i = tid; i < E; i += 256u) acc += x[i] * x[i];
-    float ss = block_sum(acc, red);
-    ss /= (float)E; ss += 1e-5f; ss = 1.0f / sqrtf(ss);
-    for (uint32_t i = tid; i < E; i += 256u) xb[i] = a.norm_w[i] * (ss * x[i]);
-    __syncthreads();
-    lowrank_down(a.qa, rank, E, xb, t);
-    lowrank_down(a.ka, rank, E, xb, t + rank);
-    lowrank_down(a.va, rank, E, xb, t + 2 * rank);
-    __syncthreads();
-    const float s = (float)a.alpha / (float)rank;
-    float *q = a.q + (size_t)b * E, *k = a.kraw + (size_t)b * KD;
-    float *v = a.v + (size_t)b * a.v_bstride + (size_t)a.pos[b] * KD;
-    for (uint32_t i = tid; i < E; i += 256u) q[i] += lowrank_up(a.qb, i, rank, t, s);
-    for (uint32_t i = tid; i < KD; i += 256u) { k[i] += lowrank_up(a.kb, i, rank, t + rank, s); v[i] += lowrank_up(a.vb, i, rank, t + 2 * rank, s); }
-}
-
-__global__ __launch_bounds__(256) void lora_o_kernel(const LoraArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, E = a.E, rank = a.rank;
-    float *xba = sm, *t = sm + ((E + 3) & ~3u);
-    for (uint32_t i = tid; i < E; i += 256u) xba[i] = a.x[(size_t)b * E + i];
-    __syncthreads();
-    lowrank_down(a.qa, rank, E, xba, t);
-    __syncthreads();
-    const float s = (float)a.alpha / (float)rank;
-    for (uint32_t i = tid; i < E; i += 256u) a.q[(size_t)b * E + i] = lowrank_up(a.qb, i, rank, t, s);
-}
-
-// ---- the per-row forms: each row takes the module its KV slot is bound to (LoraSlotDesc, device memory) or none.  The arithmetic of a
-// row with a module is the two kernels' above, operation for operation (same helpers, same LDS roles; t and red sit behind xb at
-// offsets of the row's OWN rank): the same bits.  The descriptor is one load per workgroup of an address that depends on blockIdx
-// alone, so `rank == 0` is uniform and the early return comes before the first barrier.
+// A row's module is the descriptor of its KV slot: one load per workgroup of an address that depends on blockIdx alone, so `rank == 0`
+// is uniform and the early return comes before the first barrier.  t and red sit behind xb at offsets of the row's OWN rank.
 __global__ __launch_bounds__(256) void lora_qkv_rows_kernel(const LoraRowsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const uint32_t b = blockIdx.x, tid = threadIdx.x, E = a.E, KD = a.KD;
@@ -125,7 +91,9 @@ __global__ __launch_bounds__(256) void lora_o_rows_kernel(const LoraRowsArgs a) 
 
 }  // namespace
 
+// dynamic LDS in bytes: xb | t[3][rank] | red[32] (qkv), xba | t[rank] (o)
 static size_t lora_qkv_lds(uint32_t E, uint32_t rank) { return (((size_t)E + 3) & ~(size_t)3) * 4 + 3 * (size_t)rank * 4 + 32 * 4; }
+static size_t lora_o_lds(uint32_t E, uint32_t rank) { return (((size_t)E + 3) & ~(size_t)3) * 4 + (size_t)rank * 4; }
 const char *lora_shape_error(uint32_t E, uint32_t rank) {
     if (E == 0 || E % 4) return "LoRA side branches need n_embd % 4 == 0";
     if (rank == 0) return "LoRA rank 0";
@@ -133,19 +101,6 @@ const char *lora_shape_error(uint32_t E, uint32_t rank) {
     return nullptr;
 }
 
-hipError_t launch_lora_qkv(const LoraArgs &a, uint32_t nb, hipStream_t st) {
-    if (lora_shape_error(a.E, a.rank)) return hipErrorInvalidValue;
-    const size_t lds = lora_qkv_lds(a.E, a.rank);
-    hipLaunchKernelGGL(lora_qkv_kernel, dim3(nb), dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-// x = xba [nb][E] in, q = o1 [nb][E] out, qa / qb = the o pair
-hipError_t launch_lora_o(const LoraArgs &a, uint32_t nb, hipStream_t st) {
-    if (lora_shape_error(a.E, a.rank)) return hipErrorInvalidValue;
-    const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + (size_t)a.rank * 4;
-    hipLaunchKernelGGL(lora_o_kernel, dim3(nb), dim3(256), lds, st, a);
-    return hipGetLastError();
-}
 // LDS for the largest rank a descriptor may name (every stored rank passed lora_shape_error, so max_rank does)
 hipError_t launch_lora_qkv_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st) {
     if (!a.desc || lora_shape_error(a.E, a.max_rank)) return hipErrorInvalidValue;
@@ -154,9 +109,9 @@ hipError_t launch_lora_qkv_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t 
 }
 hipError_t launch_lora_o_rows(const LoraRowsArgs &a, uint32_t nb, hipStream_t st) {
     if (!a.desc || lora_shape_error(a.E, a.max_rank)) return hipErrorInvalidValue;
-    const size_t lds = (((size_t)a.E + 3) & ~(size_t)3) * 4 + (size_t)a.max_rank * 4;
-    hipLaunchKernelGGL(lora_o_rows_kernel, dim3(nb), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(lora_o_rows_kernel, dim3(nb), dim3(256), lora_o_lds(a.E, a.max_rank), st, a);
     return hipGetLastError();
 }
 
 }  // namespace nano
+

@@ -593,8 +593,9 @@ extern "C" int nano_hip_op_fused_gemv(int device, const NanoFusedGemvDesc *dp) {
     return 0;
 }
 
-// ---- the LoRA side-branch launches (lora.hip), LoraArgs filled as enqueue_step() fills them (backend_step.hip).  The arguments are checked
-// before a device is asked for.
+// ---- the LoRA side-branch launches (lora.hip), LoraRowsArgs filled as enqueue_step() fills them (backend_step.hip), with row b in "slot" b of
+// a descriptor array built from row_adapter (layer 0 of one-layer adapters).  Two front ends, each with its own argument check before a
+// device is asked for, and one body: the single-module operators are one adapter with every row bound to it.
 static const char *lora_desc_error(const NanoLoraOpDesc *d, bool qkv) {
     if (!d || !d->x || !d->a[0] || !d->b[0] || !d->q) return "lora: null argument";
     if (qkv && (!d->norm_w || !d->a[1] || !d->b[1] || !d->a[2] || !d->b[2] || !d->pos || !d->kraw || !d->v)) return "lora: null argument";
@@ -609,38 +610,6 @@ static const char *lora_desc_error(const NanoLoraOpDesc *d, bool qkv) {
     }
     return nullptr;
 }
-static int lora_op(int device, const NanoLoraOpDesc *d, bool qkv) {
-    if (const char *msg = lora_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
-    int rc; if ((rc = begin(device))) return rc;
-    const size_t E = d->E, KD = d->KD, r = d->rank;
-    DevBufs B;
-    LoraArgs la{};
-    la.x = B.upload(d->x, d->nb * E);
-    la.qa = B.upload(d->a[0], r * E); la.qb = B.upload(d->b[0], E * r);
-    la.q = B.upload(d->q, (size_t)d->q_floats);
-    OP_CHECK(la.x && la.qa && la.qb && la.q, "device alloc failed");
-    la.E = d->E; la.KD = d->KD; la.rank = d->rank; la.alpha = d->alpha;
-    if (qkv) {
-        la.norm_w = B.upload(d->norm_w, E);
-        la.ka = B.upload(d->a[1], r * E); la.kb = B.upload(d->b[1], KD * r); la.va = B.upload(d->a[2], r * E); la.vb = B.upload(d->b[2], KD * r);
-        la.kraw = B.upload(d->kraw, (size_t)d->k_floats); la.v = B.upload(d->v, (size_t)d->v_floats);
-        la.pos = B.upload(d->pos, d->nb); la.v_bstride = d->v_bstride;
-        OP_CHECK(la.norm_w && la.ka && la.kb && la.va && la.vb && la.kraw && la.v && la.pos, "device alloc failed");
-    }
-    OP_HIP(qkv ? launch_lora_qkv(la, d->nb, 0) : launch_lora_o(la, d->nb, 0));
-    OP_HIP(hipDeviceSynchronize());
-    OP_HIP(hipMemcpy(d->q, la.q, (size_t)d->q_floats * 4, hipMemcpyDeviceToHost));
-    if (qkv) {
-        OP_HIP(hipMemcpy(d->kraw, la.kraw, (size_t)d->k_floats * 4, hipMemcpyDeviceToHost));
-        OP_HIP(hipMemcpy(d->v, la.v, (size_t)d->v_floats * 4, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-extern "C" int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, true); }
-extern "C" int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, false); }
-
-// ---- the per-row forms: LoraRowsArgs as enqueue_step() fills them for a table, with row b in "slot" b of a descriptor array built from
-// row_adapter (layer 0 of one-layer adapters).  Checked before a device is asked for.
 static const char *lora_rows_desc_error(const NanoLoraRowsOpDesc *d, bool qkv) {
     if (!d || !d->x || !d->q || !d->adapters || !d->row_adapter) return "lora rows: null argument";
     if (qkv && (!d->norm_w || !d->pos || !d->kraw || !d->v)) return "lora rows: null argument";
@@ -662,8 +631,8 @@ static const char *lora_rows_desc_error(const NanoLoraRowsOpDesc *d, bool qkv) {
     }
     return nullptr;
 }
-static int lora_rows_op(int device, const NanoLoraRowsOpDesc *d, bool qkv) {
-    if (const char *msg = lora_rows_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+// the body behind both: d passed its front end's check
+static int lora_run(int device, const NanoLoraRowsOpDesc *d, bool qkv) {
     int rc; if ((rc = begin(device))) return rc;
     const size_t E = d->E, KD = d->KD;
     DevBufs B;
@@ -708,6 +677,22 @@ static int lora_rows_op(int device, const NanoLoraRowsOpDesc *d, bool qkv) {
     }
     return 0;
 }
+static int lora_op(int device, const NanoLoraOpDesc *d, bool qkv) {
+    if (const char *msg = lora_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    const NanoLoraAdapter ad{ d->rank, d->alpha, { d->a[0], d->a[1], d->a[2] }, { d->b[0], d->b[1], d->b[2] } };
+    const std::vector<uint32_t> rows(d->nb, 0u);
+    NanoLoraRowsOpDesc r{};
+    r.E = d->E; r.KD = d->KD; r.nb = d->nb; r.S = d->S; r.v_bstride = d->v_bstride; r.n_adapters = 1;
+    r.x = d->x; r.norm_w = d->norm_w; r.adapters = &ad; r.row_adapter = rows.data(); r.pos = d->pos;
+    r.q = d->q; r.kraw = d->kraw; r.v = d->v; r.q_floats = d->q_floats; r.k_floats = d->k_floats; r.v_floats = d->v_floats;
+    return lora_run(device, &r, qkv);
+}
+static int lora_rows_op(int device, const NanoLoraRowsOpDesc *d, bool qkv) {
+    if (const char *msg = lora_rows_desc_error(d, qkv)) { nano_hip_set_error_(msg); return NANO_HIP_EINVAL; }
+    return lora_run(device, d, qkv);
+}
+extern "C" int nano_hip_op_lora_qkv(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, true); }
+extern "C" int nano_hip_op_lora_o(int device, const NanoLoraOpDesc *d) { return lora_op(device, d, false); }
 extern "C" int nano_hip_op_lora_qkv_rows(int device, const NanoLoraRowsOpDesc *d) { return lora_rows_op(device, d, true); }
 extern "C" int nano_hip_op_lora_o_rows(int device, const NanoLoraRowsOpDesc *d) { return lora_rows_op(device, d, false); }
 

@@ -1,5 +1,5 @@
 """GPU tests of the two LoRA side-branch launches (nano_amd/csrc/lora.hip) through nano_hip_op_lora_qkv / nano_hip_op_lora_o, which fill
-LoraArgs as a decode step does: every element against the float64 reference within the derived bound of tests/lora_ref.py (held
+LoraRowsArgs as a decode step with one module in every slot does: every element against the float64 reference within the derived bound of tests/lora_ref.py (held
 against the kernels' emulated order, and shown to reject mutants, in tests/test_lora_ref.py), and bit for bit against the float32
 restatement of the reference's order on inputs whose A side is exact in any order.  Every buffer travels whole: rows of v other than
 (b, pos[b]), slots beyond nb and all guard rows must come back with the bits they went with.

@@ -1,11 +1,13 @@
-"""GPU tests of the two per-row LoRA launches (nano_amd/csrc/lora.hip lora_qkv_rows_kernel / lora_o_rows_kernel) through
-nano_hip_op_lora_qkv_rows / nano_hip_op_lora_o_rows, which fill LoraRowsArgs as a step with a LoRA table does.
+"""GPU tests of the two LoRA launches (nano_amd/csrc/lora.hip lora_qkv_rows_kernel / lora_o_rows_kernel) with rows of different
+modules, through nano_hip_op_lora_qkv_rows / nano_hip_op_lora_o_rows, which fill LoraRowsArgs as a step with a LoRA table does.
 
 Three adapters A, B, C of (rank, alpha) (5, 16), (8, 4), (1, 16) -- unequal ranks, an inexact scale, and the rank-1 case in which
 tests/lora_ref.py found the largest attainable error -- and five rows with row_adapter = [A, none, B, A, C], in the decode form (a v row
 per slot, distinct positions) and the chunk form (v_bstride 0, consecutive positions).  For every row with an adapter, q, k, its v row
 and o1 are
-  (a) bit for bit what the single-module operators (nano_hip_op_lora_qkv / _o) give that row alone with that adapter,
+  (a) bit for bit what the single-module operators (nano_hip_op_lora_qkv / _o) give that row alone with that adapter -- the same
+      kernels in a launch of one row and one adapter: a row's bits depend neither on the other rows, nor on the batch size, nor on
+      its adapter's index (what pins the kernels to the reference is tests/test_gpu_lora_ops.py),
   (b) bit for bit lora_ref.emulate_qkv / emulate_o on lora_ref.exact_inputs,
   (c) within lora_ref.exact_qkv / exact_o's derived bound, per element, on lora_ref.inputs.
 The row without an adapter keeps the bytes of q, k and its v row, and its o1 row is 0x80000000 (-0.0f) in every element.  Every other

@@ -85,7 +85,7 @@ def test_model_calls_check_before_any_device_work():
     set_ = src[src.index('extern "C" int nano_hip_lora_table_set'):src.index('extern "C" int nano_hip_lora_table_clear')]
     clear = src[src.index('extern "C" int nano_hip_lora_table_clear'):src.index('extern "C" int nano_hip_lora_bind(')]
     bind = src[src.index('extern "C" int nano_hip_lora_bind('):end]
-    for needle in ("!params", "id >= NANO_LORA_TABLE_MAX", "NANO_ARCH_NANO", "m->lora_buf", "lora_shape_error(m->d.n_embd, rank)", "n_floats < total", "lora_entry_bound(m, id)"):
+    for needle in ("!params", "id >= NANO_LORA_TABLE_MAX", "NANO_ARCH_NANO", "m->lt.at.buf", "lora_shape_error(m->d.n_embd, rank)", "n_floats < total", "lora_entry_bound(m, id)"):
         assert set_.index(needle) < set_.index("hipSetDevice"), needle
     for needle in ("id >= NANO_LORA_TABLE_MAX", "lora_entry_bound(m, id)"):
         assert clear.index(needle) < clear.index("hipSetDevice"), needle

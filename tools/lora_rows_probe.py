@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""What the LoRA table costs against the single-module path it generalises.  Nano-168M shapes, synthetic FP32 weights, max_seq_len 512,
+"""What the LoRA table costs against one attached module.  Nano-168M shapes, synthetic FP32 weights, max_seq_len 512,
 64 KV slots, modules of rank 8.  Four models in one process:
   1. no module;
-  2. one module through nano_hip_lora_attach (the path before the table existed);
+  2. one module through nano_hip_lora_attach (the same launches, its descriptor in every slot);
   3. a table of one entry, bound to every slot;
   4. a table of 8 entries, bound round-robin.
 Per model: a decode step of 8 and of 64 sequences at position 20 (arg-max only; --steps steps per timing, host clock around them and a
