@@ -333,6 +333,18 @@ void nano_set_phase_observation(int on);
  * calls whose (pos, output_ids[pos]) continue them return from the queue without device work.  Any other call drops the queue.  The
  * ids are nano_hip_decode_lookup's (see there for what that promises on wide matrices).  0 = today's path. */
 void nano_set_lookup_draft(int max_draft);
+/* Greedy decode with a draft model (nano_mi355x.h nano_hip_decode_draft), opt-in: with a model file's path and max_draft = 1 .. 15 (or
+ * NANO_DRAFT_MODEL=<path> together with NANO_DRAFT_LEN=n in the environment, read once) the greedy branch of generate_next_token runs one
+ * round of that loop per call: the draft model's ids are verified by one chunk of the model, and the confirmed ids beyond the returned one
+ * go into the queue of the lookup drafts above, with the same rules.  Where both switches are set the draft model is used.  The draft is
+ * opened on the first such call of each model, on that model's device and with its max_seq_len; the engine remembers which ids the draft
+ * holds and feeds it the rest of output_ids itself.  A draft whose vocabulary size differs is refused when it is opened, with a message
+ * on stderr (generate_next_token then exits, as it does when an upload fails).  The ids are nano_hip_decode_draft's: the model's own
+ * greedy ids whatever the draft is.  path = NULL or max_draft = 0 switches it off.  Returns 0, or NANO_HIP_EINVAL for a max_draft outside
+ * 1 .. 15 or an unusable path (the switch is then off). */
+int nano_set_draft_model(const char *path, int max_draft);
+/* Opens ctx's model's draft now instead of on first use: 0, or the NANO_HIP_E* code of what refused it (message on stderr). */
+int nano_draft_model_open(Nano_Context *ctx);
 /* Opaque device model behind an LLM (NanoHipModel*, nano_mi355x.h) for measurement tools. */
 void *nano_device_model(const LLM *llm);
 

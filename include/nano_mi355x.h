@@ -365,6 +365,52 @@ int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uin
                             const NanoHipLookupParams *params, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
                             uint32_t *next_tokens_out, uint32_t *next_pos_out);
 
+/* ---- greedy decode with a draft model: several ids per read of the target's weights (opt-in) ----
+ * Two resident models with one vocabulary on one device.  A round: the draft model runs D' one-row greedy loop steps from the last id,
+ * the target verifies [last id, d1 .. dD'] as one chunk of D' + 1 rows and accepts rows exactly as nano_hip_decode_lookup does, so every
+ * emitted id is the arg-max of a target row whose whole prefix is emitted ids: the output is nano_hip_decode_lookup's -- and, with the
+ * caveat stated there for wide matrices, nano_hip_decode_greedy's -- for ANY draft model; only the number of rounds depends on it.
+ * D' = min(max_draft, 63 - (n-1) % 64, left - 1, room below both models' max_seq_len and RoPE tables), n the history's length: a chunk
+ * stays inside one 64-position bucket.  D' = 0 is a plain one-row target step (the draft falls behind and catches up later).
+ * The draft holds `draft_held` leading positions of the history in ITS slot 0; the call feeds it what it lacks (hist[dn .. n-2], from
+ * the device history, batched prefill without outputs) before it drafts: a caller never ingests the prompt into the draft by hand.
+ * Between the models' steps runs draft.hip's kernel; the models' streams are ordered by events; the host waits once per round, for
+ * the 32-byte record.  max_draft is clipped to the target's nano_hip_prefill_chunk_tokens() - 1.  A target in strict or exact mode
+ * runs plain reference-order steps (max_draft treated as 0, the draft untouched).  The draft may use any quantisation and any KV cache. */
+typedef struct NanoHipDraftParams {
+    uint32_t max_draft;   /* 0 .. 15 drafted ids per round; 0 = plain target steps only */
+    uint32_t stop_token;  /* UINT32_MAX = none */
+    uint32_t max_rounds;  /* 0 = no limit */
+    uint32_t draft_held;  /* leading positions of `history` that the draft's slot 0 already holds (0 = none) */
+} NanoHipDraftParams;
+typedef struct NanoHipDraftStats {
+    uint32_t rounds_plain, rounds_verify;
+    uint32_t drafted, accepted, emitted;
+    uint32_t draft_rows_fed;   /* catch-up rows fed to the draft, prompt included */
+    uint32_t draft_held;       /* what to pass as draft_held when the call is continued */
+} NanoHipDraftStats;
+/* The target's contract is nano_hip_decode_lookup's: slot 0 holds positions 0 .. n_history-2, history[n_history-1] is fed first, the
+ * device history is kept between calls (and shared with nano_hip_decode_lookup), the same state is left behind.  Afterwards the draft's
+ * slot 0 holds valid rows for stats->draft_held positions of history + out_ids.
+ * NANO_HIP_EINVAL before anything is queued in either model: everything nano_hip_decode_lookup refuses (its n-gram parameters aside),
+ * a null draft, draft == target, different devices, different vocab_size, max_draft > 15, draft_held > n_history - 1 or beyond the
+ * draft's max_seq_len, a draft in strict or exact mode or with LoRA on.  max_new == 0 returns 0 and touches nothing.
+ * A hand-off that gave up in either model re-issues the whole call once, the draft fed from position 0 again. */
+int nano_hip_decode_draft(NanoHipModel *target, NanoHipModel *draft, const uint32_t *history, uint32_t n_history,
+                          uint32_t max_new, const NanoHipDraftParams *p, uint32_t *out_ids, uint32_t *n_out, NanoHipDraftStats *stats);
+/* Measurement (tools/draft_probe.py): with NANO_DRAFT_TIMING=1 in the environment at the target's first nano_hip_decode_draft call, every
+ * drafted round is bracketed by timing events; this returns the summed milliseconds of {catch-up, the draft's steps, stage + verify chunk
+ * + accept} and the number of rounds since the last query, and resets them.  Without the switch: zeros. */
+int nano_hip_draft_phase_ms(NanoHipModel *target, double out_ms[3], uint32_t *rounds);
+/* The between-steps kernel alone (draft.hip; host pointers; operator tests): its STAGE role on fed[1 .. nb), then its ACCEPT role.
+ * history[0..n) in, room for n + 16 ids; the device history's capacity is min(n + 16, seq_limit + 1) rounded up to 4.  fed / amax [nb]
+ * describe the round it follows (nb = 0 .. 16; 0: none has run), dn = positions the draft held before it.  record_out[8] = {emitted,
+ * accepted, nb_next, n, dn, cursor, done, left}; next_tokens_out / next_pos_out [16] = row 0 and the positions of the next round
+ * (next_tokens_out[1 .. nb) are what STAGE put there; untouched entries are UINT32_MAX).  NANO_HIP_EINVAL: null pointers, n == 0 or n > 65536, nb > 16, max_draft > 15, dn > n - 1. */
+int nano_hip_op_draft_round(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
+                            const NanoHipDraftParams *params, uint32_t left, uint32_t seq_limit, uint32_t dn, uint32_t *record_out,
+                            uint32_t *next_tokens_out, uint32_t *next_pos_out);
+
 /* ---- ragged steps: rows of several KV slots share one weight read --------------------------------------------------
  * A step whose rows each carry their own (slot, position): several prompts in one chunk, a new prompt joining running sequences, one
  * greedy step for sequences in ANY slots, drafts of several sequences verified at once.  A segment names positions

@@ -195,6 +195,20 @@ LOOKUP_RECORD_FIELDS = ("emitted", "accepted", "nb_next", "n", "match_len", "mat
 LOOKUP_NO_STOP = 0xFFFFFFFF
 
 
+class NanoHipDraftParams(C.Structure):
+    """include/nano_mi355x.h NanoHipDraftParams: greedy decode with a draft model (max_rounds 0 = no limit; stop_token 0xffffffff = none)."""
+    _fields_ = [(n, C.c_uint32) for n in ("max_draft", "stop_token", "max_rounds", "draft_held")]
+
+
+class NanoHipDraftStats(C.Structure):
+    """include/nano_mi355x.h NanoHipDraftStats (draft_held: what to pass as draft_held when the call is continued)."""
+    _fields_ = [(n, C.c_uint32) for n in ("rounds_plain", "rounds_verify", "drafted", "accepted", "emitted", "draft_rows_fed", "draft_held")]
+
+
+# the words of the record nano_hip_op_draft_round returns (nano_amd/csrc/kernels.h DRAFT_REC_*)
+DRAFT_RECORD_FIELDS = ("emitted", "accepted", "nb_next", "n", "dn", "cursor", "done", "left")
+
+
 PHASE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)        # nano_hip_phase_fn(env, layer, phase)
 
 
@@ -234,6 +248,8 @@ def lib() -> C.CDLL:
     fn("nano_hip_decode_lookup", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(NanoHipLookupParams), vp, C.POINTER(C.c_uint32), C.POINTER(NanoHipLookupStats)])
     fn("nano_hip_verify_draft", C.c_int, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)])
     fn("nano_hip_op_lookup_step", C.c_int, [C.c_int, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(NanoHipLookupParams), C.c_uint32, C.c_uint32, vp, vp, vp])
+    fn("nano_hip_decode_draft", C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(NanoHipDraftParams), vp, C.POINTER(C.c_uint32), C.POINTER(NanoHipDraftStats)])
+    fn("nano_hip_op_draft_round", C.c_int, [C.c_int, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(NanoHipDraftParams), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp])
     fn("nano_hip_lora_attach", C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t])
     fn("nano_hip_lora_enable", C.c_int, [vp, C.c_int])
     fn("nano_hip_forward_sample", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(NanoHipSample)])
@@ -657,6 +673,19 @@ class DeviceModel:
         n, st = C.c_uint32(0), NanoHipLookupStats()
         check(lib().nano_hip_decode_lookup(self.h, h.ctypes.data if h.size else None, h.size, max_new, C.byref(p), out.ctypes.data, C.byref(n), C.byref(st)))
         return out[:n.value].copy(), {k: int(getattr(st, k)) for k, _ in NanoHipLookupStats._fields_}
+
+    def decode_draft(self, draft: "DeviceModel", history: Sequence[int], max_new: int, max_draft: int = 4, stop_token: Optional[int] = None,
+                     max_rounds: int = 0, draft_held: int = 0):
+        """Greedy decode of slot 0 with `draft` as the draft model (nano_hip_decode_draft): this model's slot 0 holds positions
+        0 .. len(history)-2, history[-1] is fed first; the draft's slot 0 holds the first draft_held positions and is fed the rest by the
+        call.  Returns (ids uint32[<= max_new], stats dict of NanoHipDraftStats' fields; pass stats["draft_held"] on to continue)."""
+        h = np.ascontiguousarray(history, np.uint32).reshape(-1)
+        p = NanoHipDraftParams(max_draft, LOOKUP_NO_STOP if stop_token is None else stop_token, max_rounds, draft_held)
+        out = np.zeros(max(max_new, 1), np.uint32)
+        n, st = C.c_uint32(0), NanoHipDraftStats()
+        check(lib().nano_hip_decode_draft(self.h, None if draft is None else draft.h, h.ctypes.data if h.size else None, h.size, max_new, C.byref(p),
+                                          out.ctypes.data, C.byref(n), C.byref(st)))
+        return out[:n.value].copy(), {k: int(getattr(st, k)) for k, _ in NanoHipDraftStats._fields_}
 
     def verify_draft(self, tokens: Sequence[int], pos0: int = 0, slot: int = 0):
         """prefill() that returns every fed row's arg-max (nano_hip_verify_draft): tokens[0] the last committed id, tokens[1:] a draft.
@@ -1468,6 +1497,26 @@ def op_lookup_step(history, fed=(), amax=(), *, left, max_draft=7, ngram_max=3, 
     check(lib().nano_hip_op_lookup_step(device, buf.ctypes.data, h.size, f.ctypes.data if f.size else None, g.ctypes.data if g.size else None, f.size,
                                         C.byref(p), left, min(seq_limit, 0xFFFFFFFF), rec.ctypes.data, nt.ctypes.data, npos.ctypes.data))
     r = dict(zip(LOOKUP_RECORD_FIELDS, (int(v) for v in rec)))
+    return r, buf[:r["n"]].copy() if h.size <= r["n"] <= buf.size else buf, nt, npos
+
+
+def op_draft_round(history, fed=(), amax=(), *, left, dn=0, max_draft=4, stop_token=None, seq_limit=1 << 30, device=0):
+    """draft_round_kernel alone (nano_hip_op_draft_round): its STAGE role on fed[1:], then its ACCEPT role behind a round that fed `fed` and
+    left the row arg-maxes `amax` (both empty: no round has run yet); dn = positions the draft held before it.  Returns (record dict of
+    DRAFT_RECORD_FIELDS, the history with the emitted ids appended, next tokens, next positions -- the latter two all 16 words: row 0 and
+    the next round's positions; next tokens 1 .. len(fed)-1 are what STAGE put there, every other word is 0xffffffff)."""
+    h = np.ascontiguousarray(history, np.uint32).reshape(-1)
+    f = np.ascontiguousarray(fed, np.uint32).reshape(-1)
+    g = np.ascontiguousarray(amax, np.uint32).reshape(-1)
+    if f.size != g.size:
+        raise ValueError(f"{f.size} fed ids but {g.size} arg-maxes")
+    buf = np.full(h.size + 16, 0xFFFFFFFF, np.uint32)
+    buf[:h.size] = h
+    p = NanoHipDraftParams(max_draft, LOOKUP_NO_STOP if stop_token is None else stop_token, 0, 0)
+    rec, nt, npos = np.zeros(8, np.uint32), np.zeros(16, np.uint32), np.zeros(16, np.uint32)
+    check(lib().nano_hip_op_draft_round(device, buf.ctypes.data, h.size, f.ctypes.data if f.size else None, g.ctypes.data if g.size else None, f.size,
+                                        C.byref(p), left, min(seq_limit, 0xFFFFFFFF), dn, rec.ctypes.data, nt.ctypes.data, npos.ctypes.data))
+    r = dict(zip(DRAFT_RECORD_FIELDS, (int(v) for v in rec)))
     return r, buf[:r["n"]].copy() if h.size <= r["n"] <= buf.size else buf, nt, npos
 
 

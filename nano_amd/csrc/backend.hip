@@ -75,6 +75,7 @@ static void destroy(NanoHipModel *m) {
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
     lookup_free(m);
+    draft_free(m);
     rows_free(m);
     kv_image_free(m);
     for (hipEvent_t ev : { m->ev0, m->ev1, m->ev2 }) if (ev) (void)hipEventDestroy(ev);

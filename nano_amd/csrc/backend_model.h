@@ -130,6 +130,16 @@ struct NanoHipModel {
         uint32_t *h_rec = nullptr;                        // pinned: the record of the last step
         bool graph = true;                                // verify chunks of the loop replay a graph per (K, range bucket); NANO_LOOKUP_GRAPH=0: eager
     } lk;
+    // greedy decode with a draft model (backend_draft.hip), on the TARGET, allocated on the first call; the history, the state and the
+    // record are lk's
+    struct Draft {
+        uint32_t *iota = nullptr;                         // [lk.cap] 0, 1, 2, ..: the positions of the draft's catch-up rows are copied from here
+        hipEvent_t ev_t = nullptr, ev_d = nullptr;        // the target's stream has the history up | the draft's stream has the round's ids
+        // measurement (NANO_DRAFT_TIMING=1, read on the first call; tools/draft_probe.py): events around a drafted round's three parts and their summed times
+        bool timing = false;
+        hipEvent_t tm[4] = {nullptr, nullptr, nullptr, nullptr};   // draft stream: before the catch-up | before the draft's steps | behind them; target stream: behind ACCEPT
+        double ms[3] = {0, 0, 0}; uint32_t timed = 0;     // catch-up | draft steps | stage + chunk + accept, over `timed` drafted rounds
+    } dr;
     // ragged steps (nano_hip_step_rows, backend_rows.hip): rows that each carry their own (slot, position)
     struct Rows {
         using Group = RowGroup;                           // (step_spec.h; a call keeps its passes' groups itself: StepSpec::groups)
@@ -276,6 +286,7 @@ int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t
 hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, const RowWant &want, uint32_t last_pos, bool replay);
 int lookup_scratch(NanoHipModel *m);                   // backend_lookup.hip
 void lookup_free(NanoHipModel *m);
+void draft_free(NanoHipModel *m);                      // backend_draft.hip
 // THE re-issue policy of every entry point that hands results over (round-6 advice: correctness after a give-up depends on every one of
 // them re-issuing at the same positions).  attempt(again) queues the call's work and synchronises the stream; an error it returns is
 // the call's, without a look at the sticky word.  A hand-off that gave up gets the same work once more (again = true: same tokens,

@@ -76,6 +76,9 @@ typedef struct ModelEntry {
     /* NANO_LOOKUP_DRAFT: ids a verify chunk confirmed beyond the one its call returned.  la_ids[la_at .. la_at + la_n) are what the
      * greedy calls at positions la_pos, la_pos + 1, .. return, provided the id fed there is the one before them (la_prev) */
     uint32_t la_ids[16], la_at, la_n, la_pos, la_prev; const void *la_lora;
+    /* NANO_DRAFT_MODEL: the draft model of this model (opened on first use), the setting it was opened under, and the ids of the
+     * draft_held leading positions its slot 0 holds (a history that departs from them is fed to the draft again from there) */
+    NanoHipModel *draft; int draft_gen; uint32_t draft_held; uint32_t *draft_ids;
 } ModelEntry;
 static ModelEntry g_reg[MAX_MODELS];
 
@@ -112,6 +115,84 @@ static void la_clear(ModelEntry *me) { if (me) me->la_n = 0; }
 static void die_hip(const char *what) {
     fprintf(stderr, "%s: %s\n", what, nano_hip_last_error());
     exit(EXIT_FAILURE);
+}
+
+/* Greedy decode with a draft model (include/nano_mi355x.h nano_hip_decode_draft), opt-in: NANO_DRAFT_MODEL=<path> with
+ * NANO_DRAFT_LEN=D (1 .. 15), read once, or nano_set_draft_model().  It serves the greedy branch of generate_next_token only and feeds
+ * the look-ahead queue of the lookup drafts; where both are set the draft model is used.  g_draft_gen counts the settings: a model entry
+ * whose draft was opened under an earlier one closes it. */
+static char g_draft_path[4096];
+static int g_draft_len = -1, g_draft_gen = 0;
+static uint32_t draft_model_len(void) {
+    if (g_draft_len < 0) {
+        const char *path = getenv("NANO_DRAFT_MODEL"), *e = getenv("NANO_DRAFT_LEN");
+        const long v = e ? strtol(e, NULL, 0) : 0;
+        g_draft_len = 0;
+        if (path && *path && strlen(path) < sizeof g_draft_path && v >= 1 && v <= 15) { strcpy(g_draft_path, path); g_draft_len = (int)v; }
+    }
+    return (uint32_t)g_draft_len;
+}
+int nano_set_draft_model(const char *path, int max_draft) {
+    g_draft_gen++;
+    g_draft_len = 0; g_draft_path[0] = 0;
+    if (!path || max_draft == 0) return 0;
+    if (max_draft < 1 || max_draft > 15 || !*path || strlen(path) >= sizeof g_draft_path) {
+        fprintf(stderr, "nano_set_draft_model: max_draft outside 1 .. 15, or no usable path\n");
+        return NANO_HIP_EINVAL;
+    }
+    strcpy(g_draft_path, path); g_draft_len = max_draft;
+    return 0;
+}
+static void draft_close(ModelEntry *me) {
+    if (me->draft) nano_hip_model_destroy(me->draft);
+    free(me->draft_ids);
+    me->draft = NULL; me->draft_ids = NULL; me->draft_held = 0;
+}
+/* the draft of `me` under the current setting: opened on the target's device with the target's max_seq_len and one sequence.  0, or a
+ * NANO_HIP_E* code with the message on stderr (a file that cannot be read, another vocabulary size, a failed upload) */
+static int draft_open(ModelEntry *me) {
+    if (me->draft && me->draft_gen == g_draft_gen) return 0;
+    draft_close(me);
+    if (!draft_model_len()) { fprintf(stderr, "draft model: none is set\n"); return NANO_HIP_EINVAL; }
+    int fd = open(g_draft_path, O_RDONLY);
+    struct stat st;
+    if (fd == -1 || fstat(fd, &st) != 0 || (size_t)st.st_size < 260) {
+        fprintf(stderr, "draft model: cannot read %s\n", g_draft_path);
+        if (fd != -1) close(fd);
+        return NANO_HIP_EINVAL;
+    }
+    uint8_t *buf = (uint8_t *)mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (buf == MAP_FAILED) { fprintf(stderr, "draft model: mmap of %s failed\n", g_draft_path); return NANO_HIP_ERUNTIME; }
+    uint32_t h[17], tok_bytes;
+    memcpy(h, buf, sizeof h);                          /* the header of load_llm_from_buffer */
+    memcpy(&tok_bytes, buf + 256, 4);
+    NanoModelDesc d;
+    d.arch = h[4]; d.block_size = h[6]; d.vocab_size = h[7]; d.n_layer = h[8]; d.n_embd = h[9]; d.n_head = h[10]; d.n_kv_head = h[11];
+    d.n_hidden = h[12]; d.is_shared_classifier = h[13]; d.head_dim = h[14];
+    d.quant_type = (h[15] == QUANT_TYPE_F32 || h[15] == QUANT_TYPE_Q80 || h[15] == QUANT_TYPE_Q4K) ? h[15] : QUANT_TYPE_Q80;
+    d.group_size = h[16];
+    int rc = 0;
+    if (d.vocab_size != me->desc.vocab_size) {
+        fprintf(stderr, "draft model: %s has a vocabulary of %u ids, the model it would draft for one of %u: refused\n", g_draft_path, d.vocab_size, me->desc.vocab_size);
+        rc = NANO_HIP_EINVAL;
+    } else if (256 + (size_t)tok_bytes >= (size_t)st.st_size) {
+        fprintf(stderr, "draft model: %s is not a model file\n", g_draft_path);
+        rc = NANO_HIP_EINVAL;
+    } else {
+        me->draft_ids = (uint32_t *)calloc((size_t)me->max_seq_len + 1, sizeof(uint32_t));
+        if (!me->draft_ids) { fprintf(stderr, "mem alloc failed!\n"); exit(EXIT_FAILURE); }
+        rc = nano_hip_model_create(&me->draft, &d, buf + 256 + tok_bytes, (size_t)st.st_size - 256 - tok_bytes, 0, nano_hip_model_device(me->dev), me->max_seq_len, 1);
+        if (rc != NANO_HIP_OK) { fprintf(stderr, "draft model: upload of %s failed: %s\n", g_draft_path, nano_hip_last_error()); draft_close(me); }
+    }
+    munmap(buf, (size_t)st.st_size);                   /* the weights live in HBM now */
+    me->draft_gen = g_draft_gen; me->draft_held = 0;
+    return rc;
+}
+int nano_draft_model_open(Nano_Context *ctx) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    if (!me || !me->dev) { fprintf(stderr, "nano_draft_model_open: model is not resident on a device\n"); return NANO_HIP_EINVAL; }
+    return draft_open(me);
 }
 
 /* =====================================================================================================
@@ -217,6 +298,7 @@ void load_llm(LLM *llm, Tokenizer *tk, char *model_path, uint32_t max_seq_len) {
 void free_llm(LLM *llm, Tokenizer *tk) {
     ModelEntry *me = reg_entry(llm);
     NanoHipModel *dev = me ? me->dev : NULL;
+    if (me) draft_close(me);
     if (me) for (int r = 1; r < me->n_replica; r++) nano_hip_model_destroy(me->replica[r]);
     if (dev) nano_hip_model_destroy(dev);
     reg_del(llm);
@@ -880,7 +962,8 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
     NanoHipModel *dev = me ? me->dev : NULL;
     if (!dev) { fprintf(stderr, "generate_next_token: model is not resident on a device\n"); exit(EXIT_FAILURE); }
     uint32_t token = output_ids[pos];
-    const uint32_t draft = lookup_draft();
+    const uint32_t dm_len = draft_model_len();           /* a draft model goes before the lookup drafts */
+    const uint32_t draft = dm_len ? dm_len : lookup_draft();
     const HostEdit *ed = ctx_edit(ctx);                  /* the context's logit edit (decode positions only), or NULL */
     const int greedy = !phase_mode(ctx) && is_prefilling != 1 && sp->temperature == 0.0f && sp->repetition_penalty == 1.0f && !ed;
     if (draft && greedy && me->la_n && pos == me->la_pos && token == me->la_prev && ctx->lora == me->la_lora) {
@@ -917,6 +1000,26 @@ uint32_t generate_next_token(Nano_Context *ctx, uint32_t *output_ids, uint32_t p
         uint32_t best = 0;                                 /* x/1.0f is exact: arg-max on the device */
         observe(ctx, -1, NANO_LLM_PHASE_EMBEDDING);
         const uint32_t lim = me->max_seq_len < llm->config.block_size ? me->max_seq_len : llm->config.block_size;
+        if (dm_len && pos < lim) {
+            /* one round of the draft loop: the draft model's ids verified by one chunk of the model, the confirmed ids beyond the one
+             * returned queued exactly as the lookup branch below queues them.  The draft is fed whatever of output_ids[0 .. pos) it does
+             * not hold: draft_ids remembers what it holds, so a history the caller changed is fed again from where it departs. */
+            if (draft_open(me) != NANO_HIP_OK) { fprintf(stderr, "generate_next_token: the draft model cannot be used\n"); exit(EXIT_FAILURE); }
+            uint32_t held = me->draft_held < pos ? me->draft_held : pos, same = 0;
+            while (same < held && me->draft_ids[same] == output_ids[same]) same++;
+            const NanoHipDraftParams dp = { dm_len, UINT32_MAX, 1, same };
+            const uint32_t max_new = lim - pos < dm_len + 1 ? lim - pos : dm_len + 1;
+            uint32_t ids[16] = { 0 }, n = 0;
+            NanoHipDraftStats ds;
+            me->draft_held = 0;
+            if (nano_hip_decode_draft(dev, me->draft, output_ids, pos + 1, max_new, &dp, ids, &n, &ds) != NANO_HIP_OK || n == 0) die_hip("generate_next_token (draft model)");
+            for (uint32_t i = 0; i < ds.draft_held && i <= me->max_seq_len; i++) me->draft_ids[i] = i <= pos ? output_ids[i] : ids[i - pos - 1];
+            me->draft_held = ds.draft_held <= me->max_seq_len ? ds.draft_held : 0;
+            memcpy(me->la_ids, ids, sizeof ids);
+            me->la_at = 1; me->la_n = n - 1; me->la_pos = pos + 1; me->la_prev = ids[0]; me->la_lora = ctx->lora;
+            observe(ctx, -1, NANO_LLM_PHASE_SAMPLE);
+            return ids[0];
+        }
         if (draft && pos < lim) {
             /* one step of the lookup loop: a plain step, or a verify chunk that confirms up to `draft` ids beyond the one returned */
             const NanoHipLookupParams lp = { draft, 3, 1, UINT32_MAX, 1 };

@@ -608,4 +608,37 @@ struct LookupArgs {
 };
 hipError_t launch_lookup_step(const LookupArgs &a, hipStream_t st);
 
+// ---- greedy decode with a draft model (draft.hip): what happens between the two models' steps of a round, one workgroup ----
+// A round feeds the target [hist[n-1], d1 .. dD'] at positions n-1 .. n-1+D' (tests/draft_ref.py restates the
+// definitions).  One kernel, three roles:
+//   STAGE    behind the draft's D' MODE_LOOP steps: their ids (the draft's trace) become rows 1 .. D' of the target's tokens
+//   ACCEPT   behind the target's step: accept / clip / stop / append as lookup.hip's, the new dn (positions the draft holds), the next
+//            round's row count by the bucket rule, row 0 and the positions of the next round for the target, row 0 for the draft
+//   BEGIN    behind a catch-up chunk of the draft (which used its token / position rows): the draft's row 0 once more
+enum { DRAFT_ROLE_STAGE = 0, DRAFT_ROLE_ACCEPT = 1, DRAFT_ROLE_BEGIN = 2 };
+enum { DRAFT_REC_EMITTED = 0, DRAFT_REC_ACCEPTED, DRAFT_REC_NB_NEXT, DRAFT_REC_N, DRAFT_REC_DN, DRAFT_REC_CURSOR, DRAFT_REC_DONE, DRAFT_REC_LEFT, DRAFT_REC_WORDS };
+struct DraftArgs {
+    uint32_t role;
+    uint32_t *hist; uint32_t cap;                 // as LookupArgs
+    uint32_t *state;                              // as LookupArgs
+    const uint32_t *fed, *amax; uint32_t nb;      // ACCEPT: the step this launch follows.  STAGE: nb - 1 ids are staged
+    const uint32_t *ids;                          // STAGE: the draft's ids [nb - 1]
+    uint32_t max_draft, stop_token;
+    uint32_t seq_limit;                           // min over both models of (max_seq_len, RoPE rows)
+    uint32_t dn;                                  // ACCEPT: positions of the history the draft held before this round
+    uint32_t *next_tokens, *next_pos;             // [LOOKUP_MAX_ROWS] the target's rows of the next round
+    uint32_t *d_tokens, *d_pos, *d_pos0;          // the draft's row 0, and where its loop's trace index starts (nullptr: there is no draft to stage)
+    uint32_t *trace; uint32_t trace_cap;          // as LookupArgs
+    uint32_t *record;                             // [DRAFT_REC_WORDS]
+};
+// rows of the round that starts at a history of n ids with `left` ids to emit (0: none -- left == 0): 1 + D'
+__host__ __device__ inline uint32_t draft_round_rows(uint32_t n, uint32_t left, uint32_t max_draft, uint32_t seq_limit) {
+    if (left == 0 || n == 0) return 0;
+    uint32_t d = max_draft < LOOKUP_MAX_ROWS - 1 ? max_draft : LOOKUP_MAX_ROWS - 1;
+    const uint32_t bucket = 63u - (n - 1u) % 64u, room = seq_limit > n ? seq_limit - n : 0u;    // the chunk inside one 64-position bucket; n - 1 + D' < seq_limit
+    d = d < bucket ? d : bucket; d = d < left - 1u ? d : left - 1u; d = d < room ? d : room;
+    return d + 1u;
+}
+hipError_t launch_draft_round(const DraftArgs &a, hipStream_t st);
+
 }  // namespace nano

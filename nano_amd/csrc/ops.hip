@@ -318,6 +318,41 @@ extern "C" int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n
     return 0;
 }
 
+// the between-steps kernel of greedy decode with a draft model alone (draft.hip): STAGE on fed[1 .. nb), then ACCEPT.  The arguments
+// are checked before a device is asked for.
+extern "C" int nano_hip_op_draft_round(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
+                                       const NanoHipDraftParams *p, uint32_t left, uint32_t seq_limit, uint32_t dn, uint32_t *record_out,
+                                       uint32_t *next_tokens_out, uint32_t *next_pos_out) {
+    if (!history || !p || !record_out || !next_tokens_out || !next_pos_out || (nb && (!fed || !amax))) { nano_hip_set_error_("draft_round: null argument"); return NANO_HIP_EINVAL; }
+    if (n == 0 || n > 65536u || nb > LOOKUP_MAX_ROWS) { nano_hip_set_error_("draft_round: n outside 1 .. 65536, or more than 16 rows"); return NANO_HIP_EINVAL; }
+    if (p->max_draft > LOOKUP_MAX_ROWS - 1 || dn > n - 1) { nano_hip_set_error_("draft_round: max_draft beyond 15, or dn beyond n - 1"); return NANO_HIP_EINVAL; }
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B;
+    DraftArgs a{};
+    const uint32_t room = n + LOOKUP_MAX_ROWS, full = seq_limit < room ? seq_limit + 1u : room;      // the loop's history holds max_seq_len + 1 ids
+    a.cap = ((full > n ? full : n) + 3u) & ~3u;
+    a.hist = B.alloc<uint32_t>(a.cap > room ? a.cap : room);
+    const uint32_t st[4] = { n, left, 0u, 0u };
+    a.state = B.upload(st, 4);
+    uint32_t *toks = B.alloc<uint32_t>(LOOKUP_MAX_ROWS);
+    a.fed = toks; a.amax = nb ? B.upload(amax, nb) : nullptr; a.ids = nb > 1 ? B.upload(fed + 1, nb - 1) : nullptr; a.nb = nb;
+    a.max_draft = p->max_draft; a.stop_token = p->stop_token; a.seq_limit = seq_limit; a.dn = dn;
+    a.next_tokens = toks; a.next_pos = B.alloc<uint32_t>(LOOKUP_MAX_ROWS); a.record = B.alloc<uint32_t>(DRAFT_REC_WORDS);
+    OP_CHECK(a.hist && a.state && toks && (!nb || a.amax) && (nb < 2 || a.ids) && a.next_pos && a.record, "device alloc failed");
+    OP_HIP(hipMemset(a.hist, 0xff, (size_t)(a.cap > room ? a.cap : room) * 4));
+    OP_HIP(hipMemcpy(a.hist, history, (size_t)n * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemset(toks, 0xff, LOOKUP_MAX_ROWS * 4)); OP_HIP(hipMemset(a.next_pos, 0xff, LOOKUP_MAX_ROWS * 4));
+    if (nb) OP_HIP(hipMemcpy(toks, fed, 4, hipMemcpyHostToDevice));          // row 0: what the ACCEPT launch of the round before staged
+    if (nb > 1) { a.role = DRAFT_ROLE_STAGE; OP_HIP(launch_draft_round(a, 0)); }
+    a.role = DRAFT_ROLE_ACCEPT;
+    OP_HIP(launch_draft_round(a, 0));
+    OP_HIP(hipMemcpy(record_out, a.record, DRAFT_REC_WORDS * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(history, a.hist, (size_t)room * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_tokens_out, toks, LOOKUP_MAX_ROWS * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_pos_out, a.next_pos, LOOKUP_MAX_ROWS * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // what is wrong with the SHAPE fields of a fused-gemv descriptor (no pointer but norm_w / attn_part / resid_add, read as flags), or nullptr
 static const char *fused_desc_shape_error(const NanoFusedGemvDesc &d) {
     if (d.kind > 2 || d.nseg == 0 || d.nseg > 3 || (d.kind == 2 && d.nseg != 2) || d.nb == 0 || d.nb > NANO_MAX_BATCH || d.n % 4) return "bad fused-gemv descriptor";
