@@ -917,7 +917,9 @@ int nano_hip_f32_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
 #define NANO_F32_GEMM_PLAN_WORDS 17
 int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_F32_GEMM_PLAN_WORDS]);
 /* The Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, role, gs, B, nv, upw, rw, nw,
- * grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}.  route: the router's choice with the step's scratch present (the value
+ * grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes, cw}.  cw = 1 (the new 17th word; words 0 .. 15 are what they were):
+ * the residual launch behind split attention runs gemv_q80_slab_cw_kernel<nv, upw, wfc>, the splits' weights made inside each wave (the
+ * environment's NANO_COMBINE_WAVE=0 refuses that form).  route: the router's choice with the step's scratch present (the value
  * route_out of nano_hip_op_fused_gemv reports).  Routes that end in the Q80 GEMV: kernel 1 = gemv_q80_slab_kernel<role, gs, B, nv, upw>
  * in its form `variant` (0 plain, 1 early, 2 wf, 3..5 wfc2..4), 2 = gemv_q80_stream_kernel<role, gs, B, nv>; nw waves x grid workgroups,
  * rw rows per workgroup, lds_bytes of dynamic LDS; pre = 1: the activation reaches the kernel quantized; the plan is that of the first
@@ -925,7 +927,7 @@ int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * seqs_per_launch = nb, zeros for the kernel fields.  takes = 0: the shape is refused before any launch (a SLAB row of more than 65536
  * values, 32768 with SwiGLU; one sequence that does not fit a CU's LDS) and every other entry is 0.  Host arithmetic on the shape fields:
  * works without a device, and no pointer of d is followed (norm_w / attn_part: null or not). */
-#define NANO_Q80_GEMV_PLAN_WORDS 16
+#define NANO_Q80_GEMV_PLAN_WORDS 17
 int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t out[NANO_Q80_GEMV_PLAN_WORDS]);
 /* The batched Q80 launch the router issues for descriptor d (quant = NANO_QUANT_Q80), likewise: out = {route, kernel, tt, nv, r, ms, tp, pp,
  * gs, sw, threads, grid, lds_bytes, norm_order, hh, ntiles, tc0, tc1, tpw, full, nu, nk, ttl, nw, rounds, tts, magic, nsa, pre, a_stage, a_ws,
@@ -959,13 +961,16 @@ int nano_hip_q4k_gemv_plan(const NanoFusedGemvDesc *d, uint32_t cus, uint32_t ou
  * rows, wg[s] on tensor s (FP32: all in wg[0]), then n_attn attention workgroups), lds_bytes of dynamic LDS.  takes = 0: the step issues the
  * two plain launches -- the shape is refused, or the projection's route is not the one GEMV / Q4K launch -- and every other entry is 0.
  * nano_hip_wo_w13_fused_plan: the Wo + W1|W3 launch (Q80) for `wo` (kind 1, optional attn_part) and `w13` (kind 2, norm_w; n = wo's rows):
- * out = {sig, threads, role, wf, wfc, nv_a, upw_a, nv_b, upw_b, wa, wb, lds_bytes, rw_a, rw_b, 0, takes} -- wo_w13_fused_kernel<role, nv_a,
+ * out = {sig, threads, role, wf, wfc, nv_a, upw_a, nv_b, upw_b, wa, wb, lds_bytes, rw_a, rw_b, 0, takes, cw} -- wo_w13_fused_kernel<role, nv_a,
  * upw_a, nv_b, upw_b, threads, wf, wfc> on wb workgroups, the first wa of which also run Wo's rows (rw_a and rw_b rows per workgroup); role
- * 2 = residual, 3 = residual behind the split combine.  takes = 0 likewise.
+ * 2 = residual, 3 = residual behind the split combine; cw 1 = the combine's weights are made inside each wave and only the live splits
+ * are read (wo_w13_fused_cw_kernel<wf, wfc>; the environment's NANO_COMBINE_WAVE=0 refuses that form).  takes = 0 likewise.
+ * LAYOUT: the array GREW from 16 to 17 words -- words 0 .. 15 are what they were, cw is the new last word; a caller built against
+ * the 16-word header must be rebuilt (its buffer is one word short).  The same holds for nano_hip_q80_gemv_plan, below.
  * Both are host arithmetic on the shape fields: they work without a device and follow no pointer (norm_w, q_norm / k_norm and attn_part
  * are read as null or not; every other pointer of the descriptors is not looked at). */
 #define NANO_QKV_ATTN_FUSED_PLAN_WORDS 16
-#define NANO_WO_W13_FUSED_PLAN_WORDS 16
+#define NANO_WO_W13_FUSED_PLAN_WORDS 17
 int nano_hip_qkv_attn_fused_plan(const NanoFusedGemvDesc *qkv, const NanoAttnDecodeDesc *attn, uint32_t cus, uint32_t out[NANO_QKV_ATTN_FUSED_PLAN_WORDS]);
 int nano_hip_wo_w13_fused_plan(const NanoFusedGemvDesc *wo, const NanoFusedGemvDesc *w13, uint32_t cus, uint32_t out[NANO_WO_W13_FUSED_PLAN_WORDS]);
 /* One q | k | v + attention launch exactly as a step issues it (replaces infer/infer.c:758-786 and 810-879 of one layer).  The op stages

@@ -107,6 +107,7 @@ F32_GEMM_PLAN_FIELDS = ("route", "sw", "threads", "grid", "lds_bytes", "rt", "nw
 # ROUTE_NAMES, kernel into Q80_KERNELS, role into Q80_ROLES, variant into Q80_VARIANTS
 Q80_PLAN_FIELDS = ("route", "kernel", "role", "gs", "B", "nv", "upw", "rw", "nw", "grid", "lds_bytes", "variant", "pre", "launches",
                    "seqs_per_launch", "takes")
+Q80_PLAN_WORDS = len(Q80_PLAN_FIELDS) + 1         # NANO_Q80_GEMV_PLAN_WORDS: a last word behind takes, the plan's cw (q80_gemv_plan_cw)
 Q80_ROLES = F32_ROLES
 Q80_KERNELS = ("none", "slab", "stream")
 Q80_VARIANTS = ("plain", "early", "wf", "wfc2", "wfc3", "wfc4")
@@ -133,7 +134,7 @@ Q4K_KERNELS = ("none", "slab", "chunk")
 QKV_ATTN_FUSED_PLAN_FIELDS = ("kernel", "nv", "upw", "d", "qv", "threads", "n_attn", "ngemv", "lds_bytes", "rw", "wg0", "wg1", "wg2", "rounds",
                               "_zero", "takes")
 WO_W13_FUSED_PLAN_FIELDS = ("sig", "threads", "role", "wf", "wfc", "nv_a", "upw_a", "nv_b", "upw_b", "wa", "wb", "lds_bytes", "rw_a", "rw_b",
-                            "_zero", "takes")
+                            "_zero", "takes", "cw")
 FUSED_KERNELS = ("none", "q80_table", "q80_wf", "q4k", "f32")
 NANO_DEVERR_HANDOFF = 2
 
@@ -1043,7 +1044,14 @@ def q80_gemv_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=
     weight tensor (kind 2: two equal counts); attn = (n_head, hd, nsplit) for a launch that combines split-attention partials.
     Returns a dict of Q80_PLAN_FIELDS; takes == 0: the router refuses the shape and every other entry is 0."""
     d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm, resid_add=bool(resid_add))
-    return _plan_query("q80_gemv", Q80_PLAN_FIELDS, len(Q80_PLAN_FIELDS), d, cus)
+    return _plan_query("q80_gemv", Q80_PLAN_FIELDS, Q80_PLAN_WORDS, d, cus)
+
+
+def q80_gemv_plan_cw(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, resid_add=False, cus=256):
+    """The last word of nano_hip_q80_gemv_plan for the arguments of q80_gemv_plan: 1 when the launch -- a residual launch behind split
+    attention -- runs gemv_q80_slab_cw_kernel, the splits' weights made inside each wave; 0: every other launch, the table form included."""
+    d = _fused_shape(0x80, kind, n, rows, nb, gs=gs, norm=bool(norm), attn=attn, ordered=ordered, use_gemm=use_gemm, resid_add=bool(resid_add))
+    return _plan_query("q80_gemv", Q80_PLAN_FIELDS + ("cw",), Q80_PLAN_WORDS, d, cus)["cw"]
 
 
 def q80_gemm_plan(kind, n, rows, nb=1, *, gs=64, norm=False, attn=None, ordered=False, use_gemm=False, cus=256):

@@ -333,6 +333,7 @@ extern "C" int nano_hip_model_create_ex(NanoHipModel **out, const NanoModelDesc 
     // NANO_FUSE_LAUNCHES: bit 0 = q | k | v + attention in one launch, bit 1 = Wo + W1|W3 in one launch (higher bits are ignored).
     // Default 3; 0 = the five launches per layer; same bits in every setting
     if (const char *fz = getenv("NANO_FUSE_LAUNCHES")) { const uint32_t v = (uint32_t)strtoul(fz, nullptr, 0); m->ho.fuse_qkv_attn = (v & 1u) != 0; m->ho.fuse_wo_w13 = (v & 2u) != 0; }
+    if (const char *cwv = getenv("NANO_COMBINE_WAVE")) m->ho.combine_wave = *cwv != '0';
     {
         // granule buffers of the fused one-sequence launches (hand2: the Wo + W1|W3 launch, Q80 only)
         const bool gran = (m->d.quant_type == NANO_QUANT_Q80 && m->d.group_size == 64) || m->d.quant_type == NANO_QUANT_Q4K || m->d.quant_type == NANO_QUANT_F32;

@@ -158,6 +158,7 @@ struct NanoHipModel {
         unsigned long long *hand = nullptr;               // its granule buffer (q_dim + 2 kv_dim entries of {tag, value}; tags are epochs: device_common.h)
         bool fuse_wo_w13 = true;                          // one sequence, Q80 gs 64: Wo + W1|W3 in one launch (x as granules); NANO_FUSE_LAUNCHES bit 1
         unsigned long long *hand2 = nullptr;              // its granule buffer (n_embd entries)
+        bool combine_wave = true;                         // Wo behind split attention: the splits' weights made inside each wave (SLAB_CW); NANO_COMBINE_WAVE=0: the table form
         uint32_t *tick = nullptr;                         // device words of the in-launch hand-offs: [0] step counter (the epoch), [1] fault word, [2] abort flag, [3] spare
         uint32_t fallbacks = 0;                           // times a hand-off gave up and the call was re-issued through the plain launches (fusion stays off after the first)
         bool reissue = true;                              // (nano_hip_debug_fault bit 1 clears it: the give-up then surfaces as NANO_HIP_ERUNTIME)

@@ -92,7 +92,7 @@ static GemvArgs wo_args(const NanoHipModel *m, uint32_t l, uint32_t nb, uint32_t
     GemvArgs a = proj_args(m, nb, m->QD, m->xba, GEMV_EPI_RESID);
     a.nseg = 1; a.seg[0] = mkseg(m->W[WO][l], m->x, m->d.n_embd, m->d.n_embd);
     if (m->lora_on) { a.resid_add = m->lora_o1; a.resid_add_bstride = m->d.n_embd; }
-    if (nsplit > 1) { a.attn_part = m->attn_part; a.attn_ml = m->attn_ml; a.attn_nsplit = nsplit; a.attn_n_head = m->d.n_head; a.attn_hd = m->hd; }
+    if (nsplit > 1) { a.attn_part = m->attn_part; a.attn_ml = m->attn_ml; a.attn_nsplit = nsplit; a.attn_n_head = m->d.n_head; a.attn_hd = m->hd; a.attn_table = m->ho.combine_wave ? 0u : 1u; }
     return a;
 }
 // W1 | W3 from xin: epi SWIGLU leaves hb = silu(W1 . xn) * (W3 . xn) (w3_out = hb), epi STORE the two products (w3_out = hb2)   infer.c:914-944

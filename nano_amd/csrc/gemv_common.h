@@ -141,13 +141,109 @@ struct Staged {
     // are fetched at kernel entry too (one round trip instead of nsplit dependent ones)
     float4 pv[B == 1 ? NV : 1][B == 1 ? 8 : 1];
     float ml_m, ml_l;
+    float cw_m[B == 1 ? NV : 1], cw_l[B == 1 ? NV : 1];      // the in-wave form of the combine (CW below): one pair per item
 };
 template <int B>
 struct Staged<B, 0> {};          // NV == 0: nothing is kept in registers, stage_finish() re-reads memory in loops
 
-template <int ROLE, int B, int NV>
+// ---- the split-attention combine with IN-WAVE weights (CW): one sequence, a wave's 64 items of a round cover whole heads ------------
+// (256 % head_dim == 0, head_dim >= 32: HPW = 256 / head_dim = 1, 2, 4 or 8 heads per wave; at most 8 splits; gemv_q80_host.h combine_wave_shape()).
+// Item round j of wave `wid` is the 256 values from (wid + j NW) * 256: heads (wid + j NW) HPW .. + HPW - 1.  Lane l < 8 HPW loads the
+// (max, sum) pair of head (wid + j NW) HPW + (l >> 3), split l & 7 -- the 8 lanes of a head are one DPP half-row, as in combine_weights()
+// -- and runs that function's chain; every lane then takes the 8 weights of its own item's head from lanes 8 (head within the wave) + s
+// (ds_bpermute: the LDS crossbar, no LDS memory).  No weight table, no workgroup barrier: a wave needs nothing of another wave.
+// The partials of split s are asked for -- and added, cw_combine() -- under wave-uniform tests s < attn_nsplit, nested: a launch of few
+// splits jumps once, a launch of 8 falls through.  What the table form does beyond that is add (+0) * w for the splits >= attn_nsplit
+// (partial: an out-of-range load, +0; w = 0 / L): for finite statistics with one live split per head that product is +0; the sum
+// starts at +0.0f and a float sum is -0 only when both operands are -0, so the running value is never -0 and acc + (+0) is acc, bit
+// for bit.  Finite statistics with a live split per head is what the attention kernels write for every causal step (split s holds
+// position 64 s <= pos).  tests/test_wo_combine_wave_order.py restates the lane schedule and compares it with the table form's bits.
+template <int NV, int S>
+__device__ __forceinline__ void cw_issue_from(const GemvDev &a, const __amdgpu_buffer_rsrc_t rp, Staged<1, NV> &r) {
+    if constexpr (S < 8) {
+        if (S == 0 || a.attn_nsplit > (uint32_t)S) {
+#pragma unroll
+            for (int j = 0; j < NV; j++) {
+                const uint32_t i = (threadIdx.x + (uint32_t)j * a.nthr) * 4u;
+                r.pv[j][S] = bload_f4(rp, (i < a.n) ? ((uint32_t)S * a.n + i) * 4u : OOB);
+            }
+            cw_issue_from<NV, S + 1>(a, rp, r);
+        }
+    }
+}
+template <int NV>
+__device__ __forceinline__ void cw_issue(const GemvDev &a, Staged<1, NV> &r) {
+    const uint32_t ns = a.attn_nsplit, nh = a.attn_n_head, n = a.n;
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, NW = a.nthr >> 6;
+    cw_issue_from<NV, 0>(a, mkrsrc(a.attn_part, ns * n * 4u), r);
+    const __amdgpu_buffer_rsrc_t rm = mkrsrc(a.attn_ml, nh * ns * 8u);
+    const uint32_t hpw = 256u >> (uint32_t)__builtin_ctz(a.attn_hd), sp = lane & 7u, hl = lane >> 3;
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+        const uint32_t h = (wid + (uint32_t)j * NW) * hpw + hl;
+        // a head beyond the last (items beyond n, which hold +0): head 0's pair, as the table form reads head 0's weights for them
+        const uint32_t mo = (hl < hpw && sp < ns) ? ((h < nh ? h : 0u) * ns + sp) * 8u : OOB;
+        r.cw_m[j] = bload_f(rm, mo);
+        r.cw_l[j] = bload_f(rm, mo == OOB ? OOB : mo + 4u);
+    }
+}
+// acc + p * w as one v_mul_f32 and one v_add_f32 the optimizer cannot pair: the SLP vectorizer made v_pk_mul_f32 of two products with the
+// weight broadcast from the low half of a register PAIR, whose high half was the destination of a weight-scale load still in flight --
+// the wait the compiler put in front of split 2 was for all but the last four loads of the launch, Wo's weights included (the step 0.8 %
+// slower than the table form).  Same instructions as the compiler's own for a + p * w under -ffp-contract=off, same rounding.
+__device__ __forceinline__ float cw_mad(float acc, float p, float w) {
+    float t, r;
+    asm("v_mul_f32_e32 %0, %1, %2" : "=v"(t) : "v"(p), "v"(w));
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(acc), "v"(t));
+    return r;
+}
+template <int NV, int S>
+__device__ __forceinline__ void cw_add_from(const GemvDev &a, const Staged<1, NV> &r, const float (&w)[NV][8], float4 (&acc)[NV]) {
+    if constexpr (S < 8) {
+        if (S == 0 || a.attn_nsplit > (uint32_t)S) {
+#pragma unroll
+            for (int j = 0; j < NV; j++) {
+                acc[j].x = cw_mad(acc[j].x, r.pv[j][S].x, w[j][S]); acc[j].y = cw_mad(acc[j].y, r.pv[j][S].y, w[j][S]);
+                acc[j].z = cw_mad(acc[j].z, r.pv[j][S].z, w[j][S]); acc[j].w = cw_mad(acc[j].w, r.pv[j][S].w, w[j][S]);
+            }
+            cw_add_from<NV, S + 1>(a, r, w, acc);
+        }
+    }
+}
+// r.x[0][j] = sum over the live splits, ascending, of part[s][item j] * weight(head of item j, s)
+template <int NV>
+__device__ __forceinline__ void cw_combine(const GemvDev &a, Staged<1, NV> &r) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int src = (int)((((lane * 4u) >> (uint32_t)__builtin_ctz(a.attn_hd)) * 8u) * 4u);      // byte address of lane 8 (head within the wave)
+    float w[NV][8];
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+        const float m = r.cw_m[j], l = r.cw_l[j];
+        const bool live = l > 0.0f;                                  // combine_weights(), operation for operation
+        float M = live ? m : -INFINITY;
+        M = fmaxf(M, DPP_F(M, 0xB1)); M = fmaxf(M, DPP_F(M, 0x4E)); M = fmaxf(M, DPP_F(M, 0x141));
+        const float e = live ? expf(m - M) : 0.0f;
+        float L = l * e;
+        L += DPP_F(L, 0xB1); L += DPP_F(L, 0x4E); L += DPP_F(L, 0x141);
+        const int wq = __float_as_int(e / L);
+#pragma unroll
+        for (int s = 0; s < 8; s++) w[j][s] = __int_as_float(__builtin_amdgcn_ds_bpermute(src + 4 * s, wq));
+    }
+    float4 acc[NV];
+#pragma unroll
+    for (int j = 0; j < NV; j++) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    cw_add_from<NV, 0>(a, r, w, acc);
+#pragma unroll
+    for (int j = 0; j < NV; j++) r.x[0][j] = acc[j];
+}
+
+template <int ROLE, int B, int NV, int CW = 0>
 __device__ __forceinline__ void stage_issue(const GemvDev &a, Staged<B, NV> &r) {
-    if constexpr (NV == 0) { (void)a; (void)r; return; } else {
+    if constexpr (NV == 0) { (void)a; (void)r; return; } else
+    if constexpr (CW != 0) {
+        static_assert(ROLE == R_RESID_COMBINE && B == 1, "CW: the one-sequence combine role");
+        cw_issue<NV>(a, r);
+    } else {
     const uint32_t tid = threadIdx.x, nthr = a.nthr, n = a.n;
     const bool plain = !has_flag<ROLE>(a, F_PRE) && !has_flag<ROLE>(a, F_COMBINE);
     const __amdgpu_buffer_rsrc_t rx = mkrsrc(a.xin, plain ? ((a.nb - 1) * a.xin_bstride + n) * 4u : 0u);

@@ -171,6 +171,12 @@ bool gemv_q80_plan(const GemvArgs &a, Q80GemvPlan *out) {
             lds = n16 + ng4 * 4 + 64 + comb + slab_unit_table(d, nch);
         }
     }
+    // Behind split attention, one sequence, ONE item per thread: the splits' weights made inside each wave (SLAB_CW).  The table's bytes
+    // stay in the request (a hole in the carve-up: the plan's lds_bytes do not depend on the form).  (Two items per thread -- Wo of n = 1280
+    // or 2048 on the plain launch's four or six waves -- were built and are not shipped: bit-identical, but the compiler's code for the two
+    // rounds of statistics loads has a wait for every load and late kernel-argument fetches inside the issue phase, which
+    // tests/test_isa_hygiene.py forbids for good reason; those launches keep the table form.)
+    p.cw = (a.gs == 64 && B == 1 && p.role == R_RESID_COMBINE && p.nv == 1 && p.variant != Q80_VAR_EARLY && combine_wave_shape(a)) ? 1u : 0u;
     if (lds > GEMV_Q80_LDS_MAX) return false;
     p.lds_bytes = (uint32_t)lds;
     if (out) *out = p;

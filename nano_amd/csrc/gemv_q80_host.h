@@ -34,6 +34,17 @@ static inline uint32_t slab_wave_fold_chunks(const GemvDev &d) {
     if (d.n % 1024u || d.n < 2048u || d.n > 4096u || d.ng * 64u != d.n) return 0u;
     return d.n / 1024u;
 }
+// The split-attention combine with in-wave weights and the live splits only (gemv_common.h cw_issue / cw_combine; gemv_q80_slab_body.inc
+// SLAB_CW): a one-sequence launch whose input is the splits' partials, at most 8 splits, heads of 32 | 64 | 128 | 256 values that tile
+// the row -- the 256 values of a wave's item round are whole heads, 8 | 4 | 2 | 1 of them.  (The callers add: the combine role, group size
+// 64, the items in registers.)  GemvArgs::attn_table refuses the form -- the table form runs: a model's NANO_COMBINE_WAVE=0, read once
+// when the model is created, and the operators' and queries' reading of the same variable (A/B measurements, the tests that compare the
+// two forms bit for bit).  Nothing is read from the environment here.
+static inline bool combine_wave_shape(const GemvArgs &a) {
+    if (!a.attn_part || a.attn_table || a.nb != 1u || a.attn_nsplit == 0u || a.attn_nsplit > 8u) return false;
+    const uint32_t hd = a.attn_hd;
+    return (hd == 32u || hd == 64u || hd == 128u || hd == 256u) && (uint64_t)a.attn_n_head * hd == a.n;
+}
 static inline size_t slab_unit_table(const GemvDev &d, uint32_t nch) { return (size_t)(d.tpw * 4) * (nch <= 2u ? 4u : 8u) * 4u; }      // [rows of the tiles][unit sums] floats
 
 // measurement hook: when both are set, the next STREAM (classifier) launch is issued with hipExtLaunchKernelGGL so that the

@@ -52,7 +52,7 @@ __device__ __forceinline__ void quant_store4(float4 v, float scale, int8_t *dst)
     *reinterpret_cast<uint32_t *>(dst) = q80_pack4(q80_quant4(v, scale));
 }
 
-template <int ROLE, int GS, int B, int NV>
+template <int ROLE, int GS, int B, int NV, int CW = 0>
 __device__ __forceinline__ void stage_finish(const GemvDev &a, Staged<B, NV> &r, int8_t *xq, float *xs, float *red, uint32_t n16, uint32_t ng4) {
     const uint32_t tid = threadIdx.x, nthr = a.nthr, n = a.n, ng = a.ng;
     const uint32_t lane = tid & 63u, wid = tid >> 6, NW = nthr >> 6;
@@ -103,6 +103,9 @@ __device__ __forceinline__ void stage_finish(const GemvDev &a, Staged<B, NV> &r,
         }
         __syncthreads();
     } else {
+        if constexpr (CW != 0) {        // in-wave weights, live splits only (gemv_common.h cw_combine): no table, no barrier
+            cw_combine<NV>(a, r);
+        } else
         if (comb) {
             if constexpr (B == 1) {
                 const bool pre_ml = a.attn_n_head * 8u <= nthr;       // every (head, split) pair has its own thread
@@ -395,72 +398,48 @@ struct Wo13Args { GemvDev wo; GemvDev w13; SlabHand hand; uint32_t wo_wgs, wait1
 // Eight waves, one float4 item per thread and one unit per wave in both bodies: the one form wo13_slabs() takes
 template <int ROLE_A, int WF, int WFA>      // WF: W1|W3's rows are one chunk (n == 1024): SLAB_WF; WFA: Wo's rows are that many whole chunks: SLAB_WFC
 __global__ __launch_bounds__(512) void wo_w13_fused_kernel(const Wo13Args fa) {
+#define WO13_CW 0
+#include "wo_w13_fused_body.inc"
+#undef WO13_CW
+}
+// The plain SLAB kernel of the combine role with the combine in the wave (SLAB_CW; one sequence, one item per thread, the table
+// form's units: plain or -- WFC -- rows of 2..4 whole chunks): what a step with the fusion off, or after a hand-off gave up, launches for Wo
+template <int NV, int UPW, int WFC>
+__global__ __launch_bounds__(1024) void gemv_q80_slab_cw_kernel(const GemvDev a) {
+    static_assert(NV == 1, "one item per thread (gemv_q80_plan)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int GS = 64, B = 1, NV = 1, UPW = 1;
-    const uint2 tk_ = hand_tick(fa.hand);
-    // Order of issue: Wo's loads, W1|W3's loads, Wo's arithmetic, W1|W3's.  (vmcnt counts in order: loads issued BEFORE Wo's would have to
-    // land before Wo may use its own -- the first build had W1|W3's in front and Wo waited for the whole 64 MB of Qwen3-4B's two matrices.)
-    // Workgroups beyond Wo's grid run Wo's part 1 on rows past the matrix (out-of-range buffer loads: no traffic) and skip its part 2.
-    {
-        constexpr int ROLE = ROLE_A;
+    constexpr int ROLE = R_RESID_COMBINE, GS = 64, B = 1;
+#define SLAB_CW 1
+#define SLAB_WFC WFC
+#define SLAB_A a
 #define SLAB_BID blockIdx.x
-#define SLAB_A fa.wo
-#define SLAB_HAND 1
-#define SLAB_HANDV fa.hand
-#define SLAB_PTAG hand_ptag(tk_, fa.hand)
-#define SLAB_XHAND 0
-#define SLAB_XHANDV (SlabHand{})
-#define SLAB_CTAG 0u
-#define SLAB_WFC WFA
-#define SLAB_PART 1
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-        auto wo_rest = [&]() __attribute__((always_inline)) {
-#define SLAB_PART 2
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-        };
-#undef SLAB_WFC
-#undef SLAB_A
-#undef SLAB_HAND
-#undef SLAB_HANDV
-#undef SLAB_PTAG
-#undef SLAB_XHAND
-#undef SLAB_XHANDV
-#undef SLAB_CTAG
-        {
-            constexpr int ROLE = R_NORM_SWIGLU;
-#define SLAB_A fa.w13
 #define SLAB_HAND 0
 #define SLAB_HANDV (SlabHand{})
 #define SLAB_PTAG 0u
-#define SLAB_XHAND 1
-#define SLAB_XHANDV fa.hand
-#define SLAB_CTAG hand_ctag(tk_, fa.hand)
-#define SLAB_XHAND_WAIT (blockIdx.x >= fa.wo_wgs ? fa.wait16 : 0u)
-#define SLAB_XHAND_NAP 2
-#define SLAB_WF WF
-#define SLAB_PART 1
+#define SLAB_XHAND 0
+#define SLAB_XHANDV (SlabHand{})
+#define SLAB_CTAG 0u
+#define SLAB_PART 0
 #include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
-            if (blockIdx.x < fa.wo_wgs) wo_rest();
-            __syncthreads();                // (LDS is W1|W3's from here)
-#define SLAB_PART 2
-#include "gemv_q80_slab_body.inc"
-#undef SLAB_PART
 #undef SLAB_A
+#undef SLAB_BID
 #undef SLAB_HAND
 #undef SLAB_HANDV
 #undef SLAB_PTAG
 #undef SLAB_XHAND
 #undef SLAB_XHANDV
 #undef SLAB_CTAG
-#undef SLAB_XHAND_WAIT
-#undef SLAB_XHAND_NAP
-#undef SLAB_WF
-        }
-#undef SLAB_BID
-    }
+#undef SLAB_PART
+#undef SLAB_WFC
+#undef SLAB_CW
+}
+// ... with Wo's combine in the wave (SLAB_CW): no weight table, no barrier in front of Wo's quantizer, the live splits only
+template <int WF, int WFA>
+__global__ __launch_bounds__(512) void wo_w13_fused_cw_kernel(const Wo13Args fa) {
+    constexpr int ROLE_A = R_RESID_COMBINE;
+#define WO13_CW 1
+#include "wo_w13_fused_body.inc"
+#undef WO13_CW
 }
 
 #endif
@@ -622,6 +601,22 @@ static hipError_t launch_slab_t(const GemvDev &d, const Q80GemvPlan &p, hipStrea
         hipLaunchKernelGGL((gemv_q80_slab_kernel<ROLE, GS, B, NV, UPW, 0, 1>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd);
         return hipGetLastError();
     }
+#if NANO_Q80_GS == 64
+    // the combine role with the splits' weights made inside each wave (the plan's cw; its variant is plain or WFC2..4)
+    if constexpr (GS == 64 && B == 1 && ROLE == R_RESID_COMBINE && NV == 1) if (p.cw) {
+        if (p.variant == Q80_VAR_PLAIN) {
+            auto kern = &gemv_q80_slab_cw_kernel<NV, UPW, 0>;
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError();
+        }
+        if constexpr (UPW <= 2) {
+            if (p.variant == Q80_VAR_WFC2) { hipLaunchKernelGGL((gemv_q80_slab_cw_kernel<NV, UPW, 2>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
+            if (p.variant == Q80_VAR_WFC3) { hipLaunchKernelGGL((gemv_q80_slab_cw_kernel<NV, UPW, 3>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
+            if (p.variant == Q80_VAR_WFC4) { hipLaunchKernelGGL((gemv_q80_slab_cw_kernel<NV, UPW, 4>), dim3(p.grid), dim3(64 * p.nw), lds, st, dd); return hipGetLastError(); }
+        }
+        return hipErrorInvalidValue;
+    }
+#endif
     // rows of 2..4 whole chunks, one sequence, the residual roles (Wo, W2; canonical launches only at this group size): every
     // wave folds the chunk of its unit to two unit sums -- 8 floats per unit in LDS instead of the product table, 2 nch - 1 adds behind the
     // barrier (gemv_q80_slab_body.inc SLAB_WFC).  (The plans of such matrices have <= 8 units on >= 6 waves: one or two units per wave.)
@@ -758,10 +753,10 @@ static void slab_dev_fill(GemvDev &d, const GemvArgs &a, const SlabPlan &p, uint
     d.wg_c0 = 0xffffffffu; d.wg_c1 = 0xffffffffu;
     d.nthr = nthr;
 }
-static size_t slab_lds(const GemvDev &d, bool table = true) {
+static size_t slab_lds(const GemvDev &d, bool table = true, bool wgt = true) {      // wgt: the combine's weight table [n_head][8] (SLAB_CW has none)
     const uint32_t nmat = d.epi == GEMV_EPI_SWIGLU ? 2 : 1;
     const size_t n16 = (d.n + 15) & ~15u, ng4 = (d.ng + 3) & ~3u, pitch = ((d.ng + 47) / 64) * 64 + 16;
-    return n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) ? (size_t)d.attn_n_head * 32 : 0) + (table ? (size_t)nmat * (d.tpw * 4) * pitch * 4 : 0);
+    return n16 + ng4 * 4 + 64 + ((d.flags & F_COMBINE) && wgt ? (size_t)d.attn_n_head * 32 : 0) + (table ? (size_t)nmat * (d.tpw * 4) * pitch * 4 : 0);
 }
 // Every choice of the launch (kernels.h WoW13FusedPlan), and the two device blocks it was made from
 static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan &f, GemvDev &da, GemvDev &db) {
@@ -774,7 +769,9 @@ static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan &
     if (wf) db.units = (db.rw + 1) / 2;
     // Wo's rows of two whole chunks (n == 2048, the widest this form takes): every wave folds its unit's chunk to two unit sums (SLAB_WFC)
     const bool wfa = slab_wave_fold_chunks(da) == 2u;
-    const size_t la = slab_lds(da, !wfa) + (wfa ? slab_unit_table(da, 2u) : 0), lb = slab_lds(db, !wf), lds = la > lb ? la : lb;
+    // Wo behind split attention: the splits' weights made inside each wave where the heads tile a wave's items (SLAB_CW)
+    const bool cw = (da.flags & F_COMBINE) && combine_wave_shape(wo);
+    const size_t la = slab_lds(da, !wfa, !cw) + (wfa ? slab_unit_table(da, 2u) : 0), lb = slab_lds(db, !wf), lds = la > lb ? la : lb;
     if (lds > FUSED_LDS_MAX) return false;
     f = WoW13FusedPlan{};
     f.sig = 3; f.threads = 512;                                                 // (sig: the queries' word for this form; 1 was the four-wave one)
@@ -783,6 +780,7 @@ static bool wo13_shape(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan &
     f.nv_a = 1; f.upw_a = 1; f.nv_b = 1; f.upw_b = 1;
     f.wa = q.wa; f.wb = q.wb; f.lds_bytes = (uint32_t)lds;
     f.rw_a = q.a.rw; f.rw_b = q.b.rw;
+    f.cw = cw ? 1u : 0u;
     return true;
 }
 
@@ -866,7 +864,13 @@ hipError_t launch_wo_w13_fused(const GemvArgs &wo, const GemvArgs &w13, unsigned
     h.base[0] = 0; h.base[1] = 0; h.base[2] = 0;
     fa.hand = h;
     const size_t lds = q.lds_bytes;
-    // the instantiations: <role, WF, WFC> of {R_RESID, R_RESID_COMBINE} x {0, 1} x {0, 2} (tests/test_fused_launch_plan.py restates the set)
+    // the instantiations: <role, WF, WFC> of {R_RESID, R_RESID_COMBINE} x {0, 1} x {0, 2} (tests/test_fused_launch_plan.py restates the set),
+    // and the in-wave combine's <WF, WFC> of {0, 1} x {0, 2} (tests/test_wo_combine_wave_order.py)
+#define WO13_CW_GO(WF_, WFC_) do { if (q.cw && q.role == (uint32_t)R_RESID_COMBINE && q.wf == WF_ && q.wfc == WFC_) { \
+        hipLaunchKernelGGL((wo_w13_fused_cw_kernel<WF_, WFC_>), dim3(q.wb), dim3(q.threads), lds, st, fa); return hipGetLastError(); } } while (0)
+    WO13_CW_GO(0, 0); WO13_CW_GO(0, 2); WO13_CW_GO(1, 0); WO13_CW_GO(1, 2);
+#undef WO13_CW_GO
+    if (q.cw) return hipErrorInvalidValue;
 #define WO13_GO(RA_, WF_, WFC_) do { if (q.role == (uint32_t)RA_ && q.wf == WF_ && q.wfc == WFC_) { \
         hipLaunchKernelGGL((wo_w13_fused_kernel<RA_, WF_, WFC_>), dim3(q.wb), dim3(q.threads), lds, st, fa); return hipGetLastError(); } } while (0)
     WO13_GO(R_RESID, 0, 0); WO13_GO(R_RESID, 0, 2); WO13_GO(R_RESID, 1, 0); WO13_GO(R_RESID, 1, 2);

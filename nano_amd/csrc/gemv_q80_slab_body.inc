@@ -28,6 +28,9 @@
 //               2 SLAB_WFC unit sums (one or two LDS reads) and adds them in ascending order -- 2 SLAB_WFC - 1 adds where the table's fold
 //               has 16 SLAB_WFC - 1 behind 4 SLAB_WFC reads.  (A wave per tile with ALL of its chunks -- no barrier at all -- was built first and
 //               lost: the dots and folds of two or three chunks in ONE wave cost more than the barrier, profiles/wave_fold_chunks.txt.)
+//   SLAB_CW    (optional, default 0) a compile-time 0 | 1: the split-attention combine with in-wave weights and live splits only (role
+//               R_RESID_COMBINE, one sequence, a wave's items cover whole heads -- the host selects it: gemv_q80_host.h combine_wave_shape(),
+//               gemv_common.h cw_issue / cw_combine): no weight table in the LDS carve-up, no barrier in front of the quantizer
 // and has ROLE, GS, B, NV, UPW, smem, in scope.
 #ifndef SLAB_WF
 #define SLAB_WF 0
@@ -40,6 +43,10 @@
 #ifndef SLAB_EARLY
 #define SLAB_EARLY 0
 #define SLAB_EARLY_DEFAULTED 1
+#endif
+#ifndef SLAB_CW
+#define SLAB_CW 0
+#define SLAB_CW_DEFAULTED 1
 #endif
 #ifndef SLAB_XHAND_WAIT
 #define SLAB_XHAND_WAIT 0u
@@ -106,7 +113,9 @@
     int8_t *xq = reinterpret_cast<int8_t *>(smem);                 // [B][n16]
     float *xs = reinterpret_cast<float *>(smem + B * n16);         // [B][ng4]
     float *red = xs + B * ng4;                                     // [B][16] (+ combine weights [B][n_head][8])
-    float *P = red + B * 16 + (has_flag<ROLE>(SLAB_A, F_COMBINE) ? B * SLAB_A.attn_n_head * 8 : 0);   // [B][nmat][RWP][PITCH] (SLAB_WFC: unit sums [RWP][UP_])
+    constexpr bool CW_ = (SLAB_CW) != 0;
+    static_assert(!CW_ || (ROLE == R_RESID_COMBINE && B == 1 && NV >= 1 && !(SLAB_XHAND)), "SLAB_CW: the one-sequence combine role, items in registers");
+    float *P = red + B * 16 + (!CW_ && has_flag<ROLE>(SLAB_A, F_COMBINE) ? B * SLAB_A.attn_n_head * 8 : 0);   // [B][nmat][RWP][PITCH] (SLAB_WFC: unit sums [RWP][UP_])
 
     // every argument the chain below reads late (output slots, strides, positions, the residual addend) is fetched NOW, with
     // the first ones (karg_touch, gemv_common.h)
@@ -121,7 +130,7 @@
     // ---- 1. activation loads (critical path) ------------------------------------------------------------
     Staged<B, NV> sx;
     if constexpr (SLAB_XHAND) stage_issue_nw<ROLE, B, NV>(SLAB_A, sx);          // (the norm weights only: the values come as granules, below)
-    else if (!(NANO_STAMPS && (SLAB_A.dbg & 2u))) stage_issue<ROLE, B, NV>(SLAB_A, sx);
+    else if (!(NANO_STAMPS && (SLAB_A.dbg & 2u))) stage_issue<ROLE, B, NV, (SLAB_CW)>(SLAB_A, sx);
 
     // ---- 2. all weight / scale loads of this wave; the workgroup's rows lie inside ONE segment ------------
     // (the residual and SwiGLU launches of a decode step have ONE weight segment: their roles skip the selection chains)
@@ -148,7 +157,7 @@
     //  (tile, chunk); rows of the tile beyond the workgroup's RW belong to the next workgroup (RW % 4 != 0): a wave-uniform select)
 #pragma unroll
     for (int k = 0; k < UPW; k++) { if (early_ == 0u || (uint32_t)k < early_) SLAB_ISSUE_UNIT(k); }
-    if (!SLAB_XHAND && NANO_STAMPS && (SLAB_A.dbg & 2u)) stage_issue<ROLE, B, NV>(SLAB_A, sx);          // (experiment: the activation behind the weights)
+    if (!SLAB_XHAND && NANO_STAMPS && (SLAB_A.dbg & 2u)) stage_issue<ROLE, B, NV, (SLAB_CW)>(SLAB_A, sx);          // (experiment: the activation behind the weights)
     // ---- 3. the fold thread's output slot (residual: old value) -----------------------------------------------
     const int fb = (int)(((uint32_t)tid * SLAB_A.magic_rw) >> 16);          // tid / RW: fold thread -> (sequence, local row)
     const int frl = tid - fb * (int)RW;
@@ -199,7 +208,7 @@
         }
         if (!got_) hand_give_up(SLAB_XHANDV, SLAB_A.err);
     }
-    stage_finish<ROLE, GS, B, NV>(SLAB_A, sx, xq, xs, red, n16, ng4);
+    stage_finish<ROLE, GS, B, NV, (SLAB_CW)>(SLAB_A, sx, xq, xs, red, n16, ng4);
     if constexpr (early_ != 0u) {
 #pragma unroll
         for (int k = 1; k < UPW; k++) { if ((uint32_t)k >= early_) SLAB_ISSUE_UNIT(k); }
@@ -429,6 +438,10 @@
 #ifdef SLAB_EARLY_DEFAULTED
 #undef SLAB_EARLY
 #undef SLAB_EARLY_DEFAULTED
+#endif
+#ifdef SLAB_CW_DEFAULTED
+#undef SLAB_CW
+#undef SLAB_CW_DEFAULTED
 #endif
 #ifdef SLAB_XHAND_WAIT_DEFAULTED
 #undef SLAB_XHAND_WAIT

@@ -45,7 +45,8 @@ struct GemvArgs {
     //   x[b][i] = sum_s part[b][s][i] * w[b][head(i)][s],  w from the (max, sum) pairs in attn_ml
     const float *attn_part; // [nb][nsplit][n] unnormalised partial outputs, or nullptr
     const float *attn_ml;   // [nb][n_head][nsplit][2] (running max, exp-sum) per split
-    uint32_t attn_nsplit, attn_n_head, attn_hd, _pad2;
+    uint32_t attn_nsplit, attn_n_head, attn_hd;
+    uint32_t attn_table;    // 1: the combine keeps its table form (weights through LDS) where the in-wave form would apply (gemv_q80_host.h combine_wave_shape())
     // residual epilogue only: an extra vector added to the GEMV result BEFORE the residual add, x += (W.act + resid_add)
     // (the LoRA o-branch, reference infer.c:898-908); [nb][resid_add_bstride] or nullptr
     const float *resid_add; uint32_t resid_add_bstride, _pad3;
@@ -129,6 +130,7 @@ struct Q80GemvPlan {
     uint32_t rw, nw, grid, lds_bytes;           // rows per workgroup (STREAM: the 16 rows of a wave's tile), waves, workgroups, dynamic LDS
     uint32_t variant, pre;                      // Q80_VAR_*; pre: the activation arrives quantized (F_PRE)
     uint32_t early, units, wg_c0, wg_c1;        // the launchers' device block: GemvDev::early, units, workgroups up to the end of segment 0 / 1
+    uint32_t cw;                                // 1: gemv_q80_slab_cw_kernel<nv, upw, wfc> -- the combine role, one item per thread, with the splits' weights made inside each wave (variant plain | wfc2..4)
 };
 bool gemv_q80_plan(const GemvArgs &a, Q80GemvPlan *p);
 uint32_t gemv_q80_fit_batch(const GemvArgs &a);            // sequences per Q80 GEMV launch that fit in LDS (8 | 4 | 2 | 1; 0: none -- the shape is refused)
@@ -323,13 +325,15 @@ hipError_t launch_qkv_attn_fused(uint32_t quant, const GemvArgs &ga, const AttnA
 // Wo + W1|W3 of one sequence in ONE launch (gemv_q80_impl.h wo_w13_fused_kernel): x reaches W1|W3 as granules of the same launch.
 // The launch: wo_w13_fused_kernel<role, wf, wfc> on wb workgroups (the first wa also run Wo's rows: rw_a and rw_b rows each) of 512 threads,
 // one float4 item per thread and one unit per wave in both bodies; role R_RESID | R_RESID_COMBINE (gemv_common.h: 2 | 3); wf 1: W1|W3's rows
-// of one chunk folded in the wave; wfc 2: Wo's rows of two chunks likewise, else 0.  wo_w13_fused_plan() makes every choice; false: refused.
+// of one chunk folded in the wave; wfc 2: Wo's rows of two chunks likewise, else 0; cw 1: wo_w13_fused_cw_kernel<wf, wfc>, the combine role with
+// the splits' weights made inside each wave (gemv_q80_host.h combine_wave_shape()).  wo_w13_fused_plan() makes every choice; false: refused.
 // sig, threads, nv_a .. upw_b are the constants 3, 512, 1, 1, 1, 1 of that one form: words of the plan queries (nano_mi355x.h).
 struct WoW13FusedPlan {
     uint32_t sig, threads, role, wf, wfc;
     uint32_t nv_a, upw_a, nv_b, upw_b;
     uint32_t wa, wb, lds_bytes;
     uint32_t rw_a, rw_b;
+    uint32_t cw;                                // 1: wo_w13_fused_cw_kernel<wf, wfc> -- Wo's split combine with in-wave weights, live splits only (role R_RESID_COMBINE)
 };
 bool wo_w13_fused_plan(const GemvArgs &wo, const GemvArgs &w13, WoW13FusedPlan *p);
 inline bool wo_w13_fused_supports(const GemvArgs &wo, const GemvArgs &w13) { return wo_w13_fused_plan(wo, w13, nullptr); }

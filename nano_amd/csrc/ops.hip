@@ -391,6 +391,8 @@ static FusedLaunch fused_launch(const NanoFusedGemvDesc &d, uint32_t cus, F32Scr
     a.epi = d.kind == 0 ? GEMV_EPI_STORE : d.kind == 1 ? GEMV_EPI_RESID : GEMV_EPI_SWIGLU;
     a.norm_w = d.norm_w;
     if (d.attn_part) { a.attn_part = d.attn_part; a.attn_nsplit = d.attn_nsplit; a.attn_n_head = d.attn_n_head; a.attn_hd = d.attn_hd; }
+    // (operators and queries only, never a model's step: NANO_COMBINE_WAVE=0 keeps the combine's table form, as a model created under it does)
+    if (d.attn_part) { const char *cwv = getenv("NANO_COMBINE_WAVE"); a.attn_table = (cwv && *cwv == '0') ? 1u : 0u; }
     if (d.resid_add) { a.resid_add = d.resid_add; a.resid_add_bstride = d.resid_add_stride; }
     a.ordered = d.ordered ? 1u : 0u;
     r.quant = d.quant; r.cus = (int)a.cus; r.mfma_min_nb = (d.use_gemm && d.quant == NANO_QUANT_Q80) ? 1u : 9u;
@@ -479,7 +481,7 @@ extern "C" int nano_hip_f32_gemm_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
 
 // The Q80 launch route_projection() issues for a descriptor: route_kind(), then for the routes that end in the Q80 GEMV kernels
 // gemv_q80_plan() of the first slice.
-// out = {route, kernel, role, gs, B, nv, upw, rw, nw, grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes}; the batched routes
+// out = {route, kernel, role, gs, B, nv, upw, rw, nw, grid, lds_bytes, variant, pre, launches, seqs_per_launch, takes, cw}; the batched routes
 // (G6 / G7 / G2 / GC) report the route, one launch of nb sequences and zeros for the kernel fields.  takes = 0: the router refuses the
 // shape (hipErrorInvalidValue before any launch) and every other entry is 0.
 extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus, uint32_t out[NANO_Q80_GEMV_PLAN_WORDS]) {
@@ -492,7 +494,9 @@ extern "C" int nano_hip_q80_gemv_plan(const NanoFusedGemvDesc *dp, uint32_t cus,
         return 0;
     }
     if (k == ROUTE_GEMV_PREQ) { a.xq_in = L.r.gq; a.xs_in = L.r.gxs; a.norm_w = nullptr; }      // (as route_projection() hands it on)
-    return report_first_slice<NANO_Q80_GEMV_PLAN_WORDS>(L, out, gemv_q80_plan, [k](const Q80GemvPlan &p) {
+    // (word 16, behind takes: the plan's cw -- the first 16 words are what they were)
+    return report_first_slice<NANO_Q80_GEMV_PLAN_WORDS>(L, out, gemv_q80_plan, [k, out](const Q80GemvPlan &p) {
+        out[16] = p.cw;
         return Words<13>{{ k, p.kernel, p.role, p.gs, p.B, p.nv, p.upw, p.rw, p.nw, p.grid, p.lds_bytes, p.variant, p.pre }}; });
 }
 
@@ -878,7 +882,7 @@ static void plan_words(const QkvAttnFusedPlan &p, uint32_t *out) {
     memcpy(out, v, sizeof(v));
 }
 static void plan_words(const WoW13FusedPlan &p, uint32_t *out) {
-    const uint32_t v[NANO_WO_W13_FUSED_PLAN_WORDS] = { p.sig, p.threads, p.role, p.wf, p.wfc, p.nv_a, p.upw_a, p.nv_b, p.upw_b, p.wa, p.wb, p.lds_bytes, p.rw_a, p.rw_b, 0u, 1u };
+    const uint32_t v[NANO_WO_W13_FUSED_PLAN_WORDS] = { p.sig, p.threads, p.role, p.wf, p.wfc, p.nv_a, p.upw_a, p.nv_b, p.upw_b, p.wa, p.wb, p.lds_bytes, p.rw_a, p.rw_b, 0u, 1u, p.cw };
     memcpy(out, v, sizeof(v));
 }
 
