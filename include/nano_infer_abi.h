@@ -290,6 +290,15 @@ int nano_prefill_batch(Nano_Context *ctx, const uint32_t *const *prompts, const 
  * Not offered: bidirectional attention (is_causal = 0), CLS pooling, texts longer than max_seq_len.  Returns 0 or a NANO_HIP_E* code. */
 int nano_embed_batch(Nano_Context *ctx, const uint32_t *const *texts, const uint32_t *n_tokens, uint32_t batch, uint32_t pooling,
                      uint32_t normalize, uint32_t dim, float *out);
+/* Greedy decode of `batch` sequences with lookup drafts, one ragged verify pass per round (nano_hip_decode_lookup_rows, nano_mi355x.h:
+ * what the ids are and how a round is built are stated there).  Sequence i lives in slot i, as in nano_forward_batch: the slot holds
+ * positions 0 .. n_history[i]-2 of histories[i], the history's last id is fed first, at most max_new[i] ids go to out_ids[i] and their
+ * count to n_out[i].  max_draft 0 .. 15 (clipped by the device entry's rule), n-grams of 1 .. 3 ids as nano_set_lookup_draft uses,
+ * stop_token UINT32_MAX = none.  Runs on the context's own device: with replicas attached or a LoRA module selected the call returns
+ * NANO_HIP_EINVAL, as it does for whatever the device entry refuses.  Not offered: a draft model, sampling, logit edits.  Returns 0
+ * or a NANO_HIP_E* code. */
+int nano_decode_batch_lookup(Nano_Context *ctx, const uint32_t *const *histories, const uint32_t *n_history, const uint32_t *max_new,
+                             uint32_t batch, int max_draft, uint32_t stop_token, uint32_t *const *out_ids, uint32_t *n_out);
 /* Feed ids[0..n_ids-1) into sequence 0 from position 0 and score ids[1..n_ids): logprobs / argmax hold n_ids-1 entries (either may be NULL),
  * *nll_sum = -(sum of the logprobs), added in double in index order.  Applies the context's LoRA selection as nano_forward_batch does.
  * logprobs[i] = log p(ids[i + 1] | ids[0..i]) and argmax[i] = the model's own choice there, both taken on the device from a batched

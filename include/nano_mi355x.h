@@ -365,6 +365,60 @@ int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n, const uin
                             const NanoHipLookupParams *params, uint32_t left, uint32_t seq_limit, uint32_t *record_out,
                             uint32_t *next_tokens_out, uint32_t *next_pos_out);
 
+/* ---- lookup drafts for several sequences: one ragged verify pass per round (opt-in) ----------
+ * nano_hip_decode_lookup's contract for n_seqs sequences at once, sequence i in KV slot seqs[i].slot: the slot holds positions
+ * 0 .. n_history-2 of histories[i], histories[i][n_history-1] is fed first, at most max_new ids go to out_ids[i] (host, max_new words)
+ * and their count to n_out[i]; afterwards the slot holds valid rows for positions 0 .. n_history + n_out[i] - 2.  p->stop_token applies
+ * to every sequence, p->max_steps bounds the call's rounds (0 = no limit).  stats (optional) holds n_seqs records, rounds (optional)
+ * receives the number of rounds run.
+ * A round is ONE ragged pass (as nano_hip_step_rows runs them) over the live sequences' rows: each sequence takes one row or a verify
+ * chunk of D_eff + 1 rows by the one-sequence loop's own gate (a draft exists, at least 2 ids left, the chunk inside one 64-position
+ * bucket and below max_seq_len / the RoPE table).  Behind the pass the definitions of the one-sequence loop run for every sequence on the
+ * device (accept, emit, lookup, draft, gate) and the next pass's tokens, positions and row -> slot map are staged there; the host
+ * waits once per round for n_seqs 32-byte records.  A finished sequence contributes no rows to later rounds.
+ * D_eff is fixed for the call: min(p->max_draft, nano_hip_prefill_chunk_tokens(m) / n_seqs - 1), so a round is always exactly one
+ * pass; in strict and exact mode it is 0 and a round is one reference-order step per live sequence in its slot (that mode's ids).
+ * What the ids are: sequence i's ids and its NanoHipLookupStats are those of nano_hip_decode_lookup for that sequence alone with
+ * max_draft = D_eff (with the caveat stated there for wide matrices): a sequence's rounds do not depend on what shares the pass.
+ * NANO_HIP_EINVAL before anything is queued (a refused call feeds nothing): null m / seqs / histories / p / out_ids / n_out or a
+ * null entry of histories / out_ids; per sequence whatever nano_hip_decode_lookup refuses; LoRA switched on or a cache the row map
+ * cannot address (as nano_hip_step_rows); two sequences in one slot; a slot >= max_batch; reserved != 0; the sum of max_new beyond the
+ * trace capacity (max_seq_len * max_batch); outside strict and exact mode n_seqs beyond nano_hip_prefill_chunk_tokens(m).
+ * n_seqs == 0 or every max_new == 0 returns 0 and touches nothing.  A record the host cannot accept (the check of
+ * nano_hip_decode_lookup, per sequence) ends the call with NANO_HIP_ERUNTIME.  No in-launch hand-off runs in an eager ragged pass, so
+ * none can give up and the call is never re-issued.
+ * Paged cache: the pages of positions n_history-1 .. n_history-2+max_new of every sequence are taken up front, all or nothing; shared
+ * pages (nano_hip_kv_fork) are copied on write.  FP32, FP16, FP8 and the paged cache are served, as for ragged steps.
+ * The histories live on the device between calls, one per KV slot (apart from nano_hip_decode_lookup's): a history that extends what
+ * the slot's previous call left uploads only the new ids.  They are allocated on the first call; NANO_HIP_ENOMEM leaves the model usable.
+ * NOT offered: a draft model for several sequences, sampling, logit edits, LoRA, replicas. */
+typedef struct NanoHipLookupSeq { uint32_t slot, n_history, max_new, reserved; } NanoHipLookupSeq;   /* 16 bytes */
+int nano_hip_decode_lookup_rows(NanoHipModel *m, const NanoHipLookupSeq *seqs, uint32_t n_seqs,
+                                const uint32_t *const *histories, const NanoHipLookupParams *p,
+                                uint32_t *const *out_ids, uint32_t *n_out, NanoHipLookupStats *stats, uint32_t *rounds);
+/* The pass of a round, device-free (the host's copy of what the pack launch of lookup_rows.hip does).  n[i] = ids in sequence i's
+ * history, nb_next[i] = its rows in the pass (0: it has none -- a dead sequence).  The live sequences are ordered stably by the range
+ * hint of position n[i] - 1 (nano_hip_rows_plan's row_hint); each sequence's rows are contiguous and ascending.  order[0 .. live) =
+ * the live sequences in pass order, row_start[i] = sequence i's first row (UINT32_MAX: dead), group_hint / group_rows [*n_groups] =
+ * the runs of equal hints and their row counts.  Every output may be NULL; the arrays hold n_seqs entries.
+ * NANO_HIP_EINVAL: null n / nb_next with n_seqs > 0, max_seq_len == 0, nb_next[i] > 16, a live sequence with n[i] == 0 or whose rows
+ * end beyond max_seq_len. */
+int nano_hip_lookup_rows_plan(const uint32_t *n, const uint32_t *nb_next, uint32_t n_seqs, uint32_t max_seq_len,
+                              uint32_t *order, uint32_t *row_start, uint32_t *group_hint, uint32_t *group_rows, uint32_t *n_groups);
+/* The two between-rounds launches alone (lookup_rows.hip; host pointers; operator tests).  Sequence i: histories[i][0 .. n[i]) in, room
+ * for n[i] + 16 ids (the emitted ids are appended in place), left[i] ids still to emit, KV slot slots[i] (distinct, < 64).  fed / amax
+ * [n_rows] are the previous pass in pass order, row_start[i] / nb[i] sequence i's rows there (nb[i] = 0: none; 0 .. 16).  params and
+ * seq_limit as nano_hip_op_lookup_step, max_seq_len clips the range hints.  records_out [n_seqs][8] as nano_hip_op_lookup_step's;
+ * next_tokens_out / next_pos_out / next_slot_out [n_seqs * 16] = the next pass in pass order (entries beyond its rows are UINT32_MAX);
+ * row_start_out [n_seqs] (UINT32_MAX: no rows).
+ * NANO_HIP_EINVAL before a device is asked for: null pointers, n_seqs outside 1 .. 64, n[i] == 0 or > 65536, rows outside the pass,
+ * a slot >= 64 or named twice, parameters out of their ranges, max_seq_len == 0. */
+int nano_hip_op_lookup_rows_round(int device, uint32_t n_seqs, uint32_t *const *histories, const uint32_t *n, const uint32_t *left,
+                                  const uint32_t *slots, const uint32_t *fed, const uint32_t *amax, uint32_t n_rows,
+                                  const uint32_t *row_start, const uint32_t *nb, const NanoHipLookupParams *params,
+                                  uint32_t seq_limit, uint32_t max_seq_len, uint32_t *records_out, uint32_t *next_tokens_out,
+                                  uint32_t *next_pos_out, uint32_t *next_slot_out, uint32_t *row_start_out);
+
 /* ---- greedy decode with a draft model: several ids per read of the target's weights (opt-in) ----
  * Two resident models with one vocabulary on one device.  A round: the draft model runs D' one-row greedy loop steps from the last id,
  * the target verifies [last id, d1 .. dD'] as one chunk of D' + 1 rows and accepts rows exactly as nano_hip_decode_lookup does, so every

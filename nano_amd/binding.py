@@ -191,6 +191,13 @@ class NanoHipLookupStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("steps_plain", "steps_verify", "drafted", "accepted", "emitted")]
 
 
+class NanoHipLookupSeq(C.Structure):
+    """include/nano_mi355x.h NanoHipLookupSeq: one sequence of nano_hip_decode_lookup_rows (reserved 0)."""
+    _fields_ = [(n, C.c_uint32) for n in ("slot", "n_history", "max_new", "reserved")]
+
+
+assert C.sizeof(NanoHipLookupSeq) == 16
+
 # the words of the record nano_hip_op_lookup_step returns (nano_amd/csrc/kernels.h LOOKUP_REC_*)
 LOOKUP_RECORD_FIELDS = ("emitted", "accepted", "nb_next", "n", "match_len", "match_end", "done", "left")
 LOOKUP_NO_STOP = 0xFFFFFFFF
@@ -316,6 +323,12 @@ def lib() -> C.CDLL:
                        ("nano_hip_rows_pool_plan", [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
                        ("nano_hip_op_pool_rows", [C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(NanoHipPoolParams), C.c_uint32, vp]),
                        ("nano_embed_batch", [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+                       # lookup drafts for several sequences
+                       ("nano_hip_decode_lookup_rows", [vp, vp, C.c_uint32, vp, C.POINTER(NanoHipLookupParams), vp, vp, vp, C.POINTER(C.c_uint32)]),
+                       ("nano_hip_lookup_rows_plan", [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32)]),
+                       ("nano_hip_op_lookup_rows_round", [C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(NanoHipLookupParams),
+                                                          C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+                       ("nano_decode_batch_lookup", [vp, vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp]),
                        # logit edits
                        ("nano_hip_forward_sample_batch_edit", [vp, u32p, u32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
                        ("nano_hip_op_sample_batch_edit", [vp, f32p, C.c_uint32, C.POINTER(NanoHipSampleParamsEdit), C.POINTER(NanoHipSample)]),
@@ -674,6 +687,25 @@ class DeviceModel:
         n, st = C.c_uint32(0), NanoHipLookupStats()
         check(lib().nano_hip_decode_lookup(self.h, h.ctypes.data if h.size else None, h.size, max_new, C.byref(p), out.ctypes.data, C.byref(n), C.byref(st)))
         return out[:n.value].copy(), {k: int(getattr(st, k)) for k, _ in NanoHipLookupStats._fields_}
+
+    def decode_lookup_rows(self, histories, slots, max_new, max_draft: int = 7, ngram_max: int = 3, ngram_min: int = 1,
+                           stop_token: Optional[int] = None, max_steps: int = 0):
+        """Greedy decode of several sequences with lookup drafts, one ragged verify pass per round (nano_hip_decode_lookup_rows): slot
+        slots[i] holds positions 0 .. len(histories[i])-2, histories[i][-1] is fed first, at most max_new[i] ids are emitted.  Returns
+        (list of uint32 id arrays, list of stats dicts as decode_lookup's, rounds)."""
+        hs = [np.ascontiguousarray(h, np.uint32).reshape(-1) for h in histories]
+        B = len(hs)
+        if len(slots) != B or len(max_new) != B:
+            raise ValueError(f"{B} histories but {len(slots)} slots / {len(max_new)} max_new")
+        seqs = (NanoHipLookupSeq * max(B, 1))(*[NanoHipLookupSeq(int(s), h.size, int(mn), 0) for h, s, mn in zip(hs, slots, max_new)])
+        outs = [np.zeros(max(int(mn), 1), np.uint32) for mn in max_new]
+        hp = (C.c_void_p * max(B, 1))(*[h.ctypes.data if h.size else None for h in hs])
+        op = (C.c_void_p * max(B, 1))(*[o.ctypes.data for o in outs])
+        p = NanoHipLookupParams(max_draft, ngram_max, ngram_min, LOOKUP_NO_STOP if stop_token is None else stop_token, max_steps)
+        n, st, rounds = np.zeros(max(B, 1), np.uint32), (NanoHipLookupStats * max(B, 1))(), C.c_uint32(0)
+        check(lib().nano_hip_decode_lookup_rows(self.h, seqs, B, hp, C.byref(p), op, n.ctypes.data, st, C.byref(rounds)))
+        return ([outs[i][:int(n[i])].copy() for i in range(B)],
+                [{k: int(getattr(st[i], k)) for k, _ in NanoHipLookupStats._fields_} for i in range(B)], int(rounds.value))
 
     def decode_draft(self, draft: "DeviceModel", history: Sequence[int], max_new: int, max_draft: int = 4, stop_token: Optional[int] = None,
                      max_rounds: int = 0, draft_held: int = 0):
@@ -1508,6 +1540,60 @@ def op_lookup_step(history, fed=(), amax=(), *, left, max_draft=7, ngram_max=3, 
     return r, buf[:r["n"]].copy() if h.size <= r["n"] <= buf.size else buf, nt, npos
 
 
+def lookup_rows_plan(n, nb_next, max_seq_len):
+    """nano_hip_lookup_rows_plan (device-free): the pass of a round.  Returns (order of the live sequences, row_start per sequence --
+    0xffffffff: dead --, list of (hint, rows) groups)."""
+    a = np.ascontiguousarray(n, np.uint32).reshape(-1)
+    b = np.ascontiguousarray(nb_next, np.uint32).reshape(-1)
+    if a.size != b.size:
+        raise ValueError(f"{a.size} lengths but {b.size} row counts")
+    B = a.size
+    order, start, gh, gr = (np.zeros(max(B, 1), np.uint32) for _ in range(4))
+    ng = C.c_uint32(0)
+    check(lib().nano_hip_lookup_rows_plan(a.ctypes.data if B else None, b.ctypes.data if B else None, B, max_seq_len, order.ctypes.data, start.ctypes.data,
+                                          gh.ctypes.data, gr.ctypes.data, C.byref(ng)))
+    live = int(np.count_nonzero(b))
+    return order[:live].tolist(), start[:B].tolist(), [(int(gh[g]), int(gr[g])) for g in range(ng.value)]
+
+
+def op_lookup_rows_round(histories, left, slots, fed=(), amax=(), row_start=None, nb=None, *, max_draft=7, ngram_max=3, ngram_min=1, stop_token=None,
+                         seq_limit=1 << 30, max_seq_len=1 << 30, device=0):
+    """The two between-rounds launches of lookup_rows.hip alone (nano_hip_op_lookup_rows_round): behind a pass that fed `fed` and left the
+    row arg-maxes `amax` (pass order), sequence i's rows being row_start[i] .. row_start[i] + nb[i] (None: no pass has run yet).
+    Returns (list of record dicts, list of histories with the emitted ids appended, next tokens, next positions, next slots -- each
+    len(histories) * 16 words, 0xffffffff beyond the pass's rows --, row_start per sequence)."""
+    hs = [np.ascontiguousarray(h, np.uint32).reshape(-1) for h in histories]
+    B = len(hs)
+    f = np.ascontiguousarray(fed, np.uint32).reshape(-1)
+    g = np.ascontiguousarray(amax, np.uint32).reshape(-1)
+    if f.size != g.size:
+        raise ValueError(f"{f.size} fed ids but {g.size} arg-maxes")
+    rs = np.ascontiguousarray([0xFFFFFFFF] * B if row_start is None else row_start, np.uint32).reshape(-1)
+    cnt = np.ascontiguousarray([0] * B if nb is None else nb, np.uint32).reshape(-1)
+    nn = np.ascontiguousarray([h.size for h in hs], np.uint32)
+    lf = np.ascontiguousarray(left, np.uint32).reshape(-1)
+    sl = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+    if not (rs.size == cnt.size == lf.size == sl.size == B):
+        raise ValueError("one entry per sequence is needed in left, slots, row_start and nb")
+    bufs = []
+    for h in hs:
+        buf = np.full(h.size + 16, 0xFFFFFFFF, np.uint32)
+        buf[:h.size] = h
+        bufs.append(buf)
+    hp = (C.c_void_p * max(B, 1))(*[b.ctypes.data for b in bufs])
+    p = NanoHipLookupParams(max_draft, ngram_max, ngram_min, LOOKUP_NO_STOP if stop_token is None else stop_token, 0)
+    rec = np.zeros((max(B, 1), 8), np.uint32)
+    nt, npos, nsl = (np.zeros(max(B, 1) * 16, np.uint32) for _ in range(3))
+    rso = np.zeros(max(B, 1), np.uint32)
+    check(lib().nano_hip_op_lookup_rows_round(device, B, hp, nn.ctypes.data, lf.ctypes.data, sl.ctypes.data, f.ctypes.data if f.size else None,
+                                              g.ctypes.data if g.size else None, f.size, rs.ctypes.data, cnt.ctypes.data, C.byref(p),
+                                              min(seq_limit, 0xFFFFFFFF), min(max_seq_len, 0xFFFFFFFF), rec.ctypes.data, nt.ctypes.data, npos.ctypes.data,
+                                              nsl.ctypes.data, rso.ctypes.data))
+    recs = [dict(zip(LOOKUP_RECORD_FIELDS, (int(v) for v in rec[i]))) for i in range(B)]
+    out_h = [bufs[i][:recs[i]["n"]].copy() if hs[i].size <= recs[i]["n"] <= bufs[i].size else bufs[i] for i in range(B)]
+    return recs, out_h, nt, npos, nsl, rso[:B].tolist()
+
+
 def op_draft_round(history, fed=(), amax=(), *, left, dn=0, max_draft=4, stop_token=None, seq_limit=1 << 30, device=0):
     """draft_round_kernel alone (nano_hip_op_draft_round): its STAGE role on fed[1:], then its ACCEPT role behind a round that fed `fed` and
     left the row arg-maxes `amax` (both empty: no round has run yet); dn = positions the draft held before it.  Returns (record dict of
@@ -1688,6 +1774,19 @@ class Engine:
         out = np.zeros((max(len(ts), 1), dim or n_embd), np.float32)
         check(self.L.nano_embed_batch(self.ctx, ptrs, n.ctypes.data, len(ts), _pooling(pooling), int(normalize), dim, out.ctypes.data))
         return out[:len(ts)]
+
+    def decode_batch_lookup(self, histories, max_new, max_draft: int = 7, stop_token: Optional[int] = None):
+        """nano_decode_batch_lookup: sequence i (slot i) decodes greedily with lookup drafts from histories[i]; returns the list of id arrays."""
+        hs = [np.ascontiguousarray(h, np.uint32).reshape(-1) for h in histories]
+        B = len(hs)
+        outs = [np.zeros(max(int(mn), 1), np.uint32) for mn in max_new]
+        hp = (C.c_void_p * max(B, 1))(*[h.ctypes.data if h.size else None for h in hs])
+        op = (C.c_void_p * max(B, 1))(*[o.ctypes.data for o in outs])
+        nh, mn = np.array([h.size for h in hs], np.uint32), np.ascontiguousarray(max_new, np.uint32)
+        n = np.zeros(max(B, 1), np.uint32)
+        check(self.L.nano_decode_batch_lookup(self.ctx, hp, nh.ctypes.data, mn.ctypes.data, B, max_draft, LOOKUP_NO_STOP if stop_token is None else stop_token,
+                                              op, n.ctypes.data))
+        return [outs[i][:int(n[i])].copy() for i in range(B)]
 
     def set_logit_edit(self, allow=None, bias=None) -> None:
         """nano_set_logit_edit: allow = mask words (or None), bias = (tokens, values) (or None); both None clears the context's edit."""

@@ -75,6 +75,7 @@ static void destroy(NanoHipModel *m) {
     for (void *p : host) if (p) (void)hipHostFree(p);
     sampler_free(m->smp);
     lookup_free(m);
+    lookup_rows_free(m);
     draft_free(m);
     rows_free(m);
     kv_image_free(m);

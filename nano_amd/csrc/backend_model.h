@@ -6,6 +6,7 @@
 //   backend_kv.hip       where the KV cache's rows are, the paged cache, fork, release, KV images (save / restore)
 //   backend_sampler.hip  the device-side sampler's scratch and its four entry points
 //   backend_lookup.hip   greedy decode with lookup drafts: the loop, the verify entry
+//   backend_lookup_rows.hip   lookup drafts for several sequences: the planner, the loop of ragged verify passes
 //   backend_rows.hip     what calls get back per fed row (RowWant: the scratch, the sink, the decode-step entry) and ragged steps
 //   backend_probe.hip    measurement, state read-back, the hand-off switches and fault injection
 #pragma once
@@ -130,6 +131,15 @@ struct NanoHipModel {
         uint32_t *h_rec = nullptr;                        // pinned: the record of the last step
         bool graph = true;                                // verify chunks of the loop replay a graph per (K, range bucket); NANO_LOOKUP_GRAPH=0: eager
     } lk;
+    // lookup drafts for several sequences (backend_lookup_rows.hip), allocated on the first call that needs it
+    struct LookupRows {
+        uint32_t *hist = nullptr; uint32_t cap = 0;       // [max_batch][cap] one history per KV slot (lookup_rows.hip appends to them); cap as Lookup::cap
+        std::vector<std::vector<uint32_t>> shadow;        // [max_batch] what each slot's history holds, host side
+        uint32_t *ctl = nullptr;                          // one block: state [max_batch][4] | seq_slot | trace_base | row_start | nb [max_batch] each | records [max_batch][8] | stage [max_batch][16]
+        uint32_t *slot = nullptr;                         // [rows of a pass] the next pass's row -> slot map
+        uint32_t *tok = nullptr, *pos = nullptr, *amax = nullptr;   // [rows of a pass] strict / exact mode: the round's rows and their arg-maxes (m->tokens / m->pos / m->amax hold the row being fed)
+        uint32_t *h_rec = nullptr;                        // pinned: [max_batch][8] the records of the last round
+    } lkr;
     // greedy decode with a draft model (backend_draft.hip), on the TARGET, allocated on the first call; the history, the state and the
     // record are lk's
     struct Draft {
@@ -287,6 +297,9 @@ int prefill_run(NanoHipModel *m, uint32_t slot, const uint32_t *tokens, uint32_t
 hipError_t enqueue_chunk(NanoHipModel *m, uint32_t slot, uint32_t nb, const RowWant &want, uint32_t last_pos, bool replay);
 int lookup_scratch(NanoHipModel *m);                   // backend_lookup.hip
 void lookup_free(NanoHipModel *m);
+void lookup_rows_free(NanoHipModel *m);                // backend_lookup_rows.hip
+// one ragged pass of nb rows (m->tokens / m->pos hold them, row_slot their slots on the device, groups their buckets), eager (backend_rows.hip)
+hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, const RowWant &want, const uint32_t *row_slot, const std::vector<RowGroup> &groups);
 void draft_free(NanoHipModel *m);                      // backend_draft.hip
 // THE re-issue policy of every entry point that hands results over (round-6 advice: correctness after a give-up depends on every one of
 // them re-issuing at the same positions).  attempt(again) queues the call's work and synchronises the stream; an error it returns is

@@ -304,7 +304,7 @@ extern "C" int nano_hip_rows_addressable(uint32_t n_layer, uint32_t max_seq_len,
 
 // one ragged pass of nb rows (m->tokens / m->pos hold them, row_slot their slots, groups their buckets): eager; every row splits as
 // its own decode step and a kernel of its own combines, as in a prefill chunk
-static hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, const RowWant &want, const uint32_t *row_slot, const std::vector<RowGroup> &groups) {
+hipError_t enqueue_rows_pass(NanoHipModel *m, uint32_t nb, const RowWant &want, const uint32_t *row_slot, const std::vector<RowGroup> &groups) {
     const StepSpec s = StepSpec::ragged(nb, want.mode_pass(), row_slot, groups.data(), (uint32_t)groups.size(), want.use_targets());
     m->nsplit = xba_nsplit(m, s);                                      // 1 (as a prefill chunk: xba is left final)
     return enqueue_step(m, s);

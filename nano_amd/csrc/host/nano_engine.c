@@ -861,6 +861,24 @@ int nano_embed_batch(Nano_Context *ctx, const uint32_t *const *texts, const uint
     return rc;
 }
 
+/* Greedy decode of `batch` sequences with lookup drafts (nano_hip_decode_lookup_rows): sequence i in slot i of the context's own device,
+ * as in nano_forward_batch; the n-gram range is nano_set_lookup_draft's (1 .. 3).  NANO_HIP_EINVAL with replicas attached or a LoRA
+ * module selected (the device entry refuses a switched-on LoRA table the same way). */
+int nano_decode_batch_lookup(Nano_Context *ctx, const uint32_t *const *histories, const uint32_t *n_history, const uint32_t *max_new,
+                             uint32_t batch, int max_draft, uint32_t stop_token, uint32_t *const *out_ids, uint32_t *n_out) {
+    ModelEntry *me = ctx ? reg_entry(ctx->llm) : NULL;
+    la_clear(me);
+    if (!me || !me->dev || !histories || !n_history || !max_new || !out_ids || !n_out || batch > NANO_MAX_BATCH || me->n_replica > 1 || ctx->lora ||
+        max_draft < 0 || max_draft > 15) return NANO_HIP_EINVAL;      /* (replica[0] is the own device) */
+    if (batch == 0) return NANO_HIP_OK;
+    NanoHipLookupSeq seqs[NANO_MAX_BATCH];
+    for (uint32_t i = 0; i < batch; i++) seqs[i] = (NanoHipLookupSeq){ i, n_history[i], max_new[i], 0 };
+    const NanoHipLookupParams lp = { (uint32_t)max_draft, 3, 1, stop_token, 0 };
+    lora_select(me->dev, NULL);
+    me->pf_session = NULL;                                    /* the sequences' rows are these histories' now */
+    return nano_hip_decode_lookup_rows(me->dev, seqs, batch, histories, &lp, out_ids, n_out, NULL, NULL);
+}
+
 /* =====================================================================================================
  * sampling (reference infer/infer.c:1026-1127; RNG infer/utils.c:959-970)
  * =================================================================================================== */

@@ -612,6 +612,34 @@ struct LookupArgs {
 };
 hipError_t launch_lookup_step(const LookupArgs &a, hipStream_t st);
 
+// ---- lookup drafts for several sequences (lookup_rows.hip): what happens between two ragged passes of nano_hip_decode_lookup_rows ----
+// Two launches.  lookup_rows_seq_kernel, one workgroup of 256 threads per sequence: lookup.hip's accept / emit / lookup / draft / gate on
+// the sequence's own history, its record and its next rows' tokens into stage[i][LOOKUP_MAX_ROWS].  lookup_rows_pack_kernel, one
+// workgroup: the live sequences (nb_next > 0) ordered stably by the range hint of position n - 1, the prefix sum of their row counts,
+// and the next pass's tokens, positions and row -> slot map in pass order, plus every sequence's first row and row count for the next
+// accept (nano_hip_lookup_rows_plan is the host's copy of the same rule).
+enum { LOOKUP_ST_N = 0, LOOKUP_ST_LEFT, LOOKUP_ST_CURSOR, LOOKUP_ST_DONE, LOOKUP_ST_WORDS };
+constexpr uint32_t LOOKUP_ROW_NONE = 0xffffffffu;  // row_start of a sequence without rows in the pass
+struct LookupRowsArgs {
+    uint32_t n_seqs;
+    uint32_t *hist; uint32_t cap;                 // sequence i's ids: hist + seq_slot[i] * cap (16-byte aligned rows; cap a multiple of 4)
+    const uint32_t *seq_slot;                     // [n_seqs] the KV slot of sequence i
+    uint32_t *state;                              // [n_seqs][LOOKUP_ST_WORDS] n | ids still to emit | ids emitted so far | finished
+    const uint32_t *fed, *amax;                   // the pass these launches follow, in pass order: its tokens and row arg-maxes
+    uint32_t *row_start, *nb;                     // [n_seqs] sequence i's first row and row count in that pass (nb 0: none); the pack launch writes the next pass's
+    uint32_t max_draft, ngram_max, ngram_min, stop_token;
+    uint32_t seq_limit, max_seq_len;              // min(max_seq_len, RoPE rows) | max_seq_len: a range hint is clipped to it
+    uint32_t *stage;                              // [n_seqs][LOOKUP_MAX_ROWS] the next rows' tokens of every sequence
+    uint32_t *record;                             // [n_seqs][LOOKUP_REC_WORDS]
+    uint32_t *trace; const uint32_t *trace_base; uint32_t trace_cap;   // the emitted ids: sequence i's from trace_base[i] on (trace nullptr: not kept)
+    uint32_t *next_tokens, *next_pos, *next_slot; // the next pass in pass order (at most n_seqs * (max_draft + 1) rows; never fed / amax's rows before they are read: the pack launch runs behind the sequences')
+};
+__host__ __device__ inline uint32_t lookup_rows_hint(uint32_t n, uint32_t max_seq_len) {      // nano_hip_rows_plan's row_hint of position n - 1
+    const uint32_t h = ((n - 1u + 64u) / 64u) * 64u;
+    return h > max_seq_len ? max_seq_len : h;
+}
+hipError_t launch_lookup_rows_round(const LookupRowsArgs &a, hipStream_t st);
+
 // ---- greedy decode with a draft model (draft.hip): what happens between the two models' steps of a round, one workgroup ----
 // A round feeds the target [hist[n-1], d1 .. dD'] at positions n-1 .. n-1+D' (tests/draft_ref.py restates the
 // definitions).  One kernel, three roles:

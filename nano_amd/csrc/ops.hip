@@ -318,6 +318,60 @@ extern "C" int nano_hip_op_lookup_step(int device, uint32_t *history, uint32_t n
     return 0;
 }
 
+// the two between-rounds launches of lookup drafts for several sequences alone (lookup_rows.hip).  The arguments are checked before a
+// device is asked for; every device index the kernels form from them stays inside the buffers made here.
+extern "C" int nano_hip_op_lookup_rows_round(int device, uint32_t n_seqs, uint32_t *const *histories, const uint32_t *n, const uint32_t *left,
+                                             const uint32_t *slots, const uint32_t *fed, const uint32_t *amax, uint32_t n_rows,
+                                             const uint32_t *row_start, const uint32_t *nb, const NanoHipLookupParams *p,
+                                             uint32_t seq_limit, uint32_t max_seq_len, uint32_t *records_out, uint32_t *next_tokens_out,
+                                             uint32_t *next_pos_out, uint32_t *next_slot_out, uint32_t *row_start_out) {
+    constexpr uint32_t MAXQ = 64;
+    if (!histories || !n || !left || !slots || !row_start || !nb || !p || !records_out || !next_tokens_out || !next_pos_out || !next_slot_out || !row_start_out ||
+        (n_rows && (!fed || !amax))) { nano_hip_set_error_("lookup_rows_round: null argument"); return NANO_HIP_EINVAL; }
+    if (n_seqs == 0 || n_seqs > MAXQ || !max_seq_len) { nano_hip_set_error_("lookup_rows_round: n_seqs outside 1 .. 64, or max_seq_len 0"); return NANO_HIP_EINVAL; }
+    if (p->max_draft > LOOKUP_MAX_ROWS - 1 || p->ngram_max < 1 || p->ngram_max > LOOKUP_MAX_NGRAM || p->ngram_min < 1 || p->ngram_min > p->ngram_max) {
+        nano_hip_set_error_("lookup_rows_round: max_draft beyond 15, ngram_max outside 1 .. 4, or ngram_min outside 1 .. ngram_max"); return NANO_HIP_EINVAL;
+    }
+    uint32_t n_max = 0, slot_max = 0;
+    uint64_t seen = 0;
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        if (!histories[i] || n[i] == 0 || n[i] > 65536u || nb[i] > LOOKUP_MAX_ROWS || (nb[i] && (uint64_t)row_start[i] + nb[i] > n_rows) || slots[i] >= MAXQ || (seen >> slots[i] & 1u)) {
+            nano_hip_set_error_("lookup_rows_round: a null history, n outside 1 .. 65536, rows outside the pass, or a slot >= 64 or named twice"); return NANO_HIP_EINVAL;
+        }
+        seen |= 1ull << slots[i];
+        n_max = std::max(n_max, n[i]); slot_max = std::max(slot_max, slots[i]);
+    }
+    int rc; if ((rc = begin(device))) return rc;
+    DevBufs B;
+    LookupRowsArgs a{};
+    a.n_seqs = n_seqs;
+    a.cap = (n_max + LOOKUP_MAX_ROWS + 4u) & ~3u;                           // (beyond n + 16: a full chunk's ids never end a sequence at the cap)
+    const size_t hist_words = (size_t)(slot_max + 1u) * a.cap, out_rows = (size_t)n_seqs * LOOKUP_MAX_ROWS;
+    a.hist = B.alloc<uint32_t>(hist_words);
+    std::vector<uint32_t> st((size_t)n_seqs * LOOKUP_ST_WORDS, 0u);
+    for (uint32_t i = 0; i < n_seqs; i++) { st[(size_t)i * LOOKUP_ST_WORDS + LOOKUP_ST_N] = n[i]; st[(size_t)i * LOOKUP_ST_WORDS + LOOKUP_ST_LEFT] = left[i]; }
+    a.state = B.upload(st.data(), st.size());
+    a.seq_slot = B.upload(slots, n_seqs);
+    const uint32_t none = 0;
+    a.fed = n_rows ? B.upload(fed, n_rows) : B.upload(&none, 1); a.amax = n_rows ? B.upload(amax, n_rows) : B.upload(&none, 1);
+    a.row_start = B.upload(row_start, n_seqs); a.nb = B.upload(nb, n_seqs);
+    a.max_draft = p->max_draft; a.ngram_max = p->ngram_max; a.ngram_min = p->ngram_min; a.stop_token = p->stop_token; a.seq_limit = seq_limit; a.max_seq_len = max_seq_len;
+    a.stage = B.alloc<uint32_t>(out_rows); a.record = B.alloc<uint32_t>((size_t)n_seqs * LOOKUP_REC_WORDS);
+    a.next_tokens = B.alloc<uint32_t>(out_rows); a.next_pos = B.alloc<uint32_t>(out_rows); a.next_slot = B.alloc<uint32_t>(out_rows);
+    OP_CHECK(a.hist && a.state && a.seq_slot && a.fed && a.amax && a.row_start && a.nb && a.stage && a.record && a.next_tokens && a.next_pos && a.next_slot, "device alloc failed");
+    OP_HIP(hipMemset(a.hist, 0xff, hist_words * 4));
+    for (uint32_t i = 0; i < n_seqs; i++) OP_HIP(hipMemcpy(a.hist + (size_t)slots[i] * a.cap, histories[i], (size_t)n[i] * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemset(a.next_tokens, 0xff, out_rows * 4)); OP_HIP(hipMemset(a.next_pos, 0xff, out_rows * 4)); OP_HIP(hipMemset(a.next_slot, 0xff, out_rows * 4));
+    OP_HIP(launch_lookup_rows_round(a, 0));
+    OP_HIP(hipMemcpy(records_out, a.record, (size_t)n_seqs * LOOKUP_REC_WORDS * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n_seqs; i++) OP_HIP(hipMemcpy(histories[i], a.hist + (size_t)slots[i] * a.cap, (size_t)(n[i] + LOOKUP_MAX_ROWS) * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_tokens_out, a.next_tokens, out_rows * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_pos_out, a.next_pos, out_rows * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(next_slot_out, a.next_slot, out_rows * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(row_start_out, a.row_start, n_seqs * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // the between-steps kernel of greedy decode with a draft model alone (draft.hip): STAGE on fed[1 .. nb), then ACCEPT.  The arguments
 // are checked before a device is asked for.
 extern "C" int nano_hip_op_draft_round(int device, uint32_t *history, uint32_t n, const uint32_t *fed, const uint32_t *amax, uint32_t nb,
